@@ -36,8 +36,14 @@ Prints ONE JSON line (rank 0):
                           restatement -- on the host cores, bounded sample of the same batch; its outputs are the
                           `check.vs_reference` comparison.  cpu_baseline_O2: the same sources at -O2
 
---min-seconds S (default 1): the timed region runs max(K, enough steps for S seconds) steps -- decided from the warm-up
-before the clock starts, `steps` reports what ran, `steps_requested` the K given; --min-seconds 0 times exactly K.
+--steps K times exactly K steps (K >= 1): `steps` in the line is K, `ms_per_step` the timed region's wall time over K.
+
+--dump-outputs DIR: after the timed region, rank 0 writes what the last timed step returned to its caller -- the result
+records of that step's batch, one float64 array per field (DIR/score.npy, DIR/opt_i.npy, ...), and the transcripts of a
+fixed sample of its pairs (DIR/transcripts.npy, float32 ASCII codes, one zero-padded row per sampled pair;
+DIR/transcript_pairs.npy, the sampled pair indices).  The inputs depend on the arguments alone, so two builds run with
+the same arguments can be compared array for array.  At most DUMP_MAX_BYTES in all (larger batches: a seeded sample of the
+records as well, DIR/record_pairs.npy).
 """
 import argparse
 import json
@@ -58,10 +64,53 @@ SCORES = dict(match=1., mismatch=-3., go=-5., ge=-2.)
 HBM_PEAK_GBS = 8000.0     # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
 N_SIMD, CLOCK_GHZ = 1024, 2.4   # MI355X_MICROARCH.md: 256 CUs x 4 SIMDs, 2.4 GHz peak engine clock
 CPU_SAMPLE_PER_CORE = 64
+DUMP_MAX_BYTES = 64 << 20
+DUMP_TX_PAIRS = 1024          # transcripts written by --dump-outputs (a seeded sample of the batch's pairs)
+DUMP_SEED = 20251015
 
 
 def batch_seed(rank, j):
     return 2 + 1000 * rank + 100 * j
+
+
+def _dump_sample(n, k, salt):
+    """Sorted indices of min(n, k) of n pairs, the same for every run with the same n."""
+    if n <= k:
+        return np.arange(n, dtype=np.int64)
+    rng = np.random.Generator(np.random.PCG64([DUMP_SEED, salt]))
+    return np.sort(rng.choice(n, size=k, replace=False)).astype(np.int64)
+
+
+def dump_outputs(out_dir, results, transcripts, origins, mutants):
+    """--dump-outputs: the result records and a sample of the transcripts of one batch as float .npy files (bench.py
+    docstring).  Returns {name: shape}."""
+    n = len(results)
+    tx_pairs = _dump_sample(n, DUMP_TX_PAIRS, 1)
+    # a row is as wide as the largest transcript slot of the sample (X + Y + 1 ops): it follows from the inputs alone
+    width = max([len(origins[k]) + len(mutants[k]) + 1 for k in tx_pairs] + [1])
+    tx_bytes = tx_pairs.size * (width * 4 + 8)
+    rec_bytes = len(results.dtype.names) * 8
+    rec_pairs = None
+    if n * rec_bytes + tx_bytes > DUMP_MAX_BYTES:
+        rec_pairs = _dump_sample(n, (DUMP_MAX_BYTES - tx_bytes) // (rec_bytes + 8), 2)
+    arrays = {}
+    recs = results if rec_pairs is None else results[rec_pairs]
+    for name in results.dtype.names:
+        arrays[name] = recs[name].astype(np.float64)
+    if rec_pairs is not None:
+        arrays['record_pairs'] = rec_pairs.astype(np.float64)
+    tx = np.zeros((tx_pairs.size, width), np.float32)
+    for row, k in enumerate(tx_pairs):
+        if transcripts[k]:
+            ops = np.frombuffer(transcripts[k].encode('ascii'), np.uint8)
+            tx[row, :ops.size] = ops
+    arrays['transcripts'] = tx
+    arrays['transcript_pairs'] = tx_pairs.astype(np.float64)
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_MAX_BYTES
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -172,14 +221,12 @@ def self_launch(args, argv):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
-    ap.add_argument('--steps', type=int, default=20)
+    ap.add_argument('--steps', type=int, default=20, help='timed steps (>= 1)')
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--pairs', type=int, default=PAIRS, help='pairs per GPU (default: the BASELINE config)')
     ap.add_argument('--inflight', type=int, default=2,
                     help='batches in flight per GPU, each on its own HIP stream (consecutive steps alternate); 2 hides the '
                          'latency-bound traceback of one batch behind the fill of the next')
-    ap.add_argument('--min-seconds', type=float, default=1.0,
-                    help='lower bound of the timed region: more than --steps steps are timed if needed (0: exactly --steps)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-extras', action='store_true', help='skip the serial / e2e / variant legs (profiling runs)')
     ap.add_argument('--force-dist', action='store_true', help='run the RCCL gather path even with one rank (self-test)')
@@ -187,7 +234,11 @@ def main():
                     help='what the transcript gather moves: the ops compacted on the device (pw_batch_pack_transcripts, about '
                          'half the bytes; they follow one use of the batch later, when their size is known) or the X + Y + 1 '
                          'byte slots as they are')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the result records and a sample of the transcripts of the last timed step as DIR/<name>.npy')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
 
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
         sys.exit(self_launch(args, sys.argv[1:]))
@@ -304,33 +355,20 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    for i in range(args.warmup):
+    for i in range(max(args.warmup, nfl)):      # (every batch in flight runs before the check below reads it)
         step(i)
     fence()
-    # how many steps the timed region needs to last --min-seconds: measured on a few untimed steps, agreed over the ranks
-    steps_run = args.steps
-    if args.min_seconds > 0 and args.steps > 0:
-        np_ = max(2 * nfl, 4)
-        tp = time.perf_counter()
-        for i in range(np_):
-            step(i)
-        fence()
-        est = (time.perf_counter() - tp) / np_
-        need = torch.tensor([int(np.ceil(args.min_seconds / max(est, 1e-6)))], dtype=torch.int64, device=dev)
-        if use_dist:
-            dist.all_reduce(need, op=dist.ReduceOp.MAX)
-        steps_run = max(args.steps, min(int(need.item()), 100000))
     drain()
     fence()
     done_cells = 0
     t0 = time.perf_counter()
-    for i in range(steps_run):
+    for i in range(args.steps):
         done_cells += step(i)
     drain()                 # the last steps' transcripts arrive inside the timed region
     fence()
     elapsed = time.perf_counter() - t0
     # fill-kernel duration of the LAST timed step of each batch: with two batches in flight the fills co-run
-    overlapped_ms = [b.fill_ms() for b in batches[:min(nfl, steps_run)]]
+    overlapped_ms = [b.fill_ms() for b in batches[:min(nfl, args.steps)]]
 
     t = torch.tensor([elapsed, float(done_cells)], dtype=torch.float64, device=dev)
     if use_dist:
@@ -352,6 +390,10 @@ def main():
         bad = verify.check_batch(seqs[j][0], seqs[j][1], res, txs, SCORES['match'], SCORES['mismatch'], SCORES['go'],
                                  SCORES['ge'], banded=True, dmins=[-RADIUS] * n_local)
         n_bad += len(bad) + (0 if traced else 1)
+    # the last timed step (step i runs batch i % nfl): what its caller received, for comparing two builds
+    last_j = (args.steps - 1) % nfl
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, results[last_j], transcripts[last_j], seqs[last_j][0], seqs[last_j][1])
     check['rescored_pairs'] = n_local * nfl
     check['rescore_failures'] = n_bad
     n_ref_bad = 0
@@ -370,7 +412,6 @@ def main():
         if rank == 0:
             # what arrived at the root: rank 0's own records bit for bit, and the last rank's records + transcripts,
             # regenerated here from its seed and re-scored
-            last_j = (steps_run - 1) % nfl if steps_run else 0
             got0 = gathered[last_j][0].cpu().numpy().view(RESULT_DTYPE)
             gather_ok = bool((got0 == results[last_j]).all())
             r_last = world - 1
@@ -516,13 +557,13 @@ def main():
 
     if rank == 0:
         value = total_done / elapsed / 1e9          # cells of every step of every rank / max-over-ranks time
-        ms_step = elapsed / steps_run * 1e3
+        ms_step = elapsed / args.steps * 1e3
         achieved = alg_bytes / (fill * 1e-3) / 1e9
         pmc, pmc_src = pmc_counters(batch.kernel_name, n_local)
         valu = pmc.get('SQ_INSTS_VALU') if pmc else None
         line = {
             'metric': 'GCUPS (DP cell updates/s) banded local align',
-            'value': round(value, 3), 'unit': 'GCUPS', 'n_gpus': world, 'steps': steps_run, 'steps_requested': args.steps,
+            'value': round(value, 3), 'unit': 'GCUPS', 'n_gpus': world, 'steps': args.steps, 'steps_requested': args.steps,
             'timed_region_s': round(elapsed, 4),
             'warmup': args.warmup, 'ms_per_step': round(ms_step, 4),
             'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,

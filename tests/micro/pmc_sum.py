@@ -53,7 +53,7 @@ if 'json' in opts:
     if 'WRITE_SIZE' in c and 'FETCH_SIZE' in c:
         rec['hbm_bytes_per_launch'] = int((c['WRITE_SIZE'] + 2 * c['FETCH_SIZE']) * 1024)
     rec['note'] = ('rocprofv3 --kernel-trace --pmc <set>, one run per counter set, on `bench.py --inflight 1 --steps 2 --warmup 1 '
-                   '--no-cpu-baseline --no-extras --min-seconds 0` (tests/micro/profile_bench.sh); per launch of the fill kernel; '
+                   '--no-cpu-baseline --no-extras` (tests/micro/profile_bench.sh); per launch of the fill kernel; '
                    'WRITE_SIZE / FETCH_SIZE in KiB, FETCH_SIZE doubled in hbm_bytes_per_launch per MI355X_MICROARCH.md')
     with open(opts['json'], 'w') as f:
         json.dump(rec, f, indent=1)
