@@ -32,7 +32,7 @@ struct PlanModel {
   StepCost wg_p16[3];      // packed 16-bit body (k_fill16_mw)
   double margin;           // one-after-another wins when its estimate < margin x the workgroups' estimate
   // The packed kernels' lane layouts: cost of one slot-step relative to the lane-packed form at 8 diagonals per lane, by
-  // diagonals per lane 4, 8, .. 32 (pw_launch.h, kPackedBK), and what one pair per wavefront saves (its descriptor sits in
+  // diagonals per lane 4, 8, .. 32 (pw_plan.h, kPackedBK), and what one pair per wavefront saves (its descriptor sits in
   // scalar registers).  Fitted to tests/micro/overlap_all_bench.py (bands of 9 .. 111 diagonals under the overlap rule, 20 000 and
   // 50 000 pairs per batch, PWLIB_PACKED_BK = 4s .. 32s) and tests/micro/ab_lane_packing.py (config 2's shape, local rule); both
   // agree within 3 % (profiles/round3_n_lane_width.txt, round3_m_lane_packing.txt).

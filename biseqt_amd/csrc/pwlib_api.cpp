@@ -165,6 +165,7 @@ struct pw_batch {
   std::vector<double> subst;
   bool simple = false, use_f64 = false;
   double plan_ms = 0;
+  pw::PlanKnobs knobs;                   // the planner's environment knobs, read by batch_plan
   int scale_shift = 0;                   // dyadic scaling: every score is held times 2^scale_shift by the integer kernels
   double score_mul = 1.0;                // 2^-scale_shift: what the kernels multiply a reported score with
   int variant = 0, brule = 0, endrule = 0, gosign = 0;
@@ -247,57 +248,66 @@ int batch_free_device(pw_batch* b) {
   return 0;
 }
 
-bool is_integral(double v) { return v == floor(v) && fabs(v) < 1e9; }
+// The planner's environment knobs (pw_plan.h, PlanKnobs), read once per batch.
+pw::PlanKnobs plan_knobs() {
+  auto on = [](const char* name) { return env_int(name, 0) != 0; };
+  pw::PlanKnobs k;
+  k.no_dyadic = on("PWLIB_NO_DYADIC");
+  k.latency_mode = env_int("PWLIB_LATENCY_MODE", -1);
+  k.no_packed_mat = on("PWLIB_NO_PACKED_MAT");
+  k.no_packed_anchored = on("PWLIB_NO_PACKED_ANCHORED");
+  k.no_packed_overlap = on("PWLIB_NO_PACKED_OVERLAP");
+  k.no_packed_mw = on("PWLIB_NO_PACKED_MW");
+  k.no_strip = on("PWLIB_NO_STRIP");
+  k.no_small_strip = on("PWLIB_NO_SMALL_STRIP");
+  k.strip_no_byte_rows = on("PWLIB_STRIP_NO_BYTE_ROWS");
+  k.no_small_tiled = on("PWLIB_NO_SMALL_TILED");
+  k.mw_wide_lanes = on("PWLIB_MW_WIDE_LANES");
+  k.simple_as_matrix = env_int("PWLIB_SIMPLE_AS_MATRIX", -1);
+  k.no_scaled16 = on("PWLIB_NO_SCALED16");
+  const char* bk = getenv("PWLIB_PACKED_BK");
+  if (bk && *bk) { k.packed_bk_forced = true; k.packed_bk = atoi(bk); k.packed_bk_seg = strchr(bk, 's') != nullptr; }
+  return k;
+}
+
+// The packed 16-bit body: consecutive (similar length) pairs share a wavefront (p16.seg), one WaveDesc per wavefront
+void plan_waves(pw_batch* b, const pw::PackedLayout& p16) {
+  const int ppw = p16.seg ? 64 / p16.nl : 1;
+  BkClass& c = b->classes[0];
+  for (size_t i = 0; i < c.order.size(); i += ppw) {
+    pw::WaveDesc wd;
+    memset(&wd, 0, sizeof wd);
+    wd.first = (int32_t)i; wd.count = (int32_t)std::min<size_t>(ppw, c.order.size() - i);
+    wd.nl = (p16.seg || p16.nw > 1) ? p16.nl : 64;      // lanes per pair in the wave / workgroup (the mask plane rows stay p16.nl wide)
+    wd.nblocks = 0; wd.steady_b0 = 0; wd.steady_b1 = 0x7fffffff;
+    for (int q = 0; q < wd.count; q++) {
+      const pw::PairDesc& d = b->descs[c.order[i + q]];
+      wd.nblocks = std::max(wd.nblocks, d.nblocks);
+      wd.steady_b0 = std::max(wd.steady_b0, d.steady_b0);
+      wd.steady_b1 = std::min(wd.steady_b1, d.steady_b1);
+    }
+    if (wd.steady_b1 < wd.steady_b0) wd.steady_b1 = wd.steady_b0;
+    b->waves.push_back(wd);
+  }
+}
 
 // Planning: host arithmetic only (dptable_init per pair, score type, kernel variant and geometry, launch classes) -- no
-// device call, so pw_plan_only can run it anywhere.  batch_alloc then creates the device buffers it sized.
+// device call, so pw_plan_only can run it anywhere.  batch_alloc then creates the device buffers it sized.  The rules that
+// choose the kernels are pure functions shared with the CPU lane emulator (pw_plan.h); this function gathers their inputs.
 int batch_plan(pw_batch* b) {
   const double t_build0 = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-  // ---- scoring analysis ----
+  // ---- scoring analysis (PW_FLAG_FORCE_F64 and PWLIB_NO_DYADIC=1 keep fractional scores as given) ----
   const int L = b->L;
-  bool integral = is_integral(b->go) && is_integral(b->ge);
-  double maxabs = std::max(fabs(b->go), std::max(fabs(b->ge), fabs(b->go + b->ge)));
-  b->simple = true;
-  {
-    const double mt0 = b->subst[0], mm0 = L > 1 ? b->subst[1] : b->subst[0];
-    for (int i = 0; i < L; i++) for (int j = 0; j < L; j++) {
-      const double v = b->subst[(size_t)i * L + j];
-      if (!(v == v) || fabs(v) > 1e300) return fail("substitution scores must be finite");
-      integral = integral && is_integral(v);
-      maxabs = std::max(maxabs, fabs(v));
-      if (v != (i == j ? mt0 : mm0)) b->simple = false;
-    }
+  const pw::PlanKnobs& kn = b->knobs = plan_knobs();
+  const pw::ScoreSummary sc = pw::summarise_scores(L, b->subst.data(), b->go, b->ge, !(b->flags & PW_FLAG_FORCE_F64) && !kn.no_dyadic);
+  if (!sc.finite) return fail("substitution scores must be finite");
+  b->simple = sc.simple;
+  if (sc.scale_shift) {
+    const double f = (double)(1 << sc.scale_shift);
+    for (auto& v : b->subst) v *= f;
+    b->go *= f; b->ge *= f;
+    b->scale_shift = sc.scale_shift; b->score_mul = 1.0 / f;
   }
-  // Dyadic scaling: scores that are all multiples of 2^-k (k <= 10; e.g. config 5's extension scores 0.25 / -1 / 0 / -1,
-  // reference experiments/blot_stats.py:365-372) are held times 2^k and run on the integer kernels.  Every partial sum of
-  // such scores is exact in the reference's doubles (the planner keeps them far below 2^53 / 2^k), scaling by a power of
-  // two preserves every comparison and tie, and the kernels report value * 2^-k, which is exact again: bit-identical
-  // results, no f64 kernel.  PW_FLAG_FORCE_F64 and PWLIB_NO_DYADIC=1 keep the scores as given.
-  if (!integral && !(b->flags & PW_FLAG_FORCE_F64) && !env_int("PWLIB_NO_DYADIC", 0) && maxabs < 1e6) {
-    for (int sh = 1; sh <= 10 && !b->scale_shift; sh++) {
-      const double f = (double)(1 << sh);
-      bool ok = is_integral(b->go * f) && is_integral(b->ge * f);
-      for (size_t i = 0; ok && i < b->subst.size(); i++) ok = is_integral(b->subst[i] * f);
-      if (ok) b->scale_shift = sh;
-    }
-    if (b->scale_shift) {
-      const double f = (double)(1 << b->scale_shift);
-      for (auto& v : b->subst) v *= f;
-      b->go *= f; b->ge *= f;
-      b->score_mul = 1.0 / f;
-      integral = true; maxabs *= f;
-    }
-  }
-  const double mt = b->subst[0], mm = L > 1 ? b->subst[1] : b->subst[0];
-  // the best and the worst substitution (any of them may be: the API accepts mismatch > match, and a matrix)
-  double smax = b->subst[0], smin = b->subst[0];
-  for (double v : b->subst) { smax = std::max(smax, v); smin = std::min(smin, v); }
-  if (b->simple) { smax = std::max(mt, mm); smin = std::min(mt, mm); }      // (L = 1: the mismatch score never occurs)
-  // An integer substitution matrix over at most 4 letters goes into the packed kernels as rows of bytes
-  // (WaveFill16<.., MAT>, _alnchoice_M reads subst_scores[o][m], _pw_internals.c:217-245): bytes subst - min, at most 127
-  // (times 4 under the scores-times-4 rule), and min <= 0 -- letters outside a sequence score the minimum and must not
-  // lift a cell that has not started.
-  const bool mat_ok = !b->simple && L <= 4 && integral && smin <= 0 && smax - smin <= 127 && !env_int("PWLIB_NO_PACKED_MAT", 0);
   pw::plan_rules(b->mode, b->type, &b->brule, &b->endrule);
   b->gosign = b->go < 0 ? -1 : (b->go > 0 ? 1 : 0);
   // ---- pass 1: per-pair plans (dptable_init arithmetic) and batch statistics ----
@@ -343,11 +353,11 @@ int batch_plan(pw_batch* b) {
   }
   // ---- score type and kernel variant ----
   // int32 is exact iff every score is an integer and no partial sum can leave +-2^27 (pw_wave.h)
-  b->use_f64 = (b->flags & PW_FLAG_FORCE_F64) || !integral || (double)maxspan * maxabs >= (double)(1 << 27);
+  b->use_f64 = (b->flags & PW_FLAG_FORCE_F64) || !sc.integral || (double)maxspan * sc.maxabs >= (double)(1 << 27);
   const bool bany = b->brule == pw::BRULE_ANY;
   const bool track = b->endrule == pw::END_STD_LOCAL || b->endrule == pw::END_BANDED_LOCAL;
   // A substitution matrix needs no kernel of its own: the wavefront kernels read every substitution score from a table in
-  // LDS (pw_wave.h, TAB), the packed kernels take small integer matrices as rows of bytes (mat_ok).  The generic kernel is
+  // LDS (pw_wave.h, TAB), the packed kernels take small integer matrices as rows of bytes (pw_plan.h).  The generic kernel is
   // left with what is decided at run time: go > 0, the score-plane dump, and alphabets beyond the LDS copy (32 letters).
   if ((b->flags & (PW_FLAG_FORCE_GENERIC | PW_FLAG_DUMP_SCORES)) || b->go > 0 || L > 32) b->variant = pw::VAR_GENERIC;
   else if (bany) b->variant = pw::VAR_FAST_ANY_TRACK;
@@ -355,257 +365,75 @@ int batch_plan(pw_batch* b) {
   else b->variant = pw::VAR_FAST;
   // latency mode: with at most 256 pairs the batch is a few hundred wavefronts on a 1024-SIMD chip, so the time is
   // the length of one pair's dependency chain, not throughput (PWLIB_LATENCY_MODE=0 / 1 overrides)
-  const int lat_env = env_int("PWLIB_LATENCY_MODE", -1);
-  const bool latency_mode = lat_env >= 0 ? lat_env != 0 : nsolv <= 256;
-  // lane-packed 16-bit kernel (pw_wave.h, WaveFill16): LOCAL / B_LOCAL, every running value fits int16.  The
-  // score bound is 8000, not 16000: the first diagonal above the band is computed like any other and its offer
-  // into the band is lowered by only 8192 (the sentinel), so no score -- in or out of the band -- may reach that
-  // (regression: test_band_edge_never_leaks_long_pairs).
-  // Rules 1 / 2 (B_OVERLAP / B_GLOBAL, WaveFill16<.., RULE>): scores go negative, the sentinel is -24000 and every
-  // real score must stay within [-23000, 30000].  Lower bound of any in-band cell: the straight run down its own diagonal
-  // from the table edge (min(X,Y) substitutions) -- for B_GLOBAL after the gap run from (0, 0) to that diagonal.
-  int pbk = 0, pnl = 0, pseg = 0, prule = -1;
-  if (b->variant == pw::VAR_FAST_ANY_TRACK && track) prule = 0;
-  // (B_OVERLAP, and standard-mode OVERLAP: the same begin rule, the best last cell of a diagonal, another order of ties)
-  else if (b->variant == pw::VAR_FAST && b->brule == pw::BRULE_EDGE &&
-           (b->endrule == pw::END_BANDED_OVERLAP || b->endrule == pw::END_STD_OVERLAP)) prule = 1;
-  // (the two mixed standard-mode types, begin and end rule read at run time by the rule-1 body: START_ANCHORED_OVERLAP begins
-  //  at (0, 0) and ends like OVERLAP, END_ANCHORED_OVERLAP begins like OVERLAP and ends at (X, Y))
-  else if (b->variant == pw::VAR_FAST && ((b->brule == pw::BRULE_ORIGIN && b->endrule == pw::END_STD_OVERLAP) ||
-                                         (b->brule == pw::BRULE_EDGE && b->endrule == pw::END_CORNER))) prule = 1;
-  // (B_GLOBAL, and standard-mode GLOBAL: the same begin / end rule on the band [-Y, X])
-  else if (b->variant == pw::VAR_FAST && b->brule == pw::BRULE_ORIGIN && b->endrule == pw::END_CORNER) prule = 2;
-  // (END_ANCHORED: begin anywhere like LOCAL, end at (X, Y) -- the captured last cell of one diagonal, nothing tracked)
-  else if (b->variant == pw::VAR_FAST_ANY_TRACK && b->endrule == pw::END_CORNER) prule = 4;
-  // (START_ANCHORED: begin at (0, 0) like GLOBAL, end at the first best cell, which must beat 0)
-  else if (b->variant == pw::VAR_FAST_TRACK && b->brule == pw::BRULE_ORIGIN && b->endrule == pw::END_STD_LOCAL) prule = 5;
-  if (!b->simple && (prule > 2 || !mat_ok)) prule = -1;   // (the packed matrix form: rules 0 .. 3, matrices it admits)
-  // The packed kernels keep cells that have not started (and cells beyond a diagonal's end) at a shallow 16-bit sentinel, pinned
-  // from below by a maximum; what keeps them from creeping UP is that letters outside a sequence "match nothing" and that
-  // scores nothing -- true only while the mismatch score (what the plain form gives such letters; with one letter the match
-  // score) is <= 0.  With mismatch > 0, which the API accepts, a diagonal that waits ~1400 steps for its first cell starts
-  // from a positive phantom score (found by the fuzz on a 3673-diagonal band, scores 1 / 6 / -5 / -2: a wrong end cell, and the
-  // walk from it left the mask plane).  Such scores take the matrix form where it applies (its off-table letters score the
-  // matrix MINIMUM, required <= 0) and the 32-bit kernels otherwise.
-  bool force_simple_mat = false;
-  if (b->simple && prule >= 0 && mm > 0) {
-    const bool can_mat = prule <= 2 && L >= 2 && L <= 4 && integral && smin <= 0 && smax - smin <= 127 && !env_int("PWLIB_NO_PACKED_MAT", 0);
-    if (can_mat) force_simple_mat = true; else prule = -1;
-  }
-  if (prule >= 4 && env_int("PWLIB_NO_PACKED_ANCHORED", 0)) prule = -1;
-  bool pfits = false;
-  // (any substitution may be the best one: the API accepts mismatch > match)
-  if (prule == 0 || prule == 4) pfits = (double)maxmin * std::max(0.0, smax) <= 8000;
-  else if (prule > 0) {
-    // real scores must stay above the values derived from the sentinel (<= -24000 + 100) and below int16's top -- rule 5
-    // below 8192, the range of its running-best key
-    const double worst = std::max(0.0, -smin);
-    const double lowest = (double)maxmin * worst + fabs(b->go) + fabs(b->ge) * (maxnd + 2);
-    const double highest = (double)maxmin * std::max(0.0, smax);
-    pfits = lowest <= 23000 && highest <= (prule == 5 ? 8000 : 30000) && b->go <= 0 && !env_int("PWLIB_NO_PACKED_OVERLAP", 0);
-  }
+  const bool latency_mode = kn.latency_mode >= 0 ? kn.latency_mode != 0 : nsolv <= 256;
+  // the strip pipeline takes standard-mode pairs with match / mismatch scores or a matrix of signed bytes (pw_strip.h, BROW),
+  // scores within +-2^25 (it tracks a row's best as 32 * H + step)
+  const bool strips_serve = b->mode == pw::STD_MODE && !kn.no_strip && !(b->flags & (PW_FLAG_DUMP_SCORES | PW_FLAG_NO_STRIP)) &&
+                            (double)maxspan * sc.maxabs < (double)(1 << 25) &&
+                            (sc.simple || (sc.integral && L <= 4 && sc.smax <= 127 && sc.smin >= -128 && !kn.strip_no_byte_rows));
   // (a few standard-mode pairs: the strips, one pair after another, when they are estimated to finish before the 16-bit body
   //  on several wavefronts per pair would -- tests/micro/few_pairs.py: 2 kb x 2 kb, one pair 0.6 ms on the strips, 1.5 ms
   //  there; four pairs 2.3 ms and 1.6 ms)
-  const bool strip_scores = b->simple || (integral && L <= 4 && smax <= 127 && smin >= -128 && !env_int("PWLIB_STRIP_NO_BYTE_ROWS", 0));
-  const bool strips_win = latency_mode && strip_scores && b->mode == pw::STD_MODE && min_x >= 127 && !(b->flags & PW_FLAG_DUMP_SCORES) &&
-                          !env_int("PWLIB_NO_STRIP", 0) && !env_int("PWLIB_NO_SMALL_STRIP", 0) && !(b->flags & PW_FLAG_NO_STRIP) &&
-                          (double)maxspan * maxabs < (double)(1 << 25) && est.strips_beat_packed_workgroups(model);
-  if (prule >= 0 && pfits && !b->use_f64 &&
-      !(b->flags & (PW_FLAG_NO_PACKED16 | PW_FLAG_FORCE_TILED | PW_FLAG_FORCE_STRIP)) && maxnd > 2048 && maxnd <= 64 * pw::kMaxWavesPerPair * 32 &&
-      nsolv > 0 && maxabs <= 100 && maxspan < 32000 && b->ge <= 0 && !env_int("PWLIB_NO_PACKED_MW", 0) && !strips_win) {
-    // bands wider than one wavefront holds, many pairs (standard-mode tables of 1 .. 8 kb, say): the 16-bit body on a
-    // workgroup of up to 8 wavefronts per pair, as few diagonals per lane as 8 wavefronts allow
-    for (int i = 0; i < pw::kNumPackedBK; i++) {
-      const int bk = pw::kPackedBK[i];
-      if ((int64_t)64 * pw::kMaxWavesPerPair * bk >= maxnd) { pbk = bk; break; }
-    }
-    if (pbk) {
-      b->packed_nw = (maxnd + 64 * pbk - 1) / (64 * pbk);
-      pnl = 64 * b->packed_nw; pseg = 0;
-      b->variant = pw::VAR_FAST16;
+  const bool strips_win = latency_mode && strips_serve && min_x >= 127 && !kn.no_small_strip && est.strips_beat_packed_workgroups(model);
+  // ---- the packed 16-bit body (pw_wave.h, WaveFill16): admission and lane layout ----
+  const int rule = b->variant == pw::VAR_GENERIC ? -1 : pw::packed_rule(b->brule, b->endrule);
+  const pw::PackedAdmission adm = pw::admit_packed(rule, sc, L, b->go, b->ge, maxmin, maxnd, maxspan, kn);
+  pw::PackedLayout p16;
+  if (adm.rule >= 0 && !b->use_f64 && nsolv > 0 && !(b->flags & (PW_FLAG_NO_PACKED16 | PW_FLAG_FORCE_TILED | PW_FLAG_FORCE_STRIP))) {
+    // bands wider than one wavefront holds, many pairs (standard-mode tables of 1 .. 8 kb, say): a workgroup per pair
+    if (maxnd > 2048) {
+      if (maxnd <= 64 * pw::kMaxWavesPerPair * 32 && !kn.no_packed_mw && !strips_win) p16 = pw::packed_workgroup_layout(maxnd);
+    } else {
+      p16 = pw::packed_lane_layout(maxnd, sumnd, nsolv, latency_mode, strips_win, kn, model);
     }
   }
-  else if (prule >= 0 && pfits && !b->use_f64 &&
-      !(b->flags & (PW_FLAG_NO_PACKED16 | PW_FLAG_FORCE_TILED | PW_FLAG_FORCE_STRIP)) && maxnd <= 2048 &&
-      nsolv > 0 && maxabs <= 100 && maxspan < 32000 && b->ge <= 0) {
-    // Diagonals per lane and pairs per wavefront.  One pair per wave keeps the pair descriptor in scalar registers (measured
-    // ~7 % cheaper per cell); several pairs per wave (lane packing) keep more of the 64 x BK diagonal slots busy.  Each layout is
-    // priced (pw_model.h): what a slot-step costs at that lane width (the wide lanes pay for their registers) / the share of
-    // busy slots x a factor for the last, partly filled round of wavefronts over the SIMDs.  Round 3 found config 4's overlap
-    // batches -- bands of 9 .. 111 diagonals, 20 000 pairs -- on 28 diagonals per lane (69 % of the slots busy, but 1250
-    // wavefronts on 1024 SIMDs: 7.4 ms) where 8 per lane take 4.9 ms; with 50 000 pairs per batch 16 per lane win
-    // (profiles/round3_n_lane_width.txt).  Packing is taken when it is priced 5 % below one pair per wavefront.
-    const char* forced = getenv("PWLIB_PACKED_BK");        // tuning / A-B: "<bk>" or "<bk>s" (force packing)
-    if (forced && !*forced) forced = nullptr;
-    const double meannd = (double)sumnd / nsolv;
-    double cost1 = 1e300, costp = 1e300; int bk1 = 0, bkp = 0, nlp = 0;
-    for (int i = 0; i < pw::kNumPackedBK; i++) {
-      const int bk = pw::kPackedBK[i];
-      if (forced && atoi(forced) != bk) continue;
-      const int nl = (maxnd + bk - 1) / bk;
-      if (nl > 64) continue;
-      if (!bk1) {                                                             // smallest BK that fits: one pair per wavefront
-        bk1 = bk;
-        cost1 = model.one_pair_discount * model.seg_slot_cost[i] * pw::last_round_factor((double)nsolv) / (meannd / (64.0 * bk));
-      }
-      const int ppw = 64 / nl;
-      const int64_t nwv = ((int64_t)nsolv + ppw - 1) / ppw;
-      // (packing must leave at least one wavefront per SIMD: 20 000 pairs with a 21-diagonal band packed 64 to a wavefront are
-      //  313 wavefronts with 12 cells per lane and step -- 0.69 ms against 0.41 ms for 10 to a wavefront)
-      const bool enough = forced || nwv >= 1024;
-      const double cp = model.seg_slot_cost[i] * pw::last_round_factor((double)nwv) / ((double)ppw * meannd / (64.0 * bk));
-      if (ppw >= 2 && enough && cp < costp - 1e-9) { costp = cp; bkp = bk; nlp = nl; }      // ties: the narrower lanes
-    }
-    const bool want_seg = bkp && (!bk1 || costp < 0.95 * cost1 || (forced && strchr(forced, 's')));
-    // pairs that fit one wavefront side by side at the narrowest lanes
-    const int ppw1 = bk1 ? std::max(1, 64 / ((maxnd + bk1 - 1) / bk1)) : 1;
-    if ((latency_mode || nsolv < 1024 * ppw1) && bk1 && !forced) {
-      // fewer wavefronts than SIMDs (side by side): the time is one wavefront's chain of steps, so as few diagonals per
-      // lane as the band allows -- several pairs side by side where they fit, which changes the number of wavefronts, not
-      // the chain (2 kb pairs, band radius 20: 1.41 -> 0.49 ms; radius 50: 0.87 -> 0.49 ms).  Round 3 (found by
-      // tests/micro/planner_check.py): this also holds for 1024 ... 1024 x ppw1 pairs, which used to fall between the two
-      // rules and ran one pair per wavefront, two wavefronts per SIMD -- 2000 pairs of 1 kb with a 21-diagonal band
-      // 0.48 ms, side by side 0.37 ms.
-      pbk = bk1; pnl = (maxnd + bk1 - 1) / bk1; pseg = 64 / pnl >= 2 ? 1 : 0;
-    }
-    else if (want_seg) { pbk = bkp; pnl = nlp; pseg = 1; }
-    else if (bk1) { pbk = bk1; pnl = (maxnd + bk1 - 1) / bk1; pseg = 0; }
-    // one pair per wavefront with 16+ diagonals per lane is a long serial chain: small batches go multi-wavefront --
-    // the strips if they win, else the 16-bit body on up to 8 wavefronts with 4 or 8 diagonals per lane
-    if (latency_mode && pbk >= 16 && !pseg) {
-      pbk = 0;
-      if (!strips_win && !forced && !env_int("PWLIB_NO_PACKED_MW", 0)) {
-        for (int i = 0; i < pw::kNumPackedBK; i++) {
-          const int bk = pw::kPackedBK[i];
-          if ((int64_t)64 * pw::kMaxWavesPerPair * bk >= maxnd) { pbk = bk; break; }
-        }
-        if (pbk) { b->packed_nw = (maxnd + 64 * pbk - 1) / (64 * pbk); pnl = 64 * b->packed_nw; pseg = 0; }
-        if (b->packed_nw <= 1) { pbk = 0; b->packed_nw = 1; }      // (one wavefront would do: not this case)
-      }
-    }
-    if (pbk) b->variant = pw::VAR_FAST16;
+  if (p16.bk) {
+    b->variant = pw::VAR_FAST16;
+    b->packed_seg = p16.seg; b->packed_nw = p16.nw;
+    b->packed_mat = pw::packed_matrix_form(adm, p16, sc.simple, kn);
+    b->packed_rule = adm.x4 && (!b->packed_mat || adm.x4_matrix) ? 3 : adm.rule;   // rule 0, scores below 2048: every score times 4
+
   }
-  if (!b->simple && b->variant == pw::VAR_FAST16) b->packed_mat = 1;
-  // Match / mismatch scoring over at most 4 letters IS such a matrix, and the matrix form's cell pair is shorter -- one
-  // v_perm_b32 instead of xor, min and multiply-add, and under the local rule the bias comes off with a saturating subtract
-  // that makes the maximum with the begin candidate 0 unnecessary -- at the price of registers (3 wavefronts per SIMD instead
-  // of 5).  Taken where an A/B on the GPU showed it faster (tests/micro/ab_simple_matrix.py,
-  // profiles/round3_h_ab_simple_matrix.txt): the local rule at 8 diagonals per lane, one pair per wavefront (config 2's shape:
-  // 3.50 -> 3.29 ms) and at 16 (2.23 -> 2.15 ms), standard-mode GLOBAL at 32 per lane (4.38 -> 4.27 ms); slower lane-packed
-  // (+4 %) and under the overlap rule (+4 %).  PWLIB_SIMPLE_AS_MATRIX=0 / 1: never / wherever the matrix form exists (A/B).
-  if (b->simple && b->variant == pw::VAR_FAST16 && prule >= 0 && prule <= 2 && L >= 2 && L <= 4 && integral && smin <= 0 &&
-      smax - smin <= 127 && !env_int("PWLIB_NO_PACKED_MAT", 0)) {
-    const int knob = env_int("PWLIB_SIMPLE_AS_MATRIX", -1);
-    const bool measured = !pseg && b->packed_nw <= 1 && (((pbk == 8 || pbk == 16) && prule == 0) || (pbk == 32 && prule == 2));
-    if (force_simple_mat || knob > 0 || (knob < 0 && measured)) b->packed_mat = 1;
-  }
-  // ---- pass 2: kernel geometry per pair, mask planes, launch classes ----
+  // ---- pass 2: kernel geometry per pair (pw_plan.h, pair_layout), mask planes, launch classes ----
+  pw::PairRules pr;
+  pr.strips = strips_serve && !b->use_f64 && b->variant != pw::VAR_GENERIC && b->variant != pw::VAR_FAST16 &&
+              !(b->flags & PW_FLAG_FORCE_TILED);
+  pr.all_strips = (b->flags & PW_FLAG_FORCE_STRIP) != 0;
+  pr.few_strips = latency_mode && !kn.no_small_strip && est.strips_beat_workgroups(model);
+  pr.all_tiled = (b->flags & PW_FLAG_FORCE_TILED) != 0;
+  pr.few_tiled = latency_mode && !(b->flags & PW_FLAG_DUMP_SCORES) && !kn.no_small_tiled && est.tiles_beat_workgroups(model, b->use_f64);
+  pr.latency_mode = latency_mode; pr.f64 = b->use_f64; pr.wide_lanes = kn.mw_wide_lanes;
+  pr.packed_bk = p16.bk; pr.packed_nl = p16.nl;
   for (int32_t k = 0; k < b->n; k++) {
     pw::PairDesc& d = b->descs[k];
     if (!d.solvable) continue;
-    int bk, nl, nw = 1;
-    bool tiled = false;
-    // (scores within +-2^25: the strip kernel tracks a row's best as 32 * H + step)
-    const bool strip_ok = b->mode == pw::STD_MODE && !b->use_f64 && (double)maxspan * maxabs < (double)(1 << 25) &&
-                          b->variant != pw::VAR_GENERIC && b->variant != pw::VAR_FAST16 && strip_scores &&
-                          !(b->flags & (PW_FLAG_DUMP_SCORES | PW_FLAG_FORCE_TILED | PW_FLAG_NO_STRIP)) && !env_int("PWLIB_NO_STRIP", 0);
-    // ... always for tables wider than a workgroup holds; and for batches of a few pairs (at most 256: latency mode) when the
-    // strips of all pairs, one pair after another, are estimated to finish before the slowest workgroup would (2 kb x 2 kb:
-    // 0.6 ms per pair against 13.6 ms for one workgroup of 32-diagonal lanes -- up to 16 such pairs; 1 kb x 1 kb: 0.3 ms
-    // against 1.0 ms -- up to 2), for tables that span at least two strips
-    const bool few = latency_mode && d.X >= 127 && est.strips_beat_workgroups(model);
-    if (strip_ok && ((b->flags & PW_FLAG_FORCE_STRIP) || d.ndiag > 2048 * pw::kMaxWavesPerPair || (few && !env_int("PWLIB_NO_SMALL_STRIP", 0)))) {
-      // one pair wider than a workgroup, integer scores, simple scoring: rows in strips of 64, a pipeline of wavefronts
+    const pw::PairLayout lay = pw::pair_layout(d.ndiag, d.X, pr);
+    d.bk = lay.bk; d.nl = lay.nl;
+    d.mask_off = mask_words;
+    d.h_off = h_elems;
+    if (lay.kind == pw::PAIR_STRIPS) {
+      // rows in strips of 64, a pipeline of wavefronts
       const int nstrips = (d.X + 1 + 63) / 64, nkq = (d.Y + 64 + pw::kStripBlock - 1) / pw::kStripBlock;
-      d.layout = 1; d.bk = 0; d.nl = 64;
-      d.mask_off = mask_words;
+      d.layout = 1;
       mask_words += (uint64_t)nstrips * nkq * 64 * 4;
-      d.h_off = h_elems;
       b->strips.push_back(k);
       b->fifo_bytes = std::max<size_t>(b->fifo_bytes, (size_t)nstrips * (size_t)pw::strip_fifo_pitch(d.Y) * 8);
       continue;
     }
-    // a few pairs with bands wider than a wavefront holds, not served by the strips (f64 scores, a substitution matrix,
-    // go > 0, banded): the tiled kernel when all pairs, one after another, are estimated to finish before the slowest workgroup
-    const bool few_tiled = latency_mode && d.ndiag > 1024 && !(b->flags & PW_FLAG_DUMP_SCORES) && !env_int("PWLIB_NO_SMALL_TILED", 0) &&
-                           est.tiles_beat_workgroups(model, b->use_f64);
-    if (b->variant == pw::VAR_FAST16) { bk = pbk; nl = pnl; }
-    else if ((b->flags & PW_FLAG_FORCE_TILED) || d.ndiag > 2048 * pw::kMaxWavesPerPair || few_tiled) {
-      // wider than a workgroup holds (or forced): time-blocked tiles of the band, one pair after another
-      if (b->flags & PW_FLAG_DUMP_SCORES) return fail("the score plane is not available for tiled (very wide) tables");
-      bk = pw::kTileBKHost;
-      nl = (d.ndiag + bk - 1) / bk;
-      tiled = true;
-    } else {
-      bk = pw::plan_pick_bk(d.ndiag, pw::kSupportedBK, pw::kNumSupportedBK);
-      nl = 64;
-      if (bk == 0) {
-        // wider than one wavefront holds: a workgroup of nw wavefronts, 2048 diagonals each -- in latency mode as many
-        // wavefronts as a workgroup takes, with as few diagonals per lane as that allows (2 kb x 2 kb: 8 x 8 instead of
-        // 2 x 32 diagonals per lane)
-        bk = 32;
-        if (latency_mode || !env_int("PWLIB_MW_WIDE_LANES", 0)) {
-          // (also with many pairs: at 32 diagonals per lane the kernel spills 1.4 - 3 KB of registers per lane; 300 pairs of
-          //  10 kb with a 3001-diagonal band: 208 ms with 2 x 32, measured below with 6 x 8)
-          for (int cand : {8, 16, 32}) {
-            if ((int64_t)64 * pw::kMaxWavesPerPair * cand >= d.ndiag) { bk = cand; break; }
-          }
-        }
-        nw = (d.ndiag + 64 * bk - 1) / (64 * bk);
-        nl = 64 * nw;
-      } else if ((latency_mode && bk >= 16) || (b->use_f64 && bk >= 32)) {
-        // (f64 with 32 diagonals per lane needs more registers than a wavefront has: 3000 pairs with a 1201-diagonal band
-        //  take 166 ms on one wavefront each, 47 ms on five wavefronts of 4 diagonals per lane)
-        // a handful of pairs cannot fill the chip anyway: spread each over up to 8 wavefronts with few diagonals
-        // per lane (the step count is fixed by X + Y; the work per step shrinks 4-8x, the exchange costs ~0.3 us)
-        for (int cand : {4, 8, 16}) {
-          if ((int64_t)64 * pw::kMaxWavesPerPair * cand >= d.ndiag) { bk = cand; break; }
-        }
-        nw = (d.ndiag + 64 * bk - 1) / (64 * bk);
-        nl = 64 * nw;
-      }
-    }
-    d.bk = bk; d.nl = nl;
-    d.mask_off = mask_words;
-    mask_words += (uint64_t)(d.nblocks + 1) * nl * bk;   // + one spare row: the branch-free stores of idle lanes land there
-    d.h_off = h_elems;
+    if (lay.kind == pw::PAIR_TILED && (b->flags & PW_FLAG_DUMP_SCORES)) return fail("the score plane is not available for tiled (very wide) tables");
+    mask_words += (uint64_t)(d.nblocks + 1) * lay.nl * lay.bk;   // + one spare row: the branch-free stores of idle lanes land there
     if (b->flags & PW_FLAG_DUMP_SCORES) h_elems += (uint64_t)d.ndiag * d.h_pitch;
-    if (tiled) { b->tiled.push_back(k); b->st_pitch = std::max(b->st_pitch, (d.ndiag + 63) / 64 * 64); continue; }
+    if (lay.kind == pw::PAIR_TILED) { b->tiled.push_back(k); b->st_pitch = std::max(b->st_pitch, (d.ndiag + 63) / 64 * 64); continue; }
     size_t ci = 0;
-    for (; ci < b->classes.size(); ci++) if (b->classes[ci].bk == bk && b->classes[ci].nw == nw) break;
-    if (ci == b->classes.size()) { b->classes.emplace_back(); b->classes.back().bk = bk; b->classes.back().nw = nw; }
+    for (; ci < b->classes.size(); ci++) if (b->classes[ci].bk == lay.bk && b->classes[ci].nw == lay.nw) break;
+    if (ci == b->classes.size()) { b->classes.emplace_back(); b->classes.back().bk = lay.bk; b->classes.back().nw = lay.nw; }
     b->classes[ci].order.push_back(k);
   }
   for (auto& c : b->classes)
     std::stable_sort(c.order.begin(), c.order.end(), [&](int32_t x, int32_t y) {
       return b->descs[x].nblocks > b->descs[y].nblocks;
     });
-  if (b->variant == pw::VAR_FAST16) {
-    // consecutive (similar length) pairs share a wavefront
-    const int ppw = pseg ? 64 / pnl : 1;
-    b->packed_seg = pseg; b->packed_rule = prule;
-    // rule 0, scores below 2048: the kernel that holds every score times 4 (WaveFill16, RULE 3)
-    if (prule == 0 && (double)maxmin * std::max(0.0, smax) <= 2047 && !env_int("PWLIB_NO_SCALED16", 0) &&
-        (!b->packed_mat || 4 * (smax - smin) <= 127))
-      b->packed_rule = 3;
-    BkClass& c = b->classes[0];
-    for (size_t i = 0; i < c.order.size(); i += ppw) {
-      pw::WaveDesc wd;
-      memset(&wd, 0, sizeof wd);
-      wd.first = (int32_t)i; wd.count = (int32_t)std::min<size_t>(ppw, c.order.size() - i);
-      wd.nl = (pseg || b->packed_nw > 1) ? pnl : 64;      // lanes per pair in the wave / workgroup (the mask plane rows stay pnl wide)
-      wd.nblocks = 0; wd.steady_b0 = 0; wd.steady_b1 = 0x7fffffff;
-      for (int q = 0; q < wd.count; q++) {
-        const pw::PairDesc& d = b->descs[c.order[i + q]];
-        wd.nblocks = std::max(wd.nblocks, d.nblocks);
-        wd.steady_b0 = std::max(wd.steady_b0, d.steady_b0);
-        wd.steady_b1 = std::min(wd.steady_b1, d.steady_b1);
-      }
-      if (wd.steady_b1 < wd.steady_b0) wd.steady_b1 = wd.steady_b0;
-      b->waves.push_back(wd);
-    }
-  }
+  if (b->variant == pw::VAR_FAST16) plan_waves(b, p16);
   b->mask_words = mask_words; b->h_elems = h_elems; b->tx_bytes = tx_bytes;
   b->arena_shared = (b->flags & PW_FLAG_SHARED_ARENA) != 0;
   b->plan_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count() - t_build0;
@@ -714,7 +542,7 @@ int xcc_queues(int device, int32_t* xcc_queue) {
 
 // The strip kernel's byte rows (pw_strip.h, BROW): at most 4 letters, every score an integer that fits a signed byte
 bool strip_byte_rows_ok(const pw_batch* b) {
-  if (b->L > 4 || env_int("PWLIB_STRIP_NO_BYTE_ROWS", 0)) return false;
+  if (b->L > 4 || b->knobs.strip_no_byte_rows) return false;
   for (double v : b->subst) if (v != std::floor(v) || v < -128 || v > 127) return false;
   return true;
 }

@@ -14,7 +14,7 @@ _lib = None
 
 
 def build(force=False):
-    deps = [SRC] + [os.path.join(CSRC, f) for f in ('pw_wave.h', 'pw_strip.h', 'pw_plan.h', 'pw_types.h')]
+    deps = [SRC] + [os.path.join(CSRC, f) for f in ('pw_wave.h', 'pw_strip.h', 'pw_plan.h', 'pw_model.h', 'pw_types.h')]
     if force or not os.path.exists(SO) or any(os.path.getmtime(d) > os.path.getmtime(SO) for d in deps):
         subprocess.check_call(['g++', '-O1', '-std=c++17', '-shared', '-fPIC', '-ffp-contract=off',
                                SRC, '-o', SO])

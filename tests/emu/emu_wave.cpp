@@ -227,12 +227,7 @@ template <int BK> struct Run16<int32_t, BK> {
       const bool seg = g_packed_mode == 1 || g_packed_mode == 4;
       const bool x4 = g_packed_mode == 3 || g_packed_mode == 4;
       wd.nl = seg ? pd.nl : 64 * g_waves;
-      const bool local_end = a.endrule == pw::END_STD_LOCAL || a.endrule == pw::END_BANDED_LOCAL;
-      int rule;
-      if (a.brule == pw::BRULE_ANY) rule = local_end ? (x4 ? 3 : 0) : 4;                 // LOCAL / B_LOCAL; END_ANCHORED
-      else if (local_end) rule = 5;                                                     // START_ANCHORED
-      else if (a.endrule == pw::END_BANDED_OVERLAP || a.endrule == pw::END_STD_OVERLAP) rule = 1;
-      else rule = a.brule == pw::BRULE_ORIGIN ? 2 : 1;                                  // END_CORNER: global, or END_ANCHORED_OVERLAP
+      const int rule0 = pw::packed_rule(a.brule, a.endrule), rule = rule0 == 0 && x4 ? 3 : rule0;
       const bool mat = g_packed_mat;
       switch (rule * 2 + (mat ? 1 : 0)) {
         case 0: seg_or_not<0, false>(a, wd, seg); break;
@@ -294,11 +289,7 @@ int solve_T(int mode, int type, const int* origin, int X, const int* mutant, int
   std::vector<T> hd;
   if (hdump) hd.assign((size_t)pl.ndiag * pd.h_pitch, T(0));
   std::vector<T> sub((size_t)L * L);
-  bool simple = true;
-  for (int i = 0; i < L; i++) for (int j = 0; j < L; j++) {
-    sub[(size_t)i * L + j] = (T)subst[(size_t)i * L + j];
-    if (subst[(size_t)i * L + j] != (i == j ? subst[0] : (L > 1 ? subst[1] : subst[0]))) simple = false;
-  }
+  for (int i = 0; i < L * L; i++) sub[i] = (T)subst[i];
   pw::Result res;
   memset(&res, 0, sizeof res);
   pw::FillParams<T> a;
@@ -308,33 +299,27 @@ int solve_T(int mode, int type, const int* origin, int X, const int* mutant, int
   a.npairs = 1; a.L = L; a.brule = pl.brule; a.endrule = pl.endrule; a.banded = (mode == pw::BANDED_MODE);
   a.match = sub[0]; a.mismatch = L > 1 ? sub[1] : sub[0]; a.go = (T)go; a.ge = (T)ge;
   a.score_mul = 1.0;
-  // a small integer matrix may go through the packed kernels' matrix form (the product's admission: pwlib_api.cpp)
-  double smin = subst[0], smax = subst[0];
-  bool integral = true;
-  for (int i = 0; i < L * L; i++) { smin = subst[i] < smin ? subst[i] : smin; smax = subst[i] > smax ? subst[i] : smax; integral = integral && subst[i] == (double)(int)subst[i]; }
+  // a small integer matrix may go through the packed kernels' matrix form (the planner's admission, pw_plan.h); the form is
+  // the caller's to choose (packed16)
+  const pw::ScoreSummary ss = pw::summarise_scores(L, subst, go, ge, false);
+  const bool simple = ss.simple;
   const bool x4mode = packed16 == 3 || packed16 == 4;
-  const bool mat16 = packed16 && !simple && L <= 4 && integral && smin <= 0 && (x4mode ? 4 : 1) * (smax - smin) <= 127 && sizeof(T) == 4;
+  const bool mat16 = packed16 && !simple && pw::packed_matrix_bytes_ok(ss, L, x4mode) && sizeof(T) == 4;
   const int generic = force_generic || (!simple && !mat16) || go > 0 || hdump != nullptr;
   const int bany = pl.brule == pw::BRULE_ANY;
   const int track = pl.endrule == pw::END_STD_LOCAL || pl.endrule == pw::END_BANDED_LOCAL;
-  const bool rule_local = bany && track;
-  const bool rule_overlap = (pl.brule == pw::BRULE_EDGE && (pl.endrule == pw::END_BANDED_OVERLAP || pl.endrule == pw::END_STD_OVERLAP)) ||
-                            (pl.brule == pw::BRULE_ORIGIN && pl.endrule == pw::END_STD_OVERLAP) ||
-                            (pl.brule == pw::BRULE_EDGE && pl.endrule == pw::END_CORNER);
-  const bool rule_global = pl.brule == pw::BRULE_ORIGIN && pl.endrule == pw::END_CORNER;      // B_GLOBAL, and GLOBAL on the full band
-  const bool rule_anchored = !mat16 && ((bany && pl.endrule == pw::END_CORNER) ||             // END_ANCHORED
-                                        (pl.brule == pw::BRULE_ORIGIN && pl.endrule == pw::END_STD_LOCAL));   // START_ANCHORED
-  const int use16 = packed16 && !generic && (rule_local || rule_overlap || rule_global || rule_anchored) && bk % 4 == 0 && sizeof(T) == 4;
+  const int rule = pw::packed_rule(pl.brule, pl.endrule);
+  const int use16 = packed16 && !generic && rule >= 0 && !(mat16 && rule > 2) && bk % 4 == 0 && sizeof(T) == 4;
   g_packed_mode = packed16;
   g_packed_mat = mat16;
   if (mat16) {
     const int scale = x4mode ? 4 : 1;
     for (int o = 0; o < 4; o++) {
       uint32_t row = 0;
-      for (int m = 0; m < 4; m++) if (o < L && m < L) row |= (uint32_t)(scale * (int)(subst[o * L + m] - smin)) << (8 * m);
+      for (int m = 0; m < 4; m++) if (o < L && m < L) row |= (uint32_t)(scale * (int)(subst[o * L + m] - ss.smin)) << (8 * m);
       a.mat_rows[o] = row;
     }
-    a.mat_bias = scale * (int)(-smin);
+    a.mat_bias = scale * (int)(-ss.smin);
   }
   if (packed16 && !generic && !use16) return -5;                   // the caller asked for a packed kernel that does not exist
   if (use16 && g_waves == 1) pd.nl = (pl.ndiag + bk - 1) / bk;
