@@ -197,6 +197,26 @@ static inline ScoreSummary summarise_scores(int L, const double* subst, double g
   return s;
 }
 
+// The reference starts every gap candidate's maximum at -INT_MAX (_pw_internals.c:267) and so does the end-cell search of
+// OVERLAP / B_OVERLAP (:320, :381): a candidate at or below it is floored there (with choices[0] as its base), a cell at
+// or below it is never an end cell.  The kernels do not reproduce that floor, so the planner refuses the problems that could
+// reach it.  What decides it is the lowest cell MAXIMUM, not the lowest path: a gap candidate out of cell c is at least
+// max(c) + ge + min(go, 0), and an end cell's score is its maximum.  Every cell that holds a choice has one out of a
+// predecessor that holds one (or the begin candidate 0), so max(x, y) >= -(x + y) * h, where h bounds the loss per unit of
+// x + y over the steps that are always there:
+//   * standard mode, and bands of 2+ diagonals: every cell but the first has a gap predecessor in the table / band (the
+//     band holds diagonal d - 1 or d + 1), so h = gap_step = max(0, -(ge + min(go, 0))) -- the substitution scores do not
+//     matter, however low;
+//   * a band of one diagonal: substitutions only, h = max(gap_step, -smin).
+// A candidate or end cell is at most X + Y + 1 steps from (0, 0): maxspan * h < INT_MAX (maxspan = X + Y + 2, scores in the
+// CALLER's units, not times 2^scale_shift) keeps every one above the floor.  Begin-anywhere rules (LOCAL, END_ANCHORED,
+// B_LOCAL) are never affected: every cell holds the begin candidate 0, so a floored candidate is never kept.
+static inline double floor_gap_step(double go, double ge) { return std::max(0.0, -(ge + std::min(go, 0.0))); }
+static inline bool reaches_reference_floor(int brule, bool one_diagonal, double gap_step, double smin, int64_t maxspan) {
+  const double h = one_diagonal ? std::max(gap_step, -smin) : gap_step;
+  return brule != BRULE_ANY && (double)maxspan * h >= 2147483647.0;
+}
+
 // The planner's environment knobs (tuning and A/B runs), read once per batch (pwlib_api.cpp, plan_knobs).  The defaults
 // are the planner's own choices; the CPU lane emulator and the tests use them.
 struct PlanKnobs {
@@ -239,6 +259,21 @@ static inline int packed_rule(int brule, int endrule) {
 // not started.  Match / mismatch scores over 2 .. 4 letters are such a matrix too.
 static inline bool packed_matrix_bytes_ok(const ScoreSummary& s, int L, bool x4) {
   return L >= 2 && L <= 4 && s.integral && s.smin <= 0 && (x4 ? 4 : 1) * (s.smax - s.smin) <= 127;
+}
+
+// ... the rows themselves: rows[o] holds scale * (subst[o][m] - min) in byte m = 0 .. 3 from the low byte up (scale 4 in
+// the scores-times-4 form), *bias = scale * -min; letters beyond L never occur.  `subst` as the kernels hold it.
+static inline void packed_matrix_rows(const double* subst, int L, bool x4, uint32_t rows[4], int32_t* bias) {
+  const int scale = x4 ? 4 : 1;
+  double smin = subst[0];
+  for (int i = 0; i < L * L; i++) smin = std::min(smin, subst[i]);
+  for (int o = 0; o < 4; o++) {
+    uint32_t row = 0;
+    for (int m = 0; m < 4; m++)
+      if (o < L && m < L) row |= (uint32_t)(scale * (int)(subst[(size_t)o * L + m] - smin)) << (8 * m);
+    rows[o] = row;
+  }
+  *bias = scale * (int)(-smin);
 }
 
 struct PackedAdmission {

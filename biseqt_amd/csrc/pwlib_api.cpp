@@ -351,6 +351,19 @@ int batch_plan(pw_batch* b) {
     }
     b->descs[k] = d;
   }
+  // the reference's -INT_MAX floor (pw_plan.h, reaches_reference_floor): refused, not silently diverged from
+  {
+    const double f = (double)(1 << sc.scale_shift);            // (b->go, b->ge, sc.smin: times 2^scale_shift)
+    const double gstep = pw::floor_gap_step(b->go, b->ge) / f, smin = sc.smin / f;
+    for (int32_t k = 0; k < b->n; k++) {
+      const pw::PairDesc& d = b->descs[k];
+      if (d.solvable && pw::reaches_reference_floor(b->brule, d.ndiag == 1 && b->mode == pw::BANDED_MODE, gstep, smin,
+                                                    (int64_t)d.X + d.Y + 2))
+        return fail("scores too low for this alignment type: (X + Y + 2) * (the most a gap step, or on a one-diagonal band a "
+                    "substitution, can lower a score) must stay below INT_MAX, where the reference floors gap candidates and "
+                    "end cells at -INT_MAX (not reproduced)");
+    }
+  }
   // ---- score type and kernel variant ----
   // int32 is exact iff every score is an integer and no partial sum can leave +-2^27 (pw_wave.h)
   b->use_f64 = (b->flags & PW_FLAG_FORCE_F64) || !sc.integral || (double)maxspan * sc.maxabs >= (double)(1 << 27);
@@ -652,19 +665,7 @@ int launch_packed_fill(pw_batch* b, hipStream_t st) {
   a.go = (int32_t)b->go; a.ge = (int32_t)b->ge;
   a.score_mul = b->score_mul;
   a.order = b->classes[0].d_order; a.waves = b->d_waves;
-  if (b->packed_mat) {
-    // rows of bytes scale * (subst[o][m] - min), m = 0 .. 3 from the low byte up; letters beyond L never occur
-    const int scale = b->packed_rule == 3 ? 4 : 1;
-    double smin = b->subst[0];
-    for (double v : b->subst) smin = std::min(smin, v);
-    for (int o = 0; o < 4; o++) {
-      uint32_t row = 0;
-      for (int m = 0; m < 4; m++)
-        if (o < b->L && m < b->L) row |= (uint32_t)(scale * (int)(b->subst[(size_t)o * b->L + m] - smin)) << (8 * m);
-      a.mat_rows[o] = row;
-    }
-    a.mat_bias = scale * (int)(-smin);
-  }
+  if (b->packed_mat) pw::packed_matrix_rows(b->subst.data(), b->L, b->packed_rule == 3, a.mat_rows, &a.mat_bias);
   if (b->packed_nw > 1) HIP_TRY(pw::launch_fill16_mw(a, b->classes[0].bk, b->packed_rule, b->packed_mat, b->packed_nw, (int)b->waves.size(), st));
   else HIP_TRY(pw::launch_fill16(a, b->classes[0].bk, b->packed_seg, b->packed_rule, b->packed_mat, (int)b->waves.size(), st));
   return 0;
@@ -1132,6 +1133,16 @@ int dptable_init(dptable* T) {
       if (type == B_GLOBAL && (X - Y > pl.dmax || X - Y < pl.dmin || (int64_t)pl.dmax * pl.dmin > 0))
         printf("End points not within band for global alignment!\n");            // :41
       else printf("Invalid band: [%d, %d]!\n", pl.dmin, pl.dmax);                // :47
+      return -1;
+    }
+  }
+  {  // the reference's -INT_MAX floor (pw_plan.h, reaches_reference_floor), as far as init can tell: it reads the frame
+     // lengths only (the alphabet is the letters' to say), so here the gap scores; dptable_solve's planner adds the
+     // substitution scores of one-diagonal bands and refuses there
+    const double gstep = pw::floor_gap_step(prob->scores->gap_open_score, prob->scores->gap_extend_score);
+    if (pw::reaches_reference_floor(pl.brule, false, gstep, 0.0, (int64_t)X + Y + 2)) {
+      fprintf(stderr, "pwlib: (X + Y + 2) * -(ge + min(go, 0)) = %.17g reaches the reference's -INT_MAX floor of gap "
+              "candidates and end cells (not reproduced); refusing\n", ((double)X + Y + 2) * gstep);
       return -1;
     }
   }

@@ -1,6 +1,7 @@
 """ctypes wrapper of the CPU lane emulator (tests/emu/emu_wave.cpp) -- TEST INFRASTRUCTURE ONLY."""
 import ctypes as C
 import os
+import re
 import subprocess
 
 import numpy as np
@@ -32,7 +33,12 @@ def lib():
 
 def solve(origin, mutant, mode=0, alntype=0, subst=None, L=None, match=1., mismatch=0., go=0., ge=0.,
           diag_range=None, origin_range=None, mutant_range=None, use_double=False, force_generic=False,
-          bk=8, want_table=False, packed16=False, waves=1, **_):
+          bk=8, want_table=False, packed16=False, waves=1, matrix=None, product_variant=False, **_):
+    """One problem on one emulated kernel.  ``packed16``: 0 the 32-bit / f64 kernels; 1 the packed 16-bit body lane-packed
+    (on ceil(ndiag / bk) lanes), 2 one pair per wavefront, 3 / 4 the same as 2 / 1 with every score times 4 (rule 3).
+    ``matrix`` (packed only): None the matrix form where the scores need it (a non-simple matrix), False never, True always
+    -- match / mismatch scores included; a matrix form that does not exist for the scores is an error.  ``product_variant``:
+    the 32-bit / f64 variant as the planner picks it (a matrix on the fast variants), else every matrix on the generic one."""
     o = np.asarray(origin, dtype=np.int32)
     m = np.asarray(mutant, dtype=np.int32)
     if L is None:
@@ -61,6 +67,8 @@ def solve(origin, mutant, mode=0, alntype=0, subst=None, L=None, match=1., misma
         hd = np.zeros(nd * (min(X, Y) + 1), np.float64)
         hp = hd.ctypes.data_as(C.POINTER(C.c_double))
     lib().emu_set_waves(int(waves))
+    lib().emu_set_packed_matrix(-1 if matrix is None else int(bool(matrix)))
+    lib().emu_set_product_variant(int(bool(product_variant)))
     rc = lib().emu_solve(mode, alntype, of.ctypes.data_as(C.POINTER(C.c_int)), X,
                          mf.ctypes.data_as(C.POINTER(C.c_int)), Y, L,
                          S.ctypes.data_as(C.POINTER(C.c_double)), C.c_double(go), C.c_double(ge),
@@ -137,3 +145,70 @@ def solve_strip(origin, mutant, alntype=0, match=1., mismatch=0., go=0., ge=0., 
         out['origin_idx'] = info[6]
         out['mutant_idx'] = info[7]
     return out
+
+
+class NotEmulated(Exception):
+    """The planner chose a kernel the emulator does not run (the tiled kernel)."""
+
+
+_KERNEL = re.compile(r'^k_fill(16_mw|16|_mw|)<(int|double|)(?:, )?(\d+)(?:, (true|false))?(?:, (\d+))?')
+
+
+def solve_planned(pairs, flags=0, **kw):
+    """Every pair of a batch on the kernel the product's planner picks for the WHOLE batch (``batch.plan_only`` on the
+    batch's shapes, with the ``PWLIB_*`` knobs of the environment): BK, lane packing, wavefronts per pair, packed rule,
+    matrix form, int32 / f64, the strips, dyadic scaling.  ``pairs``: list of (origin, mutant); ``kw``: the oracle's
+    scoring arguments (``mode``, ``alntype``, ``L``, ``subst`` or ``match`` / ``mismatch``, ``go``, ``ge``,
+    ``diag_range`` -- one band, or a list with one per pair).  Returns ``(plan, [result dict per pair])``.  Raises
+    :class:`NotEmulated` for the tiled kernel instead of running another form."""
+    from biseqt_amd.batch import plan_only
+    mode, alntype = kw.get('mode', 0), kw.get('alntype', 0)
+    L = kw['L']
+    subst = kw.get('subst')
+    if subst is None:
+        subst = [[kw.get('match', 1.) if i == j else kw.get('mismatch', 0.) for i in range(L)] for j in range(L)]
+    go, ge = float(kw.get('go', 0.)), float(kw.get('ge', 0.))
+    dr = kw.get('diag_range')
+    drs = [None] * len(pairs) if mode == 0 else ([dr] * len(pairs) if not hasattr(dr[0], '__len__') else list(dr))
+    shapes = [(len(o), len(m)) + (tuple(d) if d is not None else ()) for (o, m), d in zip(pairs, drs)]
+    plan = plan_only(shapes, alnmode=mode, alntype=alntype, alphabet_len=L, subst_scores=subst, go_score=go, ge_score=ge,
+                     flags=flags)
+    name = plan['kernel']
+    if plan['tiled']:
+        raise NotEmulated('the tiled kernel (%s) is not emulated' % name)
+    f = float(1 << plan['scale_shift'])          # dyadic scaling: the kernels hold every score times 2^shift
+    S = (np.asarray(subst, np.float64) * f).tolist()
+    base = dict(mode=mode, alntype=alntype, L=L, subst=S, go=go * f, ge=ge * f)
+    out, seen = [], {}
+    for (o, m), d in zip(pairs, drs):
+        key = (np.asarray(o, np.int32).tobytes(), np.asarray(m, np.int32).tobytes(), d)
+        if key in seen:                          # (copies of a pair, as batches that fill the chip hold: solved once)
+            out.append(dict(seen[key]))
+            continue
+        if plan['strips']:
+            if plan['strips'] != len(pairs):
+                raise NotEmulated('a batch split between the strips and other kernels (%s)' % name)
+            simple = all(S[i][j] == S[0][0 if i == j else 1] for i in range(L) for j in range(L)) if L > 1 else True
+            byte_rows = L <= 4 and all(v == int(v) and -128 <= v <= 127 for row in S for v in row) and \
+                os.environ.get('PWLIB_STRIP_NO_BYTE_ROWS', '') in ('', '0')
+            r = solve_strip(o, m, alntype=alntype, match=S[0][0], mismatch=S[0][1] if L > 1 else S[0][0], go=go * f,
+                            ge=ge * f, byte_rows=byte_rows, subst=None if simple else S)
+        else:
+            g = _KERNEL.match(name)
+            if not g:
+                raise NotEmulated('unknown kernel name %r' % name)
+            kind, bk = g.group(1), int(g.group(3))
+            waves = int(re.search(r'x (\d+) wavefronts', name).group(1)) if 'wavefronts' in name else 1
+            ekw = dict(base, diag_range=d, bk=bk, waves=waves, product_variant=True)
+            if kind.startswith('16'):
+                x4 = plan['packed_rule'] == 3
+                seg = kind == '16' and g.group(4) == 'true'
+                ekw.update(packed16=(4 if x4 else 1) if seg else (3 if x4 else 2), matrix=plan['matrix'])
+            else:
+                ekw.update(use_double=plan['score_dtype'] == 'f64')
+            r = solve(o, m, **ekw)
+        if r['score'] is not None:
+            r['score'] = r['score'] / f
+        seen[key] = r
+        out.append(dict(r))
+    return plan, out

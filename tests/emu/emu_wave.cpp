@@ -195,6 +195,14 @@ void run_fill(const pw::FillParams<T>& a, const pw::PairDesc& pd, const T* subst
 
 int g_packed_mode = 0;
 bool g_packed_mat = false;
+// the packed kernels' matrix form: -1 as the scores need it (a non-simple matrix), 0 never, 1 always (match / mismatch
+// scores over 2 .. 4 letters are such a matrix too: the form the planner gives config 2 and every positive mismatch)
+int g_packed_matrix = -1;
+extern "C" void emu_set_packed_matrix(int v) { g_packed_matrix = v < 0 ? -1 : (v ? 1 : 0); }
+// the 32-bit / f64 kernel variant as the product picks it (pwlib_api.cpp, batch_plan): a substitution matrix runs on the
+// fast variants (TAB), the generic one only for go > 0 or the score plane; off: every matrix on the generic variant
+int g_product_variant = 0;
+extern "C" void emu_set_product_variant(int v) { g_product_variant = v != 0; }
 
 template <typename T, int BK> struct Run16 {
   static bool go(const pw::FillParams<T>&, const pw::PairDesc&) { return false; }
@@ -304,23 +312,17 @@ int solve_T(int mode, int type, const int* origin, int X, const int* mutant, int
   const pw::ScoreSummary ss = pw::summarise_scores(L, subst, go, ge, false);
   const bool simple = ss.simple;
   const bool x4mode = packed16 == 3 || packed16 == 4;
-  const bool mat16 = packed16 && !simple && pw::packed_matrix_bytes_ok(ss, L, x4mode) && sizeof(T) == 4;
-  const int generic = force_generic || (!simple && !mat16) || go > 0 || hdump != nullptr;
+  const bool want_mat = g_packed_matrix < 0 ? !simple : g_packed_matrix > 0;
+  const bool mat16 = packed16 && want_mat && pw::packed_matrix_bytes_ok(ss, L, x4mode) && sizeof(T) == 4;
+  if (packed16 && g_packed_matrix > 0 && !mat16) return -5;      // a matrix form that does not exist for these scores
+  const int generic = force_generic || (!simple && !mat16 && !g_product_variant) || go > 0 || hdump != nullptr;
   const int bany = pl.brule == pw::BRULE_ANY;
   const int track = pl.endrule == pw::END_STD_LOCAL || pl.endrule == pw::END_BANDED_LOCAL;
   const int rule = pw::packed_rule(pl.brule, pl.endrule);
   const int use16 = packed16 && !generic && rule >= 0 && !(mat16 && rule > 2) && bk % 4 == 0 && sizeof(T) == 4;
   g_packed_mode = packed16;
   g_packed_mat = mat16;
-  if (mat16) {
-    const int scale = x4mode ? 4 : 1;
-    for (int o = 0; o < 4; o++) {
-      uint32_t row = 0;
-      for (int m = 0; m < 4; m++) if (o < L && m < L) row |= (uint32_t)(scale * (int)(subst[o * L + m] - ss.smin)) << (8 * m);
-      a.mat_rows[o] = row;
-    }
-    a.mat_bias = scale * (int)(-ss.smin);
-  }
+  if (mat16) pw::packed_matrix_rows(subst, L, x4mode, a.mat_rows, &a.mat_bias);
   if (packed16 && !generic && !use16) return -5;                   // the caller asked for a packed kernel that does not exist
   if (use16 && g_waves == 1) pd.nl = (pl.ndiag + bk - 1) / bk;
   switch (bk) {

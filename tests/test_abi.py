@@ -111,9 +111,23 @@ def test_unsupported_problems_fail_loudly(capfd):
     assert lib.dptable_init(C.byref(P.table)) == 0
     assert P.table.num_rows == 100001 and P.table.row_lens[5] == 100001 and not P.table.cells[5]
     lib.dptable_free(C.byref(P.table))
+    # scores that reach the reference's -INT_MAX floor of gap candidates and end cells (_pw_internals.c:267, :320, :381) are
+    # refused: 50 x 45 (X + Y + 2 = 97) where one gap step lowers a score by -(ge + min(go, 0)) = 22139006 is accepted,
+    # 22139007 is not; begin-anywhere types are never affected (every cell holds the begin candidate 0).  (dptable_init
+    # sees the gap scores; the substitution scores of a one-diagonal band are the planner's: test_range_edges.py.)
+    import numpy as np
+    o = np.random.default_rng(97).integers(0, 4, 50).tolist()
+    m = o[:20] + o[25:]
+    for go, mode, alntype, rc in ((-22139005., 0, 0, 0), (-22139006., 0, 0, -1), (-3e9, 0, 0, -1), (-3e9, 1, 0, -1),
+                                  (-3e9, 0, 1, 0), (-3e9, 0, 3, 0), (-3e9, 1, 1, 0)):
+        P = R.Problem(o, m, L=4, mode=mode, alntype=alntype, match=1., mismatch=-1., go=go, ge=-1.,
+                      diag_range=(-8, 8) if mode == 1 else None)
+        assert lib.dptable_init(C.byref(P.table)) == rc, (go, mode, alntype)
+        if rc == 0:
+            lib.dptable_free(C.byref(P.table))
     C.CDLL(None).fflush(None)
     err = capfd.readouterr().err
-    assert 'max_new_mins' in err and 'no CPU fallback' in err
+    assert 'max_new_mins' in err and 'no CPU fallback' in err and 'INT_MAX' in err
 
 
 def test_product_does_not_import_the_oracle():
