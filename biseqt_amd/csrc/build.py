@@ -64,7 +64,7 @@ F64_FLAGS = {'f64': ['-fno-honor-nans'] + os.environ.get('PW_F64_EXTRA_CXXFLAGS'
 FILL_EXTRA = {('f64', 8): ['-mllvm', '-amdgpu-sched-strategy=max-ilp']}
 # objects whose kernels get a fingerprint in biseqt_amd/pwlib/kernel_hashes.json (config 2's and config 3's fill kernels)
 HASHED_OBJECTS = ('pw_fill16_bk8_r3_mat.o', 'pw_fill16_bk8_r3.o', 'pw_fill16_bk8_r0.o', 'pw_fill_i32_bk8.o', 'pw_fill_f64_bk8.o', 'pw_strip.o')
-HEADERS = ['pw_types.h', 'pw_wave.h', 'pw_strip.h', 'pw_plan.h', 'pw_model.h', 'pw_launch.h', 'pw_device.h']
+HEADERS = ['pw_types.h', 'pw_wave.h', 'pw_strip.h', 'pw_plan.h', 'pw_model.h', 'pw_launch.h', 'pw_device.h', 'pw_hip_host.h']
 
 
 def _jobs():

@@ -20,33 +20,16 @@
 #include <rocprim/rocprim.hpp>
 
 #include "../../include/pw_overlap.h"
+#include "pw_hip_host.h"
 
 namespace {
 
 thread_local std::string g_err;
 thread_local double g_ms = 0.0;
 void set_err(const std::string& s) { g_err = s; }
-#define OV_CHECK(call)                                                                       \
-  do {                                                                                       \
-    hipError_t e_ = (call);                                                                  \
-    if (e_ != hipSuccess) {                                                                  \
-      set_err(std::string(#call) + ": " + hipGetErrorString(e_));                            \
-      return -1;                                                                             \
-    }                                                                                        \
-  } while (0)
+#define CHECK(call) PW_HIP_CHECK(set_err, call)
 
 struct DPair { uint64_t s_off, t_off; int32_t s_len, t_len; uint64_t hbase; };   // hbase: start of its histogram
-
-__device__ __forceinline__ int64_t ub_u64(const uint64_t* __restrict__ a, int64_t n, uint64_t key) {   // first > key
-  int64_t lo = 0, hi = n;
-  while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (a[mid] <= key) lo = mid + 1; else hi = mid; }
-  return lo;
-}
-__device__ __forceinline__ int64_t lb_u64(const uint64_t* __restrict__ a, int64_t n, uint64_t key) {   // first >= key
-  int64_t lo = 0, hi = n;
-  while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (a[mid] < key) lo = mid + 1; else hi = mid; }
-  return lo;
-}
 
 // side 0: S reads, side 1: T reads.  start[p] = index of pair p's first k-mer on this side (start[n] = total).
 __global__ __launch_bounds__(256) void k_enc_batch(const uint8_t* __restrict__ arena, const DPair* __restrict__ pairs,
@@ -54,7 +37,7 @@ __global__ __launch_bounds__(256) void k_enc_batch(const uint8_t* __restrict__ a
                                                    int k, int L, int kbits, uint64_t* __restrict__ keys, uint32_t* __restrict__ pos) {
   const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (g >= total) return;
-  const int64_t p = ub_u64(start, npairs + 1, (uint64_t)g) - 1;
+  const int64_t p = upper_bound_dev<uint64_t>(start, npairs + 1, (uint64_t)g) - 1;
   const DPair pr = pairs[p];
   const uint32_t q = (uint32_t)(g - (int64_t)start[p]);
   const uint8_t* __restrict__ s = arena + (side ? pr.t_off : pr.s_off) + q;
@@ -72,9 +55,9 @@ __global__ __launch_bounds__(256) void k_join_hist(const uint64_t* __restrict__ 
   const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (e >= ns) return;
   const uint64_t key = ks[e];
-  const int64_t lo = lb_u64(kt, nt, key);
+  const int64_t lo = lower_bound_dev<uint64_t>(kt, nt, key);
   if (lo >= nt || kt[lo] != key) return;
-  const int64_t hi = ub_u64(kt, nt, key);
+  const int64_t hi = upper_bound_dev<uint64_t>(kt, nt, key);
   const int64_t p = (int64_t)(key >> kbits);
   const DPair pr = pairs[p];
   const int i = (int)ps[e];
@@ -245,7 +228,7 @@ __global__ __launch_bounds__(256) void k_first_d(const uint32_t* __restrict__ fi
   if (p >= npairs) return;
   const uint32_t fe = first_e[p];
   if (fe == 0xffffffffu) { d_first[p] = 0; return; }
-  const int64_t lo = lb_u64(kt, nt, ks[fe]);
+  const int64_t lo = lower_bound_dev<uint64_t>(kt, nt, ks[fe]);
   d_first[p] = (int)ps[fe] - (int)pt[lo];
 }
 
@@ -256,7 +239,7 @@ __global__ __launch_bounds__(256) void k_enc_reads(const uint8_t* __restrict__ a
                                                    uint64_t* __restrict__ keys, uint64_t* __restrict__ vals) {
   const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (g >= total) return;
-  const int64_t r = ub_u64(rstart, nreads + 1, (uint64_t)g) - 1;
+  const int64_t r = upper_bound_dev<uint64_t>(rstart, nreads + 1, (uint64_t)g) - 1;
   const uint32_t q = (uint32_t)(g - (int64_t)rstart[r]);
   const uint8_t* __restrict__ s = arena + roff[r] + q;
   uint64_t v = 0;
@@ -272,9 +255,9 @@ __global__ __launch_bounds__(256) void k_self_count(const uint64_t* __restrict__
   if (e >= n) return;
   // multi-GPU: the pairs (a, b), a < b, are dealt round-robin by a; every rank joins only its own share
   if ((int)((vals[e] >> 32) % (uint64_t)shard_world) != shard_rank) { fs[e] = (uint32_t)e; cnt[e] = 0; return; }
-  const int64_t hi = ub_u64(keys, n, keys[e]);
+  const int64_t hi = upper_bound_dev<uint64_t>(keys, n, keys[e]);
   const uint64_t next_read = ((vals[e] >> 32) + 1) << 32;
-  const int64_t f = e + 1 + lb_u64(vals + e + 1, hi - e - 1, next_read);
+  const int64_t f = e + 1 + lower_bound_dev<uint64_t>(vals + e + 1, hi - e - 1, next_read);
   fs[e] = (uint32_t)f;
   cnt[e] = (uint64_t)(hi - f);
 }
@@ -285,7 +268,7 @@ __global__ __launch_bounds__(256) void k_self_expand(const uint64_t* __restrict_
                                                      uint64_t nreads, uint64_t* __restrict__ pkey, int32_t* __restrict__ dval) {
   const int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (o >= nseeds) return;
-  const int64_t e = ub_u64(off, n, (uint64_t)o) - 1;
+  const int64_t e = upper_bound_dev<uint64_t>(off, n, (uint64_t)o) - 1;
   const int64_t f = (int64_t)fs[e] + (o - (int64_t)off[e]);
   const uint64_t va = vals[e], vb = vals[f];
   pkey[o] = (va >> 32) * nreads + (vb >> 32);
@@ -321,7 +304,7 @@ __global__ __launch_bounds__(256) void k_scatter_hist(const int32_t* __restrict_
                                                       int sparse_max) {
   const int64_t o = s0 + (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (o >= s1) return;
-  const int64_t u = u0 + ub_u64(soff + u0, u1 - u0, (uint64_t)o) - 1;
+  const int64_t u = u0 + upper_bound_dev<uint64_t>(soff + u0, u1 - u0, (uint64_t)o) - 1;
   if ((u + 1 < u1 ? soff[u + 1] : (uint64_t)s1) - soff[u] <= (uint64_t)sparse_max) return;     // no histogram for sparse pairs
   const DPair pr = pairs[u];
   atomicAdd(&hist[pr.hbase - hchunk0 + (uint64_t)(dval[o] + pr.t_len)], 1u);
@@ -512,18 +495,6 @@ __global__ __launch_bounds__(256) void k_band_medium(const DPair* __restrict__ p
   }
 }
 
-struct Ev {
-  hipEvent_t e = nullptr;
-  int make() { OV_CHECK(hipEventCreate(&e)); return 0; }
-  ~Ev() { if (e) (void)hipEventDestroy(e); }
-};
-
-struct Buf {
-  void* p = nullptr;
-  int alloc(size_t bytes) { OV_CHECK(hipMalloc(&p, bytes ? bytes : 16)); return 0; }
-  ~Buf() { if (p) (void)hipFree(p); }
-};
-
 int run_chunk(const uint8_t* d_arena, const pw_read_pair* pairs, int64_t n, int L, int k, int kbits, BandConst bc,
               pw_overlap_band* out, hipEvent_t ev0, hipEvent_t ev1, float* ms) {
   std::vector<DPair> hp((size_t)n);
@@ -537,39 +508,37 @@ int run_chunk(const uint8_t* d_arena, const pw_read_pair* pairs, int64_t n, int 
     ct += pairs[p].t_len >= k ? (uint64_t)(pairs[p].t_len - k + 1) : 0;
   }
   ss[(size_t)n] = cs; ts[(size_t)n] = ct;
-  Buf dp, dss, dts, kin, pin, ksb, psb, ktb, ptb, hist, rows, first, dout, tmp, dlist;
-  if (dp.alloc(sizeof(DPair) * (size_t)n) || dss.alloc(8 * ((size_t)n + 1)) || dts.alloc(8 * ((size_t)n + 1)) ||
-      kin.alloc(8 * (size_t)std::max(cs, ct)) || pin.alloc(4 * (size_t)std::max(cs, ct)) || ksb.alloc(8 * (size_t)cs) ||
-      psb.alloc(4 * (size_t)cs) || ktb.alloc(8 * (size_t)ct) || ptb.alloc(4 * (size_t)ct) || hist.alloc(4 * (size_t)hb) ||
-      rows.alloc(8 * (size_t)n) || first.alloc(4 * (size_t)n) || dout.alloc(sizeof(pw_overlap_band) * (size_t)n) ||
-      dlist.alloc(256 * (size_t)n)) return -1;
-  OV_CHECK(hipMemcpy(dp.p, hp.data(), sizeof(DPair) * (size_t)n, hipMemcpyHostToDevice));
-  OV_CHECK(hipMemcpy(dss.p, ss.data(), 8 * ((size_t)n + 1), hipMemcpyHostToDevice));
-  OV_CHECK(hipMemcpy(dts.p, ts.data(), 8 * ((size_t)n + 1), hipMemcpyHostToDevice));
-  OV_CHECK(hipEventRecord(ev0, nullptr));
-  OV_CHECK(hipMemsetAsync(hist.p, 0, 4 * (size_t)hb, nullptr));
-  OV_CHECK(hipMemsetAsync(rows.p, 0, 8 * (size_t)n, nullptr));
-  OV_CHECK(hipMemsetAsync(first.p, 0xff, 4 * (size_t)n, nullptr));
+  DeviceBuffer dp, dss, dts, kin, pin, ksb, psb, ktb, ptb, hist, rows, first, dout, tmp, dlist;
+  CHECK(dp.ensure(sizeof(DPair) * (size_t)n)); CHECK(dss.ensure(8 * ((size_t)n + 1))); CHECK(dts.ensure(8 * ((size_t)n + 1)));
+  CHECK(kin.ensure(8 * (size_t)std::max(cs, ct))); CHECK(pin.ensure(4 * (size_t)std::max(cs, ct)));
+  CHECK(ksb.ensure(8 * (size_t)cs)); CHECK(psb.ensure(4 * (size_t)cs)); CHECK(ktb.ensure(8 * (size_t)ct)); CHECK(ptb.ensure(4 * (size_t)ct));
+  CHECK(hist.ensure(4 * (size_t)hb)); CHECK(rows.ensure(8 * (size_t)n)); CHECK(first.ensure(4 * (size_t)n));
+  CHECK(dout.ensure(sizeof(pw_overlap_band) * (size_t)n)); CHECK(dlist.ensure(256 * (size_t)n));
+  CHECK(hipMemcpy(dp.p, hp.data(), sizeof(DPair) * (size_t)n, hipMemcpyHostToDevice));
+  CHECK(hipMemcpy(dss.p, ss.data(), 8 * ((size_t)n + 1), hipMemcpyHostToDevice));
+  CHECK(hipMemcpy(dts.p, ts.data(), 8 * ((size_t)n + 1), hipMemcpyHostToDevice));
+  CHECK(hipEventRecord(ev0, nullptr));
+  CHECK(hipMemsetAsync(hist.p, 0, 4 * (size_t)hb, nullptr));
+  CHECK(hipMemsetAsync(rows.p, 0, 8 * (size_t)n, nullptr));
+  CHECK(hipMemsetAsync(first.p, 0xff, 4 * (size_t)n, nullptr));
   int pbits = 1; while (((uint64_t)n >> pbits) != 0) pbits++;
-  size_t tb = 0, tb2 = 0;
   for (int side = 0; side < 2; side++) {
     const uint64_t tot = side ? ct : cs;
     if (tot == 0) continue;
     hipLaunchKernelGGL(k_enc_batch, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, nullptr, d_arena, (const DPair*)dp.p,
                        (const uint64_t*)(side ? dts.p : dss.p), n, (int64_t)tot, side, k, L, kbits, (uint64_t*)kin.p, (uint32_t*)pin.p);
     uint64_t* ko = (uint64_t*)(side ? ktb.p : ksb.p); uint32_t* po = (uint32_t*)(side ? ptb.p : psb.p);
-    OV_CHECK(rocprim::radix_sort_pairs(nullptr, tb2, (const uint64_t*)kin.p, ko, (const uint32_t*)pin.p, po, (size_t)tot, 0u,
-                                       (unsigned)(kbits + pbits), (hipStream_t) nullptr));
-    if (tb2 > tb) { if (tmp.p) { (void)hipFree(tmp.p); tmp.p = nullptr; } if (tmp.alloc(tb2)) return -1; tb = tb2; }
-    OV_CHECK(rocprim::radix_sort_pairs(tmp.p, tb2, (const uint64_t*)kin.p, ko, (const uint32_t*)pin.p, po, (size_t)tot, 0u,
-                                       (unsigned)(kbits + pbits), (hipStream_t) nullptr));
+    CHECK(rocprim_run(tmp, [&](void* t, size_t& b) {
+      return rocprim::radix_sort_pairs(t, b, (const uint64_t*)kin.p, ko, (const uint32_t*)pin.p, po, (size_t)tot, 0u,
+                                       (unsigned)(kbits + pbits), (hipStream_t) nullptr);
+    }));
   }
   if (cs && ct)
     hipLaunchKernelGGL(k_join_hist, dim3((unsigned)((cs + 255) / 256)), dim3(256), 0, nullptr, (const uint64_t*)ksb.p,
                        (const uint32_t*)psb.p, (int64_t)cs, (const uint64_t*)ktb.p, (const uint32_t*)ptb.p, (int64_t)ct,
                        (const DPair*)dp.p, kbits, (uint32_t*)hist.p, (unsigned long long*)rows.p, (uint32_t*)first.p, (int32_t*)dlist.p);
-  Buf dfirst;
-  if (dfirst.alloc(4 * (size_t)n)) return -1;
+  DeviceBuffer dfirst;
+  CHECK(dfirst.ensure(4 * (size_t)n));
   hipLaunchKernelGGL(k_first_d, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, (const uint32_t*)first.p, n,
                      (const uint64_t*)ksb.p, (const uint32_t*)psb.p, (const uint64_t*)ktb.p, (const uint32_t*)ptb.p, (int64_t)ct,
                      (int32_t*)dfirst.p);
@@ -578,11 +547,11 @@ int run_chunk(const uint8_t* d_arena, const pw_read_pair* pairs, int64_t n, int 
                      (pw_overlap_band*)dout.p);
   hipLaunchKernelGGL(k_band_select, dim3((unsigned)n), dim3(256), 0, nullptr, (const DPair*)dp.p, (uint32_t*)hist.p,
                      (const unsigned long long*)rows.p, (const int32_t*)dfirst.p, (uint64_t)0, kSmallPair, bc, (pw_overlap_band*)dout.p);
-  OV_CHECK(hipEventRecord(ev1, nullptr));
-  OV_CHECK(hipMemcpy(out, dout.p, sizeof(pw_overlap_band) * (size_t)n, hipMemcpyDeviceToHost));
-  OV_CHECK(hipGetLastError());
+  CHECK(hipEventRecord(ev1, nullptr));
+  CHECK(hipMemcpy(out, dout.p, sizeof(pw_overlap_band) * (size_t)n, hipMemcpyDeviceToHost));
+  CHECK(hipGetLastError());
   float t = 0.f;
-  OV_CHECK(hipEventElapsedTime(&t, ev0, ev1));
+  CHECK(hipEventElapsedTime(&t, ev0, ev1));
   *ms += t;
   return 0;
 }
@@ -597,64 +566,56 @@ int run_all_pairs(const uint8_t* d_arena, const uint64_t* read_off, const int32_
   *n_out = 0;
   if (K == 0) return 0;
   if (K >= (1ull << 32)) { set_err("more than 2^32 k-mers in one index: split the read set"); return -1; }
-  Ev e0, e1;
-  if (e0.make() || e1.make()) return -1;
-  const hipEvent_t ev0 = e0.e, ev1 = e1.e;
-  Buf droff, drlen, drstart, kin, vin, ks, vs, fs, cnt, off, scal, tmp;
-  if (droff.alloc(8 * (size_t)R) || drlen.alloc(4 * (size_t)R) || drstart.alloc(8 * ((size_t)R + 1)) || kin.alloc(8 * (size_t)K) ||
-      vin.alloc(8 * (size_t)K) || ks.alloc(8 * (size_t)K) || vs.alloc(8 * (size_t)K) || fs.alloc(4 * (size_t)K) ||
-      cnt.alloc(8 * (size_t)K) || off.alloc(8 * (size_t)K) || scal.alloc(64)) return -1;
-  OV_CHECK(hipMemcpy(droff.p, read_off, 8 * (size_t)R, hipMemcpyHostToDevice));
-  OV_CHECK(hipMemcpy(drlen.p, read_len, 4 * (size_t)R, hipMemcpyHostToDevice));
-  OV_CHECK(hipMemcpy(drstart.p, rstart.data(), 8 * ((size_t)R + 1), hipMemcpyHostToDevice));
-  OV_CHECK(hipEventRecord(ev0, nullptr));
+  DeviceEvent ev0, ev1;
+  CHECK(ev0.create()); CHECK(ev1.create());
+  DeviceBuffer droff, drlen, drstart, kin, vin, ks, vs, fs, cnt, off, scal, tmp;
+  CHECK(droff.ensure(8 * (size_t)R)); CHECK(drlen.ensure(4 * (size_t)R)); CHECK(drstart.ensure(8 * ((size_t)R + 1)));
+  CHECK(kin.ensure(8 * (size_t)K)); CHECK(vin.ensure(8 * (size_t)K)); CHECK(ks.ensure(8 * (size_t)K)); CHECK(vs.ensure(8 * (size_t)K));
+  CHECK(fs.ensure(4 * (size_t)K)); CHECK(cnt.ensure(8 * (size_t)K)); CHECK(off.ensure(8 * (size_t)K)); CHECK(scal.ensure(64));
+  CHECK(hipMemcpy(droff.p, read_off, 8 * (size_t)R, hipMemcpyHostToDevice));
+  CHECK(hipMemcpy(drlen.p, read_len, 4 * (size_t)R, hipMemcpyHostToDevice));
+  CHECK(hipMemcpy(drstart.p, rstart.data(), 8 * ((size_t)R + 1), hipMemcpyHostToDevice));
+  CHECK(hipEventRecord(ev0.e, nullptr));
   const dim3 blk(256), gK((unsigned)((K + 255) / 256));
   hipLaunchKernelGGL(k_enc_reads, gK, blk, 0, nullptr, d_arena, (const uint64_t*)droff.p, (const uint64_t*)drstart.p, R, (int64_t)K, k, L,
                      (uint64_t*)kin.p, (uint64_t*)vin.p);
-  size_t tb = 0;
-  OV_CHECK(rocprim::radix_sort_pairs(nullptr, tb, (const uint64_t*)kin.p, (uint64_t*)ks.p, (const uint64_t*)vin.p, (uint64_t*)vs.p, (size_t)K,
-                                     0u, (unsigned)kbits, (hipStream_t) nullptr));
-  if (tmp.alloc(tb)) return -1;
-  OV_CHECK(rocprim::radix_sort_pairs(tmp.p, tb, (const uint64_t*)kin.p, (uint64_t*)ks.p, (const uint64_t*)vin.p, (uint64_t*)vs.p, (size_t)K,
-                                     0u, (unsigned)kbits, (hipStream_t) nullptr));
+  CHECK(rocprim_run(tmp, [&](void* t, size_t& b) {
+    return rocprim::radix_sort_pairs(t, b, (const uint64_t*)kin.p, (uint64_t*)ks.p, (const uint64_t*)vin.p, (uint64_t*)vs.p, (size_t)K,
+                                     0u, (unsigned)kbits, (hipStream_t) nullptr);
+  }));
   hipLaunchKernelGGL(k_self_count, gK, blk, 0, nullptr, (const uint64_t*)ks.p, (const uint64_t*)vs.p, (int64_t)K, shard_rank, shard_world,
                      (uint32_t*)fs.p, (uint64_t*)cnt.p);
-  size_t tb2 = 0;
-  OV_CHECK(rocprim::exclusive_scan(nullptr, tb2, (const uint64_t*)cnt.p, (uint64_t*)off.p, (uint64_t)0, (size_t)K, rocprim::plus<uint64_t>(), (hipStream_t) nullptr));
-  Buf tmp2;
-  if (tmp2.alloc(tb2)) return -1;
-  OV_CHECK(rocprim::exclusive_scan(tmp2.p, tb2, (const uint64_t*)cnt.p, (uint64_t*)off.p, (uint64_t)0, (size_t)K, rocprim::plus<uint64_t>(), (hipStream_t) nullptr));
+  DeviceBuffer tmp2;
+  CHECK(rocprim_run(tmp2, [&](void* t, size_t& b) {
+    return rocprim::exclusive_scan(t, b, (const uint64_t*)cnt.p, (uint64_t*)off.p, (uint64_t)0, (size_t)K, rocprim::plus<uint64_t>(), (hipStream_t) nullptr);
+  }));
   uint64_t last_off = 0, last_cnt = 0;
-  OV_CHECK(hipMemcpy(&last_off, (uint64_t*)off.p + (K - 1), 8, hipMemcpyDeviceToHost));
-  OV_CHECK(hipMemcpy(&last_cnt, (uint64_t*)cnt.p + (K - 1), 8, hipMemcpyDeviceToHost));
+  CHECK(hipMemcpy(&last_off, (uint64_t*)off.p + (K - 1), 8, hipMemcpyDeviceToHost));
+  CHECK(hipMemcpy(&last_cnt, (uint64_t*)cnt.p + (K - 1), 8, hipMemcpyDeviceToHost));
   const uint64_t NS = last_off + last_cnt;
   if (NS == 0) return 0;
   if (NS >= (1ull << 32)) { set_err("more than 2^32 seeds between the reads: use a longer word"); return -1; }
   // seeds -> (pair key, d), stably sorted by the pair key
-  Buf pk_in, dv_in, pk, dv;
-  if (pk_in.alloc(8 * (size_t)NS) || dv_in.alloc(4 * (size_t)NS) || pk.alloc(8 * (size_t)NS) || dv.alloc(4 * (size_t)NS)) return -1;
+  DeviceBuffer pk_in, dv_in, pk, dv;
+  CHECK(pk_in.ensure(8 * (size_t)NS)); CHECK(dv_in.ensure(4 * (size_t)NS)); CHECK(pk.ensure(8 * (size_t)NS)); CHECK(dv.ensure(4 * (size_t)NS));
   hipLaunchKernelGGL(k_self_expand, dim3((unsigned)((NS + 255) / 256)), blk, 0, nullptr, (const uint64_t*)off.p, (int64_t)K, (int64_t)NS,
                      (const uint64_t*)vs.p, (const uint32_t*)fs.p, (uint64_t)R, (uint64_t*)pk_in.p, (int32_t*)dv_in.p);
   int pbits = 1; while ((((uint64_t)R * (uint64_t)R) >> pbits) != 0) pbits++;
-  size_t tb3 = 0;
-  OV_CHECK(rocprim::radix_sort_pairs(nullptr, tb3, (const uint64_t*)pk_in.p, (uint64_t*)pk.p, (const int32_t*)dv_in.p, (int32_t*)dv.p, (size_t)NS,
-                                     0u, (unsigned)pbits, (hipStream_t) nullptr));
-  Buf tmp3;
-  if (tmp3.alloc(tb3)) return -1;
-  OV_CHECK(rocprim::radix_sort_pairs(tmp3.p, tb3, (const uint64_t*)pk_in.p, (uint64_t*)pk.p, (const int32_t*)dv_in.p, (int32_t*)dv.p, (size_t)NS,
-                                     0u, (unsigned)pbits, (hipStream_t) nullptr));
+  DeviceBuffer tmp3;
+  CHECK(rocprim_run(tmp3, [&](void* t, size_t& b) {
+    return rocprim::radix_sort_pairs(t, b, (const uint64_t*)pk_in.p, (uint64_t*)pk.p, (const int32_t*)dv_in.p, (int32_t*)dv.p, (size_t)NS,
+                                     0u, (unsigned)pbits, (hipStream_t) nullptr);
+  }));
   // unique pair keys with their seed counts
-  Buf uk, uc, nruns;
-  if (uk.alloc(8 * (size_t)NS) || uc.alloc(8 * (size_t)NS) || nruns.alloc(16)) return -1;
-  size_t tb4 = 0;
-  OV_CHECK(rocprim::run_length_encode(nullptr, tb4, (const uint64_t*)pk.p, (unsigned int)NS, (uint64_t*)uk.p, (unsigned long long*)uc.p,
-                                      (unsigned long long*)nruns.p, (hipStream_t) nullptr));
-  Buf tmp4;
-  if (tmp4.alloc(tb4)) return -1;
-  OV_CHECK(rocprim::run_length_encode(tmp4.p, tb4, (const uint64_t*)pk.p, (unsigned int)NS, (uint64_t*)uk.p, (unsigned long long*)uc.p,
-                                      (unsigned long long*)nruns.p, (hipStream_t) nullptr));
+  DeviceBuffer uk, uc, nruns;
+  CHECK(uk.ensure(8 * (size_t)NS)); CHECK(uc.ensure(8 * (size_t)NS)); CHECK(nruns.ensure(16));
+  DeviceBuffer tmp4;
+  CHECK(rocprim_run(tmp4, [&](void* t, size_t& b) {
+    return rocprim::run_length_encode(t, b, (const uint64_t*)pk.p, (unsigned int)NS, (uint64_t*)uk.p, (unsigned long long*)uc.p,
+                                      (unsigned long long*)nruns.p, (hipStream_t) nullptr);
+  }));
   unsigned long long NP = 0;
-  OV_CHECK(hipMemcpy(&NP, nruns.p, 8, hipMemcpyDeviceToHost));
+  CHECK(hipMemcpy(&NP, nruns.p, 8, hipMemcpyDeviceToHost));
   if ((int64_t)NP > max_pairs) {
     char msg[160];
     snprintf(msg, sizeof msg, "%llu pairs of reads share a seed (capacity %lld): raise max_pairs or the word length", NP, (long long)max_pairs);
@@ -662,18 +623,21 @@ int run_all_pairs(const uint8_t* d_arena, const uint64_t* read_off, const int32_
     return -1;
   }
   // seed offsets and histogram bases of the candidate pairs
-  Buf soff, hsize, hbase, dpairs, dfirst, dpa, dpb, dout;
-  if (soff.alloc(8 * (size_t)NP) || hsize.alloc(8 * (size_t)NP) || hbase.alloc(8 * (size_t)NP) || dpairs.alloc(sizeof(DPair) * (size_t)NP) ||
-      dfirst.alloc(4 * (size_t)NP) || dpa.alloc(4 * (size_t)NP) || dpb.alloc(4 * (size_t)NP) || dout.alloc(sizeof(pw_overlap_band) * (size_t)NP)) return -1;
+  DeviceBuffer soff, hsize, hbase, dpairs, dfirst, dpa, dpb, dout;
+  CHECK(soff.ensure(8 * (size_t)NP)); CHECK(hsize.ensure(8 * (size_t)NP)); CHECK(hbase.ensure(8 * (size_t)NP));
+  CHECK(dpairs.ensure(sizeof(DPair) * (size_t)NP)); CHECK(dfirst.ensure(4 * (size_t)NP)); CHECK(dpa.ensure(4 * (size_t)NP));
+  CHECK(dpb.ensure(4 * (size_t)NP)); CHECK(dout.ensure(sizeof(pw_overlap_band) * (size_t)NP));
   const dim3 gP((unsigned)((NP + 255) / 256));
-  size_t tb5 = 0;
-  OV_CHECK(rocprim::exclusive_scan(nullptr, tb5, (const uint64_t*)uc.p, (uint64_t*)soff.p, (uint64_t)0, (size_t)NP, rocprim::plus<uint64_t>(), (hipStream_t) nullptr));
-  Buf tmp5;
-  if (tmp5.alloc(tb5)) return -1;
-  OV_CHECK(rocprim::exclusive_scan(tmp5.p, tb5, (const uint64_t*)uc.p, (uint64_t*)soff.p, (uint64_t)0, (size_t)NP, rocprim::plus<uint64_t>(), (hipStream_t) nullptr));
+  DeviceBuffer tmp5;
+  auto scan_np = [&](const DeviceBuffer& in, DeviceBuffer& res) {
+    return rocprim_run(tmp5, [&](void* t, size_t& b) {
+      return rocprim::exclusive_scan(t, b, (const uint64_t*)in.p, (uint64_t*)res.p, (uint64_t)0, (size_t)NP, rocprim::plus<uint64_t>(), (hipStream_t) nullptr);
+    });
+  };
+  CHECK(scan_np(uc, soff));
   hipLaunchKernelGGL(k_pair_hsize, gP, blk, 0, nullptr, (const uint64_t*)uk.p, (const unsigned long long*)uc.p, (int64_t)NP, (uint64_t)R,
                      (const int32_t*)drlen.p, (uint64_t*)hsize.p, kMediumPair);
-  OV_CHECK(rocprim::exclusive_scan(tmp5.p, tb5, (const uint64_t*)hsize.p, (uint64_t*)hbase.p, (uint64_t)0, (size_t)NP, rocprim::plus<uint64_t>(), (hipStream_t) nullptr));
+  CHECK(scan_np(hsize, hbase));
   hipLaunchKernelGGL(k_cand_pairs, gP, blk, 0, nullptr, (const uint64_t*)uk.p, (const uint64_t*)soff.p, (const int32_t*)dv.p, (int64_t)NP, (uint64_t)R,
                      (const uint64_t*)droff.p, (const int32_t*)drlen.p, (const uint64_t*)hbase.p, (DPair*)dpairs.p, (int32_t*)dfirst.p,
                      (int32_t*)dpa.p, (int32_t*)dpb.p);
@@ -681,39 +645,38 @@ int run_all_pairs(const uint8_t* d_arena, const uint64_t* read_off, const int32_
                      (const unsigned long long*)uc.p, (const int32_t*)dv.p, (const int32_t*)nullptr, (int64_t)NP, bc, (pw_overlap_band*)dout.p);
   // pairs with 65 .. kMediumPair seeds: one workgroup each, from the seed list
   {
-    Buf mlist, mcount;
-    if (mlist.alloc(8 * (size_t)NP) || mcount.alloc(16)) return -1;
-    OV_CHECK(hipMemsetAsync(mcount.p, 0, 16, nullptr));
+    DeviceBuffer mlist, mcount;
+    CHECK(mlist.ensure(8 * (size_t)NP)); CHECK(mcount.ensure(16));
+    CHECK(hipMemsetAsync(mcount.p, 0, 16, nullptr));
     hipLaunchKernelGGL(k_list_medium, gP, blk, 0, nullptr, (const unsigned long long*)uc.p, (int64_t)NP, (unsigned long long*)mcount.p, (int64_t*)mlist.p);
     unsigned long long NM = 0;
-    OV_CHECK(hipMemcpy(&NM, mcount.p, 8, hipMemcpyDeviceToHost));
+    CHECK(hipMemcpy(&NM, mcount.p, 8, hipMemcpyDeviceToHost));
     if (NM) hipLaunchKernelGGL(k_band_medium, dim3((unsigned)NM), blk, 0, nullptr, (const DPair*)dpairs.p, (const int64_t*)mlist.p, (const uint64_t*)soff.p,
                                (const unsigned long long*)uc.p, (const int32_t*)dv.p, (const int32_t*)dfirst.p, bc, (pw_overlap_band*)dout.p);
-    OV_CHECK(hipDeviceSynchronize());                    // (mlist is freed at the end of this scope)
+    CHECK(hipDeviceSynchronize());                      // (mlist is freed at the end of this scope)
   }
   // chunks of pairs whose histograms fit 2^30 counters (none at all when no pair has more than kMediumPair seeds)
   uint64_t last_base = 0, last_size = 0;
   if (NP) {
-    OV_CHECK(hipMemcpy(&last_base, (const uint64_t*)hbase.p + (NP - 1), 8, hipMemcpyDeviceToHost));
-    OV_CHECK(hipMemcpy(&last_size, (const uint64_t*)hsize.p + (NP - 1), 8, hipMemcpyDeviceToHost));
+    CHECK(hipMemcpy(&last_base, (const uint64_t*)hbase.p + (NP - 1), 8, hipMemcpyDeviceToHost));
+    CHECK(hipMemcpy(&last_size, (const uint64_t*)hsize.p + (NP - 1), 8, hipMemcpyDeviceToHost));
   }
   const bool any_hist = last_base + last_size > 0;
   const size_t NPh = any_hist ? (size_t)NP : 0;
   std::vector<uint64_t> h_hbase(NPh), h_soff(NPh), h_hsize(NPh);
   if (any_hist) {
-  OV_CHECK(hipMemcpy(h_hbase.data(), hbase.p, 8 * (size_t)NP, hipMemcpyDeviceToHost));
-  OV_CHECK(hipMemcpy(h_soff.data(), soff.p, 8 * (size_t)NP, hipMemcpyDeviceToHost));
-  OV_CHECK(hipMemcpy(h_hsize.data(), hsize.p, 8 * (size_t)NP, hipMemcpyDeviceToHost));
+    CHECK(hipMemcpy(h_hbase.data(), hbase.p, 8 * (size_t)NP, hipMemcpyDeviceToHost));
+    CHECK(hipMemcpy(h_soff.data(), soff.p, 8 * (size_t)NP, hipMemcpyDeviceToHost));
+    CHECK(hipMemcpy(h_hsize.data(), hsize.p, 8 * (size_t)NP, hipMemcpyDeviceToHost));
   }
   const uint64_t cap = 1ull << 30;
-  Buf hist;
-  uint64_t hist_cap = 0;
+  DeviceBuffer hist;
   for (uint64_t u0 = 0; any_hist && u0 < NP;) {
     uint64_t u1 = u0, tot = 0;
     while (u1 < NP && (u1 == u0 || tot + h_hsize[(size_t)u1] <= cap)) { tot += h_hsize[(size_t)u1]; u1++; }
     if (tot == 0) { u0 = u1; continue; }                 // no pair of this chunk needs a histogram
-    if (tot > hist_cap) { if (hist.p) { (void)hipFree(hist.p); hist.p = nullptr; } if (hist.alloc(4 * (size_t)tot)) return -1; hist_cap = tot; }
-    OV_CHECK(hipMemsetAsync(hist.p, 0, 4 * (size_t)tot, nullptr));
+    CHECK(hist.ensure(4 * (size_t)tot));
+    CHECK(hipMemsetAsync(hist.p, 0, 4 * (size_t)tot, nullptr));
     const uint64_t s0 = h_soff[(size_t)u0], s1 = u1 < NP ? h_soff[(size_t)u1] : NS;
     hipLaunchKernelGGL(k_scatter_hist, dim3((unsigned)((s1 - s0 + 255) / 256)), blk, 0, nullptr, (const int32_t*)dv.p, (int64_t)s0, (int64_t)s1,
                        (const uint64_t*)soff.p, (int64_t)u0, (int64_t)u1, (const DPair*)dpairs.p, h_hbase[(size_t)u0], (uint32_t*)hist.p,
@@ -723,15 +686,42 @@ int run_all_pairs(const uint8_t* d_arena, const uint64_t* read_off, const int32_
                        (pw_overlap_band*)dout.p + u0);
     u0 = u1;
   }
-  OV_CHECK(hipEventRecord(ev1, nullptr));
-  OV_CHECK(hipMemcpy(out, dout.p, sizeof(pw_overlap_band) * (size_t)NP, hipMemcpyDeviceToHost));
-  OV_CHECK(hipMemcpy(pair_a, dpa.p, 4 * (size_t)NP, hipMemcpyDeviceToHost));
-  OV_CHECK(hipMemcpy(pair_b, dpb.p, 4 * (size_t)NP, hipMemcpyDeviceToHost));
-  OV_CHECK(hipGetLastError());
+  CHECK(hipEventRecord(ev1.e, nullptr));
+  CHECK(hipMemcpy(out, dout.p, sizeof(pw_overlap_band) * (size_t)NP, hipMemcpyDeviceToHost));
+  CHECK(hipMemcpy(pair_a, dpa.p, 4 * (size_t)NP, hipMemcpyDeviceToHost));
+  CHECK(hipMemcpy(pair_b, dpb.p, 4 * (size_t)NP, hipMemcpyDeviceToHost));
+  CHECK(hipGetLastError());
   float t = 0.f;
-  OV_CHECK(hipEventElapsedTime(&t, ev0, ev1));
+  CHECK(hipEventElapsedTime(&t, ev0.e, ev1.e));
   *ms = t;
   *n_out = (int64_t)NP;
+  return 0;
+}
+
+// The argument checks of both entry points, in this order: word range, counts and pointers (bad_args), coefficients,
+// shard (bad_shard), L^k, reads inside the arena (outside(i) for i < n), letters inside the alphabet.  kbits: the width of
+// the k-mer keys, the bits of L^k - 1.  L^k = 2^62 is accepted here (pw_seeds_create refuses it: its masked key is L^k).
+template <typename Outside>
+int check_args(int L, int k, bool bad_args, double len_coeff, double radius_coeff, double word_p_null, bool bad_shard, int64_t n,
+               Outside outside, const uint8_t* arena, uint64_t arena_bytes, int* kbits) {
+  if (L < 1 || L > 36 || k < 1 || k > 31) { set_err("alphabet_len 1..36, wordlen 1..31"); return -1; }
+  if (bad_args) { set_err("bad arguments"); return -1; }
+  if (!(len_coeff > 0) || !(radius_coeff > 0) || !(word_p_null > 0)) { set_err("coefficients must be positive"); return -1; }
+  if (bad_shard) { set_err("bad shard"); return -1; }
+  uint64_t kmax = 1;
+  for (int i = 0; i < k; i++) { if (kmax > (1ull << 62) / (uint64_t)L) { set_err("alphabet_len ^ wordlen must be below 2^62"); return -1; } kmax *= (uint64_t)L; }
+  *kbits = 0;
+  while (((kmax - 1) >> *kbits) != 0) ++*kbits;
+  if (*kbits == 0) *kbits = 1;
+  for (int64_t i = 0; i < n; i++) if (outside(i)) { set_err("a read lies outside the arena"); return -1; }
+  for (uint64_t i = 0; i < arena_bytes; i++) if (arena[i] >= L) { set_err("letter outside the alphabet"); return -1; }
+  return 0;
+}
+
+int upload_arena(int device, const uint8_t* arena, uint64_t arena_bytes, DeviceBuffer& d_arena) {
+  CHECK(hipSetDevice(device));
+  CHECK(d_arena.ensure((size_t)arena_bytes + 64));
+  CHECK(hipMemcpy(d_arena.p, arena, (size_t)arena_bytes, hipMemcpyHostToDevice));
   return 0;
 }
 
@@ -743,23 +733,16 @@ int pw_overlap_all_pairs(int device, const uint8_t* arena, uint64_t arena_bytes,
                          int64_t n_reads, int alphabet_len, int wordlen, double len_coeff, double radius_coeff, double word_p_null,
                          int shard_rank, int shard_world, int64_t max_pairs, int32_t* pair_a, int32_t* pair_b, pw_overlap_band* out,
                          int64_t* n_out) {
-  if (alphabet_len < 1 || alphabet_len > 36 || wordlen < 1 || wordlen > 31) { set_err("alphabet_len 1..36, wordlen 1..31"); return -1; }
-  if (n_reads < 0 || n_reads >= (1ll << 31) || !n_out || (n_reads && (!read_off || !read_len))) { set_err("bad arguments"); return -1; }
-  if (!(len_coeff > 0) || !(radius_coeff > 0) || !(word_p_null > 0)) { set_err("coefficients must be positive"); return -1; }
-  if (shard_world < 1 || shard_rank < 0 || shard_rank >= shard_world) { set_err("bad shard"); return -1; }
-  uint64_t kmax = 1; int kbits = 0;
-  for (int i = 0; i < wordlen; i++) { if (kmax > (1ull << 62) / (uint64_t)alphabet_len) { set_err("alphabet_len ^ wordlen must be below 2^62"); return -1; } kmax *= (uint64_t)alphabet_len; }
-  while (((kmax - 1) >> kbits) != 0) kbits++;
-  if (kbits == 0) kbits = 1;
-  for (int64_t r = 0; r < n_reads; r++)
-    if (read_len[r] < 0 || read_off[r] + (uint64_t)read_len[r] > arena_bytes) { set_err("a read lies outside the arena"); return -1; }
-  for (uint64_t i = 0; i < arena_bytes; i++) if (arena[i] >= alphabet_len) { set_err("letter outside the alphabet"); return -1; }
+  int kbits = 0;
+  if (check_args(alphabet_len, wordlen, n_reads < 0 || n_reads >= (1ll << 31) || !n_out || (n_reads && (!read_off || !read_len)),
+                 len_coeff, radius_coeff, word_p_null, shard_world < 1 || shard_rank < 0 || shard_rank >= shard_world, n_reads,
+                 [&](int64_t r) { return read_len[r] < 0 || read_off[r] + (uint64_t)read_len[r] > arena_bytes; },
+                 arena, arena_bytes, &kbits) != 0)
+    return -1;
   g_ms = 0.0; *n_out = 0;
   if (n_reads < 2) return 0;
-  OV_CHECK(hipSetDevice(device));
-  Buf d_arena;
-  if (d_arena.alloc((size_t)arena_bytes + 64)) return -1;
-  OV_CHECK(hipMemcpy(d_arena.p, arena, (size_t)arena_bytes, hipMemcpyHostToDevice));
+  DeviceBuffer d_arena;
+  if (upload_arena(device, arena, arena_bytes, d_arena) != 0) return -1;
   float ms = 0.f;
   const int rc = run_all_pairs((const uint8_t*)d_arena.p, read_off, read_len, n_reads, alphabet_len, wordlen, kbits,
                                BandConst{len_coeff, radius_coeff, word_p_null}, shard_rank, shard_world, max_pairs, pair_a, pair_b, out,
@@ -775,29 +758,19 @@ int pw_overlap_bands(int device, const uint8_t* arena, uint64_t arena_bytes, con
                      int alphabet_len, int wordlen, double len_coeff, double radius_coeff, double word_p_null,
                      pw_overlap_band* out) {
   static_assert(sizeof(pw_overlap_band) == 64, "pw_overlap_band is 64 bytes");
-  if (alphabet_len < 1 || alphabet_len > 36 || wordlen < 1 || wordlen > 31) { set_err("alphabet_len 1..36, wordlen 1..31"); return -1; }
-  if (n_pairs < 0 || (n_pairs && (!pairs || !out))) { set_err("bad arguments"); return -1; }
-  if (!(len_coeff > 0) || !(radius_coeff > 0) || !(word_p_null > 0)) { set_err("coefficients must be positive"); return -1; }
-  uint64_t kmax = 1; int kbits = 0;
-  for (int i = 0; i < wordlen; i++) { if (kmax > (1ull << 62) / (uint64_t)alphabet_len) { set_err("alphabet_len ^ wordlen must be below 2^62"); return -1; } kmax *= (uint64_t)alphabet_len; }
-  while (((kmax - 1) >> kbits) != 0) kbits++;
-  if (kbits == 0) kbits = 1;
-  for (int64_t p = 0; p < n_pairs; p++) {
-    const pw_read_pair& r = pairs[p];
-    if (r.s_len < 0 || r.t_len < 0 || r.s_off + (uint64_t)r.s_len > arena_bytes || r.t_off + (uint64_t)r.t_len > arena_bytes) {
-      set_err("a read lies outside the arena"); return -1;
-    }
-  }
-  for (uint64_t i = 0; i < arena_bytes; i++) if (arena[i] >= alphabet_len) { set_err("letter outside the alphabet"); return -1; }
+  int kbits = 0;
+  if (check_args(alphabet_len, wordlen, n_pairs < 0 || (n_pairs && (!pairs || !out)), len_coeff, radius_coeff, word_p_null, false,
+                 n_pairs, [&](int64_t p) {
+                   const pw_read_pair& r = pairs[p];
+                   return r.s_len < 0 || r.t_len < 0 || r.s_off + (uint64_t)r.s_len > arena_bytes || r.t_off + (uint64_t)r.t_len > arena_bytes;
+                 }, arena, arena_bytes, &kbits) != 0)
+    return -1;
   g_ms = 0.0;
   if (n_pairs == 0) return 0;
-  OV_CHECK(hipSetDevice(device));
-  Buf d_arena;
-  if (d_arena.alloc((size_t)arena_bytes + 64)) return -1;
-  OV_CHECK(hipMemcpy(d_arena.p, arena, (size_t)arena_bytes, hipMemcpyHostToDevice));
-  Ev e0, e1;
-  if (e0.make() || e1.make()) return -1;
-  const hipEvent_t ev0 = e0.e, ev1 = e1.e;
+  DeviceBuffer d_arena;
+  if (upload_arena(device, arena, arena_bytes, d_arena) != 0) return -1;
+  DeviceEvent ev0, ev1;
+  CHECK(ev0.create()); CHECK(ev1.create());
   // chunks: at most 2^31 histogram entries, 2^31 k-mers per side and pair ids that fit beside the k-mer
   const uint64_t lim = 1ull << 31;
   const int64_t max_pairs_bits = 62 - kbits;
@@ -812,7 +785,7 @@ int pw_overlap_bands(int device, const uint8_t* arena, uint64_t arena_bytes, con
       hb += h; cs += (uint64_t)pairs[p1].s_len; ct += (uint64_t)pairs[p1].t_len; p1++;
     }
     rc = run_chunk((const uint8_t*)d_arena.p, pairs + p0, p1 - p0, alphabet_len, wordlen, kbits,
-                   BandConst{len_coeff, radius_coeff, word_p_null}, out + p0, ev0, ev1, &ms);
+                   BandConst{len_coeff, radius_coeff, word_p_null}, out + p0, ev0.e, ev1.e, &ms);
     p0 = p1;
   }
   g_ms = (double)ms;

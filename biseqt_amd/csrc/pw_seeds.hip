@@ -24,19 +24,13 @@
 #include <rocprim/rocprim.hpp>
 
 #include "../../include/pw_seeds.h"
+#include "pw_hip_host.h"
 
 namespace {
 
 thread_local std::string g_err;
 void set_err(const std::string& s) { g_err = s; }
-#define SD_CHECK(call)                                                                       \
-  do {                                                                                       \
-    hipError_t e_ = (call);                                                                  \
-    if (e_ != hipSuccess) {                                                                  \
-      set_err(std::string(#call) + ": " + hipGetErrorString(e_));                            \
-      return -1;                                                                             \
-    }                                                                                        \
-  } while (0)
+#define CHECK(call) PW_HIP_CHECK(set_err, call)
 
 constexpr int kMaxMasks = 16;
 struct MaskSets { uint64_t set[kMaxMasks]; int n; };
@@ -70,21 +64,6 @@ __global__ __launch_bounds__(256) void k_encode(const uint8_t* __restrict__ seq,
   pos[p] = (uint32_t)p;
 }
 
-template <typename K>
-__device__ __forceinline__ int64_t lower_bound_k(const K* __restrict__ a, int64_t n, K key) {
-  int64_t lo = 0, hi = n;
-  while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (a[mid] < key) lo = mid + 1; else hi = mid; }
-  return lo;
-}
-template <typename K>
-__device__ __forceinline__ int64_t upper_bound_k(const K* __restrict__ a, int64_t n, K key) {
-  int64_t lo = 0, hi = n;
-  while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (a[mid] <= key) lo = mid + 1; else hi = mid; }
-  return lo;
-}
-__device__ __forceinline__ int64_t lower_bound_u64(const uint64_t* __restrict__ a, int64_t n, uint64_t key) { return lower_bound_k<uint64_t>(a, n, key); }
-__device__ __forceinline__ int64_t upper_bound_u64(const uint64_t* __restrict__ a, int64_t n, uint64_t key) { return upper_bound_k<uint64_t>(a, n, key); }
-
 // ---- K5b ------------------------------------------------------------------------------------------------
 // other = sorted keys of T (or of S itself for a self comparison).  Two ways to find an element's run [lo, hi) in it:
 //   * a direct-address table tab[key] = first index of `key` in `other` (k_table_fill) when the key space is small
@@ -102,7 +81,7 @@ __global__ __launch_bounds__(256) void k_match(const K* __restrict__ ks, int64_t
   if ((uint64_t)key >= kinv) { lo_out[e] = 0; cnt[e] = 0; return; }
   int64_t lo, hi;
   if (tab != nullptr) { lo = tab[(uint64_t)key]; hi = tab[(uint64_t)key + 1]; }
-  else { lo = lower_bound_k<K>(other, no, key); hi = upper_bound_k<K>(other, no, key); }
+  else { lo = lower_bound_dev<K>(other, no, key); hi = upper_bound_dev<K>(other, no, key); }
   lo_out[e] = (uint32_t)lo;
   if (!self) cnt[e] = (uint64_t)(hi - lo);
   else cnt[e] = (uint64_t)(hi - 1 - e) + (e == hi - 1 ? (uint64_t)(hi - lo) : 0ull);
@@ -132,15 +111,15 @@ __global__ __launch_bounds__(256) void k_expand(const uint64_t* __restrict__ off
   __shared__ int64_t win[2];
   const int64_t o0 = (int64_t)blockIdx.x * kExpRows;
   const int64_t olast = (o0 + kExpRows < nrows ? o0 + kExpRows : nrows) - 1;
-  if (threadIdx.x == 0) win[0] = upper_bound_u64(off, ns, (uint64_t)o0) - 1;
-  if (threadIdx.x == 64) win[1] = upper_bound_u64(off, ns, (uint64_t)olast) - 1;
+  if (threadIdx.x == 0) win[0] = upper_bound_dev<uint64_t>(off, ns, (uint64_t)o0) - 1;
+  if (threadIdx.x == 64) win[1] = upper_bound_dev<uint64_t>(off, ns, (uint64_t)olast) - 1;
   __syncthreads();
   const int64_t e0 = win[0], nwin = win[1] - win[0] + 1;
 #pragma unroll 1
   for (int q = 0; q < kExpRows / 256; q++) {
     const int64_t o = o0 + q * 256 + threadIdx.x;
     if (o >= nrows) return;
-    const int64_t e = e0 + upper_bound_u64(off + e0, nwin, (uint64_t)o) - 1;      // last element whose first row is <= o
+    const int64_t e = e0 + upper_bound_dev<uint64_t>(off + e0, nwin, (uint64_t)o) - 1;      // last element whose first row is <= o
     const int64_t r = o - (int64_t)off[e];
     int32_t i, j;
     if (!self) {
@@ -224,7 +203,7 @@ __global__ __launch_bounds__(256) void k_graph_keys(const int2* __restrict__ row
 __global__ __launch_bounds__(256) void k_graph_dstart(const uint64_t* __restrict__ keys, int64_t n, int64_t nd, uint32_t* __restrict__ dstart) {
   const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (q > nd) return;
-  dstart[q] = (uint32_t)lower_bound_u64(keys, n, (uint64_t)q << 32);
+  dstart[q] = (uint32_t)lower_bound_dev<uint64_t>(keys, n, (uint64_t)q << 32);
 }
 // One thread per seed in (d, a) order.  For every diagonal d' that passes the KD-tree's test on the scaled axis,
 // fl(|fl(d c) - fl(d' c)|) <= R, the seeds with |a - a'| <= R form one contiguous piece of that diagonal's run.
@@ -252,8 +231,8 @@ __global__ __launch_bounds__(256) void k_graph_scan(const uint64_t* __restrict__
     const int64_t alo = a - ra < 0 ? 0 : a - ra, ahi = a + ra;
     const uint64_t klo = ((uint64_t)(uint32_t)qq << 32) | (uint64_t)alo;
     const uint64_t khi = ((uint64_t)(uint32_t)qq << 32) | (uint64_t)(ahi > 0xffffffffll ? 0xffffffffll : ahi);
-    const int64_t lo = b + lower_bound_u64(keys + b, e - b, klo);
-    const int64_t hi = b + upper_bound_u64(keys + b, e - b, khi);
+    const int64_t lo = b + lower_bound_dev<uint64_t>(keys + b, e - b, klo);
+    const int64_t hi = b + upper_bound_dev<uint64_t>(keys + b, e - b, khi);
     if (!FILL) total += (uint32_t)(hi - lo);
     else for (int64_t t = lo; t < hi; t++) { const uint32_t v = order[t]; if (v != o) adj[w++] = v; }
   }
@@ -295,51 +274,34 @@ __global__ void k_total(const uint64_t* __restrict__ off, const uint64_t* __rest
   if (threadIdx.x == 0 && blockIdx.x == 0) out[0] = ns > 0 ? off[ns - 1] + cnt[ns - 1] : 0ull;
 }
 
-struct DevBuf {
-  void* p = nullptr; size_t cap = 0;
-  int ensure(size_t bytes) {
-    if (bytes <= cap) return 0;
-    if (p) (void)hipFree(p);
-    p = nullptr; cap = 0;
-    SD_CHECK(hipMalloc(&p, bytes ? bytes : 16));
-    cap = bytes;
-    return 0;
-  }
-  void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-};
-
 }  // namespace
 
 struct pw_seed_index {
   int device = 0, L = 0, k = 0, self = 0, bits = 0;
   bool key32 = false;                   // L^k fits 32 bits: 4-byte keys
-  DevBuf tab;                           // direct-address table of the join (small key spaces)
+  DeviceBuffer tab;                     // direct-address table of the join (small key spaces)
   int64_t nS = 0, nT = 0, nkS = 0, nkT = 0, nrows = -1;
   uint64_t kinv = 0;
   MaskSets ms;
-  DevBuf dS, dT, keys_in, keys_s, keys_t, pos_in, pos_s, pos_t, lo, cnt, off, rows, tmp, scalar;
-  DevBuf g_keys, g_order, g_dstart, g_cnt, g_off, g_adj, g_pts;     // neighbourhood graph (K7)
+  DeviceBuffer dS, dT, keys_in, keys_s, keys_t, pos_in, pos_s, pos_t, lo, cnt, off, rows, tmp, scalar;
+  DeviceBuffer g_keys, g_order, g_dstart, g_cnt, g_off, g_adj, g_pts;     // neighbourhood graph (K7)
   int64_t g_edges = -1, g_npts = -1;    // g_npts: points of the graph (= rows, or the mirrored non-trivial rows of a self comparison)
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  DeviceEvent ev0, ev1;
   float ms_build = 0.f;
 };
 
 template <typename K>
-static int encode_sort(pw_seed_index* x, const uint8_t* seq, int64_t n, int64_t nk, DevBuf& keys_out, DevBuf& pos_out,
+static int encode_sort(pw_seed_index* x, const uint8_t* seq, int64_t n, int64_t nk, DeviceBuffer& keys_out, DeviceBuffer& pos_out,
                        hipStream_t st) {
-  if (keys_out.ensure((size_t)std::max<int64_t>(nk, 1) * sizeof(K)) != 0 || pos_out.ensure((size_t)std::max<int64_t>(nk, 1) * 4) != 0) return -1;
+  CHECK(keys_out.ensure((size_t)std::max<int64_t>(nk, 1) * sizeof(K))); CHECK(pos_out.ensure((size_t)std::max<int64_t>(nk, 1) * 4));
   if (nk <= 0) return 0;
-  if (x->keys_in.ensure((size_t)nk * sizeof(K)) != 0 || x->pos_in.ensure((size_t)nk * 4) != 0) return -1;
+  CHECK(x->keys_in.ensure((size_t)nk * sizeof(K))); CHECK(x->pos_in.ensure((size_t)nk * 4));
   hipLaunchKernelGGL((k_encode<K>), dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, st, seq, n, x->k, x->L, x->kinv, x->ms,
                      (K*)x->keys_in.p, (uint32_t*)x->pos_in.p);
-  size_t tb = 0;
-  SD_CHECK(rocprim::radix_sort_pairs(nullptr, tb, (const K*)x->keys_in.p, (K*)keys_out.p,
-                                     (const uint32_t*)x->pos_in.p, (uint32_t*)pos_out.p, (size_t)nk, 0u,
-                                     (unsigned)x->bits, st));
-  if (x->tmp.ensure(tb) != 0) return -1;
-  SD_CHECK(rocprim::radix_sort_pairs(x->tmp.p, tb, (const K*)x->keys_in.p, (K*)keys_out.p,
-                                     (const uint32_t*)x->pos_in.p, (uint32_t*)pos_out.p, (size_t)nk, 0u,
-                                     (unsigned)x->bits, st));
+  CHECK(rocprim_run(x->tmp, [&](void* t, size_t& b) {
+    return rocprim::radix_sort_pairs(t, b, (const K*)x->keys_in.p, (K*)keys_out.p, (const uint32_t*)x->pos_in.p, (uint32_t*)pos_out.p,
+                                     (size_t)nk, 0u, (unsigned)x->bits, st);
+  }));
   return 0;
 }
 
@@ -356,7 +318,7 @@ static int build_join(pw_seed_index* x, hipStream_t st, int64_t ns, bool count_o
     // average no more than 64 keys between two consecutive elements of `other` (k_table_fill walks those gaps serially)
     const uint32_t* tab = nullptr;
     if (x->key32 && x->kinv <= (1ull << 26) && no > 0 && x->kinv / (uint64_t)no <= 64) {
-      if (x->tab.ensure((size_t)(x->kinv + 2) * 4) != 0) return -1;
+      CHECK(x->tab.ensure((size_t)(x->kinv + 2) * 4));
       hipLaunchKernelGGL((k_table_fill<K>), dim3((unsigned)((no + 256) / 256)), dim3(256), 0, st, other, no, x->kinv, (uint32_t*)x->tab.p);
       tab = (const uint32_t*)x->tab.p;
     }
@@ -368,6 +330,18 @@ static int build_join(pw_seed_index* x, hipStream_t st, int64_t ns, bool count_o
                      (int64_t)total, (const uint32_t*)x->pos_s.p,
                      x->self ? (const uint32_t*)x->pos_s.p : (const uint32_t*)x->pos_t.p, (const uint32_t*)x->lo.p,
                      (const K*)x->keys_s.p, x->self, (int2*)x->rows.p);
+  return 0;
+}
+
+// the device copies of S and T, and the events that time pw_seeds_build
+static int upload(pw_seed_index* x, const uint8_t* S, const uint8_t* T) {
+  CHECK(x->dS.ensure((size_t)x->nS + 64));
+  if (x->nS) CHECK(hipMemcpy(x->dS.p, S, (size_t)x->nS, hipMemcpyHostToDevice));
+  if (!x->self) {
+    CHECK(x->dT.ensure((size_t)x->nT + 64));
+    if (x->nT) CHECK(hipMemcpy(x->dT.p, T, (size_t)x->nT, hipMemcpyHostToDevice));
+  }
+  CHECK(x->ev0.create()); CHECK(x->ev1.create());
   return 0;
 }
 
@@ -403,40 +377,30 @@ pw_seed_index* pw_seeds_create(int device, const uint8_t* S, int64_t nS, const u
   x->key32 = kinv < 0xffffffffull;
   x->ms.n = n_masks;
   for (int i = 0; i < kMaxMasks; i++) x->ms.set[i] = i < n_masks ? mask_sets[i] : 0;
-  auto fail = [&](const char* what) { if (g_err.empty()) set_err(what); pw_seeds_destroy(x); return (pw_seed_index*)nullptr; };
-  if (x->dS.ensure((size_t)nS + 64) != 0) return fail("hipMalloc");
-  if (nS && hipMemcpy(x->dS.p, S, (size_t)nS, hipMemcpyHostToDevice) != hipSuccess) return fail("H2D of S failed");
-  if (!self_comp) {
-    if (x->dT.ensure((size_t)nT + 64) != 0) return fail("hipMalloc");
-    if (nT && hipMemcpy(x->dT.p, T, (size_t)nT, hipMemcpyHostToDevice) != hipSuccess) return fail("H2D of T failed");
-  }
-  if (hipEventCreate(&x->ev0) != hipSuccess || hipEventCreate(&x->ev1) != hipSuccess) return fail("hipEventCreate");
+  if (upload(x, S, T) != 0) { delete x; return nullptr; }
   return x;
 }
 
 int pw_seeds_build(pw_seed_index* x, int64_t max_rows, void* stream) {
   if (!x) { set_err("null index"); return -1; }
   hipStream_t st = (hipStream_t)stream;
-  SD_CHECK(hipSetDevice(x->device));
+  CHECK(hipSetDevice(x->device));
   if (max_rows <= 0) max_rows = (1ll << 31) - 1;
   x->nrows = -1; x->g_edges = -1; x->g_npts = -1;
-  SD_CHECK(hipEventRecord(x->ev0, st));
+  CHECK(hipEventRecord(x->ev0.e, st));
   const int64_t ns = x->nkS;
-  if (x->scalar.ensure(16) != 0) return -1;
-  if (ns > 0 && (x->lo.ensure((size_t)ns * 4) != 0 || x->cnt.ensure((size_t)ns * 8) != 0 || x->off.ensure((size_t)ns * 8) != 0)) return -1;
+  CHECK(x->scalar.ensure(16));
+  if (ns > 0) { CHECK(x->lo.ensure((size_t)ns * 4)); CHECK(x->cnt.ensure((size_t)ns * 8)); CHECK(x->off.ensure((size_t)ns * 8)); }
   if ((x->key32 ? build_join<uint32_t>(x, st, ns, true, 0) : build_join<uint64_t>(x, st, ns, true, 0)) != 0) return -1;
   unsigned long long total = 0;
   if (ns > 0) {
-    size_t tb = 0;
-    SD_CHECK(rocprim::exclusive_scan(nullptr, tb, (const uint64_t*)x->cnt.p, (uint64_t*)x->off.p, (uint64_t)0, (size_t)ns,
-                                     rocprim::plus<uint64_t>(), st));
-    if (x->tmp.ensure(tb) != 0) return -1;
-    SD_CHECK(rocprim::exclusive_scan(x->tmp.p, tb, (const uint64_t*)x->cnt.p, (uint64_t*)x->off.p, (uint64_t)0, (size_t)ns,
-                                     rocprim::plus<uint64_t>(), st));
+    CHECK(rocprim_run(x->tmp, [&](void* t, size_t& b) {
+      return rocprim::exclusive_scan(t, b, (const uint64_t*)x->cnt.p, (uint64_t*)x->off.p, (uint64_t)0, (size_t)ns, rocprim::plus<uint64_t>(), st);
+    }));
     hipLaunchKernelGGL(k_total, dim3(1), dim3(64), 0, st, (const uint64_t*)x->off.p, (const uint64_t*)x->cnt.p, ns,
                        (unsigned long long*)x->scalar.p);
-    SD_CHECK(hipMemcpyAsync(&total, x->scalar.p, 8, hipMemcpyDeviceToHost, st));
-    SD_CHECK(hipStreamSynchronize(st));
+    CHECK(hipMemcpyAsync(&total, x->scalar.p, 8, hipMemcpyDeviceToHost, st));
+    CHECK(hipStreamSynchronize(st));
   }
   if ((int64_t)total > max_rows) {
     char msg[160];
@@ -444,12 +408,12 @@ int pw_seeds_build(pw_seed_index* x, int64_t max_rows, void* stream) {
     set_err(msg);
     return -1;
   }
-  if (x->rows.ensure((size_t)std::max<unsigned long long>(total, 1) * 8) != 0) return -1;
+  CHECK(x->rows.ensure((size_t)std::max<unsigned long long>(total, 1) * 8));
   if (total > 0 && (x->key32 ? build_join<uint32_t>(x, st, ns, false, total) : build_join<uint64_t>(x, st, ns, false, total)) != 0) return -1;
-  SD_CHECK(hipEventRecord(x->ev1, st));
-  SD_CHECK(hipEventSynchronize(x->ev1));
-  SD_CHECK(hipEventElapsedTime(&x->ms_build, x->ev0, x->ev1));
-  SD_CHECK(hipGetLastError());
+  CHECK(hipEventRecord(x->ev1.e, st));
+  CHECK(hipEventSynchronize(x->ev1.e));
+  CHECK(hipEventElapsedTime(&x->ms_build, x->ev0.e, x->ev1.e));
+  CHECK(hipGetLastError());
   x->nrows = (int64_t)total;
   return 0;
 }
@@ -466,8 +430,8 @@ int64_t pw_seeds_algorithmic_bytes(const pw_seed_index* x) {
 int pw_seeds_rows(const pw_seed_index* x, int32_t* da, int64_t cap) {
   if (!x || x->nrows < 0) { set_err("pw_seeds_rows before a successful pw_seeds_build"); return -1; }
   if (cap < x->nrows) { set_err("pw_seeds_rows: capacity too small"); return -1; }
-  SD_CHECK(hipSetDevice(x->device));
-  if (x->nrows) SD_CHECK(hipMemcpy(da, x->rows.p, (size_t)x->nrows * 8, hipMemcpyDeviceToHost));
+  CHECK(hipSetDevice(x->device));
+  if (x->nrows) CHECK(hipMemcpy(da, x->rows.p, (size_t)x->nrows * 8, hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -476,33 +440,30 @@ int64_t pw_seeds_count(const pw_seed_index* x, int have_d, int32_t dmin, int32_t
   if (!x || x->nrows < 0) { set_err("pw_seeds_count before a successful pw_seeds_build"); return -1; }
   if (!have_d && !have_a) return x->nrows;
   if (x->nrows == 0) return 0;
-  SD_CHECK(hipSetDevice(x->device));
+  CHECK(hipSetDevice(x->device));
   unsigned long long* out = (unsigned long long*)x->scalar.p + 1;
-  SD_CHECK(hipMemsetAsync(out, 0, 8, nullptr));
+  CHECK(hipMemsetAsync(out, 0, 8, nullptr));
   const int64_t blocks = std::min<int64_t>((x->nrows + 255) / 256, 256 * 16);
   hipLaunchKernelGGL(k_count, dim3((unsigned)blocks), dim3(256), 0, nullptr, (const int2*)x->rows.p, x->nrows, have_d,
                      dmin, dmax, have_a, amin, amax, out);
   unsigned long long c = 0;
-  SD_CHECK(hipMemcpy(&c, out, 8, hipMemcpyDeviceToHost));
+  CHECK(hipMemcpy(&c, out, 8, hipMemcpyDeviceToHost));
   return (int64_t)c;
 }
 
-int64_t pw_seeds_kmers(const pw_seed_index* xc, int which, int64_t* out, int64_t cap) {
-  pw_seed_index* x = const_cast<pw_seed_index*>(xc);
+int64_t pw_seeds_kmers(const pw_seed_index* x, int which, int64_t* out, int64_t cap) {
   if (!x) { set_err("null index"); return -1; }
   const bool t = which != 0 && !x->self;
   const int64_t n = t ? x->nT : x->nS, nk = t ? x->nkT : x->nkS;
   if (cap < nk) { set_err("pw_seeds_kmers: capacity too small"); return -1; }
   if (nk <= 0) return 0;
-  SD_CHECK(hipSetDevice(x->device));
-  DevBuf keys, pos;
-  if (keys.ensure((size_t)nk * 8) != 0 || pos.ensure((size_t)nk * 4) != 0) { keys.release(); pos.release(); return -1; }
+  CHECK(hipSetDevice(x->device));
+  DeviceBuffer keys, pos;
+  CHECK(keys.ensure((size_t)nk * 8)); CHECK(pos.ensure((size_t)nk * 4));
   hipLaunchKernelGGL((k_encode<uint64_t>), dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, nullptr,
                      (const uint8_t*)(t ? x->dT.p : x->dS.p), n, x->k, x->L, x->kinv, x->ms, (uint64_t*)keys.p, (uint32_t*)pos.p);
   std::vector<uint64_t> h((size_t)nk);
-  const hipError_t e = hipMemcpy(h.data(), keys.p, (size_t)nk * 8, hipMemcpyDeviceToHost);
-  keys.release(); pos.release();
-  if (e != hipSuccess) { set_err("D2H of the k-mers failed"); return -1; }
+  CHECK(hipMemcpy(h.data(), keys.p, (size_t)nk * 8, hipMemcpyDeviceToHost));
   for (int64_t i = 0; i < nk; i++) out[i] = h[(size_t)i] >= x->kinv ? -1 : (int64_t)h[(size_t)i];
   return nk;
 }
@@ -516,52 +477,43 @@ int pw_seeds_band_neighbours(const pw_seed_index* xc, const double* radius, int6
   for (int64_t i = 0; i < n_radius; i++) if (!(radius[i] > 0)) { set_err("band radii must be positive"); return -1; }
   const int64_t n = x->nrows;
   if (n == 0) return 0;
-  SD_CHECK(hipSetDevice(x->device));
-  DevBuf rad, xu, xs, cn;
-  int rc = -1;
-  do {
-    if (rad.ensure((size_t)n_radius * 8) != 0 || xu.ensure((size_t)n * 8) != 0 || xs.ensure((size_t)n * 8) != 0 || cn.ensure((size_t)n * 4) != 0) break;
-    if (hipMemcpy(rad.p, radius, (size_t)n_radius * 8, hipMemcpyHostToDevice) != hipSuccess) { set_err("H2D of the radius table failed"); break; }
-    hipLaunchKernelGGL(k_scale, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, (const int2*)x->rows.p, n,
-                       (const double*)rad.p, (int)x->nT, (double*)xu.p);
-    size_t tb = 0;
-    if (rocprim::radix_sort_keys(nullptr, tb, (const double*)xu.p, (double*)xs.p, (size_t)n, 0u, 64u, (hipStream_t) nullptr) != hipSuccess) { set_err("radix_sort_keys (size) failed"); break; }
-    if (x->tmp.ensure(tb) != 0) break;
-    if (rocprim::radix_sort_keys(x->tmp.p, tb, (const double*)xu.p, (double*)xs.p, (size_t)n, 0u, 64u, (hipStream_t) nullptr) != hipSuccess) { set_err("radix_sort_keys failed"); break; }
-    hipLaunchKernelGGL(k_neigh, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, (const double*)xu.p, (const double*)xs.p, n, (int32_t*)cn.p);
-    if (hipMemcpy(counts, cn.p, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess) { set_err("D2H of the neighbour counts failed"); break; }
-    rc = 0;
-  } while (0);
-  rad.release(); xu.release(); xs.release(); cn.release();
-  return rc;
+  CHECK(hipSetDevice(x->device));
+  DeviceBuffer rad, xu, xs, cn;
+  CHECK(rad.ensure((size_t)n_radius * 8)); CHECK(xu.ensure((size_t)n * 8)); CHECK(xs.ensure((size_t)n * 8)); CHECK(cn.ensure((size_t)n * 4));
+  CHECK(hipMemcpy(rad.p, radius, (size_t)n_radius * 8, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_scale, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, (const int2*)x->rows.p, n,
+                     (const double*)rad.p, (int)x->nT, (double*)xu.p);
+  CHECK(rocprim_run(x->tmp, [&](void* t, size_t& b) {
+    return rocprim::radix_sort_keys(t, b, (const double*)xu.p, (double*)xs.p, (size_t)n, 0u, 64u, (hipStream_t) nullptr);
+  }));
+  hipLaunchKernelGGL(k_neigh, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, (const double*)xu.p, (const double*)xs.p, n, (int32_t*)cn.p);
+  CHECK(hipMemcpy(counts, cn.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+  return 0;
 }
 
 int64_t pw_seeds_graph_build(pw_seed_index* x, double d_coeff, double radius) {
   if (!x || x->nrows < 0) { set_err("pw_seeds_graph_build before a successful pw_seeds_build"); return -1; }
   if (!(d_coeff > 0) || !(radius >= 0)) { set_err("d_coeff must be positive and radius non-negative"); return -1; }
   x->g_edges = -1; x->g_npts = -1;
-  SD_CHECK(hipSetDevice(x->device));
+  CHECK(hipSetDevice(x->device));
   const int2* pts = (const int2*)x->rows.p;
   int64_t n = x->nrows;
   if (x->self && n > 0) {
     // the point list of a self comparison: non-trivial rows and their mirror images, in table order
-    DevBuf flag, pos;
-    if (flag.ensure((size_t)n * 8) != 0 || pos.ensure((size_t)n * 8) != 0) { flag.release(); pos.release(); return -1; }
+    DeviceBuffer flag, pos;                       // (freed at the end of this block)
+    CHECK(flag.ensure((size_t)n * 8)); CHECK(pos.ensure((size_t)n * 8));
     const dim3 g((unsigned)((n + 255) / 256)), bl(256);
     hipLaunchKernelGGL(k_self_flag, g, bl, 0, nullptr, (const int2*)x->rows.p, n, (uint64_t*)flag.p);
-    size_t tbs = 0;
-    hipError_t e = rocprim::exclusive_scan(nullptr, tbs, (const uint64_t*)flag.p, (uint64_t*)pos.p, (uint64_t)0, (size_t)n, rocprim::plus<uint64_t>(), (hipStream_t) nullptr);
-    if (e == hipSuccess && x->tmp.ensure(tbs) != 0) e = hipErrorOutOfMemory;
-    if (e == hipSuccess) e = rocprim::exclusive_scan(x->tmp.p, tbs, (const uint64_t*)flag.p, (uint64_t*)pos.p, (uint64_t)0, (size_t)n, rocprim::plus<uint64_t>(), (hipStream_t) nullptr);
+    CHECK(rocprim_run(x->tmp, [&](void* t, size_t& b) {
+      return rocprim::exclusive_scan(t, b, (const uint64_t*)flag.p, (uint64_t*)pos.p, (uint64_t)0, (size_t)n, rocprim::plus<uint64_t>(), (hipStream_t) nullptr);
+    }));
     uint64_t lp = 0, lf = 0;
-    if (e == hipSuccess) e = hipMemcpy(&lp, (uint64_t*)pos.p + (n - 1), 8, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(&lf, (uint64_t*)flag.p + (n - 1), 8, hipMemcpyDeviceToHost);
+    CHECK(hipMemcpy(&lp, (uint64_t*)pos.p + (n - 1), 8, hipMemcpyDeviceToHost));
+    CHECK(hipMemcpy(&lf, (uint64_t*)flag.p + (n - 1), 8, hipMemcpyDeviceToHost));
     const int64_t np = (int64_t)(2 * (lp + lf));
-    if (e == hipSuccess && x->g_pts.ensure((size_t)std::max<int64_t>(np, 1) * 8) != 0) e = hipErrorOutOfMemory;
-    if (e == hipSuccess) hipLaunchKernelGGL(k_self_points, g, bl, 0, nullptr, (const int2*)x->rows.p, n, (const uint64_t*)pos.p, (int2*)x->g_pts.p);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    flag.release(); pos.release();
-    if (e != hipSuccess) { set_err("building the point list of the self comparison failed"); return -1; }
+    CHECK(x->g_pts.ensure((size_t)std::max<int64_t>(np, 1) * 8));
+    hipLaunchKernelGGL(k_self_points, g, bl, 0, nullptr, (const int2*)x->rows.p, n, (const uint64_t*)pos.p, (int2*)x->g_pts.p);
+    CHECK(hipDeviceSynchronize());
     pts = (const int2*)x->g_pts.p; n = np;
   }
   x->g_npts = n;
@@ -569,47 +521,40 @@ int64_t pw_seeds_graph_build(pw_seed_index* x, double d_coeff, double radius) {
   const int64_t nd = x->nS + x->nT + 1;
   const double wd = floor(radius / d_coeff) + 2;
   const int win = wd > (double)nd ? (int)nd : (int)wd;
-  DevBuf kin, vin;
-  int64_t rc = -1;
-  do {
-    if (kin.ensure((size_t)n * 8) != 0 || vin.ensure((size_t)n * 4) != 0) break;
-    if (x->g_keys.ensure((size_t)n * 8) != 0 || x->g_order.ensure((size_t)n * 4) != 0 || x->g_dstart.ensure((size_t)(nd + 1) * 4) != 0 ||
-        x->g_cnt.ensure((size_t)n * 4) != 0 || x->g_off.ensure((size_t)(n + 1) * 8) != 0) break;
-    const dim3 grid((unsigned)((n + 255) / 256)), blk(256);
-    hipLaunchKernelGGL(k_graph_keys, grid, blk, 0, nullptr, pts, n, (int)x->nT, (uint64_t*)kin.p, (uint32_t*)vin.p);
-    int dbits = 1; while (((uint64_t)nd >> dbits) != 0) dbits++;
-    size_t tb = 0;
-    if (rocprim::radix_sort_pairs(nullptr, tb, (const uint64_t*)kin.p, (uint64_t*)x->g_keys.p, (const uint32_t*)vin.p, (uint32_t*)x->g_order.p,
-                                  (size_t)n, 0u, (unsigned)(32 + dbits), (hipStream_t) nullptr) != hipSuccess) { set_err("radix_sort_pairs (size) failed"); break; }
-    if (x->tmp.ensure(tb) != 0) break;
-    if (rocprim::radix_sort_pairs(x->tmp.p, tb, (const uint64_t*)kin.p, (uint64_t*)x->g_keys.p, (const uint32_t*)vin.p, (uint32_t*)x->g_order.p,
-                                  (size_t)n, 0u, (unsigned)(32 + dbits), (hipStream_t) nullptr) != hipSuccess) { set_err("radix_sort_pairs failed"); break; }
-    hipLaunchKernelGGL(k_graph_dstart, dim3((unsigned)((nd + 256) / 256)), blk, 0, nullptr, (const uint64_t*)x->g_keys.p, n, nd, (uint32_t*)x->g_dstart.p);
-    hipLaunchKernelGGL((k_graph_scan<false>), grid, blk, 0, nullptr, (const uint64_t*)x->g_keys.p, (const uint32_t*)x->g_order.p, n,
-                       (const uint32_t*)x->g_dstart.p, (int)nd, (int)x->nT, d_coeff, radius, win, (uint32_t*)x->g_cnt.p,
-                       (const uint64_t*)nullptr, (uint32_t*)nullptr);
-    // offsets = exclusive scan of the counts (64-bit)
-    uint64_t* wide = (uint64_t*)kin.p;            // reuse: n x 8 bytes
-    hipLaunchKernelGGL(k_widen, grid, blk, 0, nullptr, (const uint32_t*)x->g_cnt.p, n, wide);
-    tb = 0;
-    if (rocprim::exclusive_scan(nullptr, tb, (const uint64_t*)wide, (uint64_t*)x->g_off.p, (uint64_t)0, (size_t)n, rocprim::plus<uint64_t>(), (hipStream_t) nullptr) != hipSuccess) { set_err("exclusive_scan (size) failed"); break; }
-    if (x->tmp.ensure(tb) != 0) break;
-    if (rocprim::exclusive_scan(x->tmp.p, tb, (const uint64_t*)wide, (uint64_t*)x->g_off.p, (uint64_t)0, (size_t)n, rocprim::plus<uint64_t>(), (hipStream_t) nullptr) != hipSuccess) { set_err("exclusive_scan failed"); break; }
-    hipLaunchKernelGGL(k_total, dim3(1), dim3(64), 0, nullptr, (const uint64_t*)x->g_off.p, (const uint64_t*)wide, n, (unsigned long long*)x->scalar.p);
-    unsigned long long total = 0;
-    if (hipMemcpy(&total, x->scalar.p, 8, hipMemcpyDeviceToHost) != hipSuccess) { set_err("D2H of the edge count failed"); break; }
-    if (total >= (1ull << 32)) { set_err("the neighbourhood graph has more than 2^32 edges: use a smaller radius"); break; }
-    if (hipMemcpy((uint64_t*)x->g_off.p + n, &total, 8, hipMemcpyHostToDevice) != hipSuccess) { set_err("H2D failed"); break; }
-    if (x->g_adj.ensure((size_t)std::max<unsigned long long>(total, 1) * 4) != 0) break;
-    if (total) hipLaunchKernelGGL((k_graph_scan<true>), grid, blk, 0, nullptr, (const uint64_t*)x->g_keys.p, (const uint32_t*)x->g_order.p, n,
-                                  (const uint32_t*)x->g_dstart.p, (int)nd, (int)x->nT, d_coeff, radius, win, (uint32_t*)nullptr,
-                                  (const uint64_t*)x->g_off.p, (uint32_t*)x->g_adj.p);
-    if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess) { set_err("the graph kernels failed"); break; }
-    rc = (int64_t)total;
-  } while (0);
-  kin.release(); vin.release();
-  x->g_edges = rc;
-  return rc;
+  DeviceBuffer kin, vin;
+  CHECK(kin.ensure((size_t)n * 8)); CHECK(vin.ensure((size_t)n * 4));
+  CHECK(x->g_keys.ensure((size_t)n * 8)); CHECK(x->g_order.ensure((size_t)n * 4)); CHECK(x->g_dstart.ensure((size_t)(nd + 1) * 4));
+  CHECK(x->g_cnt.ensure((size_t)n * 4)); CHECK(x->g_off.ensure((size_t)(n + 1) * 8));
+  const dim3 grid((unsigned)((n + 255) / 256)), blk(256);
+  hipLaunchKernelGGL(k_graph_keys, grid, blk, 0, nullptr, pts, n, (int)x->nT, (uint64_t*)kin.p, (uint32_t*)vin.p);
+  int dbits = 1; while (((uint64_t)nd >> dbits) != 0) dbits++;
+  CHECK(rocprim_run(x->tmp, [&](void* t, size_t& b) {
+    return rocprim::radix_sort_pairs(t, b, (const uint64_t*)kin.p, (uint64_t*)x->g_keys.p, (const uint32_t*)vin.p, (uint32_t*)x->g_order.p,
+                                     (size_t)n, 0u, (unsigned)(32 + dbits), (hipStream_t) nullptr);
+  }));
+  hipLaunchKernelGGL(k_graph_dstart, dim3((unsigned)((nd + 256) / 256)), blk, 0, nullptr, (const uint64_t*)x->g_keys.p, n, nd, (uint32_t*)x->g_dstart.p);
+  hipLaunchKernelGGL((k_graph_scan<false>), grid, blk, 0, nullptr, (const uint64_t*)x->g_keys.p, (const uint32_t*)x->g_order.p, n,
+                     (const uint32_t*)x->g_dstart.p, (int)nd, (int)x->nT, d_coeff, radius, win, (uint32_t*)x->g_cnt.p,
+                     (const uint64_t*)nullptr, (uint32_t*)nullptr);
+  // offsets = exclusive scan of the counts (64-bit)
+  uint64_t* wide = (uint64_t*)kin.p;              // reuse: n x 8 bytes
+  hipLaunchKernelGGL(k_widen, grid, blk, 0, nullptr, (const uint32_t*)x->g_cnt.p, n, wide);
+  CHECK(rocprim_run(x->tmp, [&](void* t, size_t& b) {
+    return rocprim::exclusive_scan(t, b, (const uint64_t*)wide, (uint64_t*)x->g_off.p, (uint64_t)0, (size_t)n, rocprim::plus<uint64_t>(), (hipStream_t) nullptr);
+  }));
+  hipLaunchKernelGGL(k_total, dim3(1), dim3(64), 0, nullptr, (const uint64_t*)x->g_off.p, (const uint64_t*)wide, n, (unsigned long long*)x->scalar.p);
+  unsigned long long total = 0;
+  CHECK(hipMemcpy(&total, x->scalar.p, 8, hipMemcpyDeviceToHost));
+  if (total >= (1ull << 32)) { set_err("the neighbourhood graph has more than 2^32 edges: use a smaller radius"); return -1; }
+  CHECK(hipMemcpy((uint64_t*)x->g_off.p + n, &total, 8, hipMemcpyHostToDevice));
+  CHECK(x->g_adj.ensure((size_t)std::max<unsigned long long>(total, 1) * 4));
+  if (total) hipLaunchKernelGGL((k_graph_scan<true>), grid, blk, 0, nullptr, (const uint64_t*)x->g_keys.p, (const uint32_t*)x->g_order.p, n,
+                                (const uint32_t*)x->g_dstart.p, (int)nd, (int)x->nT, d_coeff, radius, win, (uint32_t*)nullptr,
+                                (const uint64_t*)x->g_off.p, (uint32_t*)x->g_adj.p);
+  CHECK(hipDeviceSynchronize());
+  CHECK(hipGetLastError());
+  x->g_edges = (int64_t)total;
+  return x->g_edges;
 }
 
 int64_t pw_seeds_graph_num_points(const pw_seed_index* x) { return (x && x->g_edges >= 0) ? x->g_npts : -1; }
@@ -617,25 +562,25 @@ int64_t pw_seeds_graph_num_points(const pw_seed_index* x) { return (x && x->g_ed
 int pw_seeds_graph_points(const pw_seed_index* x, int32_t* da, int64_t cap) {
   if (!x || x->g_edges < 0) { set_err("pw_seeds_graph_points before a successful pw_seeds_graph_build"); return -1; }
   if (cap < x->g_npts) { set_err("pw_seeds_graph_points: capacity too small"); return -1; }
-  SD_CHECK(hipSetDevice(x->device));
-  if (x->g_npts) SD_CHECK(hipMemcpy(da, x->self ? x->g_pts.p : x->rows.p, (size_t)x->g_npts * 8, hipMemcpyDeviceToHost));
+  CHECK(hipSetDevice(x->device));
+  if (x->g_npts) CHECK(hipMemcpy(da, x->self ? x->g_pts.p : x->rows.p, (size_t)x->g_npts * 8, hipMemcpyDeviceToHost));
   return 0;
 }
 
 int pw_seeds_graph_counts(const pw_seed_index* x, int32_t* counts, int64_t cap) {
   if (!x || x->g_edges < 0) { set_err("pw_seeds_graph_counts before a successful pw_seeds_graph_build"); return -1; }
   if (cap < x->g_npts) { set_err("pw_seeds_graph_counts: capacity too small"); return -1; }
-  SD_CHECK(hipSetDevice(x->device));
-  if (x->g_npts) SD_CHECK(hipMemcpy(counts, x->g_cnt.p, (size_t)x->g_npts * 4, hipMemcpyDeviceToHost));
+  CHECK(hipSetDevice(x->device));
+  if (x->g_npts) CHECK(hipMemcpy(counts, x->g_cnt.p, (size_t)x->g_npts * 4, hipMemcpyDeviceToHost));
   return 0;
 }
 
 int pw_seeds_graph_fetch(const pw_seed_index* x, int64_t* offsets, int32_t* neighbours) {
   if (!x || x->g_edges < 0) { set_err("pw_seeds_graph_fetch before a successful pw_seeds_graph_build"); return -1; }
-  SD_CHECK(hipSetDevice(x->device));
+  CHECK(hipSetDevice(x->device));
   if (x->g_npts == 0) { offsets[0] = 0; return 0; }
-  SD_CHECK(hipMemcpy(offsets, x->g_off.p, (size_t)(x->g_npts + 1) * 8, hipMemcpyDeviceToHost));
-  if (x->g_edges) SD_CHECK(hipMemcpy(neighbours, x->g_adj.p, (size_t)x->g_edges * 4, hipMemcpyDeviceToHost));
+  CHECK(hipMemcpy(offsets, x->g_off.p, (size_t)(x->g_npts + 1) * 8, hipMemcpyDeviceToHost));
+  if (x->g_edges) CHECK(hipMemcpy(neighbours, x->g_adj.p, (size_t)x->g_edges * 4, hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -643,40 +588,28 @@ int pw_seeds_graph_components(const pw_seed_index* x, const uint8_t* avail, int3
   if (!x || x->g_edges < 0) { set_err("pw_seeds_graph_components before a successful pw_seeds_graph_build"); return -1; }
   const int64_t n = x->g_npts;
   if (n == 0) return 0;
-  SD_CHECK(hipSetDevice(x->device));
-  DevBuf av, par, flag;
-  int rc = -1;
-  do {
-    if (av.ensure((size_t)n) != 0 || par.ensure((size_t)n * 4) != 0 || flag.ensure(16) != 0) break;
-    if (hipMemcpy(av.p, avail, (size_t)n, hipMemcpyHostToDevice) != hipSuccess) { set_err("H2D of avail failed"); break; }
-    const dim3 grid((unsigned)((n + 255) / 256)), blk(256);
-    hipLaunchKernelGGL(k_cc_init, grid, blk, 0, nullptr, (const uint8_t*)av.p, n, (int*)par.p);
-    bool ok = true;
-    for (int it = 0; it < 10000; it++) {          // every round at least halves the number of roots still to merge
-      if (hipMemsetAsync(flag.p, 0, 4, nullptr) != hipSuccess) { ok = false; break; }
-      hipLaunchKernelGGL(k_cc_hook, grid, blk, 0, nullptr, (const uint64_t*)x->g_off.p, (const uint32_t*)x->g_cnt.p,
-                         (const uint32_t*)x->g_adj.p, n, (int*)par.p, (int*)flag.p);
-      hipLaunchKernelGGL(k_cc_compress, grid, blk, 0, nullptr, n, (int*)par.p);
-      int changed = 0;
-      if (hipMemcpy(&changed, flag.p, 4, hipMemcpyDeviceToHost) != hipSuccess) { ok = false; break; }
-      if (!changed) break;
-    }
-    if (!ok) { set_err("the component kernels failed"); break; }
-    if (hipMemcpy(labels, par.p, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess) { set_err("D2H of the labels failed"); break; }
-    rc = 0;
-  } while (0);
-  av.release(); par.release(); flag.release();
-  return rc;
+  CHECK(hipSetDevice(x->device));
+  DeviceBuffer av, par, flag;
+  CHECK(av.ensure((size_t)n)); CHECK(par.ensure((size_t)n * 4)); CHECK(flag.ensure(16));
+  CHECK(hipMemcpy(av.p, avail, (size_t)n, hipMemcpyHostToDevice));
+  const dim3 grid((unsigned)((n + 255) / 256)), blk(256);
+  hipLaunchKernelGGL(k_cc_init, grid, blk, 0, nullptr, (const uint8_t*)av.p, n, (int*)par.p);
+  for (int it = 0; it < 10000; it++) {            // every round at least halves the number of roots still to merge
+    CHECK(hipMemsetAsync(flag.p, 0, 4, nullptr));
+    hipLaunchKernelGGL(k_cc_hook, grid, blk, 0, nullptr, (const uint64_t*)x->g_off.p, (const uint32_t*)x->g_cnt.p,
+                       (const uint32_t*)x->g_adj.p, n, (int*)par.p, (int*)flag.p);
+    hipLaunchKernelGGL(k_cc_compress, grid, blk, 0, nullptr, n, (int*)par.p);
+    int changed = 0;
+    CHECK(hipMemcpy(&changed, flag.p, 4, hipMemcpyDeviceToHost));
+    if (!changed) break;
+  }
+  CHECK(hipMemcpy(labels, par.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+  return 0;
 }
 
 void pw_seeds_destroy(pw_seed_index* x) {
   if (!x) return;
   (void)hipSetDevice(x->device);
-  DevBuf* bufs[] = {&x->tab, &x->dS, &x->dT, &x->keys_in, &x->keys_s, &x->keys_t, &x->pos_in, &x->pos_s, &x->pos_t, &x->lo, &x->cnt,
-                    &x->off, &x->rows, &x->tmp, &x->scalar, &x->g_keys, &x->g_order, &x->g_dstart, &x->g_cnt, &x->g_off, &x->g_adj, &x->g_pts};
-  for (DevBuf* b : bufs) b->release();
-  if (x->ev0) (void)hipEventDestroy(x->ev0);
-  if (x->ev1) (void)hipEventDestroy(x->ev1);
   delete x;
 }
 

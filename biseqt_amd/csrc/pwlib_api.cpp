@@ -22,6 +22,7 @@
 #include "pw_launch.h"
 #include "pw_plan.h"
 #include "pw_model.h"
+#include "pw_hip_host.h"
 #define PW_FN inline
 #include "pw_strip.h"
 #include <atomic>
@@ -141,11 +142,7 @@ thread_local std::string g_err;
 
 int fail(const std::string& msg) { g_err = msg; return -1; }
 
-#define HIP_TRY(expr)                                                                              \
-  do {                                                                                             \
-    hipError_t e_ = (expr);                                                                        \
-    if (e_ != hipSuccess) return fail(std::string(#expr) + ": " + hipGetErrorString(e_));          \
-  } while (0)
+#define HIP_TRY(expr) PW_HIP_CHECK(fail, expr)
 
 struct BkClass {
   int bk = 0;

@@ -163,3 +163,169 @@ def test_seed_and_overlap_entry_points_reject_bad_input_loudly():
     assert b'outside the arena' in lib.pw_overlap_last_error()
     assert lib.pw_overlap_bands(0, s.ctypes.data, len(s), rp, 1, 4, 3, 0.0, 0.7, 1. / 64, out.ctypes.data) == -1
     assert b'coefficients' in lib.pw_overlap_last_error()
+    # every refusal that comes before any device call, each with its full message
+    for name, over, msg in _SEED_REFUSALS:
+        _expect_refusal(lib, 'seeds', lambda: lib.pw_seeds_create(*_seeds_args(over)), msg, name)
+    for name, apis, over, msg in _OVERLAP_REFUSALS:
+        if 'b' in apis:
+            _expect_refusal(lib, 'overlap', lambda: lib.pw_overlap_bands(*_bands_args(over)), msg, 'bands: ' + name)
+        if 'a' in apis:
+            _expect_refusal(lib, 'overlap', lambda: lib.pw_overlap_all_pairs(*_all_pairs_args(over)), msg, 'all pairs: ' + name)
+    for name, call, msg in _NULL_INDEX_REFUSALS:
+        _expect_refusal(lib, 'seeds', lambda: call(lib), msg, 'NULL index: ' + name)
+
+
+def test_seed_and_overlap_refusals_come_in_order():
+    """With the faults of several checks at once, the first check in the library's order reports: fault i is combined
+    with every later fault of the list."""
+    lib = W.load()
+    seeds = ['alphabet 37', 'word 32', 'masks 17', 'nS < 0', 'L^k = 2^62', 'letter in S', 'letter in T']
+    bands = ['word 0', 'count < 0', 'length coefficient 0', '5^31', 'read past the arena', 'letter outside the alphabet']
+    all_pairs = ['word 0', 'NULL n_out', 'length coefficient 0', 'shard world 0', '5^31', 'read past the arena',
+                 'letter outside the alphabet']
+    seed_table = {n: (o, m) for n, o, m in _SEED_REFUSALS}
+    overlap_table = {n: (o, m) for n, _, o, m in _OVERLAP_REFUSALS}
+    for api, table, order, args in (('seeds', seed_table, seeds, _seeds_args), ('overlap', overlap_table, bands, _bands_args),
+                                    ('overlap', overlap_table, all_pairs, _all_pairs_args)):
+        fn = {_seeds_args: lib.pw_seeds_create, _bands_args: lib.pw_overlap_bands, _all_pairs_args: lib.pw_overlap_all_pairs}[args]
+        for q, name in enumerate(order):
+            over = {}
+            for later in reversed(order[q:]):
+                over.update(table[later][0])
+            _expect_refusal(lib, api, lambda: fn(*args(over)), table[name][1], '%s with every later fault' % name)
+
+
+def test_seed_and_overlap_entry_points_accept_their_edges():
+    """What is accepted without any device call: no pairs, fewer than two reads, and L^k = 2^62 for the overlap
+    entry points (pw_seeds_create refuses the same word: its masked key is L^k itself)."""
+    lib = W.load()
+    for over in (dict(offs=(), lens=(), n=0), dict(L=4, k=31, offs=(), lens=(), n=0)):
+        assert lib.pw_overlap_bands(*_bands_args(over)) == 0, (over, lib.pw_overlap_last_error())
+        assert lib.pw_overlap_last_ms() == 0.0
+    for over in (dict(offs=(), lens=(), n=0), dict(offs=(4,), lens=(6,), n=1), dict(L=4, k=31, offs=(4,), lens=(6,), n=1)):
+        args = _all_pairs_args(over)
+        assert args[-1][0] == 77
+        assert lib.pw_overlap_all_pairs(*args) == 0, (over, lib.pw_overlap_last_error())
+        assert args[-1][0] == 0 and lib.pw_overlap_last_ms() == 0.0
+    _expect_refusal(lib, 'seeds', lambda: lib.pw_seeds_create(*_seeds_args(dict(L=4, k=31))),
+                    b'alphabet_len ^ wordlen must be below 2^62', 'pw_seeds_create at 4^31')
+    # the accessors of a NULL index that report without an error message
+    assert lib.pw_seeds_num_rows(None) == -1 and lib.pw_seeds_is_self(None) == -1
+    assert lib.pw_seeds_rows_device(None) is None and lib.pw_seeds_build_ms(None) == -1.0
+    assert lib.pw_seeds_algorithmic_bytes(None) == -1 and lib.pw_seeds_graph_num_points(None) == -1
+    lib.pw_seeds_destroy(None)
+
+
+# ---- the refusal tables: keyword overrides of one valid call, listed in the order the library checks them ------------
+_S = (0, 1, 2, 3, 0, 1, 2, 3)
+_SEED_BASE = dict(S=_S, nS=None, T=_S, nT=None, L=4, k=3, n_masks=0, self_comp=0)
+_SEED_REFUSALS = [        # pw_seeds_create: (name, overrides, message)
+    ('alphabet 0', dict(L=0), b'alphabet_len must be 1..36 (kmers.py:266)'),
+    ('alphabet 37', dict(L=37), b'alphabet_len must be 1..36 (kmers.py:266)'),
+    ('word 0', dict(k=0), b'wordlen must be 1..31 (kmers.py:269)'),
+    ('word 32', dict(k=32), b'wordlen must be 1..31 (kmers.py:269)'),
+    ('masks -1', dict(n_masks=-1), b'at most 16 mask sets'),
+    ('masks 17', dict(n_masks=17), b'at most 16 mask sets'),
+    ('nS < 0', dict(nS=-1), b'sequence length out of range'),
+    ('nT < 0', dict(nT=-1), b'sequence length out of range'),
+    ('nS 2^31', dict(nS=1 << 31), b'sequence length out of range'),
+    ('nT 2^31', dict(nT=1 << 31), b'sequence length out of range'),
+    ('L^k = 2^62', dict(k=31), b'alphabet_len ^ wordlen must be below 2^62'),
+    ('36^12', dict(L=36, k=12), b'alphabet_len ^ wordlen must be below 2^62'),
+    ('letter in S', dict(S=(0, 1, 4, 3)), b'letter outside the alphabet in S'),
+    ('letter in T', dict(T=(0, 1, 4, 3)), b'letter outside the alphabet in T'),
+]
+
+_READS = (0, 1, 2, 3, 0, 1, 2, 3, 3, 2)
+_OVERLAP_BASE = dict(arena=_READS, offs=(0, 4), lens=(4, 6), n=None, L=4, k=3, len_coeff=1.1, radius_coeff=0.7,
+                     word_p_null=1. / 64, rank=0, world=1, nulls=())
+_OVERLAP_REFUSALS = [     # (name, 'b': pw_overlap_bands on the pair (read 0, read 1), 'a': pw_overlap_all_pairs, overrides, message)
+    ('alphabet 0', 'ba', dict(L=0), b'alphabet_len 1..36, wordlen 1..31'),
+    ('alphabet 37', 'ba', dict(L=37), b'alphabet_len 1..36, wordlen 1..31'),
+    ('word 0', 'ba', dict(k=0), b'alphabet_len 1..36, wordlen 1..31'),
+    ('word 32', 'ba', dict(k=32), b'alphabet_len 1..36, wordlen 1..31'),
+    ('count < 0', 'ba', dict(n=-1), b'bad arguments'),
+    ('2^31 reads', 'a', dict(n=1 << 31), b'bad arguments'),
+    ('NULL pairs', 'b', dict(nulls=('list',)), b'bad arguments'),
+    ('NULL out', 'b', dict(nulls=('out',)), b'bad arguments'),
+    ('NULL read_off', 'a', dict(nulls=('read_off',)), b'bad arguments'),
+    ('NULL read_len', 'a', dict(nulls=('read_len',)), b'bad arguments'),
+    ('NULL n_out', 'a', dict(nulls=('n_out',)), b'bad arguments'),
+    ('length coefficient 0', 'ba', dict(len_coeff=0.), b'coefficients must be positive'),
+    ('radius coefficient < 0', 'ba', dict(radius_coeff=-1.), b'coefficients must be positive'),
+    ('word probability NaN', 'ba', dict(word_p_null=float('nan')), b'coefficients must be positive'),
+    ('shard world 0', 'a', dict(world=0), b'bad shard'),
+    ('shard rank < 0', 'a', dict(rank=-1), b'bad shard'),
+    ('shard rank = world', 'a', dict(rank=2, world=2), b'bad shard'),
+    ('5^31', 'ba', dict(L=5, k=31), b'alphabet_len ^ wordlen must be below 2^62'),
+    ('36^12', 'ba', dict(L=36, k=12), b'alphabet_len ^ wordlen must be below 2^62'),
+    ('negative length', 'ba', dict(lens=(4, -1)), b'a read lies outside the arena'),
+    ('read past the arena', 'ba', dict(lens=(4, 7)), b'a read lies outside the arena'),
+    ('letter outside the alphabet', 'ba', dict(arena=_READS[:-1] + (4,)), b'letter outside the alphabet'),
+    ('letter outside the alphabet, no reads', 'ba', dict(arena=(9,), offs=(), lens=(), n=0), b'letter outside the alphabet'),
+]
+
+_NULL_INDEX_REFUSALS = [  # (name, call on a NULL index, message)
+    ('build', lambda lib: lib.pw_seeds_build(None, 0, None), b'null index'),
+    ('rows', lambda lib: lib.pw_seeds_rows(None, None, 0), b'pw_seeds_rows before a successful pw_seeds_build'),
+    ('count', lambda lib: lib.pw_seeds_count(None, 1, 0, 0, 0, 0, 0), b'pw_seeds_count before a successful pw_seeds_build'),
+    ('kmers', lambda lib: lib.pw_seeds_kmers(None, 0, None, 0), b'null index'),
+    ('band_neighbours', lambda lib: lib.pw_seeds_band_neighbours(None, None, 0, None, 0),
+     b'pw_seeds_band_neighbours before a successful pw_seeds_build'),
+    ('graph_build', lambda lib: lib.pw_seeds_graph_build(None, 1., 1.), b'pw_seeds_graph_build before a successful pw_seeds_build'),
+    ('graph_points', lambda lib: lib.pw_seeds_graph_points(None, None, 0),
+     b'pw_seeds_graph_points before a successful pw_seeds_graph_build'),
+    ('graph_counts', lambda lib: lib.pw_seeds_graph_counts(None, None, 0),
+     b'pw_seeds_graph_counts before a successful pw_seeds_graph_build'),
+    ('graph_fetch', lambda lib: lib.pw_seeds_graph_fetch(None, None, None),
+     b'pw_seeds_graph_fetch before a successful pw_seeds_graph_build'),
+    ('graph_components', lambda lib: lib.pw_seeds_graph_components(None, None, None),
+     b'pw_seeds_graph_components before a successful pw_seeds_graph_build'),
+]
+
+
+def _arr(v, t):
+    return (t * max(len(v), 1))(*v)
+
+
+# The argument tuples hold the ctypes arrays themselves (not their addresses): they stay alive while the tuple does.
+def _seeds_args(over):
+    a = dict(_SEED_BASE, **over)
+    return (0, _arr(a['S'], C.c_uint8), len(a['S']) if a['nS'] is None else a['nS'], _arr(a['T'], C.c_uint8),
+            len(a['T']) if a['nT'] is None else a['nT'], a['L'], a['k'], _arr([0] * 17, C.c_uint64), a['n_masks'], a['self_comp'])
+
+
+def _bands_args(over):
+    a = dict(_OVERLAP_BASE, **over)
+    pairs = (W.pw_read_pair * 1)(W.pw_read_pair(*a['offs'], *a['lens'])) if a['offs'] else None
+    n = (1 if a['offs'] else 0) if a['n'] is None else a['n']
+    return (0, _arr(a['arena'], C.c_uint8), len(a['arena']), None if 'list' in a['nulls'] else pairs, n, a['L'], a['k'],
+            a['len_coeff'], a['radius_coeff'], a['word_p_null'], None if 'out' in a['nulls'] else _arr([0] * 64, C.c_uint8))
+
+
+def _all_pairs_args(over):
+    """(max_pairs = 1 and room for one record: every call here returns before the device is touched)"""
+    a = dict(_OVERLAP_BASE, **over)
+    n = len(a['offs']) if a['n'] is None else a['n']
+    return (0, _arr(a['arena'], C.c_uint8), len(a['arena']), None if 'read_off' in a['nulls'] else _arr(a['offs'], C.c_uint64),
+            None if 'read_len' in a['nulls'] else _arr(a['lens'], C.c_int32), n, a['L'], a['k'], a['len_coeff'],
+            a['radius_coeff'], a['word_p_null'], a['rank'], a['world'], 1, _arr([0], C.c_int32), _arr([0], C.c_int32),
+            _arr([0] * 64, C.c_uint8), None if 'n_out' in a['nulls'] else C.pointer(C.c_int64(77)))
+
+
+def _expect_refusal(lib, api, call, msg, name):
+    """call() fails (NULL or -1) and leaves exactly `msg` in its API's error channel.  The channel holds another
+    message before the call, so a stale one cannot pass."""
+    last = lib.pw_seeds_last_error if api == 'seeds' else lib.pw_overlap_last_error
+    if api == 'seeds':
+        lib.pw_seeds_build(None, 0, None)
+        if last() == msg:
+            lib.pw_seeds_rows(None, None, 0)
+    else:
+        lib.pw_overlap_bands(0, None, 0, None, -1, 0, 3, 1., 1., 1., None)
+        if last() == msg:
+            lib.pw_overlap_bands(0, None, 0, None, -1, 4, 3, 1., 1., 1., None)
+    assert last() != msg
+    rc = call()
+    assert rc in (None, -1), (name, rc)             # NULL from pw_seeds_create, -1 from the others
+    assert last() == msg, (name, last())

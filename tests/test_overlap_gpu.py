@@ -268,3 +268,24 @@ def test_shared_device_arena_and_pipelined_batches_equal_private_copies():
             assert (b.run() == ref[:50]).all()
         finally:
             b.close()
+
+
+def test_all_pairs_over_max_pairs_refuses_then_runs_with_room():
+    """More candidate pairs than max_pairs: the call refuses with its message and writes nothing; the next call with
+    room for every pair returns the unconstrained result."""
+    from biseqt_amd import synth
+    from biseqt_amd.overlap import raw_all_pairs
+    rng = synth.rng_for(99)
+    reads, _ = _reads(rng, 6000, 20, 900, .03, .02)
+    pairs, recs, _ = raw_all_pairs(reads, 10, 4, .2, .99)
+    n = len(pairs)
+    assert n > 2
+    with pytest.raises(RuntimeError) as e:
+        raw_all_pairs(reads, 10, 4, .2, .99, max_pairs=n - 1)
+    assert str(e.value) == ('pw_overlap_all_pairs failed: %d pairs of reads share a seed (capacity %d): raise max_pairs or the '
+                            'word length' % (n, n - 1))
+    again, again_recs, _ = raw_all_pairs(reads, 10, 4, .2, .99, max_pairs=n)
+    assert (again == pairs).all()
+    for name in recs.dtype.names:
+        if name != 'pad_':
+            assert (again_recs[name] == recs[name]).all(), name

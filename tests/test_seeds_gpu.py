@@ -204,3 +204,29 @@ def test_gpu_seeds_equal_the_reference_seed_lists(A):
         idx.close()
         done += 1
     assert done >= 50
+
+
+def test_build_over_max_rows_refuses_then_builds_in_full(A):
+    """A max_rows below the table's size refuses the build with its message and leaves no table; building the same
+    index again without the limit (its buffers grow from where the refusal left them) gives the rows of a fresh index,
+    and a limit of exactly the table's size is accepted."""
+    from biseqt_amd.seeds import _Index
+    rng = np.random.default_rng(21)
+    s = rng.integers(0, 4, 3000).astype(np.uint8)
+    t = np.concatenate([s[500:2500], rng.integers(0, 4, 800)]).astype(np.uint8)
+    with _Index(s, t, 6, A, self_comp=0) as fresh:
+        n = fresh.build()
+        want = fresh.rows()
+    assert n > 2000
+    with _Index(s, t, 6, A, self_comp=0) as idx:
+        with pytest.raises(RuntimeError) as e:
+            idx.build(max_rows=n - 1)
+        assert str(e.value) == ('pw_seeds_build failed: the seeds table would hold %d rows (limit %d): raise max_rows or the '
+                                'word length' % (n, n - 1))
+        assert idx.lib.pw_seeds_num_rows(idx.handle) == -1
+        with pytest.raises(RuntimeError, match='pw_seeds_rows before a successful pw_seeds_build'):
+            idx.rows()
+        assert idx.build() == n
+        assert (idx.rows() == want).all()
+        assert idx.build(max_rows=n) == n
+        assert (idx.rows() == want).all()
