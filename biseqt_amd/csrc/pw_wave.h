@@ -802,8 +802,15 @@ struct WaveFill16 {
   // one unsigned maximum per cell pair instead of maximum, compare, subtract and multiply-add (H <= 8191: the planner
   // admits scores up to 8000); turned back into (best, step) once per block
   uint32_t kbE[RH], kbO[RH], C8, SH3, SEVEN, NEG2;
-  uint32_t up_prev;             // the lane below's last odd slot, as of the end of the previous iteration
+  // The two offers that cross lanes, as of the end of the previous exchange.  Only the DPP moves write them, and each move
+  // takes the register's own previous value as its `old` operand: the edge lane that has no source (lane 0 / lane 63 of the
+  // wavefront) keeps the sentinel it was given in run(), with no copy of the sentinel in front of every move.
+  uint32_t up_prev;             // the lane below's last odd slot
+  uint32_t left_next;           // the next lane's first even slot
   int phase_l, phase_r;         // LDS slot of the next exchange to the left / right (multi-wavefront platforms)
+  // mask plane (pw_types.h, mask_word_index): this lane's dword in block 0 and the dwords per block -- the spare row and 0 for
+  // lanes with nothing to store --, the spare row's first dword, the dwords per lane group
+  uint32_t mrow0, mrow_step, mspare, mgroup;
 
   PW_FN WaveFill16(const FillParams<int32_t>& a_, const WaveDesc& wd_) : a(a_), wd(wd_) {}
 
@@ -918,17 +925,18 @@ struct WaveFill16 {
     // slots whose values nobody reads, so the range check is needed in EDGE blocks only.
     // The letter and the left offer of the odd step travel the same way: ONE exchange (platforms whose shifts cross
     // wavefronts through LDS pay one barrier for the pair).
-    uint32_t nxt_left;
     {
+      // (MAT: feed_commit has already turned the letters outside the sequence into 0xff, whose row is 0 -- no range check
+      //  here: on a wave-uniform feed it compiled to a branch per iteration, which serialises the packed ops)
       const int oi = xfeed_o + it;
       const uint32_t fb = Base::feed_byte(fo_lo, fo_hi, k);
       uint32_t feed = (!EDGE || (uint32_t)oi < (uint32_t)X) ? fb : SENT_O;
-      if (MAT) feed = (!EDGE || (uint32_t)oi < (uint32_t)X) ? row_of(fb) : 0u;
+      if (MAT) feed = row_of(fb);
       int32_t mv[2] = {(int32_t)(MAT ? ROW[0] : OW[0]), (int32_t)LE[0]};
-      const int32_t mo[2] = {(int32_t)feed, (int32_t)NEGV};
+      const int32_t mo[2] = {(int32_t)feed, (int32_t)left_next};
       xshlv<P, 2>(mv, mo, phase_l); phase_l ^= 1;
       uint32_t nxt = (uint32_t)mv[0];
-      nxt_left = (uint32_t)mv[1];
+      left_next = (uint32_t)mv[1];
       if (SEG) nxt = seglast ? feed : nxt;
       if (MAT) {
         // whole registers: the window of rows moves on by renaming
@@ -944,7 +952,7 @@ struct WaveFill16 {
     }
     // odd step: slot BK - 1 <- next lane's slot 0, slot R - 1 <- own slot R
     {
-      uint32_t nxt = nxt_left;
+      uint32_t nxt = left_next;
       if (SEG) nxt = seglast ? NEGV : nxt;
       const uint32_t leftl = pk::align16(nxt, LE[0]);              // (own.hi, next.lo)
 #pragma unroll
@@ -960,12 +968,13 @@ struct WaveFill16 {
     {
       const int mi = yfeed_m + it;
       const uint32_t fbm = Base::feed_byte(fm_lo, fm_hi, k);
-      // (MAT: the letter arrives in a high half and is moved to the low half of the first register below: high-half code)
-      const uint32_t feed = (MAT ? ((!EDGE || (uint32_t)mi < (uint32_t)Y) ? (MSEL | (fbm + 4u)) : MSENT_HI)
+      // (MAT: the letter arrives in a high half and is moved to the low half of the first register below: high-half code;
+      //  feed_commit has turned the letters outside the sequence into 8, whose code MSEL | 12 is MSENT_HI)
+      const uint32_t feed = (MAT ? (MSEL | (fbm + 4u))
                                  : ((!EDGE || (uint32_t)mi < (uint32_t)Y) ? fbm : SENT_M)) << 16;
       // ... together with the up offer of the next iteration's even step (one exchange)
       int32_t mv[2] = {(int32_t)MW[RH - 1], (int32_t)UO[RH - 1]};
-      const int32_t mo[2] = {(int32_t)feed, (int32_t)NEGV};
+      const int32_t mo[2] = {(int32_t)feed, (int32_t)up_prev};
       xshrv<P, 2>(mv, mo, phase_r); phase_r ^= 1;
       uint32_t prv = (uint32_t)mv[0];
       up_prev = (uint32_t)mv[1];
@@ -1006,27 +1015,30 @@ struct WaveFill16 {
         key_to_best(bestO[p], btO[p], kbO[p], kb0O[p], baseO);
       }
     }
-    // 8 cells per slot -> one dword, first cell in the top nibble; un-invert: kept = 7 - (not kept).
-    // Slots are gathered into their natural order so that every group of 4 goes out as one 16-byte store.
+    // 8 cells per slot -> one dword, first cell in the top nibble; un-invert: kept = 7 - (not kept), one subtract per
+    // accumulator for both slots it holds (every nibble is at most 7: no borrows).  Slots are gathered into their natural
+    // order -- one v_perm_b32 per dword -- so that every group of 4 goes out as one 16-byte store.
     // Lanes with nothing to store (padding lanes, lanes beyond the plane's rows, blocks past the pair's last)
     // write into the plane's spare row (row `nblocks`, slot 0) instead of branching: a branch here splits the
     // unrolled block and serialises the packed ops (dependent VOP3P ops need a wait state between them).
     {
-      const bool st = valid && li < pd.nl && b < pd.nblocks;
-      const int bb = st ? b : pd.nblocks, ll = st ? li : 0;
       uint32_t mwd[BK];
 #pragma unroll
       for (int p = 0; p < RH; p++) {
-        mwd[2 * p] = 0x77777777u - (((accE[p] & 0xffffu) << 16) | (acc2E[p] & 0xffffu));
-        mwd[2 * p + R] = 0x77777777u - ((accE[p] & 0xffff0000u) | (acc2E[p] >> 16));
-        mwd[2 * p + 1] = 0x77777777u - (((accO[p] & 0xffffu) << 16) | (acc2O[p] & 0xffffu));
-        mwd[2 * p + 1 + R] = 0x77777777u - ((accO[p] & 0xffff0000u) | (acc2O[p] >> 16));
+        const uint32_t kE = 0x77777777u - accE[p], k2E = 0x77777777u - acc2E[p];
+        const uint32_t kO = 0x77777777u - accO[p], k2O = 0x77777777u - acc2O[p];
+        mwd[2 * p] = pk::perm(kE, k2E, 0x05040100u);           // (kE.lo, k2E.lo)
+        mwd[2 * p + R] = pk::perm(kE, k2E, 0x07060302u);       // (kE.hi, k2E.hi)
+        mwd[2 * p + 1] = pk::perm(kO, k2O, 0x05040100u);
+        mwd[2 * p + 1 + R] = pk::perm(kO, k2O, 0x07060302u);
       }
+      // mask_word_index(BK, nl, b, li, 4 g), or the spare row: a 32-bit dword index (run(): mrow0 / mrow_step / mspare)
+      const uint32_t row = b < pd.nblocks ? mrow0 + (uint32_t)b * mrow_step : mspare;
       uint32_t* dst = a.masks + pd.mask_off;
 #pragma unroll
       for (int g = 0; g < BK / 4; g++) {
         U4 v; v.x = mwd[4 * g]; v.y = mwd[4 * g + 1]; v.z = mwd[4 * g + 2]; v.w = mwd[4 * g + 3];
-        *(U4*)(dst + mask_word_index(BK, pd.nl, bb, ll, 4 * g)) = v;
+        *(U4*)(dst + (row + (uint32_t)g * mgroup)) = v;
       }
     }
   }
@@ -1046,10 +1058,27 @@ struct WaveFill16 {
     fo_n0 = o32[pw_clampi(wo, 0, owlast)]; fo_n1 = o32[pw_clampi(wo + 1, 0, owlast)]; fo_n2 = o32[pw_clampi(wo + 2, 0, owlast)];
     fm_n0 = m32[pw_clampi(wm, 0, mwlast)]; fm_n1 = m32[pw_clampi(wm + 1, 0, mwlast)]; fm_n2 = m32[pw_clampi(wm + 2, 0, mwlast)];
   }
-  PW_FN void feed_commit(int b) {
+  // bytes k = 0 .. 7 of the result are 0xff where i0 + k lies in [0, n), 0 elsewhere
+  PW_FN static uint64_t inside_bytes(int i0, int n) {
+    const int lo = pw_clampi(-i0, 0, 8), hi = pw_clampi(n - i0, 0, 8);
+    const uint64_t below_hi = hi >= 8 ? ~(uint64_t)0 : (((uint64_t)1 << (8 * hi)) - 1);
+    const uint64_t below_lo = lo >= 8 ? ~(uint64_t)0 : (((uint64_t)1 << (8 * lo)) - 1);
+    return below_hi & ~below_lo;
+  }
+  // MAT, blocks in which diagonals start or end (`edge`): the block's feed letters outside the sequences are replaced here,
+  // once per block, by letters that encode "outside" (origin 0xff: row 0; mutant 8: selector MSENT_HI) instead of a range
+  // check per iteration.  Steady blocks keep the letters as loaded (only out-of-band slots read those beyond a sequence).
+  PW_FN void feed_commit(int b, bool edge) {
     const int ro = (xfeed_o + 8 * b) & 3, rm = (yfeed_m + 8 * b) & 3;
     fo_lo = Base::funnel(fo_n1, fo_n0, ro); fo_hi = Base::funnel(fo_n2, fo_n1, ro);
     fm_lo = Base::funnel(fm_n1, fm_n0, rm); fm_hi = Base::funnel(fm_n2, fm_n1, rm);
+    if (MAT && edge) {
+      const uint64_t io = inside_bytes(xfeed_o + 8 * b, X), im = inside_bytes(yfeed_m + 8 * b, Y);
+      const uint64_t o = ((((uint64_t)fo_hi) << 32) | fo_lo) | ~io;
+      const uint64_t m = (((((uint64_t)fm_hi) << 32) | fm_lo) & im) | (0x0808080808080808ull & ~im);
+      fo_lo = (uint32_t)o; fo_hi = (uint32_t)(o >> 32);
+      fm_lo = (uint32_t)m; fm_hi = (uint32_t)(m >> 32);
+    }
   }
 
   PW_FN int tfirst_of(int j) const {      // first step of slot j's diagonal; never for a diagonal outside the band
@@ -1133,7 +1162,7 @@ struct WaveFill16 {
       }
       tlE[p] = pk::pack(tlast_of(e0), tlast_of(e1)); tlO[p] = pk::pack(tlast_of(o0), tlast_of(o1));
       HE[p] = UE[p] = LE[p] = HO[p] = UO[p] = LO[p] = NEGV;
-      up_prev = NEGV; phase_l = 0; phase_r = 0;
+      up_prev = left_next = NEGV; phase_l = 0; phase_r = 0;
       // rule 0: scores never go below 0, and a diagonal whose best stays 0 reports its first cell (score 0 on the table edge)
       // (rule 5: a best of 0 never wins -- the end cell must beat 0 -- so where it "was reached" does not matter)
       bestE[p] = bestO[p] = TRK ? 0u : NEGV;
@@ -1145,9 +1174,14 @@ struct WaveFill16 {
     // The planner's steady range allows a diagonal's LAST cell to be the last step of a steady block (every cell of
     // the block is still valid); rules 1 / 2 capture that cell, which only the edge body does: give up that block.
     const int sb1 = CAP ? wd.steady_b1 - 1 : wd.steady_b1;
+    mgroup = 4u * (uint32_t)pd.nl;
+    mspare = (uint32_t)mask_word_index(BK, pd.nl, pd.nblocks, 0, 0);
+    const bool mrow_ok = valid && li < pd.nl;
+    mrow0 = mrow_ok ? (uint32_t)mask_word_index(BK, pd.nl, 0, li, 0) : mspare;
+    mrow_step = mrow_ok ? (uint32_t)mask_word_index(BK, pd.nl, 1, 0, 0) : 0u;
     feed_issue(0);
     for (int b = 0; b < wd.nblocks; b++) {
-      feed_commit(b);
+      feed_commit(b, !(b >= wd.steady_b0 && b < sb1));
       if (b + 1 < wd.nblocks) feed_issue(b + 1);
       if (b >= wd.steady_b0 && b < sb1) block16<0>(b);
       else if (!ANYB) block16<3>(b);
