@@ -8,11 +8,13 @@ parts -- for every seed the seeds in its neighbourhood (KD-tree ball queries in 
 neighbouring seeds into segments (a depth-first search there) -- run on the GPU (kernels K6, K7 of pw_seeds.hip).
 ``highest_scoring_overlap_band()`` returns the ``d_band`` that the banded overlap aligner
 (``Aligner(..., alnmode=BANDED_MODE, alntype=B_OVERLAP, diag_range=d_band)``) is given.
+``WordBlotMultiple`` / ``WordBlotMultipleFast`` (:726-1083) do the same local-similarity search for more than two
+sequences on the N-way seed table of pw_mseeds.hip (kernels K9).
 """
 import numpy as np
 from scipy.special import erfcinv
 
-from .seeds import SeedIndex
+from .seeds import SeedIndex, SeedIndexMultiple
 
 
 def find_peaks(xs, rs, threshold):
@@ -400,3 +402,157 @@ class WordBlotOverlapRef(_RefMixin, WordBlotOverlap):
     def highest_scoring_overlap_band(self, seq):
         self._set_query(seq)
         return WordBlotOverlap.highest_scoring_overlap_band(self)
+
+
+class WordBlotMultiple(SeedIndexMultiple):
+    """Local similarities shared by more than two sequences (``blot.py:726-1038``).
+
+    Keyword Args:
+        g_max (float): upper bound for indel probabilities.  sensitivity (float): desired band sensitivity.
+        wordlen, alphabet, device, max_rows: as :class:`biseqt_amd.seeds.SeedIndexMultiple`.
+    """
+
+    def __init__(self, *seqs, **kw):
+        g_max, sensitivity = kw.pop('g_max'), kw.pop('sensitivity')
+        assert 0 < g_max < 1 and 0 < sensitivity < 1
+        self.g_max = g_max
+        self.sensitivity = sensitivity
+        super(WordBlotMultiple, self).__init__(*seqs, **kw)
+        self._graph_key = None
+
+    def band_radius(self, K):
+        return band_radius(K, self.g_max, self.sensitivity)
+
+    def estimate_match_probability(self, num_seeds, K, volume):
+        """``p = ((n - V p0^(w (N-1))) / K)^(1/w)``: the null word probability has the exponent ``w (N-1)``, the root
+        is the ``w``-th (``blot.py:787-801``).  0 without seeds or where the logarithm is undefined (the reference
+        turns numpy's warning into an error and answers it with 0, :34); capped at 1."""
+        word_p_null = (1. / len(self.alphabet)) ** (self.wordlen * (len(self.seqs) - 1))
+        if not num_seeds > 0:
+            return 0
+        word_p = (num_seeds - volume * word_p_null) / K
+        if not word_p > 0:
+            return 0
+        return min(np.exp(np.log(word_p) / self.wordlen), 1)
+
+    def _radii(self, K):
+        d_radius = int(np.ceil(self.band_radius(K)))
+        a_radius = int(np.ceil(len(self.seqs) * K / 2.))           # blot.py:822, :939
+        return d_radius, a_radius
+
+    def _graph(self, d_radius, a_radius):
+        """The neighbourhood graph of ``find_all_neighbors`` (``blot.py:833-868``), built on the GPU once per radii."""
+        key = (d_radius, a_radius)
+        if self._graph_key != key:
+            self._idx.graph_build(1. * a_radius / d_radius, a_radius)
+            self._graph_key = key
+
+    def find_all_neighbors(self, d_radius, a_radius):
+        """``[((ds, a), neighs), ..]``: for every seed the indices of the other seeds with ``|d_k c - d'_k c| <= R`` for
+        all k and ``|a - a'| <= R``, ``c = a_radius / d_radius``, ``R = a_radius`` (``blot.py:833-868``)."""
+        if not self.seed_count():
+            return []
+        self._graph(d_radius, a_radius)
+        off, adj = self._idx.graph_fetch()
+        return [(seed, adj[off[k]:off[k + 1]].tolist()) for k, seed in enumerate(self.seeds())]
+
+    def _seed_ps(self, K):
+        """Per seed (table order) the ``p`` of ``score_seeds``, and the radii.  The neighbour counts take few distinct
+        values: ``p`` is evaluated once per value, with the reference's scalar arithmetic."""
+        d_radius, a_radius = self._radii(K)
+        self._graph(d_radius, a_radius)
+        n = self._idx.graph_counts()
+        volume = (2 * d_radius) ** (len(self.seqs) - 1) * K        # blot.py:825: a python number, never int64
+        uniq, inv = np.unique(n, return_inverse=True)
+        vals = np.array([self.estimate_match_probability(int(c) + 1, K, volume) for c in uniq.tolist()], np.float64)
+        return vals[inv.reshape(-1)], d_radius, a_radius
+
+    def score_seeds(self, K):
+        """One dict per seed, in table order: ``seed`` (ds, a), ``neighs`` (indices of the seeds in its neighbourhood),
+        ``p`` estimated match probability of a segment of length K centred there (``blot.py:803-831``)."""
+        if not self.seed_count():
+            return []
+        p, _, _ = self._seed_ps(K)
+        off, adj = self._idx.graph_fetch()
+        return [{'seed': seed, 'neighs': adj[off[k]:off[k + 1]].tolist(), 'p': p[k]}
+                for k, seed in enumerate(self.seeds())]
+
+    def score_num_seeds(self, num_seeds, **kw):
+        """z-scores of an observed number of seeds in a volume against H0 and H1 (``blot.py:870-916``)."""
+        p_match, seglen, volume = kw['p_match'], kw['seglen'], kw['volume']
+        if volume == 0:
+            return float('-inf'), float('-inf')
+        if p_match == 1.:
+            p_match = 1 - np.finfo(float).eps
+        p_H0 = (1. / len(self.alphabet)) ** (len(self.seqs) - 1)
+        pw_H0 = p_H0 ** self.wordlen
+        mu_H0 = volume * pw_H0
+        sd_H0 = np.sqrt(volume * ((1 - pw_H0) * (pw_H0 + 2 * p_H0 * pw_H0 / (1 - p_H0)) - 2 * self.wordlen * pw_H0 ** 2))
+        p_H1 = p_match
+        pw_H1 = p_H1 ** self.wordlen
+        mu_H1 = mu_H0 + seglen * pw_H1
+        sd_H1 = np.sqrt(sd_H0 ** 2 + seglen * ((1 - pw_H1) * (pw_H1 + 2 * p_H1 * pw_H1 / (1 - p_H1)) -
+                                               2 * self.wordlen * pw_H1 ** 2))
+        return (num_seeds - mu_H0) / sd_H0, (num_seeds - mu_H1) / sd_H1
+
+    def similar_segments(self, K_min, p_min, at_least_one=False):
+        """All maximal local similarities of a minimum length and match probability (``blot.py:918-1038``): seeds
+        with ``p >= p_min`` grouped into the connected components of the neighbourhood graph (the reference's
+        depth-first search; on the GPU), each group's bounding segment clamped, scored and yielded in the order of
+        its first seed.  Every group's seed count comes from one ``count_many`` launch."""
+        if not self.seed_count():
+            assert not at_least_one, 'no seeds found while at_least_one=True'
+            return
+        N = len(self.seqs)
+        p, d_radius, a_radius = self._seed_ps(K_min)
+        avail = p >= p_min
+        if not avail.any() and at_least_one:
+            avail[np.argmax(p)] = True                   # the first seed of highest p
+        if not avail.any():
+            return
+        labels = self._idx.graph_components(avail)
+        idx = np.flatnonzero(labels >= 0)
+        order = idx[np.argsort(labels[idx], kind='stable')]     # grouped by component, table order inside
+        starts = np.flatnonzero(np.r_[True, labels[order][1:] != labels[order][:-1]])
+        rows = self.rows()[order].astype(np.int64)
+        firsts = order[starts]                           # the seed each search starts from: its smallest index
+        first_rows = self.rows()[firsts].astype(np.int64)
+        # d ranges: the first seed opens them with +-d_radius, every later one only widens them to its own d_k
+        # (blot.py:946-958); a is widened by +-a_radius for every seed
+        d_lo = np.minimum(np.minimum.reduceat(rows[:, :-1], starts), first_rows[:, :-1] - d_radius)
+        d_hi = np.maximum(np.maximum.reduceat(rows[:, :-1], starts), first_rows[:, :-1] + d_radius)
+        a_lo = np.minimum.reduceat(rows[:, -1], starts) - a_radius
+        a_hi = np.maximum.reduceat(rows[:, -1], starts) + a_radius
+        psum = np.add.reduceat(p[order], starts)
+        cnt = np.diff(np.r_[starts, len(order)])
+        len0, total = len(self.seqs[0]), sum(len(S) for S in self.seqs)
+        segs = []
+        for s in range(len(starts)):                     # labels ascend: the order of the first seeds
+            ds = [(min(len0, max(int(d_lo[s, k]), -len(self.seqs[k + 1]))),
+                   min(len0, max(int(d_hi[s, k]), -len(self.seqs[k + 1])))) for k in range(N - 1)]
+            segs.append((ds, (max(int(a_lo[s]), 0), min(int(a_hi[s]), total))))
+        counts = self.seed_counts(segs)
+        for s, seg in enumerate(segs):
+            ds_band, a_band = seg
+            p_hat = (psum[s] + p[firsts[s]]) / (cnt[s] + 1)       # the start seed is counted twice (:977-980)
+            K_hat = np.ceil((a_band[1] - a_band[0]) // N)          # python 2's integer `/` (:1016)
+            volume = a_band[1] - a_band[0]                          # python ints: no int64 overflow
+            for d_min, d_max in ds_band:
+                volume *= d_max - d_min
+            scores = self.score_num_seeds(num_seeds=counts[s], volume=volume, seglen=K_hat, p_match=p_hat)
+            yield {'segment': seg, 'p': p_hat, 'scores': scores}
+
+
+class WordBlotMultipleFast(WordBlotMultiple):
+    """The reference's in-memory variant of :class:`WordBlotMultiple` (``blot.py:1040-1083``): same results, two or more
+    sequences, and the same refusal of word lengths whose per-k-mer hit lists would not fit ``allowed_memory`` GB."""
+
+    def __init__(self, *seqs, **kw):
+        self.allowed_memory = kw.pop('allowed_memory', 1)
+        _check_ref_memory(kw['alphabet'], kw['wordlen'], self.allowed_memory)
+        g_max, sensitivity = kw.pop('g_max'), kw.pop('sensitivity')
+        assert 0 < g_max < 1 and 0 < sensitivity < 1
+        self.g_max = g_max
+        self.sensitivity = sensitivity
+        self._graph_key = None
+        self._init_index(seqs, kw)

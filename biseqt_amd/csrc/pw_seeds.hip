@@ -25,6 +25,7 @@
 
 #include "../../include/pw_seeds.h"
 #include "pw_hip_host.h"
+#include "pw_seed_kernels.h"
 
 namespace {
 
@@ -32,37 +33,7 @@ thread_local std::string g_err;
 void set_err(const std::string& s) { g_err = s; }
 #define CHECK(call) PW_HIP_CHECK(set_err, call)
 
-constexpr int kMaxMasks = 16;
-struct MaskSets { uint64_t set[kMaxMasks]; int n; };
-
-// ---- K5a ------------------------------------------------------------------------------------------------
-// Key type K: 32 bits whenever L^k (the masked key included) fits -- DNA words up to k = 15 -- which cuts the sort's
-// traffic from 12 to 8 bytes per k-mer and pass; 64 bits otherwise.
-template <typename K>
-__global__ __launch_bounds__(256) void k_encode(const uint8_t* __restrict__ seq, int64_t n, int k, int L,
-                                                uint64_t kinv, MaskSets ms, K* __restrict__ keys,
-                                                uint32_t* __restrict__ pos) {
-  __shared__ uint8_t tile[256 + 64];
-  const int64_t base = (int64_t)blockIdx.x * 256;
-  const int64_t nk = n - k + 1;
-  for (int t = (int)threadIdx.x; t < 256 + k - 1; t += 256) {
-    const int64_t p = base + t;
-    tile[t] = p < n ? seq[p] : 0;
-  }
-  __syncthreads();
-  const int64_t p = base + threadIdx.x;
-  if (p >= nk) return;
-  uint64_t v = 0, lets = 0;
-  for (int t = 0; t < k; t++) {
-    const uint32_t c = tile[threadIdx.x + t];
-    v = v * (uint64_t)L + c;
-    lets |= 1ull << c;
-  }
-  bool masked = false;
-  for (int i = 0; i < ms.n; i++) masked |= lets == ms.set[i];
-  keys[p] = (K)(masked ? kinv : v);
-  pos[p] = (uint32_t)p;
-}
+// (K5a k_encode, the CSR components k_cc_*, k_widen and k_total: pw_seed_kernels.h)
 
 // ---- K5b ------------------------------------------------------------------------------------------------
 // other = sorted keys of T (or of S itself for a self comparison).  Two ways to find an element's run [lo, hi) in it:
@@ -200,11 +171,6 @@ __global__ __launch_bounds__(256) void k_graph_keys(const int2* __restrict__ row
   keys[o] = ((uint64_t)(uint32_t)(r.x + nT) << 32) | (uint32_t)r.y;
   vals[o] = (uint32_t)o;
 }
-__global__ __launch_bounds__(256) void k_graph_dstart(const uint64_t* __restrict__ keys, int64_t n, int64_t nd, uint32_t* __restrict__ dstart) {
-  const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (q > nd) return;
-  dstart[q] = (uint32_t)lower_bound_dev<uint64_t>(keys, n, (uint64_t)q << 32);
-}
 // One thread per seed in (d, a) order.  For every diagonal d' that passes the KD-tree's test on the scaled axis,
 // fl(|fl(d c) - fl(d' c)|) <= R, the seeds with |a - a'| <= R form one contiguous piece of that diagonal's run.
 template <bool FILL>
@@ -238,42 +204,6 @@ __global__ __launch_bounds__(256) void k_graph_scan(const uint64_t* __restrict__
   }
   if (!FILL) cnt[o] = total - 1;                  // its own entry is removed (blot.py:371-372)
 }
-__global__ __launch_bounds__(256) void k_widen(const uint32_t* __restrict__ in, int64_t n, uint64_t* __restrict__ out) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < n) out[i] = in[i];
-}
-__device__ __forceinline__ int cc_root(const int* __restrict__ parent, int v) {
-  int p = parent[v];
-  while (p != v) { v = p; p = parent[v]; }
-  return v;
-}
-__global__ __launch_bounds__(256) void k_cc_init(const uint8_t* __restrict__ avail, int64_t n, int* __restrict__ parent) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < n) parent[i] = avail[i] ? (int)i : -1;
-}
-__global__ __launch_bounds__(256) void k_cc_hook(const uint64_t* __restrict__ off, const uint32_t* __restrict__ cnt,
-                                                 const uint32_t* __restrict__ adj, int64_t n, int* __restrict__ parent,
-                                                 int* __restrict__ changed) {
-  const int64_t u = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (u >= n || parent[u] < 0) return;
-  const uint64_t b = off[u], e = b + cnt[u];
-  for (uint64_t t = b; t < e; t++) {
-    const int v = (int)adj[t];
-    if (parent[v] < 0) continue;
-    const int ru = cc_root(parent, (int)u), rv = cc_root(parent, v);
-    if (ru != rv) { atomicMin(&parent[ru > rv ? ru : rv], ru > rv ? rv : ru); *changed = 1; }
-  }
-}
-__global__ __launch_bounds__(256) void k_cc_compress(int64_t n, int* __restrict__ parent) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < n && parent[i] >= 0) parent[i] = cc_root(parent, (int)i);
-}
-
-__global__ void k_total(const uint64_t* __restrict__ off, const uint64_t* __restrict__ cnt, int64_t ns,
-                        unsigned long long* __restrict__ out) {
-  if (threadIdx.x == 0 && blockIdx.x == 0) out[0] = ns > 0 ? off[ns - 1] + cnt[ns - 1] : 0ull;
-}
-
 }  // namespace
 
 struct pw_seed_index {

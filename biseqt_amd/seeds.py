@@ -238,3 +238,206 @@ class SeedIndex(object):
 
     def close(self):
         self._idx.close()
+
+
+class _MIndex(object):
+    """Thin owner of a ``pw_mseed_index`` handle (include/pw_mseeds.h)."""
+
+    def __init__(self, seqs, wordlen, alphabet, device=0):
+        self.lib = W.load()
+        arrs = [s.as_array(np.uint8) if isinstance(s, Sequence) else np.ascontiguousarray(s, np.uint8) for s in seqs]
+        self.n = len(arrs)
+        ptrs = (C.c_void_p * max(self.n, 1))(*[a.ctypes.data for a in arrs])
+        lens = (C.c_int64 * max(self.n, 1))(*[len(a) for a in arrs])
+        self.handle = self.lib.pw_mseeds_create(device, ptrs, lens, self.n, len(alphabet), wordlen)
+        if not self.handle:
+            raise RuntimeError('pw_mseeds_create failed: ' + self.error())
+        self._edges = None
+
+    def error(self):
+        return (self.lib.pw_mseeds_last_error() or b'').decode('utf-8', 'replace')
+
+    def build(self, max_rows=0, stream=None):
+        if self.lib.pw_mseeds_build(self.handle, max_rows, stream) != 0:
+            raise RuntimeError('pw_mseeds_build failed: ' + self.error())
+        self._edges = None
+        return self.num_rows()
+
+    def num_rows(self):
+        return self.lib.pw_mseeds_num_rows(self.handle)
+
+    def rows(self):
+        """(rows, N) int32 array of (d_1, .., d_{N-1}, a) in table order."""
+        n = self.num_rows()
+        out = np.zeros((max(n, 1), self.n), np.int32)
+        if self.lib.pw_mseeds_rows(self.handle, out.ctypes.data, n) != 0:
+            raise RuntimeError('pw_mseeds_rows failed: ' + self.error())
+        return out[:n]
+
+    def rows_device(self):
+        return DeviceBuffer(self.lib.pw_mseeds_rows_device(self.handle), 4 * self.n * self.num_rows(), self)
+
+    def count_many(self, lo, hi, have):
+        """Row counts of many hyper-boxes in one launch: lo, hi, have are (boxes, N) arrays (have: bound or not)."""
+        lo = np.ascontiguousarray(lo, np.int32).reshape(-1, self.n)
+        hi = np.ascontiguousarray(hi, np.int32).reshape(-1, self.n)
+        have = np.ascontiguousarray(have, np.uint8).reshape(-1, self.n)
+        assert lo.shape == hi.shape == have.shape
+        out = np.zeros(max(len(lo), 1), np.int64)
+        if self.lib.pw_mseeds_count_many(self.handle, len(lo), lo.ctypes.data, hi.ctypes.data, have.ctypes.data,
+                                         out.ctypes.data) != 0:
+            raise RuntimeError('pw_mseeds_count_many failed: ' + self.error())
+        return out[:len(lo)]
+
+    def graph_build(self, d_coeff, radius):
+        """Neighbourhood graph of the rows: max_k |d_k c - d'_k c| <= radius and |a - a'| <= radius."""
+        e = self.lib.pw_mseeds_graph_build(self.handle, float(d_coeff), float(radius))
+        if e < 0:
+            raise RuntimeError('pw_mseeds_graph_build failed: ' + self.error())
+        self._edges = e
+        return e
+
+    def graph_counts(self):
+        n = self.num_rows()
+        out = np.zeros(max(n, 1), np.int32)
+        if self.lib.pw_mseeds_graph_counts(self.handle, out.ctypes.data, n) != 0:
+            raise RuntimeError('pw_mseeds_graph_counts failed: ' + self.error())
+        return out[:n]
+
+    def graph_fetch(self):
+        """CSR adjacency: (offsets[rows + 1], neighbours[edges])."""
+        off = np.zeros(self.num_rows() + 1, np.int64)
+        adj = np.zeros(max(self._edges, 1), np.int32)
+        if self.lib.pw_mseeds_graph_fetch(self.handle, off.ctypes.data, adj.ctypes.data) != 0:
+            raise RuntimeError('pw_mseeds_graph_fetch failed: ' + self.error())
+        return off, adj[:self._edges]
+
+    def graph_components(self, avail):
+        n = self.num_rows()
+        av = np.ascontiguousarray(avail, np.uint8)
+        assert av.size == n
+        out = np.full(max(n, 1), -1, np.int32)
+        if self.lib.pw_mseeds_graph_components(self.handle, av.ctypes.data, out.ctypes.data) != 0:
+            raise RuntimeError('pw_mseeds_graph_components failed: ' + self.error())
+        return out[:n]
+
+    def timings(self):
+        """Device milliseconds of the last build, graph build, components and count_many calls (HIP events)."""
+        L = self.lib
+        return {'build': L.pw_mseeds_build_ms(self.handle), 'graph': L.pw_mseeds_graph_ms(self.handle),
+                'components': L.pw_mseeds_components_ms(self.handle), 'counts': L.pw_mseeds_count_ms(self.handle)}
+
+    def algorithmic_bytes(self):
+        return self.lib.pw_mseeds_algorithmic_bytes(self.handle)
+
+    def close(self):
+        if getattr(self, 'handle', None):
+            self.lib.pw_mseeds_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+MAX_SEQS = 16
+
+
+class SeedIndexMultiple(object):
+    """Seeds shared by more than two sequences, in diagonal coordinates (``seeds.py:234-433``).
+
+    A seed is an N-tuple of positions ``(i_1, .., i_N)`` carrying the same k-mer, stored as ``(d_1, .., d_{N-1}, a)``
+    with ``d_k = i_1 - i_{k+1}`` and ``a = sum(i_k)``.  The table lives in HBM (kernels K9 of pw_mseeds.hip); every
+    argument is its own sequence and rows come in ``WordBlotMultipleFast.seeds()`` order (``blot.py:1061-1071``: k-mers
+    ascending, then ``itertools.product`` of the positions, sequence 0 slowest) -- the SQL-backed reference drops
+    repeated sequences and leaves its row order unspecified.
+
+    Args:
+        *seqs (Sequence): the sequences, more than two (``seeds.py:243``) and at most 16.
+    Keyword Args:
+        wordlen (int), alphabet (Alphabet): as in the reference; ``path`` / ``kmer_cache`` / ``log_level`` are accepted
+        and ignored.  device (int): HIP device ordinal.  max_rows (int): refuse larger tables (default: 16 GB of rows).
+    """
+
+    def __init__(self, *seqs, **kw):
+        assert len(seqs) > 2
+        self._init_index(seqs, kw)
+
+    def _init_index(self, seqs, kw):
+        alphabet, wordlen = kw['alphabet'], kw['wordlen']
+        check_limits(alphabet, wordlen)
+        assert 2 <= len(seqs) <= MAX_SEQS, 'between 2 and %d sequences' % MAX_SEQS
+        assert all(isinstance(S, Sequence) and S.alphabet == alphabet for S in seqs)
+        self.alphabet, self.wordlen = alphabet, wordlen
+        self.seqs = tuple(seqs)
+        self._idx = _MIndex(self.seqs, wordlen, alphabet, device=kw.get('device', 0))
+        self._idx.build(kw.get('max_rows', 0))
+        self._rows = None
+
+    # ---- coordinate maps (seeds.py:262-310) ----
+    @classmethod
+    def to_diagonal_coordinates(cls, *idxs):
+        ds = tuple(idxs[0] - idxs[k] for k in range(1, len(idxs)))
+        return ds, sum(idxs)
+
+    @classmethod
+    def to_ij_coordinates(cls, ds, a):
+        # the reference divides with python 2's integer `/` (seeds.py:287)
+        i0 = (a + sum(ds)) // (len(ds) + 1)
+        return tuple([i0] + [i0 - d for d in ds])
+
+    @classmethod
+    def to_ij_coordinates_seg(cls, seg):
+        """Start and end coordinate in every sequence of a segment ``([(d_min, d_max), ..], (a_min, a_max))``: the
+        extremes over its corners, starts clipped at 0 (``seeds.py:291-310``)."""
+        ds_range, a_range = seg
+        corners = [cls.to_ij_coordinates(c[:-1], c[-1]) for c in product(*(list(ds_range) + [a_range]))]
+        return [(max(min(c[k] for c in corners), 0), max(c[k] for c in corners)) for k in range(len(ds_range) + 1)]
+
+    # ---- the table ----
+    def rows(self):
+        """(n, N) int32 array of (d_1, .., d_{N-1}, a) in table order (cached)."""
+        if self._rows is None:
+            self._rows = self._idx.rows()
+        return self._rows
+
+    def rows_device(self):
+        return self._idx.rows_device()
+
+    def seeds(self):
+        """Yields every seed as ``(ds, a)``, ``ds`` a list (``seeds.py:377-389``)."""
+        for r in self.rows().tolist():
+            yield r[:-1], r[-1]
+
+    def _box(self, ds_band, a_band):
+        """One hyper-box as the (lo, hi, have) rows of count_many; a None band, or a None entry of ds_band, is
+        unbounded."""
+        N = len(self.seqs)
+        lo, hi, have = [0] * N, [0] * N, [0] * N
+        if ds_band is not None:
+            assert len(ds_band) == N - 1
+            for k, band in enumerate(ds_band):
+                if band is None:
+                    continue
+                assert len(band) == 2
+                lo[k], hi[k], have[k] = int(band[0]), int(band[1]), 1
+        if a_band is not None:
+            assert len(a_band) == 2, 'need a 2-tuple for antidiagonal band'
+            lo[-1], hi[-1], have[-1] = int(a_band[0]), int(a_band[1]), 1
+        return lo, hi, have
+
+    def seed_counts(self, boxes):
+        """``seed_count`` of many ``(ds_band, a_band)`` boxes, counted in one launch."""
+        if not boxes:
+            return []
+        lo, hi, have = zip(*[self._box(ds, a) for ds, a in boxes])
+        return [int(c) for c in self._idx.count_many(lo, hi, have)]
+
+    def seed_count(self, ds_band=None, a_band=None):
+        """Number of seeds, optionally inside a hyper-box (``seeds.py:391-433``); counted on the device."""
+        return self.seed_counts([(ds_band, a_band)])[0]
+
+    def close(self):
+        self._idx.close()

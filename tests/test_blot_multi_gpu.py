@@ -1,0 +1,173 @@
+"""Multiple-sequence Word-Blot on the GPU (kernels K9 of pw_mseeds.hip) against the reference's fixtures
+(tests/golden/blot_multi.json.gz) and, for inputs larger than those, against the CPU yardstick tests/mseeds_ref.py."""
+import gzip
+import json
+import os
+
+import numpy as np
+import pytest
+
+from biseqt_amd.blot import WordBlotMultiple, WordBlotMultipleFast, band_radius
+from biseqt_amd.seeds import SeedIndexMultiple
+from biseqt_amd.sequence import Alphabet, Sequence
+from tests import mseeds_ref as R
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+A = Alphabet('ACGT')
+with gzip.open(os.path.join(ROOT, 'tests', 'golden', 'blot_multi.json.gz'), 'rt') as _f:
+    G = json.load(_f)
+
+
+def seq(xs):
+    return Sequence(A, [int(x) for x in xs])
+
+
+def rel_close(x, y, tol=1e-12):
+    return x == y or abs(x - y) <= tol * max(abs(x), abs(y))
+
+
+def _segs(got):
+    return [([list(d) for d in s['segment'][0]], list(s['segment'][1])) for s in got]
+
+
+# the table-backed class takes more than two sequences (seeds.py:243), the in-memory one any number
+@pytest.mark.parametrize('ci,cls', [(ci, 'Fast') for ci in range(len(G['cases']))] +
+                         [(ci, 'table') for ci, r in enumerate(G['cases']) if len(r['seqs']) > 2])
+def test_gpu_equals_the_reference_fixture(ci, cls):
+    rec = G['cases'][ci]
+    seqs = [A.parse(s) for s in rec['seqs']]
+    kw = dict(wordlen=rec['wordlen'], alphabet=A, g_max=float.fromhex(rec['g_max']),
+              sensitivity=float.fromhex(rec['sensitivity']))
+    WB = (WordBlotMultipleFast if cls == 'Fast' else WordBlotMultiple)(*seqs, **kw)
+    assert [list(ds) + [a] for ds, a in WB.seeds()] == rec['rows']
+    for c in rec['counts']:
+        assert WB.seed_count(ds_band=c['ds_band'], a_band=c['a_band']) == c['count'], c
+    assert WB.seed_counts([(c['ds_band'], c['a_band']) for c in rec['counts']]) == [c['count'] for c in rec['counts']]
+    sc = rec['score_seeds']
+    got = WB.score_seeds(sc['K'])
+    assert len(got) == len(sc['records'])
+    for g, r in zip(got, sc['records']):
+        assert list(g['seed'][0]) + [g['seed'][1]] == r['seed']
+        assert sorted(g['neighs']) == r['neighs']
+        assert float(g['p']).hex() == r['p']
+    ss = rec['similar_segments']
+    for key, p_min, alo in (('plain', float.fromhex(ss['p_min']), False), ('at_least_one', .999999, True)):
+        if key not in ss:
+            continue
+        got = list(WB.similar_segments(ss['K_min'], p_min, at_least_one=alo))
+        want = ss[key]
+        assert _segs(got) == [(w['segment'][0], w['segment'][1]) for w in want]
+        for g, w in zip(got, want):
+            assert rel_close(float(g['p']), float.fromhex(w['p']))
+            if w['scores_py2_safe']:
+                for x, y in zip(g['scores'], w['scores']):
+                    assert rel_close(float(x), float.fromhex(y), 1e-9), (g['scores'], w['scores'])
+
+
+def _random_set(rng, N, n, hom, mut=.05):
+    core = rng.integers(0, 4, hom)
+    out = []
+    for _ in range(N):
+        pre = int(rng.integers(0, max(1, n - hom)))
+        c = core.copy()
+        flip = rng.random(hom) < mut
+        c[flip] = (c[flip] + rng.integers(1, 4, int(flip.sum()))) % 4
+        out.append(np.r_[rng.integers(0, 4, pre), c, rng.integers(0, 4, max(0, n - hom - pre))])
+    return out
+
+
+@pytest.mark.parametrize('N,n,hom,w,K', [(3, 4000, 2000, 8, 400), (5, 6000, 3000, 10, 800), (8, 20000, 6000, 12, 1500),
+                                         (4, 1500, 0, 4, 60), (6, 3000, 1500, 6, 300)])
+def test_random_sets_against_the_yardstick(N, n, hom, w, K):
+    rng = np.random.default_rng(N * 1000 + w)
+    raw = _random_set(rng, N, n, hom)
+    WB = WordBlotMultipleFast(*[seq(s) for s in raw], wordlen=w, alphabet=A, g_max=.2, sensitivity=.9)
+    rows = R.seed_rows(raw, w, 4)
+    got = WB.rows()
+    assert got.shape == rows.shape and np.array_equal(got, rows)
+    if (N, w) == (4, 4):
+        assert len(rows) > 100000          # the dense case
+        K = 8                              # a small neighbourhood keeps the CPU yardstick's ball query tractable
+    d_radius = int(np.ceil(band_radius(K, .2, .9)))
+    a_radius = int(np.ceil(N * K / 2.))
+    want = R.neighbours(rows, d_radius, a_radius)
+    got_n = WB.find_all_neighbors(d_radius, a_radius)
+    assert [sorted(nb) for _, nb in got_n] == want
+    p, _, _ = WB._seed_ps(K)
+    avail = p >= np.median(p)
+    labels = WB._idx.graph_components(avail)
+    assert labels.tolist() == R.components(want, avail.tolist())
+    boxes = []
+    for t in rng.integers(0, len(rows), 50):
+        r = rows[t]
+        ds = [None if rng.random() < .3 else (int(r[k]) - 30, int(r[k]) + 30) for k in range(N - 1)]
+        boxes.append((ds, (int(r[-1]) - 2000, int(r[-1]) + 2000)))
+    assert WB.seed_counts(boxes) == [R.box_count(rows, ds, a) for ds, a in boxes]
+    assert WB.seed_counts(boxes) == [WB.seed_count(ds_band=ds, a_band=a) for ds, a in boxes]
+
+
+@pytest.mark.parametrize('K', [400, 800])
+@pytest.mark.parametrize('n_seqs', [3, 5])
+@pytest.mark.parametrize('cls', [WordBlotMultiple, WordBlotMultipleFast])
+def test_reference_scenario(K, n_seqs, cls):
+    """The reference's own test (tests/test_blot.py:200-238), with the mutation done by numpy.  The scenario is
+    statistical: on these seeds the reference itself finds exactly one segment (on some others it finds a second,
+    chance one -- as the GPU does, on the same inputs)."""
+    rng = np.random.default_rng(10000 + K + n_seqs)
+    gap, subst = .01, .01
+    hom = rng.integers(0, 4, K)
+    seqs = []
+    for _ in range(n_seqs):
+        out = []
+        for c in hom.tolist():
+            r = rng.random()
+            if r < gap / 2:
+                continue
+            if r < gap:
+                out.append(int(rng.integers(0, 4)))
+            out.append(int((c + rng.integers(1, 4)) % 4) if rng.random() < subst else c)
+        seqs.append(seq(out + rng.integers(0, 4, K).tolist()))
+    kw = {'g_max': .2, 'sensitivity': .99, 'alphabet': A, 'wordlen': 5}
+    WB = cls(*seqs, **kw)
+    p_match = (1 - gap) * (1 - subst) * .9
+    found = list(WB.similar_segments(K / 2, p_match))
+    assert len(found) == 1
+    d_ranges, (a_min, a_max) = found[0]['segment']
+    for d_min, d_max in d_ranges:
+        assert d_min < 10 and d_max > -10 and a_min < K
+    assert 0.8 * p_match <= found[0]['p'] <= 1.2 * p_match
+    kw['wordlen'] = 15
+    if cls is WordBlotMultipleFast:
+        with pytest.raises(MemoryError):
+            cls(*seqs, **kw)
+    else:
+        cls(*seqs, **kw).close()
+
+
+def test_saturating_product_is_refused_not_wrapped():
+    # eight poly-A sequences of 300 kb: one k-mer with ~3e5 hits in each, a product of ~6.6e43 rows -- far past 2^64
+    polyA = Sequence(A, [0] * 300000)
+    with pytest.raises(RuntimeError, match='2\\^64'):
+        SeedIndexMultiple(*([polyA] * 8), wordlen=4, alphabet=A)
+    with pytest.raises(RuntimeError, match='max_rows'):
+        SeedIndexMultiple(*([Sequence(A, [0] * 40)] * 3), wordlen=4, alphabet=A, max_rows=1000)
+    ok = SeedIndexMultiple(*([Sequence(A, [0] * 40)] * 3), wordlen=4, alphabet=A, max_rows=37 ** 3)
+    assert ok.seed_count() == 37 ** 3
+
+
+def test_empty_cases():
+    rng = np.random.default_rng(7)
+    # no shared k-mer: sequence 2 uses letters that the others never spell at this word length
+    S = seq(rng.integers(0, 2, 300))
+    T = seq(rng.integers(0, 2, 300))
+    U = seq(rng.integers(2, 4, 300))
+    for seqs in ([S, T, U], [S, T, seq([0, 1])]):
+        WB = WordBlotMultipleFast(*seqs, wordlen=3, alphabet=A, g_max=.2, sensitivity=.9)
+        assert list(WB.seeds()) == [] and WB.seed_count() == 0
+        assert WB.seed_counts([(None, (0, 10)), ([None, (0, 1)], None)]) == [0, 0]
+        assert WB.score_seeds(50) == [] and WB.find_all_neighbors(5, 50) == []
+        assert list(WB.similar_segments(50, .5)) == []
+        with pytest.raises(AssertionError):
+            list(WB.similar_segments(50, .5, at_least_one=True))
