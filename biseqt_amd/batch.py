@@ -415,6 +415,15 @@ class BatchAligner(object):
                  'pw_batch_scores')
         return out.reshape(nd, pitch)
 
+    def masks(self, k):
+        """Tie mask of every in-table cell of pair k (bits B 1, D 2, I 4, M 8), flat in the reference's table order: standard
+        mode ``[x * (Y + 1) + y]``, banded mode rows ``d - dmin`` back to back (``pw_batch_masks``).  The packed 16-bit
+        kernels and the strips store no M bit."""
+        out = np.zeros(max(int(self.lib.pw_batch_pair_cells(self.handle, k)), 1), np.uint8)
+        self._ck(self.lib.pw_batch_masks(self.handle, k, out.ctypes.data_as(C.POINTER(C.c_uint8)), out.size),
+                 'pw_batch_masks')
+        return out
+
     def results_device(self):
         return DeviceBuffer(self.lib.pw_batch_results_device(self.handle), 32 * self.n, self)
 

@@ -89,6 +89,34 @@ PW_FN int strip_fifo_pitch(int Y) { return (Y + 1 + 32 + 63) / 64 * 64; }
 PW_FN uint64_t strip_mask_index(int nkq, int w, int q, int lane) {      // in dwords
   return ((uint64_t)((uint64_t)w * nkq + q) * 64 + lane) * 4;
 }
+static inline int strip_nkq(int Y) { return (Y + 64 + kStripBlock - 1) / kStripBlock; }   // 32-step groups per strip row
+
+// Host read-back of layout 1 (tests, pw_batch_masks): the tie mask of cell (x, y) -- strip x >> 6, lane x & 63, step
+// k = y + (x & 63), group k >> 5, dword (k >> 3) & 3, first cell in the top nibble (what strip_walk reads).  `plane`:
+// the pair's own plane.  (strip_mask_index spelled out: that one is device code under hipcc)
+static inline uint32_t strip_mask_nibble(int nkq, const uint32_t* plane, int x, int y) {
+  const int i = x & 63, k = y + i;
+  const uint32_t w = plane[((uint64_t)((uint64_t)(x >> 6) * nkq + (k >> 5)) * 64 + i) * 4 + ((k >> 3) & 3)];
+  return (w >> (4 * (7 - (k & 7)))) & 15u;
+}
+
+// Pair `pd`'s tie masks, either layout, in the reference's table order (include/pw_batch.h, pw_batch_masks): standard mode row x, column
+// y, pitch Y + 1; banded mode rows d - dmin back to back, plan_len(X, Y, d) cells each.  `out` holds pd's cells.
+static inline void mask_table(const PairDesc& pd, const uint32_t* plane, bool banded, uint8_t* out) {
+  const int X = pd.X, Y = pd.Y;
+  if (!banded) {
+    for (int x = 0; x <= X; x++)
+      for (int y = 0; y <= Y; y++)
+        out[(size_t)x * (Y + 1) + y] = (uint8_t)(pd.layout == 1 ? strip_mask_nibble(strip_nkq(Y), plane, x, y)
+                                                                 : mask_nibble(pd, plane, x, y));
+    return;
+  }
+  size_t c = 0;
+  for (int dd = 0; dd < pd.ndiag; dd++) {
+    const int d = pd.dmin + dd, len = 1 + (d > 0 ? 0 : d) + (X - d > Y ? Y : X - d);
+    for (int a = 0; a < len; a++) out[c++] = (uint8_t)mask_nibble(pd, plane, a + (d > 0 ? d : 0), a - (d > 0 ? 0 : d));
+  }
+}
 
 // BROW (byte rows): alphabets of at most 4 letters and scores -- match / mismatch or a whole substitution matrix -- that fit
 // a signed byte: the lane holds its row of the substitution table as 4 bytes (rowreg: byte m = score of the row's letter

@@ -141,5 +141,14 @@ static inline uint64_t mask_word_index(int bk, int nl, int b, int lane, int j) {
   return ((uint64_t)((uint64_t)b * (bk / G) + (j / G)) * nl + lane) * G + (j % G);
 }
 
+// Host read-back of layout 0 (tests, pw_batch_masks): the tie mask of in-band cell (x, y) of one pair; `plane` is the
+// pair's own plane (masks + mask_off).  Diagonal slot dd = x - y - dmin sits in lane dd / bk, slot dd % bk; the dword of
+// block t >> 4 holds steps t, t + 2, .. of that slot, first in the top nibble (what trace_walk reads).
+static inline uint32_t mask_nibble(const PairDesc& pd, const uint32_t* plane, int x, int y) {
+  const int dd = x - y - pd.dmin, t = x + y - pd.s0;
+  const uint32_t w = plane[mask_word_index(pd.bk, pd.nl, t >> 4, dd / pd.bk, dd % pd.bk)];
+  return (w >> (4 * (7 - ((t & 15) >> 1)))) & 15u;
+}
+
 }  // namespace pw
 #endif

@@ -1022,11 +1022,26 @@ int pw_batch_scores(pw_batch* b, int32_t k, double* out, int64_t n) {
   HIP_TRY(hipSetDevice(b->device));
   if (b->use_f64) {
     HIP_TRY(hipMemcpy(out, (double*)b->d_hdump + d.h_off, 8 * (size_t)want, hipMemcpyDeviceToHost));
+    for (int64_t i = 0; i < want; i++) out[i] *= b->score_mul;          // (dyadic scaling on f64 as well: a power of two)
   } else {
     std::vector<int32_t> tmp((size_t)want);
     HIP_TRY(hipMemcpy(tmp.data(), (int32_t*)b->d_hdump + d.h_off, 4 * (size_t)want, hipMemcpyDeviceToHost));
     for (int64_t i = 0; i < want; i++) out[i] = (double)tmp[(size_t)i] * b->score_mul;
   }
+  return 0;
+}
+
+int pw_batch_masks(pw_batch* b, int32_t k, uint8_t* out, int64_t n) {
+  if (k < 0 || k >= b->n || !b->descs[k].solvable) return fail("no mask plane for this pair");
+  if (pw_batch* sub = repaired_sub(b, k)) return pw_batch_masks(sub, 0, out, n);   // (the replacement's plane is the live one)
+  const pw::PairDesc& d = b->descs[k];
+  if (n < b->plans[k].cells) return fail("mask buffer too small");
+  const uint64_t words = d.layout == 1 ? (uint64_t)((d.X + 1 + 63) / 64) * pw::strip_nkq(d.Y) * 64 * 4
+                                       : (uint64_t)(d.nblocks + 1) * d.nl * d.bk;
+  std::vector<uint32_t> plane((size_t)words);
+  HIP_TRY(hipSetDevice(b->device));
+  HIP_TRY(hipMemcpy(plane.data(), b->d_masks + d.mask_off, 4 * (size_t)words, hipMemcpyDeviceToHost));
+  pw::mask_table(d, plane.data(), b->mode == pw::BANDED_MODE, out);
   return 0;
 }
 
@@ -1279,6 +1294,37 @@ intpair dptable_solve(dptable* T) {
   return opt;
 }
 
+}  // extern "C"
+
+namespace {
+
+// The end cell's score when no table holds it: the walk IS the reference's chain of base choices (the predecessor rule,
+// pw_wave.h trace_walk), whose scores the reference builds forward from the start cell's B choice (score 0):
+// M / S add subst[o][m] (_pw_internals.c:234), D / I add ge and then go unless the op before was the same (:268-278).
+// Same operations in the same order as the reference: bit-exact in doubles.
+double walk_score(const dptable* T, const char* tx, int x, int y) {
+  const alnframe* fr = T->prob->frame;
+  const alnscores* sc = T->prob->scores;
+  double s = 0.0;
+  char prev = 'B';
+  for (const char* c = tx; *c; c++) {
+    if (*c == 'M' || *c == 'S') {
+      s = s + sc->subst_scores[fr->origin[fr->origin_range.i + x]][fr->mutant[fr->mutant_range.i + y]];
+      x++; y++;
+    } else {
+      s = s + sc->gap_extend_score;
+      if (*c != prev) s = s + sc->gap_open_score;
+      if (*c == 'D') x++; else y++;
+    }
+    prev = (*c == 'S') ? 'M' : *c;
+  }
+  return s;
+}
+
+}  // namespace
+
+extern "C" {
+
 alignment* dptable_traceback(dptable* T, intpair end) {
   Hidden* h = hidden_of(T);
   if (!h || !h->batch) { fprintf(stderr, "pwlib: dptable_traceback before dptable_solve\n"); return NULL; }
@@ -1309,7 +1355,7 @@ alignment* dptable_traceback(dptable* T, intpair end) {
   // table for any other cell (standard mode), otherwise unknown
   if (end.i == res.opt_i && end.j == res.opt_j) a->score = res.score;
   else if (T->cells[end.i] && T->cells[end.i][end.j].num_choices > 0) a->score = T->cells[end.i][end.j].choices[0].score;
-  else a->score = NAN;
+  else a->score = walk_score(T, a->transcript, res.origin_idx, res.mutant_idx);
   h->alns->push_back(a);
   return a;
 }

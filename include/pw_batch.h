@@ -156,6 +156,11 @@ int pw_batch_packed_total_async(pw_batch* b, uint64_t* host_out, void* stream);
 int pw_batch_packed(pw_batch* b, uint8_t* host_out, uint64_t cap, uint64_t* offsets_out);
 /* score plane of pair k (PW_FLAG_DUMP_SCORES): out[(d-dmin)*pitch + a], pitch = min(X,Y)+1, as doubles */
 int pw_batch_scores(pw_batch* b, int32_t k, double* host_out, int64_t n);
+/* Tie masks of pair k, every in-table cell (bits B 1, D 2, I 4, M 8: the choices the reference keeps), in the reference's
+ * table layout: standard mode out[x * (Y + 1) + y], banded mode rows d - dmin back to back (n >= pw_batch_pair_cells).
+ * Copies pair k's mask plane alone to the host, synchronously.  The packed 16-bit kernels and the strip pipeline store no
+ * M bit (the walker never needs it with go <= 0: M is the first kept op exactly when B, D and I are not kept). */
+int pw_batch_masks(pw_batch* b, int32_t k, uint8_t* host_out, int64_t n);
 /* Standard mode only: the same scores as the reference's table, host_out[x * (Y + 1) + y] for 0 <= x <= X,
  * 0 <= y <= Y (n >= (X + 1)(Y + 1)); transposed on the device.  Needs PW_FLAG_DUMP_SCORES. */
 int pw_batch_table(pw_batch* b, int32_t k, double* host_out, int64_t n);

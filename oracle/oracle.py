@@ -34,7 +34,7 @@ class pwo_result(C.Structure):
                 ('would_panick', C.c_int), ('tb_null', C.c_int),
                 ('origin_idx', C.c_int), ('mutant_idx', C.c_int),
                 ('tx_len', C.c_int), ('transcript', C.POINTER(C.c_char)),
-                ('maskrule_ok', C.c_int)]
+                ('maskrule_ok', C.c_int), ('no_choice', C.c_int)]
 
 
 _lib = None
@@ -57,6 +57,8 @@ def lib():
         _lib.pwo_cells.argtypes = [C.POINTER(pwo_problem)]
         _lib.pwo_cells.restype = C.c_longlong
         _lib.pwo_free_result.argtypes = [C.POINTER(pwo_result)]
+        _lib.pwo_traceback_from.argtypes = [C.POINTER(pwo_problem), C.c_int, C.c_int, C.POINTER(pwo_result)]
+        _lib.pwo_traceback_from.restype = C.c_int
     return _lib
 
 
@@ -133,5 +135,39 @@ def solve(origin, mutant, mode=STD_MODE, alntype=GLOBAL, subst=None, L=None, mat
     if want_table:
         out['H'] = H
         out['mask'] = M
+    lib().pwo_free_result(C.byref(R))
+    return out
+
+
+def traceback_from(origin, mutant, end, mode=STD_MODE, alntype=GLOBAL, subst=None, L=None, match=1., mismatch=0., go=0.,
+                   ge=0., diag_range=None, origin_range=None, mutant_range=None, max_new_mins=-1):
+    """``dptable_traceback(T, end)`` for an explicit table cell ``end`` = (i, j) (pw.c:116-150).  Keys: init_rc, opt,
+    no_choice (the cell holds no choice: nothing else is set), score (the cell's choices[0].score), would_panick, tb_null,
+    maskrule_ok, transcript / origin_idx / mutant_idx (None when the reference returns NULL or exits)."""
+    P, keep, orange, mrange = _problem(origin, mutant, mode, alntype, subst, L, match, mismatch, go, ge, diag_range,
+                                       origin_range, mutant_range, max_new_mins)
+    R = pwo_result()
+    rc = lib().pwo_traceback_from(C.byref(P), int(end[0]), int(end[1]), C.byref(R))
+    if rc == -3:
+        raise IndexError('end cell %r outside the table' % (tuple(end),))
+    if rc != 0:
+        raise ValueError('unsupported problem (rc=%d)' % rc)
+    out = dict(init_rc=R.init_rc, opt=None, no_choice=None, score=None, transcript=None, origin_idx=None,
+               mutant_idx=None, tb_null=None, would_panick=None, maskrule_ok=None)
+    if R.init_rc != 0:
+        return out
+    out['opt'] = (R.opt_i, R.opt_j)
+    out['no_choice'] = bool(R.no_choice)
+    if not R.no_choice:
+        out['score'] = R.score
+        out['would_panick'] = bool(R.would_panick)
+        out['tb_null'] = bool(R.tb_null)
+        out['maskrule_ok'] = bool(R.maskrule_ok)
+        # (start and transcript as the walk left them, also where the reference returns NULL: the kernels report them)
+        out['start'] = (R.origin_idx + orange[0], R.mutant_idx + mrange[0])
+        out['ops'] = C.string_at(R.transcript, R.tx_len).decode('ascii')
+        if not R.would_panick and not R.tb_null:
+            out['transcript'] = out['ops']
+            out['origin_idx'], out['mutant_idx'] = out['start']
     lib().pwo_free_result(C.byref(R))
     return out

@@ -302,4 +302,36 @@ int pwo_solve(const pwo_problem *p, pwo_result *r, double *Hout, unsigned char *
   return 0;
 }
 
+/* dptable_traceback(T, end) for an explicit end cell (pw.c:116-150): solve, then walk the explicit base chain from table
+ * cell (ei, ej).  The score is that cell's choices[0].score (pw.c:148).  A cell without a choice (num_choices == 0: the
+ * reference dereferences NULL there) is reported as r->no_choice = 1 and not walked. */
+int pwo_traceback_from(const pwo_problem *p, int ei, int ej, pwo_result *r) {
+  tbl t; long long n, c;
+  memset(&t, 0, sizeof t); memset(r, 0, sizeof *r);
+  r->opt_i = r->opt_j = -1;
+  if (p->max_new_mins > 0) return -2;
+  t.p = p;
+  r->init_rc = table_dims(&t);
+  r->dmin_c = t.dmin; r->dmax_c = t.dmax; r->num_rows = t.num_rows;
+  if (r->init_rc != 0) { tbl_free(&t); return 0; }
+  if (ei < 0 || ei >= t.num_rows || ej < 0 || ej >= t.row_len[ei]) { tbl_free(&t); return -3; }
+  n = t.row_off[t.num_rows];
+  r->cells = n;
+  t.H = (double *)malloc(sizeof(double) * (size_t)(n > 0 ? n : 1));
+  t.mask = (unsigned char *)calloc((size_t)(n > 0 ? n : 1), 1);
+  t.base = (unsigned char *)calloc((size_t)(n > 0 ? n : 1), 1);
+  { long long k; for (k = 0; k < n; k++) t.H[k] = NAN; }
+  fill(&t);
+  find_optimal(&t, &r->opt_i, &r->opt_j);
+  c = t.row_off[ei] + ej;
+  if (!t.mask[c]) r->no_choice = 1;
+  else {
+    r->score = t.H[c];
+    traceback(&t, ei, ej, r);
+    r->maskrule_ok = maskrule_agrees(&t, ei, ej);
+  }
+  tbl_free(&t);
+  return 0;
+}
+
 void pwo_free_result(pwo_result *r) { free(r->transcript); r->transcript = NULL; }

@@ -54,6 +54,7 @@ typedef struct {
   char *transcript;    /* malloc'd, NUL-terminated; caller frees with pwo_free_result           */
   int maskrule_ok;     /* 1 iff the mask-only predecessor rule (see pw_oracle.c) reproduces the explicit
                           base chain of this traceback -- pins the rule the device traceback relies on */
+  int no_choice;       /* pwo_traceback_from: the end cell holds no choice (the reference dereferences NULL there) */
 } pwo_result;
 
 /* Solve + end-cell search + traceback from the optimal cell.
@@ -65,6 +66,11 @@ int pwo_solve(const pwo_problem *p, pwo_result *r, double *Hout, unsigned char *
 
 /* Fill only (no end-cell search/traceback); for CPU-baseline timing of the recurrence alone. */
 long long pwo_cells(const pwo_problem *p);
+
+/* dptable_traceback from an explicit table cell (ei, ej): the fields of pwo_solve, the walk (transcript, start, tb_null,
+ * would_panick, maskrule_ok) from that cell instead of the optimum, score = its choices[0].score, or no_choice = 1 for a
+ * cell that holds none (nothing walked).  0; -2 as pwo_solve; -3 for a cell outside the table. */
+int pwo_traceback_from(const pwo_problem *p, int ei, int ej, pwo_result *r);
 
 void pwo_free_result(pwo_result *r);
 

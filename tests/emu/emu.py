@@ -31,14 +31,62 @@ def lib():
     return _lib
 
 
+def _table_cells(mode, X, Y, dr):
+    """Cells of the reference's table (banded: the clamped band's diagonals back to back)."""
+    if mode == 0:
+        return (X + 1) * (Y + 1)
+    dmin, dmax = max(dr[0], -Y), min(dr[1], X)
+    return sum(1 + min(d, 0) + min(X - d, Y) for d in range(dmin, dmax + 1))
+
+
+class _PlaneOut(object):
+    """Buffers of the whole-plane read-back (emu_set_masks_out) and of the walks from given end cells (emu_set_ends)."""
+
+    def __init__(self, cells, want_masks, ends, X, Y):
+        self.mask = np.zeros(max(cells, 1), np.uint8) if want_masks else None
+        self.ends = None if ends is None else np.ascontiguousarray(np.asarray(ends, np.int32).reshape(-1, 2))
+        n = 0 if self.ends is None else len(self.ends)
+        self.info = np.zeros(4 * max(n, 1), np.int32)
+        self.stride = X + Y + 2
+        self.tx = C.create_string_buffer(max(n, 1) * self.stride)
+
+    def __enter__(self):
+        lib().emu_set_masks_out(None if self.mask is None else self.mask.ctypes.data_as(C.POINTER(C.c_uint8)))
+        if self.ends is not None:
+            lib().emu_set_ends(self.ends.ctypes.data_as(C.POINTER(C.c_int)), len(self.ends),
+                               self.info.ctypes.data_as(C.POINTER(C.c_int)), self.tx, self.stride)
+        return self
+
+    def __exit__(self, *a):
+        lib().emu_set_masks_out(None)
+        lib().emu_set_ends(None, 0, None, None, 0)
+
+    def fill(self, out, cells, orange, mrange):
+        """Adds ``mask`` (cells of the table) and ``walks`` (one dict per end cell: origin_idx, mutant_idx, transcript,
+        status -- PW_ST_* bits) to a result dict."""
+        if self.mask is not None:
+            out['mask'] = self.mask[:cells].copy()
+        if self.ends is not None:
+            raw = self.tx.raw
+            walks = []
+            for e in range(len(self.ends)):
+                o, m, n, st = (int(v) for v in self.info[4 * e:4 * e + 4])
+                t = raw[e * self.stride:e * self.stride + n].decode('ascii') if n > 0 else ''
+                walks.append(dict(origin_idx=o + orange[0], mutant_idx=m + mrange[0], transcript=t, status=st))
+            out['walks'] = walks
+
+
 def solve(origin, mutant, mode=0, alntype=0, subst=None, L=None, match=1., mismatch=0., go=0., ge=0.,
           diag_range=None, origin_range=None, mutant_range=None, use_double=False, force_generic=False,
-          bk=8, want_table=False, packed16=False, waves=1, matrix=None, product_variant=False, **_):
+          bk=8, want_table=False, packed16=False, waves=1, matrix=None, product_variant=False, want_masks=False, end=None,
+          ends=None, **_):
     """One problem on one emulated kernel.  ``packed16``: 0 the 32-bit / f64 kernels; 1 the packed 16-bit body lane-packed
     (on ceil(ndiag / bk) lanes), 2 one pair per wavefront, 3 / 4 the same as 2 / 1 with every score times 4 (rule 3).
     ``matrix`` (packed only): None the matrix form where the scores need it (a non-simple matrix), False never, True always
     -- match / mismatch scores included; a matrix form that does not exist for the scores is an error.  ``product_variant``:
-    the 32-bit / f64 variant as the planner picks it (a matrix on the fast variants), else every matrix on the generic one."""
+    the 32-bit / f64 variant as the planner picks it (a matrix on the fast variants), else every matrix on the generic one.
+    ``want_masks``: also the decoded tie masks of every in-table cell (``mask``, the oracle's table order); ``end`` = (i, j)
+    or ``ends`` = [(i, j), ..]: the same plane walked from those table cells as well (``walks``, one dict each)."""
     o = np.asarray(origin, dtype=np.int32)
     m = np.asarray(mutant, dtype=np.int32)
     if L is None:
@@ -69,11 +117,15 @@ def solve(origin, mutant, mode=0, alntype=0, subst=None, L=None, match=1., misma
     lib().emu_set_waves(int(waves))
     lib().emu_set_packed_matrix(-1 if matrix is None else int(bool(matrix)))
     lib().emu_set_product_variant(int(bool(product_variant)))
-    rc = lib().emu_solve(mode, alntype, of.ctypes.data_as(C.POINTER(C.c_int)), X,
-                         mf.ctypes.data_as(C.POINTER(C.c_int)), Y, L,
-                         S.ctypes.data_as(C.POINTER(C.c_double)), C.c_double(go), C.c_double(ge),
-                         int(dr[0]), int(dr[1]), int(use_double), int(force_generic), bk,
-                         info, C.byref(score), txbuf, txcap, hp, int(packed16))
+    if end is not None:
+        ends = [end]
+    cells = _table_cells(mode, X, Y, dr)
+    with _PlaneOut(cells, want_masks, ends, X, Y) as po:
+        rc = lib().emu_solve(mode, alntype, of.ctypes.data_as(C.POINTER(C.c_int)), X,
+                             mf.ctypes.data_as(C.POINTER(C.c_int)), Y, L,
+                             S.ctypes.data_as(C.POINTER(C.c_double)), C.c_double(go), C.c_double(ge),
+                             int(dr[0]), int(dr[1]), int(use_double), int(force_generic), bk,
+                             info, C.byref(score), txbuf, txcap, hp, int(packed16))
     if rc != 0:
         raise ValueError('emu_solve rc=%d' % rc)
     out = dict(init_rc=info[0], opt=None, score=None, transcript=None, origin_idx=None,
@@ -83,6 +135,7 @@ def solve(origin, mutant, mode=0, alntype=0, subst=None, L=None, match=1., misma
     if info[0] != 0:
         return out
     out['num_rows'] = info[3]
+    po.fill(out, cells, orange, mrange)
     ex, ey = info[4], info[5]
     if ex < 0:
         out['opt'] = (-1, -1)
@@ -101,9 +154,10 @@ def solve(origin, mutant, mode=0, alntype=0, subst=None, L=None, match=1., misma
     return out
 
 
-def solve_strip(origin, mutant, alntype=0, match=1., mismatch=0., go=0., ge=0., epoch=7, byte_rows=True, subst=None, **_):
+def solve_strip(origin, mutant, alntype=0, match=1., mismatch=0., go=0., ge=0., epoch=7, byte_rows=True, subst=None,
+                want_masks=False, end=None, ends=None, **_):
     """Standard-mode problem through the strip pipeline (pw_strip.h): fill strip by strip, end-cell reduction, strip
-    walker, fix-up.  Same result dict as :func:`solve`."""
+    walker, fix-up.  Same result dict as :func:`solve` (``want_masks``, ``end`` / ``ends`` included)."""
     of = np.ascontiguousarray(np.asarray(origin, dtype=np.int32))
     mf = np.ascontiguousarray(np.asarray(mutant, dtype=np.int32))
     X, Y = len(of), len(mf)
@@ -121,9 +175,13 @@ def solve_strip(origin, mutant, alntype=0, match=1., mismatch=0., go=0., ge=0., 
         lib().emu_set_strip_matrix(S.ctypes.data_as(C.POINTER(C.c_double)), int(S.shape[0]))
     else:
         lib().emu_set_strip_matrix(None, 0)
-    rc = lib().emu_solve_strip(alntype, of.ctypes.data_as(C.POINTER(C.c_int)), X, mf.ctypes.data_as(C.POINTER(C.c_int)), Y,
-                               C.c_double(match), C.c_double(mismatch), C.c_double(go), C.c_double(ge), C.c_uint(epoch),
-                               info, C.byref(score), txbuf, txcap)
+    if end is not None:
+        ends = [end]
+    cells = (X + 1) * (Y + 1)
+    with _PlaneOut(cells, want_masks, ends, X, Y) as po:
+        rc = lib().emu_solve_strip(alntype, of.ctypes.data_as(C.POINTER(C.c_int)), X, mf.ctypes.data_as(C.POINTER(C.c_int)),
+                                   Y, C.c_double(match), C.c_double(mismatch), C.c_double(go), C.c_double(ge),
+                                   C.c_uint(epoch), info, C.byref(score), txbuf, txcap)
     if rc != 0:
         raise ValueError('emu_solve_strip rc=%d' % rc)
     out = dict(init_rc=info[0], opt=None, score=None, transcript=None, origin_idx=None,
@@ -131,6 +189,7 @@ def solve_strip(origin, mutant, alntype=0, match=1., mismatch=0., go=0., ge=0., 
     if info[0] != 0:
         return out
     out['num_rows'] = info[3]
+    po.fill(out, cells, (0, X), (0, Y))
     if info[4] < 0:
         out['opt'] = (-1, -1)
         return out
@@ -159,7 +218,8 @@ def solve_planned(pairs, flags=0, **kw):
     batch's shapes, with the ``PWLIB_*`` knobs of the environment): BK, lane packing, wavefronts per pair, packed rule,
     matrix form, int32 / f64, the strips, dyadic scaling.  ``pairs``: list of (origin, mutant); ``kw``: the oracle's
     scoring arguments (``mode``, ``alntype``, ``L``, ``subst`` or ``match`` / ``mismatch``, ``go``, ``ge``,
-    ``diag_range`` -- one band, or a list with one per pair).  Returns ``(plan, [result dict per pair])``.  Raises
+    ``diag_range`` -- one band, or a list with one per pair; ``want_masks``, ``end`` / ``ends`` as in :func:`solve`, for
+    every pair).  Returns ``(plan, [result dict per pair])``.  Raises
     :class:`NotEmulated` for the tiled kernel instead of running another form."""
     from biseqt_amd.batch import plan_only
     mode, alntype = kw.get('mode', 0), kw.get('alntype', 0)
@@ -178,7 +238,8 @@ def solve_planned(pairs, flags=0, **kw):
         raise NotEmulated('the tiled kernel (%s) is not emulated' % name)
     f = float(1 << plan['scale_shift'])          # dyadic scaling: the kernels hold every score times 2^shift
     S = (np.asarray(subst, np.float64) * f).tolist()
-    base = dict(mode=mode, alntype=alntype, L=L, subst=S, go=go * f, ge=ge * f)
+    base = dict(mode=mode, alntype=alntype, L=L, subst=S, go=go * f, ge=ge * f, want_masks=kw.get('want_masks', False),
+                end=kw.get('end'), ends=kw.get('ends'))
     out, seen = [], {}
     for (o, m), d in zip(pairs, drs):
         key = (np.asarray(o, np.int32).tobytes(), np.asarray(m, np.int32).tobytes(), d)
@@ -192,7 +253,8 @@ def solve_planned(pairs, flags=0, **kw):
             byte_rows = L <= 4 and all(v == int(v) and -128 <= v <= 127 for row in S for v in row) and \
                 os.environ.get('PWLIB_STRIP_NO_BYTE_ROWS', '') in ('', '0')
             r = solve_strip(o, m, alntype=alntype, match=S[0][0], mismatch=S[0][1] if L > 1 else S[0][0], go=go * f,
-                            ge=ge * f, byte_rows=byte_rows, subst=None if simple else S)
+                            ge=ge * f, byte_rows=byte_rows, subst=None if simple else S, want_masks=base['want_masks'],
+                            end=base['end'], ends=base['ends'])
         else:
             g = _KERNEL.match(name)
             if not g:

@@ -11,6 +11,7 @@
 #include <string.h>
 #include <ucontext.h>
 
+#include <algorithm>
 #include <functional>
 #include <vector>
 
@@ -204,6 +205,28 @@ extern "C" void emu_set_packed_matrix(int v) { g_packed_matrix = v < 0 ? -1 : (v
 int g_product_variant = 0;
 extern "C" void emu_set_product_variant(int v) { g_product_variant = v != 0; }
 
+// Whole-plane read-back and walks from given end cells (tests/test_emu_whole_plane.py), for the next emu_solve /
+// emu_solve_strip call: the decoded tie masks of every in-table cell (pw_strip.h, mask_table: the product's read-back), and
+// per end cell (table i, j) the walk's start, transcript length and status (4 ints) and its transcript (`stride` bytes each).
+uint8_t* g_maskout = nullptr;
+const int* g_ends = nullptr;
+int g_nends = 0, g_end_stride = 0;
+int* g_end_info = nullptr;
+char* g_end_tx = nullptr;
+extern "C" void emu_set_masks_out(uint8_t* out) { g_maskout = out; }
+extern "C" void emu_set_ends(const int* ends, int n, int* info, char* tx, int stride) {
+  g_ends = ends; g_nends = ends ? n : 0; g_end_info = info; g_end_tx = tx; g_end_stride = stride;
+}
+// one walk's record and transcript (ops right-aligned in `slot`, tx_cap bytes) into end slot e
+void record_end(int e, const pw::Result& r, const std::vector<uint8_t>& slot, int tx_cap) {
+  int* o = g_end_info + 4 * e;
+  o[0] = r.origin_idx; o[1] = r.mutant_idx; o[2] = r.tx_len; o[3] = r.status;
+  char* t = g_end_tx + (size_t)e * g_end_stride;
+  const int n = r.tx_len > 0 && r.tx_len < g_end_stride ? r.tx_len : 0;
+  if (n) memcpy(t, slot.data() + tx_cap - n, (size_t)n);
+  t[n] = 0;
+}
+
 template <typename T, int BK> struct Run16 {
   static bool go(const pw::FillParams<T>&, const pw::PairDesc&) { return false; }
 };
@@ -354,6 +377,15 @@ int solve_T(int mode, int type, const int* origin, int X, const int* mutant, int
     txbuf[res.tx_len] = 0;
   } else if (txcap > 0) txbuf[0] = 0;
   if (hdump) for (size_t i = 0; i < hd.size(); i++) hdump[i] = (double)hd[i];
+  if (g_maskout) pw::mask_table(pd, masks.data(), a.banded != 0, g_maskout);
+  for (int e = 0; e < g_nends; e++) {           // the same plane walked from each given end cell
+    pw::Result r = res;
+    std::fill(tx.begin(), tx.end(), (uint8_t)0);
+    tp.results = &r; tp.ends = g_ends + 2 * e;
+    pw::trace_walk(tp, 0, win);
+    pw::trace_fixup_serial(tp, 0);
+    record_end(e, r, tx, pd.tx_cap);
+  }
   return 0;
 }
 
@@ -439,6 +471,7 @@ extern "C" int emu_solve_strip(int type, const int* origin, int X, const int* mu
   pw::TraceParams fp;
   memset(&fp, 0, sizeof fp);
   fp.pairs = &pd; fp.arena = arena.data(); fp.results = &res; fp.transcripts = tx.data(); fp.npairs = 1;
+  const pw::Result filled = res;                // (the record as the fill and the reduction left it)
   pw::trace_fixup_serial(fp, 0);
   info[4] = res.opt_i; info[5] = res.opt_j; info[6] = res.origin_idx; info[7] = res.mutant_idx;
   info[8] = res.tx_len; info[9] = res.status;
@@ -447,6 +480,15 @@ extern "C" int emu_solve_strip(int type, const int* origin, int X, const int* mu
     memcpy(txbuf, tx.data() + pd.tx_cap - res.tx_len, (size_t)res.tx_len);
     txbuf[res.tx_len] = 0;
   } else if (txcap > 0) txbuf[0] = 0;
+  if (g_maskout) { pd.layout = 1; pw::mask_table(pd, masks.data(), false, g_maskout); }
+  for (int e = 0; e < g_nends; e++) {
+    pw::Result r = filled;
+    std::fill(tx.begin(), tx.end(), (uint8_t)0);
+    tp.result = &r; tp.ends = g_ends + 2 * e; fp.results = &r;
+    { Emu emu; emu.run([&]() { pw::strip_walk<EmuPS>(tp, win.data()); }); }
+    pw::trace_fixup_serial(fp, 0);
+    record_end(e, r, tx, pd.tx_cap);
+  }
   return 0;
 }
 
