@@ -89,6 +89,7 @@ PW_FN int strip_fifo_pitch(int Y) { return (Y + 1 + 32 + 63) / 64 * 64; }
 PW_FN uint64_t strip_mask_index(int nkq, int w, int q, int lane) {      // in dwords
   return ((uint64_t)((uint64_t)w * nkq + q) * 64 + lane) * 4;
 }
+static inline int strip_count(int X) { return (X + 1 + 63) / 64; }                        // strips of 64 rows: rows 0 .. X
 static inline int strip_nkq(int Y) { return (Y + 64 + kStripBlock - 1) / kStripBlock; }   // 32-step groups per strip row
 
 // Host read-back of layout 1 (tests, pw_batch_masks): the tie mask of cell (x, y) -- strip x >> 6, lane x & 63, step

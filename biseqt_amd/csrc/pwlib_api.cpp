@@ -14,6 +14,7 @@
 #include <algorithm>
 #include <string>
 #include <chrono>
+#include <memory>
 #include <mutex>
 #include <thread>
 #include <vector>
@@ -89,7 +90,7 @@ void* pool_take(int device, size_t bytes, size_t* got) {
   g_pool.erase(g_pool.begin() + best);
   return p;
 }
-// (the caller has made sure no kernel still uses p: batch_free_device synchronises first)
+// (the caller has made sure no kernel still uses p: ~pw_batch synchronises first)
 void pool_give(int device, void* p, size_t bytes) {
   if (!p) return;
   if (device >= 0 && device < kMaxDevices && bytes >= (1u << 20)) {
@@ -138,6 +139,27 @@ hipError_t pool_alloc(int device, void** p, size_t bytes, size_t* got) {
   return e;
 }
 
+// A buffer of the pool: taken through pool_alloc, handed back by pool_give when its owner goes (or when it is allocated
+// again).  The owner makes sure that no kernel still uses it by then.
+template <typename T>
+struct PoolBuffer {
+  int device = -1;
+  T* p = nullptr;
+  size_t bytes = 0;
+  PoolBuffer() = default;
+  PoolBuffer(PoolBuffer&& o) noexcept : device(o.device), p(std::exchange(o.p, nullptr)), bytes(std::exchange(o.bytes, 0)) {}
+  PoolBuffer& operator=(PoolBuffer&& o) noexcept { std::swap(device, o.device); std::swap(p, o.p); std::swap(bytes, o.bytes); return *this; }
+  ~PoolBuffer() { pool_give(device, p, bytes); }
+  hipError_t alloc(int dev, size_t want) {
+    pool_give(device, std::exchange(p, nullptr), bytes);
+    device = dev;
+    void* q = nullptr;
+    const hipError_t e = pool_alloc(dev, &q, want, &bytes);
+    if (e == hipSuccess) p = (T*)q;
+    return e;
+  }
+};
+
 thread_local std::string g_err;
 
 int fail(const std::string& msg) { g_err = msg; return -1; }
@@ -148,7 +170,7 @@ struct BkClass {
   int bk = 0;
   int nw = 1;                   // wavefronts per pair (> 1: multi-wavefront kernel for wide bands)
   std::vector<int32_t> order;   // pair indices, largest table first
-  int32_t* d_order = nullptr;
+  DeviceBuffer d_order;         // int32_t[order.size()]
 };
 
 }  // namespace
@@ -173,77 +195,57 @@ struct pw_batch {
   std::vector<pw::WaveDesc> waves;      // lane-packed kernel: one per wavefront
   std::vector<int32_t> strips;          // standard-mode pairs wider than a workgroup: the strip pipeline (K2c, pw_strip.h)
   std::vector<uint32_t> strip_ctl_init;                   // per strip pair: the 16 dwords its control block starts from
-  uint64_t* d_fifo = nullptr; size_t fifo_alloc = 0, fifo_bytes = 0;   // FIFO rows of the largest strip pair (pairs run one after another)
-  pw::StripBest* d_sbest = nullptr;      // [max strips]
-  uint32_t* d_ctl = nullptr;             // [strip pairs][2]: work queue head, abort flag
+  PoolBuffer<uint64_t> d_fifo; size_t fifo_bytes = 0;   // FIFO rows of the largest strip pair (pairs run one after another)
+  DeviceBuffer d_sbest;                  // pw::StripBest[max strips]
+  DeviceBuffer d_ctl;                    // uint32_t[strip pairs][16]: control blocks (work queue head, abort flag, ..)
   std::vector<int32_t> tiled;           // pairs that go through the time-blocked tiled kernel (K2b)
-  void* d_state[2] = {nullptr, nullptr}; // their per-diagonal state, double buffered (shared: pairs run one after another)
+  DeviceBuffer d_state[2];               // their per-diagonal state, double buffered (shared: pairs run one after another)
   int32_t st_pitch = 0;
   int packed_seg = 0, packed_rule = 0, packed_nw = 1;     // packed_nw: wavefronts per pair (K2a with the 16-bit body)
   int packed_mat = 0;                                     // the packed kernel reads a substitution matrix (WaveFill16<.., MAT>)
-  pw::WaveDesc* d_waves = nullptr;
+  DeviceBuffer d_waves;                  // pw::WaveDesc[waves.size()]
   int64_t cells = 0, alg_bytes = 0;
-  // device
-  uint8_t* d_arena = nullptr; uint64_t arena_bytes = 0;
-  bool arena_shared = false;             // PW_FLAG_SHARED_ARENA: d_arena belongs to the caller (pw_batch_share_arena)
-  pw::PairDesc* d_pairs = nullptr;
-  uint32_t* d_masks = nullptr; uint64_t mask_words = 0; size_t masks_alloc = 0, arena_alloc = 0, pairs_alloc = 0, results_alloc = 0;
-  void* d_hdump = nullptr; uint64_t h_elems = 0;
-  pw::Result* d_results = nullptr;
-  uint8_t* d_tx = nullptr; uint64_t tx_bytes = 0; size_t tx_alloc = 0;
-  void* d_subst = nullptr;
-  int32_t* d_ends = nullptr;
-  uint8_t* d_txpacked = nullptr; size_t txpacked_alloc = 0;    // pw_batch_pack_transcripts: the ops back to back
-  uint64_t* d_txoffsets = nullptr;                              // [n + 1]
-  hipEvent_t ev_fill0 = nullptr, ev_fill1 = nullptr, ev_tr0 = nullptr, ev_tr1 = nullptr;
+  // device (~pw_batch releases all of it)
+  bool on_device = false;                // batch_alloc ran: a batch that only planned makes no HIP call when it goes
+  PoolBuffer<uint8_t> arena; uint64_t arena_bytes = 0;
+  uint8_t* d_arena = nullptr;            // the arena the kernels read: `arena`, or the caller's (pw_batch_share_arena)
+  bool arena_shared = false;             // PW_FLAG_SHARED_ARENA: the batch owns no arena
+  PoolBuffer<pw::PairDesc> d_pairs;
+  PoolBuffer<uint32_t> d_masks; uint64_t mask_words = 0;
+  DeviceBuffer d_hdump; uint64_t h_elems = 0;   // int32_t or double score planes (PW_FLAG_DUMP_SCORES)
+  PoolBuffer<pw::Result> d_results;
+  PoolBuffer<uint8_t> d_tx; uint64_t tx_bytes = 0;
+  DeviceBuffer d_subst;                  // int32_t or double [L][L]
+  DeviceBuffer d_ends;                   // int32_t[n][2]: pw_batch_traceback_from
+  PoolBuffer<uint8_t> d_txpacked;        // pw_batch_pack_transcripts: the ops back to back
+  DeviceBuffer d_txoffsets;              // uint64_t[n + 1]
+  DeviceEvent ev_fill0, ev_fill1, ev_tr0, ev_tr1;
   bool fill_timed = false, trace_timed = false;
-  // scores as the caller gave them (batch_build may scale b->subst / go / ge by a power of two)
+  // scores as the caller gave them (batch_plan may scale b->subst / go / ge by a power of two)
   std::vector<double> subst_in; double go_in = 0, ge_in = 0;
   // Strip pairs whose pipeline gave up waiting (PW_ST_BADPATH with no end cell) are solved again by a batch of one with the
   // strips disabled (repair_strip_pair); the replacement lives as long as the batch and serves every later traceback
-  std::vector<std::pair<int32_t, pw_batch*>> repaired;
+  std::vector<std::pair<int32_t, std::unique_ptr<pw_batch>>> repaired;
   // one event per stream the batch was launched on, re-recorded behind every launch sequence: destroying the batch waits
   // for exactly these (not for the device: other batches' streams keep running)
-  std::vector<std::pair<hipStream_t, hipEvent_t>> done_events;
+  std::vector<std::pair<hipStream_t, DeviceEvent>> done_events;
   bool traced = false, traced_from = false;          // what the last traceback call was (a repaired pair repeats it)
   std::vector<int32_t> last_ends;
+  ~pw_batch();
 };
 
-namespace {
-
-int batch_free_device(pw_batch* b) {
-  if (!b) return 0;
-  for (auto& r : b->repaired) pw_batch_destroy(r.second);
-  b->repaired.clear();
-  (void)hipSetDevice(b->device);
-  // the buffers are parked for the next batch, not freed (hipFree would synchronise by itself): make sure nothing that
-  // was launched for THIS batch still reads or writes them -- the events recorded behind its launches, stream by stream
-  // (a device-wide synchronisation would stall every other batch in flight)
-  for (auto& se : b->done_events) { (void)hipEventSynchronize(se.second); (void)hipEventDestroy(se.second); }
-  b->done_events.clear();
-  for (auto& c : b->classes) if (c.d_order) (void)hipFree(c.d_order);
-  if (!b->arena_shared) pool_give(b->device, b->d_arena, b->arena_alloc);
-  pool_give(b->device, b->d_pairs, b->pairs_alloc);
-  pool_give(b->device, b->d_masks, b->masks_alloc);
-  if (b->d_hdump) (void)hipFree(b->d_hdump);
-  pool_give(b->device, b->d_results, b->results_alloc);
-  pool_give(b->device, b->d_tx, b->tx_alloc);
-  if (b->d_subst) (void)hipFree(b->d_subst);
-  if (b->d_ends) (void)hipFree(b->d_ends);
-  pool_give(b->device, b->d_txpacked, b->txpacked_alloc);
-  if (b->d_txoffsets) (void)hipFree(b->d_txoffsets);
-  if (b->d_waves) (void)hipFree(b->d_waves);
-  pool_give(b->device, b->d_fifo, b->fifo_alloc);
-  if (b->d_sbest) (void)hipFree(b->d_sbest);
-  if (b->d_ctl) (void)hipFree(b->d_ctl);
-  if (b->d_state[0]) (void)hipFree(b->d_state[0]);
-  if (b->d_state[1]) (void)hipFree(b->d_state[1]);
-  if (b->ev_fill0) (void)hipEventDestroy(b->ev_fill0);
-  if (b->ev_fill1) (void)hipEventDestroy(b->ev_fill1);
-  if (b->ev_tr0) (void)hipEventDestroy(b->ev_tr0);
-  if (b->ev_tr1) (void)hipEventDestroy(b->ev_tr1);
-  return 0;
+// The members free themselves when the body is done; the body makes that safe.  The pool's buffers are parked for the
+// next batch, not freed (freeing would synchronise by itself), and pool_give reads the free memory of the current device:
+// the batch's device is selected, and nothing that was launched for THIS batch may still read or write them -- the events
+// recorded behind its launches, stream by stream (a device-wide synchronisation would stall every other batch in flight).
+pw_batch::~pw_batch() {
+  repaired.clear();
+  if (!on_device) return;
+  (void)hipSetDevice(device);
+  for (auto& se : done_events) (void)hipEventSynchronize(se.second.e);
 }
+
+namespace {
 
 // The planner's environment knobs (pw_plan.h, PlanKnobs), read once per batch.
 pw::PlanKnobs plan_knobs() {
@@ -265,6 +267,24 @@ pw::PlanKnobs plan_knobs() {
   const char* bk = getenv("PWLIB_PACKED_BK");
   if (bk && *bk) { k.packed_bk_forced = true; k.packed_bk = atoi(bk); k.packed_bk_seg = strchr(bk, 's') != nullptr; }
   return k;
+}
+
+// The arguments of pw_batch_create / pw_plan_only, checked in this order, copied into b.  A NULL score matrix is one of
+// pw_plan_only's bad arguments; pw_batch_create reports it with the alphabet.
+int batch_inputs(pw_batch* b, bool plan_only, const pw_scoring* sc, int32_t n_pairs, const pw_pair* pairs, uint64_t arena_bytes,
+                 uint32_t flags) {
+  if (!sc || n_pairs < 0 || (n_pairs > 0 && !pairs) || (plan_only && !sc->subst))
+    return fail(plan_only ? "pw_plan_only: bad arguments" : "pw_batch_create: bad arguments");
+  if (sc->mode != pw::STD_MODE && sc->mode != pw::BANDED_MODE) return fail("unknown alignment mode");
+  if (sc->type < 0 || sc->type > (sc->mode == pw::STD_MODE ? 6 : 2)) return fail("unknown alignment type");
+  if (sc->alphabet_len < 1 || sc->alphabet_len > 256 || !sc->subst) return fail("alphabet_len must be 1..256 with a score matrix");
+  b->n = n_pairs; b->flags = flags;
+  b->mode = sc->mode; b->type = sc->type; b->L = sc->alphabet_len; b->go = sc->go; b->ge = sc->ge;
+  b->subst.assign(sc->subst, sc->subst + (size_t)b->L * b->L);
+  b->subst_in = b->subst; b->go_in = b->go; b->ge_in = b->ge;
+  b->pairs.assign(pairs, pairs + n_pairs);
+  b->arena_bytes = arena_bytes;
+  return 0;
 }
 
 // The packed 16-bit body: consecutive (similar length) pairs share a wavefront (p16.seg), one WaveDesc per wavefront
@@ -423,7 +443,7 @@ int batch_plan(pw_batch* b) {
     d.h_off = h_elems;
     if (lay.kind == pw::PAIR_STRIPS) {
       // rows in strips of 64, a pipeline of wavefronts
-      const int nstrips = (d.X + 1 + 63) / 64, nkq = (d.Y + 64 + pw::kStripBlock - 1) / pw::kStripBlock;
+      const int nstrips = pw::strip_count(d.X), nkq = pw::strip_nkq(d.Y);
       d.layout = 1;
       mask_words += (uint64_t)nstrips * nkq * 64 * 4;
       b->strips.push_back(k);
@@ -457,71 +477,66 @@ int batch_alloc(pw_batch* b) {
   const bool tim = env_int("PWLIB_TIMING", 0) != 0;
   auto tnow = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   const double t_plan = tnow();
-  HIP_TRY(hipSetDevice(b->device));
-  if (!b->arena_shared)
-    HIP_TRY(pool_alloc(b->device, (void**)&b->d_arena, b->arena_bytes + 16, &b->arena_alloc));   // kernels read whole dwords: slack past the last frame
-  HIP_TRY(pool_alloc(b->device, (void**)&b->d_pairs, sizeof(pw::PairDesc) * std::max<int32_t>(b->n, 1), &b->pairs_alloc));
-  HIP_TRY(pool_alloc(b->device, (void**)&b->d_masks, 4 * mask_words + 64, &b->masks_alloc));   // slack: the walker reads whole 16-byte groups
-  HIP_TRY(pool_alloc(b->device, (void**)&b->d_results, sizeof(pw::Result) * std::max<int32_t>(b->n, 1), &b->results_alloc));
-  HIP_TRY(pool_alloc(b->device, (void**)&b->d_tx, std::max<uint64_t>(tx_bytes, 16), &b->tx_alloc));
+  const int dev = b->device;
+  b->on_device = true;
+  HIP_TRY(hipSetDevice(dev));
+  if (!b->arena_shared) {
+    HIP_TRY(b->arena.alloc(dev, b->arena_bytes + 16));   // kernels read whole dwords: slack past the last frame
+    b->d_arena = b->arena.p;
+  }
+  HIP_TRY(b->d_pairs.alloc(dev, sizeof(pw::PairDesc) * std::max<int32_t>(b->n, 1)));
+  HIP_TRY(b->d_masks.alloc(dev, 4 * mask_words + 64));   // slack: the walker reads whole 16-byte groups
+  HIP_TRY(b->d_results.alloc(dev, sizeof(pw::Result) * std::max<int32_t>(b->n, 1)));
+  HIP_TRY(b->d_tx.alloc(dev, std::max<uint64_t>(tx_bytes, 16)));
   const size_t esz = b->use_f64 ? 8 : 4;
-  if (h_elems) HIP_TRY(hipMalloc(&b->d_hdump, esz * h_elems));
-  HIP_TRY(hipMalloc(&b->d_subst, esz * (size_t)L * L));
+  if (h_elems) HIP_TRY(b->d_hdump.ensure(esz * h_elems));
+  HIP_TRY(b->d_subst.ensure(esz * (size_t)L * L));
   if (b->use_f64) {
-    HIP_TRY(hipMemcpy(b->d_subst, b->subst.data(), 8 * (size_t)L * L, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(b->d_subst.p, b->subst.data(), 8 * (size_t)L * L, hipMemcpyHostToDevice));
   } else {
     std::vector<int32_t> si((size_t)L * L);
     for (size_t i = 0; i < si.size(); i++) si[i] = (int32_t)b->subst[i];
-    HIP_TRY(hipMemcpy(b->d_subst, si.data(), 4 * si.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(b->d_subst.p, si.data(), 4 * si.size(), hipMemcpyHostToDevice));
   }
-  if (b->n) HIP_TRY(hipMemcpy(b->d_pairs, b->descs.data(), sizeof(pw::PairDesc) * b->n, hipMemcpyHostToDevice));
+  if (b->n) HIP_TRY(hipMemcpy(b->d_pairs.p, b->descs.data(), sizeof(pw::PairDesc) * b->n, hipMemcpyHostToDevice));
   if (!b->strips.empty()) {
     int maxs = 0;
-    for (int32_t k : b->strips) maxs = std::max(maxs, (b->descs[k].X + 1 + 63) / 64);
-    HIP_TRY(pool_alloc(b->device, (void**)&b->d_fifo, b->fifo_bytes, &b->fifo_alloc));
+    for (int32_t k : b->strips) maxs = std::max(maxs, pw::strip_count(b->descs[k].X));
+    HIP_TRY(b->d_fifo.alloc(dev, b->fifo_bytes));
     // granules are recognised by their epoch tag: whatever the (possibly recycled) buffer holds must never look like one
-    HIP_TRY(hipMemset(b->d_fifo, 0, b->fifo_bytes));
-    HIP_TRY(hipMalloc((void**)&b->d_sbest, sizeof(pw::StripBest) * (size_t)maxs));
-    HIP_TRY(hipMalloc((void**)&b->d_ctl, 64 * b->strips.size()));
+    HIP_TRY(hipMemset(b->d_fifo.p, 0, b->fifo_bytes));
+    HIP_TRY(b->d_sbest.ensure(sizeof(pw::StripBest) * (size_t)maxs));
+    HIP_TRY(b->d_ctl.ensure(64 * b->strips.size()));
   }
-  if (!b->tiled.empty()) {
-    HIP_TRY(hipMalloc(&b->d_state[0], (size_t)5 * b->st_pitch * 8));
-    HIP_TRY(hipMalloc(&b->d_state[1], (size_t)5 * b->st_pitch * 8));
-  }
+  if (!b->tiled.empty())
+    for (DeviceBuffer& st : b->d_state) HIP_TRY(st.ensure((size_t)5 * b->st_pitch * 8));
   if (!b->waves.empty()) {
-    HIP_TRY(hipMalloc((void**)&b->d_waves, sizeof(pw::WaveDesc) * b->waves.size()));
-    HIP_TRY(hipMemcpy(b->d_waves, b->waves.data(), sizeof(pw::WaveDesc) * b->waves.size(), hipMemcpyHostToDevice));
+    HIP_TRY(b->d_waves.ensure(sizeof(pw::WaveDesc) * b->waves.size()));
+    HIP_TRY(hipMemcpy(b->d_waves.p, b->waves.data(), sizeof(pw::WaveDesc) * b->waves.size(), hipMemcpyHostToDevice));
   }
   for (auto& c : b->classes) {
-    HIP_TRY(hipMalloc((void**)&c.d_order, 4 * c.order.size()));
-    HIP_TRY(hipMemcpy(c.d_order, c.order.data(), 4 * c.order.size(), hipMemcpyHostToDevice));
+    HIP_TRY(c.d_order.ensure(4 * c.order.size()));
+    HIP_TRY(hipMemcpy(c.d_order.p, c.order.data(), 4 * c.order.size(), hipMemcpyHostToDevice));
   }
   {  // records of pairs no kernel will touch
     std::vector<pw::Result> init(std::max<int32_t>(b->n, 1));
     for (auto& r : init) { r.score = 0; r.opt_i = r.opt_j = -1; r.origin_idx = r.mutant_idx = 0; r.tx_len = 0; r.status = 0; }
-    HIP_TRY(hipMemcpy(b->d_results, init.data(), sizeof(pw::Result) * init.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(b->d_results.p, init.data(), sizeof(pw::Result) * init.size(), hipMemcpyHostToDevice));
   }
-  if (b->flags & PW_FLAG_PROFILE) {
-    HIP_TRY(hipEventCreate(&b->ev_fill0)); HIP_TRY(hipEventCreate(&b->ev_fill1));
-    HIP_TRY(hipEventCreate(&b->ev_tr0)); HIP_TRY(hipEventCreate(&b->ev_tr1));
-  }
+  if (b->flags & PW_FLAG_PROFILE)
+    for (DeviceEvent* ev : {&b->ev_fill0, &b->ev_fill1, &b->ev_tr0, &b->ev_tr1}) HIP_TRY(ev->create());
   if (tim && b->n > 1000) fprintf(stderr, "pwlib timing: batch of %d pairs: planning %.1f ms, device buffers + descriptors %.1f ms\n", b->n, b->plan_ms, tnow() - t_plan);
   return 0;
-}
-
-int batch_build(pw_batch* b) {
-  if (batch_plan(b) != 0) return -1;
-  return batch_alloc(b);
 }
 
 // Records "everything launched for this batch on `st` so far" (see pw_batch::done_events).
 int mark_done(pw_batch* b, hipStream_t st) {
   for (auto& se : b->done_events)
-    if (se.first == st) { HIP_TRY(hipEventRecord(se.second, st)); return 0; }
-  hipEvent_t ev = nullptr;
-  HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-  b->done_events.emplace_back(st, ev);
-  HIP_TRY(hipEventRecord(ev, st));
+    if (se.first == st) { HIP_TRY(hipEventRecord(se.second.e, st)); return 0; }
+  DeviceEvent ev;
+  HIP_TRY(hipEventCreateWithFlags(&ev.e, hipEventDisableTiming));
+  b->done_events.emplace_back(st, std::move(ev));
+  HIP_TRY(hipEventRecord(b->done_events.back().second.e, st));
   return 0;
 }
 
@@ -536,12 +551,10 @@ int xcc_queues(int device, int32_t* xcc_queue) {
   std::lock_guard<std::mutex> lk(mu);
   if (device < 0 || device >= kMaxDevices) return 0;
   if (cached_n[device] == 0) {
-    uint32_t* d = nullptr; uint32_t h[8] = {0};
-    if (hipMalloc((void**)&d, sizeof h) != hipSuccess) return 0;
-    bool ok = hipMemset(d, 0, sizeof h) == hipSuccess && pw::launch_xcc_census(d, nullptr) == hipSuccess &&
-              hipMemcpy(h, d, sizeof h, hipMemcpyDeviceToHost) == hipSuccess;
-    (void)hipFree(d);
-    if (!ok) return 0;
+    DeviceBuffer d; uint32_t h[8] = {0};
+    if (d.ensure(sizeof h) != hipSuccess || hipMemset(d.p, 0, sizeof h) != hipSuccess ||
+        pw::launch_xcc_census((uint32_t*)d.p, nullptr) != hipSuccess || hipMemcpy(h, d.p, sizeof h, hipMemcpyDeviceToHost) != hipSuccess)
+      return 0;
     int n = 0;
     for (int i = 0; i < 8; i++) cached_map[device][i] = h[i] ? n++ : -1;
     cached_n[device] = n;
@@ -568,10 +581,11 @@ int launch_strip_fills(pw_batch* b, hipStream_t st) {
     pw::StripParams a;
     memset(&a, 0, sizeof a);
     a.arena = b->d_arena; a.o_off = d.o_off; a.m_off = d.m_off;
-    a.fifo = b->d_fifo; a.masks = b->d_masks + d.mask_off; a.sbest = b->d_sbest; a.ctl = b->d_ctl + 16 * q++;
-    a.result = b->d_results + k;
+    a.fifo = b->d_fifo.p; a.masks = b->d_masks.p + d.mask_off; a.sbest = (pw::StripBest*)b->d_sbest.p;
+    a.ctl = (uint32_t*)b->d_ctl.p + 16 * q++;
+    a.result = b->d_results.p + k;
     a.X = d.X; a.Y = d.Y;
-    a.nstrips = (d.X + 1 + 63) / 64; a.nkq = (d.Y + 64 + pw::kStripBlock - 1) / pw::kStripBlock;
+    a.nstrips = pw::strip_count(d.X); a.nkq = pw::strip_nkq(d.Y);
     a.fifo_pitch = pw::strip_fifo_pitch(d.Y);
     uint32_t e = g_strip_epoch.fetch_add(1) & 0xffffffu;          // 24 bits: the tag's other 8 are the column's low bits
     if (e == 0) e = g_strip_epoch.fetch_add(1) & 0xffffffu;
@@ -588,11 +602,11 @@ int launch_strip_fills(pw_batch* b, hipStream_t st) {
     // tuning aid: PWLIB_STRIP_TRACE=<file> dumps per-strip clock stamps (100 MHz; [8 + i]: shader-clock counts at the same points) of the first strip pair: dequeue, set-up
     // done, first granules seen, steps 64 / 96 reached, end; [7] = XCC id | workgroup << 8
     const char* trace = getenv("PWLIB_STRIP_TRACE");
-    uint64_t* d_stamps = nullptr;
+    DeviceBuffer stamps;
     if (trace && *trace && q == 1) {
-      HIP_TRY(hipMalloc((void**)&d_stamps, (size_t)a.nstrips * 128));
-      HIP_TRY(hipMemset(d_stamps, 0, (size_t)a.nstrips * 128));
-      a.stamps = d_stamps;
+      HIP_TRY(stamps.ensure((size_t)a.nstrips * 128));
+      HIP_TRY(hipMemset(stamps.p, 0, (size_t)a.nstrips * 128));
+      a.stamps = (uint64_t*)stamps.p;
     }
     const bool byte_rows = strip_byte_rows_ok(b);
     if (!byte_rows && !b->simple) return fail("internal: a substitution matrix on the strips needs their byte rows");
@@ -606,30 +620,36 @@ int launch_strip_fills(pw_batch* b, hipStream_t st) {
     // (written once per batch in effect: every solve stores the same values, also while an earlier copy may still be reading them)
     for (int z = 0; z < 16; z++) ci[z] = (z >= pw::kStripRows && z < pw::kStripRows + 4) ? rows[z - pw::kStripRows] : 0u;
     HIP_TRY(pw::launch_strip_fill(a, track, byte_rows, ci, workers, lds_kb << 10, st));
-    if (d_stamps) {
+    if (stamps.p) {
       std::vector<uint64_t> h((size_t)a.nstrips * 16);
       HIP_TRY(hipStreamSynchronize(st));
-      HIP_TRY(hipMemcpy(h.data(), d_stamps, h.size() * 8, hipMemcpyDeviceToHost));
-      (void)hipFree(d_stamps);
+      HIP_TRY(hipMemcpy(h.data(), stamps.p, h.size() * 8, hipMemcpyDeviceToHost));
       if (FILE* f = fopen(trace, "wb")) { fwrite(h.data(), 8, h.size(), f); fclose(f); }
     }
   }
   return 0;
 }
 
+// The fields every fill kernel reads
 template <typename T>
-int launch_all_fills(pw_batch* b, hipStream_t st) {
+pw::FillParams<T> fill_params(const pw_batch* b) {
   pw::FillParams<T> a;
   memset(&a, 0, sizeof a);
-  a.pairs = b->d_pairs; a.arena = b->d_arena; a.masks = b->d_masks;
-  a.hdump = (T*)b->d_hdump; a.results = b->d_results; a.subst = (const T*)b->d_subst;
+  a.pairs = b->d_pairs.p; a.arena = b->d_arena; a.masks = b->d_masks.p; a.results = b->d_results.p;
   a.npairs = b->n; a.L = b->L; a.brule = b->brule; a.endrule = b->endrule;
   a.banded = b->mode == pw::BANDED_MODE;
   a.match = (T)b->subst[0]; a.mismatch = (T)(b->L > 1 ? b->subst[1] : b->subst[0]);
   a.go = (T)b->go; a.ge = (T)b->ge;
   a.score_mul = b->score_mul;
+  return a;
+}
+
+template <typename T>
+int launch_all_fills(pw_batch* b, hipStream_t st) {
+  pw::FillParams<T> a = fill_params<T>(b);
+  a.hdump = (T*)b->d_hdump.p; a.subst = (const T*)b->d_subst.p;
   for (auto& c : b->classes) {
-    a.order = c.d_order;
+    a.order = (const int32_t*)c.d_order.p;
     if (c.nw > 1) HIP_TRY(pw::launch_fill_mw(a, b->variant, c.bk, c.nw, (int)c.order.size(), st));
     else HIP_TRY(pw::launch_fill(a, b->variant, c.bk, (int)c.order.size(), st));
   }
@@ -642,26 +662,19 @@ int launch_all_fills(pw_batch* b, hipStream_t st) {
     int cur = 0;
     for (int tb = 0; tb < d.nblocks; tb += pw::kTileBlocks) {
       a.tile_b0 = tb; a.tile_nb = std::min(pw::kTileBlocks, d.nblocks - tb);
-      a.st_in = (const T*)b->d_state[cur]; a.st_out = (T*)b->d_state[cur ^ 1];
+      a.st_in = (const T*)b->d_state[cur].p; a.st_out = (T*)b->d_state[cur ^ 1].p;
       HIP_TRY(pw::launch_tile(a, b->variant, (int)k, ntiles, st));
       cur ^= 1;
     }
-    a.st_in = (const T*)b->d_state[cur];
+    a.st_in = (const T*)b->d_state[cur].p;
     HIP_TRY(pw::launch_tile_finish(a, (int)k, st));
   }
   return 0;
 }
 
 int launch_packed_fill(pw_batch* b, hipStream_t st) {
-  pw::FillParams<int32_t> a;
-  memset(&a, 0, sizeof a);
-  a.pairs = b->d_pairs; a.arena = b->d_arena; a.masks = b->d_masks; a.results = b->d_results;
-  a.npairs = b->n; a.L = b->L; a.brule = b->brule; a.endrule = b->endrule;
-  a.banded = b->mode == pw::BANDED_MODE;
-  a.match = (int32_t)b->subst[0]; a.mismatch = (int32_t)(b->L > 1 ? b->subst[1] : b->subst[0]);
-  a.go = (int32_t)b->go; a.ge = (int32_t)b->ge;
-  a.score_mul = b->score_mul;
-  a.order = b->classes[0].d_order; a.waves = b->d_waves;
+  pw::FillParams<int32_t> a = fill_params<int32_t>(b);
+  a.order = (const int32_t*)b->classes[0].d_order.p; a.waves = (const pw::WaveDesc*)b->d_waves.p;
   if (b->packed_mat) pw::packed_matrix_rows(b->subst.data(), b->L, b->packed_rule == 3, a.mat_rows, &a.mat_bias);
   if (b->packed_nw > 1) HIP_TRY(pw::launch_fill16_mw(a, b->classes[0].bk, b->packed_rule, b->packed_mat, b->packed_nw, (int)b->waves.size(), st));
   else HIP_TRY(pw::launch_fill16(a, b->classes[0].bk, b->packed_seg, b->packed_rule, b->packed_mat, (int)b->waves.size(), st));
@@ -693,40 +706,21 @@ int pw_device_count(void) {
 
 pw_batch* pw_batch_create(int device, const pw_scoring* sc, int32_t n_pairs, const pw_pair* pairs,
                           uint64_t arena_bytes, uint32_t flags) {
-  if (!sc || n_pairs < 0 || (n_pairs > 0 && !pairs)) { fail("pw_batch_create: bad arguments"); return nullptr; }
-  if (sc->mode != pw::STD_MODE && sc->mode != pw::BANDED_MODE) { fail("unknown alignment mode"); return nullptr; }
-  if (sc->type < 0 || sc->type > (sc->mode == pw::STD_MODE ? 6 : 2)) { fail("unknown alignment type"); return nullptr; }
-  if (sc->alphabet_len < 1 || sc->alphabet_len > 256 || !sc->subst) { fail("alphabet_len must be 1..256 with a score matrix"); return nullptr; }
-  pw_batch* b = new pw_batch();
-  b->device = device; b->n = n_pairs; b->flags = flags;
-  b->mode = sc->mode; b->type = sc->type; b->L = sc->alphabet_len; b->go = sc->go; b->ge = sc->ge;
-  b->subst.assign(sc->subst, sc->subst + (size_t)b->L * b->L);
-  b->subst_in = b->subst; b->go_in = b->go; b->ge_in = b->ge;
-  b->pairs.assign(pairs, pairs + n_pairs);
-  b->arena_bytes = arena_bytes;
-  if (batch_build(b) != 0) { batch_free_device(b); delete b; return nullptr; }
-  return b;
+  std::unique_ptr<pw_batch> b(new pw_batch());
+  b->device = device;
+  if (batch_inputs(b.get(), false, sc, n_pairs, pairs, arena_bytes, flags) != 0 || batch_plan(b.get()) != 0 ||
+      batch_alloc(b.get()) != 0)
+    return nullptr;
+  return b.release();
 }
 
-void pw_batch_destroy(pw_batch* b) {
-  if (!b) return;
-  batch_free_device(b);
-  delete b;
-}
+void pw_batch_destroy(pw_batch* b) { delete b; }
 
 int pw_plan_only(const pw_scoring* sc, int32_t n_pairs, const pw_pair* pairs, uint64_t arena_bytes, uint32_t flags,
                  char* kernel, int32_t kernel_cap, int32_t* info) {
-  if (!sc || n_pairs < 0 || (n_pairs > 0 && !pairs) || !sc->subst) return fail("pw_plan_only: bad arguments");
-  if (sc->mode != pw::STD_MODE && sc->mode != pw::BANDED_MODE) return fail("unknown alignment mode");
-  if (sc->type < 0 || sc->type > (sc->mode == pw::STD_MODE ? 6 : 2)) return fail("unknown alignment type");
-  if (sc->alphabet_len < 1 || sc->alphabet_len > 256) return fail("alphabet_len must be 1..256 with a score matrix");
   pw_batch b;
-  b.device = -1; b.n = n_pairs; b.flags = flags;
-  b.mode = sc->mode; b.type = sc->type; b.L = sc->alphabet_len; b.go = sc->go; b.ge = sc->ge;
-  b.subst.assign(sc->subst, sc->subst + (size_t)b.L * b.L);
-  b.pairs.assign(pairs, pairs + n_pairs);
-  b.arena_bytes = arena_bytes;
-  if (batch_plan(&b) != 0) return -1;
+  b.device = -1;
+  if (batch_inputs(&b, true, sc, n_pairs, pairs, arena_bytes, flags) != 0 || batch_plan(&b) != 0) return -1;
   if (kernel && kernel_cap > 0) { strncpy(kernel, pw_batch_kernel_name(&b), (size_t)kernel_cap - 1); kernel[kernel_cap - 1] = 0; }
   if (info) {
     int64_t one = 0, wg = 0;
@@ -822,12 +816,12 @@ int pw_batch_upload_arena_async(pw_batch* b, const uint8_t* host, uint64_t bytes
 }
 int pw_batch_results_async(pw_batch* b, pw_result* out, void* stream) {
   HIP_TRY(hipSetDevice(b->device));
-  if (b->n) HIP_TRY(hipMemcpyAsync(out, b->d_results, sizeof(pw_result) * (size_t)b->n, hipMemcpyDeviceToHost, (hipStream_t)stream));
+  if (b->n) HIP_TRY(hipMemcpyAsync(out, b->d_results.p, sizeof(pw_result) * (size_t)b->n, hipMemcpyDeviceToHost, (hipStream_t)stream));
   return mark_done(b, (hipStream_t)stream);
 }
 int pw_batch_transcripts_async(pw_batch* b, uint8_t* out, void* stream) {
   HIP_TRY(hipSetDevice(b->device));
-  if (b->tx_bytes) HIP_TRY(hipMemcpyAsync(out, b->d_tx, b->tx_bytes, hipMemcpyDeviceToHost, (hipStream_t)stream));
+  if (b->tx_bytes) HIP_TRY(hipMemcpyAsync(out, b->d_tx.p, b->tx_bytes, hipMemcpyDeviceToHost, (hipStream_t)stream));
   return mark_done(b, (hipStream_t)stream);
 }
 
@@ -838,20 +832,19 @@ int pw_batch_solve(pw_batch* b, void* stream) {
   b->traced = false; b->traced_from = false;
   if (!b->repaired.empty()) {          // a new solve: the strips get another chance
     HIP_TRY(hipDeviceSynchronize());
-    for (auto& r : b->repaired) pw_batch_destroy(r.second);
     b->repaired.clear();
   }
-  if (b->flags & PW_FLAG_PROFILE) HIP_TRY(hipEventRecord(b->ev_fill0, st));
+  if (b->flags & PW_FLAG_PROFILE) HIP_TRY(hipEventRecord(b->ev_fill0.e, st));
   int rc = b->variant == pw::VAR_FAST16 ? launch_packed_fill(b, st)
            : b->use_f64 ? launch_all_fills<double>(b, st) : launch_all_fills<int32_t>(b, st);
   if (rc == 0 && !b->strips.empty()) rc = launch_strip_fills(b, st);
   if (rc != 0) return rc;
-  if (b->flags & PW_FLAG_PROFILE) { HIP_TRY(hipEventRecord(b->ev_fill1, st)); b->fill_timed = true; }
+  if (b->flags & PW_FLAG_PROFILE) { HIP_TRY(hipEventRecord(b->ev_fill1.e, st)); b->fill_timed = true; }
   return mark_done(b, st);
 }
 
 static pw_batch* repaired_sub(pw_batch* b, int32_t k) {
-  for (auto& r : b->repaired) if (r.first == k) return r.second;
+  for (auto& r : b->repaired) if (r.first == k) return r.second.get();
   return nullptr;
 }
 
@@ -863,8 +856,8 @@ static int replay_trace(pw_batch* b, int32_t k, pw_batch* sub, hipStream_t st) {
     if (pw_batch_traceback_from(sub, e, st) != 0) return -1;
   } else if (pw_batch_traceback(sub, st) != 0) return -1;
   const pw::PairDesc& d = b->descs[k];
-  HIP_TRY(hipMemcpyAsync(b->d_results + k, sub->d_results, sizeof(pw::Result), hipMemcpyDeviceToDevice, st));
-  HIP_TRY(hipMemcpyAsync(b->d_tx + d.tx_off, sub->d_tx + sub->descs[0].tx_off, (size_t)d.tx_cap, hipMemcpyDeviceToDevice, st));
+  HIP_TRY(hipMemcpyAsync(b->d_results.p + k, sub->d_results.p, sizeof(pw::Result), hipMemcpyDeviceToDevice, st));
+  HIP_TRY(hipMemcpyAsync(b->d_tx.p + d.tx_off, sub->d_tx.p + sub->descs[0].tx_off, (size_t)d.tx_cap, hipMemcpyDeviceToDevice, st));
   return 0;
 }
 
@@ -875,13 +868,15 @@ static int repair_strip_pair(pw_batch* b, int32_t k) {
   pw_scoring sc;
   sc.mode = b->mode; sc.type = b->type; sc.alphabet_len = b->L; sc.subst = b->subst_in.data(); sc.go = b->go_in; sc.ge = b->ge_in;
   const uint32_t keep = b->flags & (PW_FLAG_FORCE_F64 | PW_FLAG_FORCE_GENERIC | PW_FLAG_NO_PACKED16);
-  pw_batch* sub = pw_batch_create(b->device, &sc, 1, &b->pairs[k], b->arena_bytes, keep | PW_FLAG_SHARED_ARENA | PW_FLAG_NO_STRIP);
+  std::unique_ptr<pw_batch> owned(pw_batch_create(b->device, &sc, 1, &b->pairs[k], b->arena_bytes,
+                                                  keep | PW_FLAG_SHARED_ARENA | PW_FLAG_NO_STRIP));
+  pw_batch* sub = owned.get();
   if (!sub) return -1;
-  if (!sub->strips.empty()) { pw_batch_destroy(sub); return fail("internal: the replacement of a strip pair took the strips again"); }
-  if (pw_batch_share_arena(sub, b->d_arena) != 0 || pw_batch_solve(sub, nullptr) != 0) { pw_batch_destroy(sub); return -1; }
-  b->repaired.emplace_back(k, sub);
+  if (!sub->strips.empty()) return fail("internal: the replacement of a strip pair took the strips again");
+  if (pw_batch_share_arena(sub, b->d_arena) != 0 || pw_batch_solve(sub, nullptr) != 0) return -1;
+  b->repaired.emplace_back(k, std::move(owned));
   if (b->traced) { if (replay_trace(b, k, sub, nullptr) != 0) return -1; }
-  else HIP_TRY(hipMemcpyAsync(b->d_results + k, sub->d_results, sizeof(pw::Result), hipMemcpyDeviceToDevice, nullptr));
+  else HIP_TRY(hipMemcpyAsync(b->d_results.p + k, sub->d_results.p, sizeof(pw::Result), hipMemcpyDeviceToDevice, nullptr));
   HIP_TRY(hipStreamSynchronize(nullptr));
   static const bool verbose = env_int("PWLIB_TIMING", 0) != 0;
   if (verbose) fprintf(stderr, "pwlib: strip pipeline of pair %d abandoned; solved again on %s\n", (int)k, pw_batch_kernel_name(sub));
@@ -891,8 +886,8 @@ static int repair_strip_pair(pw_batch* b, int32_t k) {
 static int do_trace(pw_batch* b, const int32_t* d_ends, hipStream_t st) {
   pw::TraceParams p;
   memset(&p, 0, sizeof p);
-  p.pairs = b->d_pairs; p.arena = b->d_arena; p.masks = b->d_masks; p.results = b->d_results;
-  p.transcripts = b->d_tx; p.npairs = b->n; p.gosign = b->gosign;
+  p.pairs = b->d_pairs.p; p.arena = b->d_arena; p.masks = b->d_masks.p; p.results = b->d_results.p;
+  p.transcripts = b->d_tx.p; p.npairs = b->n; p.gosign = b->gosign;
   p.banded = b->mode == pw::BANDED_MODE; p.ends = d_ends;
   // long transcripts (strip-pipeline pairs) are fixed up by several wavefronts each: ~2000 ops per segment
   if (!b->strips.empty()) {
@@ -900,20 +895,20 @@ static int do_trace(pw_batch* b, const int32_t* d_ends, hipStream_t st) {
     for (int32_t k : b->strips) longest = std::max<int64_t>(longest, b->descs[k].tx_cap);
     p.fix_segments = (int32_t)std::min<int64_t>(256, std::max<int64_t>(1, longest / 2048));
   }
-  if (b->flags & PW_FLAG_PROFILE) HIP_TRY(hipEventRecord(b->ev_tr0, st));
+  if (b->flags & PW_FLAG_PROFILE) HIP_TRY(hipEventRecord(b->ev_tr0.e, st));
   for (int32_t k : b->strips) {        // strip-layout pairs: one wavefront each (before the fix-up pass below)
     if (repaired_sub(b, k)) continue;  // (its mask plane is that of an abandoned fill: the replacement walks its own)
     const pw::PairDesc& d = b->descs[k];
     pw::StripTraceParams sp;
     memset(&sp, 0, sizeof sp);
-    sp.masks = b->d_masks + d.mask_off; sp.result = b->d_results + k; sp.tx = b->d_tx + d.tx_off;
+    sp.masks = b->d_masks.p + d.mask_off; sp.result = b->d_results.p + k; sp.tx = b->d_tx.p + d.tx_off;
     sp.ends = d_ends ? d_ends + 2 * k : nullptr;
-    sp.X = d.X; sp.Y = d.Y; sp.nkq = (d.Y + 64 + pw::kStripBlock - 1) / pw::kStripBlock; sp.tx_cap = d.tx_cap; sp.gosign = b->gosign;
+    sp.X = d.X; sp.Y = d.Y; sp.nkq = pw::strip_nkq(d.Y); sp.tx_cap = d.tx_cap; sp.gosign = b->gosign;
     HIP_TRY(pw::launch_strip_trace(sp, st));
   }
   HIP_TRY(pw::launch_trace(p, st));
-  for (auto& r : b->repaired) if (replay_trace(b, r.first, r.second, st) != 0) return -1;
-  if (b->flags & PW_FLAG_PROFILE) { HIP_TRY(hipEventRecord(b->ev_tr1, st)); b->trace_timed = true; }
+  for (auto& r : b->repaired) if (replay_trace(b, r.first, r.second.get(), st) != 0) return -1;
+  if (b->flags & PW_FLAG_PROFILE) { HIP_TRY(hipEventRecord(b->ev_tr1.e, st)); b->trace_timed = true; }
   return mark_done(b, st);
 }
 
@@ -926,7 +921,7 @@ int pw_batch_traceback(pw_batch* b, void* stream) {
 int pw_batch_traceback_from(pw_batch* b, const int32_t* ends_ij, void* stream) {
   HIP_TRY(hipSetDevice(b->device));
   hipStream_t st = (hipStream_t)stream;
-  if (!b->d_ends) HIP_TRY(hipMalloc((void**)&b->d_ends, 8 * std::max<int32_t>(b->n, 1)));
+  HIP_TRY(b->d_ends.ensure(8 * std::max<int32_t>(b->n, 1)));
   // validate on the host: an end cell outside the table would send the walker out of the mask plane
   for (int32_t k = 0; k < b->n; k++) {
     if (!b->descs[k].solvable) continue;
@@ -939,10 +934,10 @@ int pw_batch_traceback_from(pw_batch* b, const int32_t* ends_ij, void* stream) {
     else ok = i >= 0 && i < pl.num_rows && j >= 0 && j < pw::plan_len(X, Y, pl.dmin + i);
     if (!ok) return fail("traceback end cell outside the table");
   }
-  HIP_TRY(hipMemcpyAsync(b->d_ends, ends_ij, 8 * (size_t)b->n, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(b->d_ends.p, ends_ij, 8 * (size_t)b->n, hipMemcpyHostToDevice, st));
   b->traced = true; b->traced_from = true;
   b->last_ends.assign(ends_ij, ends_ij + 2 * (size_t)b->n);
-  return do_trace(b, b->d_ends, st);
+  return do_trace(b, (const int32_t*)b->d_ends.p, st);
 }
 
 int pw_batch_sync(pw_batch* b, void* stream) {
@@ -951,8 +946,8 @@ int pw_batch_sync(pw_batch* b, void* stream) {
   return 0;
 }
 
-void* pw_batch_results_device(pw_batch* b) { return b->d_results; }
-void* pw_batch_transcripts_device(pw_batch* b) { return b->d_tx; }
+void* pw_batch_results_device(pw_batch* b) { return b->d_results.p; }
+void* pw_batch_transcripts_device(pw_batch* b) { return b->d_tx.p; }
 uint64_t pw_batch_transcripts_bytes(const pw_batch* b) { return b->tx_bytes; }
 
 int pw_batch_tx_slot(const pw_batch* b, int32_t k, uint64_t* off, int32_t* cap) {
@@ -964,7 +959,7 @@ int pw_batch_tx_slot(const pw_batch* b, int32_t k, uint64_t* off, int32_t* cap) 
 
 int pw_batch_results(pw_batch* b, pw_result* out) {
   HIP_TRY(hipSetDevice(b->device));
-  if (b->n) HIP_TRY(hipMemcpy(out, b->d_results, sizeof(pw_result) * (size_t)b->n, hipMemcpyDeviceToHost));
+  if (b->n) HIP_TRY(hipMemcpy(out, b->d_results.p, sizeof(pw_result) * (size_t)b->n, hipMemcpyDeviceToHost));
   // (the D2H copy above has waited for everything launched on the default stream; callers that launched on another stream
   //  synchronise it first, as for any read of the records)
   for (int32_t k : b->strips)
@@ -973,43 +968,44 @@ int pw_batch_results(pw_batch* b, pw_result* out) {
         return fail("the strip pipeline of a wide pair was abandoned (a wavefront waited too long for the strip above it)");
       if (repair_strip_pair(b, k) != 0)
         return fail("the strip pipeline of a wide pair was abandoned and solving the pair again without it failed: " + std::string(g_err));
-      HIP_TRY(hipMemcpy(out + k, b->d_results + k, sizeof(pw_result), hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy(out + k, b->d_results.p + k, sizeof(pw_result), hipMemcpyDeviceToHost));
     }
   return 0;
 }
 
 int pw_batch_transcripts(pw_batch* b, uint8_t* out) {
   HIP_TRY(hipSetDevice(b->device));
-  if (b->tx_bytes) HIP_TRY(hipMemcpy(out, b->d_tx, b->tx_bytes, hipMemcpyDeviceToHost));
+  if (b->tx_bytes) HIP_TRY(hipMemcpy(out, b->d_tx.p, b->tx_bytes, hipMemcpyDeviceToHost));
   return 0;
 }
 
 int pw_batch_pack_transcripts(pw_batch* b, void* stream) {
   HIP_TRY(hipSetDevice(b->device));
-  if (!b->d_txoffsets) {
-    HIP_TRY(pool_alloc(b->device, (void**)&b->d_txpacked, std::max<uint64_t>(b->tx_bytes, 16), &b->txpacked_alloc));
-    HIP_TRY(hipMalloc((void**)&b->d_txoffsets, 8 * ((size_t)b->n + 1)));
+  if (!b->d_txoffsets.p) {
+    HIP_TRY(b->d_txpacked.alloc(b->device, std::max<uint64_t>(b->tx_bytes, 16)));
+    HIP_TRY(b->d_txoffsets.ensure(8 * ((size_t)b->n + 1)));
   }
-  HIP_TRY(pw::launch_tx_pack(b->d_pairs, b->d_results, b->d_tx, b->n, b->d_txoffsets, b->d_txpacked, (hipStream_t)stream));
+  HIP_TRY(pw::launch_tx_pack(b->d_pairs.p, b->d_results.p, b->d_tx.p, b->n, (uint64_t*)b->d_txoffsets.p, b->d_txpacked.p,
+                             (hipStream_t)stream));
   return mark_done(b, (hipStream_t)stream);
 }
-void* pw_batch_packed_device(pw_batch* b) { return b->d_txpacked; }
-void* pw_batch_packed_offsets_device(pw_batch* b) { return b->d_txoffsets; }
+void* pw_batch_packed_device(pw_batch* b) { return b->d_txpacked.p; }
+void* pw_batch_packed_offsets_device(pw_batch* b) { return b->d_txoffsets.p; }
 int pw_batch_packed_total_async(pw_batch* b, uint64_t* host_out, void* stream) {
-  if (!b->d_txoffsets) return fail("pw_batch_packed_total_async before pw_batch_pack_transcripts");
+  if (!b->d_txoffsets.p) return fail("pw_batch_packed_total_async before pw_batch_pack_transcripts");
   HIP_TRY(hipSetDevice(b->device));
-  HIP_TRY(hipMemcpyAsync(host_out, b->d_txoffsets + b->n, 8, hipMemcpyDeviceToHost, (hipStream_t)stream));
+  HIP_TRY(hipMemcpyAsync(host_out, (uint64_t*)b->d_txoffsets.p + b->n, 8, hipMemcpyDeviceToHost, (hipStream_t)stream));
   return mark_done(b, (hipStream_t)stream);
 }
 int pw_batch_packed(pw_batch* b, uint8_t* out, uint64_t cap, uint64_t* offsets_out) {
-  if (!b->d_txoffsets) return fail("pw_batch_packed before pw_batch_pack_transcripts");
+  if (!b->d_txoffsets.p) return fail("pw_batch_packed before pw_batch_pack_transcripts");
   HIP_TRY(hipSetDevice(b->device));
   std::vector<uint64_t> off((size_t)b->n + 1);
-  HIP_TRY(hipMemcpy(off.data(), b->d_txoffsets, 8 * off.size(), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(off.data(), b->d_txoffsets.p, 8 * off.size(), hipMemcpyDeviceToHost));
   if (offsets_out) memcpy(offsets_out, off.data(), 8 * off.size());
   if (out) {
     if (off[b->n] > cap) return fail("packed transcripts: buffer too small");
-    if (off[b->n]) HIP_TRY(hipMemcpy(out, b->d_txpacked, off[b->n], hipMemcpyDeviceToHost));
+    if (off[b->n]) HIP_TRY(hipMemcpy(out, b->d_txpacked.p, off[b->n], hipMemcpyDeviceToHost));
   }
   return 0;
 }
@@ -1021,11 +1017,11 @@ int pw_batch_scores(pw_batch* b, int32_t k, double* out, int64_t n) {
   if (n < want) return fail("score buffer too small");
   HIP_TRY(hipSetDevice(b->device));
   if (b->use_f64) {
-    HIP_TRY(hipMemcpy(out, (double*)b->d_hdump + d.h_off, 8 * (size_t)want, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out, (double*)b->d_hdump.p + d.h_off, 8 * (size_t)want, hipMemcpyDeviceToHost));
     for (int64_t i = 0; i < want; i++) out[i] *= b->score_mul;          // (dyadic scaling on f64 as well: a power of two)
   } else {
     std::vector<int32_t> tmp((size_t)want);
-    HIP_TRY(hipMemcpy(tmp.data(), (int32_t*)b->d_hdump + d.h_off, 4 * (size_t)want, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(tmp.data(), (int32_t*)b->d_hdump.p + d.h_off, 4 * (size_t)want, hipMemcpyDeviceToHost));
     for (int64_t i = 0; i < want; i++) out[i] = (double)tmp[(size_t)i] * b->score_mul;
   }
   return 0;
@@ -1036,11 +1032,11 @@ int pw_batch_masks(pw_batch* b, int32_t k, uint8_t* out, int64_t n) {
   if (pw_batch* sub = repaired_sub(b, k)) return pw_batch_masks(sub, 0, out, n);   // (the replacement's plane is the live one)
   const pw::PairDesc& d = b->descs[k];
   if (n < b->plans[k].cells) return fail("mask buffer too small");
-  const uint64_t words = d.layout == 1 ? (uint64_t)((d.X + 1 + 63) / 64) * pw::strip_nkq(d.Y) * 64 * 4
+  const uint64_t words = d.layout == 1 ? (uint64_t)pw::strip_count(d.X) * pw::strip_nkq(d.Y) * 64 * 4
                                        : (uint64_t)(d.nblocks + 1) * d.nl * d.bk;
   std::vector<uint32_t> plane((size_t)words);
   HIP_TRY(hipSetDevice(b->device));
-  HIP_TRY(hipMemcpy(plane.data(), b->d_masks + d.mask_off, 4 * (size_t)words, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(plane.data(), b->d_masks.p + d.mask_off, 4 * (size_t)words, hipMemcpyDeviceToHost));
   pw::mask_table(d, plane.data(), b->mode == pw::BANDED_MODE, out);
   return 0;
 }
@@ -1052,13 +1048,11 @@ int pw_batch_table(pw_batch* b, int32_t k, double* out, int64_t n) {
   const int64_t want = (int64_t)(d.X + 1) * (d.Y + 1);
   if (n < want) return fail("table buffer too small");
   HIP_TRY(hipSetDevice(b->device));
-  double* dev = nullptr;
-  HIP_TRY(hipMalloc((void**)&dev, 8 * (size_t)want));
-  const void* plane = b->use_f64 ? (const void*)((double*)b->d_hdump + d.h_off) : (const void*)((int32_t*)b->d_hdump + d.h_off);
-  hipError_t e = pw::launch_table_rowmajor(plane, b->use_f64, d.X, d.Y, d.h_pitch, b->score_mul, dev, nullptr);
-  if (e == hipSuccess) e = hipMemcpy(out, dev, 8 * (size_t)want, hipMemcpyDeviceToHost);
-  (void)hipFree(dev);
-  if (e != hipSuccess) return fail(hipGetErrorString(e));
+  DeviceBuffer dev;
+  HIP_TRY(dev.ensure(8 * (size_t)want));
+  const void* plane = b->use_f64 ? (const void*)((double*)b->d_hdump.p + d.h_off) : (const void*)((int32_t*)b->d_hdump.p + d.h_off);
+  HIP_TRY(pw::launch_table_rowmajor(plane, b->use_f64, d.X, d.Y, d.h_pitch, b->score_mul, (double*)dev.p, nullptr));
+  HIP_TRY(hipMemcpy(out, dev.p, 8 * (size_t)want, hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -1066,8 +1060,8 @@ float pw_batch_fill_ms(pw_batch* b) {
   if (!b->fill_timed) return -1.f;
   float ms = -1.f;
   (void)hipSetDevice(b->device);
-  if (hipEventSynchronize(b->ev_fill1) != hipSuccess) return -1.f;
-  if (hipEventElapsedTime(&ms, b->ev_fill0, b->ev_fill1) != hipSuccess) return -1.f;
+  if (hipEventSynchronize(b->ev_fill1.e) != hipSuccess) return -1.f;
+  if (hipEventElapsedTime(&ms, b->ev_fill0.e, b->ev_fill1.e) != hipSuccess) return -1.f;
   return ms;
 }
 
@@ -1075,8 +1069,8 @@ float pw_batch_trace_ms(pw_batch* b) {
   if (!b->trace_timed) return -1.f;
   float ms = -1.f;
   (void)hipSetDevice(b->device);
-  if (hipEventSynchronize(b->ev_tr1) != hipSuccess) return -1.f;
-  if (hipEventElapsedTime(&ms, b->ev_tr0, b->ev_tr1) != hipSuccess) return -1.f;
+  if (hipEventSynchronize(b->ev_tr1.e) != hipSuccess) return -1.f;
+  if (hipEventElapsedTime(&ms, b->ev_tr0.e, b->ev_tr1.e) != hipSuccess) return -1.f;
   return ms;
 }
 

@@ -417,8 +417,8 @@ extern "C" int emu_solve_strip(int type, const int* origin, int X, const int* mu
   memset(&a, 0, sizeof a);
   a.arena = arena.data(); a.o_off = 0; a.m_off = opad;
   a.X = X; a.Y = Y;
-  a.nstrips = (X + 1 + 63) / 64;
-  a.nkq = (Y + 64 + pw::kStripBlock - 1) / pw::kStripBlock;
+  a.nstrips = pw::strip_count(X);
+  a.nkq = pw::strip_nkq(Y);
   a.fifo_pitch = pw::strip_fifo_pitch(Y);
   std::vector<uint64_t> fifo((size_t)a.nstrips * a.fifo_pitch, 0x00000000deadbeefull);   // stale granules of "earlier solves"
   for (size_t i = 0; i < fifo.size(); i += 3) fifo[i] = ((uint64_t)(((epoch - 1) << 8) | (i & 0xffu)) << 32) | 12345u;

@@ -316,16 +316,105 @@ def _all_pairs_args(over):
 def _expect_refusal(lib, api, call, msg, name):
     """call() fails (NULL or -1) and leaves exactly `msg` in its API's error channel.  The channel holds another
     message before the call, so a stale one cannot pass."""
-    last = lib.pw_seeds_last_error if api == 'seeds' else lib.pw_overlap_last_error
+    last = {'seeds': lib.pw_seeds_last_error, 'overlap': lib.pw_overlap_last_error, 'batch': lib.pw_last_error}[api]
     if api == 'seeds':
         lib.pw_seeds_build(None, 0, None)
         if last() == msg:
             lib.pw_seeds_rows(None, None, 0)
+    elif api == 'batch':
+        lib.pw_plan_only(None, 0, None, 0, 0, None, 0, None)
+        if last() == msg:
+            lib.pw_batch_create(0, None, 0, None, 0, 0)
     else:
         lib.pw_overlap_bands(0, None, 0, None, -1, 0, 3, 1., 1., 1., None)
         if last() == msg:
             lib.pw_overlap_bands(0, None, 0, None, -1, 4, 3, 1., 1., 1., None)
     assert last() != msg
     rc = call()
-    assert rc in (None, -1), (name, rc)             # NULL from pw_seeds_create, -1 from the others
+    assert rc in (None, -1), (name, rc)             # NULL from pw_seeds_create / pw_batch_create, -1 from the others
     assert last() == msg, (name, last())
+
+
+# ---- the batch API's refusals before any device call: pw_plan_only and the planning stage of pw_batch_create ---------
+_FLOOR_MSG = (b'scores too low for this alignment type: (X + Y + 2) * (the most a gap step, or on a one-diagonal band a '
+              b'substitution, can lower a score) must stay below INT_MAX, where the reference floors gap candidates and end '
+              b'cells at -INT_MAX (not reproduced)')
+_BATCH_BASE = dict(null_sc=False, mode=0, type=0, L=4, subst=[1. if i == j else -1. for i in range(4) for j in range(4)],
+                   null_subst=False, go=-2., ge=-1., n=None, null_pairs=False, pair=dict(), arena=64, flags=0)
+_BATCH_REFUSALS = [       # (name, 'c': pw_batch_create, 'p': pw_plan_only, overrides, message of create, message of plan_only)
+    ('NULL scoring', 'cp', dict(null_sc=True), b'pw_batch_create: bad arguments', b'pw_plan_only: bad arguments'),
+    ('count < 0', 'cp', dict(n=-1), b'pw_batch_create: bad arguments', b'pw_plan_only: bad arguments'),
+    ('NULL pairs', 'cp', dict(null_pairs=True), b'pw_batch_create: bad arguments', b'pw_plan_only: bad arguments'),
+    ('NULL subst', 'cp', dict(null_subst=True), b'alphabet_len must be 1..256 with a score matrix',
+     b'pw_plan_only: bad arguments'),
+    ('mode -1', 'cp', dict(mode=-1), b'unknown alignment mode', None),
+    ('mode 2', 'cp', dict(mode=2), b'unknown alignment mode', None),
+    ('type -1', 'cp', dict(type=-1), b'unknown alignment type', None),
+    ('standard type 7', 'cp', dict(mode=0, type=7), b'unknown alignment type', None),
+    ('banded type 3', 'cp', dict(mode=1, type=3), b'unknown alignment type', None),
+    ('alphabet 0', 'cp', dict(L=0), b'alphabet_len must be 1..256 with a score matrix', None),
+    ('alphabet 257', 'cp', dict(L=257), b'alphabet_len must be 1..256 with a score matrix', None),
+    ('NaN score', 'cp', dict(subst=[float('nan')] + [-1.] * 15), b'substitution scores must be finite', None),
+    ('infinite score', 'cp', dict(subst=[1.] * 15 + [float('inf')]), b'substitution scores must be finite', None),
+    ('negative length', 'cp', dict(pair=dict(mutant_len=-1)), b'negative sequence length', None),
+    ('frame outside the arena', 'cp', dict(pair=dict(origin_off=1 << 40)), b'pair frame outside the arena', None),
+    ('frame one past the arena', 'cp', dict(pair=dict(mutant_off=60)), b'pair frame outside the arena', None),
+    ('sequences over 2^30', 'cp', dict(arena=1 << 31, pair=dict(origin_len=(1 << 30) - 7)), b'sequences too long', None),
+    ('frame off a 4-byte boundary', 'cp', dict(pair=dict(origin_off=2)), b'frames must start on a 4-byte boundary of the arena',
+     None),
+    ('-INT_MAX floor', 'cp', dict(go=-3e9), _FLOOR_MSG, None),
+    ('score plane of a tiled pair', 'cp', dict(flags=W.PW_FLAG_DUMP_SCORES | W.PW_FLAG_FORCE_TILED),
+     b'the score plane is not available for tiled (very wide) tables', None),
+]
+
+
+def _batch_args(over):
+    """(scoring, count, pairs, arena bytes, flags) of one call; the ctypes objects stay alive while the tuple does."""
+    a = dict(_BATCH_BASE, **over)
+    subst = _arr(a['subst'], C.c_double)
+    sc = W.pw_scoring(a['mode'], a['type'], a['L'], C.cast(subst, C.POINTER(C.c_double)) if not a['null_subst'] else None,
+                      a['go'], a['ge'])
+    pair = dict(dict(origin_off=0, mutant_off=16, origin_len=8, mutant_len=8, dmin=-2, dmax=2), **a['pair'])
+    pairs = (W.pw_pair * 1)(W.pw_pair(*(pair[f] for f, _ in W.pw_pair._fields_)))
+    return (None if a['null_sc'] else C.pointer(sc), 1 if a['n'] is None else a['n'], None if a['null_pairs'] else pairs,
+            a['arena'], a['flags'], subst, sc)
+
+
+def _batch_calls(lib):
+    """'c': pw_batch_create on device 0, 'p': pw_plan_only, each on the arguments of _batch_args"""
+    return {'c': lambda a: lib.pw_batch_create(0, *a[:5]), 'p': lambda a: lib.pw_plan_only(*a[:5], None, 0, None)}
+
+
+def test_batch_api_refuses_bad_input_before_any_device_call():
+    """Every refusal of pw_plan_only and of pw_batch_create's planning stage, each with its full message (both entry points
+    check the same arguments; only a NULL score matrix is reported differently)."""
+    lib = W.load()
+    calls = _batch_calls(lib)
+    for name, apis, over, msg_c, msg_p in _BATCH_REFUSALS:
+        for api in apis:
+            msg = msg_p if api == 'p' and msg_p is not None else msg_c
+            _expect_refusal(lib, 'batch', lambda: calls[api](_batch_args(over)), msg, '%s: %s' % (api, name))
+    # the edges the refusals above sit next to are accepted (planning only: no device)
+    for over in (dict(), dict(L=256, subst=[0.] * (256 * 256)), dict(L=1, subst=[1.]), dict(mode=0, type=6),
+                 dict(mode=1, type=2), dict(pair=dict(mutant_off=56)), dict(go=-1e6)):
+        assert calls['p'](_batch_args(over)) == 0, (over, lib.pw_last_error())
+
+
+def test_batch_api_refusals_come_in_order():
+    """With the faults of several checks at once, the first check in the library's order reports: fault i is combined with
+    every later fault of the list."""
+    lib = W.load()
+    calls = _batch_calls(lib)
+    table = {n: (o, mc, mp) for n, _, o, mc, mp in _BATCH_REFUSALS}
+    tail = ['alphabet 257', 'NaN score', 'negative length', 'frame outside the arena', 'sequences over 2^30',
+            'frame off a 4-byte boundary', '-INT_MAX floor', 'score plane of a tiled pair']
+    orders = {'c': ['NULL pairs', 'mode 2', 'standard type 7', 'NULL subst'] + tail,
+              'p': ['NULL subst', 'mode 2', 'standard type 7'] + tail}
+    for api, order in orders.items():
+        for q, name in enumerate(order):
+            over = {}
+            for later in reversed(order[q:]):
+                o = table[later][0]
+                over.update(o, pair=dict(over.get('pair', {}), **o.get('pair', {})))
+            msg = table[name][2] if api == 'p' and table[name][2] is not None else table[name][1]
+            _expect_refusal(lib, 'batch', lambda: calls[api](_batch_args(over)), msg, '%s: %s with every later fault' % (api, name))

@@ -969,13 +969,40 @@ def test_drop_in_calls_from_several_threads(oracle):
 
 def test_buffer_pool_reuse_and_trim():
     """Device buffers of a destroyed batch are handed to the next batch of similar size (no growth over repeated
-    create / destroy cycles) and pw_pool_trim gives them back."""
+    create / destroy cycles) and pw_pool_trim gives them back.  Every cycle also touches the optional resources of a batch:
+    profiling events, packed transcripts, explicit end cells, a score plane read through pw_batch_table and a batch over a
+    caller-owned arena."""
     import ctypes
     from biseqt_amd import synth, _pwlib as W
-    from biseqt_amd.batch import BatchAligner
+    from biseqt_amd.batch import BatchAligner, DeviceArena, pack_reads
     lib = W.load()
     origins, mutants = synth.pair_batch(5, 600, 1500)
     kw = dict(alnmode=1, alntype=1, alphabet_len=4, diag_range=(-150, 150), match_score=1, mismatch_score=-3, go_score=-5, ge_score=-2)
+    small = list(zip(*synth.pair_batch(6, 4, 200)))
+    std = dict(kw, alnmode=0)
+    del std['diag_range']
+
+    def extras(res):
+        n = len(origins)
+        with BatchAligner(list(zip(origins, mutants)), flags=W.PW_FLAG_PROFILE, **kw) as b:
+            b.solve()
+            b.traceback_from(np.stack([res['opt_i'], res['opt_j']], axis=1))
+            b.pack_transcripts()
+            buf, off = b.packed()
+            assert len(off) == n + 1 and int(off[-1]) == len(buf) > 0
+            assert b.fill_ms() > 0 and b.trace_ms() > 0
+            assert np.array_equal(b.results()['score'], res['score'])
+        with BatchAligner(small, flags=W.PW_FLAG_DUMP_SCORES, **std) as b:
+            sres = b.run()
+            X, Y = b.lens[0]
+            tab = np.zeros((X + 1) * (Y + 1), np.float64)
+            assert lib.pw_batch_table(b.handle, 0, tab.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), tab.size) == 0
+            assert tab.max() == sres['score'][0]
+        arena, offs, lens = pack_reads(origins[:50] + mutants[:50])
+        with DeviceArena(arena) as dev:
+            with BatchAligner.from_arena(arena, offs, lens, [(k, 50 + k) for k in range(50)], device_arena=dev,
+                                         diag_ranges=[kw['diag_range']] * 50, **{a: v for a, v in kw.items() if a != 'diag_range'}) as b:
+                assert np.array_equal(b.run()['score'], res['score'][:50])
 
     def used():
         free, total = ctypes.c_uint64(), ctypes.c_uint64()
@@ -991,6 +1018,7 @@ def test_buffer_pool_reuse_and_trim():
         with BatchAligner(list(zip(origins, mutants)), **kw) as b:
             res = b.run()
             assert (res['opt_i'] >= 0).all()
+        extras(res)
         marks.append(used())
     assert max(marks[1:]) - marks[1] < 32, marks          # steady after the first cycle
     assert marks[1] - base > 50                           # ... because the buffers are parked in the pool
