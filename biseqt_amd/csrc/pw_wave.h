@@ -668,6 +668,15 @@ PW_FN uint32_t align16(uint32_t hi, uint32_t lo) { return __builtin_amdgcn_align
 // sign mask per half (0xffff where negative): arithmetic shift by sh15 = (15, 15) held in an opaque register
 PW_FN uint32_t sign(uint32_t a, uint32_t sh15) { return __builtin_bit_cast(uint32_t, (s2_t)(as_s2(a) >> as_s2(sh15))); }
 PW_FN uint32_t opaque(uint32_t v) { asm volatile("" : "+v"(v)); return v; }
+PW_FN uint32_t opaque_su(uint32_t v) { asm volatile("" : "+s"(v)); return v; }   // a wave-uniform value, kept in a scalar register
+PW_FN uint8_t* opaque_s(uint8_t* v) { asm volatile("" : "+s"(v)); return v; }   // a wave-uniform address, kept in scalar registers
+// 16 bytes to base + off in GLOBAL memory (an address that went through opaque_s has lost its address space, and a flat store
+// would count against the scalar loads' counter as well)
+PW_FN void store_global(uint8_t* base, uint32_t off, const U4& v) {
+  typedef __attribute__((address_space(1))) uint8_t gbyte_t;
+  typedef __attribute__((address_space(1))) U4 gu4_t;
+  *(gu4_t*)((gbyte_t*)base + off) = v;
+}
 // v_perm_b32: byte i of the result is byte sel[i] of the 8 bytes {a (4 .. 7), b (0 .. 3)}; selector 8 .. 11 = the sign of
 // byte 1 / 3 / 5 / 7 spread over the byte, 12 = 0x00, 13 and up = 0xff
 PW_FN uint32_t perm(uint32_t a, uint32_t b, uint32_t sel) { return __builtin_amdgcn_perm(a, b, sel); }
@@ -698,6 +707,9 @@ PW_FN uint32_t mins(uint32_t a, uint32_t b) { return mk((uint32_t)(sl(a) < sl(b)
 PW_FN uint32_t align16(uint32_t hi, uint32_t lo) { return (lo >> 16) | (hi << 16); }
 PW_FN uint32_t sign(uint32_t a, uint32_t) { return mk(sl(a) < 0 ? 0xffffu : 0u, sh(a) < 0 ? 0xffffu : 0u); }
 PW_FN uint32_t opaque(uint32_t v) { return v; }
+PW_FN uint32_t opaque_su(uint32_t v) { return v; }
+PW_FN uint8_t* opaque_s(uint8_t* v) { return v; }
+PW_FN void store_global(uint8_t* base, uint32_t off, const U4& v) { *(U4*)(base + off) = v; }
 PW_FN uint32_t perm(uint32_t a, uint32_t b, uint32_t sel) {
   const uint64_t in = ((uint64_t)a << 32) | b;
   uint32_t r = 0;
@@ -788,7 +800,9 @@ struct WaveFill16 {
 
   // packed state: index p <-> even slots (2p, 2p + R) [E*] / odd slots (2p + 1, 2p + 1 + R) [O*]
   uint32_t HE[RH], UE[RH], LE[RH], HO[RH], UO[RH], LO[RH];
-  uint32_t bestE[RH], bestO[RH], btE[RH], btO[RH];     // running best and the step it was first reached
+  // capturing rules: the value of every diagonal's last cell (bt unused); tracking rules: the running best lives in
+  // kbE / kbO as a key and bt holds the stamp of where it was first reached (stamp_best)
+  uint32_t bestE[RH], bestO[RH], btE[RH], btO[RH];
   uint32_t gebE[RH], gebO[RH];                          // ge (+ the band-top block) per half
   uint32_t clE[RH], clO[RH];                            // RULE != 0: clamp of the "left" offer (sentinel for the slot above the band)
   uint32_t tfE[RH], tfO[RH], tlE[RH], tlO[RH];          // first / last step of each diagonal
@@ -800,8 +814,8 @@ struct WaveFill16 {
   uint32_t ONE, SH15, C2, C4, C16, NDELTA, MATCHV, GOV, GOVI, NEGV, LIMV;
   // RULE 0, steady blocks: the running best of a slot as a key 8 H + (7 - cell within the block) -- one multiply-add and
   // one unsigned maximum per cell pair instead of maximum, compare, subtract and multiply-add (H <= 8191: the planner
-  // admits scores up to 8000); turned back into (best, step) once per block
-  uint32_t kbE[RH], kbO[RH], C8, SH3, SEVEN, NEG2;
+  // admits scores up to 8000); carried from block to block and turned back into (best, step) once, in finish()
+  uint32_t kbE[RH], kbO[RH], C8, SEVEN;
   // The two offers that cross lanes, as of the end of the previous exchange.  Only the DPP moves write them, and each move
   // takes the register's own previous value as its `old` operand: the edge lane that has no source (lane 0 / lane 63 of the
   // wavefront) keeps the sentinel it was given in run(), with no copy of the sentinel in front of every move.
@@ -811,6 +825,17 @@ struct WaveFill16 {
   // mask plane (pw_types.h, mask_word_index): this lane's dword in block 0 and the dwords per block -- the spare row and 0 for
   // lanes with nothing to store --, the spare row's first dword, the dwords per lane group
   uint32_t mrow0, mrow_step, mspare, mgroup;
+  // The matrix form of the begin-anywhere rules runs one loop per kind of block (run()).  The match / mismatch form and the
+  // rules that begin on the table edge keep the single loop that chooses a body per block: split, the former changes its
+  // register profile (the BK = 8 body would fit one more wavefront per SIMD than build.py holds it to, a choice that wants
+  // an A/B of its own), the latter lost wavefronts per SIMD or spilled scalar registers.
+  static constexpr bool SPLIT = ANYB && MAT;
+  // ... and, one pair per wavefront, its mask stores take a wave-uniform base per lane group and one 32-bit byte offset per
+  // lane.  (Elsewhere the BK / 4 addresses cost registers the body has no room for: the rules that begin on the table edge
+  // spilled scalar registers, the match / mismatch body at 28 diagonals per lane lost its second wavefront per SIMD.)
+  static constexpr bool SBASE = !SEG && SPLIT;
+  uint32_t mrowb;               // SBASE: the byte offset of this lane's dwords in the block to come
+  uint8_t* mbase[BK / 4];       // SBASE: the plane's address plus the distance of lane group g
 
   PW_FN WaveFill16(const FillParams<int32_t>& a_, const WaveDesc& wd_) : a(a_), wd(wd_) {}
 
@@ -882,12 +907,17 @@ struct WaveFill16 {
     Hs = Hn;
   }
 
-  PW_FN void key_to_best(uint32_t& bests, uint32_t& bts, uint32_t kb, uint32_t kb0, uint32_t base) {
-    const uint32_t ch = pk::minu(kb ^ kb0, ONE);                 // 1 where the best strictly improved in this block
-    const uint32_t st = pk::mad(kb & SEVEN, NEG2, base);         // its step: base - 2 (7 - cell)
-    bts = pk::mad(ch, pk::sub(st, bts), bts);
-    // (unchanged where the key is; SC4: key = 2 (4 H) + cell)
-    bests = SC4 ? (pk::shru(kb, ONE) & 0xfffcfffcu) : pk::shru(kb, SH3);
+  // The running best stays a key from block to block (kbE / kbO), with no re-seeding: a block goes on taking maxima into the
+  // key as it stands (`kb0` = its value before the block).  What a block leaves behind besides the key is a STAMP of where the
+  // best was first reached, 8 (block + 1) + 7 - cell, written only where the key's SCORE part (bits 3 and up) rose in this
+  // block: the low bits are then 7 - the first cell of the block that reached the new score.  An equal score in a later
+  // block can only raise the low bits; that is not a rise of the score part, no stamp is written, and the low bits are never
+  // read again until the score part rises (which rewrites them).  Stamps only grow from block to block, so an unsigned
+  // maximum keeps the latest; where the score did not rise the candidate is 0 * stamp + (0 .. 7), below every real stamp.
+  // finish() turns key and stamp into score and step, once per pair.
+  PW_FN void stamp_best(uint32_t& bts, uint32_t kb, uint32_t kb0, uint32_t blk8) {
+    const uint32_t ch = pk::minu((kb ^ kb0) & ~SEVEN, ONE);      // 1 where the best strictly improved in this block
+    bts = pk::maxu(bts, pk::mad(ch, blk8, kb & SEVEN));
   }
 
   // HALF selects the accumulator set: iterations 0-3 of a block (cells 0-3 of every slot) or 4-7.
@@ -996,9 +1026,7 @@ struct WaveFill16 {
     uint32_t kb0E[RH], kb0O[RH];
     if (TRK) {
 #pragma unroll
-      for (int p = 0; p < RH; p++) {        // a later cell with the same score loses against 8 best + 7
-        kb0E[p] = kbE[p] = pk::mad(bestE[p], SC4 ? C2 : C8, SEVEN); kb0O[p] = kbO[p] = pk::mad(bestO[p], SC4 ? C2 : C8, SEVEN);
-      }
+      for (int p = 0; p < RH; p++) { kb0E[p] = kbE[p]; kb0O[p] = kbO[p]; }
     }
     // unroll depth: full for narrow lanes (the letter-window shifts become register renames), shallower for
     // wide ones, where the live state already fills the register file
@@ -1007,12 +1035,11 @@ struct WaveFill16 {
 #pragma clang loop unroll_count(UNR)
     for (int k = 4; k < 8; k++) iteration16<EK, 1>(8 * b + k, k);
     if (TRK) {
-      // cell c of this block (iteration 8 b + c) is step 16 b + 2 c of an even slot, 16 b + 2 c + 1 of an odd one
-      const uint32_t baseE = pk::both(16 * b + 14), baseO = pk::both(16 * b + 15);
+      const uint32_t blk8 = pk::both(8 * b + 8);
 #pragma unroll
       for (int p = 0; p < RH; p++) {
-        key_to_best(bestE[p], btE[p], kbE[p], kb0E[p], baseE);
-        key_to_best(bestO[p], btO[p], kbO[p], kb0O[p], baseO);
+        stamp_best(btE[p], kbE[p], kb0E[p], blk8);
+        stamp_best(btO[p], kbO[p], kb0O[p], blk8);
       }
     }
     // 8 cells per slot -> one dword, first cell in the top nibble; un-invert: kept = 7 - (not kept), one subtract per
@@ -1032,13 +1059,28 @@ struct WaveFill16 {
         mwd[2 * p + 1] = pk::perm(kO, k2O, 0x05040100u);
         mwd[2 * p + 1 + R] = pk::perm(kO, k2O, 0x07060302u);
       }
-      // mask_word_index(BK, nl, b, li, 4 g), or the spare row: a 32-bit dword index (run(): mrow0 / mrow_step / mspare)
-      const uint32_t row = b < pd.nblocks ? mrow0 + (uint32_t)b * mrow_step : mspare;
-      uint32_t* dst = a.masks + pd.mask_off;
+      if (!SBASE) {
+        // mask_word_index(BK, nl, b, li, 4 g), or the spare row: a 32-bit dword index (run(): mrow0 / mrow_step / mspare); a
+        // shorter pair of a lane-packed wavefront parks its stores in the spare row once its own blocks are done
+        const uint32_t row = b < pd.nblocks ? mrow0 + (uint32_t)b * mrow_step : mspare;
+        uint32_t* dst = a.masks + pd.mask_off;
 #pragma unroll
-      for (int g = 0; g < BK / 4; g++) {
-        U4 v; v.x = mwd[4 * g]; v.y = mwd[4 * g + 1]; v.z = mwd[4 * g + 2]; v.w = mwd[4 * g + 3];
-        *(U4*)(dst + (row + (uint32_t)g * mgroup)) = v;
+        for (int g = 0; g < BK / 4; g++) {
+          U4 v; v.x = mwd[4 * g]; v.y = mwd[4 * g + 1]; v.z = mwd[4 * g + 2]; v.w = mwd[4 * g + 3];
+          *(U4*)(dst + (row + (uint32_t)g * mgroup)) = v;
+        }
+      } else {
+        // One pair per wavefront runs exactly the pair's blocks (nblocks_run()), so no block is tested against the pair's
+        // count; the lane's BYTE offset into the pair's plane is carried from block to block -- one add -- and the lane
+        // group's distance sits in the wave-uniform base (mbase[g]): a store takes a scalar base and this one 32-bit
+        // register, with no 64-bit address arithmetic per lane.  (A plane stays far below 4 GiB: at most 4096 blocks of
+        // 512 lanes x 32 dwords.)
+#pragma unroll
+        for (int g = 0; g < BK / 4; g++) {
+          U4 v; v.x = mwd[4 * g]; v.y = mwd[4 * g + 1]; v.z = mwd[4 * g + 2]; v.w = mwd[4 * g + 3];
+          pk::store_global(mbase[g], mrowb, v);
+        }
+        mrowb += 4u * mrow_step;
       }
     }
   }
@@ -1059,8 +1101,15 @@ struct WaveFill16 {
     fm_n0 = m32[pw_clampi(wm, 0, mwlast)]; fm_n1 = m32[pw_clampi(wm + 1, 0, mwlast)]; fm_n2 = m32[pw_clampi(wm + 2, 0, mwlast)];
   }
   // bytes k = 0 .. 7 of the result are 0xff where i0 + k lies in [0, n), 0 elsewhere
+  // (one pair per wavefront: the arguments are wave-uniform, and a clamp written as one expression is selected as a vector
+  //  v_med3_i32 plus a v_readfirstlane_b32; split in two by an opaque scalar it stays s_max_i32 / s_min_i32)
+  PW_FN static int clamp08(int v) {
+    if (SEG) return pw_clampi(v, 0, 8);
+    const int r = (int)pk::opaque_su((uint32_t)(v > 0 ? v : 0));
+    return r < 8 ? r : 8;
+  }
   PW_FN static uint64_t inside_bytes(int i0, int n) {
-    const int lo = pw_clampi(-i0, 0, 8), hi = pw_clampi(n - i0, 0, 8);
+    const int lo = clamp08(-i0), hi = clamp08(n - i0);
     const uint64_t below_hi = hi >= 8 ? ~(uint64_t)0 : (((uint64_t)1 << (8 * hi)) - 1);
     const uint64_t below_lo = lo >= 8 ? ~(uint64_t)0 : (((uint64_t)1 << (8 * lo)) - 1);
     return below_hi & ~below_lo;
@@ -1078,6 +1127,9 @@ struct WaveFill16 {
       const uint64_t m = (((((uint64_t)fm_hi) << 32) | fm_lo) & im) | (0x0808080808080808ull & ~im);
       fo_lo = (uint32_t)o; fo_hi = (uint32_t)(o >> 32);
       fm_lo = (uint32_t)m; fm_hi = (uint32_t)(m >> 32);
+      // (seen as the halves of one 64-bit value, "the last letter is 0" became a 64-bit unsigned compare, which exists as a
+      //  vector instruction only)
+      if (!SEG) { fo_hi = pk::opaque_su(fo_hi); fm_hi = pk::opaque_su(fm_hi); }
     }
   }
 
@@ -1135,7 +1187,7 @@ struct WaveFill16 {
     yfeed_m = f;
     ONE = pk::opaque(0x00010001u); SH15 = pk::opaque(0x000f000fu);
     C2 = pk::opaque(0x00020002u); C4 = pk::opaque(0x00040004u); C16 = pk::opaque(0x00100010u);
-    C8 = pk::opaque(0x00080008u); SH3 = pk::opaque(0x00030003u); SEVEN = pk::opaque(0x00070007u); NEG2 = pk::opaque(0xfffefffeu);
+    C8 = pk::opaque(0x00080008u); SEVEN = pk::opaque(0x00070007u);
     NEGV = pk::both(NEG16); LIMV = pk::both(-32767);
     NDELTA = pk::both(SCL * (a.mismatch - a.match)); MATCHV = pk::both(SCL * a.match);
     // the multipliers of the "not kept" values: 0 / 1 each, or (SC4) 0 / 2 for D and 0 / 4 for I
@@ -1163,10 +1215,9 @@ struct WaveFill16 {
       tlE[p] = pk::pack(tlast_of(e0), tlast_of(e1)); tlO[p] = pk::pack(tlast_of(o0), tlast_of(o1));
       HE[p] = UE[p] = LE[p] = HO[p] = UO[p] = LO[p] = NEGV;
       up_prev = left_next = NEGV; phase_l = 0; phase_r = 0;
-      // rule 0: scores never go below 0, and a diagonal whose best stays 0 reports its first cell (score 0 on the table edge)
-      // (rule 5: a best of 0 never wins -- the end cell must beat 0 -- so where it "was reached" does not matter)
-      bestE[p] = bestO[p] = TRK ? 0u : NEGV;
-      btE[p] = (TRK && ANYB) ? tfE[p] : 0u; btO[p] = (TRK && ANYB) ? tfO[p] : 0u;
+      // tracking rules: best 0 and no stamp yet (finish(): such a diagonal reports its first cell under rule 0)
+      bestE[p] = bestO[p] = NEGV;
+      kbE[p] = kbO[p] = 0u; btE[p] = btO[p] = 0u;
       OW[p] = pk::pack((int32_t)letter_o(xbase + p - 1), (int32_t)letter_o(xbase + p + RH - 1));
       if (MAT) MW[p] = pk::pack((int32_t)msel_lo(ybase - p - 1), (int32_t)msel_hi(ybase - p - RH - 1));
       else MW[p] = pk::pack((int32_t)letter_m(ybase - p - 1), (int32_t)letter_m(ybase - p - RH - 1));
@@ -1179,17 +1230,47 @@ struct WaveFill16 {
     const bool mrow_ok = valid && li < pd.nl;
     mrow0 = mrow_ok ? (uint32_t)mask_word_index(BK, pd.nl, 0, li, 0) : mspare;
     mrow_step = mrow_ok ? (uint32_t)mask_word_index(BK, pd.nl, 1, 0, 0) : 0u;
+    mrowb = 4u * mrow0;
+    if (SBASE) {
+#pragma unroll
+      for (int g = 0; g < BK / 4; g++)   // (opaque: left to itself the compiler adds the group's distance per lane, in 64 bits)
+        mbase[g] = pk::opaque_s((uint8_t*)(a.masks + pd.mask_off) + (uint64_t)(4u * (uint32_t)g * mgroup));
+    }
     feed_issue(0);
-    for (int b = 0; b < wd.nblocks; b++) {
-      feed_commit(b, !(b >= wd.steady_b0 && b < sb1));
-      if (b + 1 < wd.nblocks) feed_issue(b + 1);
-      if (b >= wd.steady_b0 && b < sb1) block16<0>(b);
-      else if (!ANYB) block16<3>(b);
-      else if (b >= wd.steady_b0) block16<2>(b);                   // every diagonal has started, some may have ended
-      else if (sb1 > wd.steady_b0) block16<1>(b);                  // some have not started; none has ended before the steady range
-      else block16<3>(b);                                          // (no steady range: the planner's bounds cannot tell)
+    if constexpr (SPLIT) {
+      // One loop per kind of block, in the order a pair runs through them: with a single body the loop-carried state stays in
+      // the registers it was computed in.  (One loop that chose among the four bodies joined them in a shared tail, and the
+      // allocator then copied about 14 registers of state on every back edge.)
+      const int nb = nblocks_run();
+      const int b0 = wd.steady_b0 < nb ? (wd.steady_b0 > 0 ? wd.steady_b0 : 0) : nb;
+      const int b1 = sb1 < nb ? sb1 : nb;
+      int b = 0;
+      if (sb1 > wd.steady_b0) for (; b < b0; b++) blocks_step<1>(b);   // some have not started; none has ended before the steady range
+      else for (; b < b0; b++) blocks_step<3>(b);                      // (no steady range: the planner's bounds cannot tell)
+      for (; b < b1; b++) blocks_step<0>(b);
+      for (; b < nb; b++) blocks_step<2>(b);                           // every diagonal has started, some may have ended
+    } else {
+      for (int b = 0, nb = nblocks_run(); b < nb; b++) {
+        const bool steady = b >= wd.steady_b0 && b < sb1;
+        feed_commit(b, !steady);
+        if (b + 1 < nb) feed_issue(b + 1);
+        if (steady) block16<0>(b);
+        else if (!ANYB) block16<3>(b);
+        else if (b >= wd.steady_b0) block16<2>(b);                   // every diagonal has started, some may have ended
+        else if (sb1 > wd.steady_b0) block16<1>(b);                  // some have not started; none has ended before the steady range
+        else block16<3>(b);                                          // (no steady range: the planner's bounds cannot tell)
+      }
     }
     finish();
+  }
+  // One pair per wavefront (or workgroup): the wavefront's block count IS the pair's (plan_waves); the minimum keeps the mask
+  // stores, which no longer test the block against the pair's count, inside the plane whatever a descriptor says.
+  PW_FN int nblocks_run() const { return SBASE ? (wd.nblocks < pd.nblocks ? wd.nblocks : pd.nblocks) : wd.nblocks; }
+  template <int EK>
+  PW_FN void blocks_step(int b) {
+    feed_commit(b, EK != 0);
+    if (b + 1 < nblocks_run()) feed_issue(b + 1);
+    block16<EK>(b);
   }
 
   // End-cell search for the two rules this kernel serves (END_STD_LOCAL, END_BANDED_LOCAL): the first best
@@ -1202,7 +1283,10 @@ struct WaveFill16 {
     uint32_t parked[4 * RH];
 #pragma unroll
     for (int p = 0; p < RH; p++) {
-      parked[4 * p] = bestE[p]; parked[4 * p + 1] = btE[p]; parked[4 * p + 2] = bestO[p]; parked[4 * p + 3] = btO[p];
+      // (copies made here, after the block loops: parked straight from the loop-carried registers, the array's register
+      //  tuple was kept up to date by moves in every block)
+      parked[4 * p] = TRK ? pk::opaque(kbE[p]) : bestE[p]; parked[4 * p + 1] = TRK ? pk::opaque(btE[p]) : 0u;
+      parked[4 * p + 2] = TRK ? pk::opaque(kbO[p]) : bestO[p]; parked[4 * p + 3] = TRK ? pk::opaque(btO[p]) : 0u;
     }
 #pragma unroll 1
     for (int q = 0; q < 2 * RH; q++) {
@@ -1212,9 +1296,21 @@ struct WaveFill16 {
       for (int h = 0; h < 2; h++) {
         const int j = 2 * p + odd + h * R;
         const int dd = li * BK + j, d = pd.dmin + dd;
-        const int32_t s = (h ? pk::hi_s(bq) : pk::lo_s(bq)) / SCL;   // (exact: every running value is a multiple of SCL)
-        const int bt = (int)(h ? (tq >> 16) : (tq & 0xffffu));
         const int tfirst = (d < 0 ? -d : d) - pd.s0;
+        int32_t s; int bt;
+        if (TRK) {
+          // key = 8 score + (7 - cell) with the score unscaled (SC4: 2 (4 score) + ..); stamp = 8 (block + 1) + 7 - cell of the
+          // cell that first reached it, below 8 while the best stayed 0.  Rule 0: scores never go below 0, and a diagonal whose
+          // best stays 0 reports its first cell (score 0 on the table edge).  (Rule 5: a best of 0 never wins -- the end cell
+          // must beat 0 -- so where it "was reached" does not matter.)
+          const uint32_t key = h ? (bq >> 16) : (bq & 0xffffu), stamp = h ? (tq >> 16) : (tq & 0xffffu);
+          s = (int32_t)(key >> 3);
+          if (stamp < 8u) bt = ANYB ? (int)((uint32_t)tfirst & 0xffffu) : 0;
+          else bt = 16 * ((int)(stamp >> 3) - 1) + 2 * (7 - (int)(stamp & 7u)) + odd;
+        } else {
+          s = (h ? pk::hi_s(bq) : pk::lo_s(bq)) / SCL;                 // (exact: every running value is a multiple of SCL)
+          bt = 0;
+        }
         const int aa = (bt - tfirst) >> 1;
         int x = aa + (d > 0 ? d : 0), y = aa - (d < 0 ? d : 0);
         uint64_t k;
