@@ -139,7 +139,9 @@ MSEED_EXPORTS = ['pw_mseeds_create', 'pw_mseeds_build', 'pw_mseeds_num_seqs', 'p
                  'pw_mseeds_last_error']
 
 # every symbol include/pw_overlap.h declares
-OVERLAP_EXPORTS = ['pw_overlap_bands', 'pw_overlap_all_pairs', 'pw_overlap_last_ms', 'pw_overlap_last_error']
+OVERLAP_EXPORTS = ['pw_overlap_bands', 'pw_overlap_all_pairs', 'pw_overlap_last_ms', 'pw_overlap_last_error',
+                   'pw_overlap_bands_stranded', 'pw_overlap_all_pairs_stranded', 'pw_overlap_arena_upload', 'pw_overlap_arena_read']
+PW_STRAND_PLUS, PW_STRAND_MINUS, PW_STRAND_BOTH = 1, 2, 3
 
 
 class pw_read_pair(C.Structure):
@@ -333,6 +335,15 @@ def load():
     lib.pw_overlap_all_pairs.argtypes = [C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int,
                                          C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p]
+    lib.pw_overlap_bands_stranded.argtypes = [C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int64, C.c_int, C.c_int,
+                                              C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.pw_overlap_all_pairs_stranded.argtypes = [C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int,
+                                                  C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64,
+                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.pw_overlap_arena_upload.argtypes = [C.c_int, C.c_void_p, C.c_uint64, C.c_uint64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_int]
+    lib.pw_overlap_arena_upload.restype = C.c_void_p
+    lib.pw_overlap_arena_read.argtypes = [C.c_int, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
     lib.pw_overlap_last_ms.restype = C.c_double
     lib.pw_overlap_last_error.restype = C.c_char_p
     _lib = lib

@@ -98,6 +98,42 @@ class DeviceArena(object):
         if not self.ptr:
             raise RuntimeError('pw_arena_upload failed: ' + W.last_error())
 
+    @classmethod
+    def with_reverse_complements(cls, arena, offsets, lengths, which, complement, device=0):
+        """The arena uploaded once, and behind it the reverse complements of the reads ``which`` (indices into ``offsets`` /
+        ``lengths``), written by the device from the forward letters (``pw_overlap_arena_upload``) with the frame alignment
+        and slack of :func:`pack_reads`.  ``rc_offsets[q]`` is the offset of ``rc(reads[which[q]])``; ``nbytes`` covers the
+        forward and the reverse-complement frames, so a batch refers to either kind as an ordinary frame."""
+        self = cls.__new__(cls)
+        self.lib = W.load()
+        arena = np.ascontiguousarray(arena, np.uint8)
+        which = np.ascontiguousarray(which, np.int64).reshape(-1)
+        comp = np.ascontiguousarray(complement, np.uint8)
+        offsets, lengths = np.asarray(offsets, np.int64), np.asarray(lengths, np.int64)
+        src = np.ascontiguousarray(offsets[which].astype(np.uint64))
+        ln = np.ascontiguousarray(lengths[which].astype(np.int32))
+        sizes = (lengths[which] + 15) // 16 * 16 + 16
+        base = (arena.nbytes + 15) // 16 * 16
+        dst = np.zeros(len(which), np.uint64)
+        if len(which):
+            dst[:] = base + np.concatenate([[0], np.cumsum(sizes)[:-1]])
+        total = int(base + sizes.sum() + 16)
+        self.device, self.nbytes, self.rc_offsets = device, total, dst.astype(np.int64)
+        self.ptr = self.lib.pw_overlap_arena_upload(device, arena.ctypes.data, arena.nbytes, total, len(which), src.ctypes.data,
+                                                    dst.ctypes.data, ln.ctypes.data, comp.ctypes.data, len(comp))
+        if not self.ptr:
+            raise RuntimeError('pw_overlap_arena_upload failed: ' + (self.lib.pw_overlap_last_error() or b'').decode())
+        return self
+
+    def read(self, offset=0, nbytes=None):
+        """A piece of the device arena back on the host (uint8 array)."""
+        nbytes = self.nbytes - offset if nbytes is None else nbytes
+        assert 0 <= offset and offset + nbytes <= self.nbytes
+        out = np.zeros(max(nbytes, 1), np.uint8)
+        if self.lib.pw_overlap_arena_read(self.device, self.ptr, offset, nbytes, out.ctypes.data) != 0:
+            raise RuntimeError('pw_overlap_arena_read failed: ' + (self.lib.pw_overlap_last_error() or b'').decode())
+        return out[:nbytes]
+
     def close(self):
         if self.ptr:
             self.lib.pw_arena_free(self.device, self.ptr)
@@ -196,7 +232,8 @@ class BatchAligner(object):
         an (n, 2) array of read indices (origin, mutant), ``diag_ranges`` an (n, 2) array in banded mode.  This is the
         shape of overlap pipelines, where every read takes part in dozens of pairs.  With ``device_arena`` (a
         :class:`DeviceArena` of the same arena) the batch reads the reads from that device copy -- uploaded once for
-        all the batches of a job -- instead of allocating and uploading its own."""
+        all the batches of a job -- instead of allocating and uploading its own; ``arena_bytes`` then gives the size of that
+        copy when it holds more frames than ``arena`` (:meth:`DeviceArena.with_reverse_complements`)."""
         self = cls.__new__(cls)
         self.lib = W.load()
         self.alnmode = kw.get('alnmode', W.STD_MODE)
@@ -232,12 +269,13 @@ class BatchAligner(object):
                           float(self.go_score), float(self.ge_score))
         self.device = kw.get('device', 0)
         self.flags = kw.get('flags', 0) | (W.PW_FLAG_SHARED_ARENA if device_arena is not None else 0)
+        arena_bytes = int(kw['arena_bytes']) if device_arena is not None and kw.get('arena_bytes') else self.arena.nbytes
         self.handle = self.lib.pw_batch_create(self.device, C.byref(sc), self.n, rec.ctypes.data_as(C.POINTER(W.pw_pair)),
-                                               self.arena.nbytes, self.flags)
+                                               arena_bytes, self.flags)
         if not self.handle:
             raise RuntimeError('pw_batch_create failed: ' + W.last_error())
         if device_arena is not None:
-            assert device_arena.device == self.device and device_arena.nbytes >= self.arena.nbytes
+            assert device_arena.device == self.device and device_arena.nbytes >= arena_bytes
             self._device_arena = device_arena          # keeps it alive as long as the batch
             self._ck(self.lib.pw_batch_share_arena(self.handle, device_arena.ptr), 'pw_batch_share_arena')
         else:

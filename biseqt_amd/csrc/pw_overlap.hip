@@ -47,6 +47,37 @@ __global__ __launch_bounds__(256) void k_enc_batch(const uint8_t* __restrict__ a
   pos[g] = q;
 }
 
+// The complement table of a call in LDS (alphabet_len <= 36 bytes), read by every thread of the block.
+__device__ __forceinline__ void load_complement(const uint8_t* __restrict__ comp, int L, uint8_t* s_comp) {
+  if ((int)threadIdx.x < 36) s_comp[threadIdx.x] = (int)threadIdx.x < L ? comp[threadIdx.x] : (uint8_t)0;
+  __syncthreads();
+}
+// K8a', stranded pair list: the T side where strand[p] != 0 encodes T = rc(read): the k-mer at position q of T is
+// comp(read[len - 1 - q]), comp(read[len - 2 - q]), ... -- read backwards from the forward letters, never materialised.
+// Entries are generated in ascending q, so the stable sort keeps positions of T ascending inside a k-mer.
+__global__ __launch_bounds__(256) void k_enc_batch_rc(const uint8_t* __restrict__ arena, const DPair* __restrict__ pairs,
+                                                      const uint64_t* __restrict__ start, int64_t npairs, int64_t total,
+                                                      const uint8_t* __restrict__ strand, const uint8_t* __restrict__ comp,
+                                                      int k, int L, int kbits, uint64_t* __restrict__ keys, uint32_t* __restrict__ pos) {
+  __shared__ uint8_t s_comp[36];
+  load_complement(comp, L, s_comp);
+  const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (g >= total) return;
+  const int64_t p = upper_bound_dev<uint64_t>(start, npairs + 1, (uint64_t)g) - 1;
+  const DPair pr = pairs[p];
+  const uint32_t q = (uint32_t)(g - (int64_t)start[p]);
+  uint64_t v = 0;
+  if (strand[p]) {
+    const uint8_t* __restrict__ s = arena + pr.t_off + (uint64_t)(pr.t_len - 1) - q;      // q <= t_len - k: s[-t] stays inside
+    for (int t = 0; t < k; t++) v = v * (uint64_t)L + s_comp[s[-t]];
+  } else {
+    const uint8_t* __restrict__ s = arena + pr.t_off + q;
+    for (int t = 0; t < k; t++) v = v * (uint64_t)L + s[t];
+  }
+  keys[g] = ((uint64_t)p << kbits) | v;
+  pos[g] = q;
+}
+
 __global__ __launch_bounds__(256) void k_join_hist(const uint64_t* __restrict__ ks, const uint32_t* __restrict__ ps, int64_t ns,
                                                    const uint64_t* __restrict__ kt, const uint32_t* __restrict__ pt, int64_t nt,
                                                    const DPair* __restrict__ pairs, int kbits, uint32_t* __restrict__ hist,
@@ -274,28 +305,99 @@ __global__ __launch_bounds__(256) void k_self_expand(const uint64_t* __restrict_
   pkey[o] = (va >> 32) * nreads + (vb >> 32);
   dval[o] = (int32_t)(uint32_t)va - (int32_t)(uint32_t)vb;
 }
+// ---- both strands (K9'): a second index holds the k-mers of rc(read) for every read, computed from the forward letters ----
+// K9a': entry q of read r is the k-mer at position q of rc(read r): comp(read[len - 1 - q]), comp(read[len - 2 - q]), ...
+// Generated in ascending (read, q), so inside a run of equal k-mers the stable sort leaves (read, q) ascending.
+__global__ __launch_bounds__(256) void k_enc_reads_rc(const uint8_t* __restrict__ arena, const uint64_t* __restrict__ roff,
+                                                      const int32_t* __restrict__ rlen, const uint64_t* __restrict__ rstart,
+                                                      int64_t nreads, int64_t total, int k, int L, const uint8_t* __restrict__ comp,
+                                                      uint64_t* __restrict__ keys, uint64_t* __restrict__ vals) {
+  __shared__ uint8_t s_comp[36];
+  load_complement(comp, L, s_comp);
+  const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (g >= total) return;
+  const int64_t r = upper_bound_dev<uint64_t>(rstart, nreads + 1, (uint64_t)g) - 1;
+  const uint32_t q = (uint32_t)(g - (int64_t)rstart[r]);
+  const uint8_t* __restrict__ s = arena + roff[r] + (uint64_t)(rlen[r] - 1) - q;           // q <= len - k: s[-t] stays inside
+  uint64_t v = 0;
+  for (int t = 0; t < k; t++) v = v * (uint64_t)L + s_comp[s[-t]];
+  keys[g] = v;
+  vals[g] = ((uint64_t)r << 32) | q;
+}
+// K9b': forward element e of read a pairs with the forward entries (sel & 1) and the reverse entries (sel & 2) of every read
+// b > a that hold the same k-mer: [ff[e], ff[e] + cf[e]) of the forward index, then [fr[e], ...) of the reverse index.
+// A read is never joined with its own reverse complement, and no reverse entry plays the a side.
+__global__ __launch_bounds__(256) void k_self_count_st(const uint64_t* __restrict__ keys, const uint64_t* __restrict__ vals, int64_t n,
+                                                       const uint64_t* __restrict__ rkeys, const uint64_t* __restrict__ rvals, int sel,
+                                                       int shard_rank, int shard_world, uint32_t* __restrict__ ff, uint32_t* __restrict__ cf,
+                                                       uint32_t* __restrict__ fr, uint64_t* __restrict__ cnt) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= n) return;
+  ff[e] = 0; fr[e] = 0; cf[e] = 0;
+  if ((int)((vals[e] >> 32) % (uint64_t)shard_world) != shard_rank) { cnt[e] = 0; return; }
+  const uint64_t key = keys[e];
+  const uint64_t next_read = ((vals[e] >> 32) + 1) << 32;
+  uint64_t c = 0;
+  if (sel & 1) {
+    const int64_t hi = upper_bound_dev<uint64_t>(keys, n, key);
+    const int64_t f = e + 1 + lower_bound_dev<uint64_t>(vals + e + 1, hi - e - 1, next_read);
+    ff[e] = (uint32_t)f; cf[e] = (uint32_t)(hi - f);
+    c += (uint64_t)(hi - f);
+  }
+  if (sel & 2) {
+    const int64_t lo = lower_bound_dev<uint64_t>(rkeys, n, key);
+    const int64_t hi = upper_bound_dev<uint64_t>(rkeys, n, key);
+    const int64_t f = lo + lower_bound_dev<uint64_t>(rvals + lo, hi - lo, next_read);
+    fr[e] = (uint32_t)f;
+    c += (uint64_t)(hi - f);
+  }
+  cnt[e] = c;
+}
+// one seed per thread: key = 2 (ra * nreads + rb) + strand, value = d = pos_a - pos_b with pos_b in the frame of rc(rb) on the
+// minus strand.  Per pair and strand the seeds come out in (k-mer, i, j) order, which the stable sort by the key keeps.
+__global__ __launch_bounds__(256) void k_self_expand_st(const uint64_t* __restrict__ off, int64_t n, int64_t nseeds,
+                                                        const uint64_t* __restrict__ vals, const uint64_t* __restrict__ rvals,
+                                                        const uint32_t* __restrict__ ff, const uint32_t* __restrict__ cf,
+                                                        const uint32_t* __restrict__ fr, uint64_t nreads,
+                                                        uint64_t* __restrict__ pkey, int32_t* __restrict__ dval) {
+  const int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (o >= nseeds) return;
+  const int64_t e = upper_bound_dev<uint64_t>(off, n, (uint64_t)o) - 1;
+  const uint64_t t = (uint64_t)o - off[e];
+  const uint64_t nf = cf[e];
+  const uint64_t va = vals[e];
+  const uint64_t vb = t < nf ? vals[(uint64_t)ff[e] + t] : rvals[(uint64_t)fr[e] + (t - nf)];
+  pkey[o] = (((va >> 32) * nreads + (vb >> 32)) << 1) | (t < nf ? 0ull : 1ull);
+  dval[o] = (int32_t)(uint32_t)va - (int32_t)(uint32_t)vb;
+}
 // per candidate pair (unique key u, seeds [soff[u], soff[u] + scount[u])): its reads, histogram base, first diagonal
+// (ST = 1: the key carries the strand in its lowest bit, written to ps)
+template <int ST>
 __global__ __launch_bounds__(256) void k_cand_pairs(const uint64_t* __restrict__ ukeys, const uint64_t* __restrict__ soff,
                                                     const int32_t* __restrict__ dval, int64_t np, uint64_t nreads,
                                                     const uint64_t* __restrict__ roff, const int32_t* __restrict__ rlen,
                                                     const uint64_t* __restrict__ hbase, DPair* __restrict__ pairs,
-                                                    int32_t* __restrict__ d_first, int32_t* __restrict__ pa, int32_t* __restrict__ pb) {
+                                                    int32_t* __restrict__ d_first, int32_t* __restrict__ pa, int32_t* __restrict__ pb,
+                                                    uint8_t* __restrict__ ps) {
   const int64_t u = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (u >= np) return;
-  const uint64_t a = ukeys[u] / nreads, b = ukeys[u] % nreads;
+  const uint64_t key = ukeys[u] >> ST;
+  const uint64_t a = key / nreads, b = key % nreads;
   pairs[u] = DPair{roff[a], roff[b], rlen[a], rlen[b], hbase[u]};
   d_first[u] = dval[soff[u]];
   pa[u] = (int32_t)a; pb[u] = (int32_t)b;
+  if (ST) ps[u] = (uint8_t)(ukeys[u] & 1ull);
 }
 constexpr int kSmallPair = 64;     // pairs with at most this many seeds are scored by one wavefront, without a histogram
 constexpr int kMediumPair = 2048;  // all-pairs path: up to this many seeds by one workgroup from the seed list (k_band_medium)
+template <int ST>
 __global__ __launch_bounds__(256) void k_pair_hsize(const uint64_t* __restrict__ ukeys, const unsigned long long* __restrict__ cnt,
                                                     int64_t np, uint64_t nreads, const int32_t* __restrict__ rlen,
                                                     uint64_t* __restrict__ hsize, int sparse_max) {
   const int64_t u = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (u >= np) return;
-  hsize[u] = cnt[u] <= (unsigned long long)sparse_max ? 0ull
-                                                      : (uint64_t)rlen[ukeys[u] / nreads] + (uint64_t)rlen[ukeys[u] % nreads] + 1;
+  const uint64_t key = ukeys[u] >> ST;
+  hsize[u] = cnt[u] <= (unsigned long long)sparse_max ? 0ull : (uint64_t)rlen[key / nreads] + (uint64_t)rlen[key % nreads] + 1;
 }
 // seeds [s0, s1) belong to the pairs [u0, u1) of this chunk; hbase is relative to the chunk's first histogram entry
 __global__ __launch_bounds__(256) void k_scatter_hist(const int32_t* __restrict__ dval, int64_t s0, int64_t s1,
@@ -495,8 +597,10 @@ __global__ __launch_bounds__(256) void k_band_medium(const DPair* __restrict__ p
   }
 }
 
+// strand (host, one byte per pair of the chunk) and d_comp are null on the forward-only path
 int run_chunk(const uint8_t* d_arena, const pw_read_pair* pairs, int64_t n, int L, int k, int kbits, BandConst bc,
-              pw_overlap_band* out, hipEvent_t ev0, hipEvent_t ev1, float* ms) {
+              pw_overlap_band* out, hipEvent_t ev0, hipEvent_t ev1, float* ms, const uint8_t* strand = nullptr,
+              const uint8_t* d_comp = nullptr) {
   std::vector<DPair> hp((size_t)n);
   std::vector<uint64_t> ss((size_t)n + 1), ts((size_t)n + 1);
   uint64_t hb = 0, cs = 0, ct = 0;
@@ -517,6 +621,11 @@ int run_chunk(const uint8_t* d_arena, const pw_read_pair* pairs, int64_t n, int 
   CHECK(hipMemcpy(dp.p, hp.data(), sizeof(DPair) * (size_t)n, hipMemcpyHostToDevice));
   CHECK(hipMemcpy(dss.p, ss.data(), 8 * ((size_t)n + 1), hipMemcpyHostToDevice));
   CHECK(hipMemcpy(dts.p, ts.data(), 8 * ((size_t)n + 1), hipMemcpyHostToDevice));
+  DeviceBuffer dstrand;
+  if (strand) {
+    CHECK(dstrand.ensure((size_t)n));
+    CHECK(hipMemcpy(dstrand.p, strand, (size_t)n, hipMemcpyHostToDevice));
+  }
   CHECK(hipEventRecord(ev0, nullptr));
   CHECK(hipMemsetAsync(hist.p, 0, 4 * (size_t)hb, nullptr));
   CHECK(hipMemsetAsync(rows.p, 0, 8 * (size_t)n, nullptr));
@@ -525,8 +634,13 @@ int run_chunk(const uint8_t* d_arena, const pw_read_pair* pairs, int64_t n, int 
   for (int side = 0; side < 2; side++) {
     const uint64_t tot = side ? ct : cs;
     if (tot == 0) continue;
-    hipLaunchKernelGGL(k_enc_batch, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, nullptr, d_arena, (const DPair*)dp.p,
-                       (const uint64_t*)(side ? dts.p : dss.p), n, (int64_t)tot, side, k, L, kbits, (uint64_t*)kin.p, (uint32_t*)pin.p);
+    if (side && strand)
+      hipLaunchKernelGGL(k_enc_batch_rc, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, nullptr, d_arena, (const DPair*)dp.p,
+                         (const uint64_t*)dts.p, n, (int64_t)tot, (const uint8_t*)dstrand.p, d_comp, k, L, kbits, (uint64_t*)kin.p,
+                         (uint32_t*)pin.p);
+    else
+      hipLaunchKernelGGL(k_enc_batch, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, nullptr, d_arena, (const DPair*)dp.p,
+                         (const uint64_t*)(side ? dts.p : dss.p), n, (int64_t)tot, side, k, L, kbits, (uint64_t*)kin.p, (uint32_t*)pin.p);
     uint64_t* ko = (uint64_t*)(side ? ktb.p : ksb.p); uint32_t* po = (uint32_t*)(side ? ptb.p : psb.p);
     CHECK(rocprim_run(tmp, [&](void* t, size_t& b) {
       return rocprim::radix_sort_pairs(t, b, (const uint64_t*)kin.p, ko, (const uint32_t*)pin.p, po, (size_t)tot, 0u,
@@ -556,16 +670,24 @@ int run_chunk(const uint8_t* d_arena, const pw_read_pair* pairs, int64_t n, int 
   return 0;
 }
 
+// sel: 1 forward pairs only (d_comp and pair_strand unused: the kernels and keys of the unstranded call), 2 minus pairs only,
+// 3 both.  With sel != 1 a second index of the same size holds the reverse-strand k-mers and the pair key carries the strand.
 int run_all_pairs(const uint8_t* d_arena, const uint64_t* read_off, const int32_t* read_len, int64_t R, int L, int k, int kbits,
                   BandConst bc, int shard_rank, int shard_world, int64_t max_pairs, int32_t* pair_a, int32_t* pair_b, pw_overlap_band* out,
-                  int64_t* n_out, float* ms) {
+                  int64_t* n_out, float* ms, int sel = 1, const uint8_t* d_comp = nullptr, uint8_t* pair_strand = nullptr) {
+  const bool st = sel != 1;
   std::vector<uint64_t> rstart((size_t)R + 1);
   uint64_t K = 0;
   for (int64_t r = 0; r < R; r++) { rstart[(size_t)r] = K; K += read_len[r] >= k ? (uint64_t)(read_len[r] - k + 1) : 0; }
   rstart[(size_t)R] = K;
   *n_out = 0;
   if (K == 0) return 0;
-  if (K >= (1ull << 32)) { set_err("more than 2^32 k-mers in one index: split the read set"); return -1; }
+  if (K >= (1ull << 32)) {
+    set_err(st ? "more than 2^32 k-mers in one index: split the read set (with the reverse strand the index holds twice the entries, "
+                 "2^32 per strand)"
+               : "more than 2^32 k-mers in one index: split the read set");
+    return -1;
+  }
   DeviceEvent ev0, ev1;
   CHECK(ev0.create()); CHECK(ev1.create());
   DeviceBuffer droff, drlen, drstart, kin, vin, ks, vs, fs, cnt, off, scal, tmp;
@@ -583,8 +705,22 @@ int run_all_pairs(const uint8_t* d_arena, const uint64_t* read_off, const int32_
     return rocprim::radix_sort_pairs(t, b, (const uint64_t*)kin.p, (uint64_t*)ks.p, (const uint64_t*)vin.p, (uint64_t*)vs.p, (size_t)K,
                                      0u, (unsigned)kbits, (hipStream_t) nullptr);
   }));
-  hipLaunchKernelGGL(k_self_count, gK, blk, 0, nullptr, (const uint64_t*)ks.p, (const uint64_t*)vs.p, (int64_t)K, shard_rank, shard_world,
-                     (uint32_t*)fs.p, (uint64_t*)cnt.p);
+  DeviceBuffer kr, vr, fr, cf;       // the reverse-strand index and its side of the join
+  if (st) {
+    CHECK(kr.ensure(8 * (size_t)K)); CHECK(vr.ensure(8 * (size_t)K)); CHECK(fr.ensure(4 * (size_t)K)); CHECK(cf.ensure(4 * (size_t)K));
+    hipLaunchKernelGGL(k_enc_reads_rc, gK, blk, 0, nullptr, d_arena, (const uint64_t*)droff.p, (const int32_t*)drlen.p,
+                       (const uint64_t*)drstart.p, R, (int64_t)K, k, L, d_comp, (uint64_t*)kin.p, (uint64_t*)vin.p);
+    CHECK(rocprim_run(tmp, [&](void* t, size_t& b) {
+      return rocprim::radix_sort_pairs(t, b, (const uint64_t*)kin.p, (uint64_t*)kr.p, (const uint64_t*)vin.p, (uint64_t*)vr.p, (size_t)K,
+                                       0u, (unsigned)kbits, (hipStream_t) nullptr);
+    }));
+    hipLaunchKernelGGL(k_self_count_st, gK, blk, 0, nullptr, (const uint64_t*)ks.p, (const uint64_t*)vs.p, (int64_t)K,
+                       (const uint64_t*)kr.p, (const uint64_t*)vr.p, sel, shard_rank, shard_world, (uint32_t*)fs.p, (uint32_t*)cf.p,
+                       (uint32_t*)fr.p, (uint64_t*)cnt.p);
+  } else {
+    hipLaunchKernelGGL(k_self_count, gK, blk, 0, nullptr, (const uint64_t*)ks.p, (const uint64_t*)vs.p, (int64_t)K, shard_rank, shard_world,
+                       (uint32_t*)fs.p, (uint64_t*)cnt.p);
+  }
   DeviceBuffer tmp2;
   CHECK(rocprim_run(tmp2, [&](void* t, size_t& b) {
     return rocprim::exclusive_scan(t, b, (const uint64_t*)cnt.p, (uint64_t*)off.p, (uint64_t)0, (size_t)K, rocprim::plus<uint64_t>(), (hipStream_t) nullptr);
@@ -598,9 +734,15 @@ int run_all_pairs(const uint8_t* d_arena, const uint64_t* read_off, const int32_
   // seeds -> (pair key, d), stably sorted by the pair key
   DeviceBuffer pk_in, dv_in, pk, dv;
   CHECK(pk_in.ensure(8 * (size_t)NS)); CHECK(dv_in.ensure(4 * (size_t)NS)); CHECK(pk.ensure(8 * (size_t)NS)); CHECK(dv.ensure(4 * (size_t)NS));
-  hipLaunchKernelGGL(k_self_expand, dim3((unsigned)((NS + 255) / 256)), blk, 0, nullptr, (const uint64_t*)off.p, (int64_t)K, (int64_t)NS,
-                     (const uint64_t*)vs.p, (const uint32_t*)fs.p, (uint64_t)R, (uint64_t*)pk_in.p, (int32_t*)dv_in.p);
+  if (st)
+    hipLaunchKernelGGL(k_self_expand_st, dim3((unsigned)((NS + 255) / 256)), blk, 0, nullptr, (const uint64_t*)off.p, (int64_t)K, (int64_t)NS,
+                       (const uint64_t*)vs.p, (const uint64_t*)vr.p, (const uint32_t*)fs.p, (const uint32_t*)cf.p, (const uint32_t*)fr.p,
+                       (uint64_t)R, (uint64_t*)pk_in.p, (int32_t*)dv_in.p);
+  else
+    hipLaunchKernelGGL(k_self_expand, dim3((unsigned)((NS + 255) / 256)), blk, 0, nullptr, (const uint64_t*)off.p, (int64_t)K, (int64_t)NS,
+                       (const uint64_t*)vs.p, (const uint32_t*)fs.p, (uint64_t)R, (uint64_t*)pk_in.p, (int32_t*)dv_in.p);
   int pbits = 1; while ((((uint64_t)R * (uint64_t)R) >> pbits) != 0) pbits++;
+  if (st) pbits++;                                     // the strand bit below the pair rank
   DeviceBuffer tmp3;
   CHECK(rocprim_run(tmp3, [&](void* t, size_t& b) {
     return rocprim::radix_sort_pairs(t, b, (const uint64_t*)pk_in.p, (uint64_t*)pk.p, (const int32_t*)dv_in.p, (int32_t*)dv.p, (size_t)NS,
@@ -623,7 +765,8 @@ int run_all_pairs(const uint8_t* d_arena, const uint64_t* read_off, const int32_
     return -1;
   }
   // seed offsets and histogram bases of the candidate pairs
-  DeviceBuffer soff, hsize, hbase, dpairs, dfirst, dpa, dpb, dout;
+  DeviceBuffer soff, hsize, hbase, dpairs, dfirst, dpa, dpb, dps, dout;
+  if (st) CHECK(dps.ensure((size_t)NP));
   CHECK(soff.ensure(8 * (size_t)NP)); CHECK(hsize.ensure(8 * (size_t)NP)); CHECK(hbase.ensure(8 * (size_t)NP));
   CHECK(dpairs.ensure(sizeof(DPair) * (size_t)NP)); CHECK(dfirst.ensure(4 * (size_t)NP)); CHECK(dpa.ensure(4 * (size_t)NP));
   CHECK(dpb.ensure(4 * (size_t)NP)); CHECK(dout.ensure(sizeof(pw_overlap_band) * (size_t)NP));
@@ -635,12 +778,14 @@ int run_all_pairs(const uint8_t* d_arena, const uint64_t* read_off, const int32_
     });
   };
   CHECK(scan_np(uc, soff));
-  hipLaunchKernelGGL(k_pair_hsize, gP, blk, 0, nullptr, (const uint64_t*)uk.p, (const unsigned long long*)uc.p, (int64_t)NP, (uint64_t)R,
+  auto* const hsize_kernel = st ? k_pair_hsize<1> : k_pair_hsize<0>;
+  auto* const cand_kernel = st ? k_cand_pairs<1> : k_cand_pairs<0>;
+  hipLaunchKernelGGL(hsize_kernel, gP, blk, 0, nullptr, (const uint64_t*)uk.p, (const unsigned long long*)uc.p, (int64_t)NP, (uint64_t)R,
                      (const int32_t*)drlen.p, (uint64_t*)hsize.p, kMediumPair);
   CHECK(scan_np(hsize, hbase));
-  hipLaunchKernelGGL(k_cand_pairs, gP, blk, 0, nullptr, (const uint64_t*)uk.p, (const uint64_t*)soff.p, (const int32_t*)dv.p, (int64_t)NP, (uint64_t)R,
-                     (const uint64_t*)droff.p, (const int32_t*)drlen.p, (const uint64_t*)hbase.p, (DPair*)dpairs.p, (int32_t*)dfirst.p,
-                     (int32_t*)dpa.p, (int32_t*)dpb.p);
+  hipLaunchKernelGGL(cand_kernel, gP, blk, 0, nullptr, (const uint64_t*)uk.p, (const uint64_t*)soff.p,
+                     (const int32_t*)dv.p, (int64_t)NP, (uint64_t)R, (const uint64_t*)droff.p, (const int32_t*)drlen.p,
+                     (const uint64_t*)hbase.p, (DPair*)dpairs.p, (int32_t*)dfirst.p, (int32_t*)dpa.p, (int32_t*)dpb.p, (uint8_t*)dps.p);
   hipLaunchKernelGGL(k_band_small, dim3((unsigned)((NP * 64 + 255) / 256)), blk, 0, nullptr, (const DPair*)dpairs.p, (const uint64_t*)soff.p,
                      (const unsigned long long*)uc.p, (const int32_t*)dv.p, (const int32_t*)nullptr, (int64_t)NP, bc, (pw_overlap_band*)dout.p);
   // pairs with 65 .. kMediumPair seeds: one workgroup each, from the seed list
@@ -690,6 +835,7 @@ int run_all_pairs(const uint8_t* d_arena, const uint64_t* read_off, const int32_
   CHECK(hipMemcpy(out, dout.p, sizeof(pw_overlap_band) * (size_t)NP, hipMemcpyDeviceToHost));
   CHECK(hipMemcpy(pair_a, dpa.p, 4 * (size_t)NP, hipMemcpyDeviceToHost));
   CHECK(hipMemcpy(pair_b, dpb.p, 4 * (size_t)NP, hipMemcpyDeviceToHost));
+  if (st) CHECK(hipMemcpy(pair_strand, dps.p, (size_t)NP, hipMemcpyDeviceToHost));
   CHECK(hipGetLastError());
   float t = 0.f;
   CHECK(hipEventElapsedTime(&t, ev0.e, ev1.e));
@@ -718,6 +864,15 @@ int check_args(int L, int k, bool bad_args, double len_coeff, double radius_coef
   return 0;
 }
 
+// complement[c] for c < L: a permutation of the alphabet that is its own inverse
+int check_complement(const uint8_t* comp, int L) {
+  if (L < 1 || L > 36) return 0;                       // (check_args reports the alphabet)
+  bool ok = comp != nullptr;
+  for (int c = 0; ok && c < L; c++) ok = comp[c] < L && comp[comp[c]] == c;
+  if (!ok) { set_err("complement must be alphabet_len bytes with complement[complement[c]] == c for every letter"); return -1; }
+  return 0;
+}
+
 int upload_arena(int device, const uint8_t* arena, uint64_t arena_bytes, DeviceBuffer& d_arena) {
   CHECK(hipSetDevice(device));
   CHECK(d_arena.ensure((size_t)arena_bytes + 64));
@@ -725,38 +880,50 @@ int upload_arena(int device, const uint8_t* arena, uint64_t arena_bytes, DeviceB
   return 0;
 }
 
-}  // namespace
+// the complement table on the device (36 bytes, zero padded)
+int upload_complement(const uint8_t* comp, int L, DeviceBuffer& d_comp) {
+  uint8_t padded[36] = {0};
+  memcpy(padded, comp, (size_t)L);
+  CHECK(d_comp.ensure(sizeof padded));
+  CHECK(hipMemcpy(d_comp.p, padded, sizeof padded, hipMemcpyHostToDevice));
+  return 0;
+}
 
-extern "C" {
-
-int pw_overlap_all_pairs(int device, const uint8_t* arena, uint64_t arena_bytes, const uint64_t* read_off, const int32_t* read_len,
-                         int64_t n_reads, int alphabet_len, int wordlen, double len_coeff, double radius_coeff, double word_p_null,
-                         int shard_rank, int shard_world, int64_t max_pairs, int32_t* pair_a, int32_t* pair_b, pw_overlap_band* out,
-                         int64_t* n_out) {
+// both all-pairs entry points; stranded: pair_strand is required and the strand selection and the complement are checked
+// first (the complement only where the selection needs it), then everything in check_args' order
+int all_pairs(int device, const uint8_t* arena, uint64_t arena_bytes, const uint64_t* read_off, const int32_t* read_len,
+              int64_t n_reads, int alphabet_len, int wordlen, double len_coeff, double radius_coeff, double word_p_null,
+              bool stranded, const uint8_t* complement, int strands, int shard_rank, int shard_world, int64_t max_pairs,
+              int32_t* pair_a, int32_t* pair_b, uint8_t* pair_strand, pw_overlap_band* out, int64_t* n_out) {
+  if (stranded) {
+    if (strands < PW_STRAND_PLUS || strands > PW_STRAND_BOTH) { set_err("strands must be 1 (+), 2 (-) or 3 (both)"); return -1; }
+    if (strands != PW_STRAND_PLUS && check_complement(complement, alphabet_len) != 0) return -1;
+  }
   int kbits = 0;
-  if (check_args(alphabet_len, wordlen, n_reads < 0 || n_reads >= (1ll << 31) || !n_out || (n_reads && (!read_off || !read_len)),
+  if (check_args(alphabet_len, wordlen,
+                 n_reads < 0 || n_reads >= (1ll << 31) || !n_out || (n_reads && (!read_off || !read_len)) || (stranded && !pair_strand),
                  len_coeff, radius_coeff, word_p_null, shard_world < 1 || shard_rank < 0 || shard_rank >= shard_world, n_reads,
                  [&](int64_t r) { return read_len[r] < 0 || read_off[r] + (uint64_t)read_len[r] > arena_bytes; },
                  arena, arena_bytes, &kbits) != 0)
     return -1;
   g_ms = 0.0; *n_out = 0;
   if (n_reads < 2) return 0;
-  DeviceBuffer d_arena;
+  DeviceBuffer d_arena, d_comp;
   if (upload_arena(device, arena, arena_bytes, d_arena) != 0) return -1;
+  if (strands != PW_STRAND_PLUS && upload_complement(complement, alphabet_len, d_comp) != 0) return -1;
   float ms = 0.f;
   const int rc = run_all_pairs((const uint8_t*)d_arena.p, read_off, read_len, n_reads, alphabet_len, wordlen, kbits,
                                BandConst{len_coeff, radius_coeff, word_p_null}, shard_rank, shard_world, max_pairs, pair_a, pair_b, out,
-                               n_out, &ms);
+                               n_out, &ms, strands, (const uint8_t*)d_comp.p, pair_strand);
+  if (rc == 0 && stranded && strands == PW_STRAND_PLUS) memset(pair_strand, 0, (size_t)*n_out);
   g_ms = (double)ms;
   return rc;
 }
 
-const char* pw_overlap_last_error(void) { return g_err.c_str(); }
-double pw_overlap_last_ms(void) { return g_ms; }
-
-int pw_overlap_bands(int device, const uint8_t* arena, uint64_t arena_bytes, const pw_read_pair* pairs, int64_t n_pairs,
-                     int alphabet_len, int wordlen, double len_coeff, double radius_coeff, double word_p_null,
-                     pw_overlap_band* out) {
+// both pair-list entry points (strand == nullptr: every T as given, the complement is not read)
+int bands(int device, const uint8_t* arena, uint64_t arena_bytes, const pw_read_pair* pairs, int64_t n_pairs, int alphabet_len,
+          int wordlen, double len_coeff, double radius_coeff, double word_p_null, const uint8_t* complement, const uint8_t* strand,
+          pw_overlap_band* out) {
   static_assert(sizeof(pw_overlap_band) == 64, "pw_overlap_band is 64 bytes");
   int kbits = 0;
   if (check_args(alphabet_len, wordlen, n_pairs < 0 || (n_pairs && (!pairs || !out)), len_coeff, radius_coeff, word_p_null, false,
@@ -767,8 +934,9 @@ int pw_overlap_bands(int device, const uint8_t* arena, uint64_t arena_bytes, con
     return -1;
   g_ms = 0.0;
   if (n_pairs == 0) return 0;
-  DeviceBuffer d_arena;
+  DeviceBuffer d_arena, d_comp;
   if (upload_arena(device, arena, arena_bytes, d_arena) != 0) return -1;
+  if (strand && upload_complement(complement, alphabet_len, d_comp) != 0) return -1;
   DeviceEvent ev0, ev1;
   CHECK(ev0.create()); CHECK(ev1.create());
   // chunks: at most 2^31 histogram entries, 2^31 k-mers per side and pair ids that fit beside the k-mer
@@ -785,11 +953,120 @@ int pw_overlap_bands(int device, const uint8_t* arena, uint64_t arena_bytes, con
       hb += h; cs += (uint64_t)pairs[p1].s_len; ct += (uint64_t)pairs[p1].t_len; p1++;
     }
     rc = run_chunk((const uint8_t*)d_arena.p, pairs + p0, p1 - p0, alphabet_len, wordlen, kbits,
-                   BandConst{len_coeff, radius_coeff, word_p_null}, out + p0, ev0.e, ev1.e, &ms);
+                   BandConst{len_coeff, radius_coeff, word_p_null}, out + p0, ev0.e, ev1.e, &ms, strand ? strand + p0 : nullptr,
+                   (const uint8_t*)d_comp.p);
     p0 = p1;
   }
   g_ms = (double)ms;
   return rc;
+}
+
+// rc frames: one thread per letter
+__global__ __launch_bounds__(256) void k_revcomp_frames(uint8_t* __restrict__ arena, const uint64_t* __restrict__ src,
+                                                        const uint64_t* __restrict__ dst, const uint64_t* __restrict__ start,
+                                                        int64_t n, int64_t total, const uint8_t* __restrict__ comp, int L) {
+  __shared__ uint8_t s_comp[36];
+  load_complement(comp, L, s_comp);
+  const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (g >= total) return;
+  const int64_t f = upper_bound_dev<uint64_t>(start, n + 1, (uint64_t)g) - 1;
+  const uint64_t q = (uint64_t)g - start[f], len = start[f + 1] - start[f];
+  arena[dst[f] + q] = s_comp[arena[src[f] + (len - 1 - q)]];
+}
+
+}  // namespace
+
+extern "C" {
+
+int pw_overlap_all_pairs(int device, const uint8_t* arena, uint64_t arena_bytes, const uint64_t* read_off, const int32_t* read_len,
+                         int64_t n_reads, int alphabet_len, int wordlen, double len_coeff, double radius_coeff, double word_p_null,
+                         int shard_rank, int shard_world, int64_t max_pairs, int32_t* pair_a, int32_t* pair_b, pw_overlap_band* out,
+                         int64_t* n_out) {
+  return all_pairs(device, arena, arena_bytes, read_off, read_len, n_reads, alphabet_len, wordlen, len_coeff, radius_coeff, word_p_null,
+                   false, nullptr, PW_STRAND_PLUS, shard_rank, shard_world, max_pairs, pair_a, pair_b, nullptr, out, n_out);
+}
+
+int pw_overlap_all_pairs_stranded(int device, const uint8_t* arena, uint64_t arena_bytes, const uint64_t* read_off,
+                                  const int32_t* read_len, int64_t n_reads, int alphabet_len, int wordlen, double len_coeff,
+                                  double radius_coeff, double word_p_null, const uint8_t* complement, int strands, int shard_rank,
+                                  int shard_world, int64_t max_pairs, int32_t* pair_a, int32_t* pair_b, uint8_t* pair_strand,
+                                  pw_overlap_band* out, int64_t* n_out) {
+  return all_pairs(device, arena, arena_bytes, read_off, read_len, n_reads, alphabet_len, wordlen, len_coeff, radius_coeff, word_p_null,
+                   true, complement, strands, shard_rank, shard_world, max_pairs, pair_a, pair_b, pair_strand, out, n_out);
+}
+
+void* pw_overlap_arena_upload(int device, const uint8_t* host_arena, uint64_t bytes, uint64_t total_bytes, int64_t n_frames,
+                              const uint64_t* src_off, const uint64_t* dst_off, const int32_t* len, const uint8_t* complement,
+                              int alphabet_len) {
+  auto refuse = [](const char* m) -> void* { set_err(m); return nullptr; };
+  if (alphabet_len < 1 || alphabet_len > 36) return refuse("alphabet_len 1..36");
+  if (check_complement(complement, alphabet_len) != 0) return nullptr;
+  if (n_frames < 0 || total_bytes < bytes || (bytes && !host_arena) || (n_frames && (!src_off || !dst_off || !len))) return refuse("bad arguments");
+  std::vector<uint64_t> start((size_t)n_frames + 1);
+  uint64_t total = 0, floor = bytes;                   // frames ascending, disjoint, behind the uploaded letters
+  for (int64_t f = 0; f < n_frames; f++) {
+    if (len[f] < 0 || src_off[f] + (uint64_t)len[f] > bytes) return refuse("a read lies outside the arena");
+    if (dst_off[f] % 4 != 0) return refuse("frames must start on a 4-byte boundary of the arena");
+    if (dst_off[f] < floor || dst_off[f] + (uint64_t)len[f] > total_bytes)
+      return refuse("reverse-complement frames must ascend without overlap between the uploaded letters and total_bytes");
+    for (int32_t i = 0; i < len[f]; i++)
+      if (host_arena[src_off[f] + (uint64_t)i] >= alphabet_len) return refuse("letter outside the alphabet");
+    floor = dst_off[f] + (uint64_t)len[f];
+    start[(size_t)f] = total; total += (uint64_t)len[f];
+  }
+  start[(size_t)n_frames] = total;
+  auto run = [&](void* p) -> int {
+    CHECK(hipMemset((uint8_t*)p + bytes, 0, (size_t)(total_bytes - bytes) + 16));
+    if (bytes) CHECK(hipMemcpy(p, host_arena, (size_t)bytes, hipMemcpyHostToDevice));
+    if (total == 0) return 0;
+    DeviceBuffer dsrc, ddst, dstart, d_comp;
+    const size_t nb = 8 * (size_t)n_frames;
+    CHECK(dsrc.ensure(nb)); CHECK(ddst.ensure(nb)); CHECK(dstart.ensure(nb + 8));
+    CHECK(hipMemcpy(dsrc.p, src_off, nb, hipMemcpyHostToDevice));
+    CHECK(hipMemcpy(ddst.p, dst_off, nb, hipMemcpyHostToDevice));
+    CHECK(hipMemcpy(dstart.p, start.data(), nb + 8, hipMemcpyHostToDevice));
+    if (upload_complement(complement, alphabet_len, d_comp) != 0) return -1;
+    hipLaunchKernelGGL(k_revcomp_frames, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, nullptr, (uint8_t*)p, (const uint64_t*)dsrc.p,
+                       (const uint64_t*)ddst.p, (const uint64_t*)dstart.p, n_frames, (int64_t)total, (const uint8_t*)d_comp.p, alphabet_len);
+    CHECK(hipGetLastError());
+    CHECK(hipDeviceSynchronize());
+    return 0;
+  };
+  void* p = nullptr;
+  if (hipSetDevice(device) != hipSuccess || hipMalloc(&p, (size_t)total_bytes + 16) != hipSuccess) {
+    (void)hipGetLastError();
+    return refuse("pw_overlap_arena_upload: allocation failed");
+  }
+  if (run(p) != 0) { (void)hipFree(p); return nullptr; }
+  return p;
+}
+
+int pw_overlap_arena_read(int device, const void* dev_arena, uint64_t off, uint64_t bytes, uint8_t* host_out) {
+  if (!dev_arena || (bytes && !host_out)) { set_err("bad arguments"); return -1; }
+  CHECK(hipSetDevice(device));
+  if (bytes) CHECK(hipMemcpy(host_out, (const uint8_t*)dev_arena + off, (size_t)bytes, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+const char* pw_overlap_last_error(void) { return g_err.c_str(); }
+double pw_overlap_last_ms(void) { return g_ms; }
+
+int pw_overlap_bands(int device, const uint8_t* arena, uint64_t arena_bytes, const pw_read_pair* pairs, int64_t n_pairs,
+                     int alphabet_len, int wordlen, double len_coeff, double radius_coeff, double word_p_null,
+                     pw_overlap_band* out) {
+  return bands(device, arena, arena_bytes, pairs, n_pairs, alphabet_len, wordlen, len_coeff, radius_coeff, word_p_null, nullptr, nullptr,
+               out);
+}
+
+int pw_overlap_bands_stranded(int device, const uint8_t* arena, uint64_t arena_bytes, const pw_read_pair* pairs, int64_t n_pairs,
+                              int alphabet_len, int wordlen, double len_coeff, double radius_coeff, double word_p_null,
+                              const uint8_t* complement, const uint8_t* strand, pw_overlap_band* out) {
+  if (strand) {
+    if (check_complement(complement, alphabet_len) != 0) return -1;
+    for (int64_t p = 0; p < n_pairs; p++) if (strand[p] > 1) { set_err("strand flags must be 0 (+) or 1 (-)"); return -1; }
+  }
+  return bands(device, arena, arena_bytes, pairs, n_pairs, alphabet_len, wordlen, len_coeff, radius_coeff, word_p_null, complement, strand,
+               out);
 }
 
 }  // extern "C"

@@ -9,6 +9,12 @@ Pairs for which more than one diagonal could reach the same estimated match prob
 answer depends on the order of its seeds table) are re-scored by the single-pair path, which reproduces that order.
 One documented divergence: two reads with IDENTICAL content are scored here as two different sequences, whereas the
 reference turns such a pair into a self comparison (``seeds.py:33``) and ignores its main diagonal.
+
+Both strands: reads come from either strand of the molecule, so every entry point takes strands.  A minus-strand pair
+``(a, b, '-')`` is the pair ``S = reads[a]``, ``T = rc(reads[b])``; diagonals, bands, start indices and transcripts are
+in the frame of that ``T`` (position ``j'`` of ``T`` is letter ``len(b) - 1 - j'`` of ``reads[b]``, complemented) and
+equal what the forward code returns for ``(a, rc(b))`` with ``rc(b)`` materialised.  :func:`minus_to_forward` maps a
+result back to forward coordinates of ``reads[b]``.  A read is never paired with its own reverse complement.
 """
 import ctypes as C
 
@@ -18,7 +24,7 @@ from scipy.special import erfcinv
 from . import _pwlib as W
 from .batch import BatchAligner
 from .blot import H1_moments, WordBlotOverlap
-from .sequence import Alphabet, Sequence
+from .sequence import Alphabet, Sequence, check_complement, complement_table, reverse_complement
 
 BAND_DTYPE = np.dtype([('n_seeds', '<i8'), ('w_best', '<f8'), ('d_best', '<i4'), ('n_best', '<i4'),
                        ('r_best', '<i4'), ('len_best', '<i4'), ('band_best', '<i4'), ('tie', '<i4'),
@@ -41,10 +47,71 @@ def _same(a, b):
     return len(a) == len(b) and bool((a == b).all())
 
 
-def raw_bands(reads, pairs, wordlen, alphabet_len, g_max, sensitivity, device=0):
+_STRAND_SEL = {'+': W.PW_STRAND_PLUS, '-': W.PW_STRAND_MINUS, 'both': W.PW_STRAND_BOTH}
+
+
+def _strand_flags(strands, n):
+    """A per-pair strand list (``'+'`` / ``'-'``, or 0 / 1) as a uint8 array of 0 (+) and 1 (-); None stays None."""
+    if strands is None:
+        return None
+    flags = np.zeros(n, np.uint8)
+    strands = list(strands)
+    if len(strands) != n:
+        raise ValueError('one strand per pair: %d strands for %d pairs' % (len(strands), n))
+    for q, st in enumerate(strands):
+        if isinstance(st, str) and st in ('+', '-'):
+            flags[q] = st == '-'
+        elif not isinstance(st, str) and st in (0, 1):
+            flags[q] = st
+        else:
+            raise ValueError("a strand is '+' or '-' (or 0 / 1), not %r" % (st,))
+    return flags
+
+
+def _complement(complement, alphabet_len, alphabet=None):
+    """The complement table of a call: a table of ``alphabet_len`` letter indices or, with an :class:`Alphabet`, the
+    ``mappings`` of ``Alphabet.transform``."""
+    if complement is None:
+        raise ValueError("minus-strand pairs need a complement, e.g. complement_table(Alphabet('ACGT'), [('A', 'T'), ('C', 'G')])")
+    if alphabet is not None and (isinstance(complement, dict) or
+                                 (isinstance(complement, list) and complement and isinstance(complement[0], (tuple, list)))):
+        return complement_table(alphabet, complement)
+    return check_complement(complement, alphabet_len)
+
+
+def minus_to_forward(mutant_start, transcript, mutant_len):
+    """An alignment of a minus-strand pair in forward coordinates of ``reads[b]``: the transcript covers positions
+    ``[mutant_start, mutant_end)`` of ``T = rc(reads[b])`` (``M``, ``S`` and ``I`` consume a letter of ``T``), which are the
+    letters ``[len(b) - mutant_end, len(b) - mutant_start)`` of ``reads[b]``, read backwards and complemented.  Returns
+    that half-open forward interval ``(start, end)``."""
+    tx = transcript.encode('ascii') if isinstance(transcript, str) else bytes(transcript)
+    mutant_end = mutant_start + sum(tx.count(op) for op in b'MSI')
+    assert 0 <= mutant_start <= mutant_end <= mutant_len
+    return mutant_len - mutant_end, mutant_len - mutant_start
+
+
+def reverse_strand_keys(read, wordlen, alphabet_len, complement):
+    """Host restatement of the device's reverse-strand encoder: the k-mer keys of ``rc(read)`` at every position ``j'``,
+    computed from the FORWARD letters -- key(j') = sum over t of complement[read[len - 1 - j' - t]] * L^(k - 1 - t) -- without
+    materialising ``rc(read)``.  It is the forward key of the materialised reverse complement at ``j'``, and the reverse
+    complement (digits reversed and complemented) of the forward key of ``read`` at ``len - k - j'``."""
+    read = np.asarray(read, np.int64)
+    comp = check_complement(complement, alphabet_len).astype(np.uint64)
+    n = len(read) - wordlen + 1
+    if n <= 0:
+        return np.zeros(0, np.uint64)
+    idx = (len(read) - 1 - np.arange(n))[:, None] - np.arange(wordlen)[None, :]
+    weights = np.uint64(alphabet_len) ** np.arange(wordlen - 1, -1, -1, dtype=np.uint64)
+    return (comp[read[idx]] * weights[None, :]).sum(axis=1, dtype=np.uint64)
+
+
+def raw_bands(reads, pairs, wordlen, alphabet_len, g_max, sensitivity, device=0, strands=None, complement=None):
     """The device records (BAND_DTYPE) for ``pairs`` = list of (i, j) indices into ``reads``; also returns the
-    device time in ms."""
+    device time in ms.  ``strands``: one ``'+'`` / ``'-'`` per pair (default: all ``'+'``); a minus pair is scored against
+    the reverse complement of ``reads[j]`` under the table ``complement``."""
     assert 0 < g_max < 1 and 0 < sensitivity < 1
+    flags = _strand_flags(strands, len(pairs))
+    comp = _complement(complement, alphabet_len) if flags is not None and flags.any() else None
     lib = W.load()
     arena, offs, arrs = _arena(reads)
     n = len(pairs)
@@ -57,10 +124,17 @@ def raw_bands(reads, pairs, wordlen, alphabet_len, g_max, sensitivity, device=0)
     radius_coeff = erfcinv(1. - sensitivity) * np.sqrt(2 * g_max)
     word_p_null = (1. / alphabet_len) ** wordlen
     arena_c = np.ascontiguousarray(arena)
-    rc = lib.pw_overlap_bands(device, arena_c.ctypes.data, arena_c.size, rp, n, alphabet_len, wordlen,
-                              float(len_coeff), float(radius_coeff), float(word_p_null), out.ctypes.data)
+    if comp is None:
+        name = 'pw_overlap_bands'
+        rc = lib.pw_overlap_bands(device, arena_c.ctypes.data, arena_c.size, rp, n, alphabet_len, wordlen,
+                                  float(len_coeff), float(radius_coeff), float(word_p_null), out.ctypes.data)
+    else:
+        name = 'pw_overlap_bands_stranded'
+        rc = lib.pw_overlap_bands_stranded(device, arena_c.ctypes.data, arena_c.size, rp, n, alphabet_len, wordlen,
+                                           float(len_coeff), float(radius_coeff), float(word_p_null), comp.ctypes.data,
+                                           flags.ctypes.data, out.ctypes.data)
     if rc != 0:
-        raise RuntimeError('pw_overlap_bands failed: ' + (lib.pw_overlap_last_error() or b'').decode())
+        raise RuntimeError(name + ' failed: ' + (lib.pw_overlap_last_error() or b'').decode())
     return out[:n], lib.pw_overlap_last_ms()
 
 
@@ -78,10 +152,16 @@ def _result(d, rad, L, n_in_band, word_p, alphabet_len, wordlen):
     return res
 
 
-def _records_to_results(reads, pairs, recs, wordlen, alphabet, g_max, sensitivity, device):
-    """Device records -> the reference's dicts (shared by the pair-list and the all-pairs paths)."""
+def _records_to_results(reads, pairs, recs, wordlen, alphabet, g_max, sensitivity, device, flags=None, comp=None):
+    """Device records -> the reference's dicts (shared by the pair-list and the all-pairs paths).  ``flags``: 0 / 1 per pair
+    (None: all forward); the T of a minus pair is the reverse complement of its read."""
     L = len(alphabet)
     out, n_fallback = [], 0
+
+    def t_of(q):
+        T = reads[pairs[q][1]]
+        return reverse_complement(T, comp) if flags is not None and flags[q] else T
+
     for q, r in enumerate(recs):
         if r['n_seeds'] == 0:
             out.append(None)
@@ -89,10 +169,10 @@ def _records_to_results(reads, pairs, recs, wordlen, alphabet, g_max, sensitivit
             # every p is 0: max() keeps the first row of the table (blot.py:569)
             word_p = (r['n_first'] + 1 - (2 * int(r['r_first']) * int(r['len_first'])) * ((1. / L) ** wordlen)) / r['len_first']
             out.append(_result(int(r['d_first']), int(r['r_first']), int(r['len_first']), int(r['band_first']), word_p, L, wordlen))
-        elif r['tie'] > 1 and not _same(reads[pairs[q][0]], reads[pairs[q][1]]):
-            i, j = pairs[q]
+        elif r['tie'] > 1 and not _same(reads[pairs[q][0]], t_of(q)):
+            i, T = pairs[q][0], t_of(q)
             S = reads[i] if isinstance(reads[i], Sequence) else Sequence(alphabet, tuple(int(c) for c in reads[i]))
-            T = reads[j] if isinstance(reads[j], Sequence) else Sequence(alphabet, tuple(int(c) for c in reads[j]))
+            T = T if isinstance(T, Sequence) else Sequence(alphabet, tuple(int(c) for c in T))
             wb = WordBlotOverlap(S, T, g_max=g_max, sensitivity=sensitivity, alphabet=alphabet, wordlen=wordlen, device=device)
             out.append(wb.highest_scoring_overlap_band())
             wb.close()
@@ -102,31 +182,60 @@ def _records_to_results(reads, pairs, recs, wordlen, alphabet, g_max, sensitivit
     return out, n_fallback
 
 
-def overlap_bands(reads, pairs, wordlen, alphabet, g_max, sensitivity, device=0, stats=None):
-    """``highest_scoring_overlap_band()`` of every pair ``(i, j)`` (``reads[i]`` as S, ``reads[j]`` as T)."""
+def overlap_bands(reads, pairs, wordlen, alphabet, g_max, sensitivity, device=0, stats=None, strands=None, complement=None):
+    """``highest_scoring_overlap_band()`` of every pair ``(i, j)`` (``reads[i]`` as S, ``reads[j]`` as T -- or, where
+    ``strands[q]`` is ``'-'``, the reverse complement of ``reads[j]`` as T).  ``complement``: a table or the ``mappings`` of
+    ``Alphabet.transform``, e.g. ``[('A', 'T'), ('C', 'G')]``."""
     assert isinstance(alphabet, Alphabet)
-    recs, ms = raw_bands(reads, pairs, wordlen, len(alphabet), g_max, sensitivity, device)
-    out, n_fallback = _records_to_results(reads, pairs, recs, wordlen, alphabet, g_max, sensitivity, device)
+    flags = _strand_flags(strands, len(pairs))
+    comp = _complement(complement, len(alphabet), alphabet) if flags is not None and flags.any() else None
+    recs, ms = raw_bands(reads, pairs, wordlen, len(alphabet), g_max, sensitivity, device, strands=flags, complement=comp)
+    out, n_fallback = _records_to_results(reads, pairs, recs, wordlen, alphabet, g_max, sensitivity, device, flags, comp)
     if stats is not None:
         stats.update(device_ms=ms, fallback_pairs=n_fallback, pairs=len(pairs))
     return out
 
 
-def raw_all_pairs(reads, wordlen, alphabet_len, g_max, sensitivity, device=0, max_pairs=None, rank=0, world=1):
+def raw_all_pairs(reads, wordlen, alphabet_len, g_max, sensitivity, device=0, max_pairs=None, rank=0, world=1, strands='+',
+                  complement=None, with_strand=None):
     """All pairs ``a < b`` of ``reads`` that share at least one seed, through ONE k-mer index over all reads:
     returns ``(pairs (n, 2) int32, records BAND_DTYPE, device ms)``.  With ``world > 1`` only the pairs whose smaller
-    read index is ``rank`` modulo ``world`` (one process per GPU, no data-path collective)."""
+    read index is ``rank`` modulo ``world`` (one process per GPU, no data-path collective).
+
+    ``strands``: ``'+'`` (read a against read b, the default), ``'-'`` (read a against the reverse complement of read b
+    under the table ``complement``) or ``'both'``.  With ``with_strand`` (default: whenever ``strands`` is not ``'+'``) the
+    call goes through ``pw_overlap_all_pairs_stranded`` and returns ``(pairs, strand (n,) uint8: 0 '+' / 1 '-', records,
+    device ms)``, in ascending ``(a, b, strand)`` order."""
     assert 0 < g_max < 1 and 0 < sensitivity < 1
+    if strands not in _STRAND_SEL:
+        raise ValueError("strands is '+', '-' or 'both', not %r" % (strands,))
+    if with_strand is None:
+        with_strand = strands != '+'
+    if strands != '+' and not with_strand:
+        raise ValueError('minus-strand pairs come with their strand column')
+    comp = _complement(complement, alphabet_len) if strands != '+' else None
     lib = W.load()
     arena, offs, arrs = _arena(reads)
     R = len(arrs)
-    cap = int(max_pairs) if max_pairs is not None else min(R * (R - 1) // 2, 1 << 26)
+    cap = int(max_pairs) if max_pairs is not None else min(R * (R - 1) // 2 * (2 if strands == 'both' else 1), 1 << 26)
     pa, pb = np.zeros(max(cap, 1), np.int32), np.zeros(max(cap, 1), np.int32)
     out = np.zeros(max(cap, 1), BAND_DTYPE)
     n_out = C.c_int64(0)
     roff = np.ascontiguousarray(offs[:-1].astype(np.uint64))
     rlen = np.ascontiguousarray(np.diff(offs).astype(np.int32))
     arena_c = np.ascontiguousarray(arena)
+    if with_strand:
+        ps = np.zeros(max(cap, 1), np.uint8)
+        rc = lib.pw_overlap_all_pairs_stranded(device, arena_c.ctypes.data, arena_c.size, roff.ctypes.data, rlen.ctypes.data, R,
+                                               alphabet_len, wordlen, float(2. / (2 - g_max)),
+                                               float(erfcinv(1. - sensitivity) * np.sqrt(2 * g_max)),
+                                               float((1. / alphabet_len) ** wordlen), None if comp is None else comp.ctypes.data,
+                                               _STRAND_SEL[strands], int(rank), int(world), cap, pa.ctypes.data, pb.ctypes.data,
+                                               ps.ctypes.data, out.ctypes.data, C.byref(n_out))
+        if rc != 0:
+            raise RuntimeError('pw_overlap_all_pairs_stranded failed: ' + (lib.pw_overlap_last_error() or b'').decode())
+        n = n_out.value
+        return np.stack([pa[:n], pb[:n]], axis=1), ps[:n], out[:n], lib.pw_overlap_last_ms()
     rc = lib.pw_overlap_all_pairs(device, arena_c.ctypes.data, arena_c.size, roff.ctypes.data, rlen.ctypes.data, R, alphabet_len,
                                   wordlen, float(2. / (2 - g_max)), float(erfcinv(1. - sensitivity) * np.sqrt(2 * g_max)),
                                   float((1. / alphabet_len) ** wordlen), int(rank), int(world), cap, pa.ctypes.data, pb.ctypes.data, out.ctypes.data,
@@ -137,27 +246,53 @@ def raw_all_pairs(reads, wordlen, alphabet_len, g_max, sensitivity, device=0, ma
     return np.stack([pa[:n], pb[:n]], axis=1), out[:n], lib.pw_overlap_last_ms()
 
 
-def overlap_all_pairs(reads, wordlen, alphabet, g_max, sensitivity, device=0, max_pairs=None, stats=None):
+def overlap_all_pairs(reads, wordlen, alphabet, g_max, sensitivity, device=0, max_pairs=None, stats=None, strands='+',
+                      complement=None):
     """The reference's all-pairs loop (``experiments/blot_overlaps.py:262-272``) in one device pass: returns a dict
     ``{(a, b): highest_scoring_overlap_band()}`` for the pairs ``a < b`` that share a seed; for every other pair the
-    reference's answer is None."""
+    reference's answer is None.  With ``strands='-'`` or ``'both'`` the keys are ``(a, b, '+' | '-')`` and a minus entry
+    is the reference's answer for ``reads[a]`` against the reverse complement of ``reads[b]`` (``complement``: a table or
+    the ``mappings`` of ``Alphabet.transform``)."""
     assert isinstance(alphabet, Alphabet)
-    pairs, recs, ms = raw_all_pairs(reads, wordlen, len(alphabet), g_max, sensitivity, device, max_pairs)
-    plist = [(int(a), int(b)) for a, b in pairs.tolist()]
-    res, n_fallback = _records_to_results(reads, plist, recs, wordlen, alphabet, g_max, sensitivity, device)
+    if strands == '+':
+        pairs, recs, ms = raw_all_pairs(reads, wordlen, len(alphabet), g_max, sensitivity, device, max_pairs)
+        plist = [(int(a), int(b)) for a, b in pairs.tolist()]
+        res, n_fallback = _records_to_results(reads, plist, recs, wordlen, alphabet, g_max, sensitivity, device)
+        keys = plist
+    else:
+        comp = _complement(complement, len(alphabet), alphabet)
+        pairs, flags, recs, ms = raw_all_pairs(reads, wordlen, len(alphabet), g_max, sensitivity, device, max_pairs, strands=strands,
+                                               complement=comp)
+        plist = [(int(a), int(b)) for a, b in pairs.tolist()]
+        res, n_fallback = _records_to_results(reads, plist, recs, wordlen, alphabet, g_max, sensitivity, device, flags, comp)
+        keys = [(a, b, '-' if f else '+') for (a, b), f in zip(plist, flags.tolist())]
     if stats is not None:
         stats.update(device_ms=ms, fallback_pairs=n_fallback, pairs=len(plist))
-    return dict(zip(plist, res))
+    return dict(zip(keys, res))
 
 
-def aligned_batches(arena, offs, lens, pidx, dr, alphabet_len, device=0, max_cells=2 * 10 ** 10, flags=0, **kw):
+def aligned_batches(arena, offs, lens, pidx, dr, alphabet_len, device=0, max_cells=2 * 10 ** 10, flags=0, strands=None,
+                    complement=None, **kw):
     """Banded overlap alignment of the read pairs ``pidx`` (read indices into the packed ``arena``, :func:`pack_reads`)
     with bands ``dr``, in batches of at most ``max_cells`` cells.  The reads go to the device ONCE (``DeviceArena``) and
     every batch refers to that copy; while one batch runs on the device the next one is planned on the host
     (``pw_batch_create`` is host work: band clamps, kernel geometry, descriptors).  Yields ``(start, stop, batch)`` with
-    the batch solved, traced back and synchronised; the batch is destroyed when the generator moves on."""
+    the batch solved, traced back and synchronised; the batch is destroyed when the generator moves on.
+
+    ``strands`` (one ``'+'`` / ``'-'`` per pair) and ``complement``: the mutant of a minus pair is the reverse complement of
+    its read.  The host letters still go up once; the device writes the reverse complement of every read some minus pair
+    needs behind them (``DeviceArena.with_reverse_complements``) and the batches refer to those frames as ordinary mutants."""
     from .batch import DeviceArena
     pidx = np.ascontiguousarray(pidx, np.int64).reshape(-1, 2)
+    sflags = _strand_flags(strands, len(pidx))
+    offs, lens = np.asarray(offs, np.int64), np.asarray(lens)
+    rc_reads = np.unique(pidx[sflags == 1, 1]) if sflags is not None and sflags.any() else None
+    if rc_reads is not None:
+        comp = _complement(complement, alphabet_len)
+        pidx = pidx.copy()
+        minus = sflags == 1
+        pidx[minus, 1] = len(offs) + np.searchsorted(rc_reads, pidx[minus, 1])       # the rc frames follow the reads
+        lens = np.concatenate([lens, lens[rc_reads]])
     dr = np.ascontiguousarray(dr, np.int64).reshape(-1, 2)
     cells = (dr[:, 1] - dr[:, 0] + 1) * np.minimum(lens[pidx[:, 0]], lens[pidx[:, 1]]).astype(np.int64)
     bounds, start = [], 0
@@ -168,10 +303,16 @@ def aligned_batches(arena, offs, lens, pidx, dr, alphabet_len, device=0, max_cel
         bounds.append((start, stop)); start = stop
 
     def create(lo, hi):
-        return BatchAligner.from_arena(arena, offs, lens, pidx[lo:hi], dr[lo:hi], device_arena=dev, alnmode=W.BANDED_MODE,
-                                       alntype=W.B_OVERLAP, alphabet_len=alphabet_len, device=device, flags=flags, **kw)
+        return BatchAligner.from_arena(arena, all_offs, lens, pidx[lo:hi], dr[lo:hi], device_arena=dev, alnmode=W.BANDED_MODE,
+                                       alntype=W.B_OVERLAP, alphabet_len=alphabet_len, device=device, flags=flags,
+                                       arena_bytes=dev.nbytes, **kw)
 
-    with DeviceArena(arena, device) as dev:
+    if rc_reads is None:
+        dev, all_offs = DeviceArena(arena, device), offs
+    else:
+        dev = DeviceArena.with_reverse_complements(arena, offs, lens[:len(offs)], rc_reads, comp, device)
+        all_offs = np.concatenate([offs, dev.rc_offsets])
+    with dev:
         cur = nxt = None
         try:
             nxt = create(*bounds[0]) if bounds else None
@@ -190,15 +331,19 @@ def aligned_batches(arena, offs, lens, pidx, dr, alphabet_len, device=0, max_cel
 
 
 def overlap_alignments(reads, pairs, bands, alphabet, p_min=0., device=0, max_cells=2 * 10 ** 10, want_transcripts=True,
-                       **aligner_kw):
+                       strands=None, complement=None, **aligner_kw):
     """Banded overlap alignment (``B_OVERLAP``) of every pair whose band has ``p >= p_min``; the ``diag_range`` is the
     band clamped to the table as ``Aligner`` requires (``pw.py:224-226``).  All reads are uploaded ONCE and the pairs
     refer to them (``BatchAligner.from_arena``); the pairs are solved in batches of at most ``max_cells`` cells
     (tie masks take 0.5-0.6 bytes per cell of HBM).  ``bands`` is a list aligned with ``pairs`` (dicts or None).
     Returns a list with one entry per pair: None, or dict(score, transcript, origin_start, mutant_start,
-    diag_range)."""
+    diag_range).  With ``strands`` (one ``'+'`` / ``'-'`` per pair; ``complement`` as in :func:`overlap_bands`) the mutant
+    of a minus pair is the reverse complement of ``reads[j]``, ``mutant_start`` and the transcript are in its frame
+    (:func:`minus_to_forward`), and every dict also reports its ``strand``."""
     from .batch import pack_reads
     arena, offs, lens = pack_reads(reads)
+    sflags = _strand_flags(strands, len(pairs))
+    comp = _complement(complement, len(alphabet), alphabet) if sflags is not None and sflags.any() else None
     sel, dr = [], []
     for q, ((i, j), band) in enumerate(zip(pairs, bands)):
         if band is None or band['p'] < p_min:
@@ -215,7 +360,9 @@ def overlap_alignments(reads, pairs, bands, alphabet, p_min=0., device=0, max_ce
     kw.update(aligner_kw)
     pidx = np.array([pairs[q] for q in sel], np.int64)
     dr = np.array(dr, np.int64)
-    for start, stop, b in aligned_batches(arena, offs, lens, pidx, dr, len(alphabet), device=device, max_cells=max_cells, **kw):
+    sub = None if sflags is None else sflags[sel]
+    for start, stop, b in aligned_batches(arena, offs, lens, pidx, dr, len(alphabet), device=device, max_cells=max_cells,
+                                          strands=sub, complement=comp, **kw):
         res = b.results()
         txs = b.transcripts(res) if want_transcripts else [None] * (stop - start)
         for k in range(stop - start):
@@ -223,26 +370,36 @@ def overlap_alignments(reads, pairs, bands, alphabet, p_min=0., device=0, max_ce
                 continue
             out[sel[start + k]] = dict(score=float(res['score'][k]), transcript=txs[k], origin_start=int(res['origin_idx'][k]),
                                        mutant_start=int(res['mutant_idx'][k]), diag_range=(int(dr[start + k, 0]), int(dr[start + k, 1])))
+            if sub is not None:
+                out[sel[start + k]]['strand'] = '-' if sub[start + k] else '+'
     return out
 
 
-def raw_bands_sharded(reads, pairs, wordlen, alphabet_len, g_max, sensitivity, rank, world, device=None, gather_device=None):
+def raw_bands_sharded(reads, pairs, wordlen, alphabet_len, g_max, sensitivity, rank, world, device=None, gather_device=None,
+                      strands=None, complement=None):
     """Config 4 across GPUs: pair q is scored by rank ``q mod world`` (no data-path collective), the 64-byte band
     records are gathered to rank 0 in pair order (``torch.distributed``: RCCL on GPUs).  Returns the full record
     array on rank 0, None elsewhere."""
     from .distributed import gather_struct, shard_indices
     mine = shard_indices(len(pairs), rank, world)
+    flags = _strand_flags(strands, len(pairs))
     recs, _ = raw_bands(reads, [pairs[q] for q in mine], wordlen, alphabet_len, g_max, sensitivity,
-                        device=rank if device is None else device)
+                        device=rank if device is None else device, strands=None if flags is None else flags[list(mine)],
+                        complement=complement)
     return gather_struct(recs, len(pairs), rank, world, device=gather_device)
 
 
-def raw_all_pairs_sharded(reads, wordlen, alphabet_len, g_max, sensitivity, rank, world, device=None, max_pairs=None):
+def raw_all_pairs_sharded(reads, wordlen, alphabet_len, g_max, sensitivity, rank, world, device=None, max_pairs=None, strands='+',
+                          complement=None):
     """Config 4 across GPUs: every rank indexes all reads (cheap) and joins / scores the pairs whose smaller read
     index is ``rank`` modulo ``world``; pair lists and 64-byte records are gathered to rank 0 (ragged byte gather over
-    ``torch.distributed``) and merged in ascending (a, b) order.  Returns ``(pairs, records)`` on rank 0, None elsewhere."""
+    ``torch.distributed``) and merged in ascending (a, b) order.  Returns ``(pairs, records)`` on rank 0, None elsewhere.
+    With ``strands`` other than ``'+'``: ``(pairs, strand, records)`` in ascending (a, b, strand) order."""
     import torch
     from .distributed import gather_bytes
+    if strands != '+':
+        return _raw_all_pairs_sharded_stranded(reads, wordlen, alphabet_len, g_max, sensitivity, rank, world, device, max_pairs,
+                                               strands, complement)
     pairs, recs, _ = raw_all_pairs(reads, wordlen, alphabet_len, g_max, sensitivity, device=rank if device is None else device,
                                    max_pairs=max_pairs, rank=rank, world=world)
     blob = np.concatenate([np.ascontiguousarray(pairs, np.int32).view(np.uint8).reshape(-1), recs.view(np.uint8).reshape(-1)])
@@ -258,3 +415,26 @@ def raw_all_pairs_sharded(reads, wordlen, alphabet_len, g_max, sensitivity, rank
     pairs, recs = np.concatenate(all_pairs), np.concatenate(all_recs)
     order = np.lexsort((pairs[:, 1], pairs[:, 0]))
     return pairs[order], recs[order]
+
+
+def _raw_all_pairs_sharded_stranded(reads, wordlen, alphabet_len, g_max, sensitivity, rank, world, device, max_pairs, strands,
+                                    complement):
+    """:func:`raw_all_pairs_sharded` with the strand column: the third int32 of every gathered pair."""
+    import torch
+    from .distributed import gather_bytes
+    pairs, flags, recs, _ = raw_all_pairs(reads, wordlen, alphabet_len, g_max, sensitivity, device=rank if device is None else device,
+                                          max_pairs=max_pairs, rank=rank, world=world, strands=strands, complement=complement)
+    triples = np.ascontiguousarray(np.concatenate([pairs, flags.astype(np.int32)[:, None]], axis=1), np.int32)
+    blob = np.concatenate([triples.view(np.uint8).reshape(-1), recs.view(np.uint8).reshape(-1)])
+    got = gather_bytes(torch.from_numpy(blob.copy()), rank, world)
+    if rank != 0:
+        return None
+    all_triples, all_recs = [], []
+    for t in got:
+        raw = t.cpu().numpy()
+        n = raw.size // (12 + BAND_DTYPE.itemsize)
+        all_triples.append(raw[:12 * n].view(np.int32).reshape(n, 3))
+        all_recs.append(raw[12 * n:].view(BAND_DTYPE))
+    triples, recs = np.concatenate(all_triples), np.concatenate(all_recs)
+    order = np.lexsort((triples[:, 2], triples[:, 1], triples[:, 0]))
+    return triples[order, :2], triples[order, 2].astype(np.uint8), recs[order]

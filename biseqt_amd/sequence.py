@@ -156,3 +156,41 @@ class Sequence(object):
         else:
             contents = self.alphabet.letter_to_idx(other)
         return Sequence(self.alphabet, self.contents + contents)
+
+
+def complement_table(alphabet, mappings):
+    """The complement of every letter as an array of ``len(alphabet)`` bytes, from the ``mappings`` argument
+    :meth:`Alphabet.transform` takes (``[('A', 'T'), ('C', 'G')]`` for ``'ACGT'``; unmapped letters are their own
+    complement).  The table must be a permutation that is its own inverse; anything else is refused."""
+    table = np.asarray(alphabet.transform(range(len(alphabet)), mappings=mappings).contents, np.uint8)
+    return check_complement(table, len(alphabet))
+
+
+def check_complement(table, alphabet_len):
+    """``table`` as a contiguous uint8 array after checking that it is an involution of ``alphabet_len`` letters."""
+    table = np.asarray(table)
+    if table.ndim != 1 or len(table) != alphabet_len:
+        raise ValueError('the complement table must hold one entry per letter (%d), not %s' % (alphabet_len, table.shape))
+    if table.dtype.kind not in 'iu' or (table < 0).any() or (table >= alphabet_len).any():
+        raise ValueError('the complement table must hold letter indices below %d' % alphabet_len)
+    table = np.ascontiguousarray(table, np.uint8)
+    if (table[table] != np.arange(alphabet_len)).any():
+        raise ValueError('the complement must be its own inverse: complement[complement[c]] == c for every letter')
+    return table
+
+
+def reverse_complement(seq, complement):
+    """The reverse complement of a :class:`Sequence` (returns a Sequence) or of an array of letter indices (returns a
+    uint8 array): letter ``j`` of the result is ``complement[seq[len - 1 - j]]``.  ``complement`` is a table
+    (:func:`complement_table`) or, for a Sequence, the ``mappings`` of :meth:`Alphabet.transform`."""
+    if isinstance(seq, Sequence):
+        if isinstance(complement, (dict, list)):
+            complement = complement_table(seq.alphabet, complement)
+        table = check_complement(complement, len(seq.alphabet))
+        return Sequence(seq.alphabet, table[seq.as_array(np.uint8)[::-1]])
+    arr = np.asarray(seq)
+    table = np.asarray(complement)
+    table = check_complement(table, len(table))
+    if arr.size and (arr.min() < 0 or arr.max() >= len(table)):
+        raise ValueError('letter outside the alphabet')
+    return np.ascontiguousarray(table[arr.astype(np.intp)[::-1]])

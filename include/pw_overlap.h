@@ -66,6 +66,48 @@ int pw_overlap_all_pairs(int device, const uint8_t* arena, uint64_t arena_bytes,
                          int64_t max_pairs, int32_t* pair_a, int32_t* pair_b, pw_overlap_band* out,
                          int64_t* n_out);
 
+/* ---- both strands ---------------------------------------------------------------------------------------------
+ * Reads come from both strands of the molecule.  A minus-strand pair (a, b, '-') is the pair S = reads[a],
+ * T = rc(reads[b]), the reverse complement of read b: position j' of T is letter len(b) - 1 - j' of reads[b],
+ * complemented.  Diagonals, bands, the *_first fields -- and downstream start indices, end cells and transcripts -- are
+ * all in the frame of that T; every record equals what the unstranded call returns for (a, rc(b)) with rc(b)
+ * materialised.  The k-mer at position j' of rc(b) is the reverse complement of the k-mer of b at len(b) - k - j', so
+ * the device computes the reverse-strand keys from the forward letters: rc(b) is never materialised for seeding.
+ * `complement` is a table of alphabet_len bytes, a permutation of the letters that is its own inverse
+ * (complement[complement[c]] == c); anything else is refused.
+ * Documented exclusion: a read is never paired with its own reverse complement (hairpins are not looked for). */
+#define PW_STRAND_PLUS 1
+#define PW_STRAND_MINUS 2
+#define PW_STRAND_BOTH 3
+
+/* pw_overlap_bands with one strand flag per pair (0: T = the read as given, 1: T = its reverse complement).  strand == NULL
+ * is pw_overlap_bands itself (the complement is then not read). */
+int pw_overlap_bands_stranded(int device, const uint8_t* arena, uint64_t arena_bytes, const pw_read_pair* pairs,
+                              int64_t n_pairs, int alphabet_len, int wordlen, double len_coeff, double radius_coeff,
+                              double word_p_null, const uint8_t* complement, const uint8_t* strand, pw_overlap_band* out);
+
+/* pw_overlap_all_pairs for the strands selected by `strands` (PW_STRAND_*): forward a x forward b and / or forward a x
+ * reverse b, for a < b -- half of what an index over the reads plus their reverse complements would join.  pair_strand
+ * receives 0 (+) or 1 (-) per listed pair; the order is ascending (a, b, strand).  PW_STRAND_PLUS runs the kernels of
+ * pw_overlap_all_pairs and needs no complement.  Otherwise a second index of the same size holds the reverse-strand
+ * k-mers: the limit of 2^32 k-mers applies per strand.  Sharding by a mod shard_world as above. */
+int pw_overlap_all_pairs_stranded(int device, const uint8_t* arena, uint64_t arena_bytes, const uint64_t* read_off,
+                                  const int32_t* read_len, int64_t n_reads, int alphabet_len, int wordlen,
+                                  double len_coeff, double radius_coeff, double word_p_null, const uint8_t* complement,
+                                  int strands, int shard_rank, int shard_world, int64_t max_pairs, int32_t* pair_a,
+                                  int32_t* pair_b, uint8_t* pair_strand, pw_overlap_band* out, int64_t* n_out);
+
+/* Reads for the alignment stage: a device arena of total_bytes (+ the slack the kernels read) whose first `bytes` are the
+ * host arena, uploaded once; behind them the device writes the reverse complement of n_frames reads: frame f =
+ * rc(arena[src_off[f], src_off[f] + len[f])) at dst_off[f].  The dst frames ascend without overlap inside
+ * [bytes, total_bytes) and start on 4-byte boundaries; the bytes between them are zero.  Batches created with
+ * PW_FLAG_SHARED_ARENA (pw_batch.h) refer to these frames as ordinary mutant frames.  Free with pw_arena_free.
+ * NULL on error.  pw_overlap_arena_read copies a piece of such an arena back to the host. */
+void* pw_overlap_arena_upload(int device, const uint8_t* host_arena, uint64_t bytes, uint64_t total_bytes,
+                              int64_t n_frames, const uint64_t* src_off, const uint64_t* dst_off, const int32_t* len,
+                              const uint8_t* complement, int alphabet_len);
+int pw_overlap_arena_read(int device, const void* dev_arena, uint64_t off, uint64_t bytes, uint8_t* host_out);
+
 double pw_overlap_last_ms(void);           /* device time of the last call (HIP events) */
 const char* pw_overlap_last_error(void);
 
