@@ -39,8 +39,8 @@ typedef struct {
   int32_t n_best;          /* n(d_best): neighbours of a seed on that diagonal */
   int32_t r_best, len_best;        /* r(d_best), L(d_best) */
   int32_t band_best;       /* seeds with d in [d_best - r_best, d_best + r_best] (seed_count of the band) */
-  int32_t tie;             /* occupied diagonals whose w is within 1e-9 relative of w_best, or >= 1 when
-                              w_best >= 1, or all of them when w_best <= 0 */
+  int32_t tie;             /* occupied diagonals whose w is within 1e-9 relative of min(w_best, 1), i.e.
+                              w >= c - |c| * 1e-9 with c = min(w_best, 1); all of them when w_best <= 0 */
   /* the first row of the reference's table order (k-mer asc, i asc, j asc): it wins when every p̂ is 0 */
   int32_t d_first, n_first, r_first, len_first, band_first;
   int32_t pad_;
