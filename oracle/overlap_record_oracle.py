@@ -30,7 +30,7 @@ def kmer_keys(x, wordlen, alphabet_len):
     n = len(x) - wordlen + 1
     if n <= 0:
         return np.zeros(0, np.int64)
-    assert alphabet_len ** wordlen < 2 ** 62 and (len(x) == 0 or (0 <= x.min() and x.max() < alphabet_len))
+    assert alphabet_len ** wordlen <= 2 ** 62 and (len(x) == 0 or (0 <= x.min() and x.max() < alphabet_len))
     keys = np.zeros(n, np.int64)
     for t in range(wordlen):
         keys = keys * alphabet_len + x[t:t + n]

@@ -1,5 +1,9 @@
 """Adversarial fuzz of the seeds / band selection / local similarity / batched overlap GPU paths against their
-oracles (test infrastructure).  python tests/micro/fuzz_seeds_gpu.py [seconds] [seed]"""
+oracles (test infrastructure).  python tests/micro/fuzz_seeds_gpu.py [seconds] [seed]
+
+Half of the cases draw a long word: k from 10 (4 with twelve letters) up to the longest with L^k < 2^62 -- 31, 30 and 17 for
+2, 4 and 12 letters -- so the joins run on 4-byte keys, on 8-byte keys and on every sort width in between; their sequences
+hold at least 2 k letters and shared blocks are mutated at no more than one event in 2 k letters, so that k-mers survive."""
 import os
 import sys
 import time
@@ -16,15 +20,24 @@ from biseqt_amd import synth                              # noqa: E402
 from oracle import blot_oracle as BO, seeds_oracle as SO  # noqa: E402
 
 
-def make(rng, L, maxlen):
+def longest_word(L):
+    k = 1
+    while k < 31 and L ** (k + 1) < 2 ** 62:
+        k += 1
+    return k
+
+
+def make(rng, L, maxlen, wide_k=0):
     n = int(np.exp(rng.uniform(np.log(4), np.log(maxlen))))
+    sub, indel = (.15, .05) if not wide_k else (.4 / wide_k, .1 / wide_k)
+    n = max(n, 2 * wide_k)
     kind = int(rng.integers(0, 6))
     s = rng.integers(0, L, n)
     if kind == 0:
         t = rng.integers(0, L, max(1, n + int(rng.integers(-n // 2, n // 2 + 1))))
     elif kind == 1:                                   # shared block at random offsets
         ln = int(rng.integers(1, n + 1)); a = int(rng.integers(0, n - ln + 1))
-        t = np.concatenate([rng.integers(0, L, int(rng.integers(0, n))), synth.mutate(rng, s[a:a + ln].astype(np.uint8), rng.uniform(0, .15), rng.uniform(0, .05), .3, L=L), rng.integers(0, L, int(rng.integers(0, n)))])
+        t = np.concatenate([rng.integers(0, L, int(rng.integers(0, n))), synth.mutate(rng, s[a:a + ln].astype(np.uint8), rng.uniform(0, sub), rng.uniform(0, indel), .3, L=L), rng.integers(0, L, int(rng.integers(0, n)))])
     elif kind == 2:                                   # suffix-prefix overlap
         k = int(rng.integers(0, n)); t = np.concatenate([s[k:], rng.integers(0, L, int(rng.integers(0, n + 1)))])
     elif kind == 3:                                   # tandem repeats
@@ -44,8 +57,12 @@ def run(budget, seed):
     t0 = time.time(); n = bad = 0
     while time.time() - t0 < budget:
         A = alphs[int(rng.integers(0, 3))]; L = len(A)
-        k = int(rng.integers(2, 10)) if L <= 4 else int(rng.integers(1, 4))
-        s, t = make(rng, L, [60, 400, 1500][int(rng.integers(0, 3))])
+        wide = bool(rng.integers(0, 2))
+        if wide:
+            k = int(rng.integers(10 if L <= 4 else 4, longest_word(L) + 1))
+        else:
+            k = int(rng.integers(2, 10)) if L <= 4 else int(rng.integers(1, 4))
+        s, t = make(rng, L, [60, 400, 1500][int(rng.integers(0, 3))], k if wide else 0)
         g_max, sens = float(rng.choice([.05, .1, .2, .3])), float(rng.choice([.9, .99, .999]))
         S, T = Sequence(A, tuple(s.tolist())), Sequence(A, tuple(t.tolist()))
         why = None

@@ -16,6 +16,7 @@ import functools
 import numpy as np
 
 from oracle import overlap_record_oracle as RO
+from tests import wide_words as WW
 
 Case = collections.namedtuple('Case', 'name reads wordlen alphabet_len g_max sensitivity complement klass call')
 
@@ -23,6 +24,8 @@ COMPLEMENT = {
     4: np.array([3, 2, 1, 0], np.uint8),
     2: np.array([1, 0], np.uint8),                                                   # the swap
     20: np.array([1, 0, 3, 2, 5, 4, 7, 6, 9, 8, 11, 10, 13, 12, 15, 14, 17, 16, 18, 19], np.uint8),   # fixed points 18, 19
+    3: np.array([2, 1, 0], np.uint8),                                                # fixed point 1
+    36: np.arange(35, -1, -1).astype(np.uint8),                                      # the reversal: 32 .. 35 <-> 3 .. 0
 }
 SEED_TARGETS = (1, 2, 63, 64, 65, 66, 2047, 2048, 2049, 2050)
 SMALL_MAX, MEDIUM_MAX, KEEP_MAX, LISTED_MAX = 64, 2048, 1024, 8192
@@ -204,8 +207,26 @@ def cases():
         return U, np.concatenate([U, U]), 6, 4, .2, .99
     S, T = _first_with(doubled, lambda o: o['tie'] >= 2 and 0 < o['w_best'] < 1, 0, 'two equal best diagonals')
     add('two_equal_best', S, T, 6, 4, .2, .99, seeds=(SMALL_MAX + 1, MEDIUM_MAX), tie=(2, None), w_positive=True, w_below_one=True)
+
+    # ---- long words: one group per key width, every case with the top and the zero word (tests/wide_words.py) ----
+    for (L, k), (g, sens) in WW.OVERLAP_RUNGS.items():
+        for x in WW.inputs(L, k).values():
+            add('wide_L%d_k%d_%s' % (L, k, x.name), x.S, x.T, k, L, g, sens, **_wide_class(x))
     assert len({c.name for c in out}) == len(out)
     return tuple(out)
+
+
+def _wide_class(x):
+    L, k = x.alphabet_len, x.wordlen
+    kl = dict(mod32=True) if L ** k > 2 ** 33 and x.kind in ('basic', 'sparse', 'empty') else {}
+    if x.kind != 'empty':
+        kl['key_bits'] = WW.KEY_BITS[(L, k)]
+    kl.update({'basic': dict(seeds=(SMALL_MAX + 1, MEDIUM_MAX), tie=(1, 1), w_positive=True, w_below_one=True),
+               'sparse': dict(seeds=(1, SMALL_MAX)),
+               'empty': dict(seeds=0),
+               'periodic': dict(seeds=(MEDIUM_MAX + 1, 5000), nocc=(20, KEEP_MAX), tie=(2, None), w_ge_one=True),
+               'doubled': dict(seeds=(SMALL_MAX + 1, MEDIUM_MAX), tie=(2, 2), w_positive=True, w_below_one=True)}[x.kind])
+    return kl
 
 
 def check_class(c):
@@ -236,6 +257,13 @@ def check_class(c):
         assert clamped(o, S, T) == (True, True) and o['w_best'] > 0
         if kl.pop('clamps') == 'best':                    # and the best diagonal is one of them
             assert o['d_best'] - o['r_best'] < -len(T) or o['d_best'] + o['r_best'] > len(S)
+    if 'key_bits' in kl:                                  # the largest key uses every bit the join sorts on
+        keys = np.concatenate([RO.kmer_keys(S, c.wordlen, c.alphabet_len), RO.kmer_keys(T, c.wordlen, c.alphabet_len)])
+        assert int(keys.max()).bit_length() == kl.pop('key_bits') == (c.alphabet_len ** c.wordlen - 1).bit_length()
+        assert int(keys.min()) == 0 and int(keys.max()) == c.alphabet_len ** c.wordlen - 1
+    if kl.pop('mod32', False):                            # a join on the low 32 bits of the keys counts other seeds
+        kS, kT = RO.kmer_keys(S, c.wordlen, c.alphabet_len), RO.kmer_keys(T, c.wordlen, c.alphabet_len)
+        assert WW.count_seeds(kS, kT) == o['n_seeds'] != WW.count_seeds(kS & 0xffffffff, kT & 0xffffffff)
     if kl.pop('w_zero', False):
         assert o['w_best'] == 0.0 and o['tie'] == o['nocc'] > 1
     if kl.pop('w_negative', False):

@@ -158,7 +158,7 @@ def test_all_pairs_shards_partition_and_match_the_oracle():
 # ---- end to end: the reference's dicts ------------------------------------------------------------------------------
 def _alphabet(L):
     from biseqt_amd.sequence import Alphabet
-    return Alphabet('ACGT' if L == 4 else 'ABCDEFGHIJKLMNOPQRST'[:L])
+    return Alphabet('ACGT' if L == 4 else 'ABCDEFGHIJKLMNOPQRSTUVWXYZ0123456789'[:L])
 
 
 def _same(a, b):
