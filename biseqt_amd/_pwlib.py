@@ -1,5 +1,5 @@
 """ctypes binding of biseqt_amd/pwlib/pwlib.so (the HIP library; C ABI in include/pwlib.h,
-include/pw_batch.h and the seed headers include/pw_seeds.h, pw_mseeds.h, pw_overlap.h).
+include/pw_batch.h and the seed headers include/pw_seeds.h, pw_mseeds.h, pw_qseeds.h, pw_overlap.h).
 
 The reference binds its C library with cffi in ABI mode (``biseqt/pw.py:45-69``); cffi is not
 available in this image, so the same structs are declared with ctypes -- field for field the layout of
@@ -137,6 +137,13 @@ MSEED_EXPORTS = ['pw_mseeds_create', 'pw_mseeds_build', 'pw_mseeds_num_seqs', 'p
                  'pw_mseeds_graph_fetch', 'pw_mseeds_graph_components', 'pw_mseeds_build_ms', 'pw_mseeds_graph_ms',
                  'pw_mseeds_components_ms', 'pw_mseeds_count_ms', 'pw_mseeds_algorithmic_bytes', 'pw_mseeds_destroy',
                  'pw_mseeds_last_error']
+
+# every symbol include/pw_qseeds.h declares
+QSEED_EXPORTS = ['pw_qseeds_create', 'pw_qseeds_build', 'pw_qseeds_num_queries', 'pw_qseeds_num_rows', 'pw_qseeds_rows_device',
+                 'pw_qseeds_rows', 'pw_qseeds_row_offsets', 'pw_qseeds_count_boxes', 'pw_qseeds_graph_build',
+                 'pw_qseeds_graph_counts', 'pw_qseeds_graph_fetch', 'pw_qseeds_graph_components', 'pw_qseeds_build_ms',
+                 'pw_qseeds_graph_ms', 'pw_qseeds_components_ms', 'pw_qseeds_count_ms', 'pw_qseeds_components_rounds',
+                 'pw_qseeds_destroy', 'pw_qseeds_last_error']
 
 # every symbol include/pw_overlap.h declares
 OVERLAP_EXPORTS = ['pw_overlap_bands', 'pw_overlap_all_pairs', 'pw_overlap_last_ms', 'pw_overlap_last_error',
@@ -329,6 +336,32 @@ def load():
     lib.pw_mseeds_destroy.argtypes = [C.c_void_p]
     lib.pw_mseeds_destroy.restype = None
     lib.pw_mseeds_last_error.restype = C.c_char_p
+    # include/pw_qseeds.h
+    lib.pw_qseeds_create.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_int]
+    lib.pw_qseeds_create.restype = C.c_void_p
+    lib.pw_qseeds_build.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
+                                    C.c_void_p]
+    lib.pw_qseeds_num_queries.argtypes = [C.c_void_p]
+    lib.pw_qseeds_num_queries.restype = C.c_int64
+    lib.pw_qseeds_num_rows.argtypes = [C.c_void_p]
+    lib.pw_qseeds_num_rows.restype = C.c_int64
+    lib.pw_qseeds_rows_device.argtypes = [C.c_void_p]
+    lib.pw_qseeds_rows_device.restype = C.c_void_p
+    lib.pw_qseeds_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+    lib.pw_qseeds_row_offsets.argtypes = [C.c_void_p, C.c_void_p]
+    lib.pw_qseeds_count_boxes.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 6
+    lib.pw_qseeds_graph_build.argtypes = [C.c_void_p, C.c_double, C.c_double]
+    lib.pw_qseeds_graph_build.restype = C.c_int64
+    lib.pw_qseeds_graph_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+    lib.pw_qseeds_graph_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.pw_qseeds_graph_components.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    for f in ('pw_qseeds_build_ms', 'pw_qseeds_graph_ms', 'pw_qseeds_components_ms', 'pw_qseeds_count_ms'):
+        getattr(lib, f).argtypes = [C.c_void_p]
+        getattr(lib, f).restype = C.c_double
+    lib.pw_qseeds_components_rounds.argtypes = [C.c_void_p]
+    lib.pw_qseeds_destroy.argtypes = [C.c_void_p]
+    lib.pw_qseeds_destroy.restype = None
+    lib.pw_qseeds_last_error.restype = C.c_char_p
     # include/pw_overlap.h
     lib.pw_overlap_bands.argtypes = [C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int64, C.c_int, C.c_int,
                                      C.c_double, C.c_double, C.c_double, C.c_void_p]

@@ -9,12 +9,15 @@ neighbouring seeds into segments (a depth-first search there) -- run on the GPU 
 ``highest_scoring_overlap_band()`` returns the ``d_band`` that the banded overlap aligner
 (``Aligner(..., alnmode=BANDED_MODE, alntype=B_OVERLAP, diag_range=d_band)``) is given.
 ``WordBlotMultiple`` / ``WordBlotMultipleFast`` (:726-1083) do the same local-similarity search for more than two
-sequences on the N-way seed table of pw_mseeds.hip (kernels K9).
+sequences on the N-way seed table of pw_mseeds.hip (kernels K9).  ``WordBlotLocalRef.similar_segments_many`` answers many
+queries against one reference out of one set of launches (kernels K10 of pw_qseeds.hip).
 """
 import numpy as np
 from scipy.special import erfcinv
 
-from .seeds import SeedIndex, SeedIndexMultiple
+from .batch import pack_reads
+from .seeds import SeedIndex, SeedIndexMultiple, _QIndex
+from .sequence import Sequence
 
 
 def find_peaks(xs, rs, threshold):
@@ -86,6 +89,97 @@ def H1_moments(alphabet_len, wordlen, area, seglen, p_match):
     return mu_H1, sd_H1
 
 
+def score_num_seeds(alphabet_len, wordlen, num_seeds, area, seglen, p_match):
+    """z-scores of an observed number of seeds in a region against H0 and H1 (``blot.py:238-271``)."""
+    if area == 0:
+        return float('-inf'), float('-inf')
+    mu_H0, sd_H0 = H0_moments(alphabet_len, wordlen, area)
+    mu_H1, sd_H1 = H1_moments(alphabet_len, wordlen, area, seglen, p_match)
+    return (num_seeds - mu_H0) / sd_H0, (num_seeds - mu_H1) / sd_H1
+
+
+def seed_ps_from_counts(n, d_radius, a_radius, alphabet_len, wordlen):
+    """Per seed the estimated match probability of the segment centred there (``blot.py:376-408``), from its number of
+    neighbours ``n`` (itself excluded).  Every seed's segment has the same dimensions: K' = a_radius,
+    A = 2 d_radius a_radius (``segment_dims`` of the bands ``(-d_radius, d_radius)``, ``(-a_radius, a_radius)``)."""
+    n = np.asarray(n).astype(np.int64)
+    Kp = (a_radius - -a_radius) // 2
+    area = (d_radius - -d_radius) * Kp
+    word_p_null = (1. / alphabet_len) ** wordlen
+    word_p = (n + 1 - area * word_p_null) / Kp
+    p = np.zeros(len(n))
+    pos = word_p > 0
+    p[pos] = np.exp(np.log(word_p[pos]) / wordlen)
+    return np.minimum(p, 1)
+
+
+def available_seeds_many(p, p_min, row_offsets, at_least_one=False):
+    """Which seeds of a query-batched table (rows of query q: ``row_offsets[q]:row_offsets[q + 1]``, in the order the
+    in-memory classes list their seeds) the segments grow from: those with ``p >= p_min``; with ``at_least_one``, a query
+    none of whose seeds passes contributes its first seed of highest p (``blot.py:432-436``) -- and a query without seeds
+    is refused as the per-query call refuses it."""
+    p, row_offsets = np.asarray(p, np.float64), np.asarray(row_offsets, np.int64)
+    per_q = np.diff(row_offsets)
+    assert len(p) == row_offsets[-1]
+    if at_least_one:
+        assert (per_q > 0).all(), 'no seeds found while at_least_one=True'
+    avail = p >= p_min
+    if at_least_one and len(p):
+        nq = len(per_q)
+        qid = np.repeat(np.arange(nq), per_q)
+        has = np.zeros(nq, bool)
+        has[qid[avail]] = True
+        p_max = np.maximum.reduceat(p, row_offsets[:-1])           # (every query has rows here)
+        cand = np.flatnonzero((p == p_max[qid]) & ~has[qid])
+        _, first = np.unique(qid[cand], return_index=True)          # np.argmax over the query's list: its first maximum
+        avail[cand[first]] = True
+    return avail
+
+
+def segments_from_arrays(counts, labels, rows, row_offsets, query_lens, ref_len, d_radius, a_radius, alphabet_len, wordlen,
+                         count_boxes):
+    """The host half of :meth:`WordBlotLocalRef.similar_segments_many` as a pure function of arrays: from the neighbour
+    counts of every seed, the component label of every seed (the smallest row index of its component, -1 for seeds that
+    take no part), the rows ``(q, d, a)`` in (q, j, i) order and their per-query offsets to one list of segment dicts per
+    query -- what ``WordBlot.similar_segments`` yields for that query, in its order (``blot.py:410-490``).
+
+    A component's bounding segment is clamped with ITS query's length, its averaged p sums in presentation order with the
+    starting seed counted twice (:449,455), and segments come in the order of their first seeds.  ``count_boxes(q, d_min,
+    d_max, a_min, a_max)`` returns the seed count of every segment's box (arrays in, array out): one call for all."""
+    rows = np.asarray(rows).reshape(-1, 3)
+    labels = np.asarray(labels)
+    row_offsets, query_lens = np.asarray(row_offsets, np.int64), np.asarray(query_lens, np.int64)
+    nq = len(query_lens)
+    assert len(row_offsets) == nq + 1 and len(rows) == len(labels) == len(counts) == row_offsets[-1]
+    out = [[] for _ in range(nq)]
+    idx = np.flatnonzero(labels >= 0)
+    if not len(idx):
+        return out
+    p = seed_ps_from_counts(counts, d_radius, a_radius, alphabet_len, wordlen)
+    order = idx[np.lexsort((idx, labels[idx]))]              # grouped by component, seed order inside; a label is its
+    lab = labels[order]                                       # component's first row, so the groups ascend by (q, first seed)
+    starts = np.flatnonzero(np.r_[True, lab[1:] != lab[:-1]])
+    d, a = rows[order, 1].astype(np.int64), rows[order, 2].astype(np.int64)
+    firsts = order[starts]                                    # the seed each search starts from
+    q = rows[firsts, 0].astype(np.int64)
+    lenS, lenT = ref_len, query_lens[q]
+    d_min = np.minimum(lenS, np.maximum(np.minimum.reduceat(d, starts) - d_radius, -lenT))
+    d_max = np.minimum(lenS, np.maximum(np.maximum.reduceat(d, starts) + d_radius, -lenT))
+    a_min = np.maximum(np.minimum.reduceat(a, starts) - a_radius, 0)
+    a_max = np.minimum(np.maximum.reduceat(a, starts) + a_radius, lenS + lenT)
+    cnt = np.diff(np.r_[starts, len(order)])
+    p_hat = (np.add.reduceat(p[order], starts) + p[firsts]) / (cnt + 1)      # ... and it is counted twice (:449,455)
+    n = np.asarray(count_boxes(q, d_min, d_max, a_min, a_max))
+    assert len(n) == len(starts)
+    for s, (qs, d0, d1, a0, a1, ns) in enumerate(zip(q.tolist(), d_min.tolist(), d_max.tolist(), a_min.tolist(),
+                                                     a_max.tolist(), n.tolist())):
+        K_hat = (a1 - a0) // 2                                # segment_dims (blot.py:283-303)
+        area_hat = (d1 - d0) * K_hat
+        out[qs].append({'segment': ((d0, d1), (a0, a1)), 'p': p_hat[s],
+                        'scores': score_num_seeds(alphabet_len, wordlen, ns, area_hat, K_hat, p_hat[s])})
+    return out
+
+
 class WordBlot(SeedIndex):
     """A similarity finder based on m-dependent CLT statistics (``blot.py:228-490``).
 
@@ -108,12 +202,7 @@ class WordBlot(SeedIndex):
 
     def score_num_seeds(self, **kw):
         """z-scores of an observed number of seeds in a region against H0 and H1 (``blot.py:238-271``)."""
-        num_seeds, area = kw['num_seeds'], kw['area']
-        if area == 0:
-            return float('-inf'), float('-inf')
-        mu_H0, sd_H0 = H0_moments(len(self.alphabet), self.wordlen, area)
-        mu_H1, sd_H1 = H1_moments(len(self.alphabet), self.wordlen, area, kw['seglen'], kw['p_match'])
-        return (num_seeds - mu_H0) / sd_H0, (num_seeds - mu_H1) / sd_H1
+        return score_num_seeds(len(self.alphabet), self.wordlen, kw['num_seeds'], kw['area'], kw['seglen'], kw['p_match'])
 
     def band_radius(self, K):
         return band_radius(K, self.g_max, self.sensitivity)
@@ -150,15 +239,8 @@ class WordBlot(SeedIndex):
         d_radius = int(np.ceil(self.band_radius(K)))
         a_radius = K
         self._graph(d_radius, a_radius)
-        n = self._idx.graph_counts().astype(np.int64)
-        # every seed's segment has the same dimensions: K' = a_radius, A = 2 d_radius a_radius
-        Kp, area = self.segment_dims(d_band=(-d_radius, d_radius), a_band=(-a_radius, a_radius))
-        word_p_null = (1. / len(self.alphabet)) ** self.wordlen
-        word_p = (n + 1 - area * word_p_null) / Kp
-        p = np.zeros(len(n))
-        pos = word_p > 0
-        p[pos] = np.exp(np.log(word_p[pos]) / self.wordlen)
-        return np.minimum(p, 1), d_radius, a_radius
+        p = seed_ps_from_counts(self._idx.graph_counts(), d_radius, a_radius, len(self.alphabet), self.wordlen)
+        return p, d_radius, a_radius
 
     def score_seeds(self, K):
         """One dict per seed, in the class's seed order: ``seed`` (d, a), ``neighs`` (indices of the seeds in its
@@ -320,6 +402,7 @@ class _RefMixin(object):
         self.g_max, self.sensitivity = kw['g_max'], kw['sensitivity']
         self.S, self.T = ref, None
         self._idx = None
+        self._qidx = None                           # the query-batched index (similar_segments_many)
 
     def _set_query(self, seq):
         if self.T is not None and self.T == seq and self._idx is not None:
@@ -386,6 +469,65 @@ class WordBlotLocalRef(_RefMixin, WordBlot):
     def similar_segments(self, seq, K_min, p_min, at_least_one=False):
         self._set_query(seq)
         return WordBlot.similar_segments(self, K_min, p_min, at_least_one=at_least_one)
+
+    def similar_segments_many(self, queries, K_min, p_min, at_least_one=False, arena=None):
+        """``[list(self.similar_segments(q, K_min, p_min, at_least_one)) for q in queries]`` -- same segments, order, p
+        and scores -- out of one set of kernel launches for all queries (kernels K10 of pw_qseeds.hip) instead of one index
+        per query: the reference sequence is encoded and sorted once per object, the queries' seeds come out in the order
+        the class lists them (the query scanned left to right), and the neighbour counts, the components and the segments'
+        seed counts of all queries take one launch each.
+
+        ``K_min`` and ``p_min`` are scalars for the whole call.  A query equal to the reference is a self comparison
+        (``blot.py:612``) and goes through the per-query path.  ``arena``, optional: ``(device_arena, offsets, lengths)``
+        of a :class:`biseqt_amd.batch.DeviceArena` that already holds the queries, in order, to be read in place."""
+        queries = list(queries)
+        assert all(isinstance(T, Sequence) and T.alphabet == self.alphabet for T in queries), \
+            'queries are Sequences over the index alphabet'
+        assert np.ndim(K_min) == 0 and np.ndim(p_min) == 0, 'K_min and p_min are scalars for the whole call'
+        assert K_min > 0, 'K_min must be positive'
+        batched = [k for k, T in enumerate(queries) if not T == self.S]
+        if at_least_one:                              # (a query shorter than a word has no seeds: known without the device)
+            assert all(len(queries[k]) >= self.wordlen for k in batched), 'no seeds found while at_least_one=True'
+        out = [None] * len(queries)
+        if batched:
+            if arena is None:
+                letters, offs, lens = pack_reads([queries[k] for k in batched])
+            else:
+                letters, offs, lens = arena
+                offs, lens = np.asarray(offs, np.int64), np.asarray(lens, np.int64)
+                assert len(offs) == len(lens) == len(queries) and lens.tolist() == [len(T) for T in queries]
+                offs, lens = offs[batched], lens[batched]
+            if self._qidx is None:
+                self._qidx = _QIndex(self.S, self.wordlen, self.alphabet, device=self._ref_kw.get('device', 0))
+            qi = self._qidx
+            qi.build(letters, offs, lens, self._ref_kw.get('max_rows', 0))
+            row_offsets = qi.row_offsets()
+            d_radius, a_radius = int(np.ceil(self.band_radius(K_min))), K_min
+            L = len(self.alphabet)
+            qi.graph_build(1. * a_radius / d_radius, a_radius)
+            counts = qi.graph_counts()
+            p = seed_ps_from_counts(counts, d_radius, a_radius, L, self.wordlen)
+            avail = available_seeds_many(p, p_min, row_offsets, at_least_one)
+            labels = qi.graph_components(avail) if avail.any() else np.full(len(p), -1, np.int32)
+            segs = segments_from_arrays(counts, labels, qi.rows(), row_offsets, lens, len(self.S), d_radius, a_radius, L,
+                                        self.wordlen, qi.count_boxes)
+            for k, s in zip(batched, segs):
+                out[k] = s
+        for k, T in enumerate(queries):
+            if out[k] is None:                        # the reference itself: mirrored points, the per-query path
+                out[k] = list(self.similar_segments(T, K_min, p_min, at_least_one=at_least_one))
+        return out
+
+    def batched_timings(self):
+        """Device milliseconds of the last :meth:`similar_segments_many`: build, graph, components, counts; hook rounds."""
+        return self._qidx.timings() if self._qidx is not None else None
+
+    def close(self):
+        if self._qidx is not None:
+            self._qidx.close()
+            self._qidx = None
+        if self._idx is not None:
+            self._idx.close()
 
 
 class WordBlotOverlapRef(_RefMixin, WordBlotOverlap):

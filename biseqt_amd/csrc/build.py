@@ -4,7 +4,7 @@
 
 One object per (score type, diagonals-per-lane) fill translation unit plus the traceback unit and the
 host API, compiled in parallel, linked into one shared object that exports the four drop-in functions
-of include/pwlib.h, the batch API of include/pw_batch.h and the seed APIs of include/pw_seeds.h, pw_mseeds.h and
+of include/pwlib.h, the batch API of include/pw_batch.h and the seed APIs of include/pw_seeds.h, pw_mseeds.h, pw_qseeds.h and
 pw_overlap.h.  The header is copied next to the library
 (biseqt_amd/pwlib/pwlib.h) the way the reference keeps biseqt/pwlib/pwlib.{h,so} side by side.
 """
@@ -107,6 +107,9 @@ def _jobs():
     obj = os.path.join(OBJ_DIR, 'pw_mseeds.o')
     jobs.append((obj, [HIPCC] + COMMON + ['-Wno-unused-parameter', '-c', os.path.join(HERE, 'pw_mseeds.hip'), '-o', obj],
                  [os.path.join(HERE, 'pw_mseeds.hip'), os.path.join(HERE, 'pw_seed_kernels.h'), os.path.join(ROOT, 'include', 'pw_mseeds.h')]))
+    obj = os.path.join(OBJ_DIR, 'pw_qseeds.o')
+    jobs.append((obj, [HIPCC] + COMMON + ['-Wno-unused-parameter', '-c', os.path.join(HERE, 'pw_qseeds.hip'), '-o', obj],
+                 [os.path.join(HERE, 'pw_qseeds.hip'), os.path.join(HERE, 'pw_seed_kernels.h'), os.path.join(ROOT, 'include', 'pw_qseeds.h')]))
     obj = os.path.join(OBJ_DIR, 'pw_overlap.o')
     jobs.append((obj, [HIPCC] + COMMON + ['-Wno-unused-parameter', '-c', os.path.join(HERE, 'pw_overlap.hip'), '-o', obj],
                  [os.path.join(HERE, 'pw_overlap.hip'), os.path.join(ROOT, 'include', 'pw_overlap.h')]))

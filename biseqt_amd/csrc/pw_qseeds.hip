@@ -1,0 +1,544 @@
+// pw_qseeds.hip -- exact-match k-mer seeds of many queries against one reference sequence on gfx950 (C ABI:
+// include/pw_qseeds.h).
+//
+// The reference's in-memory Word-Blot (blot.py:582-700) keeps the hits of ONE sequence per k-mer and scans each query
+// left to right; its experiments call it in a loop over hundreds of short queries.  Here the loop is gone: every kernel
+// below runs once over the positions, rows or boxes of ALL queries, so the number of launches and host round trips does
+// not depend on the number of queries.
+//   create            K5a k_encode + one stable radix sort of the reference's (k-mer, position), once per handle; for
+//                     small key spaces K5b's direct-address table start[key] (k_table_fill) as well
+//   K10a k_qmatch     one thread per query position in (q, j) order: the query it falls in (a windowed search over the
+//                     queries' first positions), its k-mer -- none when fewer than k letters are left IN THAT QUERY --
+//                     and that k-mer's run in the sorted reference (table, or two binary searches as K5b) -> rows it
+//                     contributes; a saturating exclusive scan -> row offsets
+//   K10b k_qexpand    one thread per row (K5c's windowed search): (q, d, a) = (q, i - j, i + j).  Threads are in (q, j)
+//                     order and a run's positions ascend (the sort is stable), so rows come out in (q, j, i) order by
+//                     construction -- the order the in-memory classes list their seeds in -- with no sort of the queries
+//   K10c k_qcount     seed counts of many (query, d band, a band) boxes: one wavefront per box walks the rows of the
+//                     box's own query only, a ballot per 64 rows, no atomics
+//   K10d k_qgraph_*   the neighbourhood graph: one radix sort of the points by (q, d, a); a query's points then occupy
+//                     the same index range as its rows.  One thread per point narrows that range to the admissible
+//                     diagonals (K7's test on the scaled axis) and binary-searches the a window of each; a count pass,
+//                     a scan, a fill pass (CSR)
+//       k_cc_*        connected components of the available rows (pw_seed_kernels.h); edges never cross queries
+// All of it is memory- and latency-bound: binary searches and row traffic, no arithmetic to speak of.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <string.h>
+#include <algorithm>
+#include <string>
+#include <vector>
+#include <rocprim/rocprim.hpp>
+
+#include "../../include/pw_qseeds.h"
+#include "pw_hip_host.h"
+#include "pw_seed_kernels.h"
+
+namespace {
+
+thread_local std::string g_err;
+void set_err(const std::string& s) { g_err = s; }
+#define CHECK(call) PW_HIP_CHECK(set_err, call)
+
+struct SatAdd {
+  __host__ __device__ uint64_t operator()(uint64_t a, uint64_t b) const { const uint64_t s = a + b; return s < a ? ~0ull : s; }
+};
+
+// ---- K10a -----------------------------------------------------------------------------------------------
+// pstart[q] = number of positions of the queries before q (pstart[nq] = npos); position t belongs to the last query whose
+// pstart is <= t (empty queries share their successor's pstart and are never chosen).  The workgroup's window of queries
+// comes from two searches over all of pstart, then every thread searches inside it.
+template <typename K>
+__global__ __launch_bounds__(256) void k_qmatch(const uint8_t* __restrict__ arena, const int64_t* __restrict__ qoff,
+                                                const int32_t* __restrict__ qlen, const int64_t* __restrict__ pstart, int64_t nq,
+                                                int64_t npos, int k, int L, const K* __restrict__ rkeys, int64_t nkr,
+                                                const uint32_t* __restrict__ tab, uint32_t* __restrict__ qid,
+                                                uint32_t* __restrict__ lo_out, uint64_t* __restrict__ cnt, int* __restrict__ bad) {
+  __shared__ int64_t win[2];
+  const int64_t t0 = (int64_t)blockIdx.x * 256;
+  const int64_t tlast = (t0 + 256 < npos ? t0 + 256 : npos) - 1;
+  if (threadIdx.x == 0) win[0] = upper_bound_dev<int64_t>(pstart, nq + 1, t0) - 1;
+  if (threadIdx.x == 64) win[1] = upper_bound_dev<int64_t>(pstart, nq + 1, tlast) - 1;
+  __syncthreads();
+  const int64_t t = t0 + threadIdx.x;
+  if (t >= npos) return;
+  const int64_t q = win[0] + upper_bound_dev<int64_t>(pstart + win[0], win[1] - win[0] + 1, t) - 1;
+  const int64_t j = t - pstart[q];
+  const int64_t len = qlen[q];
+  qid[t] = (uint32_t)q;
+  uint64_t c = 0;
+  uint32_t lo32 = 0;
+  if (j + k <= len) {                             // fewer than k letters left in this query: no k-mer here
+    const uint8_t* __restrict__ s = arena + qoff[q] + j;
+    uint64_t v = 0;
+    bool ok = true;
+    for (int i = 0; i < k; i++) {
+      const uint32_t ch = s[i];
+      ok = ok && ch < (uint32_t)L;
+      v = v * (uint64_t)L + ch;
+    }
+    if (!ok) *bad = 1;
+    else {
+      const K key = (K)v;
+      int64_t lo, hi;
+      if (tab != nullptr) { lo = tab[v]; hi = tab[v + 1]; }
+      else { lo = lower_bound_dev<K>(rkeys, nkr, key); hi = lo + upper_bound_dev<K>(rkeys + lo, nkr - lo, key); }
+      lo32 = (uint32_t)lo;
+      c = (uint64_t)(hi - lo);
+    }
+  } else if (j < len) {                           // the tail of a query still holds letters: they are validated too
+    if (arena[qoff[q] + j] >= (uint32_t)L) *bad = 1;
+  }
+  lo_out[t] = lo32;
+  cnt[t] = c;
+}
+// scalar[0] = the row total (saturated), row_off[q] = first row of query q, row_off[nq] = total
+__global__ __launch_bounds__(256) void k_qoffsets(const uint64_t* __restrict__ off, const uint64_t* __restrict__ cnt, int64_t npos,
+                                                  const int64_t* __restrict__ pstart, int64_t nq,
+                                                  unsigned long long* __restrict__ scalar, uint64_t* __restrict__ row_off) {
+  const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (q > nq) return;
+  const uint64_t total = npos > 0 ? SatAdd()(off[npos - 1], cnt[npos - 1]) : 0ull;
+  if (q == 0) scalar[0] = total;
+  const int64_t p = pstart[q];
+  row_off[q] = p < npos ? off[p] : total;
+}
+
+// ---- K10b -----------------------------------------------------------------------------------------------
+// As K5c: kExpRows rows per workgroup, the workgroup's window of positions found by two searches over all offsets, then
+// ~10 cache-resident steps per row.
+constexpr int kExpRows = 2048;
+__global__ __launch_bounds__(256) void k_qexpand(const uint64_t* __restrict__ off, int64_t npos, int64_t nrows,
+                                                 const uint32_t* __restrict__ qid, const int64_t* __restrict__ pstart,
+                                                 const uint32_t* __restrict__ lo_in, const uint32_t* __restrict__ rpos,
+                                                 int32_t* __restrict__ rows) {
+  __shared__ int64_t win[2];
+  const int64_t o0 = (int64_t)blockIdx.x * kExpRows;
+  const int64_t olast = (o0 + kExpRows < nrows ? o0 + kExpRows : nrows) - 1;
+  if (threadIdx.x == 0) win[0] = upper_bound_dev<uint64_t>(off, npos, (uint64_t)o0) - 1;
+  if (threadIdx.x == 64) win[1] = upper_bound_dev<uint64_t>(off, npos, (uint64_t)olast) - 1;
+  __syncthreads();
+  const int64_t e0 = win[0], nwin = win[1] - win[0] + 1;
+#pragma unroll 1
+  for (int it = 0; it < kExpRows / 256; it++) {
+    const int64_t o = o0 + it * 256 + threadIdx.x;
+    if (o >= nrows) return;
+    const int64_t e = e0 + upper_bound_dev<uint64_t>(off + e0, nwin, (uint64_t)o) - 1;      // last position whose first row is <= o
+    const int64_t r = o - (int64_t)off[e];
+    const uint32_t q = qid[e];
+    const int32_t j = (int32_t)(e - pstart[q]);
+    const int32_t i = (int32_t)rpos[(int64_t)lo_in[e] + r];
+    rows[o * 3] = (int32_t)q; rows[o * 3 + 1] = i - j; rows[o * 3 + 2] = i + j;
+  }
+}
+
+// ---- K10c -----------------------------------------------------------------------------------------------
+// One wavefront per box: the rows of the box's query are contiguous, so nothing else is read.
+__global__ __launch_bounds__(256) void k_qcount(const int32_t* __restrict__ rows, const uint64_t* __restrict__ row_off, int64_t nq,
+                                                int64_t nboxes, const int32_t* __restrict__ bq, const int32_t* __restrict__ dmin,
+                                                const int32_t* __restrict__ dmax, const int32_t* __restrict__ amin,
+                                                const int32_t* __restrict__ amax, unsigned long long* __restrict__ counts) {
+  const int64_t b = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (b >= nboxes) return;
+  const int lane = (int)(threadIdx.x & 63u);
+  const int64_t q = bq[b];
+  unsigned long long c = 0;
+  if (q >= 0 && q < nq) {
+    const int32_t d0 = dmin[b], d1 = dmax[b], a0 = amin[b], a1 = amax[b];
+    const int64_t r1 = (int64_t)row_off[q + 1];
+    for (int64_t base = (int64_t)row_off[q]; base < r1; base += 64) {
+      const int64_t o = base + lane;
+      bool ok = false;
+      if (o < r1) {
+        const int32_t d = rows[o * 3 + 1], a = rows[o * 3 + 2];
+        ok = d >= d0 && d <= d1 && a >= a0 && a <= a1;
+      }
+      c += (unsigned long long)__popcll(__ballot(ok));
+    }
+  }
+  if (lane == 0) counts[b] = c;
+}
+
+// ---- K10d -----------------------------------------------------------------------------------------------
+// Key: query | d + d_off | a, abits for a, dbits for the diagonal, the query above them; all fields non-negative.
+struct KeyLayout { int abits, dbits, d_off; };
+__device__ __forceinline__ uint64_t make_key(const KeyLayout kl, uint64_t q, uint64_t dq, uint64_t a) {
+  return (q << (kl.dbits + kl.abits)) | (dq << kl.abits) | a;
+}
+__global__ __launch_bounds__(256) void k_qgraph_keys(const int32_t* __restrict__ rows, int64_t n, KeyLayout kl,
+                                                     uint64_t* __restrict__ keys, uint32_t* __restrict__ vals) {
+  const int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (o >= n) return;
+  keys[o] = make_key(kl, (uint64_t)(uint32_t)rows[o * 3], (uint64_t)(uint32_t)(rows[o * 3 + 1] + kl.d_off), (uint64_t)(uint32_t)rows[o * 3 + 2]);
+  vals[o] = (uint32_t)o;
+}
+// One thread per point in (q, d, a) order; the sorted points of query q are [row_off[q], row_off[q + 1]).  The admission
+// test on the scaled axis is the KD-tree's own, fl(|fl(d c) - fl(d' c)|) <= R, as K7's; on each admitted diagonal the points
+// with |a - a'| <= R form one contiguous piece.  Diagonals ascend, so every search starts where the last one ended.
+template <bool FILL>
+__global__ __launch_bounds__(256) void k_qgraph_scan(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ order, int64_t n,
+                                                     const uint64_t* __restrict__ row_off, KeyLayout kl, int nd, double c, double R,
+                                                     int win, uint32_t* __restrict__ cnt, const uint64_t* __restrict__ off,
+                                                     uint32_t* __restrict__ adj) {
+  const int64_t s = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (s >= n) return;
+  const uint64_t key = keys[s];
+  const uint32_t o = order[s];
+  const uint64_t amask = (1ull << kl.abits) - 1, dmask = (1ull << kl.dbits) - 1;
+  const uint64_t qq = key >> (kl.dbits + kl.abits);
+  const int dq = (int)((key >> kl.abits) & dmask);
+  const int64_t a = (int64_t)(key & amask);
+  const double X = (double)(dq - kl.d_off) * c;
+  const int64_t ra = (int64_t)floor(R);           // |a - a'| <= R for integers
+  const int64_t alo = a - ra < 0 ? 0 : a - ra, ahi = a + ra > (int64_t)amask ? (int64_t)amask : a + ra;
+  uint64_t w = FILL ? off[o] : 0;
+  uint32_t total = 0;
+  const int d0 = dq - win < 0 ? 0 : dq - win, d1 = dq + win > nd - 1 ? nd - 1 : dq + win;
+  const int64_t qb = (int64_t)row_off[qq], qe = (int64_t)row_off[qq + 1];
+  int64_t wlo = qb + lower_bound_dev<uint64_t>(keys + qb, qe - qb, make_key(kl, qq, (uint64_t)d0, 0));
+  const int64_t whi = wlo + upper_bound_dev<uint64_t>(keys + wlo, qe - wlo, make_key(kl, qq, (uint64_t)d1, amask));
+  for (int dd = d0; dd <= d1 && wlo < whi; dd++) {
+    const double Xp = (double)(dd - kl.d_off) * c;
+    if (!(fabs(X - Xp) <= R)) continue;
+    const int64_t lo = wlo + lower_bound_dev<uint64_t>(keys + wlo, whi - wlo, make_key(kl, qq, (uint64_t)dd, (uint64_t)alo));
+    const int64_t hi = lo + upper_bound_dev<uint64_t>(keys + lo, whi - lo, make_key(kl, qq, (uint64_t)dd, (uint64_t)ahi));
+    if (!FILL) total += (uint32_t)(hi - lo);
+    else for (int64_t t = lo; t < hi; t++) { const uint32_t v = order[t]; if (v != o) adj[w++] = v; }
+    wlo = hi;
+  }
+  if (!FILL) cnt[o] = total - 1;                  // its own entry is removed (blot.py:371-372)
+}
+
+int bits_for(uint64_t maxval) { int b = 1; while ((maxval >> b) != 0) b++; return b; }
+
+}  // namespace
+
+struct pw_qseed_index {
+  int device = 0, L = 0, k = 0, bits = 0;
+  bool key32 = false, has_tab = false;  // L^k fits 32 bits: 4-byte keys; the direct-address table is filled
+  int64_t nR = 0, nkR = 0, nq = -1, npos = 0, nrows = -1, max_qlen = 0;
+  uint64_t kinv = 0;
+  DeviceBuffer dref, rkeys, rpos, tab;                                        // the reference: filled by create
+  DeviceBuffer arena, meta, qid, lo, cnt, off, row_off, rows, tmp, scalar;    // the queries: filled by build
+  DeviceBuffer g_keys, g_order, g_cnt, g_off, g_adj;                          // neighbourhood graph (K10d)
+  int64_t g_edges = -1;
+  int cc_rounds = 0;
+  DeviceEvent ev0, ev1;
+  float ms_build = 0.f, ms_graph = 0.f, ms_cc = 0.f, ms_count = 0.f;
+};
+
+static int elapsed(pw_qseed_index* x, hipStream_t st, float* ms) {
+  CHECK(hipEventRecord(x->ev1.e, st));
+  CHECK(hipEventSynchronize(x->ev1.e));
+  CHECK(hipEventElapsedTime(ms, x->ev0.e, x->ev1.e));
+  CHECK(hipGetLastError());
+  return 0;
+}
+
+// encode + sort the reference, fill the table: everything of pw_qseeds_create that depends on the key type
+template <typename K>
+static int index_reference(pw_qseed_index* x) {
+  const int64_t nk = x->nkR;
+  CHECK(x->rkeys.ensure((size_t)std::max<int64_t>(nk, 1) * sizeof(K))); CHECK(x->rpos.ensure((size_t)std::max<int64_t>(nk, 1) * 4));
+  if (nk <= 0) return 0;
+  DeviceBuffer keys_in, pos_in;
+  CHECK(keys_in.ensure((size_t)nk * sizeof(K))); CHECK(pos_in.ensure((size_t)nk * 4));
+  const MaskSets none = {};
+  hipLaunchKernelGGL((k_encode<K>), dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, nullptr, (const uint8_t*)x->dref.p, x->nR, x->k,
+                     x->L, x->kinv, none, (K*)keys_in.p, (uint32_t*)pos_in.p);
+  CHECK(rocprim_run(x->tmp, [&](void* t, size_t& b) {
+    return rocprim::radix_sort_pairs(t, b, (const K*)keys_in.p, (K*)x->rkeys.p, (const uint32_t*)pos_in.p, (uint32_t*)x->rpos.p,
+                                     (size_t)nk, 0u, (unsigned)x->bits, (hipStream_t) nullptr);
+  }));
+  // the direct-address table pays when the key space is small and dense enough (as pw_seeds_build decides): at most 2^26
+  // keys and on average no more than 64 keys between two consecutive k-mers of the reference
+  if (x->key32 && x->kinv <= (1ull << 26) && x->kinv / (uint64_t)nk <= 64) {
+    CHECK(x->tab.ensure((size_t)(x->kinv + 2) * 4));
+    hipLaunchKernelGGL((k_table_fill<K>), dim3((unsigned)((nk + 256) / 256)), dim3(256), 0, nullptr, (const K*)x->rkeys.p, nk, x->kinv,
+                       (uint32_t*)x->tab.p);
+    x->has_tab = true;
+  }
+  CHECK(hipDeviceSynchronize());                  // (keys_in / pos_in are freed on return)
+  CHECK(hipGetLastError());
+  return 0;
+}
+
+template <typename K>
+static void launch_match(pw_qseed_index* x, const uint8_t* arena, hipStream_t st) {
+  const int64_t* meta = (const int64_t*)x->meta.p;                 // [offsets nq | pstart nq + 1 | lengths nq (int32)]
+  hipLaunchKernelGGL((k_qmatch<K>), dim3((unsigned)((x->npos + 255) / 256)), dim3(256), 0, st, arena, meta,
+                     (const int32_t*)(meta + 2 * x->nq + 1), meta + x->nq, x->nq, x->npos, x->k, x->L, (const K*)x->rkeys.p, x->nkR,
+                     x->has_tab ? (const uint32_t*)x->tab.p : (const uint32_t*)nullptr, (uint32_t*)x->qid.p, (uint32_t*)x->lo.p,
+                     (uint64_t*)x->cnt.p, (int*)((unsigned long long*)x->scalar.p + 1));
+}
+
+extern "C" {
+
+const char* pw_qseeds_last_error(void) { return g_err.c_str(); }
+
+pw_qseed_index* pw_qseeds_create(int device, const uint8_t* ref, int64_t n_ref, int alphabet_len, int wordlen) {
+  if (alphabet_len < 1 || alphabet_len > 36) { set_err("alphabet_len must be 1..36 (kmers.py:266)"); return nullptr; }
+  if (wordlen < 1 || wordlen > 31) { set_err("wordlen must be 1..31 (kmers.py:269)"); return nullptr; }
+  long double lk = 1; for (int i = 0; i < wordlen; i++) lk *= alphabet_len;
+  if (lk >= (long double)(1ull << 62)) { set_err("alphabet_len ^ wordlen must be below 2^62"); return nullptr; }
+  if (n_ref < 0 || n_ref >= (1ll << 31)) { set_err("reference length out of range (below 2^31)"); return nullptr; }
+  if (n_ref > 0 && !ref) { set_err("null reference pointer"); return nullptr; }
+  for (int64_t i = 0; i < n_ref; i++) if (ref[i] >= alphabet_len) { set_err("letter outside the alphabet in the reference"); return nullptr; }
+  if (hipSetDevice(device) != hipSuccess) { set_err("hipSetDevice failed"); return nullptr; }
+  pw_qseed_index* x = new pw_qseed_index();
+  x->device = device; x->L = alphabet_len; x->k = wordlen;
+  x->nR = n_ref; x->nkR = n_ref >= wordlen ? n_ref - wordlen + 1 : 0;
+  uint64_t kinv = 1; for (int i = 0; i < wordlen; i++) kinv *= (uint64_t)alphabet_len;
+  x->kinv = kinv;
+  x->bits = bits_for(kinv > 1 ? kinv - 1 : 1);
+  x->key32 = kinv < 0xffffffffull;
+  if (x->dref.ensure((size_t)n_ref + 64) != hipSuccess || x->scalar.ensure(16) != hipSuccess || x->ev0.create() != hipSuccess ||
+      x->ev1.create() != hipSuccess) {
+    set_err("device allocation failed"); delete x; return nullptr;
+  }
+  if (n_ref && hipMemcpy(x->dref.p, ref, (size_t)n_ref, hipMemcpyHostToDevice) != hipSuccess) {
+    set_err("copy of the reference to the device failed"); delete x; return nullptr;
+  }
+  if ((x->key32 ? index_reference<uint32_t>(x) : index_reference<uint64_t>(x)) != 0) { delete x; return nullptr; }
+  return x;
+}
+
+int pw_qseeds_build(pw_qseed_index* x, const uint8_t* arena, uint64_t arena_bytes, int arena_on_device, const int64_t* offsets,
+                    const int32_t* lengths, int64_t n_queries, int64_t max_rows, void* stream) {
+  if (!x) { set_err("null index"); return -1; }
+  if (n_queries < 0 || n_queries >= (1ll << 31)) { set_err("n_queries out of range"); return -1; }
+  if (n_queries > 0 && (!offsets || !lengths)) { set_err("null offsets / lengths"); return -1; }
+  if (arena_bytes > 0 && !arena) { set_err("null arena pointer"); return -1; }
+  hipStream_t st = (hipStream_t)stream;
+  if (max_rows <= 0) max_rows = 1ll << 30;
+  max_rows = std::min<int64_t>(max_rows, (1ll << 31) - 1);
+  x->nrows = -1; x->nq = -1; x->g_edges = -1;
+  // [offsets nq | pstart nq + 1 | lengths nq (int32)] in one block: one copy to the device
+  const int64_t nq = n_queries;
+  std::vector<int64_t> meta((size_t)(2 * nq + 1 + (nq + 1) / 2 + 1));
+  int64_t npos = 0, max_qlen = 0;
+  int32_t* hl = (int32_t*)(meta.data() + 2 * nq + 1);
+  for (int64_t q = 0; q < nq; q++) {
+    if (lengths[q] < 0 || offsets[q] < 0 || (uint64_t)offsets[q] + (uint64_t)lengths[q] > arena_bytes) {
+      set_err("query " + std::to_string(q) + " lies outside the arena"); return -1;
+    }
+    meta[(size_t)q] = offsets[q];
+    meta[(size_t)(nq + q)] = npos;
+    hl[q] = lengths[q];
+    npos += lengths[q];
+    max_qlen = std::max<int64_t>(max_qlen, lengths[q]);
+    if (npos >= (1ll << 31)) { set_err("the queries' lengths must sum to less than 2^31"); return -1; }
+  }
+  meta[(size_t)(2 * nq)] = npos;
+  CHECK(hipSetDevice(x->device));
+  CHECK(x->meta.ensure(meta.size() * 8));
+  CHECK(x->row_off.ensure((size_t)(nq + 1) * 8));
+  CHECK(hipEventRecord(x->ev0.e, st));            // (the build's time includes its copies to the device)
+  const uint8_t* darena = arena;
+  if (!arena_on_device) {
+    CHECK(x->arena.ensure((size_t)arena_bytes + 64));
+    if (arena_bytes) CHECK(hipMemcpyAsync(x->arena.p, arena, (size_t)arena_bytes, hipMemcpyHostToDevice, st));
+    darena = (const uint8_t*)x->arena.p;
+  }
+  CHECK(hipMemcpyAsync(x->meta.p, meta.data(), meta.size() * 8, hipMemcpyHostToDevice, st));
+  CHECK(hipMemsetAsync(x->scalar.p, 0, 16, st));
+  x->npos = npos; x->max_qlen = max_qlen;
+  const size_t np1 = (size_t)std::max<int64_t>(npos, 1);
+  CHECK(x->qid.ensure(np1 * 4)); CHECK(x->lo.ensure(np1 * 4)); CHECK(x->cnt.ensure(np1 * 8)); CHECK(x->off.ensure(np1 * 8));
+  x->nq = nq;                                     // (launch_match reads it; reset below on failure)
+  if (npos > 0) {
+    if (x->key32) launch_match<uint32_t>(x, darena, st); else launch_match<uint64_t>(x, darena, st);
+    CHECK(rocprim_run(x->tmp, [&](void* t, size_t& b) {
+      return rocprim::exclusive_scan(t, b, (const uint64_t*)x->cnt.p, (uint64_t*)x->off.p, (uint64_t)0, (size_t)npos, SatAdd(), st);
+    }));
+  }
+  const int64_t* dmeta = (const int64_t*)x->meta.p;
+  hipLaunchKernelGGL(k_qoffsets, dim3((unsigned)((nq + 256) / 256)), dim3(256), 0, st, (const uint64_t*)x->off.p, (const uint64_t*)x->cnt.p,
+                     npos, dmeta + nq, nq, (unsigned long long*)x->scalar.p, (uint64_t*)x->row_off.p);
+  unsigned long long res[2] = {0, 0};             // row total, bad-letter flag
+  CHECK(hipMemcpyAsync(res, x->scalar.p, 16, hipMemcpyDeviceToHost, st));
+  CHECK(hipStreamSynchronize(st));
+  x->nq = -1;
+  if ((int)res[1] != 0) { set_err("letter outside the alphabet in a query"); return -1; }
+  const unsigned long long total = res[0];
+  if (total > (unsigned long long)max_rows) {
+    char msg[200];
+    if (total == ~0ull)
+      snprintf(msg, sizeof msg, "the seeds table would hold at least 2^64 - 1 rows (limit %lld): raise the word length", (long long)max_rows);
+    else
+      snprintf(msg, sizeof msg, "the seeds table would hold %llu rows (limit %lld): raise max_rows or the word length", total, (long long)max_rows);
+    set_err(msg);
+    return -1;
+  }
+  CHECK(x->rows.ensure((size_t)std::max<unsigned long long>(total, 1) * 12));
+  if (total > 0)
+    hipLaunchKernelGGL(k_qexpand, dim3((unsigned)((total + kExpRows - 1) / kExpRows)), dim3(256), 0, st, (const uint64_t*)x->off.p, npos,
+                       (int64_t)total, (const uint32_t*)x->qid.p, dmeta + nq, (const uint32_t*)x->lo.p, (const uint32_t*)x->rpos.p,
+                       (int32_t*)x->rows.p);
+  if (elapsed(x, st, &x->ms_build) != 0) return -1;
+  x->nq = nq; x->nrows = (int64_t)total;
+  return 0;
+}
+
+int64_t pw_qseeds_num_queries(const pw_qseed_index* x) { return x ? x->nq : -1; }
+int64_t pw_qseeds_num_rows(const pw_qseed_index* x) { return x ? x->nrows : -1; }
+const int32_t* pw_qseeds_rows_device(const pw_qseed_index* x) { return (x && x->nrows >= 0) ? (const int32_t*)x->rows.p : nullptr; }
+double pw_qseeds_build_ms(const pw_qseed_index* x) { return x ? (double)x->ms_build : -1.0; }
+double pw_qseeds_graph_ms(const pw_qseed_index* x) { return x ? (double)x->ms_graph : -1.0; }
+double pw_qseeds_components_ms(const pw_qseed_index* x) { return x ? (double)x->ms_cc : -1.0; }
+double pw_qseeds_count_ms(const pw_qseed_index* x) { return x ? (double)x->ms_count : -1.0; }
+int pw_qseeds_components_rounds(const pw_qseed_index* x) { return x ? x->cc_rounds : -1; }
+
+int pw_qseeds_rows(const pw_qseed_index* x, int32_t* rows, int64_t cap) {
+  if (!x || x->nrows < 0) { set_err("pw_qseeds_rows before a successful pw_qseeds_build"); return -1; }
+  if (cap < x->nrows) { set_err("pw_qseeds_rows: capacity too small"); return -1; }
+  CHECK(hipSetDevice(x->device));
+  if (x->nrows) CHECK(hipMemcpy(rows, x->rows.p, (size_t)x->nrows * 12, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int pw_qseeds_row_offsets(const pw_qseed_index* x, int64_t* row_offsets) {
+  if (!x || x->nrows < 0) { set_err("pw_qseeds_row_offsets before a successful pw_qseeds_build"); return -1; }
+  CHECK(hipSetDevice(x->device));
+  CHECK(hipMemcpy(row_offsets, x->row_off.p, (size_t)(x->nq + 1) * 8, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int pw_qseeds_count_boxes(const pw_qseed_index* xc, int64_t n_boxes, const int32_t* q, const int32_t* dmin, const int32_t* dmax,
+                          const int32_t* amin, const int32_t* amax, int64_t* counts) {
+  pw_qseed_index* x = const_cast<pw_qseed_index*>(xc);
+  if (!x || x->nrows < 0) { set_err("pw_qseeds_count_boxes before a successful pw_qseeds_build"); return -1; }
+  if (n_boxes < 0 || n_boxes >= (1ll << 31)) { set_err("n_boxes out of range"); return -1; }
+  if (n_boxes == 0) return 0;
+  for (int64_t b = 0; b < n_boxes; b++)
+    if (q[b] < 0 || q[b] >= x->nq) { set_err("box " + std::to_string(b) + " names a query that does not exist"); return -1; }
+  CHECK(hipSetDevice(x->device));
+  const size_t nb = (size_t)n_boxes;
+  std::vector<int32_t> h(nb * 5);                 // the five bound arrays in one block: one copy to the device
+  const int32_t* src[5] = {q, dmin, dmax, amin, amax};
+  for (int f = 0; f < 5; f++) memcpy(h.data() + f * nb, src[f], nb * 4);
+  DeviceBuffer dbox, dcnt;
+  CHECK(dbox.ensure(nb * 20)); CHECK(dcnt.ensure(nb * 8));
+  CHECK(hipMemcpy(dbox.p, h.data(), nb * 20, hipMemcpyHostToDevice));
+  CHECK(hipEventRecord(x->ev0.e, nullptr));
+  const int32_t* d = (const int32_t*)dbox.p;
+  hipLaunchKernelGGL(k_qcount, dim3((unsigned)((n_boxes + 3) / 4)), dim3(256), 0, nullptr, (const int32_t*)x->rows.p,
+                     (const uint64_t*)x->row_off.p, x->nq, n_boxes, d, d + nb, d + 2 * nb, d + 3 * nb, d + 4 * nb,
+                     (unsigned long long*)dcnt.p);
+  if (elapsed(x, nullptr, &x->ms_count) != 0) return -1;
+  CHECK(hipMemcpy(counts, dcnt.p, nb * 8, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int64_t pw_qseeds_graph_build(pw_qseed_index* x, double d_coeff, double radius) {
+  if (!x || x->nrows < 0) { set_err("pw_qseeds_graph_build before a successful pw_qseeds_build"); return -1; }
+  if (!(d_coeff > 0) || !(radius >= 0)) { set_err("d_coeff must be positive and radius non-negative"); return -1; }
+  x->g_edges = -1;
+  CHECK(hipSetDevice(x->device));
+  const int64_t n = x->nrows;
+  if (n == 0) { x->g_edges = 0; x->ms_graph = 0.f; return 0; }
+  // d = i - j lies in (-max query length, nR): bucket d + max_qlen in [0, nd); a = i + j below nR + max_qlen
+  const int64_t nd = x->nR + x->max_qlen + 1;
+  KeyLayout kl;
+  kl.d_off = (int)x->max_qlen;
+  kl.dbits = bits_for((uint64_t)(nd - 1));
+  kl.abits = bits_for((uint64_t)(x->nR + x->max_qlen));
+  const int qbits = bits_for((uint64_t)std::max<int64_t>(x->nq - 1, 1));
+  if (qbits + kl.dbits + kl.abits > 64) {
+    char msg[200];
+    snprintf(msg, sizeof msg, "the graph's sort key needs %d + %d + %d bits (query, diagonal, antidiagonal): more than 64; "
+             "use fewer queries per call", qbits, kl.dbits, kl.abits);
+    set_err(msg);
+    return -1;
+  }
+  CHECK(hipEventRecord(x->ev0.e, nullptr));
+  const double wd = floor(radius / d_coeff) + 2;
+  const int win = wd > (double)nd ? (int)nd : (int)wd;
+  DeviceBuffer kin, vin;
+  CHECK(kin.ensure((size_t)n * 8)); CHECK(vin.ensure((size_t)n * 4));
+  CHECK(x->g_keys.ensure((size_t)n * 8)); CHECK(x->g_order.ensure((size_t)n * 4));
+  CHECK(x->g_cnt.ensure((size_t)n * 4)); CHECK(x->g_off.ensure((size_t)(n + 1) * 8));
+  const dim3 grid((unsigned)((n + 255) / 256)), blk(256);
+  hipLaunchKernelGGL(k_qgraph_keys, grid, blk, 0, nullptr, (const int32_t*)x->rows.p, n, kl, (uint64_t*)kin.p, (uint32_t*)vin.p);
+  CHECK(rocprim_run(x->tmp, [&](void* t, size_t& b) {
+    return rocprim::radix_sort_pairs(t, b, (const uint64_t*)kin.p, (uint64_t*)x->g_keys.p, (const uint32_t*)vin.p, (uint32_t*)x->g_order.p,
+                                     (size_t)n, 0u, (unsigned)(qbits + kl.dbits + kl.abits), (hipStream_t) nullptr);
+  }));
+  hipLaunchKernelGGL((k_qgraph_scan<false>), grid, blk, 0, nullptr, (const uint64_t*)x->g_keys.p, (const uint32_t*)x->g_order.p, n,
+                     (const uint64_t*)x->row_off.p, kl, (int)nd, d_coeff, radius, win, (uint32_t*)x->g_cnt.p, (const uint64_t*)nullptr,
+                     (uint32_t*)nullptr);
+  // offsets = exclusive scan of the counts (64-bit)
+  uint64_t* wide = (uint64_t*)kin.p;              // reuse: n x 8 bytes
+  hipLaunchKernelGGL(k_widen, grid, blk, 0, nullptr, (const uint32_t*)x->g_cnt.p, n, wide);
+  CHECK(rocprim_run(x->tmp, [&](void* t, size_t& b) {
+    return rocprim::exclusive_scan(t, b, (const uint64_t*)wide, (uint64_t*)x->g_off.p, (uint64_t)0, (size_t)n, rocprim::plus<uint64_t>(), (hipStream_t) nullptr);
+  }));
+  hipLaunchKernelGGL(k_total, dim3(1), dim3(64), 0, nullptr, (const uint64_t*)x->g_off.p, (const uint64_t*)wide, n, (unsigned long long*)x->scalar.p);
+  unsigned long long total = 0;
+  CHECK(hipMemcpy(&total, x->scalar.p, 8, hipMemcpyDeviceToHost));
+  if (total >= (1ull << 32)) { set_err("the neighbourhood graph has more than 2^32 edges: use a smaller radius"); return -1; }
+  CHECK(hipMemcpy((uint64_t*)x->g_off.p + n, &total, 8, hipMemcpyHostToDevice));
+  CHECK(x->g_adj.ensure((size_t)std::max<unsigned long long>(total, 1) * 4));
+  if (total)
+    hipLaunchKernelGGL((k_qgraph_scan<true>), grid, blk, 0, nullptr, (const uint64_t*)x->g_keys.p, (const uint32_t*)x->g_order.p, n,
+                       (const uint64_t*)x->row_off.p, kl, (int)nd, d_coeff, radius, win, (uint32_t*)nullptr, (const uint64_t*)x->g_off.p,
+                       (uint32_t*)x->g_adj.p);
+  if (elapsed(x, nullptr, &x->ms_graph) != 0) return -1;
+  x->g_edges = (int64_t)total;
+  return x->g_edges;
+}
+
+int pw_qseeds_graph_counts(const pw_qseed_index* x, int32_t* counts, int64_t cap) {
+  if (!x || x->g_edges < 0) { set_err("pw_qseeds_graph_counts before a successful pw_qseeds_graph_build"); return -1; }
+  if (cap < x->nrows) { set_err("pw_qseeds_graph_counts: capacity too small"); return -1; }
+  CHECK(hipSetDevice(x->device));
+  if (x->nrows) CHECK(hipMemcpy(counts, x->g_cnt.p, (size_t)x->nrows * 4, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int pw_qseeds_graph_fetch(const pw_qseed_index* x, int64_t* offsets, int32_t* neighbours) {
+  if (!x || x->g_edges < 0) { set_err("pw_qseeds_graph_fetch before a successful pw_qseeds_graph_build"); return -1; }
+  CHECK(hipSetDevice(x->device));
+  if (x->nrows == 0) { offsets[0] = 0; return 0; }
+  CHECK(hipMemcpy(offsets, x->g_off.p, (size_t)(x->nrows + 1) * 8, hipMemcpyDeviceToHost));
+  if (x->g_edges) CHECK(hipMemcpy(neighbours, x->g_adj.p, (size_t)x->g_edges * 4, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int pw_qseeds_graph_components(const pw_qseed_index* xc, const uint8_t* avail, int32_t* labels) {
+  pw_qseed_index* x = const_cast<pw_qseed_index*>(xc);
+  if (!x || x->g_edges < 0) { set_err("pw_qseeds_graph_components before a successful pw_qseeds_graph_build"); return -1; }
+  const int64_t n = x->nrows;
+  x->cc_rounds = 0;
+  if (n == 0) return 0;
+  CHECK(hipSetDevice(x->device));
+  DeviceBuffer av, par, flag;
+  CHECK(av.ensure((size_t)n)); CHECK(par.ensure((size_t)n * 4)); CHECK(flag.ensure(16));
+  CHECK(hipMemcpy(av.p, avail, (size_t)n, hipMemcpyHostToDevice));
+  CHECK(hipEventRecord(x->ev0.e, nullptr));
+  const dim3 grid((unsigned)((n + 255) / 256)), blk(256);
+  hipLaunchKernelGGL(k_cc_init, grid, blk, 0, nullptr, (const uint8_t*)av.p, n, (int*)par.p);
+  for (int it = 0; it < 10000; it++) {            // every round at least halves the number of roots still to merge
+    CHECK(hipMemsetAsync(flag.p, 0, 4, nullptr));
+    hipLaunchKernelGGL(k_cc_hook, grid, blk, 0, nullptr, (const uint64_t*)x->g_off.p, (const uint32_t*)x->g_cnt.p,
+                       (const uint32_t*)x->g_adj.p, n, (int*)par.p, (int*)flag.p);
+    hipLaunchKernelGGL(k_cc_compress, grid, blk, 0, nullptr, n, (int*)par.p);
+    int changed = 0;
+    CHECK(hipMemcpy(&changed, flag.p, 4, hipMemcpyDeviceToHost));
+    x->cc_rounds = it + 1;
+    if (!changed) break;
+  }
+  if (elapsed(x, nullptr, &x->ms_cc) != 0) return -1;
+  CHECK(hipMemcpy(labels, par.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+void pw_qseeds_destroy(pw_qseed_index* x) {
+  if (!x) return;
+  (void)hipSetDevice(x->device);
+  delete x;
+}
+
+}  // extern "C"

@@ -1,5 +1,6 @@
-// pw_seed_kernels.h -- device code shared by the pairwise seed index (pw_seeds.hip) and the N-way one (pw_mseeds.hip):
-// the k-mer encoder (K5a), the diagonal starts of K7's sorted points, the 64-bit widening and the last-offset read
+// pw_seed_kernels.h -- device code shared by the pairwise seed index (pw_seeds.hip), the N-way one (pw_mseeds.hip) and the
+// query-batched one (pw_qseeds.hip): the k-mer encoder (K5a), the direct-address table of the join (K5b), the diagonal
+// starts of K7's sorted points, the 64-bit widening and the last-offset read
 // used around rocPRIM's scans, and the connected components of a CSR graph (K7's hook / compress).  Kernels live in an
 // anonymous namespace: each translation unit gets its own copy.
 #pragma once
@@ -40,6 +41,19 @@ __global__ __launch_bounds__(256) void k_encode(const uint8_t* __restrict__ seq,
   for (int i = 0; i < ms.n; i++) masked |= lets == ms.set[i];
   keys[p] = (K)(masked ? kinv : v);
   pos[p] = (uint32_t)p;
+}
+
+// ---- K5b's direct-address table ---------------------------------------------------------------------------
+// tab[q] = number of elements of the sorted keys `other` below q, for q = 0 .. kinv + 1: element i (the first of its run)
+// fills the keys after the previous run's key up to its own; one extra thread fills the tail.  (Used only when the keys
+// are dense enough that these gaps are short: see pw_seeds_build.)
+template <typename K>
+__global__ __launch_bounds__(256) void k_table_fill(const K* __restrict__ other, int64_t no, uint64_t kinv, uint32_t* __restrict__ tab) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i > no) return;
+  const int64_t prev = i > 0 ? (int64_t)other[i - 1] : -1;
+  const int64_t cur = i < no ? (int64_t)other[i] : (int64_t)kinv + 1;
+  for (int64_t q = prev + 1; q <= cur; q++) tab[q] = (uint32_t)i;
 }
 
 __global__ __launch_bounds__(256) void k_widen(const uint32_t* __restrict__ in, int64_t n, uint64_t* __restrict__ out) {

@@ -57,17 +57,7 @@ __global__ __launch_bounds__(256) void k_match(const K* __restrict__ ks, int64_t
   if (!self) cnt[e] = (uint64_t)(hi - lo);
   else cnt[e] = (uint64_t)(hi - 1 - e) + (e == hi - 1 ? (uint64_t)(hi - lo) : 0ull);
 }
-// tab[q] = number of elements of `other` below q, for q = 0 .. kinv + 1: element i (the first of its run) fills the
-// keys after the previous run's key up to its own; one extra thread fills the tail.  (Used only when the keys are dense
-// enough that these gaps are short: see pw_seeds_build.)
-template <typename K>
-__global__ __launch_bounds__(256) void k_table_fill(const K* __restrict__ other, int64_t no, uint64_t kinv, uint32_t* __restrict__ tab) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i > no) return;
-  const int64_t prev = i > 0 ? (int64_t)other[i - 1] : -1;
-  const int64_t cur = i < no ? (int64_t)other[i] : (int64_t)kinv + 1;
-  for (int64_t q = prev + 1; q <= cur; q++) tab[q] = (uint32_t)i;
-}
+// (k_table_fill, which fills tab: pw_seed_kernels.h)
 
 // ---- K5c ------------------------------------------------------------------------------------------------
 // One thread per row, kExpRows rows per workgroup.  The element a row belongs to is found by a binary search over the

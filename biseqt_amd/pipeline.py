@@ -5,13 +5,14 @@ The reference has no library function for this; the flow is written out in its e
 is turned into a pair of sub-frames a few word lengths larger, and a banded global alignment of the two frames is
 solved, traced back and truncated to its first / last match.  Here the frames of ALL segments are solved by one
 batch (`BatchAligner`), i.e. a handful of kernel launches, and the arithmetic that decides the frames and bands is
-the reference's, statement by statement.
+the reference's, statement by statement.  ``map_queries`` is the many-queries-one-reference flow of
+``experiments/blot_ig_genotyping.py``: segments of all queries from one pass, one banded local batch.
 """
 import numpy as np
 
 from . import _pwlib as W
-from .batch import BatchAligner
-from .blot import WordBlot
+from .batch import BatchAligner, DeviceArena, pack_reads
+from .blot import WordBlot, WordBlotLocalRef
 from .pw import Alignment
 from .sequence import Sequence
 
@@ -67,6 +68,62 @@ def extend_segments(S, T, segments, wordlen, device=0, **aligner_kw):
             rec['alignment'] = aln
             rec['truncated'] = aln.truncate_to_match() if 'M' in txs[k] else None
         out.append(rec)
+    return out
+
+
+def map_queries(ref, queries, K_min, p_min, wordlen, g_max, sensitivity, keep=3, device=0, aligner_kw=None):
+    """Map many short queries onto one reference sequence: Word-Blot local similarities of all queries in one pass
+    (:meth:`WordBlotLocalRef.similar_segments_many`), then a banded local alignment of the best segments of every query,
+    all in ONE lane-packed batch.  The flow of ``experiments/blot_ig_genotyping.py:45-101`` as a library function: per
+    query the segments are ranked by ``p * (a_max - a_min)`` (:45-48), the best ``keep`` are kept (:72-75) and aligned
+    inside ``diag_range = (int(d_min), int(d_max))`` of the segment (:79-88).  Default scores are 1 / -3 / -5 / -2
+    (match, mismatch, gap open, gap extend).
+
+    Returns one list per query, best segment first, of dicts: ``segment``, ``p``, ``diag_range``, ``score``,
+    ``alignment`` (an :class:`Alignment` on ``ref`` and the query, or None where the batch reports no alignment),
+    ``p_aln`` (matches over the letters of the query the alignment covers, rounded to 2 places) and ``len_aln`` (:93-98)."""
+    assert isinstance(ref, Sequence) and all(isinstance(T, Sequence) for T in queries)
+    queries = list(queries)
+    kw = dict(match_score=1, mismatch_score=-3, go_score=-5, ge_score=-2)
+    kw.update(aligner_kw or {})
+    kw.pop('diag_range', None)
+    kw.update(alnmode=W.BANDED_MODE, alntype=W.B_LOCAL)
+    arena, offs, lens = pack_reads([ref] + queries)           # read 0 is the reference, read 1 + q is query q
+    out = [[] for _ in queries]
+    with DeviceArena(arena, device=device) as darena:
+        wb = WordBlotLocalRef(ref, alphabet=ref.alphabet, wordlen=wordlen, g_max=g_max, sensitivity=sensitivity, device=device)
+        try:
+            segs = wb.similar_segments_many(queries, K_min, p_min, arena=(darena, offs[1:], lens[1:]))
+        finally:
+            wb.close()
+        pairs, bands = [], []
+        for q, recs in enumerate(segs):
+            ranked = sorted(recs, key=lambda rec: -(rec['p'] * (rec['segment'][1][1] - rec['segment'][1][0])))[:keep]
+            for rec in ranked:
+                d_band = rec['segment'][0]
+                rec = dict(segment=rec['segment'], p=rec['p'], diag_range=(int(d_band[0]), int(d_band[1])), score=None,
+                           alignment=None, p_aln=None, len_aln=None)
+                out[q].append(rec)
+                pairs.append((0, 1 + q))
+                bands.append(rec['diag_range'])
+        if not pairs:
+            return out
+        with BatchAligner.from_arena(arena, offs, lens, pairs, diag_ranges=bands, device_arena=darena,
+                                     alphabet_len=len(ref.alphabet), device=device, **kw) as b:
+            res = b.run()
+            txs = b.transcripts(res)
+    k = 0
+    for q, recs in enumerate(out):
+        for rec in recs:
+            if res['opt_i'][k] >= 0 and txs[k]:
+                tx = txs[k]
+                rec['score'] = float(res['score'][k])
+                rec['alignment'] = Alignment(ref, queries[q], tx, score=rec['score'], origin_start=int(res['origin_idx'][k]),
+                                             mutant_start=int(res['mutant_idx'][k]))
+                len_on_query = sum(tx.count(op) for op in 'MSI')
+                rec['p_aln'] = round(1. * tx.count('M') / len_on_query, 2) if len_on_query else None
+                rec['len_aln'] = len_on_query
+            k += 1
     return out
 
 

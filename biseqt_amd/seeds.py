@@ -342,6 +342,127 @@ class _MIndex(object):
             pass
 
 
+class _QIndex(object):
+    """Thin owner of a ``pw_qseed_index`` handle (include/pw_qseeds.h): one reference sequence, indexed once, and the
+    seeds of any number of queries against it per :meth:`build`."""
+
+    def __init__(self, ref, wordlen, alphabet, device=0):
+        self.lib = W.load()
+        r = ref.as_array(np.uint8) if isinstance(ref, Sequence) else np.ascontiguousarray(ref, np.uint8)
+        self.device = device
+        self.handle = self.lib.pw_qseeds_create(device, r.ctypes.data, len(r), len(alphabet), wordlen)
+        if not self.handle:
+            raise RuntimeError('pw_qseeds_create failed: ' + self.error())
+        self._edges = None
+
+    def error(self):
+        return (self.lib.pw_qseeds_last_error() or b'').decode('utf-8', 'replace')
+
+    def build(self, arena, offsets, lengths, max_rows=0, stream=None):
+        """Seeds of the queries ``arena[offsets[q]:offsets[q] + lengths[q]]``.  ``arena`` is a uint8 array (the layout of
+        :func:`biseqt_amd.batch.pack_reads`) or a :class:`biseqt_amd.batch.DeviceArena`, which is read in place.
+        Returns the number of rows."""
+        offsets = np.ascontiguousarray(offsets, np.int64)
+        lengths = np.ascontiguousarray(lengths, np.int32)
+        assert offsets.ndim == 1 and offsets.shape == lengths.shape
+        if isinstance(arena, np.ndarray):
+            arena = np.ascontiguousarray(arena, np.uint8)
+            ptr, nbytes, on_device = arena.ctypes.data, arena.nbytes, 0
+        else:
+            assert arena.device == self.device, 'the arena lives on another device'
+            ptr, nbytes, on_device = arena.ptr, arena.nbytes, 1
+        self._edges = None
+        if self.lib.pw_qseeds_build(self.handle, ptr, nbytes, on_device, offsets.ctypes.data, lengths.ctypes.data, len(offsets),
+                                    max_rows, stream) != 0:
+            raise RuntimeError('pw_qseeds_build failed: ' + self.error())
+        return self.num_rows()
+
+    def num_rows(self):
+        return self.lib.pw_qseeds_num_rows(self.handle)
+
+    def num_queries(self):
+        return self.lib.pw_qseeds_num_queries(self.handle)
+
+    def rows(self):
+        """(rows, 3) int32 array of (q, d, a) in (q, j, i) order."""
+        n = self.num_rows()
+        out = np.zeros((max(n, 1), 3), np.int32)
+        if self.lib.pw_qseeds_rows(self.handle, out.ctypes.data, n) != 0:
+            raise RuntimeError('pw_qseeds_rows failed: ' + self.error())
+        return out[:n]
+
+    def row_offsets(self):
+        """int64 array of num_queries + 1 entries: the rows of query q are ``rows[off[q]:off[q + 1]]``."""
+        out = np.zeros(self.num_queries() + 1, np.int64)
+        if self.lib.pw_qseeds_row_offsets(self.handle, out.ctypes.data) != 0:
+            raise RuntimeError('pw_qseeds_row_offsets failed: ' + self.error())
+        return out
+
+    def rows_device(self):
+        return DeviceBuffer(self.lib.pw_qseeds_rows_device(self.handle), 12 * self.num_rows(), self)
+
+    def count_boxes(self, q, dmin, dmax, amin, amax):
+        """Row counts of many (query, d band, a band) boxes in one launch."""
+        arrs = [np.ascontiguousarray(v, np.int32).reshape(-1) for v in (q, dmin, dmax, amin, amax)]
+        n = len(arrs[0])
+        assert all(len(v) == n for v in arrs)
+        out = np.zeros(max(n, 1), np.int64)
+        if self.lib.pw_qseeds_count_boxes(self.handle, n, *([v.ctypes.data for v in arrs] + [out.ctypes.data])) != 0:
+            raise RuntimeError('pw_qseeds_count_boxes failed: ' + self.error())
+        return out[:n]
+
+    def graph_build(self, d_coeff, radius):
+        """Neighbourhood graph of the rows, query by query: max(|d - d'| * d_coeff, |a - a'|) <= radius."""
+        e = self.lib.pw_qseeds_graph_build(self.handle, float(d_coeff), float(radius))
+        if e < 0:
+            raise RuntimeError('pw_qseeds_graph_build failed: ' + self.error())
+        self._edges = e
+        return e
+
+    def graph_counts(self):
+        n = self.num_rows()
+        out = np.zeros(max(n, 1), np.int32)
+        if self.lib.pw_qseeds_graph_counts(self.handle, out.ctypes.data, n) != 0:
+            raise RuntimeError('pw_qseeds_graph_counts failed: ' + self.error())
+        return out[:n]
+
+    def graph_fetch(self):
+        """CSR adjacency: (offsets[rows + 1], neighbours[edges])."""
+        off = np.zeros(self.num_rows() + 1, np.int64)
+        adj = np.zeros(max(self._edges, 1), np.int32)
+        if self.lib.pw_qseeds_graph_fetch(self.handle, off.ctypes.data, adj.ctypes.data) != 0:
+            raise RuntimeError('pw_qseeds_graph_fetch failed: ' + self.error())
+        return off, adj[:self._edges]
+
+    def graph_components(self, avail):
+        n = self.num_rows()
+        av = np.ascontiguousarray(avail, np.uint8)
+        assert av.size == n
+        out = np.full(max(n, 1), -1, np.int32)
+        if self.lib.pw_qseeds_graph_components(self.handle, av.ctypes.data, out.ctypes.data) != 0:
+            raise RuntimeError('pw_qseeds_graph_components failed: ' + self.error())
+        return out[:n]
+
+    def timings(self):
+        """Device milliseconds of the last build, graph build, components and count_boxes calls (HIP events), and the hook
+        rounds the components took."""
+        L = self.lib
+        return {'build': L.pw_qseeds_build_ms(self.handle), 'graph': L.pw_qseeds_graph_ms(self.handle),
+                'components': L.pw_qseeds_components_ms(self.handle), 'counts': L.pw_qseeds_count_ms(self.handle),
+                'rounds': L.pw_qseeds_components_rounds(self.handle)}
+
+    def close(self):
+        if getattr(self, 'handle', None):
+            self.lib.pw_qseeds_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 MAX_SEQS = 16
 
 
