@@ -751,7 +751,7 @@ PW_FN int32_t hi_s(uint32_t v) { return (int32_t)(int16_t)(v >> 16); }
 // MAT: the diagonal candidate takes its score from an integer substitution matrix of up to 4 x 4 letters instead of
 // match / mismatch (_alnchoice_M, _pw_internals.c:217-245: subst_scores[o][m]).  The origin window then carries, per
 // cell, the origin letter's ROW of the matrix -- four bytes subst[o][.] - min(subst) (times 4 under rule 3), at most 127
-// each -- and the mutant window carries byte SELECTORS (0x0c00 | letter, + 4 in the high half of a register): one
+// each -- and the mutant window carries byte SELECTORS (0x0c00 | letter, + 4 in ONE half of a register, see FIXSEL): one
 // v_perm_b32 looks up both cells of a pair.  Letters outside a sequence are the all-zero row / a selector that reads as
 // 0x00: the matrix minimum, which the planner requires to be <= 0 ("matches nothing").
 template <class P, int BK, bool SEG, int RULE = 0, bool MAT = false>
@@ -776,9 +776,21 @@ struct WaveFill16 {
 #endif
   static constexpr int32_t NEG16 = ANYB ? -8192 : -24000;
   static constexpr uint32_t SENT_O = 0xfffeu, SENT_M = 0xffffu;   // letters outside a sequence: match nothing
-  // MAT: selector codes of a mutant letter in the low / high half of a register; outside the sequence 8 / 12, which both
-  // read as 0x00 (8 = the sign of a row byte, and row bytes stay below 128)
-  static constexpr uint32_t MSEL = 0x0c00u, MSENT_LO = 0x0c08u, MSENT_HI = 0x0c0cu;
+  // MAT: selector codes of a mutant letter: 0x0c00 | letter reads the row that is v_perm_b32's second operand, + 4 the row
+  // that is its first; outside the sequence the "letter" is 8, so the codes are 8 / 12, which both read as 0x00 under
+  // either operand order (8 = the sign of a row byte, and row bytes stay below 128)
+  static constexpr uint32_t MSEL = 0x0c00u, MOUT = 8u;
+  // FIXSEL (two packed registers per parity, BK = 8): a mutant letter keeps ONE code all the way through the window.  A
+  // letter walks MW[0].lo, MW[1].lo, MW[0].hi, MW[1].hi and on into the next lane's MW[0].lo, one place per iteration, so
+  // the two letters of a register are always two iterations apart.  With the + 4 given once, to the letters fed on
+  // iterations 2, 3 (mod 4) (sel4_fed), every register holds one code of each kind; which half holds the + 4 follows from
+  // the iteration and the register alone (sel4_lo), and the cell pair passes the two rows to v_perm_b32 in that order.  The
+  // iterations of a block are unrolled, so the order is fixed at compile time and nothing is left of the + 4 / - 4 that
+  // otherwise repairs the spliced register on every iteration (MADJ).  Wider lanes (RH > 2) have letters RH iterations
+  // apart and blocks that do not start on a multiple of 2 RH iterations: they keep the low half / high half codes and MADJ.
+  static constexpr bool FIXSEL = MAT && RH == 2;
+  PW_FN static uint32_t sel4_fed(int it) { return ((uint32_t)it >> 1) & 1u; }      // (it < 0: letters in the window at the start)
+  PW_FN static bool sel4_lo(int k, int p) { return (((k + 7 - p) >> 1) & 1) != 0; }   // the low half of MW[p] on iteration k (mod 4)
   using Base = WaveFill<P, int32_t, BK, true, true, false>;       // only its static feeder helpers are used
 
   // SEG = true, lane packing: a wavefront holds `count` pairs side by side, `nl` lanes each (WaveDesc).
@@ -803,13 +815,13 @@ struct WaveFill16 {
   // capturing rules: the value of every diagonal's last cell (bt unused); tracking rules: the running best lives in
   // kbE / kbO as a key and bt holds the stamp of where it was first reached (stamp_best)
   uint32_t bestE[RH], bestO[RH], btE[RH], btO[RH];
-  uint32_t gebE[RH], gebO[RH];                          // ge (+ the band-top block) per half
+  uint32_t gebE[RH], gebO[RH];                          // ge (KEPT: + go) (+ the band-top block) per half
   uint32_t clE[RH], clO[RH];                            // RULE != 0: clamp of the "left" offer (sentinel for the slot above the band)
   uint32_t tfE[RH], tfO[RH], tlE[RH], tlO[RH];          // first / last step of each diagonal
-  uint32_t accE[RH], accO[RH], acc2E[RH], acc2O[RH];    // inverted tie nibbles: cells 0-3 / 4-7 of a block
+  uint32_t accE[RH], accO[RH], acc2E[RH], acc2O[RH];    // tie nibbles, inverted unless KEPT: cells 0-3 / 4-7 of a block
   uint32_t OW[RH], MW[RH];
   uint32_t ROW[MAT ? R : 1];                            // MAT: the matrix row of every cell's origin letter
-  uint32_t BIASV, MADJ;                                 // MAT: -min(subst) in both halves; the selector fix-up of the mutant window
+  uint32_t BIASV, MADJ;                                 // MAT: -min(subst) in both halves; the selector fix-up of the mutant window (!FIXSEL)
   uint32_t MR0, MR1, MR2, MR3;                          // MAT: the four rows of the matrix
   uint32_t ONE, SH15, C2, C4, C16, NDELTA, MATCHV, GOV, GOVI, NEGV, LIMV;
   // RULE 0, steady blocks: the running best of a slot as a key 8 H + (7 - cell within the block) -- one multiply-add and
@@ -830,6 +842,12 @@ struct WaveFill16 {
   // register profile (the BK = 8 body would fit one more wavefront per SIMD than build.py holds it to, a choice that wants
   // an A/B of its own), the latter lost wavefronts per SIMD or spilled scalar registers.
   static constexpr bool SPLIT = ANYB && MAT;
+  // ... and, with every score held times 4, collects the tie bits as KEPT (1 = candidate kept), the form the plane stores: a
+  // kept-or-not difference x is 0 or at least 4, so an unsigned saturating c - x is c where the candidate is kept and 0 where
+  // not, for c = 1, 2, 4 -- the nibble's bits in place, and no "7 - nibble" per accumulator at the end of a block.  The gap
+  // offers then start from (H + ge) + go and take go back where the same gap op is kept (run(): geb, GOV, GOVI); in 16-bit
+  // wrap-around arithmetic that is the same value.
+  static constexpr bool KEPT = SC4 && SPLIT;
   // ... and, one pair per wavefront, its mask stores take a wave-uniform base per lane group and one 32-bit byte offset per
   // lane.  (Elsewhere the BK / 4 addresses cost registers the body has no room for: the rules that begin on the table edge
   // spilled scalar registers, the match / mismatch body at 28 diagonals per lane lost its second wavefront per SIMD.)
@@ -839,8 +857,8 @@ struct WaveFill16 {
 
   PW_FN WaveFill16(const FillParams<int32_t>& a_, const WaveDesc& wd_) : a(a_), wd(wd_) {}
 
-  // Two cells at once.  `acc` collects the INVERTED tie bits (1 = candidate not kept), 4 bits per cell:
-  // bit 0 B, bit 1 D, bit 2 I; bit 3 (M) stays 0 -- with go <= 0 the walker never needs it: the first
+  // Two cells at once.  `acc` collects the INVERTED tie bits (1 = candidate not kept; KEPT: the bits themselves), 4 bits per
+  // cell: bit 0 B, bit 1 D, bit 2 I; bit 3 (M) stays 0 -- with go <= 0 the walker never needs it: the first
   // kept op is M exactly when none of B, D, I is kept (pw_first_op).
   //
   // EDGE = false: steady phase, every in-band diagonal holds an in-table cell.
@@ -860,7 +878,7 @@ struct WaveFill16 {
   template <int EK>
   PW_FN void cellpair(uint32_t& Hs, uint32_t& Us, uint32_t& Ls, uint32_t& bests, uint32_t& bts, uint32_t geb,
                       uint32_t tf, uint32_t tl, uint32_t& acc, uint32_t up, uint32_t left, uint32_t oc,
-                      uint32_t mc, uint32_t tv, uint32_t clampL = 0, uint32_t och = 0) {
+                      uint32_t mc, uint32_t tv, uint32_t clampL = 0, uint32_t och = 0, bool lo4 = false) {
     constexpr bool EDGE = EK != 0;
     uint32_t hM;
     // (MAT, begin-anywhere rules outside the blocks where diagonals start: a started cell's score is never negative, so the
@@ -869,8 +887,9 @@ struct WaveFill16 {
     //  the sentinel, a large unsigned value that the subtract leaves alone.)
     constexpr bool FLOOR0 = MAT && ANYB && (EK & 1) == 0;
     if (MAT) {
-      // oc / och: the matrix rows of the low / high cell's origin letter, mc: the two selectors
-      const uint32_t hb = pk::add(Hs, pk::perm(och, oc, mc));
+      // oc / och: the matrix rows of the low / high cell's origin letter, mc: the two selectors; lo4 (FIXSEL): the low
+      // half's selector is the one that carries the + 4
+      const uint32_t hb = pk::add(Hs, lo4 ? pk::perm(oc, och, mc) : pk::perm(och, oc, mc));
       hM = FLOOR0 ? pk::subsat(hb, BIASV) : pk::sub(hb, BIASV);
     } else {
       const uint32_t ne = pk::minu(oc ^ mc, ONE);               // 0 where the letters match
@@ -881,7 +900,7 @@ struct WaveFill16 {
     if (ANYB) {
       if (EK & 1) Hn = pk::max(Hn, pk::sign(pk::sub(tv, tf), SH15) & NEGV);   // B = 0 once started, sentinel before
       else if (!FLOOR0) Hn = pk::max(Hn, 0u);                    // B: an alignment may begin anywhere, score 0
-      nB = pk::minu(Hn, ONE);
+      nB = KEPT ? pk::subsat(ONE, Hn) : pk::minu(Hn, ONE);       // (KEPT: a sentinel is a large unsigned value -- not kept)
     } else {
       // B = 0 in the one cell that may begin (step tf), the sentinel everywhere else
       const uint32_t Bc = EDGE ? pk::mad(pk::minu(tv ^ tf, ONE), NEGV, 0u) : NEGV;
@@ -889,8 +908,8 @@ struct WaveFill16 {
       nB = pk::minu(Hn ^ Bc, ONE);
     }
     // "is the candidate kept" only asks whether H == candidate: xor (a 2-cycle op) instead of a packed subtract
-    const uint32_t nD = pk::minu(Hn ^ up, SC4 ? C2 : ONE);       // SC4: 0 or 2
-    const uint32_t nI = pk::minu(Hn ^ left, SC4 ? C4 : ONE);     // SC4: 0 or 4
+    const uint32_t nD = KEPT ? pk::subsat(C2, Hn ^ up) : pk::minu(Hn ^ up, SC4 ? C2 : ONE);       // SC4: 0 or 2
+    const uint32_t nI = KEPT ? pk::subsat(C4, Hn ^ left) : pk::minu(Hn ^ left, SC4 ? C4 : ONE);   // SC4: 0 or 4
     const uint32_t hg = pk::add(Hn, geb);
     Us = pk::mad(nD, GOV, hg);                                   // (H + ge) + go unless a D choice is kept
     Ls = pk::mad(nI, GOVI, hg);
@@ -946,7 +965,7 @@ struct WaveFill16 {
       {
         cellpair<EK>(HE[p], UE[p], LE[p], bestE[p], btE[p], gebE[p], tfE[p], tlE[p], HALF == 0 ? accE[p] : acc2E[p],
                      p == 0 ? up0 : UO[p == 0 ? 0 : p - 1], LO[p], MAT ? ROW[MAT ? p : 0] : OW[p], MW[p], tv0, clE[p],
-                     MAT ? ROW[MAT ? p + RH : 0] : 0u);
+                     MAT ? ROW[MAT ? p + RH : 0] : 0u, FIXSEL && sel4_lo(k, p));
         if (TRK) track_key<EK>(kbE[p], HE[p], tlE[p], tv0, k);
       }
     }
@@ -990,7 +1009,7 @@ struct WaveFill16 {
       {
         cellpair<EK>(HO[p], UO[p], LO[p], bestO[p], btO[p], gebO[p], tfO[p], tlO[p], HALF == 0 ? accO[p] : acc2O[p],
                      UE[p], p == RH - 1 ? leftl : LE[p == RH - 1 ? p : p + 1], MAT ? ROW[MAT ? p : 0] : OW[p], MW[p], tv1, clO[p],
-                     MAT ? ROW[MAT ? p + RH : 0] : 0u);
+                     MAT ? ROW[MAT ? p + RH : 0] : 0u, FIXSEL && sel4_lo(k, p));
         if (TRK) track_key<EK>(kbO[p], HO[p], tlO[p], tv1, k);
       }
     }
@@ -998,9 +1017,10 @@ struct WaveFill16 {
     {
       const int mi = yfeed_m + it;
       const uint32_t fbm = Base::feed_byte(fm_lo, fm_hi, k);
-      // (MAT: the letter arrives in a high half and is moved to the low half of the first register below: high-half code;
-      //  feed_commit has turned the letters outside the sequence into 8, whose code MSEL | 12 is MSENT_HI)
-      const uint32_t feed = (MAT ? (MSEL | (fbm + 4u))
+      // (MAT: the letter arrives in a high half and is moved to the low half of the first register below: high-half code,
+      //  which MADJ repairs -- or, FIXSEL, the code it keeps; feed_commit has turned the letters outside the sequence into
+      //  MOUT, so their codes are 8 / 12 by the same rule)
+      const uint32_t feed = (MAT ? (MSEL | (fbm + 4u * (FIXSEL ? sel4_fed(k) : 1u)))
                                  : ((!EDGE || (uint32_t)mi < (uint32_t)Y) ? fbm : SENT_M)) << 16;
       // ... together with the up offer of the next iteration's even step (one exchange)
       int32_t mv[2] = {(int32_t)MW[RH - 1], (int32_t)UO[RH - 1]};
@@ -1011,8 +1031,8 @@ struct WaveFill16 {
       if (SEG) prv = segfirst ? feed : prv;
       uint32_t first = pk::align16(MW[RH - 1], prv);
       // MAT: what moved from a high half into the low one sheds its + 4, what moved from a low half into the high one gains
-      // it (one 32-bit add: no half borrows, codes are 4 .. 12 in the low half here)
-      if (MAT) first += MADJ;
+      // it (one 32-bit add: no half borrows, codes are 4 .. 12 in the low half here); FIXSEL: codes stay as they are
+      if (MAT && !FIXSEL) first += MADJ;
 #pragma unroll
       for (int p = RH - 1; p > 0; p--) MW[p] = MW[p - 1];
       MW[0] = first;
@@ -1043,7 +1063,7 @@ struct WaveFill16 {
       }
     }
     // 8 cells per slot -> one dword, first cell in the top nibble; un-invert: kept = 7 - (not kept), one subtract per
-    // accumulator for both slots it holds (every nibble is at most 7: no borrows).  Slots are gathered into their natural
+    // accumulator for both slots it holds (every nibble is at most 7: no borrows) -- KEPT: as collected.  Slots are gathered into their natural
     // order -- one v_perm_b32 per dword -- so that every group of 4 goes out as one 16-byte store.
     // Lanes with nothing to store (padding lanes, lanes beyond the plane's rows, blocks past the pair's last)
     // write into the plane's spare row (row `nblocks`, slot 0) instead of branching: a branch here splits the
@@ -1052,8 +1072,9 @@ struct WaveFill16 {
       uint32_t mwd[BK];
 #pragma unroll
       for (int p = 0; p < RH; p++) {
-        const uint32_t kE = 0x77777777u - accE[p], k2E = 0x77777777u - acc2E[p];
-        const uint32_t kO = 0x77777777u - accO[p], k2O = 0x77777777u - acc2O[p];
+        const uint32_t inv = KEPT ? 0u : 0x77777777u;
+        const uint32_t kE = KEPT ? accE[p] : inv - accE[p], k2E = KEPT ? acc2E[p] : inv - acc2E[p];
+        const uint32_t kO = KEPT ? accO[p] : inv - accO[p], k2O = KEPT ? acc2O[p] : inv - acc2O[p];
         mwd[2 * p] = pk::perm(kE, k2E, 0x05040100u);           // (kE.lo, k2E.lo)
         mwd[2 * p + R] = pk::perm(kE, k2E, 0x07060302u);       // (kE.hi, k2E.hi)
         mwd[2 * p + 1] = pk::perm(kO, k2O, 0x05040100u);
@@ -1115,7 +1136,7 @@ struct WaveFill16 {
     return below_hi & ~below_lo;
   }
   // MAT, blocks in which diagonals start or end (`edge`): the block's feed letters outside the sequences are replaced here,
-  // once per block, by letters that encode "outside" (origin 0xff: row 0; mutant 8: selector MSENT_HI) instead of a range
+  // once per block, by letters that encode "outside" (origin 0xff: row 0; mutant MOUT: selector 8 or 12) instead of a range
   // check per iteration.  Steady blocks keep the letters as loaded (only out-of-band slots read those beyond a sequence).
   PW_FN void feed_commit(int b, bool edge) {
     const int ro = (xfeed_o + 8 * b) & 3, rm = (yfeed_m + 8 * b) & 3;
@@ -1124,7 +1145,7 @@ struct WaveFill16 {
     if (MAT && edge) {
       const uint64_t io = inside_bytes(xfeed_o + 8 * b, X), im = inside_bytes(yfeed_m + 8 * b, Y);
       const uint64_t o = ((((uint64_t)fo_hi) << 32) | fo_lo) | ~io;
-      const uint64_t m = (((((uint64_t)fm_hi) << 32) | fm_lo) & im) | (0x0808080808080808ull & ~im);
+      const uint64_t m = (((((uint64_t)fm_hi) << 32) | fm_lo) & im) | ((0x0101010101010101ull * MOUT) & ~im);
       fo_lo = (uint32_t)o; fo_hi = (uint32_t)(o >> 32);
       fm_lo = (uint32_t)m; fm_hi = (uint32_t)(m >> 32);
       // (seen as the halves of one 64-bit value, "the last letter is 0" became a 64-bit unsigned compare, which exists as a
@@ -1160,8 +1181,8 @@ struct WaveFill16 {
     return l == 0u ? MR0 : r;
   }
   PW_FN uint32_t row_at(int i) const { return (uint32_t)i < (uint32_t)X ? row_of((uint32_t)oseq[i]) : 0u; }
-  PW_FN uint32_t msel_lo(int i) const { return (uint32_t)i < (uint32_t)Y ? (MSEL | (uint32_t)mseq[i]) : MSENT_LO; }
-  PW_FN uint32_t msel_hi(int i) const { return (uint32_t)i < (uint32_t)Y ? (MSEL | ((uint32_t)mseq[i] + 4u)) : MSENT_HI; }
+  // selector code of mutant letter i; plus4: the code reads v_perm_b32's first operand
+  PW_FN uint32_t msel(int i, uint32_t plus4) const { return MSEL | (((uint32_t)i < (uint32_t)Y ? (uint32_t)mseq[i] : MOUT) + 4u * plus4); }
   PW_FN uint32_t letter_o(int i) const { return (uint32_t)i < (uint32_t)X ? (uint32_t)oseq[i] : SENT_O; }
   PW_FN uint32_t letter_m(int i) const { return (uint32_t)i < (uint32_t)Y ? (uint32_t)mseq[i] : SENT_M; }
   PW_FN int blocked(int j) const { return li * BK + j == ndiag ? NEG16 : 0; }   // first diagonal above the band
@@ -1190,8 +1211,9 @@ struct WaveFill16 {
     C8 = pk::opaque(0x00080008u); SEVEN = pk::opaque(0x00070007u);
     NEGV = pk::both(NEG16); LIMV = pk::both(-32767);
     NDELTA = pk::both(SCL * (a.mismatch - a.match)); MATCHV = pk::both(SCL * a.match);
-    // the multipliers of the "not kept" values: 0 / 1 each, or (SC4) 0 / 2 for D and 0 / 4 for I
-    GOV = pk::both(SC4 ? 2 * a.go : a.go); GOVI = pk::both(a.go);
+    // the multipliers of the "not kept" values: 0 / 1 each, or (SC4) 0 / 2 for D and 0 / 4 for I; KEPT: of the kept values 2 and
+    // 4, which take 4 go back out of an offer that starts with it (geb below)
+    GOV = pk::both(KEPT ? -2 * a.go : (SC4 ? 2 * a.go : a.go)); GOVI = pk::both(KEPT ? -a.go : a.go);
     BIASV = pk::both(a.mat_bias); MADJ = 0x0003fffcu;
     MR0 = a.mat_rows[0]; MR1 = a.mat_rows[1]; MR2 = a.mat_rows[2]; MR3 = a.mat_rows[3];
     if (MAT) {
@@ -1202,8 +1224,9 @@ struct WaveFill16 {
     for (int p = 0; p < RH; p++) {
       const int e0 = 2 * p, e1 = 2 * p + R, o0 = 2 * p + 1, o1 = 2 * p + 1 + R;
       if (ANYB) {
-        gebE[p] = pk::pack(SCL * a.ge + blocked(e0), SCL * a.ge + blocked(e1));
-        gebO[p] = pk::pack(SCL * a.ge + blocked(o0), SCL * a.ge + blocked(o1));
+        const int geo = SCL * a.ge + (KEPT ? SCL * a.go : 0);
+        gebE[p] = pk::pack(geo + blocked(e0), geo + blocked(e1));
+        gebO[p] = pk::pack(geo + blocked(o0), geo + blocked(o1));
         tfE[p] = pk::pack(tfirst_of(e0), tfirst_of(e1)); tfO[p] = pk::pack(tfirst_of(o0), tfirst_of(o1));
         clE[p] = clO[p] = 0;
       } else {
@@ -1219,7 +1242,11 @@ struct WaveFill16 {
       bestE[p] = bestO[p] = NEGV;
       kbE[p] = kbO[p] = 0u; btE[p] = btO[p] = 0u;
       OW[p] = pk::pack((int32_t)letter_o(xbase + p - 1), (int32_t)letter_o(xbase + p + RH - 1));
-      if (MAT) MW[p] = pk::pack((int32_t)msel_lo(ybase - p - 1), (int32_t)msel_hi(ybase - p - RH - 1));
+      if (MAT) {
+        // (FIXSEL: letter y was, or would have been, fed on iteration y - f)
+        const int yl = ybase - p - 1, yh = ybase - p - RH - 1;
+        MW[p] = pk::pack((int32_t)msel(yl, FIXSEL ? sel4_fed(yl - f) : 0u), (int32_t)msel(yh, FIXSEL ? sel4_fed(yh - f) : 1u));
+      }
       else MW[p] = pk::pack((int32_t)letter_m(ybase - p - 1), (int32_t)letter_m(ybase - p - RH - 1));
     }
     // The planner's steady range allows a diagonal's LAST cell to be the last step of a steady block (every cell of
