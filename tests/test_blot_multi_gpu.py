@@ -16,8 +16,15 @@ pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 A = Alphabet('ACGT')
-with gzip.open(os.path.join(ROOT, 'tests', 'golden', 'blot_multi.json.gz'), 'rt') as _f:
-    G = json.load(_f)
+
+
+def _load(name):
+    with gzip.open(os.path.join(ROOT, 'tests', 'golden', name), 'rt') as f:
+        return json.load(f)
+
+
+G = _load('blot_multi.json.gz')
+GW = _load('blot_multi_wide.json.gz')      # N = 7 and 9 .. 16 (tests/golden/make_blot_multi_wide_golden.py)
 
 
 def seq(xs):
@@ -36,7 +43,15 @@ def _segs(got):
 @pytest.mark.parametrize('ci,cls', [(ci, 'Fast') for ci in range(len(G['cases']))] +
                          [(ci, 'table') for ci, r in enumerate(G['cases']) if len(r['seqs']) > 2])
 def test_gpu_equals_the_reference_fixture(ci, cls):
-    rec = G['cases'][ci]
+    _equals_the_fixture(G['cases'][ci], cls)
+
+
+@pytest.mark.parametrize('ci,cls', [(ci, cls) for ci in range(len(GW['cases'])) for cls in ('Fast', 'table')])
+def test_gpu_equals_the_reference_fixture_beyond_six_sequences(ci, cls):
+    _equals_the_fixture(GW['cases'][ci], cls)
+
+
+def _equals_the_fixture(rec, cls):
     seqs = [A.parse(s) for s in rec['seqs']]
     kw = dict(wordlen=rec['wordlen'], alphabet=A, g_max=float.fromhex(rec['g_max']),
               sensitivity=float.fromhex(rec['sensitivity']))
