@@ -428,11 +428,12 @@ class _QIndex(object):
 
     def graph_fetch(self):
         """CSR adjacency: (offsets[rows + 1], neighbours[edges])."""
-        off = np.zeros(self.num_rows() + 1, np.int64)
-        adj = np.zeros(max(self._edges, 1), np.int32)
+        edges = self._edges or 0                     # (None before a graph_build: the library refuses the call below)
+        off = np.zeros(max(self.num_rows(), 0) + 1, np.int64)
+        adj = np.zeros(max(edges, 1), np.int32)
         if self.lib.pw_qseeds_graph_fetch(self.handle, off.ctypes.data, adj.ctypes.data) != 0:
             raise RuntimeError('pw_qseeds_graph_fetch failed: ' + self.error())
-        return off, adj[:self._edges]
+        return off, adj[:edges]
 
     def graph_components(self, avail):
         n = self.num_rows()

@@ -175,6 +175,24 @@ def test_seed_and_overlap_entry_points_reject_bad_input_loudly():
         _expect_refusal(lib, 'seeds', lambda: call(lib), msg, 'NULL index: ' + name)
 
 
+def test_qseeds_refusals_before_any_device_call():
+    """The query-batched index (include/pw_qseeds.h): every entry point on a NULL index, and every argument check of
+    pw_qseeds_create that comes before the device is touched, each with its full message in pw_qseeds_last_error."""
+    lib = W.load()
+    for name, call, msg in _NULL_QINDEX_REFUSALS:
+        _expect_refusal(lib, 'qseeds', lambda: call(lib), msg, 'NULL index: ' + name)
+    for name, (ref, n_ref, L, k), msg in _QSEED_CREATE_REFUSALS:
+        arr = None if ref is None else _arr(ref, C.c_uint8)
+        n = len(ref) if n_ref is None else n_ref
+        _expect_refusal(lib, 'qseeds', lambda: lib.pw_qseeds_create(0, arr, n, L, k), msg, 'pw_qseeds_create: ' + name)
+    # the accessors of a NULL index that report without an error message
+    assert lib.pw_qseeds_num_rows(None) == -1 and lib.pw_qseeds_num_queries(None) == -1
+    assert lib.pw_qseeds_rows_device(None) is None and lib.pw_qseeds_components_rounds(None) == -1
+    for ms in (lib.pw_qseeds_build_ms, lib.pw_qseeds_graph_ms, lib.pw_qseeds_components_ms, lib.pw_qseeds_count_ms):
+        assert ms(None) == -1.0
+    lib.pw_qseeds_destroy(None)
+
+
 def test_seed_and_overlap_refusals_come_in_order():
     """With the faults of several checks at once, the first check in the library's order reports: fault i is combined
     with every later fault of the list."""
@@ -283,6 +301,35 @@ _NULL_INDEX_REFUSALS = [  # (name, call on a NULL index, message)
      b'pw_seeds_graph_components before a successful pw_seeds_graph_build'),
 ]
 
+_NULL_QINDEX_REFUSALS = [  # the same for pw_qseeds_*: (name, call on a NULL index, message)
+    ('build', lambda lib: lib.pw_qseeds_build(None, None, 0, 0, None, None, 0, 0, None), b'null index'),
+    ('rows', lambda lib: lib.pw_qseeds_rows(None, None, 0), b'pw_qseeds_rows before a successful pw_qseeds_build'),
+    ('row_offsets', lambda lib: lib.pw_qseeds_row_offsets(None, None),
+     b'pw_qseeds_row_offsets before a successful pw_qseeds_build'),
+    ('count_boxes', lambda lib: lib.pw_qseeds_count_boxes(None, 0, None, None, None, None, None, None),
+     b'pw_qseeds_count_boxes before a successful pw_qseeds_build'),
+    ('graph_build', lambda lib: lib.pw_qseeds_graph_build(None, 1., 1.), b'pw_qseeds_graph_build before a successful pw_qseeds_build'),
+    ('graph_counts', lambda lib: lib.pw_qseeds_graph_counts(None, None, 0),
+     b'pw_qseeds_graph_counts before a successful pw_qseeds_graph_build'),
+    ('graph_fetch', lambda lib: lib.pw_qseeds_graph_fetch(None, None, None),
+     b'pw_qseeds_graph_fetch before a successful pw_qseeds_graph_build'),
+    ('graph_components', lambda lib: lib.pw_qseeds_graph_components(None, None, None),
+     b'pw_qseeds_graph_components before a successful pw_qseeds_graph_build'),
+]
+_QSEED_S = (0, 1, 2, 3, 0, 1, 2, 3, 1)
+_QSEED_CREATE_REFUSALS = [  # pw_qseeds_create, before any device call: (name, (ref, n_ref, L, k), message)
+    ('alphabet 0', (_QSEED_S, None, 0, 3), b'alphabet_len must be 1..36 (kmers.py:266)'),
+    ('alphabet 37', (_QSEED_S, None, 37, 3), b'alphabet_len must be 1..36 (kmers.py:266)'),
+    ('word 0', (_QSEED_S, None, 4, 0), b'wordlen must be 1..31 (kmers.py:269)'),
+    ('word 32', (_QSEED_S, None, 4, 32), b'wordlen must be 1..31 (kmers.py:269)'),
+    ('L^k = 2^62', (_QSEED_S, None, 4, 31), b'alphabet_len ^ wordlen must be below 2^62'),
+    ('36^12', (_QSEED_S, None, 36, 12), b'alphabet_len ^ wordlen must be below 2^62'),
+    ('n_ref < 0', (_QSEED_S, -1, 4, 3), b'reference length out of range (below 2^31)'),
+    ('n_ref = 2^31', (_QSEED_S, 1 << 31, 4, 3), b'reference length out of range (below 2^31)'),
+    ('NULL reference', (None, 5, 4, 3), b'null reference pointer'),
+    ('letter in the reference', (_QSEED_S[:-1] + (4,), None, 4, 3), b'letter outside the alphabet in the reference'),
+]
+
 
 def _arr(v, t):
     return (t * max(len(v), 1))(*v)
@@ -316,8 +363,13 @@ def _all_pairs_args(over):
 def _expect_refusal(lib, api, call, msg, name):
     """call() fails (NULL or -1) and leaves exactly `msg` in its API's error channel.  The channel holds another
     message before the call, so a stale one cannot pass."""
-    last = {'seeds': lib.pw_seeds_last_error, 'overlap': lib.pw_overlap_last_error, 'batch': lib.pw_last_error}[api]
-    if api == 'seeds':
+    last = {'seeds': lib.pw_seeds_last_error, 'qseeds': lib.pw_qseeds_last_error, 'overlap': lib.pw_overlap_last_error,
+            'batch': lib.pw_last_error}[api]
+    if api == 'qseeds':
+        lib.pw_qseeds_build(None, None, 0, 0, None, None, 0, 0, None)
+        if last() == msg:
+            lib.pw_qseeds_rows(None, None, 0)
+    elif api == 'seeds':
         lib.pw_seeds_build(None, 0, None)
         if last() == msg:
             lib.pw_seeds_rows(None, None, 0)

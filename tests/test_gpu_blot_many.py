@@ -217,10 +217,15 @@ def test_graph_is_the_oracles_per_query():
     goff, adj = qi.graph_fetch()
     counts = qi.graph_counts()
     assert goff[-1] == edges == counts.sum() and (np.diff(goff) == counts).all()
+    neighs = [None] * len(rows)
     for q in range(len(queries)):
         pts = [(int(d), int(a)) for _, d, a in rows[roff[q]:roff[q + 1]]]
         for k, (_, ns) in enumerate(BO.find_all_neighbors(pts, d_radius, a_radius)):
             o = roff[q] + k
-            assert sorted(adj[goff[o]:goff[o + 1]].tolist()) == sorted(int(roff[q]) + v for v in ns), (q, k)
+            neighs[o] = sorted(int(roff[q]) + v for v in ns)
+            assert sorted(adj[goff[o]:goff[o + 1]].tolist()) == neighs[o], (q, k)
     assert edges > 0
+    # ... and the components of that graph, every row available and a random half of them
+    for avail in (np.ones(len(rows), bool), np.random.default_rng(15).random(len(rows)) < .5):
+        assert np.array_equal(qi.graph_components(avail), Cs.components(neighs, avail.tolist()))
     qi.close()
