@@ -1,5 +1,5 @@
 """ctypes binding of biseqt_amd/pwlib/pwlib.so (the HIP library; C ABI in include/pwlib.h,
-include/pw_batch.h and the seed headers include/pw_seeds.h, pw_mseeds.h, pw_qseeds.h, pw_overlap.h).
+include/pw_batch.h, include/pw_txsum.h and the seed headers include/pw_seeds.h, pw_mseeds.h, pw_qseeds.h, pw_overlap.h).
 
 The reference binds its C library with cffi in ABI mode (``biseqt/pw.py:45-69``); cffi is not
 available in this image, so the same structs are declared with ctypes -- field for field the layout of
@@ -101,6 +101,13 @@ class pw_result(C.Structure):
                 ('tx_len', C.c_int32), ('status', C.c_int32)]
 
 
+# ---- alignment summaries (include/pw_txsum.h) ----
+class pw_tx_summary(C.Structure):
+    _fields_ = [(f, C.c_int32) for f in ('n_match', 'n_subst', 'n_ins', 'n_del', 'n_gaps', 'first_match', 'last_match',
+                                         'head_origin', 'head_mutant', 'tail_origin', 'tail_mutant', 'flags')]
+
+
+PW_TXSUM_DONE = 1
 PW_ST_TRACED, PW_ST_EMPTY, PW_ST_PANICK, PW_ST_BADPATH = 1, 2, 4, 8
 PW_FLAG_DUMP_SCORES, PW_FLAG_FORCE_F64, PW_FLAG_FORCE_GENERIC, PW_FLAG_PROFILE = 1, 2, 4, 8
 PW_FLAG_NO_PACKED16 = 16
@@ -111,7 +118,7 @@ PW_FLAG_NO_STRIP = 256
 
 SIZEOF = dict(intpair=8, alnscores=24, alnframe=32, std_alnparams=4, banded_alnparams=12,
               alnprob=32, alnchoice=32, dpcell=16, dptable=32, alignment=24,
-              pw_scoring=40, pw_pair=32, pw_result=32)
+              pw_scoring=40, pw_pair=32, pw_result=32, pw_tx_summary=48)
 
 # every symbol include/pwlib.h and include/pw_batch.h declare
 EXPORTS = ['dptable_init', 'dptable_solve', 'dptable_traceback', 'dptable_free',
@@ -125,6 +132,9 @@ EXPORTS = ['dptable_init', 'dptable_solve', 'dptable_traceback', 'dptable_free',
            'pw_batch_results', 'pw_batch_transcripts', 'pw_batch_scores', 'pw_batch_masks', 'pw_batch_table', 'pw_batch_fill_ms',
            'pw_batch_trace_ms', 'pw_batch_pack_transcripts', 'pw_batch_packed_device', 'pw_batch_packed_offsets_device',
            'pw_batch_packed_total_async', 'pw_batch_packed', 'pw_plan_only']
+# every symbol include/pw_txsum.h declares
+TXSUM_EXPORTS = ['pw_batch_summarize', 'pw_batch_summaries_device', 'pw_batch_summaries_async', 'pw_batch_summaries',
+                 'pw_tx_summarize_packed']
 # every symbol include/pw_seeds.h declares
 SEED_EXPORTS = ['pw_seeds_create', 'pw_seeds_build', 'pw_seeds_num_rows', 'pw_seeds_is_self', 'pw_seeds_rows_device',
                 'pw_seeds_rows', 'pw_seeds_count', 'pw_seeds_kmers', 'pw_seeds_band_neighbours', 'pw_seeds_graph_build', 'pw_seeds_graph_num_points', 'pw_seeds_graph_points',
@@ -281,6 +291,13 @@ def load():
     lib.pw_batch_packed_total_async.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     lib.pw_batch_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
     lib.pw_plan_only.argtypes = [P(pw_scoring), C.c_int32, P(pw_pair), C.c_uint64, C.c_uint32, C.c_char_p, C.c_int32, P(C.c_int32)]
+    # include/pw_txsum.h
+    lib.pw_batch_summarize.argtypes = [C.c_void_p, C.c_void_p]
+    lib.pw_batch_summaries_device.argtypes = [C.c_void_p]
+    lib.pw_batch_summaries_device.restype = C.c_void_p
+    lib.pw_batch_summaries_async.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.pw_batch_summaries.argtypes = [C.c_void_p, C.c_void_p]
+    lib.pw_tx_summarize_packed.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     # include/pw_seeds.h
     lib.pw_seeds_create.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int,
                                     P(C.c_uint64), C.c_int, C.c_int]

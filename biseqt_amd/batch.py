@@ -17,6 +17,10 @@ RESULT_DTYPE = np.dtype([('score', '<f8'), ('opt_i', '<i4'), ('opt_j', '<i4'),
                          ('origin_idx', '<i4'), ('mutant_idx', '<i4'),
                          ('tx_len', '<i4'), ('status', '<i4')])
 assert RESULT_DTYPE.itemsize == 32
+# pw_tx_summary of include/pw_txsum.h: what a transcript holds, reduced on the device
+SUMMARY_DTYPE = np.dtype([(f, '<i4') for f in ('n_match', 'n_subst', 'n_ins', 'n_del', 'n_gaps', 'first_match', 'last_match',
+                                               'head_origin', 'head_mutant', 'tail_origin', 'tail_mutant', 'flags')])
+assert SUMMARY_DTYPE.itemsize == 48
 
 
 def _as_u8(seq):
@@ -443,6 +447,30 @@ class BatchAligner(object):
         return [raw[offsets[k]:offsets[k + 1]].decode('ascii') if offsets[k + 1] > offsets[k] else None
                 for k in range(len(offsets) - 1)]
 
+    # ---- alignment summaries (include/pw_txsum.h): the transcripts reduced where they are ----
+    def summarize(self, stream=None):
+        """After a traceback on ``stream``: one :data:`SUMMARY_DTYPE` record per pair -- op counts, gap runs, first / last
+        match and the letters in front of and behind them -- reduced from the ops on the device (``pw_batch_summarize``).
+        Asynchronous on ``stream``.  The records describe the traceback in front of the call: after another traceback
+        they are stale until ``summarize`` runs again (:meth:`summaries` does that itself)."""
+        self._ck(self.lib.pw_batch_summarize(self.handle, stream), 'pw_batch_summarize')
+
+    def summaries(self):
+        """Structured array (SUMMARY_DTYPE), one record per pair (synchronous D2H; runs the kernel first when a traceback
+        has happened since the last :meth:`summarize`).  ``flags`` is 0, both match indices -1 and every count 0 for a
+        pair without a transcript."""
+        out = np.zeros(max(self.n, 1), SUMMARY_DTYPE)
+        self._ck(self.lib.pw_batch_summaries(self.handle, out.ctypes.data), 'pw_batch_summaries')
+        return out[:self.n]
+
+    def summaries_async(self, pinned, stream=None):
+        """D2H of the 48-byte summaries into a :class:`PinnedArray` (``48 * n`` bytes), asynchronous on ``stream``, behind a
+        :meth:`summarize` on it."""
+        self._ck(self.lib.pw_batch_summaries_async(self.handle, pinned.ptr, stream), 'pw_batch_summaries_async')
+
+    def summaries_device(self):
+        return DeviceBuffer(self.lib.pw_batch_summaries_device(self.handle), 48 * self.n, self)
+
     def scores_plane(self, k):
         """Score of every cell of pair k as ``plane[d - dmin, a]`` (needs PW_FLAG_DUMP_SCORES)."""
         X, Y = self.lens[k]
@@ -481,6 +509,32 @@ def align_batch(pairs, **kw):
     with BatchAligner(pairs, **kw) as b:
         res = b.run()
         return res, b.transcripts(res)
+
+
+def summary_dict(rec):
+    """One SUMMARY_DTYPE record as a dict of Python ints."""
+    return {f: int(rec[f]) for f in SUMMARY_DTYPE.names}
+
+
+def summarize_transcripts(transcripts, device=0):
+    """Summaries (SUMMARY_DTYPE, one record per transcript) of transcripts that are not in a batch's slots, through the
+    same device routine (``pw_tx_summarize_packed``): ``transcripts`` is a list of ``str`` / ``None``, or ``(buf, offsets)``
+    as :meth:`BatchAligner.packed` returns them.  ``None`` and ``''`` get the record of a pair without a transcript."""
+    if isinstance(transcripts, tuple) and len(transcripts) == 2 and isinstance(transcripts[0], np.ndarray):
+        buf = np.ascontiguousarray(transcripts[0], np.uint8)
+        off = np.ascontiguousarray(transcripts[1], np.uint64)
+        assert off.ndim == 1 and off.size >= 1 and int(off[-1]) <= buf.size
+    else:
+        raw = [(t or '').encode('ascii') for t in transcripts]
+        off = np.zeros(len(raw) + 1, np.uint64)
+        if raw:
+            off[1:] = np.cumsum([len(r) for r in raw])
+        buf = np.frombuffer(b''.join(raw), np.uint8)
+    n = off.size - 1
+    out = np.zeros(max(n, 1), SUMMARY_DTYPE)
+    if W.load().pw_tx_summarize_packed(device, buf.ctypes.data if buf.size else None, off.ctypes.data, n, out.ctypes.data) != 0:
+        raise RuntimeError('pw_tx_summarize_packed failed: ' + W.last_error())
+    return out[:n]
 
 
 def plan_only(shapes, alnmode=W.STD_MODE, alntype=W.GLOBAL, alphabet_len=4, subst_scores=None, match_score=1, mismatch_score=0,

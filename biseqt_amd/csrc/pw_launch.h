@@ -28,6 +28,10 @@ hipError_t launch_trace(const TraceParams& p, hipStream_t st);
 // compaction of the transcripts: offsets[n + 1] = exclusive prefix sum of tx_len, packed = the ops back to back
 hipError_t launch_tx_pack(const PairDesc* pairs, const Result* results, const uint8_t* slots, int n, uint64_t* offsets,
                           uint8_t* packed, hipStream_t st);
+// alignment summaries (pw_txsum.hip; `out` is pw_tx_summary[n] of include/pw_txsum.h): one wavefront per transcript, over
+// the slots of a batch or over a packed buffer and its offsets[n + 1]
+hipError_t launch_tx_summary(const PairDesc* pairs, const Result* results, const uint8_t* slots, int n, void* out, hipStream_t st);
+hipError_t launch_tx_summary_packed(const uint8_t* ops, const uint64_t* offsets, int n, void* out, hipStream_t st);
 // strip pipeline (pw_strip.h / pw_strip.hip): one standard-mode pair wider than a workgroup
 struct StripParams;
 struct StripTraceParams;

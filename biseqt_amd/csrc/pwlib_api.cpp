@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../../include/pw_batch.h"
+#include "../../include/pw_txsum.h"
 #include "pw_launch.h"
 #include "pw_plan.h"
 #include "pw_model.h"
@@ -219,6 +220,8 @@ struct pw_batch {
   DeviceBuffer d_ends;                   // int32_t[n][2]: pw_batch_traceback_from
   PoolBuffer<uint8_t> d_txpacked;        // pw_batch_pack_transcripts: the ops back to back
   DeviceBuffer d_txoffsets;              // uint64_t[n + 1]
+  PoolBuffer<pw_tx_summary> d_summaries; // pw_batch_summarize: allocated on its first call
+  uint64_t trace_seq = 0, summary_seq = 0;   // tracebacks so far / the one the summaries were taken after
   DeviceEvent ev_fill0, ev_fill1, ev_tr0, ev_tr1;
   bool fill_timed = false, trace_timed = false;
   // scores as the caller gave them (batch_plan may scale b->subst / go / ge by a power of two)
@@ -875,7 +878,7 @@ static int repair_strip_pair(pw_batch* b, int32_t k) {
   if (!sub->strips.empty()) return fail("internal: the replacement of a strip pair took the strips again");
   if (pw_batch_share_arena(sub, b->d_arena) != 0 || pw_batch_solve(sub, nullptr) != 0) return -1;
   b->repaired.emplace_back(k, std::move(owned));
-  if (b->traced) { if (replay_trace(b, k, sub, nullptr) != 0) return -1; }
+  if (b->traced) { b->trace_seq++; if (replay_trace(b, k, sub, nullptr) != 0) return -1; }
   else HIP_TRY(hipMemcpyAsync(b->d_results.p + k, sub->d_results.p, sizeof(pw::Result), hipMemcpyDeviceToDevice, nullptr));
   HIP_TRY(hipStreamSynchronize(nullptr));
   static const bool verbose = env_int("PWLIB_TIMING", 0) != 0;
@@ -895,6 +898,7 @@ static int do_trace(pw_batch* b, const int32_t* d_ends, hipStream_t st) {
     for (int32_t k : b->strips) longest = std::max<int64_t>(longest, b->descs[k].tx_cap);
     p.fix_segments = (int32_t)std::min<int64_t>(256, std::max<int64_t>(1, longest / 2048));
   }
+  b->trace_seq++;                      // (summaries taken before this traceback are stale: pw_txsum.h)
   if (b->flags & PW_FLAG_PROFILE) HIP_TRY(hipEventRecord(b->ev_tr0.e, st));
   for (int32_t k : b->strips) {        // strip-layout pairs: one wavefront each (before the fix-up pass below)
     if (repaired_sub(b, k)) continue;  // (its mask plane is that of an abandoned fill: the replacement walks its own)
@@ -1007,6 +1011,52 @@ int pw_batch_packed(pw_batch* b, uint8_t* out, uint64_t cap, uint64_t* offsets_o
     if (off[b->n] > cap) return fail("packed transcripts: buffer too small");
     if (off[b->n]) HIP_TRY(hipMemcpy(out, b->d_txpacked.p, off[b->n], hipMemcpyDeviceToHost));
   }
+  return 0;
+}
+
+// ---- alignment summaries (include/pw_txsum.h; kernel in pw_txsum.hip) ----
+int pw_batch_summarize(pw_batch* b, void* stream) {
+  if (!b->traced) return fail("pw_batch_summarize before a traceback of the batch");
+  HIP_TRY(hipSetDevice(b->device));
+  if (!b->d_summaries.p) HIP_TRY(b->d_summaries.alloc(b->device, sizeof(pw_tx_summary) * (size_t)std::max<int32_t>(b->n, 1)));
+  HIP_TRY(pw::launch_tx_summary(b->d_pairs.p, b->d_results.p, b->d_tx.p, b->n, b->d_summaries.p, (hipStream_t)stream));
+  b->summary_seq = b->trace_seq;
+  return mark_done(b, (hipStream_t)stream);
+}
+void* pw_batch_summaries_device(pw_batch* b) { return b->d_summaries.p; }
+int pw_batch_summaries_async(pw_batch* b, pw_tx_summary* out, void* stream) {
+  if (!b->d_summaries.p) return fail("pw_batch_summaries_async before pw_batch_summarize");
+  HIP_TRY(hipSetDevice(b->device));
+  if (b->n) HIP_TRY(hipMemcpyAsync(out, b->d_summaries.p, sizeof(pw_tx_summary) * (size_t)b->n, hipMemcpyDeviceToHost, (hipStream_t)stream));
+  return mark_done(b, (hipStream_t)stream);
+}
+int pw_batch_summaries(pw_batch* b, pw_tx_summary* out) {
+  if (!b->traced) return fail("pw_batch_summaries before a traceback of the batch");
+  // (as for pw_batch_results: callers that launched on another stream synchronise it first)
+  if ((!b->d_summaries.p || b->summary_seq != b->trace_seq) && pw_batch_summarize(b, nullptr) != 0) return -1;
+  HIP_TRY(hipSetDevice(b->device));
+  if (b->n) HIP_TRY(hipMemcpy(out, b->d_summaries.p, sizeof(pw_tx_summary) * (size_t)b->n, hipMemcpyDeviceToHost));
+  return 0;
+}
+int pw_tx_summarize_packed(int device, const uint8_t* ops, const uint64_t* offsets, int64_t n, pw_tx_summary* out) {
+  if (n < 0 || n > INT32_MAX) return fail("pw_tx_summarize_packed: transcript count out of range");
+  if (n == 0) return 0;
+  if (!offsets || !out) return fail("pw_tx_summarize_packed: null offsets or output");
+  for (int64_t k = 0; k < n; k++) {
+    if (offsets[k + 1] < offsets[k]) return fail("pw_tx_summarize_packed: offsets must ascend");
+    if (offsets[k + 1] - offsets[k] > (uint64_t)INT32_MAX) return fail("pw_tx_summarize_packed: a transcript of 2^31 ops or more");
+  }
+  const uint64_t total = offsets[n];
+  if (total && !ops) return fail("pw_tx_summarize_packed: null ops with a non-zero total");
+  HIP_TRY(hipSetDevice(device));
+  DeviceBuffer d_ops, d_off, d_out;
+  HIP_TRY(d_ops.ensure((size_t)total));
+  HIP_TRY(d_off.ensure(8 * ((size_t)n + 1)));
+  HIP_TRY(d_out.ensure(sizeof(pw_tx_summary) * (size_t)n));
+  if (total) HIP_TRY(hipMemcpy(d_ops.p, ops, (size_t)total, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_off.p, offsets, 8 * ((size_t)n + 1), hipMemcpyHostToDevice));
+  HIP_TRY(pw::launch_tx_summary_packed((const uint8_t*)d_ops.p, (const uint64_t*)d_off.p, (int)n, d_out.p, nullptr));
+  HIP_TRY(hipMemcpy(out, d_out.p, sizeof(pw_tx_summary) * (size_t)n, hipMemcpyDeviceToHost));
   return 0;
 }
 

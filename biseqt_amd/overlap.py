@@ -331,7 +331,7 @@ def aligned_batches(arena, offs, lens, pidx, dr, alphabet_len, device=0, max_cel
 
 
 def overlap_alignments(reads, pairs, bands, alphabet, p_min=0., device=0, max_cells=2 * 10 ** 10, want_transcripts=True,
-                       strands=None, complement=None, **aligner_kw):
+                       strands=None, complement=None, want_summaries=False, **aligner_kw):
     """Banded overlap alignment (``B_OVERLAP``) of every pair whose band has ``p >= p_min``; the ``diag_range`` is the
     band clamped to the table as ``Aligner`` requires (``pw.py:224-226``).  All reads are uploaded ONCE and the pairs
     refer to them (``BatchAligner.from_arena``); the pairs are solved in batches of at most ``max_cells`` cells
@@ -339,8 +339,10 @@ def overlap_alignments(reads, pairs, bands, alphabet, p_min=0., device=0, max_ce
     Returns a list with one entry per pair: None, or dict(score, transcript, origin_start, mutant_start,
     diag_range).  With ``strands`` (one ``'+'`` / ``'-'`` per pair; ``complement`` as in :func:`overlap_bands`) the mutant
     of a minus pair is the reverse complement of ``reads[j]``, ``mutant_start`` and the transcript are in its frame
-    (:func:`minus_to_forward`), and every dict also reports its ``strand``."""
-    from .batch import pack_reads
+    (:func:`minus_to_forward`), and every dict also reports its ``strand``.  With ``want_summaries`` every dict gains
+    ``summary``: the op counts, gap runs and match bounds of its transcript (the fields of ``batch.SUMMARY_DTYPE``, in the
+    transcript's own frame), reduced on the device -- with or without ``want_transcripts``."""
+    from .batch import pack_reads, summary_dict
     arena, offs, lens = pack_reads(reads)
     sflags = _strand_flags(strands, len(pairs))
     comp = _complement(complement, len(alphabet), alphabet) if sflags is not None and sflags.any() else None
@@ -365,6 +367,7 @@ def overlap_alignments(reads, pairs, bands, alphabet, p_min=0., device=0, max_ce
                                           strands=sub, complement=comp, **kw):
         res = b.results()
         txs = b.transcripts(res) if want_transcripts else [None] * (stop - start)
+        sums = b.summaries() if want_summaries else None
         for k in range(stop - start):
             if res['opt_i'][k] < 0:
                 continue
@@ -372,6 +375,8 @@ def overlap_alignments(reads, pairs, bands, alphabet, p_min=0., device=0, max_ce
                                        mutant_start=int(res['mutant_idx'][k]), diag_range=(int(dr[start + k, 0]), int(dr[start + k, 1])))
             if sub is not None:
                 out[sel[start + k]]['strand'] = '-' if sub[start + k] else '+'
+            if sums is not None:
+                out[sel[start + k]]['summary'] = summary_dict(sums[k])
     return out
 
 

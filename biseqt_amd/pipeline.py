@@ -11,7 +11,7 @@ the reference's, statement by statement.  ``map_queries`` is the many-queries-on
 import numpy as np
 
 from . import _pwlib as W
-from .batch import BatchAligner, DeviceArena, pack_reads
+from .batch import BatchAligner, DeviceArena, pack_reads, summary_dict
 from .blot import WordBlot, WordBlotLocalRef
 from .pw import Alignment
 from .sequence import Sequence
@@ -33,13 +33,31 @@ def segment_frame(seg, lenS, lenT, wordlen):
     return (i_start, i_end), (j_start, j_end), rad
 
 
-def extend_segments(S, T, segments, wordlen, device=0, **aligner_kw):
+def truncated_frame(origin_start, mutant_start, summary):
+    """``((origin_start, origin_end), (mutant_start, mutant_end))`` of the sub-alignment between the first and the last
+    ``M`` of a transcript, from its summary record and the alignment's starts -- the starts of
+    ``Alignment.truncate_to_match()`` and the letters its transcript consumes -- or None where ``truncate_to_match`` returns
+    None (at most one ``M``) or fails (no ``M``, no transcript)."""
+    if not summary['flags'] & 1 or summary['first_match'] < 0 or summary['first_match'] >= summary['last_match']:
+        return None
+    o0, m0 = origin_start + summary['head_origin'], mutant_start + summary['head_mutant']
+    on_origin = summary['n_match'] + summary['n_subst'] + summary['n_del'] - summary['head_origin'] - summary['tail_origin']
+    on_mutant = summary['n_match'] + summary['n_subst'] + summary['n_ins'] - summary['head_mutant'] - summary['tail_mutant']
+    return (o0, o0 + on_origin), (m0, m0 + on_mutant)
+
+
+def extend_segments(S, T, segments, wordlen, device=0, alignments=True, **aligner_kw):
     """Banded alignment of the frames of all ``segments`` (dicts with a ``segment`` key, as
     ``WordBlot.similar_segments`` yields them) in one GPU batch.  ``aligner_kw`` are ``Aligner`` keywords
     (``alnmode`` / ``alntype`` default to banded global as in the reference's experiment; ``diag_range`` is set
     per segment).  Returns one dict per segment: ``frame``, ``diag_range``, ``score``, ``alignment`` (an
     :class:`Alignment` on the frame sequences, or None), ``truncated`` (``alignment.truncate_to_match()``) and ``kernel``
-    (the batch's fill kernel and score type, for diagnostics)."""
+    (the batch's fill kernel and score type, for diagnostics).
+
+    With ``alignments=False`` no transcript leaves the device: ``alignment`` and ``truncated`` are None and every dict has
+    ``summary`` (the fields of ``batch.SUMMARY_DTYPE``, None without an alignment) and ``truncated_frame``, the frame
+    coordinates ``((origin_start, origin_end), (mutant_start, mutant_end))`` of what ``truncated`` would cover
+    (:func:`truncated_frame`), both from the summaries the device reduces from the ops."""
     assert isinstance(S, Sequence) and isinstance(T, Sequence)
     kw = dict(alnmode=W.BANDED_MODE, alntype=W.B_GLOBAL)
     kw.update(aligner_kw)
@@ -55,13 +73,22 @@ def extend_segments(S, T, segments, wordlen, device=0, **aligner_kw):
         return []
     kw.pop('diag_range', None)
     with BatchAligner(pairs, alphabet_len=len(S.alphabet), diag_range=bands, device=device, **kw) as b:
-        res = b.run()
-        txs = b.transcripts(res)
+        if alignments:
+            res = b.run()
+            txs = b.transcripts(res)
+        else:
+            res, sums = _run_summarized(b)
         kernel = (b.kernel_name, b.score_dtype)
     out = []
     for k, (fi, fj) in enumerate(frames):
         rec = {'frame': (fi, fj), 'diag_range': bands[k], 'score': None, 'alignment': None, 'truncated': None, 'kernel': kernel}
-        if res['opt_i'][k] >= 0 and txs[k]:
+        if not alignments:
+            rec['summary'] = rec['truncated_frame'] = None
+            if res['opt_i'][k] >= 0 and res['tx_len'][k] > 0:
+                rec['score'] = float(res['score'][k])
+                rec['summary'] = summary_dict(sums[k])
+                rec['truncated_frame'] = truncated_frame(int(res['origin_idx'][k]), int(res['mutant_idx'][k]), rec['summary'])
+        elif res['opt_i'][k] >= 0 and txs[k]:
             rec['score'] = float(res['score'][k])
             aln = Alignment(S[fi[0]:fi[1]], T[fj[0]:fj[1]], txs[k], score=rec['score'],
                             origin_start=int(res['origin_idx'][k]), mutant_start=int(res['mutant_idx'][k]))
@@ -71,7 +98,17 @@ def extend_segments(S, T, segments, wordlen, device=0, **aligner_kw):
     return out
 
 
-def map_queries(ref, queries, K_min, p_min, wordlen, g_max, sensitivity, keep=3, device=0, aligner_kw=None):
+def _run_summarized(b):
+    """solve -> traceback -> summarize on one batch: the 32-byte records and the 48-byte summaries, no transcript."""
+    b.solve()
+    b.traceback()
+    b.summarize()
+    b.sync()
+    res = b.results()
+    return res, b.summaries()
+
+
+def map_queries(ref, queries, K_min, p_min, wordlen, g_max, sensitivity, keep=3, device=0, aligner_kw=None, alignments=True):
     """Map many short queries onto one reference sequence: Word-Blot local similarities of all queries in one pass
     (:meth:`WordBlotLocalRef.similar_segments_many`), then a banded local alignment of the best segments of every query,
     all in ONE lane-packed batch.  The flow of ``experiments/blot_ig_genotyping.py:45-101`` as a library function: per
@@ -81,7 +118,12 @@ def map_queries(ref, queries, K_min, p_min, wordlen, g_max, sensitivity, keep=3,
 
     Returns one list per query, best segment first, of dicts: ``segment``, ``p``, ``diag_range``, ``score``,
     ``alignment`` (an :class:`Alignment` on ``ref`` and the query, or None where the batch reports no alignment),
-    ``p_aln`` (matches over the letters of the query the alignment covers, rounded to 2 places) and ``len_aln`` (:93-98)."""
+    ``p_aln`` (matches over the letters of the query the alignment covers, rounded to 2 places) and ``len_aln`` (:93-98).
+
+    With ``alignments=False`` only the 32-byte records and the 48-byte summaries of the batch come to the host -- no
+    transcript is downloaded or decoded: ``alignment`` is None, ``p_aln`` and ``len_aln`` come from the op counts, and every
+    dict also has ``origin_start``, ``mutant_start`` (those of the :class:`Alignment`) and ``summary`` (the fields of
+    ``batch.SUMMARY_DTYPE``; None where there is no alignment)."""
     assert isinstance(ref, Sequence) and all(isinstance(T, Sequence) for T in queries)
     queries = list(queries)
     kw = dict(match_score=1, mismatch_score=-3, go_score=-5, ge_score=-2)
@@ -103,6 +145,8 @@ def map_queries(ref, queries, K_min, p_min, wordlen, g_max, sensitivity, keep=3,
                 d_band = rec['segment'][0]
                 rec = dict(segment=rec['segment'], p=rec['p'], diag_range=(int(d_band[0]), int(d_band[1])), score=None,
                            alignment=None, p_aln=None, len_aln=None)
+                if not alignments:
+                    rec.update(origin_start=None, mutant_start=None, summary=None)
                 out[q].append(rec)
                 pairs.append((0, 1 + q))
                 bands.append(rec['diag_range'])
@@ -110,12 +154,24 @@ def map_queries(ref, queries, K_min, p_min, wordlen, g_max, sensitivity, keep=3,
             return out
         with BatchAligner.from_arena(arena, offs, lens, pairs, diag_ranges=bands, device_arena=darena,
                                      alphabet_len=len(ref.alphabet), device=device, **kw) as b:
-            res = b.run()
-            txs = b.transcripts(res)
+            if alignments:
+                res = b.run()
+                txs = b.transcripts(res)
+            else:
+                res, sums = _run_summarized(b)
     k = 0
     for q, recs in enumerate(out):
         for rec in recs:
-            if res['opt_i'][k] >= 0 and txs[k]:
+            if not alignments:
+                if res['opt_i'][k] >= 0 and res['tx_len'][k] > 0:
+                    s = sums[k]
+                    rec['score'] = float(res['score'][k])
+                    rec['origin_start'], rec['mutant_start'] = int(res['origin_idx'][k]), int(res['mutant_idx'][k])
+                    len_on_query = int(s['n_match']) + int(s['n_subst']) + int(s['n_ins'])
+                    rec['p_aln'] = round(1. * int(s['n_match']) / len_on_query, 2) if len_on_query else None
+                    rec['len_aln'] = len_on_query
+                    rec['summary'] = summary_dict(s)
+            elif res['opt_i'][k] >= 0 and txs[k]:
                 tx = txs[k]
                 rec['score'] = float(res['score'][k])
                 rec['alignment'] = Alignment(ref, queries[q], tx, score=rec['score'], origin_start=int(res['origin_idx'][k]),
