@@ -149,7 +149,7 @@ MSEED_EXPORTS = ['pw_mseeds_create', 'pw_mseeds_build', 'pw_mseeds_num_seqs', 'p
                  'pw_mseeds_last_error']
 
 # every symbol include/pw_qseeds.h declares
-QSEED_EXPORTS = ['pw_qseeds_create', 'pw_qseeds_build', 'pw_qseeds_num_queries', 'pw_qseeds_num_rows', 'pw_qseeds_rows_device',
+QSEED_EXPORTS = ['pw_qseeds_create', 'pw_qseeds_build', 'pw_qseeds_build_stranded', 'pw_qseeds_num_queries', 'pw_qseeds_num_rows', 'pw_qseeds_rows_device',
                  'pw_qseeds_rows', 'pw_qseeds_row_offsets', 'pw_qseeds_count_boxes', 'pw_qseeds_graph_build',
                  'pw_qseeds_graph_counts', 'pw_qseeds_graph_fetch', 'pw_qseeds_graph_components', 'pw_qseeds_build_ms',
                  'pw_qseeds_graph_ms', 'pw_qseeds_components_ms', 'pw_qseeds_count_ms', 'pw_qseeds_components_rounds',
@@ -358,6 +358,8 @@ def load():
     lib.pw_qseeds_create.restype = C.c_void_p
     lib.pw_qseeds_build.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
                                     C.c_void_p]
+    lib.pw_qseeds_build_stranded.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]
     lib.pw_qseeds_num_queries.argtypes = [C.c_void_p]
     lib.pw_qseeds_num_queries.restype = C.c_int64
     lib.pw_qseeds_num_rows.argtypes = [C.c_void_p]

@@ -470,7 +470,7 @@ class WordBlotLocalRef(_RefMixin, WordBlot):
         self._set_query(seq)
         return WordBlot.similar_segments(self, K_min, p_min, at_least_one=at_least_one)
 
-    def similar_segments_many(self, queries, K_min, p_min, at_least_one=False, arena=None):
+    def similar_segments_many(self, queries, K_min, p_min, at_least_one=False, arena=None, strands='+', complement=None):
         """``[list(self.similar_segments(q, K_min, p_min, at_least_one)) for q in queries]`` -- same segments, order, p
         and scores -- out of one set of kernel launches for all queries (kernels K10 of pw_qseeds.hip) instead of one index
         per query: the reference sequence is encoded and sorted once per object, the queries' seeds come out in the order
@@ -479,12 +479,29 @@ class WordBlotLocalRef(_RefMixin, WordBlot):
 
         ``K_min`` and ``p_min`` are scalars for the whole call.  A query equal to the reference is a self comparison
         (``blot.py:612``) and goes through the per-query path.  ``arena``, optional: ``(device_arena, offsets, lengths)``
-        of a :class:`biseqt_amd.batch.DeviceArena` that already holds the queries, in order, to be read in place."""
+        of a :class:`biseqt_amd.batch.DeviceArena` that already holds the queries, in order, to be read in place.
+
+        ``strands``: ``'+'`` (the default: the queries as written), ``'-'`` or ``'both'``.  A query on the minus strand IS the
+        sequence ``T = rc(query)`` -- position ``j'`` of ``T`` is letter ``len - 1 - j'`` of the query, complemented, the
+        convention :mod:`biseqt_amd.overlap` documents -- and everything reported for it (segments, their diagonals and
+        antidiagonals) is in the frame of that ``T``: with ``'-'``, ``out[q]`` is
+        ``list(self.similar_segments(reverse_complement(queries[q], complement), K_min, p_min, at_least_one))``; with
+        ``'both'`` it is the plus list followed by the minus list, out of ONE build that lists every query on both strands.
+        Every dict then also has ``'strand'``.  ``at_least_one`` applies to each strand on its own.  The device forms the
+        minus strand's k-mers from the forward letters (with ``arena`` the caller's frames are read in place for both
+        strands); no reverse complement is materialised for seeding.  A listed entry whose letters equal the reference
+        after its own strand is applied -- a query equal to ``rc(ref)`` under ``'-'`` -- is a self comparison and goes
+        through the per-query path.  ``complement``: a table (:func:`biseqt_amd.sequence.complement_table`) or the
+        ``mappings`` of ``Alphabet.transform``; a missing or invalid one raises ``ValueError`` before any device call."""
         queries = list(queries)
         assert all(isinstance(T, Sequence) and T.alphabet == self.alphabet for T in queries), \
             'queries are Sequences over the index alphabet'
         assert np.ndim(K_min) == 0 and np.ndim(p_min) == 0, 'K_min and p_min are scalars for the whole call'
         assert K_min > 0, 'K_min must be positive'
+        if strands not in ('+', '-', 'both'):
+            raise ValueError("strands is '+', '-' or 'both', not %r" % (strands,))
+        if strands != '+':
+            return self._similar_segments_stranded(queries, K_min, p_min, at_least_one, arena, strands, complement)
         batched = [k for k, T in enumerate(queries) if not T == self.S]
         if at_least_one:                              # (a query shorter than a word has no seeds: known without the device)
             assert all(len(queries[k]) >= self.wordlen for k in batched), 'no seeds found while at_least_one=True'
@@ -497,25 +514,69 @@ class WordBlotLocalRef(_RefMixin, WordBlot):
                 offs, lens = np.asarray(offs, np.int64), np.asarray(lens, np.int64)
                 assert len(offs) == len(lens) == len(queries) and lens.tolist() == [len(T) for T in queries]
                 offs, lens = offs[batched], lens[batched]
-            if self._qidx is None:
-                self._qidx = _QIndex(self.S, self.wordlen, self.alphabet, device=self._ref_kw.get('device', 0))
-            qi = self._qidx
-            qi.build(letters, offs, lens, self._ref_kw.get('max_rows', 0))
-            row_offsets = qi.row_offsets()
-            d_radius, a_radius = int(np.ceil(self.band_radius(K_min))), K_min
-            L = len(self.alphabet)
-            qi.graph_build(1. * a_radius / d_radius, a_radius)
-            counts = qi.graph_counts()
-            p = seed_ps_from_counts(counts, d_radius, a_radius, L, self.wordlen)
-            avail = available_seeds_many(p, p_min, row_offsets, at_least_one)
-            labels = qi.graph_components(avail) if avail.any() else np.full(len(p), -1, np.int32)
-            segs = segments_from_arrays(counts, labels, qi.rows(), row_offsets, lens, len(self.S), d_radius, a_radius, L,
-                                        self.wordlen, qi.count_boxes)
-            for k, s in zip(batched, segs):
+            for k, s in zip(batched, self._batched_segments(letters, offs, lens, K_min, p_min, at_least_one)):
                 out[k] = s
         for k, T in enumerate(queries):
             if out[k] is None:                        # the reference itself: mirrored points, the per-query path
                 out[k] = list(self.similar_segments(T, K_min, p_min, at_least_one=at_least_one))
+        return out
+
+    def _batched_segments(self, letters, offs, lens, K_min, p_min, at_least_one, strands=None, comp=None):
+        """One list of segments per listed entry ``letters[offs[e]:offs[e] + lens[e]]`` (``strands``: one flag per entry, a
+        minus entry being the reverse complement of its letters), out of one build of the query-batched index."""
+        if self._qidx is None:
+            self._qidx = _QIndex(self.S, self.wordlen, self.alphabet, device=self._ref_kw.get('device', 0))
+        qi = self._qidx
+        qi.build(letters, offs, lens, self._ref_kw.get('max_rows', 0), strands=strands, complement=comp)
+        row_offsets = qi.row_offsets()
+        d_radius, a_radius = int(np.ceil(self.band_radius(K_min))), K_min
+        L = len(self.alphabet)
+        qi.graph_build(1. * a_radius / d_radius, a_radius)
+        counts = qi.graph_counts()
+        p = seed_ps_from_counts(counts, d_radius, a_radius, L, self.wordlen)
+        avail = available_seeds_many(p, p_min, row_offsets, at_least_one)
+        labels = qi.graph_components(avail) if avail.any() else np.full(len(p), -1, np.int32)
+        return segments_from_arrays(counts, labels, qi.rows(), row_offsets, lens, len(self.S), d_radius, a_radius, L,
+                                    self.wordlen, qi.count_boxes)
+
+    def _similar_segments_stranded(self, queries, K_min, p_min, at_least_one, arena, strands, complement):
+        """:meth:`similar_segments_many` for ``strands`` ``'-'`` / ``'both'``: every query is listed once per selected
+        strand (all plus entries, then all minus entries) over ONE copy of the forward letters."""
+        from .overlap import _complement
+        from .sequence import reverse_complement
+        comp = _complement(complement, len(self.alphabet), self.alphabet)         # (ValueError before any device call)
+        n = len(queries)
+        entries = [(k, f) for f in ((0, 1) if strands == 'both' else (1,)) for k in range(n)]
+        ref = self.S.as_array(np.uint8)
+        rc_ref = comp[ref[::-1]]                      # rc(T) == S  <=>  T == rc(S): no query is reversed to find out
+
+        def is_self(k, f):
+            return len(queries[k]) == len(ref) and bool((queries[k].as_array(np.uint8) == (rc_ref if f else ref)).all())
+        batched = [e for e in entries if not is_self(*e)]
+        if at_least_one:
+            assert all(len(queries[k]) >= self.wordlen for k, _ in batched), 'no seeds found while at_least_one=True'
+        if arena is None:
+            letters, offs, lens = pack_reads(queries)
+        else:
+            letters, offs, lens = arena
+            assert len(offs) == len(lens) == n and np.asarray(lens).tolist() == [len(T) for T in queries]
+        offs, lens = np.asarray(offs, np.int64), np.asarray(lens, np.int64)
+        found = {}
+        if batched:
+            qs = np.array([k for k, _ in batched], np.int64)
+            flags = np.array([f for _, f in batched], np.uint8)
+            found = dict(zip(batched, self._batched_segments(letters, offs[qs], lens[qs], K_min, p_min, at_least_one,
+                                                             strands=flags, comp=comp)))
+        out = [[] for _ in queries]
+        for k, f in entries:
+            if (k, f) in found:
+                segs = found[(k, f)]
+            else:                                     # the reference itself on this strand: the per-query path
+                T = reverse_complement(queries[k], comp) if f else queries[k]
+                segs = [dict(rec) for rec in self.similar_segments(T, K_min, p_min, at_least_one=at_least_one)]
+            for rec in segs:
+                rec['strand'] = '-' if f else '+'
+            out[k] += segs
         return out
 
     def batched_timings(self):

@@ -112,10 +112,11 @@ def _jobs():
                  [os.path.join(HERE, 'pw_mseeds.hip'), os.path.join(HERE, 'pw_seed_kernels.h'), os.path.join(ROOT, 'include', 'pw_mseeds.h')]))
     obj = os.path.join(OBJ_DIR, 'pw_qseeds.o')
     jobs.append((obj, [HIPCC] + COMMON + ['-Wno-unused-parameter', '-c', os.path.join(HERE, 'pw_qseeds.hip'), '-o', obj],
-                 [os.path.join(HERE, 'pw_qseeds.hip'), os.path.join(HERE, 'pw_seed_kernels.h'), os.path.join(ROOT, 'include', 'pw_qseeds.h')]))
+                 [os.path.join(HERE, 'pw_qseeds.hip'), os.path.join(HERE, 'pw_seed_kernels.h'), os.path.join(HERE, 'pw_complement.h'),
+                  os.path.join(ROOT, 'include', 'pw_qseeds.h')]))
     obj = os.path.join(OBJ_DIR, 'pw_overlap.o')
     jobs.append((obj, [HIPCC] + COMMON + ['-Wno-unused-parameter', '-c', os.path.join(HERE, 'pw_overlap.hip'), '-o', obj],
-                 [os.path.join(HERE, 'pw_overlap.hip'), os.path.join(ROOT, 'include', 'pw_overlap.h')]))
+                 [os.path.join(HERE, 'pw_overlap.hip'), os.path.join(HERE, 'pw_complement.h'), os.path.join(ROOT, 'include', 'pw_overlap.h')]))
     obj = os.path.join(OBJ_DIR, 'pwlib_api.o')
     jobs.append((obj, [HIPCC] + COMMON + ['-x', 'hip', '-c', os.path.join(HERE, 'pwlib_api.cpp'), '-o', obj],
                  [os.path.join(HERE, 'pwlib_api.cpp'), os.path.join(HERE, 'pw_model.h'), os.path.join(ROOT, 'include', 'pwlib.h'),

@@ -20,6 +20,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "../../include/pw_overlap.h"
+#include "pw_complement.h"
 #include "pw_hip_host.h"
 
 namespace {
@@ -47,11 +48,6 @@ __global__ __launch_bounds__(256) void k_enc_batch(const uint8_t* __restrict__ a
   pos[g] = q;
 }
 
-// The complement table of a call in LDS (alphabet_len <= 36 bytes), read by every thread of the block.
-__device__ __forceinline__ void load_complement(const uint8_t* __restrict__ comp, int L, uint8_t* s_comp) {
-  if ((int)threadIdx.x < 36) s_comp[threadIdx.x] = (int)threadIdx.x < L ? comp[threadIdx.x] : (uint8_t)0;
-  __syncthreads();
-}
 // K8a', stranded pair list: the T side where strand[p] != 0 encodes T = rc(read): the k-mer at position q of T is
 // comp(read[len - 1 - q]), comp(read[len - 2 - q]), ... -- read backwards from the forward letters, never materialised.
 // Entries are generated in ascending q, so the stable sort keeps positions of T ascending inside a k-mer.
@@ -864,14 +860,9 @@ int check_args(int L, int k, bool bad_args, double len_coeff, double radius_coef
   return 0;
 }
 
-// complement[c] for c < L: a permutation of the alphabet that is its own inverse
-int check_complement(const uint8_t* comp, int L) {
-  if (L < 1 || L > 36) return 0;                       // (check_args reports the alphabet)
-  bool ok = comp != nullptr;
-  for (int c = 0; ok && c < L; c++) ok = comp[c] < L && comp[comp[c]] == c;
-  if (!ok) { set_err("complement must be alphabet_len bytes with complement[complement[c]] == c for every letter"); return -1; }
-  return 0;
-}
+// the complement of a call (pw_complement.h), refusals into this API's error channel; an alphabet out of range passes here:
+// check_args reports it
+int check_complement(const uint8_t* comp, int L) { return ::check_complement(set_err, comp, L); }
 
 int upload_arena(int device, const uint8_t* arena, uint64_t arena_bytes, DeviceBuffer& d_arena) {
   CHECK(hipSetDevice(device));
@@ -880,14 +871,7 @@ int upload_arena(int device, const uint8_t* arena, uint64_t arena_bytes, DeviceB
   return 0;
 }
 
-// the complement table on the device (36 bytes, zero padded)
-int upload_complement(const uint8_t* comp, int L, DeviceBuffer& d_comp) {
-  uint8_t padded[36] = {0};
-  memcpy(padded, comp, (size_t)L);
-  CHECK(d_comp.ensure(sizeof padded));
-  CHECK(hipMemcpy(d_comp.p, padded, sizeof padded, hipMemcpyHostToDevice));
-  return 0;
-}
+int upload_complement(const uint8_t* comp, int L, DeviceBuffer& d_comp) { return ::upload_complement(set_err, comp, L, d_comp); }
 
 // both all-pairs entry points; stranded: pair_strand is required and the strand selection and the complement are checked
 // first (the complement only where the selection needs it), then everything in check_args' order

@@ -11,6 +11,10 @@
 //                     queries' first positions), its k-mer -- none when fewer than k letters are left IN THAT QUERY --
 //                     and that k-mer's run in the sorted reference (table, or two binary searches as K5b) -> rows it
 //                     contributes; a saturating exclusive scan -> row offsets
+//   K10a' k_qmatch_stranded  the same with a strand per listed query: a minus entry IS rc(query), and the thread at its
+//                     position j' forms the k-mer from the forward letters read backwards, complemented through a table in
+//                     LDS -- rc(query) is never materialised for seeding.  Everything behind K10a works on listed queries
+//                     and does not know about strands
 //   K10b k_qexpand    one thread per row (K5c's windowed search): (q, d, a) = (q, i - j, i + j).  Threads are in (q, j)
 //                     order and a run's positions ascend (the sort is stable), so rows come out in (q, j, i) order by
 //                     construction -- the order the in-memory classes list their seeds in -- with no sort of the queries
@@ -33,6 +37,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "../../include/pw_qseeds.h"
+#include "pw_complement.h"
 #include "pw_hip_host.h"
 #include "pw_seed_kernels.h"
 
@@ -90,6 +95,62 @@ __global__ __launch_bounds__(256) void k_qmatch(const uint8_t* __restrict__ aren
     }
   } else if (j < len) {                           // the tail of a query still holds letters: they are validated too
     if (arena[qoff[q] + j] >= (uint32_t)L) *bad = 1;
+  }
+  lo_out[t] = lo32;
+  cnt[t] = c;
+}
+// K10a', one strand per listed query: entry q with strand[q] != 0 is T = rc(query q), and position j' of T is letter
+// len - 1 - j' of the query, complemented.  The k-mer at j' is comp(s[len - 1 - j']), comp(s[len - 2 - j']), ... : the letters
+// [len - j' - k, len - j') of the query read backwards, so nothing below offsets[q] is touched; a tail position
+// (j' > len - k) validates its own letter len - 1 - j', and so every letter of the query is validated on either strand.
+// Wavefronts hold entries of both strands side by side: ONE loop serves both, each thread with its own first letter and
+// step, and the complement is a select behind a table read every lane makes (the table in LDS, as pw_overlap.hip's).
+template <typename K>
+__global__ __launch_bounds__(256) void k_qmatch_stranded(const uint8_t* __restrict__ arena, const int64_t* __restrict__ qoff,
+                                                         const int32_t* __restrict__ qlen, const int64_t* __restrict__ pstart,
+                                                         const uint8_t* __restrict__ strand, const uint8_t* __restrict__ comp,
+                                                         int64_t nq, int64_t npos, int k, int L, const K* __restrict__ rkeys,
+                                                         int64_t nkr, const uint32_t* __restrict__ tab, uint32_t* __restrict__ qid,
+                                                         uint32_t* __restrict__ lo_out, uint64_t* __restrict__ cnt,
+                                                         int* __restrict__ bad) {
+  __shared__ int64_t win[2];
+  __shared__ uint8_t s_comp[36];
+  const int64_t t0 = (int64_t)blockIdx.x * 256;
+  const int64_t tlast = (t0 + 256 < npos ? t0 + 256 : npos) - 1;
+  if (threadIdx.x == 0) win[0] = upper_bound_dev<int64_t>(pstart, nq + 1, t0) - 1;
+  if (threadIdx.x == 64) win[1] = upper_bound_dev<int64_t>(pstart, nq + 1, tlast) - 1;
+  load_complement(comp, L, s_comp);               // (its barrier publishes the window too)
+  const int64_t t = t0 + threadIdx.x;
+  if (t >= npos) return;
+  const int64_t q = win[0] + upper_bound_dev<int64_t>(pstart + win[0], win[1] - win[0] + 1, t) - 1;
+  const int64_t j = t - pstart[q];                // position in the listed sequence: of rc(query) for a minus entry
+  const int64_t len = qlen[q];
+  const bool minus = strand[q] != 0;
+  const uint8_t* __restrict__ s = arena + qoff[q] + (minus ? len - 1 - j : j);   // this position's own letter
+  const int64_t step = minus ? -1 : 1;
+  qid[t] = (uint32_t)q;
+  uint64_t c = 0;
+  uint32_t lo32 = 0;
+  if (j + k <= len) {                             // fewer than k letters left in this entry: no k-mer here
+    uint64_t v = 0;
+    bool ok = true;
+    for (int i = 0; i < k; i++) {
+      const uint32_t ch = s[i * step];
+      ok = ok && ch < (uint32_t)L;
+      const uint32_t cc = s_comp[ch < (uint32_t)L ? ch : 0u];
+      v = v * (uint64_t)L + (minus ? cc : ch);
+    }
+    if (!ok) *bad = 1;
+    else {
+      const K key = (K)v;
+      int64_t lo, hi;
+      if (tab != nullptr) { lo = tab[v]; hi = tab[v + 1]; }
+      else { lo = lower_bound_dev<K>(rkeys, nkr, key); hi = lo + upper_bound_dev<K>(rkeys + lo, nkr - lo, key); }
+      lo32 = (uint32_t)lo;
+      c = (uint64_t)(hi - lo);
+    }
+  } else if (j < len) {                           // the tail of an entry still holds letters: they are validated too
+    if (s[0] >= (uint32_t)L) *bad = 1;
   }
   lo_out[t] = lo32;
   cnt[t] = c;
@@ -222,6 +283,7 @@ struct pw_qseed_index {
   uint64_t kinv = 0;
   DeviceBuffer dref, rkeys, rpos, tab;                                        // the reference: filled by create
   DeviceBuffer arena, meta, qid, lo, cnt, off, row_off, rows, tmp, scalar;    // the queries: filled by build
+  DeviceBuffer comp;                                                          // the complement of a stranded build
   DeviceBuffer g_keys, g_order, g_cnt, g_off, g_adj;                          // neighbourhood graph (K10d)
   int64_t g_edges = -1;
   int cc_rounds = 0;
@@ -274,6 +336,107 @@ static void launch_match(pw_qseed_index* x, const uint8_t* arena, hipStream_t st
                      (uint64_t*)x->cnt.p, (int*)((unsigned long long*)x->scalar.p + 1));
 }
 
+template <typename K>
+static void launch_match_stranded(pw_qseed_index* x, const uint8_t* arena, hipStream_t st) {
+  const int64_t* meta = (const int64_t*)x->meta.p;                 // [... | strands nq (uint8)] behind launch_match's block
+  const int32_t* dlen = (const int32_t*)(meta + 2 * x->nq + 1);
+  hipLaunchKernelGGL((k_qmatch_stranded<K>), dim3((unsigned)((x->npos + 255) / 256)), dim3(256), 0, st, arena, meta, dlen, meta + x->nq,
+                     (const uint8_t*)(meta + 2 * x->nq + 1 + (x->nq + 1) / 2 + 1), (const uint8_t*)x->comp.p, x->nq, x->npos, x->k, x->L,
+                     (const K*)x->rkeys.p, x->nkR, x->has_tab ? (const uint32_t*)x->tab.p : (const uint32_t*)nullptr, (uint32_t*)x->qid.p,
+                     (uint32_t*)x->lo.p, (uint64_t*)x->cnt.p, (int*)((unsigned long long*)x->scalar.p + 1));
+}
+
+// both build entry points.  strand == nullptr: pw_qseeds_build, every query as given, the complement is not read.
+static int build_queries(pw_qseed_index* x, const uint8_t* arena, uint64_t arena_bytes, int arena_on_device, const int64_t* offsets,
+                 const int32_t* lengths, const uint8_t* strand, const uint8_t* complement, int64_t n_queries, int64_t max_rows,
+                 void* stream) {
+  if (!x) { set_err("null index"); return -1; }
+  if (n_queries < 0 || n_queries >= (1ll << 31)) { set_err("n_queries out of range"); return -1; }
+  if (n_queries > 0 && (!offsets || !lengths)) { set_err("null offsets / lengths"); return -1; }
+  if (arena_bytes > 0 && !arena) { set_err("null arena pointer"); return -1; }
+  hipStream_t st = (hipStream_t)stream;
+  if (max_rows <= 0) max_rows = 1ll << 30;
+  max_rows = std::min<int64_t>(max_rows, (1ll << 31) - 1);
+  x->nrows = -1; x->nq = -1; x->g_edges = -1;
+  const int64_t nq = n_queries;
+  bool any_minus = false;                         // (none: the unstranded kernels, and the complement is not read)
+  for (int64_t q = 0; strand && q < nq; q++) {
+    if (strand[q] > 1) { set_err("strand " + std::to_string(q) + " must be 0 (as given) or 1 (reverse complement)"); return -1; }
+    any_minus = any_minus || strand[q] == 1;
+  }
+  if (any_minus && check_complement(set_err, complement, x->L) != 0) return -1;
+  // [offsets nq | pstart nq + 1 | lengths nq (int32) | strands nq (uint8), a stranded build's] in one block: one copy to
+  // the device
+  const size_t strand_at = (size_t)(2 * nq + 1 + (nq + 1) / 2 + 1);
+  std::vector<int64_t> meta(strand_at + (any_minus ? (size_t)(nq + 7) / 8 : 0));
+  if (any_minus) memcpy(meta.data() + strand_at, strand, (size_t)nq);
+  int64_t npos = 0, max_qlen = 0;
+  int32_t* hl = (int32_t*)(meta.data() + 2 * nq + 1);
+  for (int64_t q = 0; q < nq; q++) {
+    if (lengths[q] < 0 || offsets[q] < 0 || (uint64_t)offsets[q] + (uint64_t)lengths[q] > arena_bytes) {
+      set_err("query " + std::to_string(q) + " lies outside the arena"); return -1;
+    }
+    meta[(size_t)q] = offsets[q];
+    meta[(size_t)(nq + q)] = npos;
+    hl[q] = lengths[q];
+    npos += lengths[q];
+    max_qlen = std::max<int64_t>(max_qlen, lengths[q]);
+    if (npos >= (1ll << 31)) { set_err("the queries' lengths must sum to less than 2^31"); return -1; }
+  }
+  meta[(size_t)(2 * nq)] = npos;
+  CHECK(hipSetDevice(x->device));
+  CHECK(x->meta.ensure(meta.size() * 8));
+  CHECK(x->row_off.ensure((size_t)(nq + 1) * 8));
+  if (any_minus && upload_complement(set_err, complement, x->L, x->comp) != 0) return -1;
+  CHECK(hipEventRecord(x->ev0.e, st));            // (the build's time includes its copies to the device)
+  const uint8_t* darena = arena;
+  if (!arena_on_device) {
+    CHECK(x->arena.ensure((size_t)arena_bytes + 64));
+    if (arena_bytes) CHECK(hipMemcpyAsync(x->arena.p, arena, (size_t)arena_bytes, hipMemcpyHostToDevice, st));
+    darena = (const uint8_t*)x->arena.p;
+  }
+  CHECK(hipMemcpyAsync(x->meta.p, meta.data(), meta.size() * 8, hipMemcpyHostToDevice, st));
+  CHECK(hipMemsetAsync(x->scalar.p, 0, 16, st));
+  x->npos = npos; x->max_qlen = max_qlen;
+  const size_t np1 = (size_t)std::max<int64_t>(npos, 1);
+  CHECK(x->qid.ensure(np1 * 4)); CHECK(x->lo.ensure(np1 * 4)); CHECK(x->cnt.ensure(np1 * 8)); CHECK(x->off.ensure(np1 * 8));
+  x->nq = nq;                                     // (launch_match reads it; reset below on failure)
+  if (npos > 0) {
+    if (!any_minus) { if (x->key32) launch_match<uint32_t>(x, darena, st); else launch_match<uint64_t>(x, darena, st); }
+    else if (x->key32) launch_match_stranded<uint32_t>(x, darena, st);
+    else launch_match_stranded<uint64_t>(x, darena, st);
+    CHECK(rocprim_run(x->tmp, [&](void* t, size_t& b) {
+      return rocprim::exclusive_scan(t, b, (const uint64_t*)x->cnt.p, (uint64_t*)x->off.p, (uint64_t)0, (size_t)npos, SatAdd(), st);
+    }));
+  }
+  const int64_t* dmeta = (const int64_t*)x->meta.p;
+  hipLaunchKernelGGL(k_qoffsets, dim3((unsigned)((nq + 256) / 256)), dim3(256), 0, st, (const uint64_t*)x->off.p, (const uint64_t*)x->cnt.p,
+                     npos, dmeta + nq, nq, (unsigned long long*)x->scalar.p, (uint64_t*)x->row_off.p);
+  unsigned long long res[2] = {0, 0};             // row total, bad-letter flag
+  CHECK(hipMemcpyAsync(res, x->scalar.p, 16, hipMemcpyDeviceToHost, st));
+  CHECK(hipStreamSynchronize(st));
+  x->nq = -1;
+  if ((int)res[1] != 0) { set_err("letter outside the alphabet in a query"); return -1; }
+  const unsigned long long total = res[0];
+  if (total > (unsigned long long)max_rows) {
+    char msg[200];
+    if (total == ~0ull)
+      snprintf(msg, sizeof msg, "the seeds table would hold at least 2^64 - 1 rows (limit %lld): raise the word length", (long long)max_rows);
+    else
+      snprintf(msg, sizeof msg, "the seeds table would hold %llu rows (limit %lld): raise max_rows or the word length", total, (long long)max_rows);
+    set_err(msg);
+    return -1;
+  }
+  CHECK(x->rows.ensure((size_t)std::max<unsigned long long>(total, 1) * 12));
+  if (total > 0)
+    hipLaunchKernelGGL(k_qexpand, dim3((unsigned)((total + kExpRows - 1) / kExpRows)), dim3(256), 0, st, (const uint64_t*)x->off.p, npos,
+                       (int64_t)total, (const uint32_t*)x->qid.p, dmeta + nq, (const uint32_t*)x->lo.p, (const uint32_t*)x->rpos.p,
+                       (int32_t*)x->rows.p);
+  if (elapsed(x, st, &x->ms_build) != 0) return -1;
+  x->nq = nq; x->nrows = (int64_t)total;
+  return 0;
+}
+
 extern "C" {
 
 const char* pw_qseeds_last_error(void) { return g_err.c_str(); }
@@ -307,79 +470,13 @@ pw_qseed_index* pw_qseeds_create(int device, const uint8_t* ref, int64_t n_ref, 
 
 int pw_qseeds_build(pw_qseed_index* x, const uint8_t* arena, uint64_t arena_bytes, int arena_on_device, const int64_t* offsets,
                     const int32_t* lengths, int64_t n_queries, int64_t max_rows, void* stream) {
-  if (!x) { set_err("null index"); return -1; }
-  if (n_queries < 0 || n_queries >= (1ll << 31)) { set_err("n_queries out of range"); return -1; }
-  if (n_queries > 0 && (!offsets || !lengths)) { set_err("null offsets / lengths"); return -1; }
-  if (arena_bytes > 0 && !arena) { set_err("null arena pointer"); return -1; }
-  hipStream_t st = (hipStream_t)stream;
-  if (max_rows <= 0) max_rows = 1ll << 30;
-  max_rows = std::min<int64_t>(max_rows, (1ll << 31) - 1);
-  x->nrows = -1; x->nq = -1; x->g_edges = -1;
-  // [offsets nq | pstart nq + 1 | lengths nq (int32)] in one block: one copy to the device
-  const int64_t nq = n_queries;
-  std::vector<int64_t> meta((size_t)(2 * nq + 1 + (nq + 1) / 2 + 1));
-  int64_t npos = 0, max_qlen = 0;
-  int32_t* hl = (int32_t*)(meta.data() + 2 * nq + 1);
-  for (int64_t q = 0; q < nq; q++) {
-    if (lengths[q] < 0 || offsets[q] < 0 || (uint64_t)offsets[q] + (uint64_t)lengths[q] > arena_bytes) {
-      set_err("query " + std::to_string(q) + " lies outside the arena"); return -1;
-    }
-    meta[(size_t)q] = offsets[q];
-    meta[(size_t)(nq + q)] = npos;
-    hl[q] = lengths[q];
-    npos += lengths[q];
-    max_qlen = std::max<int64_t>(max_qlen, lengths[q]);
-    if (npos >= (1ll << 31)) { set_err("the queries' lengths must sum to less than 2^31"); return -1; }
-  }
-  meta[(size_t)(2 * nq)] = npos;
-  CHECK(hipSetDevice(x->device));
-  CHECK(x->meta.ensure(meta.size() * 8));
-  CHECK(x->row_off.ensure((size_t)(nq + 1) * 8));
-  CHECK(hipEventRecord(x->ev0.e, st));            // (the build's time includes its copies to the device)
-  const uint8_t* darena = arena;
-  if (!arena_on_device) {
-    CHECK(x->arena.ensure((size_t)arena_bytes + 64));
-    if (arena_bytes) CHECK(hipMemcpyAsync(x->arena.p, arena, (size_t)arena_bytes, hipMemcpyHostToDevice, st));
-    darena = (const uint8_t*)x->arena.p;
-  }
-  CHECK(hipMemcpyAsync(x->meta.p, meta.data(), meta.size() * 8, hipMemcpyHostToDevice, st));
-  CHECK(hipMemsetAsync(x->scalar.p, 0, 16, st));
-  x->npos = npos; x->max_qlen = max_qlen;
-  const size_t np1 = (size_t)std::max<int64_t>(npos, 1);
-  CHECK(x->qid.ensure(np1 * 4)); CHECK(x->lo.ensure(np1 * 4)); CHECK(x->cnt.ensure(np1 * 8)); CHECK(x->off.ensure(np1 * 8));
-  x->nq = nq;                                     // (launch_match reads it; reset below on failure)
-  if (npos > 0) {
-    if (x->key32) launch_match<uint32_t>(x, darena, st); else launch_match<uint64_t>(x, darena, st);
-    CHECK(rocprim_run(x->tmp, [&](void* t, size_t& b) {
-      return rocprim::exclusive_scan(t, b, (const uint64_t*)x->cnt.p, (uint64_t*)x->off.p, (uint64_t)0, (size_t)npos, SatAdd(), st);
-    }));
-  }
-  const int64_t* dmeta = (const int64_t*)x->meta.p;
-  hipLaunchKernelGGL(k_qoffsets, dim3((unsigned)((nq + 256) / 256)), dim3(256), 0, st, (const uint64_t*)x->off.p, (const uint64_t*)x->cnt.p,
-                     npos, dmeta + nq, nq, (unsigned long long*)x->scalar.p, (uint64_t*)x->row_off.p);
-  unsigned long long res[2] = {0, 0};             // row total, bad-letter flag
-  CHECK(hipMemcpyAsync(res, x->scalar.p, 16, hipMemcpyDeviceToHost, st));
-  CHECK(hipStreamSynchronize(st));
-  x->nq = -1;
-  if ((int)res[1] != 0) { set_err("letter outside the alphabet in a query"); return -1; }
-  const unsigned long long total = res[0];
-  if (total > (unsigned long long)max_rows) {
-    char msg[200];
-    if (total == ~0ull)
-      snprintf(msg, sizeof msg, "the seeds table would hold at least 2^64 - 1 rows (limit %lld): raise the word length", (long long)max_rows);
-    else
-      snprintf(msg, sizeof msg, "the seeds table would hold %llu rows (limit %lld): raise max_rows or the word length", total, (long long)max_rows);
-    set_err(msg);
-    return -1;
-  }
-  CHECK(x->rows.ensure((size_t)std::max<unsigned long long>(total, 1) * 12));
-  if (total > 0)
-    hipLaunchKernelGGL(k_qexpand, dim3((unsigned)((total + kExpRows - 1) / kExpRows)), dim3(256), 0, st, (const uint64_t*)x->off.p, npos,
-                       (int64_t)total, (const uint32_t*)x->qid.p, dmeta + nq, (const uint32_t*)x->lo.p, (const uint32_t*)x->rpos.p,
-                       (int32_t*)x->rows.p);
-  if (elapsed(x, st, &x->ms_build) != 0) return -1;
-  x->nq = nq; x->nrows = (int64_t)total;
-  return 0;
+  return build_queries(x, arena, arena_bytes, arena_on_device, offsets, lengths, nullptr, nullptr, n_queries, max_rows, stream);
+}
+
+int pw_qseeds_build_stranded(pw_qseed_index* x, const uint8_t* arena, uint64_t arena_bytes, int arena_on_device, const int64_t* offsets,
+                             const int32_t* lengths, const uint8_t* strand, const uint8_t* complement, int64_t n_queries,
+                             int64_t max_rows, void* stream) {
+  return build_queries(x, arena, arena_bytes, arena_on_device, offsets, lengths, strand, complement, n_queries, max_rows, stream);
 }
 
 int64_t pw_qseeds_num_queries(const pw_qseed_index* x) { return x ? x->nq : -1; }

@@ -13,8 +13,9 @@ import numpy as np
 from . import _pwlib as W
 from .batch import BatchAligner, DeviceArena, pack_reads, summary_dict
 from .blot import WordBlot, WordBlotLocalRef
+from .overlap import _complement
 from .pw import Alignment
-from .sequence import Sequence
+from .sequence import Sequence, reverse_complement
 
 
 def segment_frame(seg, lenS, lenT, wordlen):
@@ -108,7 +109,26 @@ def _run_summarized(b):
     return res, b.summaries()
 
 
-def map_queries(ref, queries, K_min, p_min, wordlen, g_max, sensitivity, keep=3, device=0, aligner_kw=None, alignments=True):
+def rank_segments(segments, keep):
+    """The best ``keep`` of one query's segments (dicts with ``p`` and ``segment``) by ``p * (a_max - a_min)``, best first
+    (``experiments/blot_ig_genotyping.py:45-48, 72-75``).  The sort is stable: with the plus strand's segments listed before
+    the minus strand's, as ``similar_segments_many(strands='both')`` lists them, a tie goes to ``'+'``."""
+    return sorted(segments, key=lambda rec: -(rec['p'] * (rec['segment'][1][1] - rec['segment'][1][0])))[:keep]
+
+
+def query_interval(strand, mutant_start, len_aln, query_len):
+    """The half-open interval of the query AS GIVEN that an alignment covers: it starts at ``mutant_start`` of the aligned
+    sequence and consumes ``len_aln`` of its letters.  On ``'+'`` the aligned sequence is the query; on ``'-'`` it is
+    ``rc(query)`` and the interval is the one :func:`biseqt_amd.overlap.minus_to_forward` returns for the transcript, here
+    from the number of letters alone (the op counts stand in where no transcript comes to the host)."""
+    assert strand in ('+', '-') and 0 <= mutant_start and len_aln >= 0 and mutant_start + len_aln <= query_len
+    if strand == '+':
+        return mutant_start, mutant_start + len_aln
+    return query_len - (mutant_start + len_aln), query_len - mutant_start
+
+
+def map_queries(ref, queries, K_min, p_min, wordlen, g_max, sensitivity, keep=3, device=0, aligner_kw=None, alignments=True,
+                strands='+', complement=None):
     """Map many short queries onto one reference sequence: Word-Blot local similarities of all queries in one pass
     (:meth:`WordBlotLocalRef.similar_segments_many`), then a banded local alignment of the best segments of every query,
     all in ONE lane-packed batch.  The flow of ``experiments/blot_ig_genotyping.py:45-101`` as a library function: per
@@ -123,37 +143,60 @@ def map_queries(ref, queries, K_min, p_min, wordlen, g_max, sensitivity, keep=3,
     With ``alignments=False`` only the 32-byte records and the 48-byte summaries of the batch come to the host -- no
     transcript is downloaded or decoded: ``alignment`` is None, ``p_aln`` and ``len_aln`` come from the op counts, and every
     dict also has ``origin_start``, ``mutant_start`` (those of the :class:`Alignment`) and ``summary`` (the fields of
-    ``batch.SUMMARY_DTYPE``; None where there is no alignment)."""
+    ``batch.SUMMARY_DTYPE``; None where there is no alignment).
+
+    ``strands``: ``'+'`` (the default, with exactly the keys above), ``'-'`` or ``'both'``; ``complement`` as in
+    :meth:`WordBlotLocalRef.similar_segments_many`.  A record on the minus strand maps ``T = rc(query)`` -- position ``j'``
+    of ``T`` is letter ``len - 1 - j'`` of the query, complemented; the convention :mod:`biseqt_amd.overlap` documents --
+    and its segment, ``diag_range``, start indices and transcript are in the frame of that ``T``: they equal what the
+    default call returns for the materialised ``rc(query)``, and ``alignment`` is
+    ``Alignment(ref, reverse_complement(query), ...)``.  A query's segments of the selected strands are ranked together
+    (:func:`rank_segments`: a tie goes to ``'+'``) and the best ``keep`` aligned in the one batch.  Every record then also
+    has ``strand`` and ``query_interval``: the half-open interval of the query AS GIVEN that the alignment covers
+    (:func:`query_interval`; None without an alignment).  The seeding reads the forward letters only; for the alignment
+    step the device writes the reverse complement of every query behind the uploaded letters, once, before the seeding."""
     assert isinstance(ref, Sequence) and all(isinstance(T, Sequence) for T in queries)
     queries = list(queries)
+    if strands not in ('+', '-', 'both'):
+        raise ValueError("strands is '+', '-' or 'both', not %r" % (strands,))
+    stranded = strands != '+'
     kw = dict(match_score=1, mismatch_score=-3, go_score=-5, ge_score=-2)
     kw.update(aligner_kw or {})
     kw.pop('diag_range', None)
     kw.update(alnmode=W.BANDED_MODE, alntype=W.B_LOCAL)
     arena, offs, lens = pack_reads([ref] + queries)           # read 0 is the reference, read 1 + q is query q
+    nq = len(queries)
+    if stranded:                                              # ... and frame 1 + nq + q is rc(query q), written by the device
+        comp = _complement(complement, len(ref.alphabet), ref.alphabet)
+        darena = DeviceArena.with_reverse_complements(arena, offs, lens, np.arange(1, 1 + nq), comp, device)
+        all_offs, all_lens = np.concatenate([offs, darena.rc_offsets]), np.concatenate([lens, lens[1:]])
+        seed_kw = dict(strands=strands, complement=comp)
+    else:
+        darena, all_offs, all_lens, seed_kw = DeviceArena(arena, device=device), offs, lens, {}
     out = [[] for _ in queries]
-    with DeviceArena(arena, device=device) as darena:
+    with darena:
         wb = WordBlotLocalRef(ref, alphabet=ref.alphabet, wordlen=wordlen, g_max=g_max, sensitivity=sensitivity, device=device)
         try:
-            segs = wb.similar_segments_many(queries, K_min, p_min, arena=(darena, offs[1:], lens[1:]))
+            segs = wb.similar_segments_many(queries, K_min, p_min, arena=(darena, offs[1:], lens[1:]), **seed_kw)
         finally:
             wb.close()
         pairs, bands = [], []
         for q, recs in enumerate(segs):
-            ranked = sorted(recs, key=lambda rec: -(rec['p'] * (rec['segment'][1][1] - rec['segment'][1][0])))[:keep]
-            for rec in ranked:
-                d_band = rec['segment'][0]
-                rec = dict(segment=rec['segment'], p=rec['p'], diag_range=(int(d_band[0]), int(d_band[1])), score=None,
+            for seg in rank_segments(recs, keep):
+                d_band = seg['segment'][0]
+                rec = dict(segment=seg['segment'], p=seg['p'], diag_range=(int(d_band[0]), int(d_band[1])), score=None,
                            alignment=None, p_aln=None, len_aln=None)
                 if not alignments:
                     rec.update(origin_start=None, mutant_start=None, summary=None)
+                if stranded:
+                    rec.update(strand=seg['strand'], query_interval=None)
                 out[q].append(rec)
-                pairs.append((0, 1 + q))
+                pairs.append((0, 1 + q + (nq if stranded and seg['strand'] == '-' else 0)))
                 bands.append(rec['diag_range'])
         if not pairs:
             return out
-        with BatchAligner.from_arena(arena, offs, lens, pairs, diag_ranges=bands, device_arena=darena,
-                                     alphabet_len=len(ref.alphabet), device=device, **kw) as b:
+        with BatchAligner.from_arena(arena, all_offs, all_lens, pairs, diag_ranges=bands, device_arena=darena,
+                                     alphabet_len=len(ref.alphabet), device=device, arena_bytes=darena.nbytes, **kw) as b:
             if alignments:
                 res = b.run()
                 txs = b.transcripts(res)
@@ -162,11 +205,12 @@ def map_queries(ref, queries, K_min, p_min, wordlen, g_max, sensitivity, keep=3,
     k = 0
     for q, recs in enumerate(out):
         for rec in recs:
+            mutant_start = int(res['mutant_idx'][k])
             if not alignments:
                 if res['opt_i'][k] >= 0 and res['tx_len'][k] > 0:
                     s = sums[k]
                     rec['score'] = float(res['score'][k])
-                    rec['origin_start'], rec['mutant_start'] = int(res['origin_idx'][k]), int(res['mutant_idx'][k])
+                    rec['origin_start'], rec['mutant_start'] = int(res['origin_idx'][k]), mutant_start
                     len_on_query = int(s['n_match']) + int(s['n_subst']) + int(s['n_ins'])
                     rec['p_aln'] = round(1. * int(s['n_match']) / len_on_query, 2) if len_on_query else None
                     rec['len_aln'] = len_on_query
@@ -174,11 +218,14 @@ def map_queries(ref, queries, K_min, p_min, wordlen, g_max, sensitivity, keep=3,
             elif res['opt_i'][k] >= 0 and txs[k]:
                 tx = txs[k]
                 rec['score'] = float(res['score'][k])
-                rec['alignment'] = Alignment(ref, queries[q], tx, score=rec['score'], origin_start=int(res['origin_idx'][k]),
-                                             mutant_start=int(res['mutant_idx'][k]))
+                T = reverse_complement(queries[q], comp) if stranded and rec['strand'] == '-' else queries[q]
+                rec['alignment'] = Alignment(ref, T, tx, score=rec['score'], origin_start=int(res['origin_idx'][k]),
+                                             mutant_start=mutant_start)
                 len_on_query = sum(tx.count(op) for op in 'MSI')
                 rec['p_aln'] = round(1. * tx.count('M') / len_on_query, 2) if len_on_query else None
                 rec['len_aln'] = len_on_query
+            if stranded and rec['len_aln'] is not None:
+                rec['query_interval'] = query_interval(rec['strand'], mutant_start, rec['len_aln'], len(queries[q]))
             k += 1
     return out
 

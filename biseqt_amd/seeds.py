@@ -349,7 +349,7 @@ class _QIndex(object):
     def __init__(self, ref, wordlen, alphabet, device=0):
         self.lib = W.load()
         r = ref.as_array(np.uint8) if isinstance(ref, Sequence) else np.ascontiguousarray(ref, np.uint8)
-        self.device = device
+        self.device, self.alphabet_len = device, len(alphabet)
         self.handle = self.lib.pw_qseeds_create(device, r.ctypes.data, len(r), len(alphabet), wordlen)
         if not self.handle:
             raise RuntimeError('pw_qseeds_create failed: ' + self.error())
@@ -358,13 +358,24 @@ class _QIndex(object):
     def error(self):
         return (self.lib.pw_qseeds_last_error() or b'').decode('utf-8', 'replace')
 
-    def build(self, arena, offsets, lengths, max_rows=0, stream=None):
+    def build(self, arena, offsets, lengths, max_rows=0, stream=None, strands=None, complement=None):
         """Seeds of the queries ``arena[offsets[q]:offsets[q] + lengths[q]]``.  ``arena`` is a uint8 array (the layout of
         :func:`biseqt_amd.batch.pack_reads`) or a :class:`biseqt_amd.batch.DeviceArena`, which is read in place.
-        Returns the number of rows."""
+        Returns the number of rows.
+
+        ``strands``: one ``'+'`` / ``'-'`` (or 0 / 1) per listed entry.  A minus entry IS the sequence ``T = rc(query)``
+        (position ``j'`` of ``T`` is letter ``len - 1 - j'`` of the query, complemented -- the convention of
+        :mod:`biseqt_amd.overlap`): its rows are those of the materialised reverse complement passed as an ordinary query,
+        and the device forms its k-mers from the forward letters.  Two entries may name the same letters with different
+        strands.  ``complement`` (a table of ``len(alphabet)`` letter indices, its own inverse) is needed when some entry is
+        ``'-'``; bad strands or a bad complement raise ``ValueError`` before any device call."""
         offsets = np.ascontiguousarray(offsets, np.int64)
         lengths = np.ascontiguousarray(lengths, np.int32)
         assert offsets.ndim == 1 and offsets.shape == lengths.shape
+        if strands is not None:
+            from .overlap import _complement, _strand_flags
+            flags = _strand_flags(strands, len(offsets))
+            comp = _complement(complement, self.alphabet_len) if flags.any() or complement is not None else None
         if isinstance(arena, np.ndarray):
             arena = np.ascontiguousarray(arena, np.uint8)
             ptr, nbytes, on_device = arena.ctypes.data, arena.nbytes, 0
@@ -372,8 +383,13 @@ class _QIndex(object):
             assert arena.device == self.device, 'the arena lives on another device'
             ptr, nbytes, on_device = arena.ptr, arena.nbytes, 1
         self._edges = None
-        if self.lib.pw_qseeds_build(self.handle, ptr, nbytes, on_device, offsets.ctypes.data, lengths.ctypes.data, len(offsets),
-                                    max_rows, stream) != 0:
+        if strands is not None:
+            if self.lib.pw_qseeds_build_stranded(self.handle, ptr, nbytes, on_device, offsets.ctypes.data, lengths.ctypes.data,
+                                                 flags.ctypes.data, None if comp is None else comp.ctypes.data, len(offsets),
+                                                 max_rows, stream) != 0:
+                raise RuntimeError('pw_qseeds_build_stranded failed: ' + self.error())
+        elif self.lib.pw_qseeds_build(self.handle, ptr, nbytes, on_device, offsets.ctypes.data, lengths.ctypes.data, len(offsets),
+                                      max_rows, stream) != 0:
             raise RuntimeError('pw_qseeds_build failed: ' + self.error())
         return self.num_rows()
 

@@ -12,6 +12,12 @@
  * scanned left to right, the reference's hits of a k-mer ascending).  No mask (the in-memory classes take none) and no
  * self comparison: a query equal to the reference is compared like any other (the caller routes such a query elsewhere).
  *
+ * Strands (pw_qseeds_build_stranded): a listed query with strand 1 IS the sequence T = rc(query) -- position j' of T is
+ * letter len - 1 - j' of the query, complemented; the convention of include/pw_overlap.h.  Its rows, and everything
+ * derived from them (graph, components, box counts), are in the frame of that T and equal, field for field, what the
+ * unstranded build returns when rc(query) is materialised and passed as an ordinary query.  The device computes the
+ * reverse-strand keys from the forward letters: rc(query) is never materialised for seeding.
+ *
  * Plain pointers and sizes only; letters are one byte each (index into the alphabet).  Everything fails loudly
  * (NULL / negative return + pw_qseeds_last_error()); there is no CPU fallback.
  */
@@ -39,6 +45,19 @@ pw_qseed_index* pw_qseeds_create(int device, const uint8_t* ref, int64_t n_ref, 
  * max_rows rows (max_rows <= 0: the default, 2^30; never more than 2^31 - 1, the graph indexes rows with int32). */
 int pw_qseeds_build(pw_qseed_index* idx, const uint8_t* arena, uint64_t arena_bytes, int arena_on_device,
                     const int64_t* offsets, const int32_t* lengths, int64_t n_queries, int64_t max_rows, void* stream);
+
+/* pw_qseeds_build with a strand per listed query: strand[q] is 0 (as given) or 1 (reverse complement); any other value
+ * returns -1.  strand == NULL is pw_qseeds_build itself, and the complement is not read.  `complement` is alphabet_len
+ * bytes, complement[c] for every letter c: a permutation that is its own inverse (checked as pw_overlap.h's; anything else
+ * returns -1).  It is required only when some strand[q] == 1.  Two listed entries may name the same bytes with different
+ * strands: that is how a caller asks for both strands of a query.  The limit "lengths sum to less than 2^31" applies to
+ * the LISTED entries, so both strands of a read set allow 2^30 letters.  A row of a minus entry is (q, i - j', i + j') for
+ * position j' of rc(query); rows are in (q, j', i) order.  Every letter of every listed query is validated on either
+ * strand; a minus entry is read backwards from its last letter and never below offsets[q].  After a refused build the
+ * handle stays usable. */
+int pw_qseeds_build_stranded(pw_qseed_index* idx, const uint8_t* arena, uint64_t arena_bytes, int arena_on_device,
+                             const int64_t* offsets, const int32_t* lengths, const uint8_t* strand,
+                             const uint8_t* complement, int64_t n_queries, int64_t max_rows, void* stream);
 
 int64_t pw_qseeds_num_queries(const pw_qseed_index* idx);
 int64_t pw_qseeds_num_rows(const pw_qseed_index* idx);
