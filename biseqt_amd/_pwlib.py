@@ -1,5 +1,5 @@
 """ctypes binding of biseqt_amd/pwlib/pwlib.so (the HIP library; C ABI in include/pwlib.h,
-include/pw_batch.h, include/pw_txsum.h and the seed headers include/pw_seeds.h, pw_mseeds.h, pw_qseeds.h, pw_overlap.h).
+include/pw_batch.h, include/pw_txsum.h, include/pw_cigar.h and the seed headers include/pw_seeds.h, pw_mseeds.h, pw_qseeds.h, pw_overlap.h).
 
 The reference binds its C library with cffi in ABI mode (``biseqt/pw.py:45-69``); cffi is not
 available in this image, so the same structs are declared with ctypes -- field for field the layout of
@@ -135,6 +135,12 @@ EXPORTS = ['dptable_init', 'dptable_solve', 'dptable_traceback', 'dptable_free',
 # every symbol include/pw_txsum.h declares
 TXSUM_EXPORTS = ['pw_batch_summarize', 'pw_batch_summaries_device', 'pw_batch_summaries_async', 'pw_batch_summaries',
                  'pw_tx_summarize_packed']
+# every symbol and constant include/pw_cigar.h declares
+CIGAR_EXPORTS = ['pw_batch_cigars', 'pw_batch_cigar_runs_device', 'pw_batch_cigar_offsets_device', 'pw_batch_cigar_total', 'pw_batch_cigar',
+                 'pw_tx_cigar_packed']
+PW_CIGAR_EXTENDED, PW_CIGAR_CLASSIC = 0, 1
+PW_CIGAR_OP_M, PW_CIGAR_OP_I, PW_CIGAR_OP_D, PW_CIGAR_OP_EQ, PW_CIGAR_OP_X = 0, 1, 2, 7, 8
+PW_CIGAR_MAX_LEN = 1 << 28
 # every symbol include/pw_seeds.h declares
 SEED_EXPORTS = ['pw_seeds_create', 'pw_seeds_build', 'pw_seeds_num_rows', 'pw_seeds_is_self', 'pw_seeds_rows_device',
                 'pw_seeds_rows', 'pw_seeds_count', 'pw_seeds_kmers', 'pw_seeds_band_neighbours', 'pw_seeds_graph_build', 'pw_seeds_graph_num_points', 'pw_seeds_graph_points',
@@ -298,6 +304,16 @@ def load():
     lib.pw_batch_summaries_async.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     lib.pw_batch_summaries.argtypes = [C.c_void_p, C.c_void_p]
     lib.pw_tx_summarize_packed.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    # include/pw_cigar.h
+    lib.pw_batch_cigars.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    lib.pw_batch_cigar_runs_device.argtypes = [C.c_void_p]
+    lib.pw_batch_cigar_runs_device.restype = C.c_void_p
+    lib.pw_batch_cigar_offsets_device.argtypes = [C.c_void_p]
+    lib.pw_batch_cigar_offsets_device.restype = C.c_void_p
+    lib.pw_batch_cigar_total.argtypes = [C.c_void_p]
+    lib.pw_batch_cigar_total.restype = C.c_uint64
+    lib.pw_batch_cigar.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p]
+    lib.pw_tx_cigar_packed.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p]
     # include/pw_seeds.h
     lib.pw_seeds_create.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int,
                                     P(C.c_uint64), C.c_int, C.c_int]

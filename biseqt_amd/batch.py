@@ -21,6 +21,20 @@ assert RESULT_DTYPE.itemsize == 32
 SUMMARY_DTYPE = np.dtype([(f, '<i4') for f in ('n_match', 'n_subst', 'n_ins', 'n_del', 'n_gaps', 'first_match', 'last_match',
                                                'head_origin', 'head_mutant', 'tail_origin', 'tail_mutant', 'flags')])
 assert SUMMARY_DTYPE.itemsize == 48
+# include/pw_cigar.h: a run is one uint32, (length << 4) | op with BAM's op codes
+CIGAR_EXTENDED, CIGAR_CLASSIC = W.PW_CIGAR_EXTENDED, W.PW_CIGAR_CLASSIC
+CIGAR_OPS = 'MIDNSHP=X'
+_CIGAR_FORMS = {'extended': CIGAR_EXTENDED, 'classic': CIGAR_CLASSIC}
+_CIGAR_LETTERS = ({'M': '=', 'S': 'X', 'I': 'I', 'D': 'D'}, {'M': 'M', 'S': 'M', 'I': 'I', 'D': 'D'})
+
+
+def _cigar_form(form):
+    """``'extended'`` / ``'classic'`` (or the constants) -> PW_CIGAR_EXTENDED / PW_CIGAR_CLASSIC."""
+    if isinstance(form, str) and form in _CIGAR_FORMS:
+        return _CIGAR_FORMS[form]
+    if not isinstance(form, (str, bool)) and form in (CIGAR_EXTENDED, CIGAR_CLASSIC):
+        return int(form)
+    raise ValueError("form is 'extended' or 'classic', not %r" % (form,))
 
 
 def _as_u8(seq):
@@ -471,6 +485,32 @@ class BatchAligner(object):
     def summaries_device(self):
         return DeviceBuffer(self.lib.pw_batch_summaries_device(self.handle), 48 * self.n, self)
 
+    # ---- CIGARs (include/pw_cigar.h): the transcripts run-length encoded where they are ----
+    def cigars(self, form='extended', stream=None):
+        """After a traceback on ``stream``: ``(runs uint32[total], offsets uint64[n + 1])`` on the host -- the runs
+        ``(length << 4) | op`` of all pairs back to back in transcript order, pair ``k`` owning
+        ``runs[offsets[k]:offsets[k + 1]]`` (``pw_batch_cigars``, then a synchronous D2H).  ``form`` is ``'extended'`` (``=`` /
+        ``X``) or ``'classic'`` (``M``).  A pair without a summary (:meth:`summaries`) has zero runs.  The call reads the
+        8-byte total back between the offsets and the write kernel: it blocks on ``stream`` once."""
+        f = _cigar_form(form)
+        self._ck(self.lib.pw_batch_cigars(self.handle, f, stream), 'pw_batch_cigars')
+        if stream is not None:
+            self.sync(stream)
+        off = np.zeros(self.n + 1, np.uint64)
+        self._ck(self.lib.pw_batch_cigar(self.handle, f, None, 0, off.ctypes.data), 'pw_batch_cigar')
+        total = int(off[-1])
+        runs = np.zeros(max(total, 1), np.uint32)
+        self._ck(self.lib.pw_batch_cigar(self.handle, f, runs.ctypes.data, runs.size, None), 'pw_batch_cigar')
+        return runs[:total], off
+
+    def cigars_device(self):
+        """(runs, offsets) of the last ``pw_batch_cigars`` -- :meth:`cigars`, or a direct call -- as :class:`DeviceBuffer` views;
+        the runs view spans ``pw_batch_cigar_total`` runs."""
+        runs, off = self.lib.pw_batch_cigar_runs_device(self.handle), self.lib.pw_batch_cigar_offsets_device(self.handle)
+        if not runs or not off:
+            raise RuntimeError('cigars_device before cigars')
+        return DeviceBuffer(runs, 4 * int(self.lib.pw_batch_cigar_total(self.handle)), self), DeviceBuffer(off, 8 * (self.n + 1), self)
+
     def scores_plane(self, k):
         """Score of every cell of pair k as ``plane[d - dmin, a]`` (needs PW_FLAG_DUMP_SCORES)."""
         X, Y = self.lens[k]
@@ -535,6 +575,77 @@ def summarize_transcripts(transcripts, device=0):
     if W.load().pw_tx_summarize_packed(device, buf.ctypes.data if buf.size else None, off.ctypes.data, n, out.ctypes.data) != 0:
         raise RuntimeError('pw_tx_summarize_packed failed: ' + W.last_error())
     return out[:n]
+
+
+def _packed_transcripts(transcripts):
+    """``(buf uint8, offsets uint64[n + 1])`` of a list of ``str`` / ``None``, or of such a tuple itself."""
+    if isinstance(transcripts, tuple) and len(transcripts) == 2 and isinstance(transcripts[0], np.ndarray):
+        buf = np.ascontiguousarray(transcripts[0], np.uint8)
+        off = np.ascontiguousarray(transcripts[1], np.uint64)
+        assert off.ndim == 1 and off.size >= 1 and int(off[-1]) <= buf.size
+        return buf, off
+    raw = [(t or '').encode('ascii') for t in transcripts]
+    off = np.zeros(len(raw) + 1, np.uint64)
+    if raw:
+        off[1:] = np.cumsum([len(r) for r in raw])
+    return np.frombuffer(b''.join(raw), np.uint8), off
+
+
+def cigars_of_transcripts(transcripts, form='extended', device=0):
+    """``(runs uint32[total], offsets uint64[n + 1])`` of transcripts that are not in a batch's slots, through the same
+    device routine (``pw_tx_cigar_packed``): ``transcripts`` is a list of ``str`` / ``None``, or ``(buf, offsets)`` as
+    :meth:`BatchAligner.packed` returns them.  ``None`` and ``''`` have zero runs."""
+    f = _cigar_form(form)
+    buf, off = _packed_transcripts(transcripts)
+    n = off.size - 1
+    lib = W.load()
+    roff = np.zeros(n + 1, np.uint64)
+    ops = buf.ctypes.data if buf.size else None
+    runs = np.zeros(max(int(off[-1]) - int(off[0]), 1), np.uint32)       # (room for one run per op: one call, no size query)
+    if lib.pw_tx_cigar_packed(device, ops, off.ctypes.data, n, f, runs.ctypes.data, runs.size, roff.ctypes.data) != 0:
+        raise RuntimeError('pw_tx_cigar_packed failed: ' + W.last_error())
+    return runs[:int(roff[-1])].copy(), roff
+
+
+def cigar_strings(runs, offsets):
+    """One CIGAR string per pair from ``(runs, offsets)`` of :meth:`BatchAligner.cigars`; zero runs give ``''``."""
+    runs, offsets = np.asarray(runs, np.uint32), np.asarray(offsets, np.int64)
+    lens, ops = (runs >> 4).tolist(), (runs & 15).tolist()
+    return [''.join('%d%s' % (lens[r], CIGAR_OPS[ops[r]]) for r in range(int(offsets[k]), int(offsets[k + 1])))
+            for k in range(len(offsets) - 1)]
+
+
+def cigar_of_transcript(tx, form='extended'):
+    """The CIGAR string of one transcript over ``MSID``, on the host (``None`` and ``''`` give ``''``)."""
+    letters = _CIGAR_LETTERS[_cigar_form(form)]
+    out, cur, n = [], None, 0
+    for op in tx or '':
+        if op not in letters:
+            raise ValueError('transcript op %r is none of M, S, I, D' % (op,))
+        if letters[op] == cur:
+            n += 1
+            continue
+        if cur is not None:
+            out.append('%d%s' % (n, cur))
+        cur, n = letters[op], 1
+    if cur is not None:
+        out.append('%d%s' % (n, cur))
+    return ''.join(out)
+
+
+def transcript_of_cigar(s):
+    """The transcript of a CIGAR string in the extended form.  ``ValueError`` for a classic ``M`` (it does not say which of
+    its letters match), any other op and anything that is not a CIGAR."""
+    import re
+    if not re.fullmatch(r'(?:[0-9]+[A-Za-z=])*', s):
+        raise ValueError('not a CIGAR string: %r' % (s,))
+    back = {'=': 'M', 'X': 'S', 'I': 'I', 'D': 'D'}
+    out = []
+    for n, op in re.findall(r'([0-9]+)([A-Za-z=])', s):
+        if op not in back:
+            raise ValueError('CIGAR op %r has no transcript letter (only the extended form =, X, I, D has)' % (op,))
+        out.append(back[op] * int(n))
+    return ''.join(out)
 
 
 def plan_only(shapes, alnmode=W.STD_MODE, alntype=W.GLOBAL, alphabet_len=4, subst_scores=None, match_score=1, mismatch_score=0,

@@ -32,6 +32,16 @@ hipError_t launch_tx_pack(const PairDesc* pairs, const Result* results, const ui
 // the slots of a batch or over a packed buffer and its offsets[n + 1]
 hipError_t launch_tx_summary(const PairDesc* pairs, const Result* results, const uint8_t* slots, int n, void* out, hipStream_t st);
 hipError_t launch_tx_summary_packed(const uint8_t* ops, const uint64_t* offsets, int n, void* out, hipStream_t st);
+// CIGARs (pw_cigar.hip; forms and the run dword in include/pw_cigar.h): one wavefront per transcript, over the slots of a
+// batch or over a packed buffer and its offsets[n + 1].  count: the runs per transcript and, behind them on the stream,
+// their exclusive prefix sums in offsets[n + 1] ([n] = total); write: every run to runs[offsets[k] + index]
+hipError_t launch_cigar_count(const PairDesc* pairs, const Result* results, const uint8_t* slots, int n, int form, uint64_t* offsets,
+                              hipStream_t st);
+hipError_t launch_cigar_write(const PairDesc* pairs, const Result* results, const uint8_t* slots, int n, int form, const uint64_t* offsets,
+                              uint32_t* runs, hipStream_t st);
+hipError_t launch_cigar_count_packed(const uint8_t* ops, const uint64_t* offsets, int n, int form, uint64_t* run_offsets, hipStream_t st);
+hipError_t launch_cigar_write_packed(const uint8_t* ops, const uint64_t* offsets, int n, int form, const uint64_t* run_offsets, uint32_t* runs,
+                                     hipStream_t st);
 // strip pipeline (pw_strip.h / pw_strip.hip): one standard-mode pair wider than a workgroup
 struct StripParams;
 struct StripTraceParams;

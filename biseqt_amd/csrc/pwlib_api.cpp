@@ -21,6 +21,7 @@
 
 #include "../../include/pw_batch.h"
 #include "../../include/pw_txsum.h"
+#include "../../include/pw_cigar.h"
 #include "pw_launch.h"
 #include "pw_plan.h"
 #include "pw_model.h"
@@ -222,6 +223,11 @@ struct pw_batch {
   DeviceBuffer d_txoffsets;              // uint64_t[n + 1]
   PoolBuffer<pw_tx_summary> d_summaries; // pw_batch_summarize: allocated on its first call
   uint64_t trace_seq = 0, summary_seq = 0;   // tracebacks so far / the one the summaries were taken after
+  DeviceBuffer d_cigoffsets;             // pw_batch_cigars: uint64_t[n + 1], allocated on its first call
+  PoolBuffer<uint32_t> d_cigruns;        // ... and the runs; grows to the largest total seen
+  uint64_t cigar_room = 0, cigar_total = 0, cigar_seq = 0;   // runs d_cigruns holds / the last total / the traceback it describes
+  int cigar_form = -1;
+  hipStream_t cigar_stream = nullptr;    // the stream of the last pw_batch_cigars
   DeviceEvent ev_fill0, ev_fill1, ev_tr0, ev_tr1;
   bool fill_timed = false, trace_timed = false;
   // scores as the caller gave them (batch_plan may scale b->subst / go / ge by a power of two)
@@ -1057,6 +1063,87 @@ int pw_tx_summarize_packed(int device, const uint8_t* ops, const uint64_t* offse
   HIP_TRY(hipMemcpy(d_off.p, offsets, 8 * ((size_t)n + 1), hipMemcpyHostToDevice));
   HIP_TRY(pw::launch_tx_summary_packed((const uint8_t*)d_ops.p, (const uint64_t*)d_off.p, (int)n, d_out.p, nullptr));
   HIP_TRY(hipMemcpy(out, d_out.p, sizeof(pw_tx_summary) * (size_t)n, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// ---- CIGARs (include/pw_cigar.h; kernels in pw_cigar.hip) ----
+namespace {
+bool cigar_form_ok(int form) { return form == PW_CIGAR_EXTENDED || form == PW_CIGAR_CLASSIC; }
+}  // namespace
+int pw_batch_cigars(pw_batch* b, int form, void* stream) {
+  if (!b->traced) return fail("pw_batch_cigars before a traceback of the batch");
+  if (!cigar_form_ok(form)) return fail("pw_batch_cigars: unknown form (PW_CIGAR_EXTENDED or PW_CIGAR_CLASSIC)");
+  for (const pw::PairDesc& d : b->descs)
+    if ((int64_t)d.tx_cap >= (int64_t)PW_CIGAR_MAX_LEN) return fail("pw_batch_cigars: a transcript slot of 2^28 bytes or more (run lengths are 28 bits)");
+  const hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(hipSetDevice(b->device));
+  // (the offsets are rewritten in place: a write kernel of an earlier call on ANOTHER stream may still read them)
+  if (b->d_cigoffsets.p && st != b->cigar_stream)
+    for (auto& se : b->done_events) HIP_TRY(hipEventSynchronize(se.second.e));
+  b->cigar_stream = st;
+  HIP_TRY(b->d_cigoffsets.ensure(8 * ((size_t)b->n + 1)));
+  HIP_TRY(pw::launch_cigar_count(b->d_pairs.p, b->d_results.p, b->d_tx.p, b->n, form, (uint64_t*)b->d_cigoffsets.p, st));
+  // the one blocking read: the total sizes the run buffer
+  uint64_t total = 0;
+  HIP_TRY(hipMemcpyAsync(&total, (uint64_t*)b->d_cigoffsets.p + b->n, 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (!b->d_cigruns.p || total > b->cigar_room) {
+    // (a write of an earlier call may still run on another stream: the old buffer goes back to the pool only behind it)
+    for (auto& se : b->done_events) HIP_TRY(hipEventSynchronize(se.second.e));
+    HIP_TRY(b->d_cigruns.alloc(b->device, 4 * (size_t)std::max<uint64_t>(total, 4)));
+    b->cigar_room = std::max<uint64_t>(total, 4);
+  }
+  HIP_TRY(pw::launch_cigar_write(b->d_pairs.p, b->d_results.p, b->d_tx.p, b->n, form, (const uint64_t*)b->d_cigoffsets.p, b->d_cigruns.p, st));
+  b->cigar_total = total; b->cigar_seq = b->trace_seq; b->cigar_form = form;
+  return mark_done(b, st);
+}
+void* pw_batch_cigar_runs_device(pw_batch* b) { return b->d_cigruns.p; }
+void* pw_batch_cigar_offsets_device(pw_batch* b) { return b->d_cigoffsets.p; }
+uint64_t pw_batch_cigar_total(const pw_batch* b) { return b->d_cigoffsets.p ? b->cigar_total : 0; }
+int pw_batch_cigar(pw_batch* b, int form, uint32_t* runs_out, uint64_t cap, uint64_t* offsets_out) {
+  if (!b->traced) return fail("pw_batch_cigar before a traceback of the batch");
+  if (!cigar_form_ok(form)) return fail("pw_batch_cigar: unknown form (PW_CIGAR_EXTENDED or PW_CIGAR_CLASSIC)");
+  // (as for pw_batch_results: callers that launched on another stream synchronise it first)
+  if ((!b->d_cigruns.p || b->cigar_seq != b->trace_seq || b->cigar_form != form) && pw_batch_cigars(b, form, nullptr) != 0) return -1;
+  if (runs_out && b->cigar_total > cap) return fail("pw_batch_cigar: run buffer too small");
+  HIP_TRY(hipSetDevice(b->device));
+  if (offsets_out) HIP_TRY(hipMemcpy(offsets_out, b->d_cigoffsets.p, 8 * ((size_t)b->n + 1), hipMemcpyDeviceToHost));
+  if (runs_out && b->cigar_total) HIP_TRY(hipMemcpy(runs_out, b->d_cigruns.p, 4 * (size_t)b->cigar_total, hipMemcpyDeviceToHost));
+  return 0;
+}
+int pw_tx_cigar_packed(int device, const uint8_t* ops, const uint64_t* offsets, int64_t n, int form, uint32_t* runs_out, uint64_t cap,
+                       uint64_t* run_offsets_out) {
+  if (n < 0 || n > INT32_MAX) return fail("pw_tx_cigar_packed: transcript count out of range");
+  if (!cigar_form_ok(form)) return fail("pw_tx_cigar_packed: unknown form (PW_CIGAR_EXTENDED or PW_CIGAR_CLASSIC)");
+  if (n == 0) return 0;
+  if (!offsets || !run_offsets_out) return fail("pw_tx_cigar_packed: null offsets or output");
+  for (int64_t k = 0; k < n; k++) {
+    if (offsets[k + 1] < offsets[k]) return fail("pw_tx_cigar_packed: offsets must ascend");
+    if (offsets[k + 1] - offsets[k] >= (uint64_t)PW_CIGAR_MAX_LEN) return fail("pw_tx_cigar_packed: a transcript of 2^28 ops or more");
+  }
+  const uint64_t total = offsets[n];
+  if (total && !ops) return fail("pw_tx_cigar_packed: null ops with a non-zero total");
+  for (uint64_t k = offsets[0]; k < total; k++)
+    if (ops[k] != 'M' && ops[k] != 'S' && ops[k] != 'I' && ops[k] != 'D')
+      return fail("pw_tx_cigar_packed: byte " + std::to_string(k) + " is none of M, S, I, D");
+  HIP_TRY(hipSetDevice(device));
+  DeviceBuffer d_ops, d_off, d_roff, d_runs;
+  HIP_TRY(d_ops.ensure((size_t)total));
+  HIP_TRY(d_off.ensure(8 * ((size_t)n + 1)));
+  HIP_TRY(d_roff.ensure(8 * ((size_t)n + 1)));
+  if (total) HIP_TRY(hipMemcpy(d_ops.p, ops, (size_t)total, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_off.p, offsets, 8 * ((size_t)n + 1), hipMemcpyHostToDevice));
+  HIP_TRY(pw::launch_cigar_count_packed((const uint8_t*)d_ops.p, (const uint64_t*)d_off.p, (int)n, form, (uint64_t*)d_roff.p, nullptr));
+  std::vector<uint64_t> roff((size_t)n + 1);
+  HIP_TRY(hipMemcpy(roff.data(), d_roff.p, 8 * roff.size(), hipMemcpyDeviceToHost));
+  if (runs_out) {
+    if (roff[n] > cap) return fail("pw_tx_cigar_packed: run buffer too small");
+    HIP_TRY(d_runs.ensure(4 * (size_t)roff[n]));
+    HIP_TRY(pw::launch_cigar_write_packed((const uint8_t*)d_ops.p, (const uint64_t*)d_off.p, (int)n, form, (const uint64_t*)d_roff.p,
+                                          (uint32_t*)d_runs.p, nullptr));
+    if (roff[n]) HIP_TRY(hipMemcpy(runs_out, d_runs.p, 4 * (size_t)roff[n], hipMemcpyDeviceToHost));
+  }
+  memcpy(run_offsets_out, roff.data(), 8 * roff.size());
   return 0;
 }
 

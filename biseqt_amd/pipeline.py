@@ -11,7 +11,7 @@ the reference's, statement by statement.  ``map_queries`` is the many-queries-on
 import numpy as np
 
 from . import _pwlib as W
-from .batch import BatchAligner, DeviceArena, pack_reads, summary_dict
+from .batch import BatchAligner, DeviceArena, cigar_strings, pack_reads, summary_dict
 from .blot import WordBlot, WordBlotLocalRef
 from .overlap import _complement
 from .pw import Alignment
@@ -128,7 +128,7 @@ def query_interval(strand, mutant_start, len_aln, query_len):
 
 
 def map_queries(ref, queries, K_min, p_min, wordlen, g_max, sensitivity, keep=3, device=0, aligner_kw=None, alignments=True,
-                strands='+', complement=None):
+                strands='+', complement=None, cigar=None):
     """Map many short queries onto one reference sequence: Word-Blot local similarities of all queries in one pass
     (:meth:`WordBlotLocalRef.similar_segments_many`), then a banded local alignment of the best segments of every query,
     all in ONE lane-packed batch.  The flow of ``experiments/blot_ig_genotyping.py:45-101`` as a library function: per
@@ -154,11 +154,20 @@ def map_queries(ref, queries, K_min, p_min, wordlen, g_max, sensitivity, keep=3,
     (:func:`rank_segments`: a tie goes to ``'+'``) and the best ``keep`` aligned in the one batch.  Every record then also
     has ``strand`` and ``query_interval``: the half-open interval of the query AS GIVEN that the alignment covers
     (:func:`query_interval`; None without an alignment).  The seeding reads the forward letters only; for the alignment
-    step the device writes the reverse complement of every query behind the uploaded letters, once, before the seeding."""
+    step the device writes the reverse complement of every query behind the uploaded letters, once, before the seeding.
+
+    ``cigar``: None (the default: exactly the keys above and no further launch), ``'extended'`` (``=`` / ``X``) or
+    ``'classic'`` (``M``).  Every record then also has ``cigar``: the alignment as a CIGAR string with ``ref`` as the target
+    and the aligned sequence as the query (None without an alignment), run-length encoded on the device from the ops
+    (:meth:`BatchAligner.cigars`) in both ``alignments=`` modes -- with ``alignments=False`` still no transcript leaves the
+    device.  On the minus strand the CIGAR is in the frame of ``T = rc(query)`` against the forward reference, which is PAF's
+    and SAM's convention for ``-``: nothing is reversed."""
     assert isinstance(ref, Sequence) and all(isinstance(T, Sequence) for T in queries)
     queries = list(queries)
     if strands not in ('+', '-', 'both'):
         raise ValueError("strands is '+', '-' or 'both', not %r" % (strands,))
+    if cigar not in (None, 'extended', 'classic'):
+        raise ValueError("cigar is None, 'extended' or 'classic', not %r" % (cigar,))
     stranded = strands != '+'
     kw = dict(match_score=1, mismatch_score=-3, go_score=-5, ge_score=-2)
     kw.update(aligner_kw or {})
@@ -190,6 +199,8 @@ def map_queries(ref, queries, K_min, p_min, wordlen, g_max, sensitivity, keep=3,
                     rec.update(origin_start=None, mutant_start=None, summary=None)
                 if stranded:
                     rec.update(strand=seg['strand'], query_interval=None)
+                if cigar is not None:
+                    rec.update(cigar=None)
                 out[q].append(rec)
                 pairs.append((0, 1 + q + (nq if stranded and seg['strand'] == '-' else 0)))
                 bands.append(rec['diag_range'])
@@ -202,6 +213,8 @@ def map_queries(ref, queries, K_min, p_min, wordlen, g_max, sensitivity, keep=3,
                 txs = b.transcripts(res)
             else:
                 res, sums = _run_summarized(b)
+            if cigar is not None:
+                cgs = cigar_strings(*b.cigars(cigar))
     k = 0
     for q, recs in enumerate(out):
         for rec in recs:
@@ -224,10 +237,46 @@ def map_queries(ref, queries, K_min, p_min, wordlen, g_max, sensitivity, keep=3,
                 len_on_query = sum(tx.count(op) for op in 'MSI')
                 rec['p_aln'] = round(1. * tx.count('M') / len_on_query, 2) if len_on_query else None
                 rec['len_aln'] = len_on_query
+            if cigar is not None and rec['score'] is not None:
+                rec['cigar'] = cgs[k] or None
             if stranded and rec['len_aln'] is not None:
                 rec['query_interval'] = query_interval(rec['strand'], mutant_start, rec['len_aln'], len(queries[q]))
             k += 1
     return out
+
+
+def paf_lines(mapped, ref_name, ref_len, query_names, query_lens):
+    """The records of :func:`map_queries` (either ``alignments=`` mode, any ``strands``) as PAF: one line -- a ``str`` without
+    the newline -- per record that has an alignment, in the order of ``mapped``.  ``ref`` is the target.  Columns: query name,
+    query length, query start and end on the query AS GIVEN (``query_interval``; without strands ``mutant_start`` and
+    ``mutant_start + len_aln``), strand (``+`` for a record without a ``strand`` key), target name, target length, target start
+    (``origin_start``), target end (start + the letters of ``ref`` the alignment consumes), matches, alignment length (every
+    op), mapping quality 255 (not available).  Tags: ``AS:i:`` for an integral score, ``AS:f:`` for any other, and ``cg:Z:``
+    when the record has ``cigar``.  The op counts come from ``summary`` where there is one, otherwise from the transcript."""
+    lines = []
+    for q, recs in enumerate(mapped):
+        for rec in recs:
+            if rec['score'] is None:
+                continue
+            aln = rec.get('alignment')
+            if rec.get('summary') is not None:
+                n_match, n_subst, n_ins, n_del = (int(rec['summary'][f]) for f in ('n_match', 'n_subst', 'n_ins', 'n_del'))
+            else:
+                n_match, n_subst, n_ins, n_del = (aln.transcript.count(op) for op in 'MSID')
+            origin_start = rec['origin_start'] if aln is None else aln.origin_start
+            mutant_start = rec['mutant_start'] if aln is None else aln.mutant_start
+            if 'strand' in rec:
+                strand, (q_start, q_end) = rec['strand'], rec['query_interval']
+            else:
+                strand, q_start, q_end = '+', mutant_start, mutant_start + rec['len_aln']
+            score = float(rec['score'])
+            cols = [query_names[q], int(query_lens[q]), q_start, q_end, strand, ref_name, int(ref_len), origin_start,
+                    origin_start + n_match + n_subst + n_del, n_match, n_match + n_subst + n_ins + n_del, 255,
+                    'AS:i:%d' % int(score) if score == int(score) else 'AS:f:%r' % score]
+            if rec.get('cigar'):
+                cols.append('cg:Z:' + rec['cigar'])
+            lines.append('\t'.join(str(c) for c in cols))
+    return lines
 
 
 def local_homology_scan(S, T, K_min, p_min, wordlen, g_max=.3, sensitivity=.99, mask=(), device=0,
