@@ -109,13 +109,13 @@ def _jobs():
                  [os.path.join(HERE, 'pw_strip.hip')]))
     obj = os.path.join(OBJ_DIR, 'pw_seeds.o')
     jobs.append((obj, [HIPCC] + COMMON + ['-Wno-unused-parameter', '-c', os.path.join(HERE, 'pw_seeds.hip'), '-o', obj],
-                 [os.path.join(HERE, 'pw_seeds.hip'), os.path.join(HERE, 'pw_seed_kernels.h'), os.path.join(ROOT, 'include', 'pw_seeds.h')]))
+                 [os.path.join(HERE, 'pw_seeds.hip'), os.path.join(HERE, 'pw_seed_kernels.h'), os.path.join(HERE, 'pw_seed_host.h'), os.path.join(ROOT, 'include', 'pw_seeds.h')]))
     obj = os.path.join(OBJ_DIR, 'pw_mseeds.o')
     jobs.append((obj, [HIPCC] + COMMON + ['-Wno-unused-parameter', '-c', os.path.join(HERE, 'pw_mseeds.hip'), '-o', obj],
-                 [os.path.join(HERE, 'pw_mseeds.hip'), os.path.join(HERE, 'pw_seed_kernels.h'), os.path.join(ROOT, 'include', 'pw_mseeds.h')]))
+                 [os.path.join(HERE, 'pw_mseeds.hip'), os.path.join(HERE, 'pw_seed_kernels.h'), os.path.join(HERE, 'pw_seed_host.h'), os.path.join(ROOT, 'include', 'pw_mseeds.h')]))
     obj = os.path.join(OBJ_DIR, 'pw_qseeds.o')
     jobs.append((obj, [HIPCC] + COMMON + ['-Wno-unused-parameter', '-c', os.path.join(HERE, 'pw_qseeds.hip'), '-o', obj],
-                 [os.path.join(HERE, 'pw_qseeds.hip'), os.path.join(HERE, 'pw_seed_kernels.h'), os.path.join(HERE, 'pw_complement.h'),
+                 [os.path.join(HERE, 'pw_qseeds.hip'), os.path.join(HERE, 'pw_seed_kernels.h'), os.path.join(HERE, 'pw_seed_host.h'), os.path.join(HERE, 'pw_complement.h'),
                   os.path.join(ROOT, 'include', 'pw_qseeds.h')]))
     obj = os.path.join(OBJ_DIR, 'pw_overlap.o')
     jobs.append((obj, [HIPCC] + COMMON + ['-Wno-unused-parameter', '-c', os.path.join(HERE, 'pw_overlap.hip'), '-o', obj],

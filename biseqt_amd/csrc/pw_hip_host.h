@@ -1,5 +1,6 @@
-// pw_hip_host.h -- host-side plumbing shared by the seed index (pw_seeds.hip), overlap band selection (pw_overlap.hip)
-// and the batch API (pwlib_api.cpp): checked HIP calls, a device buffer and an event that free themselves, rocPRIM's
+// pw_hip_host.h -- host-side plumbing shared by the three seed indexes (pw_seeds.hip, pw_mseeds.hip and pw_qseeds.hip, through
+// pw_seed_host.h and pw_seed_kernels.h), overlap band selection (pw_overlap.hip), the complement table of the stranded paths
+// (pw_complement.h) and the batch API (pwlib_api.cpp): checked HIP calls, a device buffer and an event that free themselves, rocPRIM's
 // two-phase calls in one.  Device code: the two binary searches of the seed joins.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -27,8 +27,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "../../include/pw_mseeds.h"
-#include "pw_hip_host.h"
-#include "pw_seed_kernels.h"
+#include "pw_seed_host.h"
 
 namespace {
 
@@ -41,9 +40,7 @@ constexpr int kMaxSeqs = 16;
 struct SeqOffsets { int64_t koff[kMaxSeqs + 1]; };
 
 __device__ __forceinline__ uint64_t sat_mul(uint64_t a, uint64_t b) { return __umul64hi(a, b) ? ~0ull : a * b; }
-struct SatAdd {
-  __host__ __device__ uint64_t operator()(uint64_t a, uint64_t b) const { const uint64_t s = a + b; return s < a ? ~0ull : s; }
-};
+// (SatAdd: pw_seed_host.h)
 
 // ---- K9b ------------------------------------------------------------------------------------------------
 // lo[s * nk0 + e] / rl[s * nk0 + e]: start and length of the run of e's k-mer in sequence s (filled for run starts only).
@@ -221,25 +218,16 @@ __global__ __launch_bounds__(256) void k_mgraph_scan(const uint64_t* __restrict_
 }  // namespace
 
 struct pw_mseed_index {
-  int device = 0, L = 0, k = 0, n = 0, bits = 0;
-  bool key32 = false;                   // L^k fits 32 bits: 4-byte keys
+  int device = 0, n = 0;
+  WordSpace ws;
   int64_t len[kMaxSeqs] = {}, soff[kMaxSeqs + 1] = {}, nrows = -1;
   SeqOffsets so = {};
-  uint64_t kinv = 0;
   DeviceBuffer dseq, keys_in, pos_in, keys, pos, lo, rl, cnt, off, rows, tmp, scalar;
-  DeviceBuffer g_keys, g_order, g_srows, g_dstart, g_cnt, g_off, g_adj;     // neighbourhood graph (K9e)
-  int64_t g_edges = -1;
+  SeedGraph g;                          // neighbourhood graph (K9e); g.npts: the rows
+  DeviceBuffer g_srows, g_dstart;
   DeviceEvent ev0, ev1;
   float ms_build = 0.f, ms_graph = 0.f, ms_cc = 0.f, ms_count = 0.f;
 };
-
-static int elapsed(pw_mseed_index* x, hipStream_t st, float* ms) {
-  CHECK(hipEventRecord(x->ev1.e, st));
-  CHECK(hipEventSynchronize(x->ev1.e));
-  CHECK(hipEventElapsedTime(ms, x->ev0.e, x->ev1.e));
-  CHECK(hipGetLastError());
-  return 0;
-}
 
 // encode + sort every sequence, join on sequence 0: everything of pw_mseeds_build that depends on the key type
 template <typename K>
@@ -247,21 +235,14 @@ static int build_join(pw_mseed_index* x, hipStream_t st) {
   const int64_t nk_all = x->so.koff[x->n], nk0 = x->so.koff[1];
   int64_t nk_max = 1;
   for (int s = 0; s < x->n; s++) nk_max = std::max(nk_max, x->so.koff[s + 1] - x->so.koff[s]);
+  // every sequence sorts into its own piece of keys / pos through one pair of staging buffers: all sized here
   CHECK(x->keys.ensure((size_t)std::max<int64_t>(nk_all, 1) * sizeof(K))); CHECK(x->pos.ensure((size_t)std::max<int64_t>(nk_all, 1) * 4));
   CHECK(x->keys_in.ensure((size_t)nk_max * sizeof(K))); CHECK(x->pos_in.ensure((size_t)nk_max * 4));
   const MaskSets none = {};
-  for (int s = 0; s < x->n; s++) {
-    const int64_t nk = x->so.koff[s + 1] - x->so.koff[s];
-    if (nk <= 0) continue;
-    K* ko = (K*)x->keys.p + x->so.koff[s];
-    uint32_t* po = (uint32_t*)x->pos.p + x->so.koff[s];
-    hipLaunchKernelGGL((k_encode<K>), dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, st, (const uint8_t*)x->dseq.p + x->soff[s],
-                       x->len[s], x->k, x->L, x->kinv, none, (K*)x->keys_in.p, (uint32_t*)x->pos_in.p);
-    CHECK(rocprim_run(x->tmp, [&](void* t, size_t& b) {
-      return rocprim::radix_sort_pairs(t, b, (const K*)x->keys_in.p, ko, (const uint32_t*)x->pos_in.p, po, (size_t)nk, 0u,
-                                       (unsigned)x->bits, st);
-    }));
-  }
+  for (int s = 0; s < x->n; s++)
+    if (encode_sort<K>(set_err, x->ws, none, (const uint8_t*)x->dseq.p + x->soff[s], x->len[s], x->so.koff[s + 1] - x->so.koff[s], x->keys_in,
+                       x->pos_in, x->tmp, x->keys, x->pos, x->so.koff[s], st) != 0)
+      return -1;
   hipLaunchKernelGGL((k_mjoin<K>), dim3((unsigned)((nk0 + 255) / 256)), dim3(256), 0, st, (const K*)x->keys.p, x->so, x->n,
                      (uint32_t*)x->lo.p, (uint32_t*)x->rl.p, (uint64_t*)x->cnt.p);
   return 0;
@@ -274,10 +255,8 @@ const char* pw_mseeds_last_error(void) { return g_err.c_str(); }
 pw_mseed_index* pw_mseeds_create(int device, const uint8_t* const* seqs, const int64_t* lens, int n_seqs,
                                  int alphabet_len, int wordlen) {
   if (n_seqs < 2 || n_seqs > kMaxSeqs) { set_err("n_seqs must be 2..16"); return nullptr; }
-  if (alphabet_len < 1 || alphabet_len > 36) { set_err("alphabet_len must be 1..36 (kmers.py:266)"); return nullptr; }
-  if (wordlen < 1 || wordlen > 31) { set_err("wordlen must be 1..31 (kmers.py:269)"); return nullptr; }
-  long double lk = 1; for (int i = 0; i < wordlen; i++) lk *= alphabet_len;
-  if (lk >= (long double)(1ull << 62)) { set_err("alphabet_len ^ wordlen must be below 2^62"); return nullptr; }
+  WordSpace ws;
+  if (check_word(set_err, alphabet_len, wordlen) != 0 || word_space(set_err, alphabet_len, wordlen, false, &ws) != 0) return nullptr;
   int64_t total = 0;
   for (int s = 0; s < n_seqs; s++) {             // all lengths first: nothing is read before they are known to be sane
     if (lens[s] < 0) { set_err("negative sequence length"); return nullptr; }
@@ -291,12 +270,7 @@ pw_mseed_index* pw_mseeds_create(int device, const uint8_t* const* seqs, const i
   }
   if (hipSetDevice(device) != hipSuccess) { set_err("hipSetDevice failed"); return nullptr; }
   pw_mseed_index* x = new pw_mseed_index();
-  x->device = device; x->L = alphabet_len; x->k = wordlen; x->n = n_seqs;
-  uint64_t kinv = 1; for (int i = 0; i < wordlen; i++) kinv *= (uint64_t)alphabet_len;
-  x->kinv = kinv;
-  const uint64_t kmax = kinv > 1 ? kinv - 1 : 1;
-  x->bits = 1; while ((kmax >> x->bits) != 0) x->bits++;
-  x->key32 = kinv < 0xffffffffull;
+  x->device = device; x->ws = ws; x->n = n_seqs;
   for (int s = 0; s < n_seqs; s++) {
     x->len[s] = lens[s];
     x->soff[s + 1] = x->soff[s] + lens[s];
@@ -320,7 +294,7 @@ int pw_mseeds_build(pw_mseed_index* x, int64_t max_rows, void* stream) {
   // default: the rows (4 N bytes each) within 16 GB; never above 2^31 - 1 rows (int32 row indices in the graph)
   if (max_rows <= 0) max_rows = (16ll << 30) / (4ll * x->n);
   max_rows = std::min<int64_t>(max_rows, (1ll << 31) - 1);
-  x->nrows = -1; x->g_edges = -1;
+  x->nrows = -1; x->g.edges = -1; x->g.npts = -1;
   CHECK(hipEventRecord(x->ev0.e, st));
   CHECK(x->scalar.ensure(16));
   const int64_t nk0 = x->so.koff[1];
@@ -330,7 +304,7 @@ int pw_mseeds_build(pw_mseed_index* x, int64_t max_rows, void* stream) {
   if (!empty) {
     CHECK(x->lo.ensure((size_t)nk0 * x->n * 4)); CHECK(x->rl.ensure((size_t)nk0 * x->n * 4));
     CHECK(x->cnt.ensure((size_t)nk0 * 8)); CHECK(x->off.ensure((size_t)nk0 * 8));
-    if ((x->key32 ? build_join<uint32_t>(x, st) : build_join<uint64_t>(x, st)) != 0) return -1;
+    if ((x->ws.key32 ? build_join<uint32_t>(x, st) : build_join<uint64_t>(x, st)) != 0) return -1;
     CHECK(rocprim_run(x->tmp, [&](void* t, size_t& b) {
       return rocprim::exclusive_scan(t, b, (const uint64_t*)x->cnt.p, (uint64_t*)x->off.p, (uint64_t)0, (size_t)nk0, SatAdd(), st);
     }));
@@ -339,15 +313,7 @@ int pw_mseeds_build(pw_mseed_index* x, int64_t max_rows, void* stream) {
     CHECK(hipMemcpyAsync(&total, x->scalar.p, 8, hipMemcpyDeviceToHost, st));
     CHECK(hipStreamSynchronize(st));
   }
-  if (total > (unsigned long long)max_rows) {
-    char msg[200];
-    if (total == ~0ull)
-      snprintf(msg, sizeof msg, "the seeds table would hold at least 2^64 - 1 rows (limit %lld): raise the word length", (long long)max_rows);
-    else
-      snprintf(msg, sizeof msg, "the seeds table would hold %llu rows (limit %lld): raise max_rows or the word length", total, (long long)max_rows);
-    set_err(msg);
-    return -1;
-  }
+  if (check_row_limit(set_err, total, max_rows) != 0) return -1;
   CHECK(x->rows.ensure((size_t)std::max<unsigned long long>(total, 1) * 4 * x->n));
   if (total > 0) {
     const dim3 g((unsigned)((total + kExpRows - 1) / kExpRows)), b(256);
@@ -357,7 +323,7 @@ int pw_mseeds_build(pw_mseed_index* x, int64_t max_rows, void* stream) {
     PW_MSEEDS_FOR_N(x->n, PW_LAUNCH_EXPAND)
 #undef PW_LAUNCH_EXPAND
   }
-  if (elapsed(x, st, &x->ms_build) != 0) return -1;
+  if (elapsed(set_err, x->ev0, x->ev1, st, &x->ms_build) != 0) return -1;
   x->nrows = (int64_t)total;
   return 0;
 }
@@ -406,7 +372,7 @@ int pw_mseeds_count_many(const pw_mseed_index* xc, int64_t n_boxes, const int32_
     PW_MSEEDS_FOR_N(x->n, PW_LAUNCH_COUNT)
 #undef PW_LAUNCH_COUNT
   }
-  if (elapsed(x, nullptr, &x->ms_count) != 0) return -1;
+  if (elapsed(set_err, x->ev0, x->ev1, nullptr, &x->ms_count) != 0) return -1;
   CHECK(hipMemcpy(counts, dcnt.p, (size_t)n_boxes * 8, hipMemcpyDeviceToHost));
   return 0;
 }
@@ -414,10 +380,11 @@ int pw_mseeds_count_many(const pw_mseed_index* xc, int64_t n_boxes, const int32_
 int64_t pw_mseeds_graph_build(pw_mseed_index* x, double d_coeff, double radius) {
   if (!x || x->nrows < 0) { set_err("pw_mseeds_graph_build before a successful pw_mseeds_build"); return -1; }
   if (!(d_coeff > 0) || !(radius >= 0)) { set_err("d_coeff must be positive and radius non-negative"); return -1; }
-  x->g_edges = -1;
+  SeedGraph& g = x->g;
+  g.edges = -1;
   CHECK(hipSetDevice(x->device));
-  const int64_t n = x->nrows;
-  if (n == 0) { x->g_edges = 0; x->ms_graph = 0.f; return 0; }
+  const int64_t n = g.npts = x->nrows;
+  if (n == 0) { g.edges = 0; x->ms_graph = 0.f; return 0; }
   CHECK(hipEventRecord(x->ev0.e, nullptr));
   const int N = x->n;
   // d_1 = i_1 - i_2 lies in (-len_2, len_1): bucket q = d_1 + len_2 in [0, nd)
@@ -427,91 +394,46 @@ int64_t pw_mseeds_graph_build(pw_mseed_index* x, double d_coeff, double radius) 
   const int win = wd > (double)nd ? (int)nd : (int)wd;
   DeviceBuffer kin, vin;
   CHECK(kin.ensure((size_t)n * 8)); CHECK(vin.ensure((size_t)n * 4));
-  CHECK(x->g_keys.ensure((size_t)n * 8)); CHECK(x->g_order.ensure((size_t)n * 4)); CHECK(x->g_srows.ensure((size_t)n * 4 * N));
-  CHECK(x->g_dstart.ensure((size_t)(nd + 1) * 4)); CHECK(x->g_cnt.ensure((size_t)n * 4)); CHECK(x->g_off.ensure((size_t)(n + 1) * 8));
+  CHECK(x->g_srows.ensure((size_t)n * 4 * N)); CHECK(x->g_dstart.ensure((size_t)(nd + 1) * 4));
   const dim3 grid((unsigned)((n + 255) / 256)), blk(256);
   hipLaunchKernelGGL(k_mgraph_keys, grid, blk, 0, nullptr, (const int32_t*)x->rows.p, n, N, nd_off, (uint64_t*)kin.p, (uint32_t*)vin.p);
-  int dbits = 1; while (((uint64_t)nd >> dbits) != 0) dbits++;
-  CHECK(rocprim_run(x->tmp, [&](void* t, size_t& b) {
-    return rocprim::radix_sort_pairs(t, b, (const uint64_t*)kin.p, (uint64_t*)x->g_keys.p, (const uint32_t*)vin.p, (uint32_t*)x->g_order.p,
-                                     (size_t)n, 0u, (unsigned)(32 + dbits), (hipStream_t) nullptr);
-  }));
-  hipLaunchKernelGGL(k_mgraph_gather, grid, blk, 0, nullptr, (const int32_t*)x->rows.p, (const uint32_t*)x->g_order.p, n, N,
+  if (graph_sort(set_err, g, x->tmp, kin, vin, n, 32 + bits_for((uint64_t)nd)) != 0) return -1;
+  hipLaunchKernelGGL(k_mgraph_gather, grid, blk, 0, nullptr, (const int32_t*)x->rows.p, (const uint32_t*)g.order.p, n, N,
                      (int32_t*)x->g_srows.p);
-  hipLaunchKernelGGL(k_graph_dstart, dim3((unsigned)((nd + 256) / 256)), blk, 0, nullptr, (const uint64_t*)x->g_keys.p, n, nd,
+  hipLaunchKernelGGL(k_graph_dstart, dim3((unsigned)((nd + 256) / 256)), blk, 0, nullptr, (const uint64_t*)g.keys.p, n, nd,
                      (uint32_t*)x->g_dstart.p);
-#define PW_LAUNCH_SCAN(N_)                                                                                               \
-  hipLaunchKernelGGL((k_mgraph_scan<N_, false>), grid, blk, 0, nullptr, (const uint64_t*)x->g_keys.p, (const uint32_t*)x->g_order.p, \
+  // the count pass (FILL_ = false: cnt) and the fill pass (off -> adj)
+#define PW_LAUNCH_SCAN(N_, FILL_, CNT_, OFF_, ADJ_)                                                                      \
+  hipLaunchKernelGGL((k_mgraph_scan<N_, FILL_>), grid, blk, 0, nullptr, (const uint64_t*)g.keys.p, (const uint32_t*)g.order.p,       \
                      (const int32_t*)x->g_srows.p, n, (const uint32_t*)x->g_dstart.p, (int)nd, nd_off, d_coeff, radius, win,       \
-                     (uint32_t*)x->g_cnt.p, (const uint64_t*)nullptr, (uint32_t*)nullptr)
-  PW_MSEEDS_FOR_N(N, PW_LAUNCH_SCAN)
+                     (uint32_t*)(CNT_), (const uint64_t*)(OFF_), (uint32_t*)(ADJ_))
+#define PW_LAUNCH_COUNT_PASS(N_) PW_LAUNCH_SCAN(N_, false, g.cnt.p, nullptr, nullptr)
+#define PW_LAUNCH_FILL_PASS(N_) PW_LAUNCH_SCAN(N_, true, nullptr, g.off.p, g.adj.p)
+  PW_MSEEDS_FOR_N(N, PW_LAUNCH_COUNT_PASS)
+  const int64_t total = graph_finish(set_err, g, x->tmp, x->scalar, (uint64_t*)kin.p, n, [&]() -> int {
+    PW_MSEEDS_FOR_N(N, PW_LAUNCH_FILL_PASS)
+    return 0;
+  });
+#undef PW_LAUNCH_FILL_PASS
+#undef PW_LAUNCH_COUNT_PASS
 #undef PW_LAUNCH_SCAN
-  // offsets = exclusive scan of the counts (64-bit)
-  uint64_t* wide = (uint64_t*)kin.p;              // reuse: n x 8 bytes
-  hipLaunchKernelGGL(k_widen, grid, blk, 0, nullptr, (const uint32_t*)x->g_cnt.p, n, wide);
-  CHECK(rocprim_run(x->tmp, [&](void* t, size_t& b) {
-    return rocprim::exclusive_scan(t, b, (const uint64_t*)wide, (uint64_t*)x->g_off.p, (uint64_t)0, (size_t)n, rocprim::plus<uint64_t>(), (hipStream_t) nullptr);
-  }));
-  hipLaunchKernelGGL(k_total, dim3(1), dim3(64), 0, nullptr, (const uint64_t*)x->g_off.p, (const uint64_t*)wide, n, (unsigned long long*)x->scalar.p);
-  unsigned long long total = 0;
-  CHECK(hipMemcpy(&total, x->scalar.p, 8, hipMemcpyDeviceToHost));
-  if (total >= (1ull << 32)) { set_err("the neighbourhood graph has more than 2^32 edges: use a smaller radius"); return -1; }
-  CHECK(hipMemcpy((uint64_t*)x->g_off.p + n, &total, 8, hipMemcpyHostToDevice));
-  CHECK(x->g_adj.ensure((size_t)std::max<unsigned long long>(total, 1) * 4));
-  if (total) {
-#define PW_LAUNCH_FILL(N_)                                                                                               \
-  hipLaunchKernelGGL((k_mgraph_scan<N_, true>), grid, blk, 0, nullptr, (const uint64_t*)x->g_keys.p, (const uint32_t*)x->g_order.p,  \
-                     (const int32_t*)x->g_srows.p, n, (const uint32_t*)x->g_dstart.p, (int)nd, nd_off, d_coeff, radius, win,       \
-                     (uint32_t*)nullptr, (const uint64_t*)x->g_off.p, (uint32_t*)x->g_adj.p)
-    PW_MSEEDS_FOR_N(N, PW_LAUNCH_FILL)
-#undef PW_LAUNCH_FILL
-  }
-  if (elapsed(x, nullptr, &x->ms_graph) != 0) return -1;
-  x->g_edges = (int64_t)total;
-  return x->g_edges;
+  if (total < 0) return -1;
+  if (elapsed(set_err, x->ev0, x->ev1, nullptr, &x->ms_graph) != 0) return -1;
+  g.edges = total;
+  return total;
 }
 
 int pw_mseeds_graph_counts(const pw_mseed_index* x, int32_t* counts, int64_t cap) {
-  if (!x || x->g_edges < 0) { set_err("pw_mseeds_graph_counts before a successful pw_mseeds_graph_build"); return -1; }
-  if (cap < x->nrows) { set_err("pw_mseeds_graph_counts: capacity too small"); return -1; }
-  CHECK(hipSetDevice(x->device));
-  if (x->nrows) CHECK(hipMemcpy(counts, x->g_cnt.p, (size_t)x->nrows * 4, hipMemcpyDeviceToHost));
-  return 0;
+  return graph_counts_to_host(set_err, "pw_mseeds_graph_counts", x, counts, cap);
 }
 
 int pw_mseeds_graph_fetch(const pw_mseed_index* x, int64_t* offsets, int32_t* neighbours) {
-  if (!x || x->g_edges < 0) { set_err("pw_mseeds_graph_fetch before a successful pw_mseeds_graph_build"); return -1; }
-  CHECK(hipSetDevice(x->device));
-  if (x->nrows == 0) { offsets[0] = 0; return 0; }
-  CHECK(hipMemcpy(offsets, x->g_off.p, (size_t)(x->nrows + 1) * 8, hipMemcpyDeviceToHost));
-  if (x->g_edges) CHECK(hipMemcpy(neighbours, x->g_adj.p, (size_t)x->g_edges * 4, hipMemcpyDeviceToHost));
-  return 0;
+  return graph_fetch_to_host(set_err, "pw_mseeds_graph_fetch", x, offsets, neighbours);
 }
 
 int pw_mseeds_graph_components(const pw_mseed_index* xc, const uint8_t* avail, int32_t* labels) {
   pw_mseed_index* x = const_cast<pw_mseed_index*>(xc);
-  if (!x || x->g_edges < 0) { set_err("pw_mseeds_graph_components before a successful pw_mseeds_graph_build"); return -1; }
-  const int64_t n = x->nrows;
-  if (n == 0) return 0;
-  CHECK(hipSetDevice(x->device));
-  DeviceBuffer av, par, flag;
-  CHECK(av.ensure((size_t)n)); CHECK(par.ensure((size_t)n * 4)); CHECK(flag.ensure(16));
-  CHECK(hipMemcpy(av.p, avail, (size_t)n, hipMemcpyHostToDevice));
-  CHECK(hipEventRecord(x->ev0.e, nullptr));
-  const dim3 grid((unsigned)((n + 255) / 256)), blk(256);
-  hipLaunchKernelGGL(k_cc_init, grid, blk, 0, nullptr, (const uint8_t*)av.p, n, (int*)par.p);
-  for (int it = 0; it < 10000; it++) {            // every round at least halves the number of roots still to merge
-    CHECK(hipMemsetAsync(flag.p, 0, 4, nullptr));
-    hipLaunchKernelGGL(k_cc_hook, grid, blk, 0, nullptr, (const uint64_t*)x->g_off.p, (const uint32_t*)x->g_cnt.p,
-                       (const uint32_t*)x->g_adj.p, n, (int*)par.p, (int*)flag.p);
-    hipLaunchKernelGGL(k_cc_compress, grid, blk, 0, nullptr, n, (int*)par.p);
-    int changed = 0;
-    CHECK(hipMemcpy(&changed, flag.p, 4, hipMemcpyDeviceToHost));
-    if (!changed) break;
-  }
-  if (elapsed(x, nullptr, &x->ms_cc) != 0) return -1;
-  CHECK(hipMemcpy(labels, par.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-  return 0;
+  return graph_components(set_err, "pw_mseeds_graph_components", x, avail, labels, x ? &x->ms_cc : nullptr, nullptr);
 }
 
 void pw_mseeds_destroy(pw_mseed_index* x) {

@@ -38,8 +38,7 @@
 
 #include "../../include/pw_qseeds.h"
 #include "pw_complement.h"
-#include "pw_hip_host.h"
-#include "pw_seed_kernels.h"
+#include "pw_seed_host.h"
 
 namespace {
 
@@ -47,9 +46,7 @@ thread_local std::string g_err;
 void set_err(const std::string& s) { g_err = s; }
 #define CHECK(call) PW_HIP_CHECK(set_err, call)
 
-struct SatAdd {
-  __host__ __device__ uint64_t operator()(uint64_t a, uint64_t b) const { const uint64_t s = a + b; return s < a ? ~0ull : s; }
-};
+// (SatAdd, bits_for: pw_seed_host.h)
 
 // ---- K10a -----------------------------------------------------------------------------------------------
 // pstart[q] = number of positions of the queries before q (pstart[nq] = npos); position t belongs to the last query whose
@@ -272,54 +269,32 @@ __global__ __launch_bounds__(256) void k_qgraph_scan(const uint64_t* __restrict_
   if (!FILL) cnt[o] = total - 1;                  // its own entry is removed (blot.py:371-372)
 }
 
-int bits_for(uint64_t maxval) { int b = 1; while ((maxval >> b) != 0) b++; return b; }
-
 }  // namespace
 
 struct pw_qseed_index {
-  int device = 0, L = 0, k = 0, bits = 0;
-  bool key32 = false, has_tab = false;  // L^k fits 32 bits: 4-byte keys; the direct-address table is filled
+  int device = 0;
+  WordSpace ws;
+  bool has_tab = false;                 // the direct-address table is filled
   int64_t nR = 0, nkR = 0, nq = -1, npos = 0, nrows = -1, max_qlen = 0;
-  uint64_t kinv = 0;
   DeviceBuffer dref, rkeys, rpos, tab;                                        // the reference: filled by create
   DeviceBuffer arena, meta, qid, lo, cnt, off, row_off, rows, tmp, scalar;    // the queries: filled by build
   DeviceBuffer comp;                                                          // the complement of a stranded build
-  DeviceBuffer g_keys, g_order, g_cnt, g_off, g_adj;                          // neighbourhood graph (K10d)
-  int64_t g_edges = -1;
+  SeedGraph g;                                                                // neighbourhood graph (K10d); g.npts: the rows
   int cc_rounds = 0;
   DeviceEvent ev0, ev1;
   float ms_build = 0.f, ms_graph = 0.f, ms_cc = 0.f, ms_count = 0.f;
 };
 
-static int elapsed(pw_qseed_index* x, hipStream_t st, float* ms) {
-  CHECK(hipEventRecord(x->ev1.e, st));
-  CHECK(hipEventSynchronize(x->ev1.e));
-  CHECK(hipEventElapsedTime(ms, x->ev0.e, x->ev1.e));
-  CHECK(hipGetLastError());
-  return 0;
-}
-
 // encode + sort the reference, fill the table: everything of pw_qseeds_create that depends on the key type
 template <typename K>
 static int index_reference(pw_qseed_index* x) {
-  const int64_t nk = x->nkR;
-  CHECK(x->rkeys.ensure((size_t)std::max<int64_t>(nk, 1) * sizeof(K))); CHECK(x->rpos.ensure((size_t)std::max<int64_t>(nk, 1) * 4));
-  if (nk <= 0) return 0;
   DeviceBuffer keys_in, pos_in;
-  CHECK(keys_in.ensure((size_t)nk * sizeof(K))); CHECK(pos_in.ensure((size_t)nk * 4));
   const MaskSets none = {};
-  hipLaunchKernelGGL((k_encode<K>), dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, nullptr, (const uint8_t*)x->dref.p, x->nR, x->k,
-                     x->L, x->kinv, none, (K*)keys_in.p, (uint32_t*)pos_in.p);
-  CHECK(rocprim_run(x->tmp, [&](void* t, size_t& b) {
-    return rocprim::radix_sort_pairs(t, b, (const K*)keys_in.p, (K*)x->rkeys.p, (const uint32_t*)pos_in.p, (uint32_t*)x->rpos.p,
-                                     (size_t)nk, 0u, (unsigned)x->bits, (hipStream_t) nullptr);
-  }));
-  // the direct-address table pays when the key space is small and dense enough (as pw_seeds_build decides): at most 2^26
-  // keys and on average no more than 64 keys between two consecutive k-mers of the reference
-  if (x->key32 && x->kinv <= (1ull << 26) && x->kinv / (uint64_t)nk <= 64) {
-    CHECK(x->tab.ensure((size_t)(x->kinv + 2) * 4));
-    hipLaunchKernelGGL((k_table_fill<K>), dim3((unsigned)((nk + 256) / 256)), dim3(256), 0, nullptr, (const K*)x->rkeys.p, nk, x->kinv,
-                       (uint32_t*)x->tab.p);
+  if (encode_sort<K>(set_err, x->ws, none, (const uint8_t*)x->dref.p, x->nR, x->nkR, keys_in, pos_in, x->tmp, x->rkeys, x->rpos, 0, nullptr) != 0)
+    return -1;
+  if (x->nkR <= 0) return 0;
+  if (table_pays(x->ws, x->nkR)) {
+    if (table_fill<K>(set_err, x->ws, (const K*)x->rkeys.p, x->nkR, x->tab, nullptr) != 0) return -1;
     x->has_tab = true;
   }
   CHECK(hipDeviceSynchronize());                  // (keys_in / pos_in are freed on return)
@@ -331,7 +306,7 @@ template <typename K>
 static void launch_match(pw_qseed_index* x, const uint8_t* arena, hipStream_t st) {
   const int64_t* meta = (const int64_t*)x->meta.p;                 // [offsets nq | pstart nq + 1 | lengths nq (int32)]
   hipLaunchKernelGGL((k_qmatch<K>), dim3((unsigned)((x->npos + 255) / 256)), dim3(256), 0, st, arena, meta,
-                     (const int32_t*)(meta + 2 * x->nq + 1), meta + x->nq, x->nq, x->npos, x->k, x->L, (const K*)x->rkeys.p, x->nkR,
+                     (const int32_t*)(meta + 2 * x->nq + 1), meta + x->nq, x->nq, x->npos, x->ws.k, x->ws.L, (const K*)x->rkeys.p, x->nkR,
                      x->has_tab ? (const uint32_t*)x->tab.p : (const uint32_t*)nullptr, (uint32_t*)x->qid.p, (uint32_t*)x->lo.p,
                      (uint64_t*)x->cnt.p, (int*)((unsigned long long*)x->scalar.p + 1));
 }
@@ -341,7 +316,7 @@ static void launch_match_stranded(pw_qseed_index* x, const uint8_t* arena, hipSt
   const int64_t* meta = (const int64_t*)x->meta.p;                 // [... | strands nq (uint8)] behind launch_match's block
   const int32_t* dlen = (const int32_t*)(meta + 2 * x->nq + 1);
   hipLaunchKernelGGL((k_qmatch_stranded<K>), dim3((unsigned)((x->npos + 255) / 256)), dim3(256), 0, st, arena, meta, dlen, meta + x->nq,
-                     (const uint8_t*)(meta + 2 * x->nq + 1 + (x->nq + 1) / 2 + 1), (const uint8_t*)x->comp.p, x->nq, x->npos, x->k, x->L,
+                     (const uint8_t*)(meta + 2 * x->nq + 1 + (x->nq + 1) / 2 + 1), (const uint8_t*)x->comp.p, x->nq, x->npos, x->ws.k, x->ws.L,
                      (const K*)x->rkeys.p, x->nkR, x->has_tab ? (const uint32_t*)x->tab.p : (const uint32_t*)nullptr, (uint32_t*)x->qid.p,
                      (uint32_t*)x->lo.p, (uint64_t*)x->cnt.p, (int*)((unsigned long long*)x->scalar.p + 1));
 }
@@ -357,14 +332,14 @@ static int build_queries(pw_qseed_index* x, const uint8_t* arena, uint64_t arena
   hipStream_t st = (hipStream_t)stream;
   if (max_rows <= 0) max_rows = 1ll << 30;
   max_rows = std::min<int64_t>(max_rows, (1ll << 31) - 1);
-  x->nrows = -1; x->nq = -1; x->g_edges = -1;
+  x->nrows = -1; x->nq = -1; x->g.edges = -1; x->g.npts = -1;
   const int64_t nq = n_queries;
   bool any_minus = false;                         // (none: the unstranded kernels, and the complement is not read)
   for (int64_t q = 0; strand && q < nq; q++) {
     if (strand[q] > 1) { set_err("strand " + std::to_string(q) + " must be 0 (as given) or 1 (reverse complement)"); return -1; }
     any_minus = any_minus || strand[q] == 1;
   }
-  if (any_minus && check_complement(set_err, complement, x->L) != 0) return -1;
+  if (any_minus && check_complement(set_err, complement, x->ws.L) != 0) return -1;
   // [offsets nq | pstart nq + 1 | lengths nq (int32) | strands nq (uint8), a stranded build's] in one block: one copy to
   // the device
   const size_t strand_at = (size_t)(2 * nq + 1 + (nq + 1) / 2 + 1);
@@ -387,7 +362,7 @@ static int build_queries(pw_qseed_index* x, const uint8_t* arena, uint64_t arena
   CHECK(hipSetDevice(x->device));
   CHECK(x->meta.ensure(meta.size() * 8));
   CHECK(x->row_off.ensure((size_t)(nq + 1) * 8));
-  if (any_minus && upload_complement(set_err, complement, x->L, x->comp) != 0) return -1;
+  if (any_minus && upload_complement(set_err, complement, x->ws.L, x->comp) != 0) return -1;
   CHECK(hipEventRecord(x->ev0.e, st));            // (the build's time includes its copies to the device)
   const uint8_t* darena = arena;
   if (!arena_on_device) {
@@ -402,8 +377,8 @@ static int build_queries(pw_qseed_index* x, const uint8_t* arena, uint64_t arena
   CHECK(x->qid.ensure(np1 * 4)); CHECK(x->lo.ensure(np1 * 4)); CHECK(x->cnt.ensure(np1 * 8)); CHECK(x->off.ensure(np1 * 8));
   x->nq = nq;                                     // (launch_match reads it; reset below on failure)
   if (npos > 0) {
-    if (!any_minus) { if (x->key32) launch_match<uint32_t>(x, darena, st); else launch_match<uint64_t>(x, darena, st); }
-    else if (x->key32) launch_match_stranded<uint32_t>(x, darena, st);
+    if (!any_minus) { if (x->ws.key32) launch_match<uint32_t>(x, darena, st); else launch_match<uint64_t>(x, darena, st); }
+    else if (x->ws.key32) launch_match_stranded<uint32_t>(x, darena, st);
     else launch_match_stranded<uint64_t>(x, darena, st);
     CHECK(rocprim_run(x->tmp, [&](void* t, size_t& b) {
       return rocprim::exclusive_scan(t, b, (const uint64_t*)x->cnt.p, (uint64_t*)x->off.p, (uint64_t)0, (size_t)npos, SatAdd(), st);
@@ -418,21 +393,13 @@ static int build_queries(pw_qseed_index* x, const uint8_t* arena, uint64_t arena
   x->nq = -1;
   if ((int)res[1] != 0) { set_err("letter outside the alphabet in a query"); return -1; }
   const unsigned long long total = res[0];
-  if (total > (unsigned long long)max_rows) {
-    char msg[200];
-    if (total == ~0ull)
-      snprintf(msg, sizeof msg, "the seeds table would hold at least 2^64 - 1 rows (limit %lld): raise the word length", (long long)max_rows);
-    else
-      snprintf(msg, sizeof msg, "the seeds table would hold %llu rows (limit %lld): raise max_rows or the word length", total, (long long)max_rows);
-    set_err(msg);
-    return -1;
-  }
+  if (check_row_limit(set_err, total, max_rows) != 0) return -1;
   CHECK(x->rows.ensure((size_t)std::max<unsigned long long>(total, 1) * 12));
   if (total > 0)
     hipLaunchKernelGGL(k_qexpand, dim3((unsigned)((total + kExpRows - 1) / kExpRows)), dim3(256), 0, st, (const uint64_t*)x->off.p, npos,
                        (int64_t)total, (const uint32_t*)x->qid.p, dmeta + nq, (const uint32_t*)x->lo.p, (const uint32_t*)x->rpos.p,
                        (int32_t*)x->rows.p);
-  if (elapsed(x, st, &x->ms_build) != 0) return -1;
+  if (elapsed(set_err, x->ev0, x->ev1, st, &x->ms_build) != 0) return -1;
   x->nq = nq; x->nrows = (int64_t)total;
   return 0;
 }
@@ -442,21 +409,15 @@ extern "C" {
 const char* pw_qseeds_last_error(void) { return g_err.c_str(); }
 
 pw_qseed_index* pw_qseeds_create(int device, const uint8_t* ref, int64_t n_ref, int alphabet_len, int wordlen) {
-  if (alphabet_len < 1 || alphabet_len > 36) { set_err("alphabet_len must be 1..36 (kmers.py:266)"); return nullptr; }
-  if (wordlen < 1 || wordlen > 31) { set_err("wordlen must be 1..31 (kmers.py:269)"); return nullptr; }
-  long double lk = 1; for (int i = 0; i < wordlen; i++) lk *= alphabet_len;
-  if (lk >= (long double)(1ull << 62)) { set_err("alphabet_len ^ wordlen must be below 2^62"); return nullptr; }
+  WordSpace ws;
+  if (check_word(set_err, alphabet_len, wordlen) != 0 || word_space(set_err, alphabet_len, wordlen, false, &ws) != 0) return nullptr;
   if (n_ref < 0 || n_ref >= (1ll << 31)) { set_err("reference length out of range (below 2^31)"); return nullptr; }
   if (n_ref > 0 && !ref) { set_err("null reference pointer"); return nullptr; }
   for (int64_t i = 0; i < n_ref; i++) if (ref[i] >= alphabet_len) { set_err("letter outside the alphabet in the reference"); return nullptr; }
   if (hipSetDevice(device) != hipSuccess) { set_err("hipSetDevice failed"); return nullptr; }
   pw_qseed_index* x = new pw_qseed_index();
-  x->device = device; x->L = alphabet_len; x->k = wordlen;
+  x->device = device; x->ws = ws;
   x->nR = n_ref; x->nkR = n_ref >= wordlen ? n_ref - wordlen + 1 : 0;
-  uint64_t kinv = 1; for (int i = 0; i < wordlen; i++) kinv *= (uint64_t)alphabet_len;
-  x->kinv = kinv;
-  x->bits = bits_for(kinv > 1 ? kinv - 1 : 1);
-  x->key32 = kinv < 0xffffffffull;
   if (x->dref.ensure((size_t)n_ref + 64) != hipSuccess || x->scalar.ensure(16) != hipSuccess || x->ev0.create() != hipSuccess ||
       x->ev1.create() != hipSuccess) {
     set_err("device allocation failed"); delete x; return nullptr;
@@ -464,7 +425,7 @@ pw_qseed_index* pw_qseeds_create(int device, const uint8_t* ref, int64_t n_ref, 
   if (n_ref && hipMemcpy(x->dref.p, ref, (size_t)n_ref, hipMemcpyHostToDevice) != hipSuccess) {
     set_err("copy of the reference to the device failed"); delete x; return nullptr;
   }
-  if ((x->key32 ? index_reference<uint32_t>(x) : index_reference<uint64_t>(x)) != 0) { delete x; return nullptr; }
+  if ((x->ws.key32 ? index_reference<uint32_t>(x) : index_reference<uint64_t>(x)) != 0) { delete x; return nullptr; }
   return x;
 }
 
@@ -524,7 +485,7 @@ int pw_qseeds_count_boxes(const pw_qseed_index* xc, int64_t n_boxes, const int32
   hipLaunchKernelGGL(k_qcount, dim3((unsigned)((n_boxes + 3) / 4)), dim3(256), 0, nullptr, (const int32_t*)x->rows.p,
                      (const uint64_t*)x->row_off.p, x->nq, n_boxes, d, d + nb, d + 2 * nb, d + 3 * nb, d + 4 * nb,
                      (unsigned long long*)dcnt.p);
-  if (elapsed(x, nullptr, &x->ms_count) != 0) return -1;
+  if (elapsed(set_err, x->ev0, x->ev1, nullptr, &x->ms_count) != 0) return -1;
   CHECK(hipMemcpy(counts, dcnt.p, nb * 8, hipMemcpyDeviceToHost));
   return 0;
 }
@@ -532,10 +493,11 @@ int pw_qseeds_count_boxes(const pw_qseed_index* xc, int64_t n_boxes, const int32
 int64_t pw_qseeds_graph_build(pw_qseed_index* x, double d_coeff, double radius) {
   if (!x || x->nrows < 0) { set_err("pw_qseeds_graph_build before a successful pw_qseeds_build"); return -1; }
   if (!(d_coeff > 0) || !(radius >= 0)) { set_err("d_coeff must be positive and radius non-negative"); return -1; }
-  x->g_edges = -1;
+  SeedGraph& g = x->g;
+  g.edges = -1;
   CHECK(hipSetDevice(x->device));
-  const int64_t n = x->nrows;
-  if (n == 0) { x->g_edges = 0; x->ms_graph = 0.f; return 0; }
+  const int64_t n = g.npts = x->nrows;
+  if (n == 0) { g.edges = 0; x->ms_graph = 0.f; return 0; }
   // d = i - j lies in (-max query length, nR): bucket d + max_qlen in [0, nd); a = i + j below nR + max_qlen
   const int64_t nd = x->nR + x->max_qlen + 1;
   KeyLayout kl;
@@ -555,81 +517,35 @@ int64_t pw_qseeds_graph_build(pw_qseed_index* x, double d_coeff, double radius) 
   const int win = wd > (double)nd ? (int)nd : (int)wd;
   DeviceBuffer kin, vin;
   CHECK(kin.ensure((size_t)n * 8)); CHECK(vin.ensure((size_t)n * 4));
-  CHECK(x->g_keys.ensure((size_t)n * 8)); CHECK(x->g_order.ensure((size_t)n * 4));
-  CHECK(x->g_cnt.ensure((size_t)n * 4)); CHECK(x->g_off.ensure((size_t)(n + 1) * 8));
   const dim3 grid((unsigned)((n + 255) / 256)), blk(256);
   hipLaunchKernelGGL(k_qgraph_keys, grid, blk, 0, nullptr, (const int32_t*)x->rows.p, n, kl, (uint64_t*)kin.p, (uint32_t*)vin.p);
-  CHECK(rocprim_run(x->tmp, [&](void* t, size_t& b) {
-    return rocprim::radix_sort_pairs(t, b, (const uint64_t*)kin.p, (uint64_t*)x->g_keys.p, (const uint32_t*)vin.p, (uint32_t*)x->g_order.p,
-                                     (size_t)n, 0u, (unsigned)(qbits + kl.dbits + kl.abits), (hipStream_t) nullptr);
-  }));
-  hipLaunchKernelGGL((k_qgraph_scan<false>), grid, blk, 0, nullptr, (const uint64_t*)x->g_keys.p, (const uint32_t*)x->g_order.p, n,
-                     (const uint64_t*)x->row_off.p, kl, (int)nd, d_coeff, radius, win, (uint32_t*)x->g_cnt.p, (const uint64_t*)nullptr,
+  if (graph_sort(set_err, g, x->tmp, kin, vin, n, qbits + kl.dbits + kl.abits) != 0) return -1;
+  hipLaunchKernelGGL((k_qgraph_scan<false>), grid, blk, 0, nullptr, (const uint64_t*)g.keys.p, (const uint32_t*)g.order.p, n,
+                     (const uint64_t*)x->row_off.p, kl, (int)nd, d_coeff, radius, win, (uint32_t*)g.cnt.p, (const uint64_t*)nullptr,
                      (uint32_t*)nullptr);
-  // offsets = exclusive scan of the counts (64-bit)
-  uint64_t* wide = (uint64_t*)kin.p;              // reuse: n x 8 bytes
-  hipLaunchKernelGGL(k_widen, grid, blk, 0, nullptr, (const uint32_t*)x->g_cnt.p, n, wide);
-  CHECK(rocprim_run(x->tmp, [&](void* t, size_t& b) {
-    return rocprim::exclusive_scan(t, b, (const uint64_t*)wide, (uint64_t*)x->g_off.p, (uint64_t)0, (size_t)n, rocprim::plus<uint64_t>(), (hipStream_t) nullptr);
-  }));
-  hipLaunchKernelGGL(k_total, dim3(1), dim3(64), 0, nullptr, (const uint64_t*)x->g_off.p, (const uint64_t*)wide, n, (unsigned long long*)x->scalar.p);
-  unsigned long long total = 0;
-  CHECK(hipMemcpy(&total, x->scalar.p, 8, hipMemcpyDeviceToHost));
-  if (total >= (1ull << 32)) { set_err("the neighbourhood graph has more than 2^32 edges: use a smaller radius"); return -1; }
-  CHECK(hipMemcpy((uint64_t*)x->g_off.p + n, &total, 8, hipMemcpyHostToDevice));
-  CHECK(x->g_adj.ensure((size_t)std::max<unsigned long long>(total, 1) * 4));
-  if (total)
-    hipLaunchKernelGGL((k_qgraph_scan<true>), grid, blk, 0, nullptr, (const uint64_t*)x->g_keys.p, (const uint32_t*)x->g_order.p, n,
-                       (const uint64_t*)x->row_off.p, kl, (int)nd, d_coeff, radius, win, (uint32_t*)nullptr, (const uint64_t*)x->g_off.p,
-                       (uint32_t*)x->g_adj.p);
-  if (elapsed(x, nullptr, &x->ms_graph) != 0) return -1;
-  x->g_edges = (int64_t)total;
-  return x->g_edges;
+  const int64_t total = graph_finish(set_err, g, x->tmp, x->scalar, (uint64_t*)kin.p, n, [&] {
+    hipLaunchKernelGGL((k_qgraph_scan<true>), grid, blk, 0, nullptr, (const uint64_t*)g.keys.p, (const uint32_t*)g.order.p, n,
+                       (const uint64_t*)x->row_off.p, kl, (int)nd, d_coeff, radius, win, (uint32_t*)nullptr, (const uint64_t*)g.off.p,
+                       (uint32_t*)g.adj.p);
+    return 0;
+  });
+  if (total < 0) return -1;
+  if (elapsed(set_err, x->ev0, x->ev1, nullptr, &x->ms_graph) != 0) return -1;
+  g.edges = total;
+  return total;
 }
 
 int pw_qseeds_graph_counts(const pw_qseed_index* x, int32_t* counts, int64_t cap) {
-  if (!x || x->g_edges < 0) { set_err("pw_qseeds_graph_counts before a successful pw_qseeds_graph_build"); return -1; }
-  if (cap < x->nrows) { set_err("pw_qseeds_graph_counts: capacity too small"); return -1; }
-  CHECK(hipSetDevice(x->device));
-  if (x->nrows) CHECK(hipMemcpy(counts, x->g_cnt.p, (size_t)x->nrows * 4, hipMemcpyDeviceToHost));
-  return 0;
+  return graph_counts_to_host(set_err, "pw_qseeds_graph_counts", x, counts, cap);
 }
 
 int pw_qseeds_graph_fetch(const pw_qseed_index* x, int64_t* offsets, int32_t* neighbours) {
-  if (!x || x->g_edges < 0) { set_err("pw_qseeds_graph_fetch before a successful pw_qseeds_graph_build"); return -1; }
-  CHECK(hipSetDevice(x->device));
-  if (x->nrows == 0) { offsets[0] = 0; return 0; }
-  CHECK(hipMemcpy(offsets, x->g_off.p, (size_t)(x->nrows + 1) * 8, hipMemcpyDeviceToHost));
-  if (x->g_edges) CHECK(hipMemcpy(neighbours, x->g_adj.p, (size_t)x->g_edges * 4, hipMemcpyDeviceToHost));
-  return 0;
+  return graph_fetch_to_host(set_err, "pw_qseeds_graph_fetch", x, offsets, neighbours);
 }
 
 int pw_qseeds_graph_components(const pw_qseed_index* xc, const uint8_t* avail, int32_t* labels) {
   pw_qseed_index* x = const_cast<pw_qseed_index*>(xc);
-  if (!x || x->g_edges < 0) { set_err("pw_qseeds_graph_components before a successful pw_qseeds_graph_build"); return -1; }
-  const int64_t n = x->nrows;
-  x->cc_rounds = 0;
-  if (n == 0) return 0;
-  CHECK(hipSetDevice(x->device));
-  DeviceBuffer av, par, flag;
-  CHECK(av.ensure((size_t)n)); CHECK(par.ensure((size_t)n * 4)); CHECK(flag.ensure(16));
-  CHECK(hipMemcpy(av.p, avail, (size_t)n, hipMemcpyHostToDevice));
-  CHECK(hipEventRecord(x->ev0.e, nullptr));
-  const dim3 grid((unsigned)((n + 255) / 256)), blk(256);
-  hipLaunchKernelGGL(k_cc_init, grid, blk, 0, nullptr, (const uint8_t*)av.p, n, (int*)par.p);
-  for (int it = 0; it < 10000; it++) {            // every round at least halves the number of roots still to merge
-    CHECK(hipMemsetAsync(flag.p, 0, 4, nullptr));
-    hipLaunchKernelGGL(k_cc_hook, grid, blk, 0, nullptr, (const uint64_t*)x->g_off.p, (const uint32_t*)x->g_cnt.p,
-                       (const uint32_t*)x->g_adj.p, n, (int*)par.p, (int*)flag.p);
-    hipLaunchKernelGGL(k_cc_compress, grid, blk, 0, nullptr, n, (int*)par.p);
-    int changed = 0;
-    CHECK(hipMemcpy(&changed, flag.p, 4, hipMemcpyDeviceToHost));
-    x->cc_rounds = it + 1;
-    if (!changed) break;
-  }
-  if (elapsed(x, nullptr, &x->ms_cc) != 0) return -1;
-  CHECK(hipMemcpy(labels, par.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-  return 0;
+  return graph_components(set_err, "pw_qseeds_graph_components", x, avail, labels, x ? &x->ms_cc : nullptr, x ? &x->cc_rounds : nullptr);
 }
 
 void pw_qseeds_destroy(pw_qseed_index* x) {

@@ -2,7 +2,8 @@
 // query-batched one (pw_qseeds.hip): the k-mer encoder (K5a), the direct-address table of the join (K5b), the diagonal
 // starts of K7's sorted points, the 64-bit widening and the last-offset read
 // used around rocPRIM's scans, and the connected components of a CSR graph (K7's hook / compress).  Kernels live in an
-// anonymous namespace: each translation unit gets its own copy.
+// anonymous namespace: each translation unit gets its own copy.  The three include it through pw_seed_host.h, which holds
+// the host code that launches most of these kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -46,7 +47,7 @@ __global__ __launch_bounds__(256) void k_encode(const uint8_t* __restrict__ seq,
 // ---- K5b's direct-address table ---------------------------------------------------------------------------
 // tab[q] = number of elements of the sorted keys `other` below q, for q = 0 .. kinv + 1: element i (the first of its run)
 // fills the keys after the previous run's key up to its own; one extra thread fills the tail.  (Used only when the keys
-// are dense enough that these gaps are short: see pw_seeds_build.)
+// are dense enough that these gaps are short: table_pays, pw_seed_host.h.)
 template <typename K>
 __global__ __launch_bounds__(256) void k_table_fill(const K* __restrict__ other, int64_t no, uint64_t kinv, uint32_t* __restrict__ tab) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;

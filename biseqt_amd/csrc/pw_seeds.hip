@@ -24,8 +24,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "../../include/pw_seeds.h"
-#include "pw_hip_host.h"
-#include "pw_seed_kernels.h"
+#include "pw_seed_host.h"
 
 namespace {
 
@@ -33,7 +32,7 @@ thread_local std::string g_err;
 void set_err(const std::string& s) { g_err = s; }
 #define CHECK(call) PW_HIP_CHECK(set_err, call)
 
-// (K5a k_encode, the CSR components k_cc_*, k_widen and k_total: pw_seed_kernels.h)
+// (K5a k_encode, the CSR components k_cc_*, k_widen and k_total: pw_seed_kernels.h; the host code around them: pw_seed_host.h)
 
 // ---- K5b ------------------------------------------------------------------------------------------------
 // other = sorted keys of T (or of S itself for a self comparison).  Two ways to find an element's run [lo, hi) in it:
@@ -197,53 +196,38 @@ __global__ __launch_bounds__(256) void k_graph_scan(const uint64_t* __restrict__
 }  // namespace
 
 struct pw_seed_index {
-  int device = 0, L = 0, k = 0, self = 0, bits = 0;
-  bool key32 = false;                   // L^k fits 32 bits: 4-byte keys
+  int device = 0, self = 0;
+  WordSpace ws;
   DeviceBuffer tab;                     // direct-address table of the join (small key spaces)
   int64_t nS = 0, nT = 0, nkS = 0, nkT = 0, nrows = -1;
-  uint64_t kinv = 0;
   MaskSets ms;
   DeviceBuffer dS, dT, keys_in, keys_s, keys_t, pos_in, pos_s, pos_t, lo, cnt, off, rows, tmp, scalar;
-  DeviceBuffer g_keys, g_order, g_dstart, g_cnt, g_off, g_adj, g_pts;     // neighbourhood graph (K7)
-  int64_t g_edges = -1, g_npts = -1;    // g_npts: points of the graph (= rows, or the mirrored non-trivial rows of a self comparison)
+  SeedGraph g;                          // neighbourhood graph (K7); g.npts: the rows, or the mirrored non-trivial rows of a self comparison
+  DeviceBuffer g_dstart, g_pts;
   DeviceEvent ev0, ev1;
   float ms_build = 0.f;
 };
 
-template <typename K>
-static int encode_sort(pw_seed_index* x, const uint8_t* seq, int64_t n, int64_t nk, DeviceBuffer& keys_out, DeviceBuffer& pos_out,
-                       hipStream_t st) {
-  CHECK(keys_out.ensure((size_t)std::max<int64_t>(nk, 1) * sizeof(K))); CHECK(pos_out.ensure((size_t)std::max<int64_t>(nk, 1) * 4));
-  if (nk <= 0) return 0;
-  CHECK(x->keys_in.ensure((size_t)nk * sizeof(K))); CHECK(x->pos_in.ensure((size_t)nk * 4));
-  hipLaunchKernelGGL((k_encode<K>), dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, st, seq, n, x->k, x->L, x->kinv, x->ms,
-                     (K*)x->keys_in.p, (uint32_t*)x->pos_in.p);
-  CHECK(rocprim_run(x->tmp, [&](void* t, size_t& b) {
-    return rocprim::radix_sort_pairs(t, b, (const K*)x->keys_in.p, (K*)keys_out.p, (const uint32_t*)x->pos_in.p, (uint32_t*)pos_out.p,
-                                     (size_t)nk, 0u, (unsigned)x->bits, st);
-  }));
-  return 0;
-}
-
 // encode + sort both sequences, join them: everything of pw_seeds_build that depends on the key type
 template <typename K>
 static int build_join(pw_seed_index* x, hipStream_t st, int64_t ns, bool count_only, unsigned long long total) {
+  const WordSpace& ws = x->ws;
   if (count_only) {
-    if (encode_sort<K>(x, (const uint8_t*)x->dS.p, x->nS, x->nkS, x->keys_s, x->pos_s, st) != 0) return -1;
-    if (!x->self && encode_sort<K>(x, (const uint8_t*)x->dT.p, x->nT, x->nkT, x->keys_t, x->pos_t, st) != 0) return -1;
+    if (encode_sort<K>(set_err, ws, x->ms, (const uint8_t*)x->dS.p, x->nS, x->nkS, x->keys_in, x->pos_in, x->tmp, x->keys_s, x->pos_s, 0, st) != 0)
+      return -1;
+    if (!x->self &&
+        encode_sort<K>(set_err, ws, x->ms, (const uint8_t*)x->dT.p, x->nT, x->nkT, x->keys_in, x->pos_in, x->tmp, x->keys_t, x->pos_t, 0, st) != 0)
+      return -1;
     if (ns <= 0) return 0;
     const K* other = x->self ? (const K*)x->keys_s.p : (const K*)x->keys_t.p;
     const int64_t no = x->self ? ns : x->nkT;
-    // the direct-address table pays when the key space is small and dense enough: at most 2^26 keys (256 MB of table) and on
-    // average no more than 64 keys between two consecutive elements of `other` (k_table_fill walks those gaps serially)
     const uint32_t* tab = nullptr;
-    if (x->key32 && x->kinv <= (1ull << 26) && no > 0 && x->kinv / (uint64_t)no <= 64) {
-      CHECK(x->tab.ensure((size_t)(x->kinv + 2) * 4));
-      hipLaunchKernelGGL((k_table_fill<K>), dim3((unsigned)((no + 256) / 256)), dim3(256), 0, st, other, no, x->kinv, (uint32_t*)x->tab.p);
+    if (table_pays(ws, no)) {
+      if (table_fill<K>(set_err, ws, other, no, x->tab, st) != 0) return -1;
       tab = (const uint32_t*)x->tab.p;
     }
     hipLaunchKernelGGL((k_match<K>), dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, st, (const K*)x->keys_s.p, ns,
-                       other, no, x->kinv, x->self, tab, (uint32_t*)x->lo.p, (uint64_t*)x->cnt.p);
+                       other, no, ws.kinv, x->self, tab, (uint32_t*)x->lo.p, (uint64_t*)x->cnt.p);
     return 0;
   }
   hipLaunchKernelGGL((k_expand<K>), dim3((unsigned)((total + kExpRows - 1) / kExpRows)), dim3(256), 0, st, (const uint64_t*)x->off.p, ns,
@@ -272,29 +256,20 @@ const char* pw_seeds_last_error(void) { return g_err.c_str(); }
 pw_seed_index* pw_seeds_create(int device, const uint8_t* S, int64_t nS, const uint8_t* T, int64_t nT,
                                int alphabet_len, int wordlen, const uint64_t* mask_sets, int n_masks,
                                int self_comp) {
-  if (alphabet_len < 1 || alphabet_len > 36) { set_err("alphabet_len must be 1..36 (kmers.py:266)"); return nullptr; }
-  if (wordlen < 1 || wordlen > 31) { set_err("wordlen must be 1..31 (kmers.py:269)"); return nullptr; }
+  if (check_word(set_err, alphabet_len, wordlen) != 0) return nullptr;
   if (n_masks < 0 || n_masks > kMaxMasks) { set_err("at most 16 mask sets"); return nullptr; }
   if (nS < 0 || nT < 0 || nS >= (1ll << 31) || nT >= (1ll << 31)) { set_err("sequence length out of range"); return nullptr; }
-  // L^k must fit: the masked key is L^k itself
-  long double lk = 1; for (int i = 0; i < wordlen; i++) lk *= alphabet_len;
-  if (lk >= (long double)(1ull << 62)) { set_err("alphabet_len ^ wordlen must be below 2^62"); return nullptr; }
+  WordSpace ws;
+  if (word_space(set_err, alphabet_len, wordlen, n_masks > 0, &ws) != 0) return nullptr;
   for (int64_t i = 0; i < nS; i++) if (S[i] >= alphabet_len) { set_err("letter outside the alphabet in S"); return nullptr; }
   if (self_comp < 0) self_comp = (nS == nT && (nS == 0 || memcmp(S, T, (size_t)nS) == 0)) ? 1 : 0;
   if (!self_comp) for (int64_t i = 0; i < nT; i++) if (T[i] >= alphabet_len) { set_err("letter outside the alphabet in T"); return nullptr; }
   if (hipSetDevice(device) != hipSuccess) { set_err("hipSetDevice failed"); return nullptr; }
   pw_seed_index* x = new pw_seed_index();
-  x->device = device; x->L = alphabet_len; x->k = wordlen; x->self = self_comp;
+  x->device = device; x->ws = ws; x->self = self_comp;
   x->nS = nS; x->nT = self_comp ? nS : nT;
   x->nkS = nS >= wordlen ? nS - wordlen + 1 : 0;
   x->nkT = self_comp ? x->nkS : (nT >= wordlen ? nT - wordlen + 1 : 0);
-  uint64_t kinv = 1; for (int i = 0; i < wordlen; i++) kinv *= (uint64_t)alphabet_len;
-  x->kinv = kinv;
-  // sort width: the largest key that occurs -- L^k - 1, or the masked key L^k when mask sets are given (for DNA words
-  // without masks that is 2k bits: k = 12 sorts in three 8-bit passes instead of four)
-  const uint64_t kmax = n_masks > 0 ? kinv : (kinv > 1 ? kinv - 1 : 1);
-  x->bits = 1; while ((kmax >> x->bits) != 0) x->bits++;
-  x->key32 = kinv < 0xffffffffull;
   x->ms.n = n_masks;
   for (int i = 0; i < kMaxMasks; i++) x->ms.set[i] = i < n_masks ? mask_sets[i] : 0;
   if (upload(x, S, T) != 0) { delete x; return nullptr; }
@@ -306,12 +281,12 @@ int pw_seeds_build(pw_seed_index* x, int64_t max_rows, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   CHECK(hipSetDevice(x->device));
   if (max_rows <= 0) max_rows = (1ll << 31) - 1;
-  x->nrows = -1; x->g_edges = -1; x->g_npts = -1;
+  x->nrows = -1; x->g.edges = -1; x->g.npts = -1;
   CHECK(hipEventRecord(x->ev0.e, st));
   const int64_t ns = x->nkS;
   CHECK(x->scalar.ensure(16));
   if (ns > 0) { CHECK(x->lo.ensure((size_t)ns * 4)); CHECK(x->cnt.ensure((size_t)ns * 8)); CHECK(x->off.ensure((size_t)ns * 8)); }
-  if ((x->key32 ? build_join<uint32_t>(x, st, ns, true, 0) : build_join<uint64_t>(x, st, ns, true, 0)) != 0) return -1;
+  if ((x->ws.key32 ? build_join<uint32_t>(x, st, ns, true, 0) : build_join<uint64_t>(x, st, ns, true, 0)) != 0) return -1;
   unsigned long long total = 0;
   if (ns > 0) {
     CHECK(rocprim_run(x->tmp, [&](void* t, size_t& b) {
@@ -322,18 +297,10 @@ int pw_seeds_build(pw_seed_index* x, int64_t max_rows, void* stream) {
     CHECK(hipMemcpyAsync(&total, x->scalar.p, 8, hipMemcpyDeviceToHost, st));
     CHECK(hipStreamSynchronize(st));
   }
-  if ((int64_t)total > max_rows) {
-    char msg[160];
-    snprintf(msg, sizeof msg, "the seeds table would hold %llu rows (limit %lld): raise max_rows or the word length", total, (long long)max_rows);
-    set_err(msg);
-    return -1;
-  }
+  if (check_row_limit(set_err, total, max_rows) != 0) return -1;    // (a sum of at most nS * nT: never saturated)
   CHECK(x->rows.ensure((size_t)std::max<unsigned long long>(total, 1) * 8));
-  if (total > 0 && (x->key32 ? build_join<uint32_t>(x, st, ns, false, total) : build_join<uint64_t>(x, st, ns, false, total)) != 0) return -1;
-  CHECK(hipEventRecord(x->ev1.e, st));
-  CHECK(hipEventSynchronize(x->ev1.e));
-  CHECK(hipEventElapsedTime(&x->ms_build, x->ev0.e, x->ev1.e));
-  CHECK(hipGetLastError());
+  if (total > 0 && (x->ws.key32 ? build_join<uint32_t>(x, st, ns, false, total) : build_join<uint64_t>(x, st, ns, false, total)) != 0) return -1;
+  if (elapsed(set_err, x->ev0, x->ev1, st, &x->ms_build) != 0) return -1;
   x->nrows = (int64_t)total;
   return 0;
 }
@@ -381,10 +348,10 @@ int64_t pw_seeds_kmers(const pw_seed_index* x, int which, int64_t* out, int64_t 
   DeviceBuffer keys, pos;
   CHECK(keys.ensure((size_t)nk * 8)); CHECK(pos.ensure((size_t)nk * 4));
   hipLaunchKernelGGL((k_encode<uint64_t>), dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, nullptr,
-                     (const uint8_t*)(t ? x->dT.p : x->dS.p), n, x->k, x->L, x->kinv, x->ms, (uint64_t*)keys.p, (uint32_t*)pos.p);
+                     (const uint8_t*)(t ? x->dT.p : x->dS.p), n, x->ws.k, x->ws.L, x->ws.kinv, x->ms, (uint64_t*)keys.p, (uint32_t*)pos.p);
   std::vector<uint64_t> h((size_t)nk);
   CHECK(hipMemcpy(h.data(), keys.p, (size_t)nk * 8, hipMemcpyDeviceToHost));
-  for (int64_t i = 0; i < nk; i++) out[i] = h[(size_t)i] >= x->kinv ? -1 : (int64_t)h[(size_t)i];
+  for (int64_t i = 0; i < nk; i++) out[i] = h[(size_t)i] >= x->ws.kinv ? -1 : (int64_t)h[(size_t)i];
   return nk;
 }
 
@@ -414,7 +381,8 @@ int pw_seeds_band_neighbours(const pw_seed_index* xc, const double* radius, int6
 int64_t pw_seeds_graph_build(pw_seed_index* x, double d_coeff, double radius) {
   if (!x || x->nrows < 0) { set_err("pw_seeds_graph_build before a successful pw_seeds_build"); return -1; }
   if (!(d_coeff > 0) || !(radius >= 0)) { set_err("d_coeff must be positive and radius non-negative"); return -1; }
-  x->g_edges = -1; x->g_npts = -1;
+  SeedGraph& g = x->g;
+  g.edges = -1; g.npts = -1;
   CHECK(hipSetDevice(x->device));
   const int2* pts = (const int2*)x->rows.p;
   int64_t n = x->nrows;
@@ -436,95 +404,53 @@ int64_t pw_seeds_graph_build(pw_seed_index* x, double d_coeff, double radius) {
     CHECK(hipDeviceSynchronize());
     pts = (const int2*)x->g_pts.p; n = np;
   }
-  x->g_npts = n;
-  if (n == 0) { x->g_edges = 0; return 0; }
+  g.npts = n;
+  if (n == 0) { g.edges = 0; return 0; }
   const int64_t nd = x->nS + x->nT + 1;
   const double wd = floor(radius / d_coeff) + 2;
   const int win = wd > (double)nd ? (int)nd : (int)wd;
   DeviceBuffer kin, vin;
-  CHECK(kin.ensure((size_t)n * 8)); CHECK(vin.ensure((size_t)n * 4));
-  CHECK(x->g_keys.ensure((size_t)n * 8)); CHECK(x->g_order.ensure((size_t)n * 4)); CHECK(x->g_dstart.ensure((size_t)(nd + 1) * 4));
-  CHECK(x->g_cnt.ensure((size_t)n * 4)); CHECK(x->g_off.ensure((size_t)(n + 1) * 8));
+  CHECK(kin.ensure((size_t)n * 8)); CHECK(vin.ensure((size_t)n * 4)); CHECK(x->g_dstart.ensure((size_t)(nd + 1) * 4));
   const dim3 grid((unsigned)((n + 255) / 256)), blk(256);
   hipLaunchKernelGGL(k_graph_keys, grid, blk, 0, nullptr, pts, n, (int)x->nT, (uint64_t*)kin.p, (uint32_t*)vin.p);
-  int dbits = 1; while (((uint64_t)nd >> dbits) != 0) dbits++;
-  CHECK(rocprim_run(x->tmp, [&](void* t, size_t& b) {
-    return rocprim::radix_sort_pairs(t, b, (const uint64_t*)kin.p, (uint64_t*)x->g_keys.p, (const uint32_t*)vin.p, (uint32_t*)x->g_order.p,
-                                     (size_t)n, 0u, (unsigned)(32 + dbits), (hipStream_t) nullptr);
-  }));
-  hipLaunchKernelGGL(k_graph_dstart, dim3((unsigned)((nd + 256) / 256)), blk, 0, nullptr, (const uint64_t*)x->g_keys.p, n, nd, (uint32_t*)x->g_dstart.p);
-  hipLaunchKernelGGL((k_graph_scan<false>), grid, blk, 0, nullptr, (const uint64_t*)x->g_keys.p, (const uint32_t*)x->g_order.p, n,
-                     (const uint32_t*)x->g_dstart.p, (int)nd, (int)x->nT, d_coeff, radius, win, (uint32_t*)x->g_cnt.p,
+  if (graph_sort(set_err, g, x->tmp, kin, vin, n, 32 + bits_for((uint64_t)nd)) != 0) return -1;
+  hipLaunchKernelGGL(k_graph_dstart, dim3((unsigned)((nd + 256) / 256)), blk, 0, nullptr, (const uint64_t*)g.keys.p, n, nd, (uint32_t*)x->g_dstart.p);
+  hipLaunchKernelGGL((k_graph_scan<false>), grid, blk, 0, nullptr, (const uint64_t*)g.keys.p, (const uint32_t*)g.order.p, n,
+                     (const uint32_t*)x->g_dstart.p, (int)nd, (int)x->nT, d_coeff, radius, win, (uint32_t*)g.cnt.p,
                      (const uint64_t*)nullptr, (uint32_t*)nullptr);
-  // offsets = exclusive scan of the counts (64-bit)
-  uint64_t* wide = (uint64_t*)kin.p;              // reuse: n x 8 bytes
-  hipLaunchKernelGGL(k_widen, grid, blk, 0, nullptr, (const uint32_t*)x->g_cnt.p, n, wide);
-  CHECK(rocprim_run(x->tmp, [&](void* t, size_t& b) {
-    return rocprim::exclusive_scan(t, b, (const uint64_t*)wide, (uint64_t*)x->g_off.p, (uint64_t)0, (size_t)n, rocprim::plus<uint64_t>(), (hipStream_t) nullptr);
-  }));
-  hipLaunchKernelGGL(k_total, dim3(1), dim3(64), 0, nullptr, (const uint64_t*)x->g_off.p, (const uint64_t*)wide, n, (unsigned long long*)x->scalar.p);
-  unsigned long long total = 0;
-  CHECK(hipMemcpy(&total, x->scalar.p, 8, hipMemcpyDeviceToHost));
-  if (total >= (1ull << 32)) { set_err("the neighbourhood graph has more than 2^32 edges: use a smaller radius"); return -1; }
-  CHECK(hipMemcpy((uint64_t*)x->g_off.p + n, &total, 8, hipMemcpyHostToDevice));
-  CHECK(x->g_adj.ensure((size_t)std::max<unsigned long long>(total, 1) * 4));
-  if (total) hipLaunchKernelGGL((k_graph_scan<true>), grid, blk, 0, nullptr, (const uint64_t*)x->g_keys.p, (const uint32_t*)x->g_order.p, n,
-                                (const uint32_t*)x->g_dstart.p, (int)nd, (int)x->nT, d_coeff, radius, win, (uint32_t*)nullptr,
-                                (const uint64_t*)x->g_off.p, (uint32_t*)x->g_adj.p);
-  CHECK(hipDeviceSynchronize());
+  const int64_t total = graph_finish(set_err, g, x->tmp, x->scalar, (uint64_t*)kin.p, n, [&] {
+    hipLaunchKernelGGL((k_graph_scan<true>), grid, blk, 0, nullptr, (const uint64_t*)g.keys.p, (const uint32_t*)g.order.p, n,
+                       (const uint32_t*)x->g_dstart.p, (int)nd, (int)x->nT, d_coeff, radius, win, (uint32_t*)nullptr,
+                       (const uint64_t*)g.off.p, (uint32_t*)g.adj.p);
+    return 0;
+  });
+  if (total < 0) return -1;
+  CHECK(hipDeviceSynchronize());                  // (no event timing: the pairwise ABI has no graph_ms)
   CHECK(hipGetLastError());
-  x->g_edges = (int64_t)total;
-  return x->g_edges;
+  g.edges = total;
+  return total;
 }
 
-int64_t pw_seeds_graph_num_points(const pw_seed_index* x) { return (x && x->g_edges >= 0) ? x->g_npts : -1; }
+int64_t pw_seeds_graph_num_points(const pw_seed_index* x) { return (x && x->g.edges >= 0) ? x->g.npts : -1; }
 
 int pw_seeds_graph_points(const pw_seed_index* x, int32_t* da, int64_t cap) {
-  if (!x || x->g_edges < 0) { set_err("pw_seeds_graph_points before a successful pw_seeds_graph_build"); return -1; }
-  if (cap < x->g_npts) { set_err("pw_seeds_graph_points: capacity too small"); return -1; }
+  if (!x || x->g.edges < 0) { set_err("pw_seeds_graph_points before a successful pw_seeds_graph_build"); return -1; }
+  if (cap < x->g.npts) { set_err("pw_seeds_graph_points: capacity too small"); return -1; }
   CHECK(hipSetDevice(x->device));
-  if (x->g_npts) CHECK(hipMemcpy(da, x->self ? x->g_pts.p : x->rows.p, (size_t)x->g_npts * 8, hipMemcpyDeviceToHost));
+  if (x->g.npts) CHECK(hipMemcpy(da, x->self ? x->g_pts.p : x->rows.p, (size_t)x->g.npts * 8, hipMemcpyDeviceToHost));
   return 0;
 }
 
 int pw_seeds_graph_counts(const pw_seed_index* x, int32_t* counts, int64_t cap) {
-  if (!x || x->g_edges < 0) { set_err("pw_seeds_graph_counts before a successful pw_seeds_graph_build"); return -1; }
-  if (cap < x->g_npts) { set_err("pw_seeds_graph_counts: capacity too small"); return -1; }
-  CHECK(hipSetDevice(x->device));
-  if (x->g_npts) CHECK(hipMemcpy(counts, x->g_cnt.p, (size_t)x->g_npts * 4, hipMemcpyDeviceToHost));
-  return 0;
+  return graph_counts_to_host(set_err, "pw_seeds_graph_counts", x, counts, cap);
 }
 
 int pw_seeds_graph_fetch(const pw_seed_index* x, int64_t* offsets, int32_t* neighbours) {
-  if (!x || x->g_edges < 0) { set_err("pw_seeds_graph_fetch before a successful pw_seeds_graph_build"); return -1; }
-  CHECK(hipSetDevice(x->device));
-  if (x->g_npts == 0) { offsets[0] = 0; return 0; }
-  CHECK(hipMemcpy(offsets, x->g_off.p, (size_t)(x->g_npts + 1) * 8, hipMemcpyDeviceToHost));
-  if (x->g_edges) CHECK(hipMemcpy(neighbours, x->g_adj.p, (size_t)x->g_edges * 4, hipMemcpyDeviceToHost));
-  return 0;
+  return graph_fetch_to_host(set_err, "pw_seeds_graph_fetch", x, offsets, neighbours);
 }
 
 int pw_seeds_graph_components(const pw_seed_index* x, const uint8_t* avail, int32_t* labels) {
-  if (!x || x->g_edges < 0) { set_err("pw_seeds_graph_components before a successful pw_seeds_graph_build"); return -1; }
-  const int64_t n = x->g_npts;
-  if (n == 0) return 0;
-  CHECK(hipSetDevice(x->device));
-  DeviceBuffer av, par, flag;
-  CHECK(av.ensure((size_t)n)); CHECK(par.ensure((size_t)n * 4)); CHECK(flag.ensure(16));
-  CHECK(hipMemcpy(av.p, avail, (size_t)n, hipMemcpyHostToDevice));
-  const dim3 grid((unsigned)((n + 255) / 256)), blk(256);
-  hipLaunchKernelGGL(k_cc_init, grid, blk, 0, nullptr, (const uint8_t*)av.p, n, (int*)par.p);
-  for (int it = 0; it < 10000; it++) {            // every round at least halves the number of roots still to merge
-    CHECK(hipMemsetAsync(flag.p, 0, 4, nullptr));
-    hipLaunchKernelGGL(k_cc_hook, grid, blk, 0, nullptr, (const uint64_t*)x->g_off.p, (const uint32_t*)x->g_cnt.p,
-                       (const uint32_t*)x->g_adj.p, n, (int*)par.p, (int*)flag.p);
-    hipLaunchKernelGGL(k_cc_compress, grid, blk, 0, nullptr, n, (int*)par.p);
-    int changed = 0;
-    CHECK(hipMemcpy(&changed, flag.p, 4, hipMemcpyDeviceToHost));
-    if (!changed) break;
-  }
-  CHECK(hipMemcpy(labels, par.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-  return 0;
+  return graph_components(set_err, "pw_seeds_graph_components", x, avail, labels, nullptr, nullptr);      // (neither timed nor counted)
 }
 
 void pw_seeds_destroy(pw_seed_index* x) {

@@ -22,8 +22,75 @@ from .kmers import check_limits, mask_bits
 from .sequence import Sequence
 
 
-class _Index(object):
+class _Handle(object):
+    """What the three index owners share: the library's error channel, the handle's lifetime, and the neighbourhood graph
+    of the index's points -- the rows of its table, except for a pairwise self comparison -- behind ``<_prefix>graph_*``."""
+    _prefix = None                                   # 'pw_seeds_', 'pw_mseeds_' or 'pw_qseeds_'
+    _edges = None                                    # edge count of the last graph_build; None before one
+
+    def _call(self, name, *args):
+        """``<_prefix><name>(handle, *args)``; a negative return raises with the library's message."""
+        r = getattr(self.lib, self._prefix + name)(self.handle, *args)
+        if r < 0:
+            raise RuntimeError('%s%s failed: %s' % (self._prefix, name, self.error()))
+        return r
+
+    def error(self):
+        return (getattr(self.lib, self._prefix + 'last_error')() or b'').decode('utf-8', 'replace')
+
+    def _num_points(self):
+        return self.num_rows()
+
+    def graph_build(self, d_coeff, radius):
+        """Neighbourhood graph of the points: max(|d - d'| * d_coeff, |a - a'|) <= radius -- for an N-way index with every
+        diagonal coordinate held to it, max_k |d_k c - d'_k c| <= radius and |a - a'| <= radius; for a query-batched one
+        query by query.  Returns the edge count."""
+        self._edges = self._call('graph_build', float(d_coeff), float(radius))
+        return self._edges
+
+    def graph_counts(self):
+        n = self._num_points()
+        out = np.zeros(max(n, 1), np.int32)
+        self._call('graph_counts', out.ctypes.data, n)
+        return out[:n]
+
+    def graph_fetch(self):
+        """CSR adjacency: (offsets[n + 1], neighbours[edges])."""
+        edges = self._edges or 0                     # (None before a graph_build: the library refuses the call below)
+        off = np.zeros(max(self._num_points(), 0) + 1, np.int64)
+        adj = np.zeros(max(edges, 1), np.int32)
+        self._call('graph_fetch', off.ctypes.data, adj.ctypes.data)
+        return off, adj[:edges]
+
+    def graph_components(self, avail):
+        n = self._num_points()
+        av = np.ascontiguousarray(avail, np.uint8)
+        assert av.size == n
+        out = np.full(max(n, 1), -1, np.int32)
+        self._call('graph_components', av.ctypes.data, out.ctypes.data)
+        return out[:n]
+
+    def close(self):
+        if getattr(self, 'handle', None):
+            getattr(self.lib, self._prefix + 'destroy')(self.handle)
+            self.handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class _Index(_Handle):
     """Thin owner of a ``pw_seed_index`` handle."""
+    _prefix = 'pw_seeds_'
 
     def __init__(self, S, T, wordlen, alphabet, mask=(), self_comp=-1, device=0):
         self.lib = W.load()
@@ -37,9 +104,6 @@ class _Index(object):
         if not self.handle:
             raise RuntimeError('pw_seeds_create failed: ' + self.error())
         self.built = False
-
-    def error(self):
-        return (self.lib.pw_seeds_last_error() or b'').decode('utf-8', 'replace')
 
     def build(self, max_rows=0, stream=None):
         if self.lib.pw_seeds_build(self.handle, max_rows, stream) != 0:
@@ -77,14 +141,6 @@ class _Index(object):
             raise RuntimeError('pw_seeds_band_neighbours failed: ' + self.error())
         return out[:n]
 
-    def graph_build(self, d_coeff, radius):
-        """Neighbourhood graph of the rows: max(|d - d'| * d_coeff, |a - a'|) <= radius.  Returns the edge count."""
-        e = self.lib.pw_seeds_graph_build(self.handle, float(d_coeff), float(radius))
-        if e < 0:
-            raise RuntimeError('pw_seeds_graph_build failed: ' + self.error())
-        self._edges = e
-        return e
-
     def graph_points(self):
         """(n, 2) int32 array of the graph's points (d, a): the rows, or for a self comparison the non-trivial rows
         each followed by its mirror image."""
@@ -94,30 +150,8 @@ class _Index(object):
             raise RuntimeError('pw_seeds_graph_points failed: ' + self.error())
         return out[:n]
 
-    def graph_counts(self):
-        n = self.lib.pw_seeds_graph_num_points(self.handle)
-        out = np.zeros(max(n, 1), np.int32)
-        if self.lib.pw_seeds_graph_counts(self.handle, out.ctypes.data, n) != 0:
-            raise RuntimeError('pw_seeds_graph_counts failed: ' + self.error())
-        return out[:n]
-
-    def graph_fetch(self):
-        """CSR adjacency: (offsets[n + 1], neighbours[edges])."""
-        n = self.lib.pw_seeds_graph_num_points(self.handle)
-        off = np.zeros(n + 1, np.int64)
-        adj = np.zeros(max(self._edges, 1), np.int32)
-        if self.lib.pw_seeds_graph_fetch(self.handle, off.ctypes.data, adj.ctypes.data) != 0:
-            raise RuntimeError('pw_seeds_graph_fetch failed: ' + self.error())
-        return off, adj[:self._edges]
-
-    def graph_components(self, avail):
-        n = self.lib.pw_seeds_graph_num_points(self.handle)
-        av = np.ascontiguousarray(avail, np.uint8)
-        assert av.size == n
-        out = np.full(max(n, 1), -1, np.int32)
-        if self.lib.pw_seeds_graph_components(self.handle, av.ctypes.data, out.ctypes.data) != 0:
-            raise RuntimeError('pw_seeds_graph_components failed: ' + self.error())
-        return out[:n]
+    def _num_points(self):
+        return self.lib.pw_seeds_graph_num_points(self.handle)
 
     def kmers(self, which):
         n = (self.nT if which else self.nS) - self.wordlen + 1
@@ -136,23 +170,6 @@ class _Index(object):
 
     def algorithmic_bytes(self):
         return self.lib.pw_seeds_algorithmic_bytes(self.handle)
-
-    def close(self):
-        if getattr(self, 'handle', None):
-            self.lib.pw_seeds_destroy(self.handle)
-            self.handle = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class SeedIndex(object):
@@ -240,8 +257,9 @@ class SeedIndex(object):
         self._idx.close()
 
 
-class _MIndex(object):
+class _MIndex(_Handle):
     """Thin owner of a ``pw_mseed_index`` handle (include/pw_mseeds.h)."""
+    _prefix = 'pw_mseeds_'
 
     def __init__(self, seqs, wordlen, alphabet, device=0):
         self.lib = W.load()
@@ -253,9 +271,6 @@ class _MIndex(object):
         if not self.handle:
             raise RuntimeError('pw_mseeds_create failed: ' + self.error())
         self._edges = None
-
-    def error(self):
-        return (self.lib.pw_mseeds_last_error() or b'').decode('utf-8', 'replace')
 
     def build(self, max_rows=0, stream=None):
         if self.lib.pw_mseeds_build(self.handle, max_rows, stream) != 0:
@@ -289,38 +304,6 @@ class _MIndex(object):
             raise RuntimeError('pw_mseeds_count_many failed: ' + self.error())
         return out[:len(lo)]
 
-    def graph_build(self, d_coeff, radius):
-        """Neighbourhood graph of the rows: max_k |d_k c - d'_k c| <= radius and |a - a'| <= radius."""
-        e = self.lib.pw_mseeds_graph_build(self.handle, float(d_coeff), float(radius))
-        if e < 0:
-            raise RuntimeError('pw_mseeds_graph_build failed: ' + self.error())
-        self._edges = e
-        return e
-
-    def graph_counts(self):
-        n = self.num_rows()
-        out = np.zeros(max(n, 1), np.int32)
-        if self.lib.pw_mseeds_graph_counts(self.handle, out.ctypes.data, n) != 0:
-            raise RuntimeError('pw_mseeds_graph_counts failed: ' + self.error())
-        return out[:n]
-
-    def graph_fetch(self):
-        """CSR adjacency: (offsets[rows + 1], neighbours[edges])."""
-        off = np.zeros(self.num_rows() + 1, np.int64)
-        adj = np.zeros(max(self._edges, 1), np.int32)
-        if self.lib.pw_mseeds_graph_fetch(self.handle, off.ctypes.data, adj.ctypes.data) != 0:
-            raise RuntimeError('pw_mseeds_graph_fetch failed: ' + self.error())
-        return off, adj[:self._edges]
-
-    def graph_components(self, avail):
-        n = self.num_rows()
-        av = np.ascontiguousarray(avail, np.uint8)
-        assert av.size == n
-        out = np.full(max(n, 1), -1, np.int32)
-        if self.lib.pw_mseeds_graph_components(self.handle, av.ctypes.data, out.ctypes.data) != 0:
-            raise RuntimeError('pw_mseeds_graph_components failed: ' + self.error())
-        return out[:n]
-
     def timings(self):
         """Device milliseconds of the last build, graph build, components and count_many calls (HIP events)."""
         L = self.lib
@@ -330,21 +313,11 @@ class _MIndex(object):
     def algorithmic_bytes(self):
         return self.lib.pw_mseeds_algorithmic_bytes(self.handle)
 
-    def close(self):
-        if getattr(self, 'handle', None):
-            self.lib.pw_mseeds_destroy(self.handle)
-            self.handle = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class _QIndex(object):
+class _QIndex(_Handle):
     """Thin owner of a ``pw_qseed_index`` handle (include/pw_qseeds.h): one reference sequence, indexed once, and the
     seeds of any number of queries against it per :meth:`build`."""
+    _prefix = 'pw_qseeds_'
 
     def __init__(self, ref, wordlen, alphabet, device=0):
         self.lib = W.load()
@@ -354,9 +327,6 @@ class _QIndex(object):
         if not self.handle:
             raise RuntimeError('pw_qseeds_create failed: ' + self.error())
         self._edges = None
-
-    def error(self):
-        return (self.lib.pw_qseeds_last_error() or b'').decode('utf-8', 'replace')
 
     def build(self, arena, offsets, lengths, max_rows=0, stream=None, strands=None, complement=None):
         """Seeds of the queries ``arena[offsets[q]:offsets[q] + lengths[q]]``.  ``arena`` is a uint8 array (the layout of
@@ -427,39 +397,6 @@ class _QIndex(object):
             raise RuntimeError('pw_qseeds_count_boxes failed: ' + self.error())
         return out[:n]
 
-    def graph_build(self, d_coeff, radius):
-        """Neighbourhood graph of the rows, query by query: max(|d - d'| * d_coeff, |a - a'|) <= radius."""
-        e = self.lib.pw_qseeds_graph_build(self.handle, float(d_coeff), float(radius))
-        if e < 0:
-            raise RuntimeError('pw_qseeds_graph_build failed: ' + self.error())
-        self._edges = e
-        return e
-
-    def graph_counts(self):
-        n = self.num_rows()
-        out = np.zeros(max(n, 1), np.int32)
-        if self.lib.pw_qseeds_graph_counts(self.handle, out.ctypes.data, n) != 0:
-            raise RuntimeError('pw_qseeds_graph_counts failed: ' + self.error())
-        return out[:n]
-
-    def graph_fetch(self):
-        """CSR adjacency: (offsets[rows + 1], neighbours[edges])."""
-        edges = self._edges or 0                     # (None before a graph_build: the library refuses the call below)
-        off = np.zeros(max(self.num_rows(), 0) + 1, np.int64)
-        adj = np.zeros(max(edges, 1), np.int32)
-        if self.lib.pw_qseeds_graph_fetch(self.handle, off.ctypes.data, adj.ctypes.data) != 0:
-            raise RuntimeError('pw_qseeds_graph_fetch failed: ' + self.error())
-        return off, adj[:edges]
-
-    def graph_components(self, avail):
-        n = self.num_rows()
-        av = np.ascontiguousarray(avail, np.uint8)
-        assert av.size == n
-        out = np.full(max(n, 1), -1, np.int32)
-        if self.lib.pw_qseeds_graph_components(self.handle, av.ctypes.data, out.ctypes.data) != 0:
-            raise RuntimeError('pw_qseeds_graph_components failed: ' + self.error())
-        return out[:n]
-
     def timings(self):
         """Device milliseconds of the last build, graph build, components and count_boxes calls (HIP events), and the hook
         rounds the components took."""
@@ -467,17 +404,6 @@ class _QIndex(object):
         return {'build': L.pw_qseeds_build_ms(self.handle), 'graph': L.pw_qseeds_graph_ms(self.handle),
                 'components': L.pw_qseeds_components_ms(self.handle), 'counts': L.pw_qseeds_count_ms(self.handle),
                 'rounds': L.pw_qseeds_components_rounds(self.handle)}
-
-    def close(self):
-        if getattr(self, 'handle', None):
-            self.lib.pw_qseeds_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 MAX_SEQS = 16

@@ -26,11 +26,14 @@ def _has(ref_hits, word, L):
 def test_the_constants_are_the_kernels():
     """The copies in qseeds_cases.py against the source they name."""
     import os
-    src = open(os.path.join(os.path.dirname(__file__), '..', 'biseqt_amd', 'csrc', 'pw_qseeds.hip')).read()
+    csrc = os.path.join(os.path.dirname(__file__), '..', 'biseqt_amd', 'csrc')
+    src = open(os.path.join(csrc, 'pw_qseeds.hip')).read()
+    host = open(os.path.join(csrc, 'pw_seed_host.h')).read()          # the table decision: shared by the seed indexes
     assert 'blockIdx.x * 256' in src and QC.MATCH_WG == 256
     assert 'constexpr int kExpRows = %d;' % QC.EXP_ROWS in src
     assert 'blockIdx.x * %d + (threadIdx.x >> 6)' % QC.BOX_WG in src and 'base += %d' % QC.BALLOT in src
-    assert 'x->kinv <= (1ull << 26) && x->kinv / (uint64_t)nk <= %d' % QC.TAB_SPARSITY in src and QC.TAB_MAX == 1 << 26
+    assert 'ws.kinv <= (1ull << 26) && ws.kinv / (uint64_t)n_other <= %d' % QC.TAB_SPARSITY in host and QC.TAB_MAX == 1 << 26
+    assert 'if (table_pays(x->ws, x->nkR))' in src
 
 
 # ---- k_qmatch ------------------------------------------------------------------------------------------------
