@@ -715,11 +715,12 @@ def test_tiled_kernel_forced(oracle):
                     assert txs[1] == r2['transcript'], kw
 
 
-def test_wide_table_kernels_natural_vs_oracle(oracle):
+def test_wide_table_kernels_natural_vs_oracle(oracle, monkeypatch):
     """A table wider than one workgroup holds (9000 x ~9000 standard mode, 18 000 diagonals) goes by itself to the
     strip pipeline (K2c: integer scores, simple scoring) or to the tiled kernel (K2b: f64 here); the oracle still
     fits (8e7 cells): score, end cell, start and transcript must be identical.  The wide pair shares its batch with
     small pairs that take the ordinary one-wavefront kernel."""
+    monkeypatch.setenv('PWLIB_NO_STRIP_REPAIR', '1')
     from biseqt_amd import synth, _pwlib as W
     from biseqt_amd.batch import BatchAligner
     rng = synth.rng_for(31)
@@ -742,11 +743,12 @@ def test_wide_table_kernels_natural_vs_oracle(oracle):
                 assert (res['origin_idx'][k], res['mutant_idx'][k]) == (r['origin_idx'], r['mutant_idx'])
 
 
-def test_strip_pipeline_forced_on_small_tables(oracle):
+def test_strip_pipeline_forced_on_small_tables(oracle, monkeypatch):
     """The strip pipeline (K2c, pw_strip.h) forced on standard-mode tables the oracle can check: all seven alignment
     types, seven score sets (linear and affine gaps, mismatch above match), 1 - 3 pairs per batch running one after
     another, every batch solved twice (FIFO granules of the first solve must never pass for fresh ones), tables from
     empty to 40 strips."""
+    monkeypatch.setenv('PWLIB_NO_STRIP_REPAIR', '1')
     import importlib.util
     spec = importlib.util.spec_from_file_location('strip_check', os.path.join(os.path.dirname(__file__), 'micro', 'strip_check.py'))
     sc = importlib.util.module_from_spec(spec)
@@ -758,12 +760,13 @@ def test_strip_pipeline_forced_on_small_tables(oracle):
     assert sc.run(cases=70, seed=20261006, maxlen=900, matrices=True) == 0
 
 
-def test_config3_full_size_properties():
+def test_config3_full_size_properties(monkeypatch):
     """BASELINE config 3: ONE 100 kb x ~100 kb pair, standard mode LOCAL, 1/-3/-5/-2 (1.0e10 cells, 200 k diagonals;
     the reference would need ~0.5 TB, so no oracle exists -- SURVEY 8c).  Size-independent check: re-scoring the
     transcript with the reference's rule reproduces the reported score, the path runs from the reported start to
     the reported end cell, every M / S agrees with the letters; and the score is at least that of the best
     alignment of a 6 kb window the oracle can solve."""
+    monkeypatch.setenv('PWLIB_NO_STRIP_REPAIR', '1')
     from biseqt_amd import synth
     from biseqt_amd.batch import BatchAligner
     rng = synth.rng_for(3)

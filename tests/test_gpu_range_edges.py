@@ -35,6 +35,8 @@ def _run(case, flags):
 def test_gpu_range_edge(case, monkeypatch, oracle):
     plan = planned(case, monkeypatch)
     check_plan(case, plan)
+    if plan['strips']:
+        monkeypatch.setenv('PWLIB_NO_STRIP_REPAIR', '1')
     flags = case.get('flags', 0)
     name, res, txs, packed = _run(case, flags)
     assert name == plan['kernel'], (case['id'], name, plan['kernel'])

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 from tests.helpers import dec, kw_of, load_golden
+from tests.plane_checks import bkw_of, check_masks, check_walks, okw_of
 
 pytestmark = pytest.mark.gpu
 
@@ -36,57 +37,6 @@ def table_cells(res, X, Y, mode):
         d = res['band'][0] + i
         out += [(i, a) for a in range(1 + min(d, 0) + min(X - d, Y))]
     return out
-
-
-def okw_of(kw):
-    out = dict(mode=kw['mode'], alntype=kw['alntype'], L=4, go=kw['go'], ge=kw['ge'])
-    if 'subst' in kw:
-        out['subst'] = kw['subst']
-    else:
-        out.update(match=kw['match'], mismatch=kw['mismatch'])
-    if 'diag_range' in kw:
-        out['diag_range'] = kw['diag_range']
-    return out
-
-
-def bkw_of(kw):
-    out = dict(alnmode=kw['mode'], alntype=kw['alntype'], alphabet_len=4, go_score=kw['go'], ge_score=kw['ge'])
-    if 'subst' in kw:
-        out['subst_scores'] = kw['subst']
-    else:
-        out.update(match_score=kw['match'], mismatch_score=kw['mismatch'])
-    if 'diag_range' in kw:
-        out['diag_range'] = kw['diag_range']
-    return out
-
-
-def check_masks(oracle, b, k, o, m, okw, no_m, label):
-    want = oracle.solve(o, m, want_table=True, **okw)
-    got = b.masks(k)
-    bits = 7 if no_m else 15
-    if no_m:
-        assert okw['go'] <= 0, label
-    assert got.shape == want['mask'].shape, label
-    bad = np.nonzero((got & bits) != (want['mask'] & bits))[0]
-    assert bad.size == 0, (label, k, '%d of %d cells differ' % (bad.size, got.size), bad[:8].tolist())
-    return want
-
-
-def check_walks(oracle, o, m, okw, ends, res, txs, label):
-    for k, e in enumerate(ends):
-        if e[0] < 0:
-            assert res['tx_len'][k] == 0 and res['status'][k] == 0, (label, k)
-            continue
-        r = oracle.traceback_from(o, m, e, **okw)
-        if r['no_choice']:
-            continue
-        st = int(res['status'][k])
-        assert st & 1 and not st & 8, (label, e, st)
-        g = (txs[k] or '', (int(res['origin_idx'][k]), int(res['mutant_idx'][k])), bool(st & 4),
-             bool(st & 2) and not st & 4)
-        assert g[1:] == (r['start'], r['would_panick'], r['tb_null']), (label, e, g, r)
-        if not st & 2:
-            assert g[0] == r['ops'], (label, e)
 
 
 def pick_ends(cells, seed):
@@ -160,9 +110,10 @@ def test_family_masks_and_walks_from_any_end(fam, oracle, monkeypatch):
     check_walks(oracle, o, m, okw, ends, res, txs, '%s on %s' % (fid, name))
 
 
-def test_strips_forced_masks_and_repeated_walks(oracle):
+def test_strips_forced_masks_and_repeated_walks(oracle, monkeypatch):
     """Small tables forced onto the strip pipeline (layout 1): X = 0, 1, 63 (mod 64) and flat tables, byte rows and a
     matrix; every cell's mask, then traceback_from again and again on one solved batch."""
+    monkeypatch.setenv('PWLIB_NO_STRIP_REPAIR', '1')
     from biseqt_amd import _pwlib as W
     from biseqt_amd.batch import BatchAligner
     shapes = [(128, 40), (129, 70), (127, 33), (64, 3), (191, 100)]
@@ -186,8 +137,9 @@ def test_strips_forced_masks_and_repeated_walks(oracle):
                     check_walks(oracle, o, m, okw, [e], res[:1], b.transcripts(res)[:1], 'strips %dx%d' % (X, Y))
 
 
-def test_natural_wide_strip_pair_masks_and_walks(oracle):
+def test_natural_wide_strip_pair_masks_and_walks(oracle, monkeypatch):
     """A 9 kb x 9 kb pair goes to the strips by itself: its whole plane (8e7 cells) and walks from sampled cells."""
+    monkeypatch.setenv('PWLIB_NO_STRIP_REPAIR', '1')
     from biseqt_amd.batch import BatchAligner
     o, m = related(9000, 31)
     kw = dict(mode=0, alntype=1, **SC)
