@@ -1,7 +1,7 @@
 // pw_hip_host.h -- host-side plumbing shared by the three seed indexes (pw_seeds.hip, pw_mseeds.hip and pw_qseeds.hip, through
 // pw_seed_host.h and pw_seed_kernels.h), overlap band selection (pw_overlap.hip), the complement table of the stranded paths
 // (pw_complement.h) and the batch API (pwlib_api.cpp): checked HIP calls, a device buffer and an event that free themselves, rocPRIM's
-// two-phase calls in one.  Device code: the two binary searches of the seed joins.
+// two-phase calls in one, the width of a sort-key field (bits_for).  Device code: the two binary searches of the seed joins.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -55,6 +55,9 @@ hipError_t rocprim_run(DeviceBuffer& scratch, F&& f) {
   if (e == hipSuccess) e = scratch.ensure(bytes);
   return e == hipSuccess ? f(scratch.p, bytes) : e;
 }
+
+// the width of a sort-key field that holds 0 .. maxval
+inline int bits_for(uint64_t maxval) { int b = 1; while ((maxval >> b) != 0) b++; return b; }
 
 // First index of the ascending a[0, n) whose element is >= key (lower) / > key (upper).
 template <typename K>

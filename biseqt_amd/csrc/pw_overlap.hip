@@ -6,9 +6,13 @@
 //                     is one seed: atomicAdd into the pair's per-diagonal histogram (rows are never written), the
 //                     pair's row count, and atomicMin of the element index (-> the first row in table order)
 //   K8c k_band_select one workgroup per pair: prefix sums of the histogram, then for every occupied diagonal the
-//                     window of diagonals within 1 on the axis d / r(d) (binary searches on the reference's own
-//                     floating-point predicate; d / r(d) is monotone in d), n(d), w(d); block reduction to the
-//                     best diagonal, the tie count and the seed count of its band
+//                     window of diagonals within 1 on the axis d / r(d) (the reference's own floating-point
+//                     predicate; d / r(d) is monotone in d), n(d), w(d); block reduction to the best diagonal, the
+//                     tie count and the seed count of its band
+//   K8d k_band_small  at most 64 seeds: one wavefront per pair, from the seed list
+//   K8e k_band_medium 65 .. 2048 seeds (all-pairs path): one workgroup per pair, from the seed list in LDS
+// K8c, K8d and K8e differ only in how they count the seeds of a window: the window (ov_window), the score (band_w), the order
+// of two diagonals (better), the tie rule (tie_threshold, ties) and the record (band_record) exist once; records are byte-identical.
 // All floating point is IEEE double in the reference's operation order (compiled with -ffp-contract=off).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -32,6 +36,20 @@ void set_err(const std::string& s) { g_err = s; }
 
 struct DPair { uint64_t s_off, t_off; int32_t s_len, t_len; uint64_t hbase; };   // hbase: start of its histogram
 
+// the k-mer s[0], s[1], ... s[k - 1], in base L
+__device__ __forceinline__ uint64_t kmer_fwd(const uint8_t* __restrict__ s, int k, int L) {
+  uint64_t v = 0;
+  for (int t = 0; t < k; t++) v = v * (uint64_t)L + s[t];
+  return v;
+}
+// The k-mer at position q of rc(read), never materialised: comp(read[len - 1 - q]), comp(read[len - 2 - q]), ... -- read
+// backwards from the forward letters, s_last = &read[len - 1 - q].  q <= len - k, so s_last[-t] stays inside the read.
+__device__ __forceinline__ uint64_t kmer_rc(const uint8_t* __restrict__ s_last, int k, int L, const uint8_t* s_comp) {
+  uint64_t v = 0;
+  for (int t = 0; t < k; t++) v = v * (uint64_t)L + s_comp[s_last[-t]];
+  return v;
+}
+
 // side 0: S reads, side 1: T reads.  start[p] = index of pair p's first k-mer on this side (start[n] = total).
 __global__ __launch_bounds__(256) void k_enc_batch(const uint8_t* __restrict__ arena, const DPair* __restrict__ pairs,
                                                    const uint64_t* __restrict__ start, int64_t npairs, int64_t total, int side,
@@ -41,15 +59,11 @@ __global__ __launch_bounds__(256) void k_enc_batch(const uint8_t* __restrict__ a
   const int64_t p = upper_bound_dev<uint64_t>(start, npairs + 1, (uint64_t)g) - 1;
   const DPair pr = pairs[p];
   const uint32_t q = (uint32_t)(g - (int64_t)start[p]);
-  const uint8_t* __restrict__ s = arena + (side ? pr.t_off : pr.s_off) + q;
-  uint64_t v = 0;
-  for (int t = 0; t < k; t++) v = v * (uint64_t)L + s[t];
-  keys[g] = ((uint64_t)p << kbits) | v;
+  keys[g] = ((uint64_t)p << kbits) | kmer_fwd(arena + (side ? pr.t_off : pr.s_off) + q, k, L);
   pos[g] = q;
 }
 
-// K8a', stranded pair list: the T side where strand[p] != 0 encodes T = rc(read): the k-mer at position q of T is
-// comp(read[len - 1 - q]), comp(read[len - 2 - q]), ... -- read backwards from the forward letters, never materialised.
+// K8a', stranded pair list: the T side where strand[p] != 0 encodes T = rc(read) (kmer_rc).
 // Entries are generated in ascending q, so the stable sort keeps positions of T ascending inside a k-mer.
 __global__ __launch_bounds__(256) void k_enc_batch_rc(const uint8_t* __restrict__ arena, const DPair* __restrict__ pairs,
                                                       const uint64_t* __restrict__ start, int64_t npairs, int64_t total,
@@ -62,14 +76,8 @@ __global__ __launch_bounds__(256) void k_enc_batch_rc(const uint8_t* __restrict_
   const int64_t p = upper_bound_dev<uint64_t>(start, npairs + 1, (uint64_t)g) - 1;
   const DPair pr = pairs[p];
   const uint32_t q = (uint32_t)(g - (int64_t)start[p]);
-  uint64_t v = 0;
-  if (strand[p]) {
-    const uint8_t* __restrict__ s = arena + pr.t_off + (uint64_t)(pr.t_len - 1) - q;      // q <= t_len - k: s[-t] stays inside
-    for (int t = 0; t < k; t++) v = v * (uint64_t)L + s_comp[s[-t]];
-  } else {
-    const uint8_t* __restrict__ s = arena + pr.t_off + q;
-    for (int t = 0; t < k; t++) v = v * (uint64_t)L + s[t];
-  }
+  const uint64_t v = strand[p] ? kmer_rc(arena + pr.t_off + (uint64_t)(pr.t_len - 1) - q, k, L, s_comp)
+                               : kmer_fwd(arena + pr.t_off + q, k, L);
   keys[g] = ((uint64_t)p << kbits) | v;
   pos[g] = q;
 }
@@ -112,6 +120,75 @@ __device__ __forceinline__ double ov_x(int d, int ls, int lt, BandConst c) {
   return (double)d / (double)ov_rad(ov_len(d, ls, lt, c.q), c.C);
 }
 
+// ---- what the three scoring kernels share -------------------------------------------------------------------------
+// L, r and the window [first, last] of diagonals within 1 of d on the axis d / r(d).  Both predicates are monotone in d'
+// (what the binary searches of the first version relied on), so the same two boundaries are found by walking from a
+// guess -- d -+ r, where they are unless r(d') changes in between: a handful of evaluations of x(d') instead of 2 x 14.
+__device__ __forceinline__ void ov_window(int d, int ls, int lt, BandConst c, int& L, int& r, int& first, int& last) {
+  L = ov_len(d, ls, lt, c.q); r = ov_rad(L, c.C);
+  const double x = (double)d / (double)r;
+  first = d - r < -lt ? -lt : d - r;                   // smallest d' in [-lt, d] with x - x(d') <= 1
+  if (x - ov_x(first, ls, lt, c) <= 1.0) { while (first > -lt && x - ov_x(first - 1, ls, lt, c) <= 1.0) first--; }
+  else { do first++; while (first < d && !(x - ov_x(first, ls, lt, c) <= 1.0)); }
+  last = d + r > ls ? ls : d + r;                      // largest d' in [d, ls] with x(d') - x <= 1
+  if (ov_x(last, ls, lt, c) - x <= 1.0) { while (last < ls && ov_x(last + 1, ls, lt, c) - x <= 1.0) last++; }
+  else { do last--; while (last > d && !(ov_x(last, ls, lt, c) - x <= 1.0)); }
+}
+// w(d) of a diagonal with n neighbours in its window: the seeds above the 2 r L p0 expected by chance, per letter
+__device__ __forceinline__ double band_w(int n, int r, int L, double p0) {
+  const long long area = 2ll * r * L;
+  return ((double)(n + 1) - (double)area * p0) / (double)L;
+}
+// Which of two diagonals wins: the larger w, then the smaller d; d == kNoDiag is no diagonal at all and loses to any.
+constexpr int kNoDiag = 0x7fffffff;
+struct Best { double w; int d; };
+__device__ __forceinline__ bool better(Best a, Best b) {
+  return a.d != kNoDiag && (b.d == kNoDiag || a.w > b.w || (a.w == b.w && a.d < b.d));
+}
+// The tie rule.  p = min(w^(1/k), 1): everything at or above 1 ties, below it whatever is within 1e-9 relative of the best;
+// where no w is positive every p is 0 and every occupied diagonal ties.
+__device__ __forceinline__ double tie_threshold(double wbest) {
+  const double wcap = wbest >= 1.0 ? 1.0 : wbest;
+  return wcap - fabs(wcap) * 1e-9;
+}
+__device__ __forceinline__ bool ties(double wbest, double thr, double w) { return wbest <= 0.0 || w >= thr; }
+// The best of a workgroup's 256 candidates, to every thread (s_w, s_d: 256 entries each).
+__device__ __forceinline__ Best block_best(Best mine, double* s_w, int* s_d, int tid) {
+  s_w[tid] = mine.w; s_d[tid] = mine.d;
+  __syncthreads();
+  for (int off = 128; off >= 1; off >>= 1) {
+    if (tid < off) {
+      const Best o{s_w[tid + off], s_d[tid + off]};
+      if (better(o, Best{s_w[tid], s_d[tid]})) { s_w[tid] = o.w; s_d[tid] = o.d; }
+    }
+    __syncthreads();
+  }
+  const Best b{s_w[0], s_d[0]};
+  __syncthreads();
+  return b;
+}
+// N sums over a workgroup's 256 threads in one tree, to every thread (s: N x 256 entries).
+template <int N>
+__device__ __forceinline__ void block_sum(int (&v)[N], int* s, int tid) {
+  for (int i = 0; i < N; i++) s[256 * i + tid] = v[i];
+  __syncthreads();
+  for (int off = 128; off >= 1; off >>= 1) {
+    for (int i = 0; i < N; i++) if (tid < off) s[256 * i + tid] += s[256 * i + tid + off];
+    __syncthreads();
+  }
+  for (int i = 0; i < N; i++) v[i] = s[256 * i];
+}
+// A diagonal as the record reports it -- the best one, or the first row's: n(d), L(d), r(d) and the seeds of [d - r, d + r].
+struct BandSide { int d, n, len, r, band; };
+__device__ __forceinline__ pw_overlap_band band_record(int64_t n_seeds, double w_best, int tie, BandSide best, BandSide first) {
+  pw_overlap_band o;
+  memset(&o, 0, sizeof o);
+  o.n_seeds = n_seeds; o.w_best = w_best; o.tie = tie;
+  o.d_best = best.d; o.n_best = best.n; o.len_best = best.len; o.r_best = best.r; o.band_best = best.band;
+  o.d_first = first.d; o.n_first = first.n; o.len_first = first.len; o.r_first = first.r; o.band_first = first.band;
+  return o;
+}
+
 // one workgroup per pair
 __global__ __launch_bounds__(256) void k_band_select(const DPair* __restrict__ pairs, uint32_t* hist,
                                                      const unsigned long long* __restrict__ nrows, const int32_t* __restrict__ d_first,
@@ -129,11 +206,9 @@ __global__ __launch_bounds__(256) void k_band_select(const DPair* __restrict__ p
   const DPair pr = pairs[p];
   const int ls = pr.s_len, lt = pr.t_len, nd = ls + lt + 1;
   uint32_t* h = hist + (pr.hbase - hist_first);        // `hist` starts at counter hist_first; index dd = d + lt
-  pw_overlap_band o;
-  memset(&o, 0, sizeof o);
-  o.n_seeds = (int64_t)nrows[p];
-  if (o.n_seeds == 0) { if (tid == 0) out[p] = o; return; }
-  if (o.n_seeds <= small_max) return;                  // the sparse kernel (k_band_small) scores these
+  const int64_t n_seeds = (int64_t)nrows[p];
+  if (n_seeds == 0) { if (tid == 0) out[p] = band_record(0, 0.0, 0, BandSide{}, BandSide{}); return; }
+  if (n_seeds <= small_max) return;                    // the sparse kernel (k_band_small) scores these
   // ---- inclusive prefix sums in place: every thread owns a contiguous chunk ----
   const int chunk = (nd + 255) / 256;
   const int b = tid * chunk, e = b + chunk < nd ? b + chunk : nd;
@@ -162,88 +237,45 @@ __global__ __launch_bounds__(256) void k_band_select(const DPair* __restrict__ p
   auto pre = [&](int dd) -> uint32_t { return dd < 0 ? 0u : h[dd < nd ? dd : nd - 1]; };
   // neighbours of a seed on diagonal d and the score of its band
   auto eval = [&](int d, int& n, int& L, int& r) -> double {
-    L = ov_len(d, ls, lt, c.q); r = ov_rad(L, c.C);
-    const double x = (double)d / (double)r;
-    // The window of diagonals within 1 of d on the axis d / r(d).  Both predicates are monotone in d' (what the binary
-    // searches of the first version relied on), so the same two boundaries are found by walking from a guess -- d -+ r,
-    // where they are unless r(d') changes in between: a handful of evaluations of x(d') instead of 2 x 14.
-    int first = d - r < -lt ? -lt : d - r;             // smallest d' in [-lt, d] with x - x(d') <= 1
-    if (x - ov_x(first, ls, lt, c) <= 1.0) { while (first > -lt && x - ov_x(first - 1, ls, lt, c) <= 1.0) first--; }
-    else { do first++; while (first < d && !(x - ov_x(first, ls, lt, c) <= 1.0)); }
-    int lo = d + r > ls ? ls : d + r;                  // largest d' in [d, ls] with x(d') - x <= 1
-    if (ov_x(lo, ls, lt, c) - x <= 1.0) { while (lo < ls && ov_x(lo + 1, ls, lt, c) - x <= 1.0) lo++; }
-    else { do lo--; while (lo > d && !(ov_x(lo, ls, lt, c) - x <= 1.0)); }
-    n = (int)(pre(lo + lt) - pre(first + lt - 1)) - 1;
-    const long long area = 2ll * r * L;
-    return ((double)(n + 1) - (double)area * c.p0) / (double)L;
+    int first, last;
+    ov_window(d, ls, lt, c, L, r, first, last);
+    n = (int)(pre(last + lt) - pre(first + lt - 1)) - 1;
+    return band_w(n, r, L, c.p0);
   };
-  // ---- pass 1: the best occupied diagonal (largest w, then smallest d) ----
-  double bw = 0.0; int bd = 0x7fffffff;
   constexpr int kKeep = 4;                             // scores of this thread's first diagonals, kept for pass 2
   double wkeep[kKeep];
-  if (listed) {
-    int it = 0;
-    for (int q = tid; q < nocc; q += 256, it++) {
-      const int d = s_occ[q] - lt;
-      int n, L, r;
-      const double w = eval(d, n, L, r);
-      if (it < kKeep) wkeep[it] = w;
-      if (bd == 0x7fffffff || w > bw || (w == bw && d < bd)) { bw = w; bd = d; }
-    }
-  } else {
-    for (int dd = b; dd < e; dd++) {
-      if (pre(dd) == pre(dd - 1)) continue;
-      int n, L, r;
-      const double w = eval(dd - lt, n, L, r);
-      if (bd == 0x7fffffff || w > bw) { bw = w; bd = dd - lt; }
-    }
-  }
-  s_w[tid] = bw; s_d[tid] = bd;
-  __syncthreads();
-  for (int off = 128; off >= 1; off >>= 1) {
-    if (tid < off) {
-      const double ow = s_w[tid + off]; const int od = s_d[tid + off];
-      const bool have = s_d[tid] != 0x7fffffff, ohave = od != 0x7fffffff;
-      if (ohave && (!have || ow > s_w[tid] || (ow == s_w[tid] && od < s_d[tid]))) { s_w[tid] = ow; s_d[tid] = od; }
-    }
-    __syncthreads();
-  }
-  const double wbest = s_w[0]; const int dbest = s_d[0];
-  __syncthreads();
-  // ---- pass 2: how many occupied diagonals could reach the same p ----
-  int ties = 0;
-  const double wcap = wbest >= 1.0 ? 1.0 : wbest;           // p = min(w^(1/k), 1): everything at or above 1 ties
-  const double thr = wcap - fabs(wcap) * 1e-9;
-  if (listed) {
-    int it = 0;
-    for (int q = tid; q < nocc; q += 256, it++) {
-      int n, L, r;
-      const double w = it < kKeep ? wkeep[it] : eval(s_occ[q] - lt, n, L, r);
-      ties += (wbest <= 0.0 || w >= thr) ? 1 : 0;
-    }
-  } else {
-    for (int dd = b; dd < e; dd++) {
-      if (pre(dd) == pre(dd - 1)) continue;
-      int n, L, r;
-      const double w = eval(dd - lt, n, L, r);
-      ties += (wbest <= 0.0 || w >= thr) ? 1 : 0;
-    }
-  }
-  s_cnt[tid] = ties;
-  __syncthreads();
-  for (int off = 128; off >= 1; off >>= 1) { if (tid < off) s_cnt[tid] += s_cnt[tid + off]; __syncthreads(); }
-  if (tid == 0) {
+  // f(d, it) for every occupied diagonal of this thread; it < kKeep numbers the first ones of a listed pair
+  auto each_occupied = [&](auto&& f) {
+    if (listed) { int it = 0; for (int q = tid; q < nocc; q += 256, it++) f(s_occ[q] - lt, it); }
+    else { for (int dd = b; dd < e; dd++) if (pre(dd) != pre(dd - 1)) f(dd - lt, kKeep); }
+  };
+  // ---- pass 1: the best occupied diagonal ----
+  Best mine{0.0, kNoDiag};
+  each_occupied([&](int d, int it) {
     int n, L, r;
-    o.w_best = eval(dbest, n, L, r);
-    o.d_best = dbest; o.n_best = n; o.len_best = L; o.r_best = r;
-    o.band_best = (int)(pre(dbest + r + lt) - pre(dbest - r + lt - 1));
-    o.tie = s_cnt[0];
-    // the diagonal of the first row of the table (k-mer asc, i asc, j asc)
-    const int df = d_first[p];
-    (void)eval(df, n, L, r);
-    o.d_first = df; o.n_first = n; o.len_first = L; o.r_first = r;
-    o.band_first = (int)(pre(df + r + lt) - pre(df - r + lt - 1));
-    out[p] = o;
+    const double w = eval(d, n, L, r);
+    if (it < kKeep) wkeep[it] = w;
+    if (better(Best{w, d}, mine)) mine = Best{w, d};
+  });
+  const Best best = block_best(mine, s_w, s_d, tid);
+  // ---- pass 2: how many occupied diagonals could reach the same p ----
+  int tie[1] = {0};
+  const double thr = tie_threshold(best.w);
+  each_occupied([&](int d, int it) {
+    int n, L, r;
+    tie[0] += ties(best.w, thr, it < kKeep ? wkeep[it] : eval(d, n, L, r)) ? 1 : 0;
+  });
+  block_sum(tie, s_cnt, tid);
+  if (tid == 0) {
+    // the best diagonal, and the diagonal of the first row of the table (k-mer asc, i asc, j asc)
+    BandSide side[2];
+    for (int i = 0; i < 2; i++) {
+      const int d = i ? d_first[p] : best.d;
+      int n, L, r;
+      (void)eval(d, n, L, r);
+      side[i] = BandSide{d, n, L, r, (int)(pre(d + r + lt) - pre(d - r + lt - 1))};
+    }
+    out[p] = band_record(n_seeds, best.w, tie[0], side[0], side[1]);
   }
 }
 
@@ -268,10 +300,7 @@ __global__ __launch_bounds__(256) void k_enc_reads(const uint8_t* __restrict__ a
   if (g >= total) return;
   const int64_t r = upper_bound_dev<uint64_t>(rstart, nreads + 1, (uint64_t)g) - 1;
   const uint32_t q = (uint32_t)(g - (int64_t)rstart[r]);
-  const uint8_t* __restrict__ s = arena + roff[r] + q;
-  uint64_t v = 0;
-  for (int t = 0; t < k; t++) v = v * (uint64_t)L + s[t];
-  keys[g] = v;
+  keys[g] = kmer_fwd(arena + roff[r] + q, k, L);
   vals[g] = ((uint64_t)r << 32) | q;
 }
 // K9b: self join.  Inside a run of equal k-mers the entries are ordered by (read, pos); element e pairs with every
@@ -302,7 +331,7 @@ __global__ __launch_bounds__(256) void k_self_expand(const uint64_t* __restrict_
   dval[o] = (int32_t)(uint32_t)va - (int32_t)(uint32_t)vb;
 }
 // ---- both strands (K9'): a second index holds the k-mers of rc(read) for every read, computed from the forward letters ----
-// K9a': entry q of read r is the k-mer at position q of rc(read r): comp(read[len - 1 - q]), comp(read[len - 2 - q]), ...
+// K9a': entry q of read r is the k-mer at position q of rc(read r) (kmer_rc).
 // Generated in ascending (read, q), so inside a run of equal k-mers the stable sort leaves (read, q) ascending.
 __global__ __launch_bounds__(256) void k_enc_reads_rc(const uint8_t* __restrict__ arena, const uint64_t* __restrict__ roff,
                                                       const int32_t* __restrict__ rlen, const uint64_t* __restrict__ rstart,
@@ -314,10 +343,7 @@ __global__ __launch_bounds__(256) void k_enc_reads_rc(const uint8_t* __restrict_
   if (g >= total) return;
   const int64_t r = upper_bound_dev<uint64_t>(rstart, nreads + 1, (uint64_t)g) - 1;
   const uint32_t q = (uint32_t)(g - (int64_t)rstart[r]);
-  const uint8_t* __restrict__ s = arena + roff[r] + (uint64_t)(rlen[r] - 1) - q;           // q <= len - k: s[-t] stays inside
-  uint64_t v = 0;
-  for (int t = 0; t < k; t++) v = v * (uint64_t)L + s_comp[s[-t]];
-  keys[g] = v;
+  keys[g] = kmer_rc(arena + roff[r] + (uint64_t)(rlen[r] - 1) - q, k, L, s_comp);
   vals[g] = ((uint64_t)r << 32) | q;
 }
 // K9b': forward element e of read a pairs with the forward entries (sel & 1) and the reverse entries (sel & 2) of every read
@@ -409,7 +435,7 @@ __global__ __launch_bounds__(256) void k_scatter_hist(const int32_t* __restrict_
 }
 
 // K8d: a pair with at most 64 seeds is scored by ONE wavefront straight from its seed list (lane l = seed l, in table
-// order): same L, r, window, n, w as k_band_select's eval(), the neighbour count by a shuffle loop over the lanes.
+// order): the shared window, score, ordering and tie rule; the neighbour count by a shuffle loop over the lanes.
 // Seeds of pair u: dval[soff[u] + l] in table order (all-pairs path, soff != nullptr) or dval[64 u + l] in arbitrary order
 // with the first row's diagonal given in d_first (pair-list path).
 __global__ __launch_bounds__(256) void k_band_small(const DPair* __restrict__ pairs, const uint64_t* __restrict__ soff,
@@ -424,36 +450,25 @@ __global__ __launch_bounds__(256) void k_band_small(const DPair* __restrict__ pa
   const DPair pr = pairs[u];
   const int ls = pr.s_len, lt = pr.t_len;
   const bool valid = l < ns;
-  const int d = valid ? dval[(soff ? soff[u] : (uint64_t)u * 64ull) + (uint64_t)l] : 0x7fffffff;
+  const int d = valid ? dval[(soff ? soff[u] : (uint64_t)u * 64ull) + (uint64_t)l] : kNoDiag;
   if (ns == 0) return;
   int L = 1, r = 1, first = 0, last = 0;
-  if (valid) {
-    L = ov_len(d, ls, lt, c.q); r = ov_rad(L, c.C);
-    const double x = (double)d / (double)r;
-    int lo = -lt, hi = d;
-    while (lo < hi) { const int mid = lo + ((hi - lo) >> 1); if (!(x - ov_x(mid, ls, lt, c) <= 1.0)) lo = mid + 1; else hi = mid; }
-    first = lo;
-    lo = d; hi = ls;
-    while (lo < hi) { const int mid = lo + ((hi - lo + 1) >> 1); if (ov_x(mid, ls, lt, c) - x <= 1.0) lo = mid; else hi = mid - 1; }
-    last = lo;
-  }
+  if (valid) ov_window(d, ls, lt, c, L, r, first, last);
   int n = -1; bool rep = valid;
   for (int j = 0; j < ns; j++) {
     const int dj = __shfl(d, j, 64);
     n += (valid && dj >= first && dj <= last) ? 1 : 0;
     rep = rep && !(j < l && dj == d);              // the first lane of every occupied diagonal represents it
   }
-  const double w = valid ? ((double)(n + 1) - (double)(2ll * r * L) * c.p0) / (double)L : 0.0;
-  // best occupied diagonal: largest w, then smallest d
-  double bw = w; int bd = rep ? d : 0x7fffffff;
+  const double w = valid ? band_w(n, r, L, c.p0) : 0.0;
+  Best best{w, rep ? d : kNoDiag};                   // the best occupied diagonal: a butterfly over the representatives
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) {
-    const double ow = __shfl_xor(bw, off, 64); const int od = __shfl_xor(bd, off, 64);
-    if (od != 0x7fffffff && (bd == 0x7fffffff || ow > bw || (ow == bw && od < bd))) { bw = ow; bd = od; }
+    const Best o{__shfl_xor(best.w, off, 64), __shfl_xor(best.d, off, 64)};
+    if (better(o, best)) best = o;
   }
-  const double wcap = bw >= 1.0 ? 1.0 : bw;
-  const double thr = wcap - fabs(wcap) * 1e-9;
-  const unsigned long long tie_mask = __ballot(rep && (bw <= 0.0 || w >= thr));
+  const double bw = best.w; const int bd = best.d;
+  const unsigned long long tie_mask = __ballot(rep && ties(bw, tie_threshold(bw), w));
   const unsigned long long win_mask = __ballot(rep && d == bd);
   const int wl = __ffsll((long long)win_mask) - 1;
   const int rb = __shfl(r, wl, 64), Lb = __shfl(L, wl, 64), nb = __shfl(n, wl, 64);
@@ -462,30 +477,13 @@ __global__ __launch_bounds__(256) void k_band_small(const DPair* __restrict__ pa
   const int r0 = __shfl(r, fl, 64), L0 = __shfl(L, fl, 64), n0 = __shfl(n, fl, 64);
   const unsigned long long band_b = __ballot(valid && d >= bd - rb && d <= bd + rb);
   const unsigned long long band_f = __ballot(valid && d >= d0 - r0 && d <= d0 + r0);
-  if (l == 0) {
-    pw_overlap_band o;
-    memset(&o, 0, sizeof o);
-    o.n_seeds = ns; o.w_best = bw; o.d_best = bd; o.n_best = nb; o.r_best = rb; o.len_best = Lb;
-    o.band_best = __popcll(band_b); o.tie = __popcll(tie_mask);
-    o.d_first = d0; o.n_first = n0; o.r_first = r0; o.len_first = L0; o.band_first = __popcll(band_f);
-    out[u] = o;
-  }
-}
-
-// L, r and the window [first, last] of diagonals within 1 of d on the axis d / r(d): the values k_band_select's eval() uses
-__device__ __forceinline__ void ov_window(int d, int ls, int lt, BandConst c, int& L, int& r, int& first, int& last) {
-  L = ov_len(d, ls, lt, c.q); r = ov_rad(L, c.C);
-  const double x = (double)d / (double)r;
-  first = d - r < -lt ? -lt : d - r;
-  if (x - ov_x(first, ls, lt, c) <= 1.0) { while (first > -lt && x - ov_x(first - 1, ls, lt, c) <= 1.0) first--; }
-  else { do first++; while (first < d && !(x - ov_x(first, ls, lt, c) <= 1.0)); }
-  last = d + r > ls ? ls : d + r;
-  if (ov_x(last, ls, lt, c) - x <= 1.0) { while (last < ls && ov_x(last + 1, ls, lt, c) - x <= 1.0) last++; }
-  else { do last--; while (last > d && !(ov_x(last, ls, lt, c) - x <= 1.0)); }
+  if (l == 0)
+    out[u] = band_record(ns, bw, (int)__popcll(tie_mask), BandSide{bd, nb, Lb, rb, (int)__popcll(band_b)},
+                         BandSide{d0, n0, L0, r0, (int)__popcll(band_f)});
 }
 
 // K8e: a pair with 65 .. kMediumPair seeds is scored by ONE workgroup straight from its seed list in LDS (all-pairs path):
-// the same L, r, window, n, w per occupied diagonal as k_band_select -- the neighbour count by a loop over the list instead
+// the shared window, score, ordering and tie rule per occupied diagonal -- the neighbour count by a loop over the list instead
 // of a prefix-summed histogram of |S| + |T| + 1 counters per pair (10 001 for 5 kb reads: reading and summing them was the
 // bulk of the dense kernel's time, for the ~250 seeds of a true overlap).  The first seed of every occupied diagonal
 // represents it.
@@ -502,7 +500,7 @@ __global__ __launch_bounds__(256) void k_band_medium(const DPair* __restrict__ p
   constexpr int PER = kMediumPair / 256;
   __shared__ int s_dv[kMediumPair];
   __shared__ double s_w[256];
-  __shared__ int s_d[256], s_cnt[256], s_b1[256], s_b2[256];
+  __shared__ int s_d[256], s_sum[3 * 256];
   __shared__ int s_best[3], s_first[3];
   const int64_t u = list[blockIdx.x];
   const int tid = (int)threadIdx.x;
@@ -515,7 +513,7 @@ __global__ __launch_bounds__(256) void k_band_medium(const DPair* __restrict__ p
   const int d0 = d_first[u];
   double wq[PER];
   unsigned repmask = 0;
-  double bw = 0.0; int bd = 0x7fffffff;
+  Best mine{0.0, kNoDiag};
 #pragma unroll
   for (int q = 0; q < PER; q++) {
     const int l = tid + 256 * q;
@@ -530,35 +528,24 @@ __global__ __launch_bounds__(256) void k_band_medium(const DPair* __restrict__ p
         n += (dj >= first && dj <= last) ? 1 : 0;
         rp = rp && !(j < l && dj == d);
       }
-      const double w = ((double)(n + 1) - (double)(2ll * r * L) * c.p0) / (double)L;
+      const double w = band_w(n, r, L, c.p0);
       wq[q] = w;
       if (rp) {
         repmask |= 1u << q;
-        if (bd == 0x7fffffff || w > bw || (w == bw && d < bd)) { bw = w; bd = d; }
+        if (better(Best{w, d}, mine)) mine = Best{w, d};
       }
       if (d == d0 && rp) { s_first[0] = n; s_first[1] = L; s_first[2] = r; }       // (one representative per diagonal)
     }
   }
-  s_w[tid] = bw; s_d[tid] = bd;
-  __syncthreads();
-  for (int off = 128; off >= 1; off >>= 1) {
-    if (tid < off) {
-      const double ow = s_w[tid + off]; const int od = s_d[tid + off];
-      const bool have = s_d[tid] != 0x7fffffff, ohave = od != 0x7fffffff;
-      if (ohave && (!have || ow > s_w[tid] || (ow == s_w[tid] && od < s_d[tid]))) { s_w[tid] = ow; s_d[tid] = od; }
-    }
-    __syncthreads();
-  }
-  const double wbest = s_w[0]; const int dbest = s_d[0];
-  __syncthreads();
-  const double wcap = wbest >= 1.0 ? 1.0 : wbest;
-  const double thr = wcap - fabs(wcap) * 1e-9;
-  int ties = 0;
+  const Best best = block_best(mine, s_w, s_d, tid);
+  const double wbest = best.w; const int dbest = best.d;
+  const double thr = tie_threshold(wbest);
+  int sum[3] = {0, 0, 0};                                                           // ties, seeds of the best band, of the first row's
 #pragma unroll
   for (int q = 0; q < PER; q++) {
     const int l = tid + 256 * q;
     if (l < ns && (repmask >> q & 1u)) {
-      ties += (wbest <= 0.0 || wq[q] >= thr) ? 1 : 0;
+      sum[0] += ties(wbest, thr, wq[q]) ? 1 : 0;
       if (s_dv[l] == dbest) {                                                       // the best diagonal's representative
         int L, r, first, last;
         ov_window(dbest, ls, lt, c, L, r, first, last);
@@ -568,29 +555,41 @@ __global__ __launch_bounds__(256) void k_band_medium(const DPair* __restrict__ p
       }
     }
   }
-  s_cnt[tid] = ties;
   __syncthreads();
   const int rb = s_best[2], r0 = s_first[2];
-  int b1 = 0, b2 = 0;
   for (int l = tid; l < ns; l += 256) {
     const int d = s_dv[l];
-    b1 += (d >= dbest - rb && d <= dbest + rb) ? 1 : 0;
-    b2 += (d >= d0 - r0 && d <= d0 + r0) ? 1 : 0;
+    sum[1] += (d >= dbest - rb && d <= dbest + rb) ? 1 : 0;
+    sum[2] += (d >= d0 - r0 && d <= d0 + r0) ? 1 : 0;
   }
-  s_b1[tid] = b1; s_b2[tid] = b2;
-  __syncthreads();
-  for (int off = 128; off >= 1; off >>= 1) {
-    if (tid < off) { s_cnt[tid] += s_cnt[tid + off]; s_b1[tid] += s_b1[tid + off]; s_b2[tid] += s_b2[tid + off]; }
-    __syncthreads();
-  }
-  if (tid == 0) {
-    pw_overlap_band o;
-    memset(&o, 0, sizeof o);
-    o.n_seeds = ns; o.w_best = wbest; o.d_best = dbest; o.n_best = s_best[0]; o.len_best = s_best[1]; o.r_best = s_best[2];
-    o.band_best = s_b1[0]; o.tie = s_cnt[0];
-    o.d_first = d0; o.n_first = s_first[0]; o.len_first = s_first[1]; o.r_first = s_first[2]; o.band_first = s_b2[0];
-    out[u] = o;
-  }
+  block_sum(sum, s_sum, tid);
+  if (tid == 0)
+    out[u] = band_record(ns, wbest, sum[0], BandSide{dbest, s_best[0], s_best[1], rb, sum[1]},
+                         BandSide{d0, s_first[0], s_first[1], r0, sum[2]});
+}
+
+// ---- host helpers: everything runs on the null stream --------------------------------------------------------------
+// `buf` grown to `bytes` and filled from the host
+int upload(DeviceBuffer& buf, const void* host, size_t bytes) {
+  CHECK(buf.ensure(bytes));
+  CHECK(hipMemcpy(buf.p, host, bytes, hipMemcpyHostToDevice));
+  return 0;
+}
+// n (key, value) pairs stably sorted by the low `bits` bits of the key
+template <typename K, typename V>
+hipError_t sort_pairs(DeviceBuffer& tmp, const DeviceBuffer& kin, DeviceBuffer& kout, const DeviceBuffer& vin, DeviceBuffer& vout,
+                      size_t n, int bits) {
+  return rocprim_run(tmp, [&](void* t, size_t& b) {
+    return rocprim::radix_sort_pairs(t, b, (const K*)kin.p, (K*)kout.p, (const V*)vin.p, (V*)vout.p, n, 0u, (unsigned)bits,
+                                     (hipStream_t) nullptr);
+  });
+}
+// out[i] = in[0] + ... + in[i - 1]
+hipError_t scan_u64(DeviceBuffer& tmp, const DeviceBuffer& in, DeviceBuffer& out, size_t n) {
+  return rocprim_run(tmp, [&](void* t, size_t& b) {
+    return rocprim::exclusive_scan(t, b, (const uint64_t*)in.p, (uint64_t*)out.p, (uint64_t)0, n, rocprim::plus<uint64_t>(),
+                                   (hipStream_t) nullptr);
+  });
 }
 
 // strand (host, one byte per pair of the chunk) and d_comp are null on the forward-only path
@@ -608,25 +607,19 @@ int run_chunk(const uint8_t* d_arena, const pw_read_pair* pairs, int64_t n, int 
     ct += pairs[p].t_len >= k ? (uint64_t)(pairs[p].t_len - k + 1) : 0;
   }
   ss[(size_t)n] = cs; ts[(size_t)n] = ct;
-  DeviceBuffer dp, dss, dts, kin, pin, ksb, psb, ktb, ptb, hist, rows, first, dout, tmp, dlist;
-  CHECK(dp.ensure(sizeof(DPair) * (size_t)n)); CHECK(dss.ensure(8 * ((size_t)n + 1))); CHECK(dts.ensure(8 * ((size_t)n + 1)));
+  DeviceBuffer dp, dss, dts, dstrand, kin, pin, ksb, psb, ktb, ptb, hist, rows, first, dout, tmp, dlist;
   CHECK(kin.ensure(8 * (size_t)std::max(cs, ct))); CHECK(pin.ensure(4 * (size_t)std::max(cs, ct)));
   CHECK(ksb.ensure(8 * (size_t)cs)); CHECK(psb.ensure(4 * (size_t)cs)); CHECK(ktb.ensure(8 * (size_t)ct)); CHECK(ptb.ensure(4 * (size_t)ct));
   CHECK(hist.ensure(4 * (size_t)hb)); CHECK(rows.ensure(8 * (size_t)n)); CHECK(first.ensure(4 * (size_t)n));
   CHECK(dout.ensure(sizeof(pw_overlap_band) * (size_t)n)); CHECK(dlist.ensure(256 * (size_t)n));
-  CHECK(hipMemcpy(dp.p, hp.data(), sizeof(DPair) * (size_t)n, hipMemcpyHostToDevice));
-  CHECK(hipMemcpy(dss.p, ss.data(), 8 * ((size_t)n + 1), hipMemcpyHostToDevice));
-  CHECK(hipMemcpy(dts.p, ts.data(), 8 * ((size_t)n + 1), hipMemcpyHostToDevice));
-  DeviceBuffer dstrand;
-  if (strand) {
-    CHECK(dstrand.ensure((size_t)n));
-    CHECK(hipMemcpy(dstrand.p, strand, (size_t)n, hipMemcpyHostToDevice));
-  }
+  if (upload(dp, hp.data(), sizeof(DPair) * (size_t)n) != 0 || upload(dss, ss.data(), 8 * ((size_t)n + 1)) != 0 ||
+      upload(dts, ts.data(), 8 * ((size_t)n + 1)) != 0 || (strand && upload(dstrand, strand, (size_t)n) != 0))
+    return -1;
   CHECK(hipEventRecord(ev0, nullptr));
   CHECK(hipMemsetAsync(hist.p, 0, 4 * (size_t)hb, nullptr));
   CHECK(hipMemsetAsync(rows.p, 0, 8 * (size_t)n, nullptr));
   CHECK(hipMemsetAsync(first.p, 0xff, 4 * (size_t)n, nullptr));
-  int pbits = 1; while (((uint64_t)n >> pbits) != 0) pbits++;
+  const int pbits = bits_for((uint64_t)n);
   for (int side = 0; side < 2; side++) {
     const uint64_t tot = side ? ct : cs;
     if (tot == 0) continue;
@@ -637,11 +630,7 @@ int run_chunk(const uint8_t* d_arena, const pw_read_pair* pairs, int64_t n, int 
     else
       hipLaunchKernelGGL(k_enc_batch, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, nullptr, d_arena, (const DPair*)dp.p,
                          (const uint64_t*)(side ? dts.p : dss.p), n, (int64_t)tot, side, k, L, kbits, (uint64_t*)kin.p, (uint32_t*)pin.p);
-    uint64_t* ko = (uint64_t*)(side ? ktb.p : ksb.p); uint32_t* po = (uint32_t*)(side ? ptb.p : psb.p);
-    CHECK(rocprim_run(tmp, [&](void* t, size_t& b) {
-      return rocprim::radix_sort_pairs(t, b, (const uint64_t*)kin.p, ko, (const uint32_t*)pin.p, po, (size_t)tot, 0u,
-                                       (unsigned)(kbits + pbits), (hipStream_t) nullptr);
-    }));
+    CHECK((sort_pairs<uint64_t, uint32_t>(tmp, kin, side ? ktb : ksb, pin, side ? ptb : psb, (size_t)tot, kbits + pbits)));
   }
   if (cs && ct)
     hipLaunchKernelGGL(k_join_hist, dim3((unsigned)((cs + 255) / 256)), dim3(256), 0, nullptr, (const uint64_t*)ksb.p,
@@ -666,179 +655,193 @@ int run_chunk(const uint8_t* d_arena, const pw_read_pair* pairs, int64_t n, int 
   return 0;
 }
 
+// ---- all reads against all reads (K9): one call, stage by stage on the null stream ----------------------------------------
 // sel: 1 forward pairs only (d_comp and pair_strand unused: the kernels and keys of the unstranded call), 2 minus pairs only,
 // 3 both.  With sel != 1 a second index of the same size holds the reverse-strand k-mers and the pair key carries the strand.
-int run_all_pairs(const uint8_t* d_arena, const uint64_t* read_off, const int32_t* read_len, int64_t R, int L, int k, int kbits,
-                  BandConst bc, int shard_rank, int shard_world, int64_t max_pairs, int32_t* pair_a, int32_t* pair_b, pw_overlap_band* out,
-                  int64_t* n_out, float* ms, int sel = 1, const uint8_t* d_comp = nullptr, uint8_t* pair_strand = nullptr) {
-  const bool st = sel != 1;
-  std::vector<uint64_t> rstart((size_t)R + 1);
-  uint64_t K = 0;
-  for (int64_t r = 0; r < R; r++) { rstart[(size_t)r] = K; K += read_len[r] >= k ? (uint64_t)(read_len[r] - k + 1) : 0; }
-  rstart[(size_t)R] = K;
-  *n_out = 0;
-  if (K == 0) return 0;
-  if (K >= (1ull << 32)) {
-    set_err(st ? "more than 2^32 k-mers in one index: split the read set (with the reverse strand the index holds twice the entries, "
-                 "2^32 per strand)"
-               : "more than 2^32 k-mers in one index: split the read set");
-    return -1;
+// The buffers are listed under the stage that fills them; all of them live until the call returns, so none is freed between
+// the two events.
+struct AllPairs {
+  const uint8_t* d_arena; const uint8_t* d_comp;
+  int64_t R; int L, k, kbits, sel, shard_rank, shard_world; int64_t max_pairs; BandConst bc;
+  bool st = false;                                     // sel != 1
+  uint64_t K = 0, NS = 0;                              // k-mers per index, seeds
+  unsigned long long NP = 0;                           // candidate pairs
+  const dim3 blk = dim3(256);
+  DeviceBuffer droff, drlen, drstart, tmp;             // the reads (run); rocPRIM's scratch, one for the whole call
+  DeviceBuffer kin, vin, ks, vs, kr, vr;               // build_index: staging, the forward index, the reverse-strand index
+  DeviceBuffer fs, cnt, off, fr, cf, pk_in, dv_in, pk, dv;                          // self_join: (pair key, d) per seed
+  DeviceBuffer uk, uc, nruns, soff, hsize, hbase, dpairs, dfirst, dpa, dpb, dps;    // group_pairs: the candidate pairs
+  DeviceBuffer dout, hist;                             // score_tiers: the records
+
+  // Stage 1, once per strand: K9a (K9a' for the reverse strand) into kin / vin, then the stable sort by k-mer.
+  int build_index(bool reverse) {
+    const dim3 gK((unsigned)((K + 255) / 256));
+    if (reverse)
+      hipLaunchKernelGGL(k_enc_reads_rc, gK, blk, 0, nullptr, d_arena, (const uint64_t*)droff.p, (const int32_t*)drlen.p,
+                         (const uint64_t*)drstart.p, R, (int64_t)K, k, L, d_comp, (uint64_t*)kin.p, (uint64_t*)vin.p);
+    else
+      hipLaunchKernelGGL(k_enc_reads, gK, blk, 0, nullptr, d_arena, (const uint64_t*)droff.p, (const uint64_t*)drstart.p, R, (int64_t)K, k, L,
+                         (uint64_t*)kin.p, (uint64_t*)vin.p);
+    CHECK((sort_pairs<uint64_t, uint64_t>(tmp, kin, reverse ? kr : ks, vin, reverse ? vr : vs, (size_t)K, kbits)));
+    return 0;
   }
-  DeviceEvent ev0, ev1;
-  CHECK(ev0.create()); CHECK(ev1.create());
-  DeviceBuffer droff, drlen, drstart, kin, vin, ks, vs, fs, cnt, off, scal, tmp;
-  CHECK(droff.ensure(8 * (size_t)R)); CHECK(drlen.ensure(4 * (size_t)R)); CHECK(drstart.ensure(8 * ((size_t)R + 1)));
-  CHECK(kin.ensure(8 * (size_t)K)); CHECK(vin.ensure(8 * (size_t)K)); CHECK(ks.ensure(8 * (size_t)K)); CHECK(vs.ensure(8 * (size_t)K));
-  CHECK(fs.ensure(4 * (size_t)K)); CHECK(cnt.ensure(8 * (size_t)K)); CHECK(off.ensure(8 * (size_t)K)); CHECK(scal.ensure(64));
-  CHECK(hipMemcpy(droff.p, read_off, 8 * (size_t)R, hipMemcpyHostToDevice));
-  CHECK(hipMemcpy(drlen.p, read_len, 4 * (size_t)R, hipMemcpyHostToDevice));
-  CHECK(hipMemcpy(drstart.p, rstart.data(), 8 * ((size_t)R + 1), hipMemcpyHostToDevice));
-  CHECK(hipEventRecord(ev0.e, nullptr));
-  const dim3 blk(256), gK((unsigned)((K + 255) / 256));
-  hipLaunchKernelGGL(k_enc_reads, gK, blk, 0, nullptr, d_arena, (const uint64_t*)droff.p, (const uint64_t*)drstart.p, R, (int64_t)K, k, L,
-                     (uint64_t*)kin.p, (uint64_t*)vin.p);
-  CHECK(rocprim_run(tmp, [&](void* t, size_t& b) {
-    return rocprim::radix_sort_pairs(t, b, (const uint64_t*)kin.p, (uint64_t*)ks.p, (const uint64_t*)vin.p, (uint64_t*)vs.p, (size_t)K,
-                                     0u, (unsigned)kbits, (hipStream_t) nullptr);
-  }));
-  DeviceBuffer kr, vr, fr, cf;       // the reverse-strand index and its side of the join
-  if (st) {
-    CHECK(kr.ensure(8 * (size_t)K)); CHECK(vr.ensure(8 * (size_t)K)); CHECK(fr.ensure(4 * (size_t)K)); CHECK(cf.ensure(4 * (size_t)K));
-    hipLaunchKernelGGL(k_enc_reads_rc, gK, blk, 0, nullptr, d_arena, (const uint64_t*)droff.p, (const int32_t*)drlen.p,
-                       (const uint64_t*)drstart.p, R, (int64_t)K, k, L, d_comp, (uint64_t*)kin.p, (uint64_t*)vin.p);
+
+  // Stage 2: the self join (K9b, K9b') to seeds -> (pair key, d), stably sorted by the pair key.  NS stays 0 when no two reads
+  // share a k-mer.
+  int self_join() {
+    const dim3 gK((unsigned)((K + 255) / 256));
+    if (st)
+      hipLaunchKernelGGL(k_self_count_st, gK, blk, 0, nullptr, (const uint64_t*)ks.p, (const uint64_t*)vs.p, (int64_t)K,
+                         (const uint64_t*)kr.p, (const uint64_t*)vr.p, sel, shard_rank, shard_world, (uint32_t*)fs.p, (uint32_t*)cf.p,
+                         (uint32_t*)fr.p, (uint64_t*)cnt.p);
+    else
+      hipLaunchKernelGGL(k_self_count, gK, blk, 0, nullptr, (const uint64_t*)ks.p, (const uint64_t*)vs.p, (int64_t)K, shard_rank, shard_world,
+                         (uint32_t*)fs.p, (uint64_t*)cnt.p);
+    CHECK(scan_u64(tmp, cnt, off, (size_t)K));
+    uint64_t last_off = 0, last_cnt = 0;
+    CHECK(hipMemcpy(&last_off, (uint64_t*)off.p + (K - 1), 8, hipMemcpyDeviceToHost));
+    CHECK(hipMemcpy(&last_cnt, (uint64_t*)cnt.p + (K - 1), 8, hipMemcpyDeviceToHost));
+    NS = last_off + last_cnt;
+    if (NS == 0) return 0;
+    if (NS >= (1ull << 32)) { set_err("more than 2^32 seeds between the reads: use a longer word"); return -1; }
+    CHECK(pk_in.ensure(8 * (size_t)NS)); CHECK(dv_in.ensure(4 * (size_t)NS)); CHECK(pk.ensure(8 * (size_t)NS)); CHECK(dv.ensure(4 * (size_t)NS));
+    if (st)
+      hipLaunchKernelGGL(k_self_expand_st, dim3((unsigned)((NS + 255) / 256)), blk, 0, nullptr, (const uint64_t*)off.p, (int64_t)K, (int64_t)NS,
+                         (const uint64_t*)vs.p, (const uint64_t*)vr.p, (const uint32_t*)fs.p, (const uint32_t*)cf.p, (const uint32_t*)fr.p,
+                         (uint64_t)R, (uint64_t*)pk_in.p, (int32_t*)dv_in.p);
+    else
+      hipLaunchKernelGGL(k_self_expand, dim3((unsigned)((NS + 255) / 256)), blk, 0, nullptr, (const uint64_t*)off.p, (int64_t)K, (int64_t)NS,
+                         (const uint64_t*)vs.p, (const uint32_t*)fs.p, (uint64_t)R, (uint64_t*)pk_in.p, (int32_t*)dv_in.p);
+    const int pbits = bits_for((uint64_t)R * (uint64_t)R) + (st ? 1 : 0);       // (the strand bit below the pair rank)
+    CHECK((sort_pairs<uint64_t, int32_t>(tmp, pk_in, pk, dv_in, dv, (size_t)NS, pbits)));
+    return 0;
+  }
+
+  // Stage 3: the sorted seeds grouped into candidate pairs -- unique pair keys with their seed counts, then seed offsets,
+  // histogram bases and DPairs.
+  int group_pairs() {
+    CHECK(uk.ensure(8 * (size_t)NS)); CHECK(uc.ensure(8 * (size_t)NS)); CHECK(nruns.ensure(16));
     CHECK(rocprim_run(tmp, [&](void* t, size_t& b) {
-      return rocprim::radix_sort_pairs(t, b, (const uint64_t*)kin.p, (uint64_t*)kr.p, (const uint64_t*)vin.p, (uint64_t*)vr.p, (size_t)K,
-                                       0u, (unsigned)kbits, (hipStream_t) nullptr);
+      return rocprim::run_length_encode(t, b, (const uint64_t*)pk.p, (unsigned int)NS, (uint64_t*)uk.p, (unsigned long long*)uc.p,
+                                        (unsigned long long*)nruns.p, (hipStream_t) nullptr);
     }));
-    hipLaunchKernelGGL(k_self_count_st, gK, blk, 0, nullptr, (const uint64_t*)ks.p, (const uint64_t*)vs.p, (int64_t)K,
-                       (const uint64_t*)kr.p, (const uint64_t*)vr.p, sel, shard_rank, shard_world, (uint32_t*)fs.p, (uint32_t*)cf.p,
-                       (uint32_t*)fr.p, (uint64_t*)cnt.p);
-  } else {
-    hipLaunchKernelGGL(k_self_count, gK, blk, 0, nullptr, (const uint64_t*)ks.p, (const uint64_t*)vs.p, (int64_t)K, shard_rank, shard_world,
-                       (uint32_t*)fs.p, (uint64_t*)cnt.p);
+    CHECK(hipMemcpy(&NP, nruns.p, 8, hipMemcpyDeviceToHost));
+    if ((int64_t)NP > max_pairs) {
+      char msg[160];
+      snprintf(msg, sizeof msg, "%llu pairs of reads share a seed (capacity %lld): raise max_pairs or the word length", NP, (long long)max_pairs);
+      set_err(msg);
+      return -1;
+    }
+    if (st) CHECK(dps.ensure((size_t)NP));
+    CHECK(soff.ensure(8 * (size_t)NP)); CHECK(hsize.ensure(8 * (size_t)NP)); CHECK(hbase.ensure(8 * (size_t)NP));
+    CHECK(dpairs.ensure(sizeof(DPair) * (size_t)NP)); CHECK(dfirst.ensure(4 * (size_t)NP)); CHECK(dpa.ensure(4 * (size_t)NP));
+    CHECK(dpb.ensure(4 * (size_t)NP));
+    const dim3 gP((unsigned)((NP + 255) / 256));
+    CHECK(scan_u64(tmp, uc, soff, (size_t)NP));
+    auto* const hsize_kernel = st ? k_pair_hsize<1> : k_pair_hsize<0>;
+    auto* const cand_kernel = st ? k_cand_pairs<1> : k_cand_pairs<0>;
+    hipLaunchKernelGGL(hsize_kernel, gP, blk, 0, nullptr, (const uint64_t*)uk.p, (const unsigned long long*)uc.p, (int64_t)NP, (uint64_t)R,
+                       (const int32_t*)drlen.p, (uint64_t*)hsize.p, kMediumPair);
+    CHECK(scan_u64(tmp, hsize, hbase, (size_t)NP));
+    hipLaunchKernelGGL(cand_kernel, gP, blk, 0, nullptr, (const uint64_t*)uk.p, (const uint64_t*)soff.p,
+                       (const int32_t*)dv.p, (int64_t)NP, (uint64_t)R, (const uint64_t*)droff.p, (const int32_t*)drlen.p,
+                       (const uint64_t*)hbase.p, (DPair*)dpairs.p, (int32_t*)dfirst.p, (int32_t*)dpa.p, (int32_t*)dpb.p, (uint8_t*)dps.p);
+    return 0;
   }
-  DeviceBuffer tmp2;
-  CHECK(rocprim_run(tmp2, [&](void* t, size_t& b) {
-    return rocprim::exclusive_scan(t, b, (const uint64_t*)cnt.p, (uint64_t*)off.p, (uint64_t)0, (size_t)K, rocprim::plus<uint64_t>(), (hipStream_t) nullptr);
-  }));
-  uint64_t last_off = 0, last_cnt = 0;
-  CHECK(hipMemcpy(&last_off, (uint64_t*)off.p + (K - 1), 8, hipMemcpyDeviceToHost));
-  CHECK(hipMemcpy(&last_cnt, (uint64_t*)cnt.p + (K - 1), 8, hipMemcpyDeviceToHost));
-  const uint64_t NS = last_off + last_cnt;
-  if (NS == 0) return 0;
-  if (NS >= (1ull << 32)) { set_err("more than 2^32 seeds between the reads: use a longer word"); return -1; }
-  // seeds -> (pair key, d), stably sorted by the pair key
-  DeviceBuffer pk_in, dv_in, pk, dv;
-  CHECK(pk_in.ensure(8 * (size_t)NS)); CHECK(dv_in.ensure(4 * (size_t)NS)); CHECK(pk.ensure(8 * (size_t)NS)); CHECK(dv.ensure(4 * (size_t)NS));
-  if (st)
-    hipLaunchKernelGGL(k_self_expand_st, dim3((unsigned)((NS + 255) / 256)), blk, 0, nullptr, (const uint64_t*)off.p, (int64_t)K, (int64_t)NS,
-                       (const uint64_t*)vs.p, (const uint64_t*)vr.p, (const uint32_t*)fs.p, (const uint32_t*)cf.p, (const uint32_t*)fr.p,
-                       (uint64_t)R, (uint64_t*)pk_in.p, (int32_t*)dv_in.p);
-  else
-    hipLaunchKernelGGL(k_self_expand, dim3((unsigned)((NS + 255) / 256)), blk, 0, nullptr, (const uint64_t*)off.p, (int64_t)K, (int64_t)NS,
-                       (const uint64_t*)vs.p, (const uint32_t*)fs.p, (uint64_t)R, (uint64_t*)pk_in.p, (int32_t*)dv_in.p);
-  int pbits = 1; while ((((uint64_t)R * (uint64_t)R) >> pbits) != 0) pbits++;
-  if (st) pbits++;                                     // the strand bit below the pair rank
-  DeviceBuffer tmp3;
-  CHECK(rocprim_run(tmp3, [&](void* t, size_t& b) {
-    return rocprim::radix_sort_pairs(t, b, (const uint64_t*)pk_in.p, (uint64_t*)pk.p, (const int32_t*)dv_in.p, (int32_t*)dv.p, (size_t)NS,
-                                     0u, (unsigned)pbits, (hipStream_t) nullptr);
-  }));
-  // unique pair keys with their seed counts
-  DeviceBuffer uk, uc, nruns;
-  CHECK(uk.ensure(8 * (size_t)NS)); CHECK(uc.ensure(8 * (size_t)NS)); CHECK(nruns.ensure(16));
-  DeviceBuffer tmp4;
-  CHECK(rocprim_run(tmp4, [&](void* t, size_t& b) {
-    return rocprim::run_length_encode(t, b, (const uint64_t*)pk.p, (unsigned int)NS, (uint64_t*)uk.p, (unsigned long long*)uc.p,
-                                      (unsigned long long*)nruns.p, (hipStream_t) nullptr);
-  }));
-  unsigned long long NP = 0;
-  CHECK(hipMemcpy(&NP, nruns.p, 8, hipMemcpyDeviceToHost));
-  if ((int64_t)NP > max_pairs) {
-    char msg[160];
-    snprintf(msg, sizeof msg, "%llu pairs of reads share a seed (capacity %lld): raise max_pairs or the word length", NP, (long long)max_pairs);
-    set_err(msg);
-    return -1;
+
+  // Stage 4: every candidate pair's record, by the tier its seed count puts it in.
+  int score_tiers() {
+    const dim3 gP((unsigned)((NP + 255) / 256));
+    CHECK(dout.ensure(sizeof(pw_overlap_band) * (size_t)NP));
+    hipLaunchKernelGGL(k_band_small, dim3((unsigned)((NP * 64 + 255) / 256)), blk, 0, nullptr, (const DPair*)dpairs.p, (const uint64_t*)soff.p,
+                       (const unsigned long long*)uc.p, (const int32_t*)dv.p, (const int32_t*)nullptr, (int64_t)NP, bc, (pw_overlap_band*)dout.p);
+    // pairs with 65 .. kMediumPair seeds: one workgroup each, from the seed list
+    {
+      DeviceBuffer mlist, mcount;
+      CHECK(mlist.ensure(8 * (size_t)NP)); CHECK(mcount.ensure(16));
+      CHECK(hipMemsetAsync(mcount.p, 0, 16, nullptr));
+      hipLaunchKernelGGL(k_list_medium, gP, blk, 0, nullptr, (const unsigned long long*)uc.p, (int64_t)NP, (unsigned long long*)mcount.p, (int64_t*)mlist.p);
+      unsigned long long NM = 0;
+      CHECK(hipMemcpy(&NM, mcount.p, 8, hipMemcpyDeviceToHost));
+      if (NM) hipLaunchKernelGGL(k_band_medium, dim3((unsigned)NM), blk, 0, nullptr, (const DPair*)dpairs.p, (const int64_t*)mlist.p, (const uint64_t*)soff.p,
+                                 (const unsigned long long*)uc.p, (const int32_t*)dv.p, (const int32_t*)dfirst.p, bc, (pw_overlap_band*)dout.p);
+      CHECK(hipDeviceSynchronize());                      // (mlist is freed at the end of this scope)
+    }
+    // chunks of pairs whose histograms fit 2^30 counters (none at all when no pair has more than kMediumPair seeds)
+    uint64_t last_base = 0, last_size = 0;
+    if (NP) {
+      CHECK(hipMemcpy(&last_base, (const uint64_t*)hbase.p + (NP - 1), 8, hipMemcpyDeviceToHost));
+      CHECK(hipMemcpy(&last_size, (const uint64_t*)hsize.p + (NP - 1), 8, hipMemcpyDeviceToHost));
+    }
+    const bool any_hist = last_base + last_size > 0;
+    const size_t NPh = any_hist ? (size_t)NP : 0;
+    std::vector<uint64_t> h_hbase(NPh), h_soff(NPh), h_hsize(NPh);
+    if (any_hist) {
+      CHECK(hipMemcpy(h_hbase.data(), hbase.p, 8 * (size_t)NP, hipMemcpyDeviceToHost));
+      CHECK(hipMemcpy(h_soff.data(), soff.p, 8 * (size_t)NP, hipMemcpyDeviceToHost));
+      CHECK(hipMemcpy(h_hsize.data(), hsize.p, 8 * (size_t)NP, hipMemcpyDeviceToHost));
+    }
+    const uint64_t cap = 1ull << 30;
+    for (uint64_t u0 = 0; any_hist && u0 < NP;) {
+      uint64_t u1 = u0, tot = 0;
+      while (u1 < NP && (u1 == u0 || tot + h_hsize[(size_t)u1] <= cap)) { tot += h_hsize[(size_t)u1]; u1++; }
+      if (tot == 0) { u0 = u1; continue; }                 // no pair of this chunk needs a histogram
+      CHECK(hist.ensure(4 * (size_t)tot));
+      CHECK(hipMemsetAsync(hist.p, 0, 4 * (size_t)tot, nullptr));
+      const uint64_t s0 = h_soff[(size_t)u0], s1 = u1 < NP ? h_soff[(size_t)u1] : NS;
+      hipLaunchKernelGGL(k_scatter_hist, dim3((unsigned)((s1 - s0 + 255) / 256)), blk, 0, nullptr, (const int32_t*)dv.p, (int64_t)s0, (int64_t)s1,
+                         (const uint64_t*)soff.p, (int64_t)u0, (int64_t)u1, (const DPair*)dpairs.p, h_hbase[(size_t)u0], (uint32_t*)hist.p,
+                         kMediumPair);
+      hipLaunchKernelGGL(k_band_select, dim3((unsigned)(u1 - u0)), blk, 0, nullptr, (const DPair*)dpairs.p + u0, (uint32_t*)hist.p,
+                         (const unsigned long long*)uc.p + u0, (const int32_t*)dfirst.p + u0, h_hbase[(size_t)u0], kMediumPair, bc,
+                         (pw_overlap_band*)dout.p + u0);
+      u0 = u1;
+    }
+    return 0;
   }
-  // seed offsets and histogram bases of the candidate pairs
-  DeviceBuffer soff, hsize, hbase, dpairs, dfirst, dpa, dpb, dps, dout;
-  if (st) CHECK(dps.ensure((size_t)NP));
-  CHECK(soff.ensure(8 * (size_t)NP)); CHECK(hsize.ensure(8 * (size_t)NP)); CHECK(hbase.ensure(8 * (size_t)NP));
-  CHECK(dpairs.ensure(sizeof(DPair) * (size_t)NP)); CHECK(dfirst.ensure(4 * (size_t)NP)); CHECK(dpa.ensure(4 * (size_t)NP));
-  CHECK(dpb.ensure(4 * (size_t)NP)); CHECK(dout.ensure(sizeof(pw_overlap_band) * (size_t)NP));
-  const dim3 gP((unsigned)((NP + 255) / 256));
-  DeviceBuffer tmp5;
-  auto scan_np = [&](const DeviceBuffer& in, DeviceBuffer& res) {
-    return rocprim_run(tmp5, [&](void* t, size_t& b) {
-      return rocprim::exclusive_scan(t, b, (const uint64_t*)in.p, (uint64_t*)res.p, (uint64_t)0, (size_t)NP, rocprim::plus<uint64_t>(), (hipStream_t) nullptr);
-    });
-  };
-  CHECK(scan_np(uc, soff));
-  auto* const hsize_kernel = st ? k_pair_hsize<1> : k_pair_hsize<0>;
-  auto* const cand_kernel = st ? k_cand_pairs<1> : k_cand_pairs<0>;
-  hipLaunchKernelGGL(hsize_kernel, gP, blk, 0, nullptr, (const uint64_t*)uk.p, (const unsigned long long*)uc.p, (int64_t)NP, (uint64_t)R,
-                     (const int32_t*)drlen.p, (uint64_t*)hsize.p, kMediumPair);
-  CHECK(scan_np(hsize, hbase));
-  hipLaunchKernelGGL(cand_kernel, gP, blk, 0, nullptr, (const uint64_t*)uk.p, (const uint64_t*)soff.p,
-                     (const int32_t*)dv.p, (int64_t)NP, (uint64_t)R, (const uint64_t*)droff.p, (const int32_t*)drlen.p,
-                     (const uint64_t*)hbase.p, (DPair*)dpairs.p, (int32_t*)dfirst.p, (int32_t*)dpa.p, (int32_t*)dpb.p, (uint8_t*)dps.p);
-  hipLaunchKernelGGL(k_band_small, dim3((unsigned)((NP * 64 + 255) / 256)), blk, 0, nullptr, (const DPair*)dpairs.p, (const uint64_t*)soff.p,
-                     (const unsigned long long*)uc.p, (const int32_t*)dv.p, (const int32_t*)nullptr, (int64_t)NP, bc, (pw_overlap_band*)dout.p);
-  // pairs with 65 .. kMediumPair seeds: one workgroup each, from the seed list
-  {
-    DeviceBuffer mlist, mcount;
-    CHECK(mlist.ensure(8 * (size_t)NP)); CHECK(mcount.ensure(16));
-    CHECK(hipMemsetAsync(mcount.p, 0, 16, nullptr));
-    hipLaunchKernelGGL(k_list_medium, gP, blk, 0, nullptr, (const unsigned long long*)uc.p, (int64_t)NP, (unsigned long long*)mcount.p, (int64_t*)mlist.p);
-    unsigned long long NM = 0;
-    CHECK(hipMemcpy(&NM, mcount.p, 8, hipMemcpyDeviceToHost));
-    if (NM) hipLaunchKernelGGL(k_band_medium, dim3((unsigned)NM), blk, 0, nullptr, (const DPair*)dpairs.p, (const int64_t*)mlist.p, (const uint64_t*)soff.p,
-                               (const unsigned long long*)uc.p, (const int32_t*)dv.p, (const int32_t*)dfirst.p, bc, (pw_overlap_band*)dout.p);
-    CHECK(hipDeviceSynchronize());                      // (mlist is freed at the end of this scope)
+
+  int run(const uint64_t* read_off, const int32_t* read_len, int32_t* pair_a, int32_t* pair_b, uint8_t* pair_strand, pw_overlap_band* out,
+          int64_t* n_out, float* ms) {
+    st = sel != 1;
+    std::vector<uint64_t> rstart((size_t)R + 1);
+    for (int64_t r = 0; r < R; r++) { rstart[(size_t)r] = K; K += read_len[r] >= k ? (uint64_t)(read_len[r] - k + 1) : 0; }
+    rstart[(size_t)R] = K;
+    *n_out = 0;
+    if (K == 0) return 0;
+    if (K >= (1ull << 32)) {
+      set_err(st ? "more than 2^32 k-mers in one index: split the read set (with the reverse strand the index holds twice the entries, "
+                   "2^32 per strand)"
+                 : "more than 2^32 k-mers in one index: split the read set");
+      return -1;
+    }
+    DeviceEvent ev0, ev1;
+    CHECK(ev0.create()); CHECK(ev1.create());
+    // what the forward strand needs is allocated before the first event: no allocation of it is timed
+    CHECK(kin.ensure(8 * (size_t)K)); CHECK(vin.ensure(8 * (size_t)K)); CHECK(ks.ensure(8 * (size_t)K)); CHECK(vs.ensure(8 * (size_t)K));
+    CHECK(fs.ensure(4 * (size_t)K)); CHECK(cnt.ensure(8 * (size_t)K)); CHECK(off.ensure(8 * (size_t)K));
+    if (upload(droff, read_off, 8 * (size_t)R) != 0 || upload(drlen, read_len, 4 * (size_t)R) != 0 ||
+        upload(drstart, rstart.data(), 8 * ((size_t)R + 1)) != 0)
+      return -1;
+    CHECK(hipEventRecord(ev0.e, nullptr));
+    if (build_index(false) != 0) return -1;
+    if (st) {
+      CHECK(kr.ensure(8 * (size_t)K)); CHECK(vr.ensure(8 * (size_t)K)); CHECK(fr.ensure(4 * (size_t)K)); CHECK(cf.ensure(4 * (size_t)K));
+      if (build_index(true) != 0) return -1;
+    }
+    if (self_join() != 0) return -1;
+    if (NS == 0) return 0;
+    if (group_pairs() != 0 || score_tiers() != 0) return -1;
+    CHECK(hipEventRecord(ev1.e, nullptr));
+    CHECK(hipMemcpy(out, dout.p, sizeof(pw_overlap_band) * (size_t)NP, hipMemcpyDeviceToHost));
+    CHECK(hipMemcpy(pair_a, dpa.p, 4 * (size_t)NP, hipMemcpyDeviceToHost));
+    CHECK(hipMemcpy(pair_b, dpb.p, 4 * (size_t)NP, hipMemcpyDeviceToHost));
+    if (st) CHECK(hipMemcpy(pair_strand, dps.p, (size_t)NP, hipMemcpyDeviceToHost));
+    CHECK(hipGetLastError());
+    CHECK(hipEventElapsedTime(ms, ev0.e, ev1.e));
+    *n_out = (int64_t)NP;
+    return 0;
   }
-  // chunks of pairs whose histograms fit 2^30 counters (none at all when no pair has more than kMediumPair seeds)
-  uint64_t last_base = 0, last_size = 0;
-  if (NP) {
-    CHECK(hipMemcpy(&last_base, (const uint64_t*)hbase.p + (NP - 1), 8, hipMemcpyDeviceToHost));
-    CHECK(hipMemcpy(&last_size, (const uint64_t*)hsize.p + (NP - 1), 8, hipMemcpyDeviceToHost));
-  }
-  const bool any_hist = last_base + last_size > 0;
-  const size_t NPh = any_hist ? (size_t)NP : 0;
-  std::vector<uint64_t> h_hbase(NPh), h_soff(NPh), h_hsize(NPh);
-  if (any_hist) {
-    CHECK(hipMemcpy(h_hbase.data(), hbase.p, 8 * (size_t)NP, hipMemcpyDeviceToHost));
-    CHECK(hipMemcpy(h_soff.data(), soff.p, 8 * (size_t)NP, hipMemcpyDeviceToHost));
-    CHECK(hipMemcpy(h_hsize.data(), hsize.p, 8 * (size_t)NP, hipMemcpyDeviceToHost));
-  }
-  const uint64_t cap = 1ull << 30;
-  DeviceBuffer hist;
-  for (uint64_t u0 = 0; any_hist && u0 < NP;) {
-    uint64_t u1 = u0, tot = 0;
-    while (u1 < NP && (u1 == u0 || tot + h_hsize[(size_t)u1] <= cap)) { tot += h_hsize[(size_t)u1]; u1++; }
-    if (tot == 0) { u0 = u1; continue; }                 // no pair of this chunk needs a histogram
-    CHECK(hist.ensure(4 * (size_t)tot));
-    CHECK(hipMemsetAsync(hist.p, 0, 4 * (size_t)tot, nullptr));
-    const uint64_t s0 = h_soff[(size_t)u0], s1 = u1 < NP ? h_soff[(size_t)u1] : NS;
-    hipLaunchKernelGGL(k_scatter_hist, dim3((unsigned)((s1 - s0 + 255) / 256)), blk, 0, nullptr, (const int32_t*)dv.p, (int64_t)s0, (int64_t)s1,
-                       (const uint64_t*)soff.p, (int64_t)u0, (int64_t)u1, (const DPair*)dpairs.p, h_hbase[(size_t)u0], (uint32_t*)hist.p,
-                       kMediumPair);
-    hipLaunchKernelGGL(k_band_select, dim3((unsigned)(u1 - u0)), blk, 0, nullptr, (const DPair*)dpairs.p + u0, (uint32_t*)hist.p,
-                       (const unsigned long long*)uc.p + u0, (const int32_t*)dfirst.p + u0, h_hbase[(size_t)u0], kMediumPair, bc,
-                       (pw_overlap_band*)dout.p + u0);
-    u0 = u1;
-  }
-  CHECK(hipEventRecord(ev1.e, nullptr));
-  CHECK(hipMemcpy(out, dout.p, sizeof(pw_overlap_band) * (size_t)NP, hipMemcpyDeviceToHost));
-  CHECK(hipMemcpy(pair_a, dpa.p, 4 * (size_t)NP, hipMemcpyDeviceToHost));
-  CHECK(hipMemcpy(pair_b, dpb.p, 4 * (size_t)NP, hipMemcpyDeviceToHost));
-  if (st) CHECK(hipMemcpy(pair_strand, dps.p, (size_t)NP, hipMemcpyDeviceToHost));
-  CHECK(hipGetLastError());
-  float t = 0.f;
-  CHECK(hipEventElapsedTime(&t, ev0.e, ev1.e));
-  *ms = t;
-  *n_out = (int64_t)NP;
-  return 0;
-}
+};
 
 // The argument checks of both entry points, in this order: word range, counts and pointers (bad_args), coefficients,
 // shard (bad_shard), L^k, reads inside the arena (outside(i) for i < n), letters inside the alphabet.  kbits: the width of
@@ -852,9 +855,7 @@ int check_args(int L, int k, bool bad_args, double len_coeff, double radius_coef
   if (bad_shard) { set_err("bad shard"); return -1; }
   uint64_t kmax = 1;
   for (int i = 0; i < k; i++) { if (kmax > (1ull << 62) / (uint64_t)L) { set_err("alphabet_len ^ wordlen must be below 2^62"); return -1; } kmax *= (uint64_t)L; }
-  *kbits = 0;
-  while (((kmax - 1) >> *kbits) != 0) ++*kbits;
-  if (*kbits == 0) *kbits = 1;
+  *kbits = bits_for(kmax - 1);
   for (int64_t i = 0; i < n; i++) if (outside(i)) { set_err("a read lies outside the arena"); return -1; }
   for (uint64_t i = 0; i < arena_bytes; i++) if (arena[i] >= L) { set_err("letter outside the alphabet"); return -1; }
   return 0;
@@ -896,9 +897,9 @@ int all_pairs(int device, const uint8_t* arena, uint64_t arena_bytes, const uint
   if (upload_arena(device, arena, arena_bytes, d_arena) != 0) return -1;
   if (strands != PW_STRAND_PLUS && upload_complement(complement, alphabet_len, d_comp) != 0) return -1;
   float ms = 0.f;
-  const int rc = run_all_pairs((const uint8_t*)d_arena.p, read_off, read_len, n_reads, alphabet_len, wordlen, kbits,
-                               BandConst{len_coeff, radius_coeff, word_p_null}, shard_rank, shard_world, max_pairs, pair_a, pair_b, out,
-                               n_out, &ms, strands, (const uint8_t*)d_comp.p, pair_strand);
+  AllPairs job{(const uint8_t*)d_arena.p, (const uint8_t*)d_comp.p, n_reads, alphabet_len, wordlen, kbits, strands, shard_rank, shard_world,
+               max_pairs, BandConst{len_coeff, radius_coeff, word_p_null}};
+  const int rc = job.run(read_off, read_len, pair_a, pair_b, pair_strand, out, n_out, &ms);
   if (rc == 0 && stranded && strands == PW_STRAND_PLUS) memset(pair_strand, 0, (size_t)*n_out);
   g_ms = (double)ms;
   return rc;
@@ -1005,10 +1006,7 @@ void* pw_overlap_arena_upload(int device, const uint8_t* host_arena, uint64_t by
     if (total == 0) return 0;
     DeviceBuffer dsrc, ddst, dstart, d_comp;
     const size_t nb = 8 * (size_t)n_frames;
-    CHECK(dsrc.ensure(nb)); CHECK(ddst.ensure(nb)); CHECK(dstart.ensure(nb + 8));
-    CHECK(hipMemcpy(dsrc.p, src_off, nb, hipMemcpyHostToDevice));
-    CHECK(hipMemcpy(ddst.p, dst_off, nb, hipMemcpyHostToDevice));
-    CHECK(hipMemcpy(dstart.p, start.data(), nb + 8, hipMemcpyHostToDevice));
+    if (upload(dsrc, src_off, nb) != 0 || upload(ddst, dst_off, nb) != 0 || upload(dstart, start.data(), nb + 8) != 0) return -1;
     if (upload_complement(complement, alphabet_len, d_comp) != 0) return -1;
     hipLaunchKernelGGL(k_revcomp_frames, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, nullptr, (uint8_t*)p, (const uint64_t*)dsrc.p,
                        (const uint64_t*)ddst.p, (const uint64_t*)dstart.p, n_frames, (int64_t)total, (const uint8_t*)d_comp.p, alphabet_len);

@@ -46,7 +46,7 @@ thread_local std::string g_err;
 void set_err(const std::string& s) { g_err = s; }
 #define CHECK(call) PW_HIP_CHECK(set_err, call)
 
-// (SatAdd, bits_for: pw_seed_host.h)
+// (SatAdd: pw_seed_host.h; bits_for: pw_hip_host.h)
 
 // ---- K10a -----------------------------------------------------------------------------------------------
 // pstart[q] = number of positions of the queries before q (pstart[nq] = npos); position t belongs to the last query whose

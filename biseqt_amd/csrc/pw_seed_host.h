@@ -21,9 +21,6 @@ namespace {
 
 using ErrSink = void (*)(const std::string&);
 
-// the width of a sort-key field that holds 0 .. maxval
-int bits_for(uint64_t maxval) { int b = 1; while ((maxval >> b) != 0) b++; return b; }
-
 // Between two recorded events: the milliseconds from ev0 to `stream`'s present end, which this waits for.
 int elapsed(ErrSink sink, const DeviceEvent& ev0, const DeviceEvent& ev1, hipStream_t stream, float* ms) {
   PW_HIP_CHECK(sink, hipEventRecord(ev1.e, stream));

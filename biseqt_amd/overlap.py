@@ -105,6 +105,15 @@ def reverse_strand_keys(read, wordlen, alphabet_len, complement):
     return (comp[read[idx]] * weights[None, :]).sum(axis=1, dtype=np.uint64)
 
 
+def _band_coeffs(g_max, sensitivity, alphabet_len, wordlen):
+    """``(len_coeff, radius_coeff, word_p_null)`` of the C calls: the reference's constants, computed as it computes them
+    (blot.py:109, 134-136, 538) -- they reach the device as doubles."""
+    len_coeff = 2. / (2 - g_max)
+    radius_coeff = erfcinv(1. - sensitivity) * np.sqrt(2 * g_max)
+    word_p_null = (1. / alphabet_len) ** wordlen
+    return float(len_coeff), float(radius_coeff), float(word_p_null)
+
+
 def raw_bands(reads, pairs, wordlen, alphabet_len, g_max, sensitivity, device=0, strands=None, complement=None):
     """The device records (BAND_DTYPE) for ``pairs`` = list of (i, j) indices into ``reads``; also returns the
     device time in ms.  ``strands``: one ``'+'`` / ``'-'`` per pair (default: all ``'+'``); a minus pair is scored against
@@ -119,20 +128,15 @@ def raw_bands(reads, pairs, wordlen, alphabet_len, g_max, sensitivity, device=0,
     for q, (i, j) in enumerate(pairs):
         rp[q] = W.pw_read_pair(int(offs[i]), int(offs[j]), len(arrs[i]), len(arrs[j]))
     out = np.zeros(max(n, 1), BAND_DTYPE)
-    # the reference's constants, computed as it computes them (blot.py:109, 134-136, 538)
-    len_coeff = 2. / (2 - g_max)
-    radius_coeff = erfcinv(1. - sensitivity) * np.sqrt(2 * g_max)
-    word_p_null = (1. / alphabet_len) ** wordlen
+    coeffs = _band_coeffs(g_max, sensitivity, alphabet_len, wordlen)
     arena_c = np.ascontiguousarray(arena)
     if comp is None:
         name = 'pw_overlap_bands'
-        rc = lib.pw_overlap_bands(device, arena_c.ctypes.data, arena_c.size, rp, n, alphabet_len, wordlen,
-                                  float(len_coeff), float(radius_coeff), float(word_p_null), out.ctypes.data)
+        rc = lib.pw_overlap_bands(device, arena_c.ctypes.data, arena_c.size, rp, n, alphabet_len, wordlen, *coeffs, out.ctypes.data)
     else:
         name = 'pw_overlap_bands_stranded'
-        rc = lib.pw_overlap_bands_stranded(device, arena_c.ctypes.data, arena_c.size, rp, n, alphabet_len, wordlen,
-                                           float(len_coeff), float(radius_coeff), float(word_p_null), comp.ctypes.data,
-                                           flags.ctypes.data, out.ctypes.data)
+        rc = lib.pw_overlap_bands_stranded(device, arena_c.ctypes.data, arena_c.size, rp, n, alphabet_len, wordlen, *coeffs,
+                                           comp.ctypes.data, flags.ctypes.data, out.ctypes.data)
     if rc != 0:
         raise RuntimeError(name + ' failed: ' + (lib.pw_overlap_last_error() or b'').decode())
     return out[:n], lib.pw_overlap_last_ms()
@@ -224,12 +228,11 @@ def raw_all_pairs(reads, wordlen, alphabet_len, g_max, sensitivity, device=0, ma
     roff = np.ascontiguousarray(offs[:-1].astype(np.uint64))
     rlen = np.ascontiguousarray(np.diff(offs).astype(np.int32))
     arena_c = np.ascontiguousarray(arena)
+    coeffs = _band_coeffs(g_max, sensitivity, alphabet_len, wordlen)
     if with_strand:
         ps = np.zeros(max(cap, 1), np.uint8)
         rc = lib.pw_overlap_all_pairs_stranded(device, arena_c.ctypes.data, arena_c.size, roff.ctypes.data, rlen.ctypes.data, R,
-                                               alphabet_len, wordlen, float(2. / (2 - g_max)),
-                                               float(erfcinv(1. - sensitivity) * np.sqrt(2 * g_max)),
-                                               float((1. / alphabet_len) ** wordlen), None if comp is None else comp.ctypes.data,
+                                               alphabet_len, wordlen, *coeffs, None if comp is None else comp.ctypes.data,
                                                _STRAND_SEL[strands], int(rank), int(world), cap, pa.ctypes.data, pb.ctypes.data,
                                                ps.ctypes.data, out.ctypes.data, C.byref(n_out))
         if rc != 0:
@@ -237,8 +240,7 @@ def raw_all_pairs(reads, wordlen, alphabet_len, g_max, sensitivity, device=0, ma
         n = n_out.value
         return np.stack([pa[:n], pb[:n]], axis=1), ps[:n], out[:n], lib.pw_overlap_last_ms()
     rc = lib.pw_overlap_all_pairs(device, arena_c.ctypes.data, arena_c.size, roff.ctypes.data, rlen.ctypes.data, R, alphabet_len,
-                                  wordlen, float(2. / (2 - g_max)), float(erfcinv(1. - sensitivity) * np.sqrt(2 * g_max)),
-                                  float((1. / alphabet_len) ** wordlen), int(rank), int(world), cap, pa.ctypes.data, pb.ctypes.data, out.ctypes.data,
+                                  wordlen, *coeffs, int(rank), int(world), cap, pa.ctypes.data, pb.ctypes.data, out.ctypes.data,
                                   C.byref(n_out))
     if rc != 0:
         raise RuntimeError('pw_overlap_all_pairs failed: ' + (lib.pw_overlap_last_error() or b'').decode())

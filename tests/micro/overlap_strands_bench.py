@@ -32,8 +32,8 @@ COMP = np.array([3, 2, 1, 0], np.uint8)
 def make_reads(R, cache=None):
     if cache and os.path.exists(cache):
         z = np.load(cache)
-        offs = z['offs']
-        return [z['arena'][offs[q]:offs[q + 1]] for q in range(R)], z['starts'], z['flips']
+        arena, offs = z['arena'], z['offs']            # (every z[...] reads the whole array from the file again)
+        return [arena[offs[q]:offs[q + 1]] for q in range(R)], z['starts'], z['flips']
     rng = synth.rng_for(4)
     read_len, cov = 5000, 25
     G = R * read_len // cov

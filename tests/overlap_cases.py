@@ -208,6 +208,15 @@ def cases():
     S, T = _first_with(doubled, lambda o: o['tie'] >= 2 and 0 < o['w_best'] < 1, 0, 'two equal best diagonals')
     add('two_equal_best', S, T, 6, 4, .2, .99, seeds=(SMALL_MAX + 1, MEDIUM_MAX), tie=(2, None), w_positive=True, w_below_one=True)
 
+    # A near tie: a block of 8 words on a diagonal with L = 30 and one of 16 words on a diagonal with L = 60, nothing else shared
+    # (the fillers use disjoint letters).  (n + 1) / L is 4 / 15 on both, their radii differ and p0 = 4^-20, so the two w differ by
+    # 7e-12 relative: within the tie rule's 1e-9 (tie = 2), yet not equal (a rule without the tolerance would say tie = 1).
+    rng = np.random.default_rng(303)
+    X, Y = _rand(rng, 4, 8 + 19), _rand(rng, 4, 16 + 19)
+    S = np.concatenate([_rand(rng, 2, 10), Y, X])
+    T = np.concatenate([X, 2 + _rand(rng, 2, 3), Y, 2 + _rand(rng, 2, 9)])
+    add('near_tie', S, T, 20, 4, .2, .9, seeds=24, nocc=(2, 2), tie=(2, 2), near_tie=True, w_positive=True, w_below_one=True)
+
     # ---- long words: one group per key width, every case with the top and the zero word (tests/wide_words.py) ----
     for (L, k), (g, sens) in WW.OVERLAP_RUNGS.items():
         for x in WW.inputs(L, k).values():
@@ -268,6 +277,8 @@ def check_class(c):
         assert o['w_best'] == 0.0 and o['tie'] == o['nocc'] > 1
     if kl.pop('w_negative', False):
         assert o['w_best'] < 0 and o['tie'] == o['nocc'] > 1
+    if kl.pop('near_tie', False):                         # the tied scores are unequal, apart by less than the rule's 1e-9
+        assert 0 < abs(o['w'][0] - o['w'][1]) < 1e-10 * o['w_best']
     if kl.pop('first_differs', False):
         assert o['d_first'] != o['d_best']
     if kl.pop('w_positive', False):

@@ -76,7 +76,7 @@ def lookup_of(L, k, nref):
 
 
 def bits_for(maxval):
-    """pw_seed_host.h's bits_for: the width of a sort-key field that holds 0 .. maxval."""
+    """pw_hip_host.h's bits_for: the width of a sort-key field that holds 0 .. maxval."""
     b = 1
     while maxval >> b:
         b += 1

@@ -36,6 +36,8 @@ def test_the_required_classes_are_all_there():
     assert any(o['n_seeds'] and o['w_best'] < 0 and o['nocc'] > 1 for o in rec.values())
     assert any(o['n_seeds'] and o['w_best'] >= 1 for o in rec.values())
     assert any(o['n_seeds'] and 0 < o['w_best'] < 1 and o['tie'] >= 2 for o in rec.values())
+    o = rec['near_tie']                                 # a tie that only the rule's tolerance makes: the second score is not the best one
+    assert o['tie'] == 2 and OC.tier(o) == 'small' and (o['w'] == o['w_best']).sum() == 1
     # in every tier some occupied diagonal's window crosses the low edge of the table and some the high edge
     for t in ('small', 'medium', 'dense_kept', 'dense_listed', 'dense_chunks'):
         got = [OC.clamped(rec[c.name], *c.reads) for c in CASES if rec[c.name]['n_seeds'] and OC.tier(rec[c.name]) == t]
