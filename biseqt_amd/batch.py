@@ -25,6 +25,9 @@ assert SUMMARY_DTYPE.itemsize == 48
 CIGAR_EXTENDED, CIGAR_CLASSIC = W.PW_CIGAR_EXTENDED, W.PW_CIGAR_CLASSIC
 CIGAR_OPS = 'MIDNSHP=X'
 _CIGAR_FORMS = {'extended': CIGAR_EXTENDED, 'classic': CIGAR_CLASSIC}
+# pw_pileup_site of include/pw_pileup.h: one called column of a pileup
+SITE_DTYPE = np.dtype([('depth', '<u4'), ('call', 'u1'), ('ref', 'u1'), ('flags', '<u2')])
+assert SITE_DTYPE.itemsize == 8
 _CIGAR_LETTERS = ({'M': '=', 'S': 'X', 'I': 'I', 'D': 'D'}, {'M': 'M', 'S': 'M', 'I': 'I', 'D': 'D'})
 
 
@@ -168,6 +171,132 @@ class DeviceArena(object):
             self.close()
         except Exception:
             pass
+
+
+class Pileup(object):
+    """Per-column base counts of the origins of many alignments, device-resident (include/pw_pileup.h): ``uint32
+    counts[n_cols][alphabet_len + 2]`` -- one channel per letter, then ``DEL`` (the ``D`` ops over the column) and ``INS`` (the
+    insertion events anchored to the column on their left) -- zeroed at creation and filled by
+    :meth:`BatchAligner.pileup_add` from the transcripts where the traceback left them.  The header has the definition op by
+    op.  A cell wraps past ``2**32 - 1``; keeping the depth below that is the caller's business.  A context manager that
+    frees itself, like :class:`DeviceArena`."""
+
+    def __init__(self, n_cols, alphabet_len, device=0):
+        self.handle = None
+        n_cols, alphabet_len = int(n_cols), int(alphabet_len)
+        if not 1 <= alphabet_len <= 32:
+            raise ValueError('alphabet_len must be 1..32, not %d' % alphabet_len)
+        if n_cols < 0:
+            raise ValueError('n_cols must not be negative')
+        self.lib = W.load()
+        self.n_cols, self.alphabet_len, self.device = n_cols, alphabet_len, device
+        self.DEL, self.INS = alphabet_len, alphabet_len + 1
+        self._ref = None                     # the device copy of a host reference given to call(): alive as long as the sites
+        self.handle = self.lib.pw_pileup_create(device, n_cols, alphabet_len)
+        if not self.handle:
+            raise RuntimeError('pw_pileup_create failed: ' + W.last_error())
+
+    def close(self):
+        if getattr(self, 'handle', None):
+            self.lib.pw_pileup_destroy(self.handle)
+            self.handle = None
+        if getattr(self, '_ref', None) is not None:
+            self._ref.close()
+            self._ref = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _ck(self, rc, what):
+        if rc != 0:
+            raise RuntimeError('%s failed: %s' % (what, W.last_error()))
+
+    def _range(self, lo, hi):
+        hi = self.n_cols if hi is None else int(hi)
+        lo = int(lo)
+        if not 0 <= lo <= hi <= self.n_cols:
+            raise ValueError('columns [%d, %d) outside the pileup of %d' % (lo, hi, self.n_cols))
+        return lo, hi
+
+    def clear(self, stream=None):
+        """All counts back to zero (asynchronous on ``stream``)."""
+        self._ck(self.lib.pw_pileup_clear(self.handle, stream), 'pw_pileup_clear')
+
+    def counts(self, lo=0, hi=None):
+        """``uint32[hi - lo, alphabet_len + 2]`` of the columns ``[lo, hi)`` (synchronous D2H)."""
+        lo, hi = self._range(lo, hi)
+        out = np.zeros((hi - lo, self.alphabet_len + 2), np.uint32)
+        self._ck(self.lib.pw_pileup_counts(self.handle, lo, hi, out.ctypes.data), 'pw_pileup_counts')
+        return out
+
+    def set_counts(self, counts, lo=0):
+        """Overwrite the columns ``[lo, lo + len(counts))`` with host counts: a pileup saved earlier, or one summed over
+        several devices (synchronous H2D)."""
+        a = np.ascontiguousarray(counts, np.uint32)
+        if a.ndim != 2 or a.shape[1] != self.alphabet_len + 2:
+            raise ValueError('counts must be [columns, alphabet_len + 2]')
+        lo, hi = self._range(lo, int(lo) + len(a))
+        self._ck(self.lib.pw_pileup_set_counts(self.handle, lo, hi, a.ctypes.data), 'pw_pileup_set_counts')
+
+    def counts_device(self):
+        return DeviceBuffer(self.lib.pw_pileup_counts_device(self.handle), 4 * self.n_cols * (self.alphabet_len + 2), self)
+
+    def call(self, ref=None, min_depth=1, stream=None):
+        """One :data:`SITE_DTYPE` record per column from the counts as they are (``pw_pileup_call``, asynchronous on ``stream``):
+        ``depth`` (letters + ``DEL``), ``call`` (the channel with the largest count, a tie to the lowest; 255 below
+        ``min_depth`` or at depth 0), ``ref`` and ``flags`` (``PW_PILEUP_COVERED | DIFFERS | INSERT``).  ``ref``: None, a host
+        array of ``n_cols`` letters (uploaded here), or ``(DeviceArena, offset)`` for letters that are on the device already."""
+        min_depth = int(min_depth)
+        if not 0 <= min_depth < 1 << 32:
+            raise ValueError('min_depth must fit 32 bits')
+        ptr, held = None, None
+        if isinstance(ref, tuple):
+            arena, off = ref
+            if not isinstance(arena, DeviceArena) or arena.device != self.device or not 0 <= int(off) <= arena.nbytes - self.n_cols:
+                raise ValueError('ref is (DeviceArena on device %d, offset) with n_cols letters behind the offset' % self.device)
+            ptr = arena.ptr + int(off)
+        elif ref is not None:
+            letters = _as_u8(ref)
+            if len(letters) != self.n_cols:
+                raise ValueError('ref has %d letters, the pileup %d columns' % (len(letters), self.n_cols))
+            held = DeviceArena(letters if len(letters) else np.zeros(1, np.uint8), device=self.device)
+            ptr = held.ptr
+        self._ck(self.lib.pw_pileup_call(self.handle, ptr, min_depth, stream), 'pw_pileup_call')
+        if self._ref is not None:
+            self._ref.close()                # (pw_arena_free waits for the device: an earlier call has read it by now)
+        self._ref = held
+
+    def sites(self, lo=0, hi=None):
+        """Structured array (:data:`SITE_DTYPE`) of the columns ``[lo, hi)`` as the last :meth:`call` left them (synchronous D2H)."""
+        lo, hi = self._range(lo, hi)
+        out = np.zeros(hi - lo, SITE_DTYPE)
+        self._ck(self.lib.pw_pileup_sites(self.handle, lo, hi, out.ctypes.data), 'pw_pileup_sites')
+        return out
+
+    def sites_device(self):
+        ptr = self.lib.pw_pileup_sites_device(self.handle)
+        if not ptr:
+            raise RuntimeError('sites_device before call')
+        return DeviceBuffer(ptr, 8 * self.n_cols, self)
+
+    def consensus(self, lo=0, hi=None):
+        """The ``call`` bytes of the columns ``[lo, hi)``: a letter, ``alphabet_len`` for a deletion, 255 for no call."""
+        return self.sites(lo, hi)['call'].copy()
+
+    def variants(self, lo=0, hi=None):
+        """The column indices in ``[lo, hi)`` flagged ``PW_PILEUP_DIFFERS`` or ``PW_PILEUP_INSERT`` by the last :meth:`call`."""
+        lo, hi = self._range(lo, hi)
+        flags = self.sites(lo, hi)['flags']
+        return lo + np.flatnonzero(flags & (W.PW_PILEUP_DIFFERS | W.PW_PILEUP_INSERT)).astype(np.int64)
 
 
 class BatchAligner(object):
@@ -510,6 +639,23 @@ class BatchAligner(object):
         if not runs or not off:
             raise RuntimeError('cigars_device before cigars')
         return DeviceBuffer(runs, 4 * int(self.lib.pw_batch_cigar_total(self.handle)), self), DeviceBuffer(off, 8 * (self.n + 1), self)
+
+    # ---- pileups (include/pw_pileup.h): the transcripts scattered into per-column counts where they are ----
+    def pileup_add(self, pileup, col0=None, arena_first=0, stream=None):
+        """After a traceback on ``stream``: every pair with an alignment adds its ops to the columns of its origin in
+        ``pileup`` (a :class:`Pileup` on the same device; ``pw_batch_pileup_add``, asynchronous on ``stream``).  The origin
+        frame of pair ``k`` starts at column ``col0[k]`` -- an int64 per pair, negative to skip the pair -- or, without
+        ``col0``, at its arena offset minus ``arena_first``; a pair whose frame does not lie inside the pileup adds nothing.
+        Adding is cumulative."""
+        if not isinstance(pileup, Pileup) or not pileup.handle:
+            raise ValueError('pileup must be an open Pileup')
+        c = None
+        if col0 is not None:
+            c = np.ascontiguousarray(col0, np.int64).reshape(-1)
+            if len(c) != self.n:
+                raise ValueError('col0 has %d entries for %d pairs' % (len(c), self.n))
+        self._ck(self.lib.pw_batch_pileup_add(self.handle, pileup.handle, None if c is None else c.ctypes.data, int(arena_first), stream),
+                 'pw_batch_pileup_add')
 
     def scores_plane(self, k):
         """Score of every cell of pair k as ``plane[d - dmin, a]`` (needs PW_FLAG_DUMP_SCORES)."""

@@ -42,6 +42,13 @@ hipError_t launch_cigar_write(const PairDesc* pairs, const Result* results, cons
 hipError_t launch_cigar_count_packed(const uint8_t* ops, const uint64_t* offsets, int n, int form, uint64_t* run_offsets, hipStream_t st);
 hipError_t launch_cigar_write_packed(const uint8_t* ops, const uint64_t* offsets, int n, int form, const uint64_t* run_offsets, uint32_t* runs,
                                      hipStream_t st);
+// pileups (pw_pileup.hip; the definition in include/pw_pileup.h): add -- one wavefront per pair scatters its ops into
+// counts[n_cols][L + 2] (col0: device array of frame starts per pair, or null for o_off - arena_first); call -- one thread per
+// column writes sites[n_cols] (pw_pileup_site; ref: device letters or null)
+hipError_t launch_pileup_add(const PairDesc* pairs, const Result* results, const uint8_t* slots, const uint8_t* arena, int n,
+                             const int64_t* col0, int64_t arena_first, uint32_t* counts, int64_t n_cols, int L, hipStream_t st);
+hipError_t launch_pileup_call(const uint32_t* counts, const uint8_t* ref, int64_t n_cols, int L, uint32_t min_depth, void* sites,
+                              hipStream_t st);
 // strip pipeline (pw_strip.h / pw_strip.hip): one standard-mode pair wider than a workgroup
 struct StripParams;
 struct StripTraceParams;

@@ -22,6 +22,7 @@
 #include "../../include/pw_batch.h"
 #include "../../include/pw_txsum.h"
 #include "../../include/pw_cigar.h"
+#include "../../include/pw_pileup.h"
 #include "pw_launch.h"
 #include "pw_plan.h"
 #include "pw_model.h"
@@ -228,6 +229,7 @@ struct pw_batch {
   uint64_t cigar_room = 0, cigar_total = 0, cigar_seq = 0;   // runs d_cigruns holds / the last total / the traceback it describes
   int cigar_form = -1;
   hipStream_t cigar_stream = nullptr;    // the stream of the last pw_batch_cigars
+  DeviceBuffer d_col0;                   // pw_batch_pileup_add: int64_t[n] frame starts, allocated on its first call with a col0
   DeviceEvent ev_fill0, ev_fill1, ev_tr0, ev_tr1;
   bool fill_timed = false, trace_timed = false;
   // scores as the caller gave them (batch_plan may scale b->subst / go / ge by a power of two)
@@ -1144,6 +1146,100 @@ int pw_tx_cigar_packed(int device, const uint8_t* ops, const uint64_t* offsets, 
     if (roff[n]) HIP_TRY(hipMemcpy(runs_out, d_runs.p, 4 * (size_t)roff[n], hipMemcpyDeviceToHost));
   }
   memcpy(run_offsets_out, roff.data(), 8 * roff.size());
+  return 0;
+}
+
+// ---- pileups (include/pw_pileup.h; kernels in pw_pileup.hip) ----
+struct pw_pileup {
+  int device = 0;
+  int64_t n_cols = 0;
+  int L = 0;
+  DeviceBuffer d_counts;                 // uint32_t[n_cols][L + 2]
+  DeviceBuffer d_sites;                  // pw_pileup_site[n_cols]: allocated by the first pw_pileup_call
+  size_t count_bytes() const { return 4 * (size_t)n_cols * (size_t)(L + 2); }
+};
+
+pw_pileup* pw_pileup_create(int device, int64_t n_cols, int alphabet_len) {
+  if (alphabet_len < 1 || alphabet_len > 32) { fail("pw_pileup_create: alphabet_len must be 1..32"); return nullptr; }
+  if (n_cols < 0 || n_cols > ((int64_t)1 << 36)) { fail("pw_pileup_create: n_cols out of range"); return nullptr; }
+  std::unique_ptr<pw_pileup> p(new pw_pileup);
+  p->device = device; p->n_cols = n_cols; p->L = alphabet_len;
+  if (hipSetDevice(device) != hipSuccess || p->d_counts.ensure(p->count_bytes()) != hipSuccess ||
+      hipMemset(p->d_counts.p, 0, std::max<size_t>(p->count_bytes(), 16)) != hipSuccess) {
+    (void)hipGetLastError();
+    fail("pw_pileup_create: allocation failed");
+    return nullptr;
+  }
+  return p.release();
+}
+void pw_pileup_destroy(pw_pileup* p) {
+  if (!p) return;
+  (void)hipSetDevice(p->device);         // (hipFree waits for the device: no kernel still writes the counts)
+  delete p;
+}
+int pw_pileup_clear(pw_pileup* p, void* stream) {
+  if (!p) return fail("pw_pileup_clear: null pileup");
+  HIP_TRY(hipSetDevice(p->device));
+  if (p->count_bytes()) HIP_TRY(hipMemsetAsync(p->d_counts.p, 0, p->count_bytes(), (hipStream_t)stream));
+  return 0;
+}
+int pw_batch_pileup_add(pw_batch* b, pw_pileup* p, const int64_t* col0, int64_t arena_first, void* stream) {
+  if (!b || !p) return fail("pw_batch_pileup_add: null batch or pileup");
+  if (!b->traced) return fail("pw_batch_pileup_add before a traceback of the batch");
+  if (b->device != p->device) return fail("pw_batch_pileup_add: the batch and the pileup live on different devices");
+  if (p->L < 1 || p->L > 32) return fail("pw_batch_pileup_add: alphabet_len must be 1..32");
+  const hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(hipSetDevice(b->device));
+  const int64_t* d_col0 = nullptr;
+  if (col0 && b->n) {
+    // (the staging buffer is rewritten in place: an add of an earlier call on ANOTHER stream may still read it)
+    if (b->d_col0.p) for (auto& se : b->done_events) if (se.first != st) HIP_TRY(hipEventSynchronize(se.second.e));
+    HIP_TRY(b->d_col0.ensure(8 * (size_t)b->n));
+    HIP_TRY(hipMemcpyAsync(b->d_col0.p, col0, 8 * (size_t)b->n, hipMemcpyHostToDevice, st));
+    d_col0 = (const int64_t*)b->d_col0.p;
+  }
+  HIP_TRY(pw::launch_pileup_add(b->d_pairs.p, b->d_results.p, b->d_tx.p, b->d_arena, b->n, d_col0, arena_first, (uint32_t*)p->d_counts.p,
+                                p->n_cols, p->L, st));
+  return mark_done(b, st);
+}
+void* pw_pileup_counts_device(pw_pileup* p) { return p ? p->d_counts.p : nullptr; }
+int pw_pileup_counts(pw_pileup* p, int64_t lo, int64_t hi, uint32_t* host_out) {
+  if (!p) return fail("pw_pileup_counts: null pileup");
+  if (lo < 0 || hi < lo || hi > p->n_cols) return fail("pw_pileup_counts: columns outside the pileup");
+  if (hi == lo) return 0;
+  if (!host_out) return fail("pw_pileup_counts: null output");
+  HIP_TRY(hipSetDevice(p->device));
+  const size_t row = 4 * (size_t)(p->L + 2);
+  HIP_TRY(hipMemcpy(host_out, (const uint8_t*)p->d_counts.p + row * (size_t)lo, row * (size_t)(hi - lo), hipMemcpyDeviceToHost));
+  return 0;
+}
+int pw_pileup_set_counts(pw_pileup* p, int64_t lo, int64_t hi, const uint32_t* host_in) {
+  if (!p) return fail("pw_pileup_set_counts: null pileup");
+  if (lo < 0 || hi < lo || hi > p->n_cols) return fail("pw_pileup_set_counts: columns outside the pileup");
+  if (hi == lo) return 0;
+  if (!host_in) return fail("pw_pileup_set_counts: null input");
+  HIP_TRY(hipSetDevice(p->device));
+  const size_t row = 4 * (size_t)(p->L + 2);
+  HIP_TRY(hipMemcpy((uint8_t*)p->d_counts.p + row * (size_t)lo, host_in, row * (size_t)(hi - lo), hipMemcpyHostToDevice));
+  return 0;
+}
+int pw_pileup_call(pw_pileup* p, const uint8_t* ref_letters_device, uint32_t min_depth, void* stream) {
+  if (!p) return fail("pw_pileup_call: null pileup");
+  HIP_TRY(hipSetDevice(p->device));
+  if (!p->d_sites.p) HIP_TRY(p->d_sites.ensure(sizeof(pw_pileup_site) * (size_t)p->n_cols));
+  HIP_TRY(pw::launch_pileup_call((const uint32_t*)p->d_counts.p, ref_letters_device, p->n_cols, p->L, min_depth, p->d_sites.p,
+                                 (hipStream_t)stream));
+  return 0;
+}
+void* pw_pileup_sites_device(pw_pileup* p) { return p ? p->d_sites.p : nullptr; }
+int pw_pileup_sites(pw_pileup* p, int64_t lo, int64_t hi, pw_pileup_site* host_out) {
+  if (!p) return fail("pw_pileup_sites: null pileup");
+  if (!p->d_sites.p) return fail("pw_pileup_sites before pw_pileup_call");
+  if (lo < 0 || hi < lo || hi > p->n_cols) return fail("pw_pileup_sites: columns outside the pileup");
+  if (hi == lo) return 0;
+  if (!host_out) return fail("pw_pileup_sites: null output");
+  HIP_TRY(hipSetDevice(p->device));
+  HIP_TRY(hipMemcpy(host_out, (const pw_pileup_site*)p->d_sites.p + lo, sizeof(pw_pileup_site) * (size_t)(hi - lo), hipMemcpyDeviceToHost));
   return 0;
 }
 

@@ -333,7 +333,7 @@ def aligned_batches(arena, offs, lens, pidx, dr, alphabet_len, device=0, max_cel
 
 
 def overlap_alignments(reads, pairs, bands, alphabet, p_min=0., device=0, max_cells=2 * 10 ** 10, want_transcripts=True,
-                       strands=None, complement=None, want_summaries=False, **aligner_kw):
+                       strands=None, complement=None, want_summaries=False, pileup=None, **aligner_kw):
     """Banded overlap alignment (``B_OVERLAP``) of every pair whose band has ``p >= p_min``; the ``diag_range`` is the
     band clamped to the table as ``Aligner`` requires (``pw.py:224-226``).  All reads are uploaded ONCE and the pairs
     refer to them (``BatchAligner.from_arena``); the pairs are solved in batches of at most ``max_cells`` cells
@@ -343,9 +343,23 @@ def overlap_alignments(reads, pairs, bands, alphabet, p_min=0., device=0, max_ce
     of a minus pair is the reverse complement of ``reads[j]``, ``mutant_start`` and the transcript are in its frame
     (:func:`minus_to_forward`), and every dict also reports its ``strand``.  With ``want_summaries`` every dict gains
     ``summary``: the op counts, gap runs and match bounds of its transcript (the fields of ``batch.SUMMARY_DTYPE``, in the
-    transcript's own frame), reduced on the device -- with or without ``want_transcripts``."""
-    from .batch import pack_reads, summary_dict
+    transcript's own frame), reduced on the device -- with or without ``want_transcripts``.
+
+    ``pileup``: None, or a :class:`biseqt_amd.batch.Pileup` that spans the arena of ``pack_reads(reads)`` -- ``n_cols`` is the
+    size of that arena in bytes, ``alphabet_len`` the alphabet's.  Every batch then adds its pairs onto their ORIGIN reads
+    (:meth:`BatchAligner.pileup_add` with ``arena_first = 0`` and no ``col0``), with or without ``want_transcripts``: read
+    ``a`` of a pair ``(a, b)`` is always in its forward frame, minus strand included, where the letters piled onto it are
+    those of ``rc(reads[b])``.  With ``arena, offs, lens = pack_reads(reads)``, letter ``x`` of read ``r`` is column
+    ``offs[r] + x``: the columns of read ``r`` are ``pileup.counts(offs[r], offs[r] + lens[r])``; the columns between two
+    reads (alignment padding) stay zero.  The caller owns the pileup."""
+    from .batch import Pileup, pack_reads, summary_dict
     arena, offs, lens = pack_reads(reads)
+    if pileup is not None:
+        if not isinstance(pileup, Pileup) or not pileup.handle:
+            raise ValueError('pileup must be an open biseqt_amd.batch.Pileup')
+        if pileup.n_cols != arena.nbytes or pileup.alphabet_len != len(alphabet) or pileup.device != device:
+            raise ValueError('pileup must span the arena of pack_reads(reads): n_cols == %d, alphabet_len %d, on device %d'
+                             % (arena.nbytes, len(alphabet), device))
     sflags = _strand_flags(strands, len(pairs))
     comp = _complement(complement, len(alphabet), alphabet) if sflags is not None and sflags.any() else None
     sel, dr = [], []
@@ -370,6 +384,9 @@ def overlap_alignments(reads, pairs, bands, alphabet, p_min=0., device=0, max_ce
         res = b.results()
         txs = b.transcripts(res) if want_transcripts else [None] * (stop - start)
         sums = b.summaries() if want_summaries else None
+        if pileup is not None:
+            b.pileup_add(pileup)
+            b.sync()                                               # (the batch goes when the generator moves on)
         for k in range(stop - start):
             if res['opt_i'][k] < 0:
                 continue

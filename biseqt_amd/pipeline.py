@@ -11,7 +11,7 @@ the reference's, statement by statement.  ``map_queries`` is the many-queries-on
 import numpy as np
 
 from . import _pwlib as W
-from .batch import BatchAligner, DeviceArena, cigar_strings, pack_reads, summary_dict
+from .batch import BatchAligner, DeviceArena, Pileup, cigar_strings, pack_reads, summary_dict
 from .blot import WordBlot, WordBlotLocalRef
 from .overlap import _complement
 from .pw import Alignment
@@ -127,8 +127,30 @@ def query_interval(strand, mutant_start, len_aln, query_len):
     return query_len - (mutant_start + len_aln), query_len - mutant_start
 
 
+def pileup_col0(res, per_query, which):
+    """The ``col0`` array of :meth:`BatchAligner.pileup_add` for the batch of :func:`map_queries`: 0 for a chosen record, -1
+    for the others.  ``res`` are the batch's records (query by query, rank order within a query), ``per_query`` the number
+    of records of every query.  A record has an alignment when ``opt_i >= 0 and tx_len > 0``.  ``which`` = ``'all'`` chooses
+    every such record, ``'best'`` per query the one with the highest score, a tie going to the earlier one."""
+    has = (np.asarray(res['opt_i']) >= 0) & (np.asarray(res['tx_len']) > 0)
+    col0 = np.full(len(has), -1, np.int64)
+    if which == 'all':
+        col0[has] = 0
+        return col0
+    k = 0
+    for n in per_query:
+        best = None
+        for r in range(k, k + n):
+            if has[r] and (best is None or res['score'][r] > res['score'][best]):
+                best = r
+        if best is not None:
+            col0[best] = 0
+        k += n
+    return col0
+
+
 def map_queries(ref, queries, K_min, p_min, wordlen, g_max, sensitivity, keep=3, device=0, aligner_kw=None, alignments=True,
-                strands='+', complement=None, cigar=None):
+                strands='+', complement=None, cigar=None, pileup=None, pileup_records='best'):
     """Map many short queries onto one reference sequence: Word-Blot local similarities of all queries in one pass
     (:meth:`WordBlotLocalRef.similar_segments_many`), then a banded local alignment of the best segments of every query,
     all in ONE lane-packed batch.  The flow of ``experiments/blot_ig_genotyping.py:45-101`` as a library function: per
@@ -161,13 +183,31 @@ def map_queries(ref, queries, K_min, p_min, wordlen, g_max, sensitivity, keep=3,
     and the aligned sequence as the query (None without an alignment), run-length encoded on the device from the ops
     (:meth:`BatchAligner.cigars`) in both ``alignments=`` modes -- with ``alignments=False`` still no transcript leaves the
     device.  On the minus strand the CIGAR is in the frame of ``T = rc(query)`` against the forward reference, which is PAF's
-    and SAM's convention for ``-``: nothing is reversed."""
+    and SAM's convention for ``-``: nothing is reversed.
+
+    ``pileup``: None (the default: no further launch, identical output) or a :class:`biseqt_amd.batch.Pileup` with
+    ``n_cols == len(ref)`` and the reference's alphabet length, on ``device``.  Behind the batch's traceback the records
+    ``pileup_records`` names add their ops to the columns of ``ref`` (:meth:`BatchAligner.pileup_add`; column = reference
+    position) without a transcript leaving the device: ``'best'`` -- per query the record with an alignment and the highest
+    score, a tie going to the earlier one in rank order -- or ``'all'`` -- every record with an alignment.  It works in both
+    ``alignments=`` modes, with any ``strands`` and any ``cigar``; a minus-strand record piles the letters of ``rc(query)``
+    onto the forward reference, which is what its frame already is.  The function returns what it returns without
+    ``pileup``; the caller owns the pileup (adding is cumulative: several calls may add to one) and reads it with
+    ``counts()``, or ``call()`` and ``sites()`` / ``consensus()`` / ``variants()``."""
     assert isinstance(ref, Sequence) and all(isinstance(T, Sequence) for T in queries)
     queries = list(queries)
     if strands not in ('+', '-', 'both'):
         raise ValueError("strands is '+', '-' or 'both', not %r" % (strands,))
     if cigar not in (None, 'extended', 'classic'):
         raise ValueError("cigar is None, 'extended' or 'classic', not %r" % (cigar,))
+    if pileup_records not in ('best', 'all'):
+        raise ValueError("pileup_records is 'best' or 'all', not %r" % (pileup_records,))
+    if pileup is not None:
+        if not isinstance(pileup, Pileup) or not pileup.handle:
+            raise ValueError('pileup must be an open biseqt_amd.batch.Pileup')
+        if pileup.n_cols != len(ref) or pileup.alphabet_len != len(ref.alphabet) or pileup.device != device:
+            raise ValueError('pileup must have n_cols == len(ref) = %d and alphabet_len %d, on device %d'
+                             % (len(ref), len(ref.alphabet), device))
     stranded = strands != '+'
     kw = dict(match_score=1, mismatch_score=-3, go_score=-5, ge_score=-2)
     kw.update(aligner_kw or {})
@@ -215,6 +255,10 @@ def map_queries(ref, queries, K_min, p_min, wordlen, g_max, sensitivity, keep=3,
                 res, sums = _run_summarized(b)
             if cigar is not None:
                 cgs = cigar_strings(*b.cigars(cigar))
+            if pileup is not None:
+                # the reference is read 0 at arena offset 0: a chosen record's frame starts at column 0
+                b.pileup_add(pileup, col0=pileup_col0(res, [len(recs) for recs in out], pileup_records))
+                b.sync()
     k = 0
     for q, recs in enumerate(out):
         for rec in recs:
