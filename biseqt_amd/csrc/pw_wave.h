@@ -652,6 +652,8 @@ PW_FN s2_t as_s2(uint32_t v) { return __builtin_bit_cast(s2_t, v); }
 PW_FN u2_t as_u2(uint32_t v) { return __builtin_bit_cast(u2_t, v); }
 PW_FN uint32_t add(uint32_t a, uint32_t b) { return __builtin_bit_cast(uint32_t, (u2_t)(as_u2(a) + as_u2(b))); }
 PW_FN uint32_t sub(uint32_t a, uint32_t b) { return __builtin_bit_cast(uint32_t, (u2_t)(as_u2(a) - as_u2(b))); }
+// packed add where no half can carry: a plain 32-bit add.  Contract: no half of a in [0xff80, 0xffff], b a byte per half
+PW_FN uint32_t add32(uint32_t a, uint32_t b) { return a + b; }
 // unsigned saturating subtract per half: max(a - b, 0) (v_pk_sub_u16 ... clamp)
 PW_FN uint32_t subsat(uint32_t a, uint32_t b) { return __builtin_bit_cast(uint32_t, __builtin_elementwise_sub_sat(as_u2(a), as_u2(b))); }
 PW_FN uint32_t max(uint32_t a, uint32_t b) { return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(as_s2(a), as_s2(b))); }
@@ -686,6 +688,17 @@ PW_FN int32_t sl(uint32_t v) { return (int16_t)(v & 0xffffu); }
 PW_FN int32_t sh(uint32_t v) { return (int16_t)(v >> 16); }
 PW_FN uint32_t add(uint32_t a, uint32_t b) { return mk((a & 0xffffu) + (b & 0xffffu), (a >> 16) + (b >> 16)); }
 PW_FN uint32_t sub(uint32_t a, uint32_t b) { return mk((a & 0xffffu) - (b & 0xffffu), (a >> 16) - (b >> 16)); }
+// add32's contract, checked here on the CPU only: no half of `a` lies in [0xff80, 0xffff] (b holds a byte per half, so no
+// half carries into its neighbour).  Breaches are counted, not fatal: the CPU tests read and reset the count.
+#if !defined(__HIPCC__)
+inline unsigned& add32_breaches() { static unsigned n = 0; return n; }
+PW_FN uint32_t add32(uint32_t a, uint32_t b) {
+  if ((a & 0xffffu) >= 0xff80u || (a >> 16) >= 0xff80u) add32_breaches()++;
+  return a + b;
+}
+#else
+PW_FN uint32_t add32(uint32_t a, uint32_t b) { return a + b; }   // (the host pass of a device build: never run)
+#endif
 PW_FN uint32_t subsat(uint32_t a, uint32_t b) {
   const uint32_t al = a & 0xffffu, bl = b & 0xffffu, ah = a >> 16, bh = b >> 16;
   return mk(al > bl ? al - bl : 0u, ah > bh ? ah - bh : 0u);
@@ -730,6 +743,14 @@ PW_FN uint32_t pack(int32_t lo, int32_t hi) { return ((uint32_t)lo & 0xffffu) | 
 PW_FN int32_t lo_s(uint32_t v) { return (int32_t)(int16_t)(v & 0xffffu); }
 PW_FN int32_t hi_s(uint32_t v) { return (int32_t)(int16_t)(v >> 16); }
 }  // namespace pk
+#if !defined(__HIPCC__)
+// (the CPU emulator's library exports the count of pk::add32 contract breaches; reset = 1 clears it after reading)
+extern "C" __attribute__((used, visibility("default"))) inline unsigned pw_pk_add32_breaches(int reset) {
+  const unsigned n = pk::add32_breaches();
+  if (reset) pk::add32_breaches() = 0;
+  return n;
+}
+#endif
 
 // RULE selects the begin / end rules the kernel serves:
 //   0  LOCAL / B_LOCAL            begin anywhere (B = 0 in every started cell), end = first best cell (tracked)
@@ -889,7 +910,30 @@ struct WaveFill16 {
     if (MAT) {
       // oc / och: the matrix rows of the low / high cell's origin letter, mc: the two selectors; lo4 (FIXSEL): the low
       // half's selector is the one that carries the + 4
-      const uint32_t hb = pk::add(Hs, lo4 ? pk::perm(oc, och, mc) : pk::perm(och, oc, mc));
+      //
+      // Begin-anywhere rules: the diagonal add is a plain 32-bit add (v_add_u32, the 2-cycle issue class, instead of
+      // v_pk_add_u16).  INVARIANT: no half of H lies in [0xff80, 0xffff] on entry; the addend is a row byte, 0 .. 127, in each
+      // half, so no half carries into its neighbour and the bits are the packed add's.  A half of H is one of
+      //   * a started cell's score, or a cell's beyond its diagonal's end: 0 .. 8191 -- admit_packed (pw_plan.h) holds
+      //     min(X, Y) * max(subst) to 8000, to 2047 times 4 in the scores-times-4 form, and letters outside a sequence score
+      //     the matrix minimum, which packed_matrix_bytes_ok requires to be <= 0;
+      //   * the first diagonal above the band (slot ndiag): begins at step 0 (tfirst_of), so it is 0 .. 8191 like a started
+      //     cell from its first update on.  (Left at the sentinel it took the in-band offers H + ge + go, small negative
+      //     values, and carried into the slot it shares a register with.)  Its offers go out 8192 lower (blocked), below every
+      //     started cell as before;
+      //   * a cell that has not started, a slot further above the band, a lane without a pair: the sentinel -8192 plus what
+      //     the substitutions of at most min(X, Y) in-table cells add, or an offer that came through slot ndiag -- at most
+      //     8000 - 8192 = -192, i.e. 0xff40.  A positive mismatch score cannot lift them further: admit_packed sends such
+      //     scores to this form, whose off-sequence letters score <= 0 (the creep commit 78c26ef bounded).  From below they
+      //     are held by the maximum with the sentinel in the blocks where diagonals start, and elsewhere by the offers of
+      //     their neighbours: slot ndiag + k stays at or above -8192 - k |go + ge|.  The planner's layouts leave at most 255
+      //     spare slots and |go + ge| <= 100, so only the last ten of them could fall past -32768 and wrap round to this
+      //     range, and only with every substitution on the way at -100 too; a layout forced wider (PWLIB_PACKED_BK) can.
+      //     What then carries is one spare slot into another: the band reads neither except through slot ndiag's offers.
+      // The rules that begin on the table edge hold negative scores: they keep the packed add.  The CPU emulation of
+      // pk::add32 counts every breach of the invariant.
+      const uint32_t sub2 = lo4 ? pk::perm(oc, och, mc) : pk::perm(och, oc, mc);
+      const uint32_t hb = ANYB ? pk::add32(Hs, sub2) : pk::add(Hs, sub2);
       hM = FLOOR0 ? pk::subsat(hb, BIASV) : pk::sub(hb, BIASV);
     } else {
       const uint32_t ne = pk::minu(oc ^ mc, ONE);               // 0 where the letters match
@@ -1156,6 +1200,7 @@ struct WaveFill16 {
 
   PW_FN int tfirst_of(int j) const {      // first step of slot j's diagonal; never for a diagonal outside the band
     const int dd = li * BK + j, d = pd.dmin + dd;
+    if (MAT && ANYB && valid && dd == ndiag) return 0;   // the first diagonal above the band: see cellpair, the diagonal add
     return (valid && dd < ndiag) ? (d < 0 ? -d : d) - pd.s0 : 32767;
   }
   PW_FN int tlast_of(int j) const {
