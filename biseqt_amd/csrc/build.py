@@ -4,8 +4,8 @@
 
 One object per (score type, diagonals-per-lane) fill translation unit plus the traceback unit and the
 host API, compiled in parallel, linked into one shared object that exports the four drop-in functions
-of include/pwlib.h, the batch API of include/pw_batch.h, the alignment summaries of include/pw_txsum.h, the CIGARs of include/pw_cigar.h, the pileups of include/pw_pileup.h and the seed APIs of include/pw_seeds.h, pw_mseeds.h, pw_qseeds.h and
-pw_overlap.h.  The header is copied next to the library
+of include/pwlib.h, the batch API of include/pw_batch.h, the alignment summaries of include/pw_txsum.h, the CIGARs of include/pw_cigar.h, the pileups of include/pw_pileup.h, the seed APIs of include/pw_seeds.h, pw_mseeds.h, pw_qseeds.h and
+pw_overlap.h, and the k-mer table of include/pw_kmers.h.  The header is copied next to the library
 (biseqt_amd/pwlib/pwlib.h) the way the reference keeps biseqt/pwlib/pwlib.{h,so} side by side.
 """
 import concurrent.futures
@@ -122,7 +122,12 @@ def _jobs():
                   os.path.join(ROOT, 'include', 'pw_qseeds.h')]))
     obj = os.path.join(OBJ_DIR, 'pw_overlap.o')
     jobs.append((obj, [HIPCC] + COMMON + ['-Wno-unused-parameter', '-c', os.path.join(HERE, 'pw_overlap.hip'), '-o', obj],
-                 [os.path.join(HERE, 'pw_overlap.hip'), os.path.join(HERE, 'pw_complement.h'), os.path.join(ROOT, 'include', 'pw_overlap.h')]))
+                 [os.path.join(HERE, 'pw_overlap.hip'), os.path.join(HERE, 'pw_complement.h'), os.path.join(HERE, 'pw_kmer_encode.h'),
+                  os.path.join(ROOT, 'include', 'pw_overlap.h')]))
+    obj = os.path.join(OBJ_DIR, 'pw_kmers.o')
+    jobs.append((obj, [HIPCC] + COMMON + ['-Wno-unused-parameter', '-c', os.path.join(HERE, 'pw_kmers.hip'), '-o', obj],
+                 [os.path.join(HERE, 'pw_kmers.hip'), os.path.join(HERE, 'pw_complement.h'), os.path.join(HERE, 'pw_kmer_encode.h'),
+                  os.path.join(ROOT, 'include', 'pw_kmers.h'), os.path.join(ROOT, 'include', 'pw_overlap.h')]))
     obj = os.path.join(OBJ_DIR, 'pwlib_api.o')
     jobs.append((obj, [HIPCC] + COMMON + ['-x', 'hip', '-c', os.path.join(HERE, 'pwlib_api.cpp'), '-o', obj],
                  [os.path.join(HERE, 'pwlib_api.cpp'), os.path.join(HERE, 'pw_model.h'), os.path.join(ROOT, 'include', 'pwlib.h'),

@@ -26,6 +26,7 @@
 #include "../../include/pw_overlap.h"
 #include "pw_complement.h"
 #include "pw_hip_host.h"
+#include "pw_kmer_encode.h"
 
 namespace {
 
@@ -35,20 +36,6 @@ void set_err(const std::string& s) { g_err = s; }
 #define CHECK(call) PW_HIP_CHECK(set_err, call)
 
 struct DPair { uint64_t s_off, t_off; int32_t s_len, t_len; uint64_t hbase; };   // hbase: start of its histogram
-
-// the k-mer s[0], s[1], ... s[k - 1], in base L
-__device__ __forceinline__ uint64_t kmer_fwd(const uint8_t* __restrict__ s, int k, int L) {
-  uint64_t v = 0;
-  for (int t = 0; t < k; t++) v = v * (uint64_t)L + s[t];
-  return v;
-}
-// The k-mer at position q of rc(read), never materialised: comp(read[len - 1 - q]), comp(read[len - 2 - q]), ... -- read
-// backwards from the forward letters, s_last = &read[len - 1 - q].  q <= len - k, so s_last[-t] stays inside the read.
-__device__ __forceinline__ uint64_t kmer_rc(const uint8_t* __restrict__ s_last, int k, int L, const uint8_t* s_comp) {
-  uint64_t v = 0;
-  for (int t = 0; t < k; t++) v = v * (uint64_t)L + s_comp[s_last[-t]];
-  return v;
-}
 
 // side 0: S reads, side 1: T reads.  start[p] = index of pair p's first k-mer on this side (start[n] = total).
 __global__ __launch_bounds__(256) void k_enc_batch(const uint8_t* __restrict__ arena, const DPair* __restrict__ pairs,
@@ -292,30 +279,51 @@ __global__ __launch_bounds__(256) void k_first_d(const uint32_t* __restrict__ fi
 }
 
 // ---- all reads against all reads through ONE index (K9) -----------------------------------------------------------
-// K9a: k-mer of every position of every read; value = (read << 32) | pos.  rstart[r] = first k-mer index of read r.
-__global__ __launch_bounds__(256) void k_enc_reads(const uint8_t* __restrict__ arena, const uint64_t* __restrict__ roff,
-                                                   const uint64_t* __restrict__ rstart, int64_t nreads, int64_t total, int k, int L,
-                                                   uint64_t* __restrict__ keys, uint64_t* __restrict__ vals) {
-  const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (g >= total) return;
-  const int64_t r = upper_bound_dev<uint64_t>(rstart, nreads + 1, (uint64_t)g) - 1;
-  const uint32_t q = (uint32_t)(g - (int64_t)rstart[r]);
-  keys[g] = kmer_fwd(arena + roff[r] + q, k, L);
-  vals[g] = ((uint64_t)r << 32) | q;
-}
+// (K9a and K9a', the read encoders, live in pw_kmer_encode.h: the k-mer table of pw_kmers.hip is built by the same two)
 // K9b: self join.  Inside a run of equal k-mers the entries are ordered by (read, pos); element e pairs with every
 // later entry of a DIFFERENT read: those start at fs[e].
+// CAP (pw_overlap_all_pairs_capped): a k-mer whose run [lo, hi) holds more than max_occ entries is masked -- its entries get
+// cnt[e] = 0, so its seeds are never expanded, sorted or grouped.  The run is counted over the WHOLE index, before the shard
+// test, so every rank masks the same k-mers.  stats[0..2] += masked entries, masked runs (counted at their first entry),
+// the seeds this rank's masked entries would have produced: one 64-bit integer atomic per wavefront and counter.
+template <int N>
+__device__ __forceinline__ void cap_tally(const unsigned long long (&t)[N], unsigned long long* __restrict__ stats) {
+  for (int i = 0; i < N; i++) {
+    unsigned long long v = t[i];
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off, 64);
+    if ((threadIdx.x & 63u) == 0 && v) atomicAdd(&stats[i], v);
+  }
+}
+template <bool CAP>
 __global__ __launch_bounds__(256) void k_self_count(const uint64_t* __restrict__ keys, const uint64_t* __restrict__ vals, int64_t n,
-                                                    int shard_rank, int shard_world, uint32_t* __restrict__ fs, uint64_t* __restrict__ cnt) {
+                                                    int shard_rank, int shard_world, uint32_t* __restrict__ fs, uint64_t* __restrict__ cnt,
+                                                    uint32_t max_occ, unsigned long long* __restrict__ stats) {
   const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (e >= n) return;
-  // multi-GPU: the pairs (a, b), a < b, are dealt round-robin by a; every rank joins only its own share
-  if ((int)((vals[e] >> 32) % (uint64_t)shard_world) != shard_rank) { fs[e] = (uint32_t)e; cnt[e] = 0; return; }
-  const int64_t hi = upper_bound_dev<uint64_t>(keys, n, keys[e]);
-  const uint64_t next_read = ((vals[e] >> 32) + 1) << 32;
-  const int64_t f = e + 1 + lower_bound_dev<uint64_t>(vals + e + 1, hi - e - 1, next_read);
-  fs[e] = (uint32_t)f;
-  cnt[e] = (uint64_t)(hi - f);
+  unsigned long long tally[3] = {0, 0, 0};
+  if (e < n) {
+    // multi-GPU: the pairs (a, b), a < b, are dealt round-robin by a; every rank joins only its own share
+    const bool mine = (int)((vals[e] >> 32) % (uint64_t)shard_world) == shard_rank;
+    if (!mine) { fs[e] = (uint32_t)e; cnt[e] = 0; }
+    if (mine || CAP) {
+      const uint64_t key = keys[e];
+      const int64_t hi = upper_bound_dev<uint64_t>(keys, n, key);
+      bool masked = false;
+      if (CAP) {
+        const int64_t lo = lower_bound_dev<uint64_t>(keys, n, key);
+        masked = (uint64_t)(hi - lo) > (uint64_t)max_occ;
+        if (masked) { tally[0] = 1; tally[1] = lo == e ? 1 : 0; }
+      }
+      if (mine) {
+        const uint64_t next_read = ((vals[e] >> 32) + 1) << 32;
+        const int64_t f = e + 1 + lower_bound_dev<uint64_t>(vals + e + 1, hi - e - 1, next_read);
+        fs[e] = (uint32_t)f;
+        cnt[e] = masked ? 0ull : (uint64_t)(hi - f);
+        if (masked) tally[2] = (unsigned long long)(hi - f);
+      }
+    }
+  }
+  if (CAP) cap_tally(tally, stats);
 }
 // one seed per thread: key = rank of the pair (ra < rb) = ra * nreads + rb, value = d = pos_a - pos_b.  Seeds are
 // produced in (k-mer, i, j) order per pair, which a STABLE sort by the pair key keeps.
@@ -331,49 +339,56 @@ __global__ __launch_bounds__(256) void k_self_expand(const uint64_t* __restrict_
   dval[o] = (int32_t)(uint32_t)va - (int32_t)(uint32_t)vb;
 }
 // ---- both strands (K9'): a second index holds the k-mers of rc(read) for every read, computed from the forward letters ----
-// K9a': entry q of read r is the k-mer at position q of rc(read r) (kmer_rc).
-// Generated in ascending (read, q), so inside a run of equal k-mers the stable sort leaves (read, q) ascending.
-__global__ __launch_bounds__(256) void k_enc_reads_rc(const uint8_t* __restrict__ arena, const uint64_t* __restrict__ roff,
-                                                      const int32_t* __restrict__ rlen, const uint64_t* __restrict__ rstart,
-                                                      int64_t nreads, int64_t total, int k, int L, const uint8_t* __restrict__ comp,
-                                                      uint64_t* __restrict__ keys, uint64_t* __restrict__ vals) {
-  __shared__ uint8_t s_comp[36];
-  load_complement(comp, L, s_comp);
-  const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (g >= total) return;
-  const int64_t r = upper_bound_dev<uint64_t>(rstart, nreads + 1, (uint64_t)g) - 1;
-  const uint32_t q = (uint32_t)(g - (int64_t)rstart[r]);
-  keys[g] = kmer_rc(arena + roff[r] + (uint64_t)(rlen[r] - 1) - q, k, L, s_comp);
-  vals[g] = ((uint64_t)r << 32) | q;
-}
 // K9b': forward element e of read a pairs with the forward entries (sel & 1) and the reverse entries (sel & 2) of every read
 // b > a that hold the same k-mer: [ff[e], ff[e] + cf[e]) of the forward index, then [fr[e], ...) of the reverse index.
 // A read is never joined with its own reverse complement, and no reverse entry plays the a side.
+// CAP: occ(x) = the forward entries with the key + the reverse entries with the key, whatever `sel` joins -- count(x) of a k-mer
+// table over both strands (pw_kmers.h).  x is masked exactly when rc(x) is, and the reverse index holds rc(x) as often as the
+// forward index holds x: the masked reverse entries are as many as the masked forward ones, and a masked k-mer that only the
+// reverse index holds is the reverse complement of a masked forward run without reverse entries -- both are counted from the
+// forward entries alone (stats[1] += 2 for such a run).
+template <bool CAP>
 __global__ __launch_bounds__(256) void k_self_count_st(const uint64_t* __restrict__ keys, const uint64_t* __restrict__ vals, int64_t n,
                                                        const uint64_t* __restrict__ rkeys, const uint64_t* __restrict__ rvals, int sel,
                                                        int shard_rank, int shard_world, uint32_t* __restrict__ ff, uint32_t* __restrict__ cf,
-                                                       uint32_t* __restrict__ fr, uint64_t* __restrict__ cnt) {
+                                                       uint32_t* __restrict__ fr, uint64_t* __restrict__ cnt, uint32_t max_occ,
+                                                       unsigned long long* __restrict__ stats) {
   const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (e >= n) return;
-  ff[e] = 0; fr[e] = 0; cf[e] = 0;
-  if ((int)((vals[e] >> 32) % (uint64_t)shard_world) != shard_rank) { cnt[e] = 0; return; }
-  const uint64_t key = keys[e];
-  const uint64_t next_read = ((vals[e] >> 32) + 1) << 32;
-  uint64_t c = 0;
-  if (sel & 1) {
-    const int64_t hi = upper_bound_dev<uint64_t>(keys, n, key);
-    const int64_t f = e + 1 + lower_bound_dev<uint64_t>(vals + e + 1, hi - e - 1, next_read);
-    ff[e] = (uint32_t)f; cf[e] = (uint32_t)(hi - f);
-    c += (uint64_t)(hi - f);
+  unsigned long long tally[3] = {0, 0, 0};
+  if (e < n) {
+    const bool mine = (int)((vals[e] >> 32) % (uint64_t)shard_world) == shard_rank;
+    uint32_t f_f = 0, c_f = 0, f_r = 0;
+    uint64_t c = 0;
+    if (mine || CAP) {
+      const uint64_t key = keys[e];
+      bool masked = false;
+      if (CAP) {
+        const int64_t flo = lower_bound_dev<uint64_t>(keys, n, key), fhi = upper_bound_dev<uint64_t>(keys, n, key);
+        const int64_t rlo = lower_bound_dev<uint64_t>(rkeys, n, key), rhi = upper_bound_dev<uint64_t>(rkeys, n, key);
+        masked = (uint64_t)(fhi - flo) + (uint64_t)(rhi - rlo) > (uint64_t)max_occ;
+        if (masked) { tally[0] = 1; tally[1] = flo == e ? (rhi == rlo ? 2 : 1) : 0; }
+      }
+      if (mine) {
+        const uint64_t next_read = ((vals[e] >> 32) + 1) << 32;
+        if (sel & 1) {
+          const int64_t hi = upper_bound_dev<uint64_t>(keys, n, key);
+          const int64_t f = e + 1 + lower_bound_dev<uint64_t>(vals + e + 1, hi - e - 1, next_read);
+          f_f = (uint32_t)f; c_f = (uint32_t)(hi - f);
+          c += (uint64_t)(hi - f);
+        }
+        if (sel & 2) {
+          const int64_t lo = lower_bound_dev<uint64_t>(rkeys, n, key);
+          const int64_t hi = upper_bound_dev<uint64_t>(rkeys, n, key);
+          const int64_t f = lo + lower_bound_dev<uint64_t>(rvals + lo, hi - lo, next_read);
+          f_r = (uint32_t)f;
+          c += (uint64_t)(hi - f);
+        }
+        if (masked) { tally[2] = c; f_f = 0; c_f = 0; f_r = 0; c = 0; }
+      }
+    }
+    ff[e] = f_f; cf[e] = c_f; fr[e] = f_r; cnt[e] = c;
   }
-  if (sel & 2) {
-    const int64_t lo = lower_bound_dev<uint64_t>(rkeys, n, key);
-    const int64_t hi = upper_bound_dev<uint64_t>(rkeys, n, key);
-    const int64_t f = lo + lower_bound_dev<uint64_t>(rvals + lo, hi - lo, next_read);
-    fr[e] = (uint32_t)f;
-    c += (uint64_t)(hi - f);
-  }
-  cnt[e] = c;
+  if (CAP) cap_tally(tally, stats);
 }
 // one seed per thread: key = 2 (ra * nreads + rb) + strand, value = d = pos_a - pos_b with pos_b in the frame of rc(rb) on the
 // minus strand.  Per pair and strand the seeds come out in (k-mer, i, j) order, which the stable sort by the key keeps.
@@ -575,23 +590,6 @@ int upload(DeviceBuffer& buf, const void* host, size_t bytes) {
   CHECK(hipMemcpy(buf.p, host, bytes, hipMemcpyHostToDevice));
   return 0;
 }
-// n (key, value) pairs stably sorted by the low `bits` bits of the key
-template <typename K, typename V>
-hipError_t sort_pairs(DeviceBuffer& tmp, const DeviceBuffer& kin, DeviceBuffer& kout, const DeviceBuffer& vin, DeviceBuffer& vout,
-                      size_t n, int bits) {
-  return rocprim_run(tmp, [&](void* t, size_t& b) {
-    return rocprim::radix_sort_pairs(t, b, (const K*)kin.p, (K*)kout.p, (const V*)vin.p, (V*)vout.p, n, 0u, (unsigned)bits,
-                                     (hipStream_t) nullptr);
-  });
-}
-// out[i] = in[0] + ... + in[i - 1]
-hipError_t scan_u64(DeviceBuffer& tmp, const DeviceBuffer& in, DeviceBuffer& out, size_t n) {
-  return rocprim_run(tmp, [&](void* t, size_t& b) {
-    return rocprim::exclusive_scan(t, b, (const uint64_t*)in.p, (uint64_t*)out.p, (uint64_t)0, n, rocprim::plus<uint64_t>(),
-                                   (hipStream_t) nullptr);
-  });
-}
-
 // strand (host, one byte per pair of the chunk) and d_comp are null on the forward-only path
 int run_chunk(const uint8_t* d_arena, const pw_read_pair* pairs, int64_t n, int L, int k, int kbits, BandConst bc,
               pw_overlap_band* out, hipEvent_t ev0, hipEvent_t ev1, float* ms, const uint8_t* strand = nullptr,
@@ -663,6 +661,9 @@ int run_chunk(const uint8_t* d_arena, const pw_read_pair* pairs, int64_t n, int 
 struct AllPairs {
   const uint8_t* d_arena; const uint8_t* d_comp;
   int64_t R; int L, k, kbits, sel, shard_rank, shard_world; int64_t max_pairs; BandConst bc;
+  uint32_t max_occ;                                    // 0: no cap, K9b / K9b' as they always were
+  pw_overlap_cap_stats cap{};                          // (max_occ != 0) filled by self_join
+  DeviceBuffer dstats;
   bool st = false;                                     // sel != 1
   uint64_t K = 0, NS = 0;                              // k-mers per index, seeds
   unsigned long long NP = 0;                           // candidate pairs
@@ -690,18 +691,28 @@ struct AllPairs {
   // share a k-mer.
   int self_join() {
     const dim3 gK((unsigned)((K + 255) / 256));
+    const bool capped = max_occ != 0;
+    if (capped) { CHECK(dstats.ensure(24)); CHECK(hipMemsetAsync(dstats.p, 0, 24, nullptr)); }
+    auto* const count_kernel = capped ? k_self_count<true> : k_self_count<false>;
+    auto* const count_st_kernel = capped ? k_self_count_st<true> : k_self_count_st<false>;
     if (st)
-      hipLaunchKernelGGL(k_self_count_st, gK, blk, 0, nullptr, (const uint64_t*)ks.p, (const uint64_t*)vs.p, (int64_t)K,
+      hipLaunchKernelGGL(count_st_kernel, gK, blk, 0, nullptr, (const uint64_t*)ks.p, (const uint64_t*)vs.p, (int64_t)K,
                          (const uint64_t*)kr.p, (const uint64_t*)vr.p, sel, shard_rank, shard_world, (uint32_t*)fs.p, (uint32_t*)cf.p,
-                         (uint32_t*)fr.p, (uint64_t*)cnt.p);
+                         (uint32_t*)fr.p, (uint64_t*)cnt.p, max_occ, (unsigned long long*)dstats.p);
     else
-      hipLaunchKernelGGL(k_self_count, gK, blk, 0, nullptr, (const uint64_t*)ks.p, (const uint64_t*)vs.p, (int64_t)K, shard_rank, shard_world,
-                         (uint32_t*)fs.p, (uint64_t*)cnt.p);
+      hipLaunchKernelGGL(count_kernel, gK, blk, 0, nullptr, (const uint64_t*)ks.p, (const uint64_t*)vs.p, (int64_t)K, shard_rank, shard_world,
+                         (uint32_t*)fs.p, (uint64_t*)cnt.p, max_occ, (unsigned long long*)dstats.p);
     CHECK(scan_u64(tmp, cnt, off, (size_t)K));
     uint64_t last_off = 0, last_cnt = 0;
     CHECK(hipMemcpy(&last_off, (uint64_t*)off.p + (K - 1), 8, hipMemcpyDeviceToHost));
     CHECK(hipMemcpy(&last_cnt, (uint64_t*)cnt.p + (K - 1), 8, hipMemcpyDeviceToHost));
     NS = last_off + last_cnt;
+    if (capped) {
+      unsigned long long t[3];
+      CHECK(hipMemcpy(t, dstats.p, 24, hipMemcpyDeviceToHost));
+      // (both strands: the reverse index holds as many masked entries as the forward one, see K9b')
+      cap = pw_overlap_cap_stats{(st ? 2 : 1) * K, (st ? 2 : 1) * t[0], t[1], NS, t[2]};
+    }
     if (NS == 0) return 0;
     if (NS >= (1ull << 32)) { set_err("more than 2^32 seeds between the reads: use a longer word"); return -1; }
     CHECK(pk_in.ensure(8 * (size_t)NS)); CHECK(dv_in.ensure(4 * (size_t)NS)); CHECK(pk.ensure(8 * (size_t)NS)); CHECK(dv.ensure(4 * (size_t)NS));
@@ -843,24 +854,6 @@ struct AllPairs {
   }
 };
 
-// The argument checks of both entry points, in this order: word range, counts and pointers (bad_args), coefficients,
-// shard (bad_shard), L^k, reads inside the arena (outside(i) for i < n), letters inside the alphabet.  kbits: the width of
-// the k-mer keys, the bits of L^k - 1.  L^k = 2^62 is accepted here (pw_seeds_create refuses it: its masked key is L^k).
-template <typename Outside>
-int check_args(int L, int k, bool bad_args, double len_coeff, double radius_coeff, double word_p_null, bool bad_shard, int64_t n,
-               Outside outside, const uint8_t* arena, uint64_t arena_bytes, int* kbits) {
-  if (L < 1 || L > 36 || k < 1 || k > 31) { set_err("alphabet_len 1..36, wordlen 1..31"); return -1; }
-  if (bad_args) { set_err("bad arguments"); return -1; }
-  if (!(len_coeff > 0) || !(radius_coeff > 0) || !(word_p_null > 0)) { set_err("coefficients must be positive"); return -1; }
-  if (bad_shard) { set_err("bad shard"); return -1; }
-  uint64_t kmax = 1;
-  for (int i = 0; i < k; i++) { if (kmax > (1ull << 62) / (uint64_t)L) { set_err("alphabet_len ^ wordlen must be below 2^62"); return -1; } kmax *= (uint64_t)L; }
-  *kbits = bits_for(kmax - 1);
-  for (int64_t i = 0; i < n; i++) if (outside(i)) { set_err("a read lies outside the arena"); return -1; }
-  for (uint64_t i = 0; i < arena_bytes; i++) if (arena[i] >= L) { set_err("letter outside the alphabet"); return -1; }
-  return 0;
-}
-
 // the complement of a call (pw_complement.h), refusals into this API's error channel; an alphabet out of range passes here:
 // check_args reports it
 int check_complement(const uint8_t* comp, int L) { return ::check_complement(set_err, comp, L); }
@@ -879,13 +872,15 @@ int upload_complement(const uint8_t* comp, int L, DeviceBuffer& d_comp) { return
 int all_pairs(int device, const uint8_t* arena, uint64_t arena_bytes, const uint64_t* read_off, const int32_t* read_len,
               int64_t n_reads, int alphabet_len, int wordlen, double len_coeff, double radius_coeff, double word_p_null,
               bool stranded, const uint8_t* complement, int strands, int shard_rank, int shard_world, int64_t max_pairs,
-              int32_t* pair_a, int32_t* pair_b, uint8_t* pair_strand, pw_overlap_band* out, int64_t* n_out) {
+              int32_t* pair_a, int32_t* pair_b, uint8_t* pair_strand, pw_overlap_band* out, int64_t* n_out, uint32_t max_occ = 0,
+              pw_overlap_cap_stats* stats = nullptr) {
+  if (stats) memset(stats, 0, sizeof *stats);
   if (stranded) {
     if (strands < PW_STRAND_PLUS || strands > PW_STRAND_BOTH) { set_err("strands must be 1 (+), 2 (-) or 3 (both)"); return -1; }
     if (strands != PW_STRAND_PLUS && check_complement(complement, alphabet_len) != 0) return -1;
   }
   int kbits = 0;
-  if (check_args(alphabet_len, wordlen,
+  if (check_args(set_err, alphabet_len, wordlen,
                  n_reads < 0 || n_reads >= (1ll << 31) || !n_out || (n_reads && (!read_off || !read_len)) || (stranded && !pair_strand),
                  len_coeff, radius_coeff, word_p_null, shard_world < 1 || shard_rank < 0 || shard_rank >= shard_world, n_reads,
                  [&](int64_t r) { return read_len[r] < 0 || read_off[r] + (uint64_t)read_len[r] > arena_bytes; },
@@ -898,8 +893,9 @@ int all_pairs(int device, const uint8_t* arena, uint64_t arena_bytes, const uint
   if (strands != PW_STRAND_PLUS && upload_complement(complement, alphabet_len, d_comp) != 0) return -1;
   float ms = 0.f;
   AllPairs job{(const uint8_t*)d_arena.p, (const uint8_t*)d_comp.p, n_reads, alphabet_len, wordlen, kbits, strands, shard_rank, shard_world,
-               max_pairs, BandConst{len_coeff, radius_coeff, word_p_null}};
+               max_pairs, BandConst{len_coeff, radius_coeff, word_p_null}, max_occ};
   const int rc = job.run(read_off, read_len, pair_a, pair_b, pair_strand, out, n_out, &ms);
+  if (stats) *stats = job.cap;                         // (what the join counted, also where a refusal followed it)
   if (rc == 0 && stranded && strands == PW_STRAND_PLUS) memset(pair_strand, 0, (size_t)*n_out);
   g_ms = (double)ms;
   return rc;
@@ -911,7 +907,7 @@ int bands(int device, const uint8_t* arena, uint64_t arena_bytes, const pw_read_
           pw_overlap_band* out) {
   static_assert(sizeof(pw_overlap_band) == 64, "pw_overlap_band is 64 bytes");
   int kbits = 0;
-  if (check_args(alphabet_len, wordlen, n_pairs < 0 || (n_pairs && (!pairs || !out)), len_coeff, radius_coeff, word_p_null, false,
+  if (check_args(set_err, alphabet_len, wordlen, n_pairs < 0 || (n_pairs && (!pairs || !out)), len_coeff, radius_coeff, word_p_null, false,
                  n_pairs, [&](int64_t p) {
                    const pw_read_pair& r = pairs[p];
                    return r.s_len < 0 || r.t_len < 0 || r.s_off + (uint64_t)r.s_len > arena_bytes || r.t_off + (uint64_t)r.t_len > arena_bytes;
@@ -978,6 +974,15 @@ int pw_overlap_all_pairs_stranded(int device, const uint8_t* arena, uint64_t are
                                   pw_overlap_band* out, int64_t* n_out) {
   return all_pairs(device, arena, arena_bytes, read_off, read_len, n_reads, alphabet_len, wordlen, len_coeff, radius_coeff, word_p_null,
                    true, complement, strands, shard_rank, shard_world, max_pairs, pair_a, pair_b, pair_strand, out, n_out);
+}
+
+int pw_overlap_all_pairs_capped(int device, const uint8_t* arena, uint64_t arena_bytes, const uint64_t* read_off,
+                                const int32_t* read_len, int64_t n_reads, int alphabet_len, int wordlen, double len_coeff,
+                                double radius_coeff, double word_p_null, const uint8_t* complement, int strands, int shard_rank,
+                                int shard_world, int64_t max_pairs, int32_t* pair_a, int32_t* pair_b, uint8_t* pair_strand,
+                                pw_overlap_band* out, int64_t* n_out, uint32_t max_occ, pw_overlap_cap_stats* stats) {
+  return all_pairs(device, arena, arena_bytes, read_off, read_len, n_reads, alphabet_len, wordlen, len_coeff, radius_coeff, word_p_null,
+                   true, complement, strands, shard_rank, shard_world, max_pairs, pair_a, pair_b, pair_strand, out, n_out, max_occ, stats);
 }
 
 void* pw_overlap_arena_upload(int device, const uint8_t* host_arena, uint64_t bytes, uint64_t total_bytes, int64_t n_frames,

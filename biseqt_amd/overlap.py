@@ -156,9 +156,10 @@ def _result(d, rad, L, n_in_band, word_p, alphabet_len, wordlen):
     return res
 
 
-def _records_to_results(reads, pairs, recs, wordlen, alphabet, g_max, sensitivity, device, flags=None, comp=None):
+def _records_to_results(reads, pairs, recs, wordlen, alphabet, g_max, sensitivity, device, flags=None, comp=None, fallback=True):
     """Device records -> the reference's dicts (shared by the pair-list and the all-pairs paths).  ``flags``: 0 / 1 per pair
-    (None: all forward); the T of a minus pair is the reverse complement of its read."""
+    (None: all forward); the T of a minus pair is the reverse complement of its read.  ``fallback=False``: a ``tie > 1`` pair
+    keeps the record's own choice (largest ``w``, then smallest ``d``) instead of going to the single-pair path."""
     L = len(alphabet)
     out, n_fallback = [], 0
 
@@ -173,7 +174,7 @@ def _records_to_results(reads, pairs, recs, wordlen, alphabet, g_max, sensitivit
             # every p is 0: max() keeps the first row of the table (blot.py:569)
             word_p = (r['n_first'] + 1 - (2 * int(r['r_first']) * int(r['len_first'])) * ((1. / L) ** wordlen)) / r['len_first']
             out.append(_result(int(r['d_first']), int(r['r_first']), int(r['len_first']), int(r['band_first']), word_p, L, wordlen))
-        elif r['tie'] > 1 and not _same(reads[pairs[q][0]], t_of(q)):
+        elif fallback and r['tie'] > 1 and not _same(reads[pairs[q][0]], t_of(q)):
             i, T = pairs[q][0], t_of(q)
             S = reads[i] if isinstance(reads[i], Sequence) else Sequence(alphabet, tuple(int(c) for c in reads[i]))
             T = T if isinstance(T, Sequence) else Sequence(alphabet, tuple(int(c) for c in T))
@@ -201,7 +202,7 @@ def overlap_bands(reads, pairs, wordlen, alphabet, g_max, sensitivity, device=0,
 
 
 def raw_all_pairs(reads, wordlen, alphabet_len, g_max, sensitivity, device=0, max_pairs=None, rank=0, world=1, strands='+',
-                  complement=None, with_strand=None):
+                  complement=None, with_strand=None, max_kmer_occ=None, stats=None):
     """All pairs ``a < b`` of ``reads`` that share at least one seed, through ONE k-mer index over all reads:
     returns ``(pairs (n, 2) int32, records BAND_DTYPE, device ms)``.  With ``world > 1`` only the pairs whose smaller
     read index is ``rank`` modulo ``world`` (one process per GPU, no data-path collective).
@@ -209,8 +210,15 @@ def raw_all_pairs(reads, wordlen, alphabet_len, g_max, sensitivity, device=0, ma
     ``strands``: ``'+'`` (read a against read b, the default), ``'-'`` (read a against the reverse complement of read b
     under the table ``complement``) or ``'both'``.  With ``with_strand`` (default: whenever ``strands`` is not ``'+'``) the
     call goes through ``pw_overlap_all_pairs_stranded`` and returns ``(pairs, strand (n,) uint8: 0 '+' / 1 '-', records,
-    device ms)``, in ascending ``(a, b, strand)`` order."""
+    device ms)``, in ascending ``(a, b, strand)`` order.
+
+    ``max_kmer_occ``: None or 0 (today's calls, unchanged), or the occurrence cap of ``pw_overlap_all_pairs_capped``: a k-mer
+    that occurs more than ``max_kmer_occ`` times in the whole read set (both strands counted unless ``strands == '+'``) gives
+    no seeds.  ``stats`` (a dict) then receives the fields of ``pw_overlap_cap_stats``: ``entries``, ``masked_entries``,
+    ``distinct_masked``, ``seeds_kept``, ``seeds_dropped``."""
     assert 0 < g_max < 1 and 0 < sensitivity < 1
+    if max_kmer_occ is not None and not 0 <= int(max_kmer_occ) < 2 ** 32:
+        raise ValueError('max_kmer_occ is None or 0 (no cap) or a count below 2^32, not %r' % (max_kmer_occ,))
     if strands not in _STRAND_SEL:
         raise ValueError("strands is '+', '-' or 'both', not %r" % (strands,))
     if with_strand is None:
@@ -229,6 +237,20 @@ def raw_all_pairs(reads, wordlen, alphabet_len, g_max, sensitivity, device=0, ma
     rlen = np.ascontiguousarray(np.diff(offs).astype(np.int32))
     arena_c = np.ascontiguousarray(arena)
     coeffs = _band_coeffs(g_max, sensitivity, alphabet_len, wordlen)
+    if max_kmer_occ:
+        ps = np.zeros(max(cap, 1), np.uint8)
+        cs = W.pw_overlap_cap_stats()
+        rc = lib.pw_overlap_all_pairs_capped(device, arena_c.ctypes.data, arena_c.size, roff.ctypes.data, rlen.ctypes.data, R,
+                                             alphabet_len, wordlen, *coeffs, None if comp is None else comp.ctypes.data,
+                                             _STRAND_SEL[strands], int(rank), int(world), cap, pa.ctypes.data, pb.ctypes.data,
+                                             ps.ctypes.data, out.ctypes.data, C.byref(n_out), int(max_kmer_occ), C.byref(cs))
+        if stats is not None:
+            stats.update((f, int(getattr(cs, f))) for f, _ in cs._fields_)
+        if rc != 0:
+            raise RuntimeError('pw_overlap_all_pairs_capped failed: ' + (lib.pw_overlap_last_error() or b'').decode())
+        n = n_out.value
+        pairs = np.stack([pa[:n], pb[:n]], axis=1)
+        return (pairs, ps[:n], out[:n], lib.pw_overlap_last_ms()) if with_strand else (pairs, out[:n], lib.pw_overlap_last_ms())
     if with_strand:
         ps = np.zeros(max(cap, 1), np.uint8)
         rc = lib.pw_overlap_all_pairs_stranded(device, arena_c.ctypes.data, arena_c.size, roff.ctypes.data, rlen.ctypes.data, R,
@@ -249,27 +271,37 @@ def raw_all_pairs(reads, wordlen, alphabet_len, g_max, sensitivity, device=0, ma
 
 
 def overlap_all_pairs(reads, wordlen, alphabet, g_max, sensitivity, device=0, max_pairs=None, stats=None, strands='+',
-                      complement=None):
+                      complement=None, max_kmer_occ=None):
     """The reference's all-pairs loop (``experiments/blot_overlaps.py:262-272``) in one device pass: returns a dict
     ``{(a, b): highest_scoring_overlap_band()}`` for the pairs ``a < b`` that share a seed; for every other pair the
     reference's answer is None.  With ``strands='-'`` or ``'both'`` the keys are ``(a, b, '+' | '-')`` and a minus entry
     is the reference's answer for ``reads[a]`` against the reverse complement of ``reads[b]`` (``complement``: a table or
-    the ``mappings`` of ``Alphabet.transform``)."""
+    the ``mappings`` of ``Alphabet.transform``).
+
+    ``max_kmer_occ`` (None or 0: no cap): k-mers that occur more often in the whole read set give no seeds
+    (:func:`raw_all_pairs`), and ``stats`` also receives the cap's five counters.  With a cap no pair goes to the
+    single-pair fallback -- that path knows no cap, and the reference defines no row order for a filtered seeds table:
+    where ``tie > 1`` the record's own rule decides (largest ``w``, then smallest ``d``) and ``fallback_pairs`` is 0."""
     assert isinstance(alphabet, Alphabet)
+    cap_stats = {}
+    cap_kw = dict(max_kmer_occ=max_kmer_occ, stats=cap_stats)
     if strands == '+':
-        pairs, recs, ms = raw_all_pairs(reads, wordlen, len(alphabet), g_max, sensitivity, device, max_pairs)
+        pairs, recs, ms = raw_all_pairs(reads, wordlen, len(alphabet), g_max, sensitivity, device, max_pairs, **cap_kw)
         plist = [(int(a), int(b)) for a, b in pairs.tolist()]
-        res, n_fallback = _records_to_results(reads, plist, recs, wordlen, alphabet, g_max, sensitivity, device)
+        res, n_fallback = _records_to_results(reads, plist, recs, wordlen, alphabet, g_max, sensitivity, device,
+                                              fallback=not max_kmer_occ)
         keys = plist
     else:
         comp = _complement(complement, len(alphabet), alphabet)
         pairs, flags, recs, ms = raw_all_pairs(reads, wordlen, len(alphabet), g_max, sensitivity, device, max_pairs, strands=strands,
-                                               complement=comp)
+                                               complement=comp, **cap_kw)
         plist = [(int(a), int(b)) for a, b in pairs.tolist()]
-        res, n_fallback = _records_to_results(reads, plist, recs, wordlen, alphabet, g_max, sensitivity, device, flags, comp)
+        res, n_fallback = _records_to_results(reads, plist, recs, wordlen, alphabet, g_max, sensitivity, device, flags, comp,
+                                              fallback=not max_kmer_occ)
         keys = [(a, b, '-' if f else '+') for (a, b), f in zip(plist, flags.tolist())]
     if stats is not None:
         stats.update(device_ms=ms, fallback_pairs=n_fallback, pairs=len(plist))
+        stats.update(cap_stats)
     return dict(zip(keys, res))
 
 
@@ -414,18 +446,20 @@ def raw_bands_sharded(reads, pairs, wordlen, alphabet_len, g_max, sensitivity, r
 
 
 def raw_all_pairs_sharded(reads, wordlen, alphabet_len, g_max, sensitivity, rank, world, device=None, max_pairs=None, strands='+',
-                          complement=None):
+                          complement=None, max_kmer_occ=None, stats=None):
     """Config 4 across GPUs: every rank indexes all reads (cheap) and joins / scores the pairs whose smaller read
     index is ``rank`` modulo ``world``; pair lists and 64-byte records are gathered to rank 0 (ragged byte gather over
     ``torch.distributed``) and merged in ascending (a, b) order.  Returns ``(pairs, records)`` on rank 0, None elsewhere.
-    With ``strands`` other than ``'+'``: ``(pairs, strand, records)`` in ascending (a, b, strand) order."""
+    With ``strands`` other than ``'+'``: ``(pairs, strand, records)`` in ascending (a, b, strand) order.
+    ``max_kmer_occ`` / ``stats``: the occurrence cap of :func:`raw_all_pairs`, counted over the whole read set on every rank, so
+    the merged output equals the unsharded capped call's; ``stats`` receives THIS rank's counters."""
     import torch
     from .distributed import gather_bytes
     if strands != '+':
         return _raw_all_pairs_sharded_stranded(reads, wordlen, alphabet_len, g_max, sensitivity, rank, world, device, max_pairs,
-                                               strands, complement)
+                                               strands, complement, max_kmer_occ, stats)
     pairs, recs, _ = raw_all_pairs(reads, wordlen, alphabet_len, g_max, sensitivity, device=rank if device is None else device,
-                                   max_pairs=max_pairs, rank=rank, world=world)
+                                   max_pairs=max_pairs, rank=rank, world=world, max_kmer_occ=max_kmer_occ, stats=stats)
     blob = np.concatenate([np.ascontiguousarray(pairs, np.int32).view(np.uint8).reshape(-1), recs.view(np.uint8).reshape(-1)])
     got = gather_bytes(torch.from_numpy(blob.copy()), rank, world)
     if rank != 0:
@@ -442,12 +476,13 @@ def raw_all_pairs_sharded(reads, wordlen, alphabet_len, g_max, sensitivity, rank
 
 
 def _raw_all_pairs_sharded_stranded(reads, wordlen, alphabet_len, g_max, sensitivity, rank, world, device, max_pairs, strands,
-                                    complement):
+                                    complement, max_kmer_occ=None, stats=None):
     """:func:`raw_all_pairs_sharded` with the strand column: the third int32 of every gathered pair."""
     import torch
     from .distributed import gather_bytes
     pairs, flags, recs, _ = raw_all_pairs(reads, wordlen, alphabet_len, g_max, sensitivity, device=rank if device is None else device,
-                                          max_pairs=max_pairs, rank=rank, world=world, strands=strands, complement=complement)
+                                          max_pairs=max_pairs, rank=rank, world=world, strands=strands, complement=complement,
+                                          max_kmer_occ=max_kmer_occ, stats=stats)
     triples = np.ascontiguousarray(np.concatenate([pairs, flags.astype(np.int32)[:, None]], axis=1), np.int32)
     blob = np.concatenate([triples.view(np.uint8).reshape(-1), recs.view(np.uint8).reshape(-1)])
     got = gather_bytes(torch.from_numpy(blob.copy()), rank, world)

@@ -97,6 +97,29 @@ int pw_overlap_all_pairs_stranded(int device, const uint8_t* arena, uint64_t are
                                   int strands, int shard_rank, int shard_world, int64_t max_pairs, int32_t* pair_a,
                                   int32_t* pair_b, uint8_t* pair_strand, pw_overlap_band* out, int64_t* n_out);
 
+/* ---- the occurrence cap -----------------------------------------------------------------------------------------
+ * pw_overlap_all_pairs_stranded with repetitive k-mers left out of the join.  occ(x) of a k-mer x is counted over the
+ * WHOLE read set, whatever the shard (every rank builds the whole index): the forward entries with key x when strands ==
+ * PW_STRAND_PLUS, otherwise those plus the reverse-index entries with key x -- exactly count(x) of a pw_kmers_build
+ * (pw_kmers.h) with the same strands (PW_STRAND_MINUS counts as PW_STRAND_BOTH does).  A seed whose k-mer has occ(x) >
+ * max_occ does not exist: it is not in n_seeds, in no histogram, band_* or *_first field, and a pair left without seeds
+ * is not listed; occ(x) == max_occ is kept.  The masked entries never reach the seed expansion, so the refusals (2^32
+ * seeds, max_pairs) are judged on what survives the cap, and the union of the ranks' outputs equals the unsharded output.
+ * max_occ == 0: no cap -- the call is pw_overlap_all_pairs_stranded bit for bit, and stats is zeroed.
+ * stats (may be NULL; zeroed first, filled once the join has run, also where a refusal follows it):
+ *   entries          rows of the index: the k-mers of all reads, twice that with the reverse strand
+ *   masked_entries   rows whose k-mer is masked           } over the whole read set,
+ *   distinct_masked  distinct masked k-mers               } the same on every rank
+ *   seeds_kept       the seeds this rank expanded (the sum of n_seeds over its listed pairs)
+ *   seeds_dropped    the seeds this rank's masked entries would have produced: a 64-bit sum, never expanded */
+typedef struct { uint64_t entries, masked_entries, distinct_masked, seeds_kept, seeds_dropped; } pw_overlap_cap_stats;
+int pw_overlap_all_pairs_capped(int device, const uint8_t* arena, uint64_t arena_bytes, const uint64_t* read_off,
+                                const int32_t* read_len, int64_t n_reads, int alphabet_len, int wordlen,
+                                double len_coeff, double radius_coeff, double word_p_null, const uint8_t* complement,
+                                int strands, int shard_rank, int shard_world, int64_t max_pairs, int32_t* pair_a,
+                                int32_t* pair_b, uint8_t* pair_strand, pw_overlap_band* out, int64_t* n_out,
+                                uint32_t max_occ, pw_overlap_cap_stats* stats);
+
 /* Reads for the alignment stage: a device arena of total_bytes (+ the slack the kernels read) whose first `bytes` are the
  * host arena, uploaded once; behind them the device writes the reverse complement of n_frames reads: frame f =
  * rc(arena[src_off[f], src_off[f] + len[f])) at dst_off[f].  The dst frames ascend without overlap inside
