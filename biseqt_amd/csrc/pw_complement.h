@@ -1,5 +1,5 @@
-// pw_complement.h -- the complement table of a stranded call, shared by overlap band selection (pw_overlap.hip) and the
-// query-batched seed index (pw_qseeds.hip): the host check, the copy to the device and the kernels' LDS copy.  The table
+// pw_complement.h -- the complement table of a stranded call, shared by overlap band selection (pw_overlap.hip), the k-mer
+// table (pw_kmers.hip) and the query-batched seed index (pw_qseeds.hip): the host check, the copy to the device and the kernels' LDS copy.  The table
 // is alphabet_len <= 36 bytes, complement[c] for every letter c: a permutation of the alphabet that is its own inverse.
 // Each C API keeps its own error channel: `sink` takes the message (as PW_HIP_CHECK's).
 #pragma once
@@ -26,12 +26,17 @@ int check_complement(Sink&& sink, const uint8_t* comp, int L) {
   return 0;
 }
 
-// the complement table on the device (36 bytes, zero padded)
+// the complement table on the device (36 bytes, zero padded): copied before the call returns, or, given a stream (null
+// included), by hipMemcpyAsync on it (upload, pw_hip_host.h)
 template <typename Sink>
-int upload_complement(Sink&& sink, const uint8_t* comp, int L, DeviceBuffer& d_comp) {
+int upload_complement(Sink&& sink, const uint8_t* comp, int L, DeviceArray<uint8_t>& d_comp) {
   uint8_t padded[36] = {0};
   memcpy(padded, comp, (size_t)L);
-  PW_HIP_CHECK(sink, d_comp.ensure(sizeof padded));
-  PW_HIP_CHECK(sink, hipMemcpy(d_comp.p, padded, sizeof padded, hipMemcpyHostToDevice));
-  return 0;
+  return upload(sink, d_comp, padded, sizeof padded);
+}
+template <typename Sink>
+int upload_complement(Sink&& sink, const uint8_t* comp, int L, DeviceArray<uint8_t>& d_comp, hipStream_t st) {
+  uint8_t padded[36] = {0};
+  memcpy(padded, comp, (size_t)L);
+  return upload(sink, d_comp, padded, sizeof padded, st);
 }

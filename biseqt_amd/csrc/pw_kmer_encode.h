@@ -1,7 +1,8 @@
 // pw_kmer_encode.h -- what the two translation units that index a whole READ SET share: overlap band selection (pw_overlap.hip,
 // K9) and the k-mer table (pw_kmers.hip).  Device code: the k-mer of a position in either strand (kmer_fwd, kmer_rc) and the
 // read encoders K9a / K9a'.  Host code: the argument checks of the all-pairs entry points (check_args) and the two rocPRIM
-// helpers every stage of both goes through (sort_pairs, scan_u64).  Everything lives in an anonymous namespace: each
+// helpers every stage of both goes through (sort_pairs, scan_u64), over typed device arrays (DeviceArray<T>, pw_hip_host.h: the
+// element types are rocPRIM's template arguments).  Everything lives in an anonymous namespace: each
 // translation unit gets its own copy of the kernels and reports through its own error channel (`sink`, as PW_HIP_CHECK's).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -58,17 +59,25 @@ __global__ __launch_bounds__(256) void k_enc_reads_rc(const uint8_t* __restrict_
 
 // n (key, value) pairs stably sorted by the low `bits` bits of the key
 template <typename K, typename V>
-hipError_t sort_pairs(DeviceBuffer& tmp, const DeviceBuffer& kin, DeviceBuffer& kout, const DeviceBuffer& vin, DeviceBuffer& vout,
+hipError_t sort_pairs(DeviceBuffer& tmp, const DeviceArray<K>& kin, DeviceArray<K>& kout, const DeviceArray<V>& vin, DeviceArray<V>& vout,
                       size_t n, int bits, hipStream_t stream = nullptr) {
   return rocprim_run(tmp, [&](void* t, size_t& b) {
-    return rocprim::radix_sort_pairs(t, b, (const K*)kin.p, (K*)kout.p, (const V*)vin.p, (V*)vout.p, n, 0u, (unsigned)bits, stream);
+    return rocprim::radix_sort_pairs(t, b, kin.cp(), kout.p, vin.cp(), vout.p, n, 0u, (unsigned)bits, stream);
   });
 }
-// out[i] = in[0] + ... + in[i - 1]
-hipError_t scan_u64(DeviceBuffer& tmp, const DeviceBuffer& in, DeviceBuffer& out, size_t n, hipStream_t stream = nullptr) {
+// out[i] = in[0] + ... + in[i - 1].  Ordinary functions, not a template on the input's type: rocPRIM's scan is instantiated
+// here, ahead of the including unit's own, and the unit's kernels keep their order and fingerprints.  (unsigned long long: as rocPRIM wrote the counts)
+hipError_t scan_u64(DeviceBuffer& tmp, const uint64_t* in, DeviceArray<uint64_t>& out, size_t n, hipStream_t stream) {
   return rocprim_run(tmp, [&](void* t, size_t& b) {
-    return rocprim::exclusive_scan(t, b, (const uint64_t*)in.p, (uint64_t*)out.p, (uint64_t)0, n, rocprim::plus<uint64_t>(), stream);
+    return rocprim::exclusive_scan(t, b, in, out.p, (uint64_t)0, n, rocprim::plus<uint64_t>(), stream);
   });
+}
+hipError_t scan_u64(DeviceBuffer& tmp, const DeviceArray<uint64_t>& in, DeviceArray<uint64_t>& out, size_t n, hipStream_t stream = nullptr) {
+  return scan_u64(tmp, in.cp(), out, n, stream);
+}
+hipError_t scan_u64(DeviceBuffer& tmp, const DeviceArray<unsigned long long>& in, DeviceArray<uint64_t>& out, size_t n,
+                    hipStream_t stream = nullptr) {
+  return scan_u64(tmp, in.as<const uint64_t>(), out, n, stream);
 }
 
 // The argument checks of the entry points that take a read set or a pair list, in this order: word range, counts and

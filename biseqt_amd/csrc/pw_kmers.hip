@@ -124,23 +124,20 @@ struct pw_kmer_index {
   uint64_t K = 0, N = 0;                               // forward rows, rows
   int64_t D = -1;                                      // distinct keys; -1: still on the device (n_runs)
   hipStream_t stream = nullptr;
-  DeviceBuffer arena, comp, roff, rlen, rstart;        // the reads
-  DeviceBuffer kin, vin, keys, hits;                   // staging (after the sort: run heads, ranks), the sorted table
-  DeviceBuffer ukeys, ustart, n_runs, tmp;             // the runs; rocPRIM's scratch
+  DeviceArray<uint8_t> arena, comp; DeviceArray<uint64_t> roff, rstart; DeviceArray<int32_t> rlen;     // the reads
+  DeviceArray<uint64_t> kin, vin, keys, hits;          // staging (after the sort: run heads, ranks), the sorted table
+  DeviceArray<uint64_t> ukeys, ustart; DeviceArray<unsigned long long> n_runs; DeviceBuffer tmp;        // the runs; rocPRIM's scratch
   DeviceEvent bev0, bev1, qev0, qev1;                  // the build, a query
 };
 
 namespace {
-
-const dim3 kBlk(256);
-dim3 grid_for(uint64_t n) { return dim3((unsigned)((n + 255) / 256)); }
 
 // waits for the build where its number of runs is still on the device; its device time becomes pw_kmers_last_ms()
 int finish_build(pw_kmer_index* x) {
   CHECK(hipSetDevice(x->device));
   if (x->D >= 0) return 0;
   unsigned long long d = 0;
-  CHECK(hipMemcpyAsync(&d, x->n_runs.p, 8, hipMemcpyDeviceToHost, x->stream));
+  CHECK(hipMemcpyAsync(&d, x->n_runs.p, sizeof d, hipMemcpyDeviceToHost, x->stream));
   CHECK(hipStreamSynchronize(x->stream));
   CHECK(hipGetLastError());
   float ms = 0.f;
@@ -163,22 +160,17 @@ int query_end(pw_kmer_index* x) {
   g_ms = (double)ms;
   return 0;
 }
-int upload_async(DeviceBuffer& buf, const void* host, size_t bytes, hipStream_t st) {
-  CHECK(buf.ensure(bytes));
-  if (bytes) CHECK(hipMemcpyAsync(buf.p, host, bytes, hipMemcpyHostToDevice, st));
-  return 0;
-}
 // counts / first rows of n host keys (starts may be null)
 int lookup(pw_kmer_index* x, const uint64_t* keys, int64_t n, uint32_t* counts_out, uint64_t* starts_out) {
-  DeviceBuffer dq, dc, ds;
-  CHECK(dc.ensure(4 * (size_t)n));
-  if (starts_out) CHECK(ds.ensure(8 * (size_t)n));
-  if (upload_async(dq, keys, 8 * (size_t)n, x->stream) != 0 || query_begin(x) != 0) return -1;
-  hipLaunchKernelGGL(k_kmers_lookup, grid_for((uint64_t)n), kBlk, 0, x->stream, (const uint64_t*)x->ukeys.p, (const uint64_t*)x->ustart.p,
-                     (const unsigned long long*)x->n_runs.p, (const uint64_t*)dq.p, n, (uint32_t*)dc.p, (uint64_t*)ds.p);
+  DeviceArray<uint64_t> dq, ds; DeviceArray<uint32_t> dc;
+  CHECK(dc.ensure((size_t)n));
+  if (starts_out) CHECK(ds.ensure((size_t)n));
+  if (upload(set_err, dq, keys, (size_t)n, x->stream) != 0 || query_begin(x) != 0) return -1;
+  hipLaunchKernelGGL(k_kmers_lookup, rows_grid((uint64_t)n), kBlock256, 0, x->stream, x->ukeys.p, x->ustart.p, x->n_runs.p, dq.p, n, dc.p,
+                     ds.p);
   if (query_end(x) != 0) return -1;
-  CHECK(hipMemcpy(counts_out, dc.p, 4 * (size_t)n, hipMemcpyDeviceToHost));
-  if (starts_out) CHECK(hipMemcpy(starts_out, ds.p, 8 * (size_t)n, hipMemcpyDeviceToHost));
+  CHECK(hipMemcpy(counts_out, dc.p, dc.bytes((size_t)n), hipMemcpyDeviceToHost));
+  if (starts_out) CHECK(hipMemcpy(starts_out, ds.p, ds.bytes((size_t)n), hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -210,32 +202,28 @@ int build(pw_kmer_index* x, const uint8_t* arena, uint64_t arena_bytes, const ui
   const uint64_t N = both ? 2 * K : K;
   x->stream = st; x->strands = strands; x->R = n_reads; x->K = K; x->N = N; x->D = N ? -1 : 0;
   if (N == 0) { x->built = true; return 0; }
-  CHECK(x->kin.ensure(8 * (size_t)N)); CHECK(x->vin.ensure(8 * (size_t)N)); CHECK(x->keys.ensure(8 * (size_t)N)); CHECK(x->hits.ensure(8 * (size_t)N));
-  CHECK(x->ukeys.ensure(8 * (size_t)N)); CHECK(x->ustart.ensure(8 * ((size_t)N + 1))); CHECK(x->n_runs.ensure(16));
-  if (upload_async(x->arena, arena, (size_t)arena_bytes, st) != 0 || upload_async(x->roff, read_off, 8 * (size_t)n_reads, st) != 0 ||
-      upload_async(x->rlen, read_len, 4 * (size_t)n_reads, st) != 0 || upload_async(x->rstart, rstart.data(), 8 * ((size_t)n_reads + 1), st) != 0)
+  CHECK(x->kin.ensure((size_t)N)); CHECK(x->vin.ensure((size_t)N)); CHECK(x->keys.ensure((size_t)N)); CHECK(x->hits.ensure((size_t)N));
+  CHECK(x->ukeys.ensure((size_t)N)); CHECK(x->ustart.ensure((size_t)N + 1)); CHECK(x->n_runs.ensure(1));
+  if (upload(set_err, x->arena, arena, (size_t)arena_bytes, st) != 0 || upload(set_err, x->roff, read_off, (size_t)n_reads, st) != 0 ||
+      upload(set_err, x->rlen, read_len, (size_t)n_reads, st) != 0 ||
+      upload(set_err, x->rstart, rstart.data(), (size_t)n_reads + 1, st) != 0)
     return -1;
-  if (both) {
-    uint8_t padded[36] = {0};
-    memcpy(padded, complement, (size_t)x->L);
-    if (upload_async(x->comp, padded, sizeof padded, st) != 0) return -1;
-  }
-  CHECK(hipStreamSynchronize(st));                     // the host arrays (rstart, padded among them) are the caller's again
+  if (both && upload_complement(set_err, complement, x->L, x->comp, st) != 0) return -1;
+  CHECK(hipStreamSynchronize(st));                     // the host arrays (rstart among them) are the caller's again
   CHECK(hipEventRecord(x->bev0.e, st));
-  hipLaunchKernelGGL(k_enc_reads, grid_for(K), kBlk, 0, st, (const uint8_t*)x->arena.p, (const uint64_t*)x->roff.p, (const uint64_t*)x->rstart.p,
-                     n_reads, (int64_t)K, x->k, x->L, (uint64_t*)x->kin.p, (uint64_t*)x->vin.p);
+  hipLaunchKernelGGL(k_enc_reads, rows_grid(K), kBlock256, 0, st, x->arena.p, x->roff.p, x->rstart.p, n_reads, (int64_t)K, x->k, x->L,
+                     x->kin.p, x->vin.p);
   if (both) {
-    hipLaunchKernelGGL(k_enc_reads_rc, grid_for(K), kBlk, 0, st, (const uint8_t*)x->arena.p, (const uint64_t*)x->roff.p, (const int32_t*)x->rlen.p,
-                       (const uint64_t*)x->rstart.p, n_reads, (int64_t)K, x->k, x->L, (const uint8_t*)x->comp.p, (uint64_t*)x->kin.p + K,
-                       (uint64_t*)x->vin.p + K);
-    hipLaunchKernelGGL(k_kmers_tag, grid_for(K), kBlk, 0, st, (uint64_t*)x->vin.p + K, (int64_t)K);
+    hipLaunchKernelGGL(k_enc_reads_rc, rows_grid(K), kBlock256, 0, st, x->arena.p, x->roff.p, x->rlen.p, x->rstart.p, n_reads, (int64_t)K,
+                       x->k, x->L, x->comp.p, x->kin.p + K, x->vin.p + K);
+    hipLaunchKernelGGL(k_kmers_tag, rows_grid(K), kBlock256, 0, st, x->vin.p + K, (int64_t)K);
   }
-  CHECK((sort_pairs<uint64_t, uint64_t>(x->tmp, x->kin, x->keys, x->vin, x->hits, (size_t)N, kbits, st)));
+  CHECK(sort_pairs(x->tmp, x->kin, x->keys, x->vin, x->hits, (size_t)N, kbits, st));
   // the staging buffers are free again: run heads in kin, their ranks in vin
-  hipLaunchKernelGGL(k_kmers_heads, grid_for(N), kBlk, 0, st, (const uint64_t*)x->keys.p, (int64_t)N, (uint64_t*)x->kin.p);
+  hipLaunchKernelGGL(k_kmers_heads, rows_grid(N), kBlock256, 0, st, x->keys.p, (int64_t)N, x->kin.p);
   CHECK(scan_u64(x->tmp, x->kin, x->vin, (size_t)N, st));
-  hipLaunchKernelGGL(k_kmers_runs, grid_for(N), kBlk, 0, st, (const uint64_t*)x->keys.p, (const uint64_t*)x->kin.p, (const uint64_t*)x->vin.p,
-                     (int64_t)N, (uint64_t*)x->ukeys.p, (uint64_t*)x->ustart.p, (unsigned long long*)x->n_runs.p);
+  hipLaunchKernelGGL(k_kmers_runs, rows_grid(N), kBlock256, 0, st, x->keys.p, x->kin.p, x->vin.p, (int64_t)N, x->ukeys.p, x->ustart.p,
+                     x->n_runs.p);
   CHECK(hipEventRecord(x->bev1.e, st));
   CHECK(hipGetLastError());
   x->built = true;
@@ -279,8 +267,8 @@ int pw_kmers_distinct(pw_kmer_index* x, uint64_t* keys_out, uint32_t* counts_out
   if (x->D == 0) return 0;
   if (!keys_out || !counts_out) { set_err("bad arguments"); return -1; }
   std::vector<uint64_t> start((size_t)x->D + 1);
-  CHECK(hipMemcpy(keys_out, x->ukeys.p, 8 * (size_t)x->D, hipMemcpyDeviceToHost));
-  CHECK(hipMemcpy(start.data(), x->ustart.p, 8 * ((size_t)x->D + 1), hipMemcpyDeviceToHost));
+  CHECK(hipMemcpy(keys_out, x->ukeys.p, x->ukeys.bytes((size_t)x->D), hipMemcpyDeviceToHost));
+  CHECK(hipMemcpy(start.data(), x->ustart.p, x->ustart.bytes((size_t)x->D + 1), hipMemcpyDeviceToHost));
   for (int64_t u = 0; u < x->D; u++) counts_out[u] = (uint32_t)std::min<uint64_t>(start[(size_t)u + 1] - start[(size_t)u], 0xffffffffull);
   return 0;
 }
@@ -307,7 +295,7 @@ int pw_kmers_hits(pw_kmer_index* x, uint64_t key, uint64_t* hits_out, int64_t ca
     set_err(msg);
     return -1;
   }
-  if (count) CHECK(hipMemcpy(hits_out, (const uint64_t*)x->hits.p + start, 8 * (size_t)count, hipMemcpyDeviceToHost));
+  if (count) CHECK(hipMemcpy(hits_out, x->hits.p + start, x->hits.bytes(count), hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -315,17 +303,16 @@ int pw_kmers_spectrum(pw_kmer_index* x, int max_mult, uint64_t* hist_out) {
   if (ready(x, "pw_kmers_spectrum") != 0) return -1;
   if (max_mult < 1 || max_mult > 65536) { set_err("max_mult must be 1..65536"); return -1; }
   if (!hist_out) { set_err("bad arguments"); return -1; }
-  const size_t bytes = 8 * ((size_t)max_mult + 1);
+  DeviceArray<unsigned long long> dh;
+  const size_t bins = (size_t)max_mult + 1, bytes = dh.bytes(bins);
   memset(hist_out, 0, bytes);
   if (x->D == 0) return 0;
-  DeviceBuffer dh;
-  CHECK(dh.ensure(bytes));
+  CHECK(dh.ensure(bins));
   CHECK(hipMemsetAsync(dh.p, 0, bytes, x->stream));
   if (query_begin(x) != 0) return -1;
   // a fixed grid: every workgroup flushes its LDS histogram once, whatever the table's size
   const unsigned blocks = (unsigned)std::min<uint64_t>(((uint64_t)x->D + 255) / 256, 2048);
-  hipLaunchKernelGGL(k_kmers_spectrum, dim3(blocks), kBlk, 0, x->stream, (const uint64_t*)x->ustart.p, (const unsigned long long*)x->n_runs.p,
-                     (uint32_t)max_mult, (unsigned long long*)dh.p);
+  hipLaunchKernelGGL(k_kmers_spectrum, dim3(blocks), kBlock256, 0, x->stream, x->ustart.p, x->n_runs.p, (uint32_t)max_mult, dh.p);
   if (query_end(x) != 0) return -1;
   CHECK(hipMemcpy(hist_out, dh.p, bytes, hipMemcpyDeviceToHost));
   return 0;
@@ -335,13 +322,13 @@ int pw_kmers_occurrences(pw_kmer_index* x, uint32_t* occ_out) {
   if (ready(x, "pw_kmers_occurrences") != 0) return -1;
   if (x->K == 0) return 0;
   if (!occ_out) { set_err("bad arguments"); return -1; }
-  DeviceBuffer docc;
-  CHECK(docc.ensure(4 * (size_t)x->K));
+  DeviceArray<uint32_t> docc;
+  CHECK(docc.ensure((size_t)x->K));
   if (query_begin(x) != 0) return -1;
-  hipLaunchKernelGGL(k_kmers_occ, grid_for(x->N), kBlk, 0, x->stream, (const uint64_t*)x->hits.p, (int64_t)x->N, (const uint64_t*)x->ustart.p,
-                     (const unsigned long long*)x->n_runs.p, (const uint64_t*)x->rstart.p, (uint32_t*)docc.p);
+  hipLaunchKernelGGL(k_kmers_occ, rows_grid(x->N), kBlock256, 0, x->stream, x->hits.p, (int64_t)x->N, x->ustart.p, x->n_runs.p, x->rstart.p,
+                     docc.p);
   if (query_end(x) != 0) return -1;
-  CHECK(hipMemcpy(occ_out, docc.p, 4 * (size_t)x->K, hipMemcpyDeviceToHost));
+  CHECK(hipMemcpy(occ_out, docc.p, docc.bytes((size_t)x->K), hipMemcpyDeviceToHost));
   return 0;
 }
 

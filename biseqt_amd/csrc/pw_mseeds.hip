@@ -222,9 +222,11 @@ struct pw_mseed_index {
   WordSpace ws;
   int64_t len[kMaxSeqs] = {}, soff[kMaxSeqs + 1] = {}, nrows = -1;
   SeqOffsets so = {};
-  DeviceBuffer dseq, keys_in, pos_in, keys, pos, lo, rl, cnt, off, rows, tmp, scalar;
+  DeviceArray<uint8_t> dseq; DeviceBuffer keys_in, keys, tmp;      // (the keys: uint32_t or uint64_t by ws.key32; rocPRIM's scratch)
+  DeviceArray<uint32_t> pos_in, pos, lo, rl; DeviceArray<uint64_t> cnt, off;
+  DeviceArray<int32_t> rows; DeviceArray<unsigned long long> scalar;   // rows: n indices each
   SeedGraph g;                          // neighbourhood graph (K9e); g.npts: the rows
-  DeviceBuffer g_srows, g_dstart;
+  DeviceArray<int32_t> g_srows; DeviceArray<uint32_t> g_dstart;
   DeviceEvent ev0, ev1;
   float ms_build = 0.f, ms_graph = 0.f, ms_cc = 0.f, ms_count = 0.f;
 };
@@ -236,15 +238,14 @@ static int build_join(pw_mseed_index* x, hipStream_t st) {
   int64_t nk_max = 1;
   for (int s = 0; s < x->n; s++) nk_max = std::max(nk_max, x->so.koff[s + 1] - x->so.koff[s]);
   // every sequence sorts into its own piece of keys / pos through one pair of staging buffers: all sized here
-  CHECK(x->keys.ensure((size_t)std::max<int64_t>(nk_all, 1) * sizeof(K))); CHECK(x->pos.ensure((size_t)std::max<int64_t>(nk_all, 1) * 4));
-  CHECK(x->keys_in.ensure((size_t)nk_max * sizeof(K))); CHECK(x->pos_in.ensure((size_t)nk_max * 4));
+  CHECK(x->keys.ensure((size_t)std::max<int64_t>(nk_all, 1) * sizeof(K))); CHECK(x->pos.ensure((size_t)std::max<int64_t>(nk_all, 1)));
+  CHECK(x->keys_in.ensure((size_t)nk_max * sizeof(K))); CHECK(x->pos_in.ensure((size_t)nk_max));
   const MaskSets none = {};
   for (int s = 0; s < x->n; s++)
-    if (encode_sort<K>(set_err, x->ws, none, (const uint8_t*)x->dseq.p + x->soff[s], x->len[s], x->so.koff[s + 1] - x->so.koff[s], x->keys_in,
-                       x->pos_in, x->tmp, x->keys, x->pos, x->so.koff[s], st) != 0)
+    if (encode_sort<K>(set_err, x->ws, none, x->dseq.p + x->soff[s], x->len[s], x->so.koff[s + 1] - x->so.koff[s], x->keys_in, x->pos_in,
+                       x->tmp, x->keys, x->pos, x->so.koff[s], st) != 0)
       return -1;
-  hipLaunchKernelGGL((k_mjoin<K>), dim3((unsigned)((nk0 + 255) / 256)), dim3(256), 0, st, (const K*)x->keys.p, x->so, x->n,
-                     (uint32_t*)x->lo.p, (uint32_t*)x->rl.p, (uint64_t*)x->cnt.p);
+  hipLaunchKernelGGL((k_mjoin<K>), rows_grid((uint64_t)nk0), kBlock256, 0, st, x->keys.as<const K>(), x->so, x->n, x->lo.p, x->rl.p, x->cnt.p);
   return 0;
 }
 
@@ -281,7 +282,7 @@ pw_mseed_index* pw_mseeds_create(int device, const uint8_t* const* seqs, const i
     set_err("device allocation failed"); delete x; return nullptr;
   }
   for (int s = 0; s < n_seqs; s++)
-    if (lens[s] && hipMemcpy((uint8_t*)x->dseq.p + x->soff[s], seqs[s], (size_t)lens[s], hipMemcpyHostToDevice) != hipSuccess) {
+    if (lens[s] && hipMemcpy(x->dseq.p + x->soff[s], seqs[s], (size_t)lens[s], hipMemcpyHostToDevice) != hipSuccess) {
       set_err("copy of the sequences to the device failed"); delete x; return nullptr;
     }
   return x;
@@ -296,30 +297,28 @@ int pw_mseeds_build(pw_mseed_index* x, int64_t max_rows, void* stream) {
   max_rows = std::min<int64_t>(max_rows, (1ll << 31) - 1);
   x->nrows = -1; x->g.edges = -1; x->g.npts = -1;
   CHECK(hipEventRecord(x->ev0.e, st));
-  CHECK(x->scalar.ensure(16));
+  CHECK(x->scalar.ensure(2));
   const int64_t nk0 = x->so.koff[1];
   bool empty = false;
   for (int s = 0; s < x->n; s++) empty |= x->so.koff[s + 1] == x->so.koff[s];
   unsigned long long total = 0;
   if (!empty) {
-    CHECK(x->lo.ensure((size_t)nk0 * x->n * 4)); CHECK(x->rl.ensure((size_t)nk0 * x->n * 4));
-    CHECK(x->cnt.ensure((size_t)nk0 * 8)); CHECK(x->off.ensure((size_t)nk0 * 8));
+    CHECK(x->lo.ensure((size_t)nk0 * x->n)); CHECK(x->rl.ensure((size_t)nk0 * x->n));
+    CHECK(x->cnt.ensure((size_t)nk0)); CHECK(x->off.ensure((size_t)nk0));
     if ((x->ws.key32 ? build_join<uint32_t>(x, st) : build_join<uint64_t>(x, st)) != 0) return -1;
     CHECK(rocprim_run(x->tmp, [&](void* t, size_t& b) {
-      return rocprim::exclusive_scan(t, b, (const uint64_t*)x->cnt.p, (uint64_t*)x->off.p, (uint64_t)0, (size_t)nk0, SatAdd(), st);
+      return rocprim::exclusive_scan(t, b, x->cnt.cp(), x->off.p, (uint64_t)0, (size_t)nk0, SatAdd(), st);
     }));
-    hipLaunchKernelGGL(k_total_sat, dim3(1), dim3(64), 0, st, (const uint64_t*)x->off.p, (const uint64_t*)x->cnt.p, nk0,
-                       (unsigned long long*)x->scalar.p);
-    CHECK(hipMemcpyAsync(&total, x->scalar.p, 8, hipMemcpyDeviceToHost, st));
+    hipLaunchKernelGGL(k_total_sat, dim3(1), dim3(64), 0, st, x->off.p, x->cnt.p, nk0, x->scalar.p);
+    CHECK(hipMemcpyAsync(&total, x->scalar.p, sizeof total, hipMemcpyDeviceToHost, st));
     CHECK(hipStreamSynchronize(st));
   }
   if (check_row_limit(set_err, total, max_rows) != 0) return -1;
-  CHECK(x->rows.ensure((size_t)std::max<unsigned long long>(total, 1) * 4 * x->n));
+  CHECK(x->rows.ensure((size_t)std::max<unsigned long long>(total, 1) * x->n));
   if (total > 0) {
-    const dim3 g((unsigned)((total + kExpRows - 1) / kExpRows)), b(256);
-#define PW_LAUNCH_EXPAND(N_)                                                                                        \
-  hipLaunchKernelGGL((k_mexpand<N_>), g, b, 0, st, (const uint64_t*)x->off.p, nk0, (int64_t)total, (const uint32_t*)x->pos.p, \
-                     x->so, (const uint32_t*)x->lo.p, (const uint32_t*)x->rl.p, (int32_t*)x->rows.p)
+    const dim3 g((unsigned)((total + kExpRows - 1) / kExpRows)), b = kBlock256;
+#define PW_LAUNCH_EXPAND(N_) \
+  hipLaunchKernelGGL((k_mexpand<N_>), g, b, 0, st, x->off.p, nk0, (int64_t)total, x->pos.p, x->so, x->lo.p, x->rl.p, x->rows.p)
     PW_MSEEDS_FOR_N(x->n, PW_LAUNCH_EXPAND)
 #undef PW_LAUNCH_EXPAND
   }
@@ -330,7 +329,7 @@ int pw_mseeds_build(pw_mseed_index* x, int64_t max_rows, void* stream) {
 
 int pw_mseeds_num_seqs(const pw_mseed_index* x) { return x ? x->n : -1; }
 int64_t pw_mseeds_num_rows(const pw_mseed_index* x) { return x ? x->nrows : -1; }
-const int32_t* pw_mseeds_rows_device(const pw_mseed_index* x) { return (x && x->nrows >= 0) ? (const int32_t*)x->rows.p : nullptr; }
+const int32_t* pw_mseeds_rows_device(const pw_mseed_index* x) { return (x && x->nrows >= 0) ? x->rows.p : nullptr; }
 double pw_mseeds_build_ms(const pw_mseed_index* x) { return x ? (double)x->ms_build : -1.0; }
 double pw_mseeds_graph_ms(const pw_mseed_index* x) { return x ? (double)x->ms_graph : -1.0; }
 double pw_mseeds_components_ms(const pw_mseed_index* x) { return x ? (double)x->ms_cc : -1.0; }
@@ -344,7 +343,7 @@ int pw_mseeds_rows(const pw_mseed_index* x, int32_t* rows, int64_t cap) {
   if (!x || x->nrows < 0) { set_err("pw_mseeds_rows before a successful pw_mseeds_build"); return -1; }
   if (cap < x->nrows) { set_err("pw_mseeds_rows: capacity too small"); return -1; }
   CHECK(hipSetDevice(x->device));
-  if (x->nrows) CHECK(hipMemcpy(rows, x->rows.p, (size_t)x->nrows * 4 * x->n, hipMemcpyDeviceToHost));
+  if (x->nrows) CHECK(hipMemcpy(rows, x->rows.p, x->rows.bytes((size_t)x->nrows * x->n), hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -357,23 +356,19 @@ int pw_mseeds_count_many(const pw_mseed_index* xc, int64_t n_boxes, const int32_
   if (n_boxes > (int64_t)kBoxChunk * 65535) { set_err("at most 64 * 65535 boxes per call"); return -1; }
   CHECK(hipSetDevice(x->device));
   const size_t nb = (size_t)n_boxes * x->n;
-  DeviceBuffer dlo, dhi, dhave, dcnt;
-  CHECK(dlo.ensure(nb * 4)); CHECK(dhi.ensure(nb * 4)); CHECK(dhave.ensure(nb)); CHECK(dcnt.ensure((size_t)n_boxes * 8));
-  CHECK(hipMemcpy(dlo.p, lo, nb * 4, hipMemcpyHostToDevice));
-  CHECK(hipMemcpy(dhi.p, hi, nb * 4, hipMemcpyHostToDevice));
-  CHECK(hipMemcpy(dhave.p, have, nb, hipMemcpyHostToDevice));
-  CHECK(hipMemsetAsync(dcnt.p, 0, (size_t)n_boxes * 8, nullptr));
+  DeviceArray<int32_t> dlo, dhi; DeviceArray<uint8_t> dhave; DeviceArray<unsigned long long> dcnt;
+  CHECK(dlo.ensure(nb)); CHECK(dhi.ensure(nb)); CHECK(dhave.ensure(nb)); CHECK(dcnt.ensure((size_t)n_boxes));
+  if (upload(set_err, dlo, lo, nb) != 0 || upload(set_err, dhi, hi, nb) != 0 || upload(set_err, dhave, have, nb) != 0) return -1;
+  CHECK(hipMemsetAsync(dcnt.p, 0, dcnt.bytes((size_t)n_boxes), nullptr));
   CHECK(hipEventRecord(x->ev0.e, nullptr));
   if (x->nrows > 0) {
-    const dim3 g((unsigned)std::min<int64_t>((x->nrows + 255) / 256, 1024), (unsigned)((n_boxes + kBoxChunk - 1) / kBoxChunk)), b(256);
-#define PW_LAUNCH_COUNT(N_)                                                                                           \
-  hipLaunchKernelGGL((k_mcount<N_>), g, b, 0, nullptr, (const int32_t*)x->rows.p, x->nrows, n_boxes, (const int32_t*)dlo.p, \
-                     (const int32_t*)dhi.p, (const uint8_t*)dhave.p, (unsigned long long*)dcnt.p)
+    const dim3 g((unsigned)std::min<int64_t>((x->nrows + 255) / 256, 1024), (unsigned)((n_boxes + kBoxChunk - 1) / kBoxChunk)), b = kBlock256;
+#define PW_LAUNCH_COUNT(N_) hipLaunchKernelGGL((k_mcount<N_>), g, b, 0, nullptr, x->rows.p, x->nrows, n_boxes, dlo.p, dhi.p, dhave.p, dcnt.p)
     PW_MSEEDS_FOR_N(x->n, PW_LAUNCH_COUNT)
 #undef PW_LAUNCH_COUNT
   }
   if (elapsed(set_err, x->ev0, x->ev1, nullptr, &x->ms_count) != 0) return -1;
-  CHECK(hipMemcpy(counts, dcnt.p, (size_t)n_boxes * 8, hipMemcpyDeviceToHost));
+  CHECK(hipMemcpy(counts, dcnt.p, dcnt.bytes((size_t)n_boxes), hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -392,25 +387,23 @@ int64_t pw_mseeds_graph_build(pw_mseed_index* x, double d_coeff, double radius) 
   const int64_t nd = x->len[0] + x->len[1] + 1;
   const double wd = floor(radius / d_coeff) + 2;
   const int win = wd > (double)nd ? (int)nd : (int)wd;
-  DeviceBuffer kin, vin;
-  CHECK(kin.ensure((size_t)n * 8)); CHECK(vin.ensure((size_t)n * 4));
-  CHECK(x->g_srows.ensure((size_t)n * 4 * N)); CHECK(x->g_dstart.ensure((size_t)(nd + 1) * 4));
-  const dim3 grid((unsigned)((n + 255) / 256)), blk(256);
-  hipLaunchKernelGGL(k_mgraph_keys, grid, blk, 0, nullptr, (const int32_t*)x->rows.p, n, N, nd_off, (uint64_t*)kin.p, (uint32_t*)vin.p);
+  DeviceArray<uint64_t> kin; DeviceArray<uint32_t> vin;      // kin: the sort keys, then graph_finish's widened counts
+  CHECK(kin.ensure((size_t)n)); CHECK(vin.ensure((size_t)n));
+  CHECK(x->g_srows.ensure((size_t)n * N)); CHECK(x->g_dstart.ensure((size_t)nd + 1));
+  const dim3 grid = rows_grid((uint64_t)n), blk = kBlock256;
+  hipLaunchKernelGGL(k_mgraph_keys, grid, blk, 0, nullptr, x->rows.p, n, N, nd_off, kin.p, vin.p);
   if (graph_sort(set_err, g, x->tmp, kin, vin, n, 32 + bits_for((uint64_t)nd)) != 0) return -1;
-  hipLaunchKernelGGL(k_mgraph_gather, grid, blk, 0, nullptr, (const int32_t*)x->rows.p, (const uint32_t*)g.order.p, n, N,
-                     (int32_t*)x->g_srows.p);
-  hipLaunchKernelGGL(k_graph_dstart, dim3((unsigned)((nd + 256) / 256)), blk, 0, nullptr, (const uint64_t*)g.keys.p, n, nd,
-                     (uint32_t*)x->g_dstart.p);
+  hipLaunchKernelGGL(k_mgraph_gather, grid, blk, 0, nullptr, x->rows.p, g.order.p, n, N, x->g_srows.p);
+  hipLaunchKernelGGL(k_graph_dstart, rows_grid((uint64_t)nd + 1), blk, 0, nullptr, g.keys.p, n, nd, x->g_dstart.p);
   // the count pass (FILL_ = false: cnt) and the fill pass (off -> adj)
-#define PW_LAUNCH_SCAN(N_, FILL_, CNT_, OFF_, ADJ_)                                                                      \
-  hipLaunchKernelGGL((k_mgraph_scan<N_, FILL_>), grid, blk, 0, nullptr, (const uint64_t*)g.keys.p, (const uint32_t*)g.order.p,       \
-                     (const int32_t*)x->g_srows.p, n, (const uint32_t*)x->g_dstart.p, (int)nd, nd_off, d_coeff, radius, win,       \
-                     (uint32_t*)(CNT_), (const uint64_t*)(OFF_), (uint32_t*)(ADJ_))
-#define PW_LAUNCH_COUNT_PASS(N_) PW_LAUNCH_SCAN(N_, false, g.cnt.p, nullptr, nullptr)
-#define PW_LAUNCH_FILL_PASS(N_) PW_LAUNCH_SCAN(N_, true, nullptr, g.off.p, g.adj.p)
+  uint32_t* const no_counts = nullptr; uint32_t* const no_adj = nullptr; const uint64_t* const no_off = nullptr;
+#define PW_LAUNCH_SCAN(N_, FILL_, CNT_, OFF_, ADJ_)                                                                              \
+  hipLaunchKernelGGL((k_mgraph_scan<N_, FILL_>), grid, blk, 0, nullptr, g.keys.p, g.order.p, x->g_srows.p, n, x->g_dstart.p, (int)nd, \
+                     nd_off, d_coeff, radius, win, CNT_, OFF_, ADJ_)
+#define PW_LAUNCH_COUNT_PASS(N_) PW_LAUNCH_SCAN(N_, false, g.cnt.p, no_off, no_adj)
+#define PW_LAUNCH_FILL_PASS(N_) PW_LAUNCH_SCAN(N_, true, no_counts, g.off.p, g.adj.p)
   PW_MSEEDS_FOR_N(N, PW_LAUNCH_COUNT_PASS)
-  const int64_t total = graph_finish(set_err, g, x->tmp, x->scalar, (uint64_t*)kin.p, n, [&]() -> int {
+  const int64_t total = graph_finish(set_err, g, x->tmp, x->scalar, kin.p, n, [&]() -> int {
     PW_MSEEDS_FOR_N(N, PW_LAUNCH_FILL_PASS)
     return 0;
   });

@@ -584,12 +584,6 @@ __global__ __launch_bounds__(256) void k_band_medium(const DPair* __restrict__ p
 }
 
 // ---- host helpers: everything runs on the null stream --------------------------------------------------------------
-// `buf` grown to `bytes` and filled from the host
-int upload(DeviceBuffer& buf, const void* host, size_t bytes) {
-  CHECK(buf.ensure(bytes));
-  CHECK(hipMemcpy(buf.p, host, bytes, hipMemcpyHostToDevice));
-  return 0;
-}
 // strand (host, one byte per pair of the chunk) and d_comp are null on the forward-only path
 int run_chunk(const uint8_t* d_arena, const pw_read_pair* pairs, int64_t n, int L, int k, int kbits, BandConst bc,
               pw_overlap_band* out, hipEvent_t ev0, hipEvent_t ev1, float* ms, const uint8_t* strand = nullptr,
@@ -605,47 +599,43 @@ int run_chunk(const uint8_t* d_arena, const pw_read_pair* pairs, int64_t n, int 
     ct += pairs[p].t_len >= k ? (uint64_t)(pairs[p].t_len - k + 1) : 0;
   }
   ss[(size_t)n] = cs; ts[(size_t)n] = ct;
-  DeviceBuffer dp, dss, dts, dstrand, kin, pin, ksb, psb, ktb, ptb, hist, rows, first, dout, tmp, dlist;
-  CHECK(kin.ensure(8 * (size_t)std::max(cs, ct))); CHECK(pin.ensure(4 * (size_t)std::max(cs, ct)));
-  CHECK(ksb.ensure(8 * (size_t)cs)); CHECK(psb.ensure(4 * (size_t)cs)); CHECK(ktb.ensure(8 * (size_t)ct)); CHECK(ptb.ensure(4 * (size_t)ct));
-  CHECK(hist.ensure(4 * (size_t)hb)); CHECK(rows.ensure(8 * (size_t)n)); CHECK(first.ensure(4 * (size_t)n));
-  CHECK(dout.ensure(sizeof(pw_overlap_band) * (size_t)n)); CHECK(dlist.ensure(256 * (size_t)n));
-  if (upload(dp, hp.data(), sizeof(DPair) * (size_t)n) != 0 || upload(dss, ss.data(), 8 * ((size_t)n + 1)) != 0 ||
-      upload(dts, ts.data(), 8 * ((size_t)n + 1)) != 0 || (strand && upload(dstrand, strand, (size_t)n) != 0))
+  DeviceArray<DPair> dp; DeviceArray<uint64_t> dss, dts, kin, ksb, ktb; DeviceArray<uint32_t> pin, psb, ptb, hist, first;
+  DeviceArray<uint8_t> dstrand; DeviceArray<unsigned long long> rows; DeviceArray<int32_t> dlist, dfirst;     // dlist: 64 diagonals per pair
+  DeviceArray<pw_overlap_band> dout; DeviceBuffer tmp;
+  CHECK(kin.ensure((size_t)std::max(cs, ct))); CHECK(pin.ensure((size_t)std::max(cs, ct)));
+  CHECK(ksb.ensure((size_t)cs)); CHECK(psb.ensure((size_t)cs)); CHECK(ktb.ensure((size_t)ct)); CHECK(ptb.ensure((size_t)ct));
+  CHECK(hist.ensure((size_t)hb)); CHECK(rows.ensure((size_t)n)); CHECK(first.ensure((size_t)n));
+  CHECK(dout.ensure((size_t)n)); CHECK(dlist.ensure(64 * (size_t)n));
+  if (upload(set_err, dp, hp.data(), (size_t)n) != 0 || upload(set_err, dss, ss.data(), (size_t)n + 1) != 0 ||
+      upload(set_err, dts, ts.data(), (size_t)n + 1) != 0 || (strand && upload(set_err, dstrand, strand, (size_t)n) != 0))
     return -1;
   CHECK(hipEventRecord(ev0, nullptr));
-  CHECK(hipMemsetAsync(hist.p, 0, 4 * (size_t)hb, nullptr));
-  CHECK(hipMemsetAsync(rows.p, 0, 8 * (size_t)n, nullptr));
-  CHECK(hipMemsetAsync(first.p, 0xff, 4 * (size_t)n, nullptr));
+  CHECK(hipMemsetAsync(hist.p, 0, hist.bytes((size_t)hb), nullptr));
+  CHECK(hipMemsetAsync(rows.p, 0, rows.bytes((size_t)n), nullptr));
+  CHECK(hipMemsetAsync(first.p, 0xff, first.bytes((size_t)n), nullptr));
   const int pbits = bits_for((uint64_t)n);
   for (int side = 0; side < 2; side++) {
     const uint64_t tot = side ? ct : cs;
     if (tot == 0) continue;
     if (side && strand)
-      hipLaunchKernelGGL(k_enc_batch_rc, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, nullptr, d_arena, (const DPair*)dp.p,
-                         (const uint64_t*)dts.p, n, (int64_t)tot, (const uint8_t*)dstrand.p, d_comp, k, L, kbits, (uint64_t*)kin.p,
-                         (uint32_t*)pin.p);
+      hipLaunchKernelGGL(k_enc_batch_rc, rows_grid(tot), kBlock256, 0, nullptr, d_arena, dp.p, dts.p, n, (int64_t)tot, dstrand.p, d_comp, k,
+                         L, kbits, kin.p, pin.p);
     else
-      hipLaunchKernelGGL(k_enc_batch, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, nullptr, d_arena, (const DPair*)dp.p,
-                         (const uint64_t*)(side ? dts.p : dss.p), n, (int64_t)tot, side, k, L, kbits, (uint64_t*)kin.p, (uint32_t*)pin.p);
-    CHECK((sort_pairs<uint64_t, uint32_t>(tmp, kin, side ? ktb : ksb, pin, side ? ptb : psb, (size_t)tot, kbits + pbits)));
+      hipLaunchKernelGGL(k_enc_batch, rows_grid(tot), kBlock256, 0, nullptr, d_arena, dp.p, side ? dts.p : dss.p, n, (int64_t)tot, side, k, L,
+                         kbits, kin.p, pin.p);
+    CHECK(sort_pairs(tmp, kin, side ? ktb : ksb, pin, side ? ptb : psb, (size_t)tot, kbits + pbits));
   }
   if (cs && ct)
-    hipLaunchKernelGGL(k_join_hist, dim3((unsigned)((cs + 255) / 256)), dim3(256), 0, nullptr, (const uint64_t*)ksb.p,
-                       (const uint32_t*)psb.p, (int64_t)cs, (const uint64_t*)ktb.p, (const uint32_t*)ptb.p, (int64_t)ct,
-                       (const DPair*)dp.p, kbits, (uint32_t*)hist.p, (unsigned long long*)rows.p, (uint32_t*)first.p, (int32_t*)dlist.p);
-  DeviceBuffer dfirst;
-  CHECK(dfirst.ensure(4 * (size_t)n));
-  hipLaunchKernelGGL(k_first_d, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, (const uint32_t*)first.p, n,
-                     (const uint64_t*)ksb.p, (const uint32_t*)psb.p, (const uint64_t*)ktb.p, (const uint32_t*)ptb.p, (int64_t)ct,
-                     (int32_t*)dfirst.p);
-  hipLaunchKernelGGL(k_band_small, dim3((unsigned)(((uint64_t)n * 64 + 255) / 256)), dim3(256), 0, nullptr, (const DPair*)dp.p,
-                     (const uint64_t*)nullptr, (const unsigned long long*)rows.p, (const int32_t*)dlist.p, (const int32_t*)dfirst.p, n, bc,
-                     (pw_overlap_band*)dout.p);
-  hipLaunchKernelGGL(k_band_select, dim3((unsigned)n), dim3(256), 0, nullptr, (const DPair*)dp.p, (uint32_t*)hist.p,
-                     (const unsigned long long*)rows.p, (const int32_t*)dfirst.p, (uint64_t)0, kSmallPair, bc, (pw_overlap_band*)dout.p);
+    hipLaunchKernelGGL(k_join_hist, rows_grid(cs), kBlock256, 0, nullptr, ksb.p, psb.p, (int64_t)cs, ktb.p, ptb.p, (int64_t)ct, dp.p, kbits,
+                       hist.p, rows.p, first.p, dlist.p);
+  CHECK(dfirst.ensure((size_t)n));
+  hipLaunchKernelGGL(k_first_d, rows_grid((uint64_t)n), kBlock256, 0, nullptr, first.p, n, ksb.p, psb.p, ktb.p, ptb.p, (int64_t)ct, dfirst.p);
+  hipLaunchKernelGGL(k_band_small, rows_grid((uint64_t)n * 64), kBlock256, 0, nullptr, dp.p, (const uint64_t*)nullptr, rows.p, dlist.p,
+                     dfirst.p, n, bc, dout.p);
+  hipLaunchKernelGGL(k_band_select, dim3((unsigned)n), kBlock256, 0, nullptr, dp.p, hist.p, rows.p, dfirst.p, (uint64_t)0, kSmallPair, bc,
+                     dout.p);
   CHECK(hipEventRecord(ev1, nullptr));
-  CHECK(hipMemcpy(out, dout.p, sizeof(pw_overlap_band) * (size_t)n, hipMemcpyDeviceToHost));
+  CHECK(hipMemcpy(out, dout.p, dout.bytes((size_t)n), hipMemcpyDeviceToHost));
   CHECK(hipGetLastError());
   float t = 0.f;
   CHECK(hipEventElapsedTime(&t, ev0, ev1));
@@ -663,80 +653,75 @@ struct AllPairs {
   int64_t R; int L, k, kbits, sel, shard_rank, shard_world; int64_t max_pairs; BandConst bc;
   uint32_t max_occ;                                    // 0: no cap, K9b / K9b' as they always were
   pw_overlap_cap_stats cap{};                          // (max_occ != 0) filled by self_join
-  DeviceBuffer dstats;
+  DeviceArray<unsigned long long> dstats;              // the three counters of the cap
   bool st = false;                                     // sel != 1
   uint64_t K = 0, NS = 0;                              // k-mers per index, seeds
   unsigned long long NP = 0;                           // candidate pairs
-  const dim3 blk = dim3(256);
-  DeviceBuffer droff, drlen, drstart, tmp;             // the reads (run); rocPRIM's scratch, one for the whole call
-  DeviceBuffer kin, vin, ks, vs, kr, vr;               // build_index: staging, the forward index, the reverse-strand index
-  DeviceBuffer fs, cnt, off, fr, cf, pk_in, dv_in, pk, dv;                          // self_join: (pair key, d) per seed
-  DeviceBuffer uk, uc, nruns, soff, hsize, hbase, dpairs, dfirst, dpa, dpb, dps;    // group_pairs: the candidate pairs
-  DeviceBuffer dout, hist;                             // score_tiers: the records
+  const dim3 blk = kBlock256;
+  DeviceArray<uint64_t> droff, drstart; DeviceArray<int32_t> drlen; DeviceBuffer tmp;   // the reads (run); rocPRIM's scratch, one for the whole call
+  DeviceArray<uint64_t> kin, vin, ks, vs, kr, vr;      // build_index: staging, the forward index, the reverse-strand index
+  DeviceArray<uint32_t> fs, fr, cf; DeviceArray<uint64_t> cnt, off, pk_in, pk; DeviceArray<int32_t> dv_in, dv;   // self_join: (pair key, d) per seed
+  DeviceArray<uint64_t> uk, soff, hsize, hbase; DeviceArray<unsigned long long> uc, nruns;                       // group_pairs: the candidate pairs
+  DeviceArray<DPair> dpairs; DeviceArray<int32_t> dfirst, dpa, dpb; DeviceArray<uint8_t> dps;
+  DeviceArray<pw_overlap_band> dout; DeviceArray<uint32_t> hist;                                                 // score_tiers: the records
 
   // Stage 1, once per strand: K9a (K9a' for the reverse strand) into kin / vin, then the stable sort by k-mer.
   int build_index(bool reverse) {
-    const dim3 gK((unsigned)((K + 255) / 256));
     if (reverse)
-      hipLaunchKernelGGL(k_enc_reads_rc, gK, blk, 0, nullptr, d_arena, (const uint64_t*)droff.p, (const int32_t*)drlen.p,
-                         (const uint64_t*)drstart.p, R, (int64_t)K, k, L, d_comp, (uint64_t*)kin.p, (uint64_t*)vin.p);
+      hipLaunchKernelGGL(k_enc_reads_rc, rows_grid(K), blk, 0, nullptr, d_arena, droff.p, drlen.p, drstart.p, R, (int64_t)K, k, L, d_comp,
+                         kin.p, vin.p);
     else
-      hipLaunchKernelGGL(k_enc_reads, gK, blk, 0, nullptr, d_arena, (const uint64_t*)droff.p, (const uint64_t*)drstart.p, R, (int64_t)K, k, L,
-                         (uint64_t*)kin.p, (uint64_t*)vin.p);
-    CHECK((sort_pairs<uint64_t, uint64_t>(tmp, kin, reverse ? kr : ks, vin, reverse ? vr : vs, (size_t)K, kbits)));
+      hipLaunchKernelGGL(k_enc_reads, rows_grid(K), blk, 0, nullptr, d_arena, droff.p, drstart.p, R, (int64_t)K, k, L, kin.p, vin.p);
+    CHECK(sort_pairs(tmp, kin, reverse ? kr : ks, vin, reverse ? vr : vs, (size_t)K, kbits));
     return 0;
   }
 
   // Stage 2: the self join (K9b, K9b') to seeds -> (pair key, d), stably sorted by the pair key.  NS stays 0 when no two reads
   // share a k-mer.
   int self_join() {
-    const dim3 gK((unsigned)((K + 255) / 256));
+    const dim3 gK = rows_grid(K);
     const bool capped = max_occ != 0;
-    if (capped) { CHECK(dstats.ensure(24)); CHECK(hipMemsetAsync(dstats.p, 0, 24, nullptr)); }
+    if (capped) { CHECK(dstats.ensure(3)); CHECK(hipMemsetAsync(dstats.p, 0, dstats.bytes(3), nullptr)); }
     auto* const count_kernel = capped ? k_self_count<true> : k_self_count<false>;
     auto* const count_st_kernel = capped ? k_self_count_st<true> : k_self_count_st<false>;
     if (st)
-      hipLaunchKernelGGL(count_st_kernel, gK, blk, 0, nullptr, (const uint64_t*)ks.p, (const uint64_t*)vs.p, (int64_t)K,
-                         (const uint64_t*)kr.p, (const uint64_t*)vr.p, sel, shard_rank, shard_world, (uint32_t*)fs.p, (uint32_t*)cf.p,
-                         (uint32_t*)fr.p, (uint64_t*)cnt.p, max_occ, (unsigned long long*)dstats.p);
+      hipLaunchKernelGGL(count_st_kernel, gK, blk, 0, nullptr, ks.p, vs.p, (int64_t)K, kr.p, vr.p, sel, shard_rank, shard_world, fs.p, cf.p,
+                         fr.p, cnt.p, max_occ, dstats.p);
     else
-      hipLaunchKernelGGL(count_kernel, gK, blk, 0, nullptr, (const uint64_t*)ks.p, (const uint64_t*)vs.p, (int64_t)K, shard_rank, shard_world,
-                         (uint32_t*)fs.p, (uint64_t*)cnt.p, max_occ, (unsigned long long*)dstats.p);
+      hipLaunchKernelGGL(count_kernel, gK, blk, 0, nullptr, ks.p, vs.p, (int64_t)K, shard_rank, shard_world, fs.p, cnt.p, max_occ, dstats.p);
     CHECK(scan_u64(tmp, cnt, off, (size_t)K));
     uint64_t last_off = 0, last_cnt = 0;
-    CHECK(hipMemcpy(&last_off, (uint64_t*)off.p + (K - 1), 8, hipMemcpyDeviceToHost));
-    CHECK(hipMemcpy(&last_cnt, (uint64_t*)cnt.p + (K - 1), 8, hipMemcpyDeviceToHost));
+    CHECK(hipMemcpy(&last_off, off.p + (K - 1), sizeof last_off, hipMemcpyDeviceToHost));
+    CHECK(hipMemcpy(&last_cnt, cnt.p + (K - 1), sizeof last_cnt, hipMemcpyDeviceToHost));
     NS = last_off + last_cnt;
     if (capped) {
       unsigned long long t[3];
-      CHECK(hipMemcpy(t, dstats.p, 24, hipMemcpyDeviceToHost));
+      CHECK(hipMemcpy(t, dstats.p, sizeof t, hipMemcpyDeviceToHost));
       // (both strands: the reverse index holds as many masked entries as the forward one, see K9b')
       cap = pw_overlap_cap_stats{(st ? 2 : 1) * K, (st ? 2 : 1) * t[0], t[1], NS, t[2]};
     }
     if (NS == 0) return 0;
     if (NS >= (1ull << 32)) { set_err("more than 2^32 seeds between the reads: use a longer word"); return -1; }
-    CHECK(pk_in.ensure(8 * (size_t)NS)); CHECK(dv_in.ensure(4 * (size_t)NS)); CHECK(pk.ensure(8 * (size_t)NS)); CHECK(dv.ensure(4 * (size_t)NS));
+    CHECK(pk_in.ensure((size_t)NS)); CHECK(dv_in.ensure((size_t)NS)); CHECK(pk.ensure((size_t)NS)); CHECK(dv.ensure((size_t)NS));
     if (st)
-      hipLaunchKernelGGL(k_self_expand_st, dim3((unsigned)((NS + 255) / 256)), blk, 0, nullptr, (const uint64_t*)off.p, (int64_t)K, (int64_t)NS,
-                         (const uint64_t*)vs.p, (const uint64_t*)vr.p, (const uint32_t*)fs.p, (const uint32_t*)cf.p, (const uint32_t*)fr.p,
-                         (uint64_t)R, (uint64_t*)pk_in.p, (int32_t*)dv_in.p);
+      hipLaunchKernelGGL(k_self_expand_st, rows_grid(NS), blk, 0, nullptr, off.p, (int64_t)K, (int64_t)NS, vs.p, vr.p, fs.p, cf.p, fr.p,
+                         (uint64_t)R, pk_in.p, dv_in.p);
     else
-      hipLaunchKernelGGL(k_self_expand, dim3((unsigned)((NS + 255) / 256)), blk, 0, nullptr, (const uint64_t*)off.p, (int64_t)K, (int64_t)NS,
-                         (const uint64_t*)vs.p, (const uint32_t*)fs.p, (uint64_t)R, (uint64_t*)pk_in.p, (int32_t*)dv_in.p);
+      hipLaunchKernelGGL(k_self_expand, rows_grid(NS), blk, 0, nullptr, off.p, (int64_t)K, (int64_t)NS, vs.p, fs.p, (uint64_t)R, pk_in.p,
+                         dv_in.p);
     const int pbits = bits_for((uint64_t)R * (uint64_t)R) + (st ? 1 : 0);       // (the strand bit below the pair rank)
-    CHECK((sort_pairs<uint64_t, int32_t>(tmp, pk_in, pk, dv_in, dv, (size_t)NS, pbits)));
+    CHECK(sort_pairs(tmp, pk_in, pk, dv_in, dv, (size_t)NS, pbits));
     return 0;
   }
 
   // Stage 3: the sorted seeds grouped into candidate pairs -- unique pair keys with their seed counts, then seed offsets,
   // histogram bases and DPairs.
   int group_pairs() {
-    CHECK(uk.ensure(8 * (size_t)NS)); CHECK(uc.ensure(8 * (size_t)NS)); CHECK(nruns.ensure(16));
+    CHECK(uk.ensure((size_t)NS)); CHECK(uc.ensure((size_t)NS)); CHECK(nruns.ensure(1));
     CHECK(rocprim_run(tmp, [&](void* t, size_t& b) {
-      return rocprim::run_length_encode(t, b, (const uint64_t*)pk.p, (unsigned int)NS, (uint64_t*)uk.p, (unsigned long long*)uc.p,
-                                        (unsigned long long*)nruns.p, (hipStream_t) nullptr);
+      return rocprim::run_length_encode(t, b, pk.cp(), (unsigned int)NS, uk.p, uc.p, nruns.p, (hipStream_t) nullptr);
     }));
-    CHECK(hipMemcpy(&NP, nruns.p, 8, hipMemcpyDeviceToHost));
+    CHECK(hipMemcpy(&NP, nruns.p, sizeof NP, hipMemcpyDeviceToHost));
     if ((int64_t)NP > max_pairs) {
       char msg[160];
       snprintf(msg, sizeof msg, "%llu pairs of reads share a seed (capacity %lld): raise max_pairs or the word length", NP, (long long)max_pairs);
@@ -744,68 +729,63 @@ struct AllPairs {
       return -1;
     }
     if (st) CHECK(dps.ensure((size_t)NP));
-    CHECK(soff.ensure(8 * (size_t)NP)); CHECK(hsize.ensure(8 * (size_t)NP)); CHECK(hbase.ensure(8 * (size_t)NP));
-    CHECK(dpairs.ensure(sizeof(DPair) * (size_t)NP)); CHECK(dfirst.ensure(4 * (size_t)NP)); CHECK(dpa.ensure(4 * (size_t)NP));
-    CHECK(dpb.ensure(4 * (size_t)NP));
-    const dim3 gP((unsigned)((NP + 255) / 256));
+    CHECK(soff.ensure((size_t)NP)); CHECK(hsize.ensure((size_t)NP)); CHECK(hbase.ensure((size_t)NP));
+    CHECK(dpairs.ensure((size_t)NP)); CHECK(dfirst.ensure((size_t)NP)); CHECK(dpa.ensure((size_t)NP));
+    CHECK(dpb.ensure((size_t)NP));
+    const dim3 gP = rows_grid(NP);
     CHECK(scan_u64(tmp, uc, soff, (size_t)NP));
     auto* const hsize_kernel = st ? k_pair_hsize<1> : k_pair_hsize<0>;
     auto* const cand_kernel = st ? k_cand_pairs<1> : k_cand_pairs<0>;
-    hipLaunchKernelGGL(hsize_kernel, gP, blk, 0, nullptr, (const uint64_t*)uk.p, (const unsigned long long*)uc.p, (int64_t)NP, (uint64_t)R,
-                       (const int32_t*)drlen.p, (uint64_t*)hsize.p, kMediumPair);
+    hipLaunchKernelGGL(hsize_kernel, gP, blk, 0, nullptr, uk.p, uc.p, (int64_t)NP, (uint64_t)R, drlen.p, hsize.p, kMediumPair);
     CHECK(scan_u64(tmp, hsize, hbase, (size_t)NP));
-    hipLaunchKernelGGL(cand_kernel, gP, blk, 0, nullptr, (const uint64_t*)uk.p, (const uint64_t*)soff.p,
-                       (const int32_t*)dv.p, (int64_t)NP, (uint64_t)R, (const uint64_t*)droff.p, (const int32_t*)drlen.p,
-                       (const uint64_t*)hbase.p, (DPair*)dpairs.p, (int32_t*)dfirst.p, (int32_t*)dpa.p, (int32_t*)dpb.p, (uint8_t*)dps.p);
+    hipLaunchKernelGGL(cand_kernel, gP, blk, 0, nullptr, uk.p, soff.p, dv.p, (int64_t)NP, (uint64_t)R, droff.p, drlen.p, hbase.p, dpairs.p,
+                       dfirst.p, dpa.p, dpb.p, dps.p);
     return 0;
   }
 
   // Stage 4: every candidate pair's record, by the tier its seed count puts it in.
   int score_tiers() {
-    const dim3 gP((unsigned)((NP + 255) / 256));
-    CHECK(dout.ensure(sizeof(pw_overlap_band) * (size_t)NP));
-    hipLaunchKernelGGL(k_band_small, dim3((unsigned)((NP * 64 + 255) / 256)), blk, 0, nullptr, (const DPair*)dpairs.p, (const uint64_t*)soff.p,
-                       (const unsigned long long*)uc.p, (const int32_t*)dv.p, (const int32_t*)nullptr, (int64_t)NP, bc, (pw_overlap_band*)dout.p);
+    const dim3 gP = rows_grid(NP);
+    CHECK(dout.ensure((size_t)NP));
+    hipLaunchKernelGGL(k_band_small, rows_grid(NP * 64), blk, 0, nullptr, dpairs.p, soff.p, uc.p, dv.p, (const int32_t*)nullptr, (int64_t)NP,
+                       bc, dout.p);
     // pairs with 65 .. kMediumPair seeds: one workgroup each, from the seed list
     {
-      DeviceBuffer mlist, mcount;
-      CHECK(mlist.ensure(8 * (size_t)NP)); CHECK(mcount.ensure(16));
-      CHECK(hipMemsetAsync(mcount.p, 0, 16, nullptr));
-      hipLaunchKernelGGL(k_list_medium, gP, blk, 0, nullptr, (const unsigned long long*)uc.p, (int64_t)NP, (unsigned long long*)mcount.p, (int64_t*)mlist.p);
+      DeviceArray<int64_t> mlist; DeviceArray<unsigned long long> mcount;
+      CHECK(mlist.ensure((size_t)NP)); CHECK(mcount.ensure(1));
+      CHECK(hipMemsetAsync(mcount.p, 0, mcount.bytes(1), nullptr));
+      hipLaunchKernelGGL(k_list_medium, gP, blk, 0, nullptr, uc.p, (int64_t)NP, mcount.p, mlist.p);
       unsigned long long NM = 0;
-      CHECK(hipMemcpy(&NM, mcount.p, 8, hipMemcpyDeviceToHost));
-      if (NM) hipLaunchKernelGGL(k_band_medium, dim3((unsigned)NM), blk, 0, nullptr, (const DPair*)dpairs.p, (const int64_t*)mlist.p, (const uint64_t*)soff.p,
-                                 (const unsigned long long*)uc.p, (const int32_t*)dv.p, (const int32_t*)dfirst.p, bc, (pw_overlap_band*)dout.p);
+      CHECK(hipMemcpy(&NM, mcount.p, sizeof NM, hipMemcpyDeviceToHost));
+      if (NM) hipLaunchKernelGGL(k_band_medium, dim3((unsigned)NM), blk, 0, nullptr, dpairs.p, mlist.p, soff.p, uc.p, dv.p, dfirst.p, bc, dout.p);
       CHECK(hipDeviceSynchronize());                      // (mlist is freed at the end of this scope)
     }
     // chunks of pairs whose histograms fit 2^30 counters (none at all when no pair has more than kMediumPair seeds)
     uint64_t last_base = 0, last_size = 0;
     if (NP) {
-      CHECK(hipMemcpy(&last_base, (const uint64_t*)hbase.p + (NP - 1), 8, hipMemcpyDeviceToHost));
-      CHECK(hipMemcpy(&last_size, (const uint64_t*)hsize.p + (NP - 1), 8, hipMemcpyDeviceToHost));
+      CHECK(hipMemcpy(&last_base, hbase.p + (NP - 1), sizeof last_base, hipMemcpyDeviceToHost));
+      CHECK(hipMemcpy(&last_size, hsize.p + (NP - 1), sizeof last_size, hipMemcpyDeviceToHost));
     }
     const bool any_hist = last_base + last_size > 0;
     const size_t NPh = any_hist ? (size_t)NP : 0;
     std::vector<uint64_t> h_hbase(NPh), h_soff(NPh), h_hsize(NPh);
     if (any_hist) {
-      CHECK(hipMemcpy(h_hbase.data(), hbase.p, 8 * (size_t)NP, hipMemcpyDeviceToHost));
-      CHECK(hipMemcpy(h_soff.data(), soff.p, 8 * (size_t)NP, hipMemcpyDeviceToHost));
-      CHECK(hipMemcpy(h_hsize.data(), hsize.p, 8 * (size_t)NP, hipMemcpyDeviceToHost));
+      CHECK(hipMemcpy(h_hbase.data(), hbase.p, hbase.bytes(NPh), hipMemcpyDeviceToHost));
+      CHECK(hipMemcpy(h_soff.data(), soff.p, soff.bytes(NPh), hipMemcpyDeviceToHost));
+      CHECK(hipMemcpy(h_hsize.data(), hsize.p, hsize.bytes(NPh), hipMemcpyDeviceToHost));
     }
     const uint64_t cap = 1ull << 30;
     for (uint64_t u0 = 0; any_hist && u0 < NP;) {
       uint64_t u1 = u0, tot = 0;
       while (u1 < NP && (u1 == u0 || tot + h_hsize[(size_t)u1] <= cap)) { tot += h_hsize[(size_t)u1]; u1++; }
       if (tot == 0) { u0 = u1; continue; }                 // no pair of this chunk needs a histogram
-      CHECK(hist.ensure(4 * (size_t)tot));
-      CHECK(hipMemsetAsync(hist.p, 0, 4 * (size_t)tot, nullptr));
+      CHECK(hist.ensure((size_t)tot));
+      CHECK(hipMemsetAsync(hist.p, 0, hist.bytes((size_t)tot), nullptr));
       const uint64_t s0 = h_soff[(size_t)u0], s1 = u1 < NP ? h_soff[(size_t)u1] : NS;
-      hipLaunchKernelGGL(k_scatter_hist, dim3((unsigned)((s1 - s0 + 255) / 256)), blk, 0, nullptr, (const int32_t*)dv.p, (int64_t)s0, (int64_t)s1,
-                         (const uint64_t*)soff.p, (int64_t)u0, (int64_t)u1, (const DPair*)dpairs.p, h_hbase[(size_t)u0], (uint32_t*)hist.p,
-                         kMediumPair);
-      hipLaunchKernelGGL(k_band_select, dim3((unsigned)(u1 - u0)), blk, 0, nullptr, (const DPair*)dpairs.p + u0, (uint32_t*)hist.p,
-                         (const unsigned long long*)uc.p + u0, (const int32_t*)dfirst.p + u0, h_hbase[(size_t)u0], kMediumPair, bc,
-                         (pw_overlap_band*)dout.p + u0);
+      hipLaunchKernelGGL(k_scatter_hist, rows_grid(s1 - s0), blk, 0, nullptr, dv.p, (int64_t)s0, (int64_t)s1, soff.p, (int64_t)u0, (int64_t)u1,
+                         dpairs.p, h_hbase[(size_t)u0], hist.p, kMediumPair);
+      hipLaunchKernelGGL(k_band_select, dim3((unsigned)(u1 - u0)), blk, 0, nullptr, dpairs.p + u0, hist.p, uc.p + u0, dfirst.p + u0,
+                         h_hbase[(size_t)u0], kMediumPair, bc, dout.p + u0);
       u0 = u1;
     }
     return 0;
@@ -828,24 +808,24 @@ struct AllPairs {
     DeviceEvent ev0, ev1;
     CHECK(ev0.create()); CHECK(ev1.create());
     // what the forward strand needs is allocated before the first event: no allocation of it is timed
-    CHECK(kin.ensure(8 * (size_t)K)); CHECK(vin.ensure(8 * (size_t)K)); CHECK(ks.ensure(8 * (size_t)K)); CHECK(vs.ensure(8 * (size_t)K));
-    CHECK(fs.ensure(4 * (size_t)K)); CHECK(cnt.ensure(8 * (size_t)K)); CHECK(off.ensure(8 * (size_t)K));
-    if (upload(droff, read_off, 8 * (size_t)R) != 0 || upload(drlen, read_len, 4 * (size_t)R) != 0 ||
-        upload(drstart, rstart.data(), 8 * ((size_t)R + 1)) != 0)
+    CHECK(kin.ensure((size_t)K)); CHECK(vin.ensure((size_t)K)); CHECK(ks.ensure((size_t)K)); CHECK(vs.ensure((size_t)K));
+    CHECK(fs.ensure((size_t)K)); CHECK(cnt.ensure((size_t)K)); CHECK(off.ensure((size_t)K));
+    if (upload(set_err, droff, read_off, (size_t)R) != 0 || upload(set_err, drlen, read_len, (size_t)R) != 0 ||
+        upload(set_err, drstart, rstart.data(), (size_t)R + 1) != 0)
       return -1;
     CHECK(hipEventRecord(ev0.e, nullptr));
     if (build_index(false) != 0) return -1;
     if (st) {
-      CHECK(kr.ensure(8 * (size_t)K)); CHECK(vr.ensure(8 * (size_t)K)); CHECK(fr.ensure(4 * (size_t)K)); CHECK(cf.ensure(4 * (size_t)K));
+      CHECK(kr.ensure((size_t)K)); CHECK(vr.ensure((size_t)K)); CHECK(fr.ensure((size_t)K)); CHECK(cf.ensure((size_t)K));
       if (build_index(true) != 0) return -1;
     }
     if (self_join() != 0) return -1;
     if (NS == 0) return 0;
     if (group_pairs() != 0 || score_tiers() != 0) return -1;
     CHECK(hipEventRecord(ev1.e, nullptr));
-    CHECK(hipMemcpy(out, dout.p, sizeof(pw_overlap_band) * (size_t)NP, hipMemcpyDeviceToHost));
-    CHECK(hipMemcpy(pair_a, dpa.p, 4 * (size_t)NP, hipMemcpyDeviceToHost));
-    CHECK(hipMemcpy(pair_b, dpb.p, 4 * (size_t)NP, hipMemcpyDeviceToHost));
+    CHECK(hipMemcpy(out, dout.p, dout.bytes((size_t)NP), hipMemcpyDeviceToHost));
+    CHECK(hipMemcpy(pair_a, dpa.p, dpa.bytes((size_t)NP), hipMemcpyDeviceToHost));
+    CHECK(hipMemcpy(pair_b, dpb.p, dpb.bytes((size_t)NP), hipMemcpyDeviceToHost));
     if (st) CHECK(hipMemcpy(pair_strand, dps.p, (size_t)NP, hipMemcpyDeviceToHost));
     CHECK(hipGetLastError());
     CHECK(hipEventElapsedTime(ms, ev0.e, ev1.e));
@@ -858,14 +838,14 @@ struct AllPairs {
 // check_args reports it
 int check_complement(const uint8_t* comp, int L) { return ::check_complement(set_err, comp, L); }
 
-int upload_arena(int device, const uint8_t* arena, uint64_t arena_bytes, DeviceBuffer& d_arena) {
+// the arena on `device`, with 64 bytes of slack behind the last read
+int upload_arena(int device, const uint8_t* arena, uint64_t arena_bytes, DeviceArray<uint8_t>& d_arena) {
   CHECK(hipSetDevice(device));
   CHECK(d_arena.ensure((size_t)arena_bytes + 64));
-  CHECK(hipMemcpy(d_arena.p, arena, (size_t)arena_bytes, hipMemcpyHostToDevice));
-  return 0;
+  return upload(set_err, d_arena, arena, (size_t)arena_bytes);
 }
 
-int upload_complement(const uint8_t* comp, int L, DeviceBuffer& d_comp) { return ::upload_complement(set_err, comp, L, d_comp); }
+int upload_complement(const uint8_t* comp, int L, DeviceArray<uint8_t>& d_comp) { return ::upload_complement(set_err, comp, L, d_comp); }
 
 // both all-pairs entry points; stranded: pair_strand is required and the strand selection and the complement are checked
 // first (the complement only where the selection needs it), then everything in check_args' order
@@ -888,11 +868,11 @@ int all_pairs(int device, const uint8_t* arena, uint64_t arena_bytes, const uint
     return -1;
   g_ms = 0.0; *n_out = 0;
   if (n_reads < 2) return 0;
-  DeviceBuffer d_arena, d_comp;
+  DeviceArray<uint8_t> d_arena, d_comp;
   if (upload_arena(device, arena, arena_bytes, d_arena) != 0) return -1;
   if (strands != PW_STRAND_PLUS && upload_complement(complement, alphabet_len, d_comp) != 0) return -1;
   float ms = 0.f;
-  AllPairs job{(const uint8_t*)d_arena.p, (const uint8_t*)d_comp.p, n_reads, alphabet_len, wordlen, kbits, strands, shard_rank, shard_world,
+  AllPairs job{d_arena.p, d_comp.p, n_reads, alphabet_len, wordlen, kbits, strands, shard_rank, shard_world,
                max_pairs, BandConst{len_coeff, radius_coeff, word_p_null}, max_occ};
   const int rc = job.run(read_off, read_len, pair_a, pair_b, pair_strand, out, n_out, &ms);
   if (stats) *stats = job.cap;                         // (what the join counted, also where a refusal followed it)
@@ -915,7 +895,7 @@ int bands(int device, const uint8_t* arena, uint64_t arena_bytes, const pw_read_
     return -1;
   g_ms = 0.0;
   if (n_pairs == 0) return 0;
-  DeviceBuffer d_arena, d_comp;
+  DeviceArray<uint8_t> d_arena, d_comp;
   if (upload_arena(device, arena, arena_bytes, d_arena) != 0) return -1;
   if (strand && upload_complement(complement, alphabet_len, d_comp) != 0) return -1;
   DeviceEvent ev0, ev1;
@@ -933,9 +913,8 @@ int bands(int device, const uint8_t* arena, uint64_t arena_bytes, const pw_read_
                       (max_pairs_bits < 40 && (p1 - p0 + 1) >= (1ll << max_pairs_bits)))) break;
       hb += h; cs += (uint64_t)pairs[p1].s_len; ct += (uint64_t)pairs[p1].t_len; p1++;
     }
-    rc = run_chunk((const uint8_t*)d_arena.p, pairs + p0, p1 - p0, alphabet_len, wordlen, kbits,
-                   BandConst{len_coeff, radius_coeff, word_p_null}, out + p0, ev0.e, ev1.e, &ms, strand ? strand + p0 : nullptr,
-                   (const uint8_t*)d_comp.p);
+    rc = run_chunk(d_arena.p, pairs + p0, p1 - p0, alphabet_len, wordlen, kbits, BandConst{len_coeff, radius_coeff, word_p_null}, out + p0,
+                   ev0.e, ev1.e, &ms, strand ? strand + p0 : nullptr, d_comp.p);
     p0 = p1;
   }
   g_ms = (double)ms;
@@ -1009,12 +988,13 @@ void* pw_overlap_arena_upload(int device, const uint8_t* host_arena, uint64_t by
     CHECK(hipMemset((uint8_t*)p + bytes, 0, (size_t)(total_bytes - bytes) + 16));
     if (bytes) CHECK(hipMemcpy(p, host_arena, (size_t)bytes, hipMemcpyHostToDevice));
     if (total == 0) return 0;
-    DeviceBuffer dsrc, ddst, dstart, d_comp;
-    const size_t nb = 8 * (size_t)n_frames;
-    if (upload(dsrc, src_off, nb) != 0 || upload(ddst, dst_off, nb) != 0 || upload(dstart, start.data(), nb + 8) != 0) return -1;
+    DeviceArray<uint64_t> dsrc, ddst, dstart; DeviceArray<uint8_t> d_comp;
+    const size_t nf = (size_t)n_frames;
+    if (upload(set_err, dsrc, src_off, nf) != 0 || upload(set_err, ddst, dst_off, nf) != 0 || upload(set_err, dstart, start.data(), nf + 1) != 0)
+      return -1;
     if (upload_complement(complement, alphabet_len, d_comp) != 0) return -1;
-    hipLaunchKernelGGL(k_revcomp_frames, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, nullptr, (uint8_t*)p, (const uint64_t*)dsrc.p,
-                       (const uint64_t*)ddst.p, (const uint64_t*)dstart.p, n_frames, (int64_t)total, (const uint8_t*)d_comp.p, alphabet_len);
+    hipLaunchKernelGGL(k_revcomp_frames, rows_grid(total), kBlock256, 0, nullptr, (uint8_t*)p, dsrc.p, ddst.p, dstart.p, n_frames,
+                       (int64_t)total, d_comp.p, alphabet_len);
     CHECK(hipGetLastError());
     CHECK(hipDeviceSynchronize());
     return 0;

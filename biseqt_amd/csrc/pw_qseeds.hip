@@ -276,9 +276,11 @@ struct pw_qseed_index {
   WordSpace ws;
   bool has_tab = false;                 // the direct-address table is filled
   int64_t nR = 0, nkR = 0, nq = -1, npos = 0, nrows = -1, max_qlen = 0;
-  DeviceBuffer dref, rkeys, rpos, tab;                                        // the reference: filled by create
-  DeviceBuffer arena, meta, qid, lo, cnt, off, row_off, rows, tmp, scalar;    // the queries: filled by build
-  DeviceBuffer comp;                                                          // the complement of a stranded build
+  DeviceArray<uint8_t> dref; DeviceBuffer rkeys; DeviceArray<uint32_t> rpos, tab;      // the reference: filled by create (rkeys: uint32_t or uint64_t by ws.key32)
+  DeviceArray<uint8_t> arena; DeviceArray<int64_t> meta; DeviceArray<uint32_t> qid, lo;  // the queries: filled by build (meta: build_queries has the layout)
+  DeviceArray<uint64_t> cnt, off, row_off; DeviceArray<int32_t> rows;                 // ... rows: (query, i, j) each
+  DeviceArray<unsigned long long> scalar; DeviceBuffer tmp;                           // [the row total | the bad-letter flag]; rocPRIM's scratch
+  DeviceArray<uint8_t> comp;                                                  // the complement of a stranded build
   SeedGraph g;                                                                // neighbourhood graph (K10d); g.npts: the rows
   int cc_rounds = 0;
   DeviceEvent ev0, ev1;
@@ -288,13 +290,12 @@ struct pw_qseed_index {
 // encode + sort the reference, fill the table: everything of pw_qseeds_create that depends on the key type
 template <typename K>
 static int index_reference(pw_qseed_index* x) {
-  DeviceBuffer keys_in, pos_in;
+  DeviceBuffer keys_in; DeviceArray<uint32_t> pos_in;
   const MaskSets none = {};
-  if (encode_sort<K>(set_err, x->ws, none, (const uint8_t*)x->dref.p, x->nR, x->nkR, keys_in, pos_in, x->tmp, x->rkeys, x->rpos, 0, nullptr) != 0)
-    return -1;
+  if (encode_sort<K>(set_err, x->ws, none, x->dref.p, x->nR, x->nkR, keys_in, pos_in, x->tmp, x->rkeys, x->rpos, 0, nullptr) != 0) return -1;
   if (x->nkR <= 0) return 0;
   if (table_pays(x->ws, x->nkR)) {
-    if (table_fill<K>(set_err, x->ws, (const K*)x->rkeys.p, x->nkR, x->tab, nullptr) != 0) return -1;
+    if (table_fill<K>(set_err, x->ws, x->rkeys.as<const K>(), x->nkR, x->tab, nullptr) != 0) return -1;
     x->has_tab = true;
   }
   CHECK(hipDeviceSynchronize());                  // (keys_in / pos_in are freed on return)
@@ -302,23 +303,24 @@ static int index_reference(pw_qseed_index* x) {
   return 0;
 }
 
+// the flag a match kernel raises at a letter outside the alphabet: an int in the second word of `scalar`
+static int* bad_letter_flag(pw_qseed_index* x) { return reinterpret_cast<int*>(x->scalar.p + 1); }
+
 template <typename K>
 static void launch_match(pw_qseed_index* x, const uint8_t* arena, hipStream_t st) {
-  const int64_t* meta = (const int64_t*)x->meta.p;                 // [offsets nq | pstart nq + 1 | lengths nq (int32)]
-  hipLaunchKernelGGL((k_qmatch<K>), dim3((unsigned)((x->npos + 255) / 256)), dim3(256), 0, st, arena, meta,
-                     (const int32_t*)(meta + 2 * x->nq + 1), meta + x->nq, x->nq, x->npos, x->ws.k, x->ws.L, (const K*)x->rkeys.p, x->nkR,
-                     x->has_tab ? (const uint32_t*)x->tab.p : (const uint32_t*)nullptr, (uint32_t*)x->qid.p, (uint32_t*)x->lo.p,
-                     (uint64_t*)x->cnt.p, (int*)((unsigned long long*)x->scalar.p + 1));
+  const int64_t* meta = x->meta.p;                                 // [offsets nq | pstart nq + 1 | lengths nq (int32)]
+  hipLaunchKernelGGL((k_qmatch<K>), rows_grid((uint64_t)x->npos), kBlock256, 0, st, arena, meta, (const int32_t*)(meta + 2 * x->nq + 1),
+                     meta + x->nq, x->nq, x->npos, x->ws.k, x->ws.L, x->rkeys.as<const K>(), x->nkR, x->has_tab ? x->tab.p : nullptr,
+                     x->qid.p, x->lo.p, x->cnt.p, bad_letter_flag(x));
 }
 
 template <typename K>
 static void launch_match_stranded(pw_qseed_index* x, const uint8_t* arena, hipStream_t st) {
-  const int64_t* meta = (const int64_t*)x->meta.p;                 // [... | strands nq (uint8)] behind launch_match's block
+  const int64_t* meta = x->meta.p;                                 // [... | strands nq (uint8)] behind launch_match's block
   const int32_t* dlen = (const int32_t*)(meta + 2 * x->nq + 1);
-  hipLaunchKernelGGL((k_qmatch_stranded<K>), dim3((unsigned)((x->npos + 255) / 256)), dim3(256), 0, st, arena, meta, dlen, meta + x->nq,
-                     (const uint8_t*)(meta + 2 * x->nq + 1 + (x->nq + 1) / 2 + 1), (const uint8_t*)x->comp.p, x->nq, x->npos, x->ws.k, x->ws.L,
-                     (const K*)x->rkeys.p, x->nkR, x->has_tab ? (const uint32_t*)x->tab.p : (const uint32_t*)nullptr, (uint32_t*)x->qid.p,
-                     (uint32_t*)x->lo.p, (uint64_t*)x->cnt.p, (int*)((unsigned long long*)x->scalar.p + 1));
+  hipLaunchKernelGGL((k_qmatch_stranded<K>), rows_grid((uint64_t)x->npos), kBlock256, 0, st, arena, meta, dlen, meta + x->nq,
+                     (const uint8_t*)(meta + 2 * x->nq + 1 + (x->nq + 1) / 2 + 1), x->comp.p, x->nq, x->npos, x->ws.k, x->ws.L,
+                     x->rkeys.as<const K>(), x->nkR, x->has_tab ? x->tab.p : nullptr, x->qid.p, x->lo.p, x->cnt.p, bad_letter_flag(x));
 }
 
 // both build entry points.  strand == nullptr: pw_qseeds_build, every query as given, the complement is not read.
@@ -360,45 +362,44 @@ static int build_queries(pw_qseed_index* x, const uint8_t* arena, uint64_t arena
   }
   meta[(size_t)(2 * nq)] = npos;
   CHECK(hipSetDevice(x->device));
-  CHECK(x->meta.ensure(meta.size() * 8));
-  CHECK(x->row_off.ensure((size_t)(nq + 1) * 8));
+  CHECK(x->meta.ensure(meta.size()));
+  CHECK(x->row_off.ensure((size_t)nq + 1));
   if (any_minus && upload_complement(set_err, complement, x->ws.L, x->comp) != 0) return -1;
   CHECK(hipEventRecord(x->ev0.e, st));            // (the build's time includes its copies to the device)
   const uint8_t* darena = arena;
   if (!arena_on_device) {
     CHECK(x->arena.ensure((size_t)arena_bytes + 64));
-    if (arena_bytes) CHECK(hipMemcpyAsync(x->arena.p, arena, (size_t)arena_bytes, hipMemcpyHostToDevice, st));
-    darena = (const uint8_t*)x->arena.p;
+    if (upload(set_err, x->arena, arena, (size_t)arena_bytes, st) != 0) return -1;
+    darena = x->arena.p;
   }
-  CHECK(hipMemcpyAsync(x->meta.p, meta.data(), meta.size() * 8, hipMemcpyHostToDevice, st));
-  CHECK(hipMemsetAsync(x->scalar.p, 0, 16, st));
+  if (upload(set_err, x->meta, meta.data(), meta.size(), st) != 0) return -1;
+  CHECK(hipMemsetAsync(x->scalar.p, 0, x->scalar.bytes(2), st));
   x->npos = npos; x->max_qlen = max_qlen;
   const size_t np1 = (size_t)std::max<int64_t>(npos, 1);
-  CHECK(x->qid.ensure(np1 * 4)); CHECK(x->lo.ensure(np1 * 4)); CHECK(x->cnt.ensure(np1 * 8)); CHECK(x->off.ensure(np1 * 8));
+  CHECK(x->qid.ensure(np1)); CHECK(x->lo.ensure(np1)); CHECK(x->cnt.ensure(np1)); CHECK(x->off.ensure(np1));
   x->nq = nq;                                     // (launch_match reads it; reset below on failure)
   if (npos > 0) {
     if (!any_minus) { if (x->ws.key32) launch_match<uint32_t>(x, darena, st); else launch_match<uint64_t>(x, darena, st); }
     else if (x->ws.key32) launch_match_stranded<uint32_t>(x, darena, st);
     else launch_match_stranded<uint64_t>(x, darena, st);
     CHECK(rocprim_run(x->tmp, [&](void* t, size_t& b) {
-      return rocprim::exclusive_scan(t, b, (const uint64_t*)x->cnt.p, (uint64_t*)x->off.p, (uint64_t)0, (size_t)npos, SatAdd(), st);
+      return rocprim::exclusive_scan(t, b, x->cnt.cp(), x->off.p, (uint64_t)0, (size_t)npos, SatAdd(), st);
     }));
   }
-  const int64_t* dmeta = (const int64_t*)x->meta.p;
-  hipLaunchKernelGGL(k_qoffsets, dim3((unsigned)((nq + 256) / 256)), dim3(256), 0, st, (const uint64_t*)x->off.p, (const uint64_t*)x->cnt.p,
-                     npos, dmeta + nq, nq, (unsigned long long*)x->scalar.p, (uint64_t*)x->row_off.p);
+  const int64_t* dmeta = x->meta.p;
+  hipLaunchKernelGGL(k_qoffsets, rows_grid((uint64_t)nq + 1), kBlock256, 0, st, x->off.p, x->cnt.p, npos, dmeta + nq, nq, x->scalar.p,
+                     x->row_off.p);
   unsigned long long res[2] = {0, 0};             // row total, bad-letter flag
-  CHECK(hipMemcpyAsync(res, x->scalar.p, 16, hipMemcpyDeviceToHost, st));
+  CHECK(hipMemcpyAsync(res, x->scalar.p, sizeof res, hipMemcpyDeviceToHost, st));
   CHECK(hipStreamSynchronize(st));
   x->nq = -1;
   if ((int)res[1] != 0) { set_err("letter outside the alphabet in a query"); return -1; }
   const unsigned long long total = res[0];
   if (check_row_limit(set_err, total, max_rows) != 0) return -1;
-  CHECK(x->rows.ensure((size_t)std::max<unsigned long long>(total, 1) * 12));
+  CHECK(x->rows.ensure((size_t)std::max<unsigned long long>(total, 1) * 3));
   if (total > 0)
-    hipLaunchKernelGGL(k_qexpand, dim3((unsigned)((total + kExpRows - 1) / kExpRows)), dim3(256), 0, st, (const uint64_t*)x->off.p, npos,
-                       (int64_t)total, (const uint32_t*)x->qid.p, dmeta + nq, (const uint32_t*)x->lo.p, (const uint32_t*)x->rpos.p,
-                       (int32_t*)x->rows.p);
+    hipLaunchKernelGGL(k_qexpand, dim3((unsigned)((total + kExpRows - 1) / kExpRows)), kBlock256, 0, st, x->off.p, npos, (int64_t)total,
+                       x->qid.p, dmeta + nq, x->lo.p, x->rpos.p, x->rows.p);
   if (elapsed(set_err, x->ev0, x->ev1, st, &x->ms_build) != 0) return -1;
   x->nq = nq; x->nrows = (int64_t)total;
   return 0;
@@ -418,7 +419,7 @@ pw_qseed_index* pw_qseeds_create(int device, const uint8_t* ref, int64_t n_ref, 
   pw_qseed_index* x = new pw_qseed_index();
   x->device = device; x->ws = ws;
   x->nR = n_ref; x->nkR = n_ref >= wordlen ? n_ref - wordlen + 1 : 0;
-  if (x->dref.ensure((size_t)n_ref + 64) != hipSuccess || x->scalar.ensure(16) != hipSuccess || x->ev0.create() != hipSuccess ||
+  if (x->dref.ensure((size_t)n_ref + 64) != hipSuccess || x->scalar.ensure(2) != hipSuccess || x->ev0.create() != hipSuccess ||
       x->ev1.create() != hipSuccess) {
     set_err("device allocation failed"); delete x; return nullptr;
   }
@@ -442,7 +443,7 @@ int pw_qseeds_build_stranded(pw_qseed_index* x, const uint8_t* arena, uint64_t a
 
 int64_t pw_qseeds_num_queries(const pw_qseed_index* x) { return x ? x->nq : -1; }
 int64_t pw_qseeds_num_rows(const pw_qseed_index* x) { return x ? x->nrows : -1; }
-const int32_t* pw_qseeds_rows_device(const pw_qseed_index* x) { return (x && x->nrows >= 0) ? (const int32_t*)x->rows.p : nullptr; }
+const int32_t* pw_qseeds_rows_device(const pw_qseed_index* x) { return (x && x->nrows >= 0) ? x->rows.p : nullptr; }
 double pw_qseeds_build_ms(const pw_qseed_index* x) { return x ? (double)x->ms_build : -1.0; }
 double pw_qseeds_graph_ms(const pw_qseed_index* x) { return x ? (double)x->ms_graph : -1.0; }
 double pw_qseeds_components_ms(const pw_qseed_index* x) { return x ? (double)x->ms_cc : -1.0; }
@@ -453,14 +454,14 @@ int pw_qseeds_rows(const pw_qseed_index* x, int32_t* rows, int64_t cap) {
   if (!x || x->nrows < 0) { set_err("pw_qseeds_rows before a successful pw_qseeds_build"); return -1; }
   if (cap < x->nrows) { set_err("pw_qseeds_rows: capacity too small"); return -1; }
   CHECK(hipSetDevice(x->device));
-  if (x->nrows) CHECK(hipMemcpy(rows, x->rows.p, (size_t)x->nrows * 12, hipMemcpyDeviceToHost));
+  if (x->nrows) CHECK(hipMemcpy(rows, x->rows.p, x->rows.bytes((size_t)x->nrows * 3), hipMemcpyDeviceToHost));
   return 0;
 }
 
 int pw_qseeds_row_offsets(const pw_qseed_index* x, int64_t* row_offsets) {
   if (!x || x->nrows < 0) { set_err("pw_qseeds_row_offsets before a successful pw_qseeds_build"); return -1; }
   CHECK(hipSetDevice(x->device));
-  CHECK(hipMemcpy(row_offsets, x->row_off.p, (size_t)(x->nq + 1) * 8, hipMemcpyDeviceToHost));
+  CHECK(hipMemcpy(row_offsets, x->row_off.p, x->row_off.bytes((size_t)x->nq + 1), hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -476,17 +477,16 @@ int pw_qseeds_count_boxes(const pw_qseed_index* xc, int64_t n_boxes, const int32
   const size_t nb = (size_t)n_boxes;
   std::vector<int32_t> h(nb * 5);                 // the five bound arrays in one block: one copy to the device
   const int32_t* src[5] = {q, dmin, dmax, amin, amax};
-  for (int f = 0; f < 5; f++) memcpy(h.data() + f * nb, src[f], nb * 4);
-  DeviceBuffer dbox, dcnt;
-  CHECK(dbox.ensure(nb * 20)); CHECK(dcnt.ensure(nb * 8));
-  CHECK(hipMemcpy(dbox.p, h.data(), nb * 20, hipMemcpyHostToDevice));
+  for (int f = 0; f < 5; f++) memcpy(h.data() + f * nb, src[f], nb * sizeof(int32_t));
+  DeviceArray<int32_t> dbox; DeviceArray<unsigned long long> dcnt;
+  CHECK(dbox.ensure(h.size())); CHECK(dcnt.ensure(nb));
+  if (upload(set_err, dbox, h.data(), h.size()) != 0) return -1;
   CHECK(hipEventRecord(x->ev0.e, nullptr));
-  const int32_t* d = (const int32_t*)dbox.p;
-  hipLaunchKernelGGL(k_qcount, dim3((unsigned)((n_boxes + 3) / 4)), dim3(256), 0, nullptr, (const int32_t*)x->rows.p,
-                     (const uint64_t*)x->row_off.p, x->nq, n_boxes, d, d + nb, d + 2 * nb, d + 3 * nb, d + 4 * nb,
-                     (unsigned long long*)dcnt.p);
+  const int32_t* d = dbox.p;
+  hipLaunchKernelGGL(k_qcount, dim3((unsigned)((n_boxes + 3) / 4)), kBlock256, 0, nullptr, x->rows.p, x->row_off.p, x->nq, n_boxes, d, d + nb,
+                     d + 2 * nb, d + 3 * nb, d + 4 * nb, dcnt.p);
   if (elapsed(set_err, x->ev0, x->ev1, nullptr, &x->ms_count) != 0) return -1;
-  CHECK(hipMemcpy(counts, dcnt.p, nb * 8, hipMemcpyDeviceToHost));
+  CHECK(hipMemcpy(counts, dcnt.p, dcnt.bytes(nb), hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -515,18 +515,16 @@ int64_t pw_qseeds_graph_build(pw_qseed_index* x, double d_coeff, double radius) 
   CHECK(hipEventRecord(x->ev0.e, nullptr));
   const double wd = floor(radius / d_coeff) + 2;
   const int win = wd > (double)nd ? (int)nd : (int)wd;
-  DeviceBuffer kin, vin;
-  CHECK(kin.ensure((size_t)n * 8)); CHECK(vin.ensure((size_t)n * 4));
-  const dim3 grid((unsigned)((n + 255) / 256)), blk(256);
-  hipLaunchKernelGGL(k_qgraph_keys, grid, blk, 0, nullptr, (const int32_t*)x->rows.p, n, kl, (uint64_t*)kin.p, (uint32_t*)vin.p);
+  DeviceArray<uint64_t> kin; DeviceArray<uint32_t> vin;      // kin: the sort keys, then graph_finish's widened counts
+  CHECK(kin.ensure((size_t)n)); CHECK(vin.ensure((size_t)n));
+  const dim3 grid = rows_grid((uint64_t)n), blk = kBlock256;
+  hipLaunchKernelGGL(k_qgraph_keys, grid, blk, 0, nullptr, x->rows.p, n, kl, kin.p, vin.p);
   if (graph_sort(set_err, g, x->tmp, kin, vin, n, qbits + kl.dbits + kl.abits) != 0) return -1;
-  hipLaunchKernelGGL((k_qgraph_scan<false>), grid, blk, 0, nullptr, (const uint64_t*)g.keys.p, (const uint32_t*)g.order.p, n,
-                     (const uint64_t*)x->row_off.p, kl, (int)nd, d_coeff, radius, win, (uint32_t*)g.cnt.p, (const uint64_t*)nullptr,
-                     (uint32_t*)nullptr);
-  const int64_t total = graph_finish(set_err, g, x->tmp, x->scalar, (uint64_t*)kin.p, n, [&] {
-    hipLaunchKernelGGL((k_qgraph_scan<true>), grid, blk, 0, nullptr, (const uint64_t*)g.keys.p, (const uint32_t*)g.order.p, n,
-                       (const uint64_t*)x->row_off.p, kl, (int)nd, d_coeff, radius, win, (uint32_t*)nullptr, (const uint64_t*)g.off.p,
-                       (uint32_t*)g.adj.p);
+  hipLaunchKernelGGL((k_qgraph_scan<false>), grid, blk, 0, nullptr, g.keys.p, g.order.p, n, x->row_off.p, kl, (int)nd, d_coeff, radius, win,
+                     g.cnt.p, (const uint64_t*)nullptr, (uint32_t*)nullptr);
+  const int64_t total = graph_finish(set_err, g, x->tmp, x->scalar, kin.p, n, [&] {
+    hipLaunchKernelGGL((k_qgraph_scan<true>), grid, blk, 0, nullptr, g.keys.p, g.order.p, n, x->row_off.p, kl, (int)nd, d_coeff, radius, win,
+                       (uint32_t*)nullptr, g.off.p, g.adj.p);
     return 0;
   });
   if (total < 0) return -1;

@@ -4,7 +4,8 @@
 // neighbourhood graph from its sorted points on -- CSR tail, read-backs, connected components.  Everything lives in an
 // anonymous namespace and reports through `sink`, as PW_HIP_CHECK does: each translation unit keeps its own thread_local
 // error channel.  The functions that take a handle `x` read its `device` and its SeedGraph `g` (the components its two
-// events as well).
+// events as well).  Device memory is typed (DeviceArray<T>, pw_hip_host.h); only the k-mer keys, 4 or 8 bytes wide by
+// WordSpace::key32, and rocPRIM's scratch are DeviceBuffers: the function templates on the key type K name the type at the use.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -76,17 +77,16 @@ int check_row_limit(ErrSink sink, unsigned long long total, int64_t max_rows) {
 // one), the caller's staging buffers to nk: a caller that fills one buffer piece by piece sizes all of them first.
 template <typename K>
 int encode_sort(ErrSink sink, const WordSpace& ws, const MaskSets& ms, const uint8_t* seq, int64_t n, int64_t nk,
-                DeviceBuffer& keys_in, DeviceBuffer& pos_in, DeviceBuffer& tmp, DeviceBuffer& keys_out, DeviceBuffer& pos_out,
-                int64_t at, hipStream_t st) {
+                DeviceBuffer& keys_in, DeviceArray<uint32_t>& pos_in, DeviceBuffer& tmp, DeviceBuffer& keys_out,
+                DeviceArray<uint32_t>& pos_out, int64_t at, hipStream_t st) {
   const size_t nout = (size_t)std::max<int64_t>(at + std::max<int64_t>(nk, 0), 1);
-  PW_HIP_CHECK(sink, keys_out.ensure(nout * sizeof(K))); PW_HIP_CHECK(sink, pos_out.ensure(nout * 4));
+  PW_HIP_CHECK(sink, keys_out.ensure(nout * sizeof(K))); PW_HIP_CHECK(sink, pos_out.ensure(nout));
   if (nk <= 0) return 0;
-  PW_HIP_CHECK(sink, keys_in.ensure((size_t)nk * sizeof(K))); PW_HIP_CHECK(sink, pos_in.ensure((size_t)nk * 4));
-  hipLaunchKernelGGL((k_encode<K>), dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, st, seq, n, ws.k, ws.L, ws.kinv, ms,
-                     (K*)keys_in.p, (uint32_t*)pos_in.p);
+  PW_HIP_CHECK(sink, keys_in.ensure((size_t)nk * sizeof(K))); PW_HIP_CHECK(sink, pos_in.ensure((size_t)nk));
+  hipLaunchKernelGGL((k_encode<K>), rows_grid((uint64_t)nk), kBlock256, 0, st, seq, n, ws.k, ws.L, ws.kinv, ms, keys_in.as<K>(), pos_in.p);
   PW_HIP_CHECK(sink, rocprim_run(tmp, [&](void* t, size_t& b) {
-    return rocprim::radix_sort_pairs(t, b, (const K*)keys_in.p, (K*)keys_out.p + at, (const uint32_t*)pos_in.p, (uint32_t*)pos_out.p + at,
-                                     (size_t)nk, 0u, (unsigned)ws.bits, st);
+    return rocprim::radix_sort_pairs(t, b, keys_in.as<const K>(), keys_out.as<K>() + at, pos_in.cp(), pos_out.p + at, (size_t)nk, 0u,
+                                     (unsigned)ws.bits, st);
   }));
   return 0;
 }
@@ -98,16 +98,16 @@ bool table_pays(const WordSpace& ws, int64_t n_other) {
   return ws.key32 && n_other > 0 && ws.kinv <= (1ull << 26) && ws.kinv / (uint64_t)n_other <= 64;
 }
 template <typename K>
-int table_fill(ErrSink sink, const WordSpace& ws, const K* other, int64_t n_other, DeviceBuffer& tab, hipStream_t st) {
-  PW_HIP_CHECK(sink, tab.ensure((size_t)(ws.kinv + 2) * 4));
-  hipLaunchKernelGGL((k_table_fill<K>), dim3((unsigned)((n_other + 256) / 256)), dim3(256), 0, st, other, n_other, ws.kinv, (uint32_t*)tab.p);
+int table_fill(ErrSink sink, const WordSpace& ws, const K* other, int64_t n_other, DeviceArray<uint32_t>& tab, hipStream_t st) {
+  PW_HIP_CHECK(sink, tab.ensure((size_t)(ws.kinv + 2)));
+  hipLaunchKernelGGL((k_table_fill<K>), rows_grid((uint64_t)n_other + 1), kBlock256, 0, st, other, n_other, ws.kinv, tab.p);
   return 0;
 }
 
 // ---- the neighbourhood graph (K7, K9e, K10d) from its sorted points on --------------------------------------
 // keys / order: the points' sort keys, sorted, and the point each belongs to; cnt / off / adj: CSR (off 64-bit, n + 1
 // entries).  npts / edges: -1 until a graph_build has succeeded.
-struct SeedGraph { DeviceBuffer keys, order, cnt, off, adj; int64_t npts = -1, edges = -1; };
+struct SeedGraph { DeviceArray<uint64_t> keys, off; DeviceArray<uint32_t> order, cnt, adj; int64_t npts = -1, edges = -1; };
 
 std::string before_graph_build(const char* entry) {      // entry = "<api>_graph_<what>"
   const std::string s(entry);
@@ -116,12 +116,13 @@ std::string before_graph_build(const char* entry) {      // entry = "<api>_graph
 
 // The caller's n keys `kin` (values `vin`: the point numbers) sorted over `bits` bits into g.keys / g.order; the count
 // pass that follows writes g.cnt.  All on the null stream, as everything of the graph.
-int graph_sort(ErrSink sink, SeedGraph& g, DeviceBuffer& tmp, const DeviceBuffer& kin, const DeviceBuffer& vin, int64_t n, int bits) {
-  PW_HIP_CHECK(sink, g.keys.ensure((size_t)n * 8)); PW_HIP_CHECK(sink, g.order.ensure((size_t)n * 4));
-  PW_HIP_CHECK(sink, g.cnt.ensure((size_t)n * 4)); PW_HIP_CHECK(sink, g.off.ensure((size_t)(n + 1) * 8));
+int graph_sort(ErrSink sink, SeedGraph& g, DeviceBuffer& tmp, const DeviceArray<uint64_t>& kin, const DeviceArray<uint32_t>& vin, int64_t n,
+               int bits) {
+  PW_HIP_CHECK(sink, g.keys.ensure((size_t)n)); PW_HIP_CHECK(sink, g.order.ensure((size_t)n));
+  PW_HIP_CHECK(sink, g.cnt.ensure((size_t)n)); PW_HIP_CHECK(sink, g.off.ensure((size_t)n + 1));
   PW_HIP_CHECK(sink, rocprim_run(tmp, [&](void* t, size_t& b) {
-    return rocprim::radix_sort_pairs(t, b, (const uint64_t*)kin.p, (uint64_t*)g.keys.p, (const uint32_t*)vin.p, (uint32_t*)g.order.p,
-                                     (size_t)n, 0u, (unsigned)bits, (hipStream_t) nullptr);
+    return rocprim::radix_sort_pairs(t, b, kin.cp(), g.keys.p, vin.cp(), g.order.p, (size_t)n, 0u, (unsigned)bits,
+                                     (hipStream_t) nullptr);
   }));
   return 0;
 }
@@ -131,18 +132,18 @@ int graph_sort(ErrSink sink, SeedGraph& g, DeviceBuffer& tmp, const DeviceBuffer
 // -1 -- when there is an edge at all.  Returns the number of edges, which the caller records once its own synchronisation
 // has succeeded, or -1.  (Not a template on the callable: as an ordinary function it leaves the order in which a translation
 // unit's kernels are emitted, and so their fingerprints, as they were.)
-int64_t graph_finish(ErrSink sink, SeedGraph& g, DeviceBuffer& tmp, DeviceBuffer& scalar, uint64_t* wide, int64_t n,
+int64_t graph_finish(ErrSink sink, SeedGraph& g, DeviceBuffer& tmp, DeviceArray<unsigned long long>& scalar, uint64_t* wide, int64_t n,
                      const std::function<int()>& fill_pass) {
-  hipLaunchKernelGGL(k_widen, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, (const uint32_t*)g.cnt.p, n, wide);
+  hipLaunchKernelGGL(k_widen, rows_grid((uint64_t)n), kBlock256, 0, nullptr, g.cnt.p, n, wide);
   PW_HIP_CHECK(sink, rocprim_run(tmp, [&](void* t, size_t& b) {
-    return rocprim::exclusive_scan(t, b, (const uint64_t*)wide, (uint64_t*)g.off.p, (uint64_t)0, (size_t)n, rocprim::plus<uint64_t>(), (hipStream_t) nullptr);
+    return rocprim::exclusive_scan(t, b, (const uint64_t*)wide, g.off.p, (uint64_t)0, (size_t)n, rocprim::plus<uint64_t>(), (hipStream_t) nullptr);
   }));
-  hipLaunchKernelGGL(k_total, dim3(1), dim3(64), 0, nullptr, (const uint64_t*)g.off.p, (const uint64_t*)wide, n, (unsigned long long*)scalar.p);
+  hipLaunchKernelGGL(k_total, dim3(1), dim3(64), 0, nullptr, g.off.p, wide, n, scalar.p);
   unsigned long long total = 0;
-  PW_HIP_CHECK(sink, hipMemcpy(&total, scalar.p, 8, hipMemcpyDeviceToHost));
+  PW_HIP_CHECK(sink, hipMemcpy(&total, scalar.p, sizeof total, hipMemcpyDeviceToHost));
   if (total >= (1ull << 32)) { sink("the neighbourhood graph has more than 2^32 edges: use a smaller radius"); return -1; }
-  PW_HIP_CHECK(sink, hipMemcpy((uint64_t*)g.off.p + n, &total, 8, hipMemcpyHostToDevice));
-  PW_HIP_CHECK(sink, g.adj.ensure((size_t)std::max<unsigned long long>(total, 1) * 4));
+  PW_HIP_CHECK(sink, hipMemcpy(g.off.p + n, &total, sizeof total, hipMemcpyHostToDevice));
+  PW_HIP_CHECK(sink, g.adj.ensure((size_t)std::max<unsigned long long>(total, 1)));
   if (total && fill_pass() != 0) return -1;
   return (int64_t)total;
 }
@@ -152,7 +153,7 @@ int graph_counts_to_host(ErrSink sink, const char* entry, const X* x, int32_t* c
   if (!x || x->g.edges < 0) { sink(before_graph_build(entry)); return -1; }
   if (cap < x->g.npts) { sink(std::string(entry) + ": capacity too small"); return -1; }
   PW_HIP_CHECK(sink, hipSetDevice(x->device));
-  if (x->g.npts) PW_HIP_CHECK(sink, hipMemcpy(counts, x->g.cnt.p, (size_t)x->g.npts * 4, hipMemcpyDeviceToHost));
+  if (x->g.npts) PW_HIP_CHECK(sink, hipMemcpy(counts, x->g.cnt.p, x->g.cnt.bytes((size_t)x->g.npts), hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -161,8 +162,8 @@ int graph_fetch_to_host(ErrSink sink, const char* entry, const X* x, int64_t* of
   if (!x || x->g.edges < 0) { sink(before_graph_build(entry)); return -1; }
   PW_HIP_CHECK(sink, hipSetDevice(x->device));
   if (x->g.npts == 0) { offsets[0] = 0; return 0; }
-  PW_HIP_CHECK(sink, hipMemcpy(offsets, x->g.off.p, (size_t)(x->g.npts + 1) * 8, hipMemcpyDeviceToHost));
-  if (x->g.edges) PW_HIP_CHECK(sink, hipMemcpy(neighbours, x->g.adj.p, (size_t)x->g.edges * 4, hipMemcpyDeviceToHost));
+  PW_HIP_CHECK(sink, hipMemcpy(offsets, x->g.off.p, x->g.off.bytes((size_t)x->g.npts + 1), hipMemcpyDeviceToHost));
+  if (x->g.edges) PW_HIP_CHECK(sink, hipMemcpy(neighbours, x->g.adj.p, x->g.adj.bytes((size_t)x->g.edges), hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -177,24 +178,23 @@ int graph_components(ErrSink sink, const char* entry, const X* x, const uint8_t*
   if (rounds) *rounds = 0;
   if (n == 0) return 0;
   PW_HIP_CHECK(sink, hipSetDevice(x->device));
-  DeviceBuffer av, par, flag;
-  PW_HIP_CHECK(sink, av.ensure((size_t)n)); PW_HIP_CHECK(sink, par.ensure((size_t)n * 4)); PW_HIP_CHECK(sink, flag.ensure(16));
-  PW_HIP_CHECK(sink, hipMemcpy(av.p, avail, (size_t)n, hipMemcpyHostToDevice));
+  DeviceArray<uint8_t> av; DeviceArray<int> par, flag;
+  if (upload(sink, av, avail, (size_t)n) != 0) return -1;
+  PW_HIP_CHECK(sink, par.ensure((size_t)n)); PW_HIP_CHECK(sink, flag.ensure(1));
   if (ms) PW_HIP_CHECK(sink, hipEventRecord(x->ev0.e, nullptr));
-  const dim3 grid((unsigned)((n + 255) / 256)), blk(256);
-  hipLaunchKernelGGL(k_cc_init, grid, blk, 0, nullptr, (const uint8_t*)av.p, n, (int*)par.p);
+  const dim3 grid = rows_grid((uint64_t)n), blk = kBlock256;
+  hipLaunchKernelGGL(k_cc_init, grid, blk, 0, nullptr, av.p, n, par.p);
   for (int it = 0; it < 10000; it++) {            // every round at least halves the number of roots still to merge
-    PW_HIP_CHECK(sink, hipMemsetAsync(flag.p, 0, 4, nullptr));
-    hipLaunchKernelGGL(k_cc_hook, grid, blk, 0, nullptr, (const uint64_t*)g.off.p, (const uint32_t*)g.cnt.p, (const uint32_t*)g.adj.p, n,
-                       (int*)par.p, (int*)flag.p);
-    hipLaunchKernelGGL(k_cc_compress, grid, blk, 0, nullptr, n, (int*)par.p);
+    PW_HIP_CHECK(sink, hipMemsetAsync(flag.p, 0, flag.bytes(1), nullptr));
+    hipLaunchKernelGGL(k_cc_hook, grid, blk, 0, nullptr, g.off.p, g.cnt.p, g.adj.p, n, par.p, flag.p);
+    hipLaunchKernelGGL(k_cc_compress, grid, blk, 0, nullptr, n, par.p);
     int changed = 0;
-    PW_HIP_CHECK(sink, hipMemcpy(&changed, flag.p, 4, hipMemcpyDeviceToHost));
+    PW_HIP_CHECK(sink, hipMemcpy(&changed, flag.p, sizeof changed, hipMemcpyDeviceToHost));
     if (rounds) *rounds = it + 1;
     if (!changed) break;
   }
   if (ms && elapsed(sink, x->ev0, x->ev1, nullptr, ms) != 0) return -1;
-  PW_HIP_CHECK(sink, hipMemcpy(labels, par.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+  PW_HIP_CHECK(sink, hipMemcpy(labels, par.p, par.bytes((size_t)n), hipMemcpyDeviceToHost));
   return 0;
 }
 

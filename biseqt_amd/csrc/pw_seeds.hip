@@ -198,12 +198,14 @@ __global__ __launch_bounds__(256) void k_graph_scan(const uint64_t* __restrict__
 struct pw_seed_index {
   int device = 0, self = 0;
   WordSpace ws;
-  DeviceBuffer tab;                     // direct-address table of the join (small key spaces)
+  DeviceArray<uint32_t> tab;            // direct-address table of the join (small key spaces)
   int64_t nS = 0, nT = 0, nkS = 0, nkT = 0, nrows = -1;
   MaskSets ms;
-  DeviceBuffer dS, dT, keys_in, keys_s, keys_t, pos_in, pos_s, pos_t, lo, cnt, off, rows, tmp, scalar;
+  DeviceArray<uint8_t> dS, dT; DeviceBuffer keys_in, keys_s, keys_t, tmp;      // (the keys: uint32_t or uint64_t by ws.key32; rocPRIM's scratch)
+  DeviceArray<uint32_t> pos_in, pos_s, pos_t, lo; DeviceArray<uint64_t> cnt, off; DeviceArray<int2> rows;
+  DeviceArray<unsigned long long> scalar;         // [the row total | pw_seeds_count's counter]
   SeedGraph g;                          // neighbourhood graph (K7); g.npts: the rows, or the mirrored non-trivial rows of a self comparison
-  DeviceBuffer g_dstart, g_pts;
+  DeviceArray<uint32_t> g_dstart; DeviceArray<int2> g_pts;
   DeviceEvent ev0, ev1;
   float ms_build = 0.f;
 };
@@ -213,37 +215,34 @@ template <typename K>
 static int build_join(pw_seed_index* x, hipStream_t st, int64_t ns, bool count_only, unsigned long long total) {
   const WordSpace& ws = x->ws;
   if (count_only) {
-    if (encode_sort<K>(set_err, ws, x->ms, (const uint8_t*)x->dS.p, x->nS, x->nkS, x->keys_in, x->pos_in, x->tmp, x->keys_s, x->pos_s, 0, st) != 0)
+    if (encode_sort<K>(set_err, ws, x->ms, x->dS.p, x->nS, x->nkS, x->keys_in, x->pos_in, x->tmp, x->keys_s, x->pos_s, 0, st) != 0)
       return -1;
-    if (!x->self &&
-        encode_sort<K>(set_err, ws, x->ms, (const uint8_t*)x->dT.p, x->nT, x->nkT, x->keys_in, x->pos_in, x->tmp, x->keys_t, x->pos_t, 0, st) != 0)
+    if (!x->self && encode_sort<K>(set_err, ws, x->ms, x->dT.p, x->nT, x->nkT, x->keys_in, x->pos_in, x->tmp, x->keys_t, x->pos_t, 0, st) != 0)
       return -1;
     if (ns <= 0) return 0;
-    const K* other = x->self ? (const K*)x->keys_s.p : (const K*)x->keys_t.p;
+    const K* other = x->self ? x->keys_s.as<const K>() : x->keys_t.as<const K>();
     const int64_t no = x->self ? ns : x->nkT;
     const uint32_t* tab = nullptr;
     if (table_pays(ws, no)) {
       if (table_fill<K>(set_err, ws, other, no, x->tab, st) != 0) return -1;
-      tab = (const uint32_t*)x->tab.p;
+      tab = x->tab.p;
     }
-    hipLaunchKernelGGL((k_match<K>), dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, st, (const K*)x->keys_s.p, ns,
-                       other, no, ws.kinv, x->self, tab, (uint32_t*)x->lo.p, (uint64_t*)x->cnt.p);
+    hipLaunchKernelGGL((k_match<K>), rows_grid((uint64_t)ns), kBlock256, 0, st, x->keys_s.as<const K>(), ns, other, no, ws.kinv, x->self, tab,
+                       x->lo.p, x->cnt.p);
     return 0;
   }
-  hipLaunchKernelGGL((k_expand<K>), dim3((unsigned)((total + kExpRows - 1) / kExpRows)), dim3(256), 0, st, (const uint64_t*)x->off.p, ns,
-                     (int64_t)total, (const uint32_t*)x->pos_s.p,
-                     x->self ? (const uint32_t*)x->pos_s.p : (const uint32_t*)x->pos_t.p, (const uint32_t*)x->lo.p,
-                     (const K*)x->keys_s.p, x->self, (int2*)x->rows.p);
+  hipLaunchKernelGGL((k_expand<K>), dim3((unsigned)((total + kExpRows - 1) / kExpRows)), kBlock256, 0, st, x->off.p, ns, (int64_t)total,
+                     x->pos_s.p, x->self ? x->pos_s.p : x->pos_t.p, x->lo.p, x->keys_s.as<const K>(), x->self, x->rows.p);
   return 0;
 }
 
-// the device copies of S and T, and the events that time pw_seeds_build
-static int upload(pw_seed_index* x, const uint8_t* S, const uint8_t* T) {
+// the device copies of S and T (64 bytes of slack behind each), and the events that time pw_seeds_build
+static int to_device(pw_seed_index* x, const uint8_t* S, const uint8_t* T) {
   CHECK(x->dS.ensure((size_t)x->nS + 64));
-  if (x->nS) CHECK(hipMemcpy(x->dS.p, S, (size_t)x->nS, hipMemcpyHostToDevice));
+  if (upload(set_err, x->dS, S, (size_t)x->nS) != 0) return -1;
   if (!x->self) {
     CHECK(x->dT.ensure((size_t)x->nT + 64));
-    if (x->nT) CHECK(hipMemcpy(x->dT.p, T, (size_t)x->nT, hipMemcpyHostToDevice));
+    if (upload(set_err, x->dT, T, (size_t)x->nT) != 0) return -1;
   }
   CHECK(x->ev0.create()); CHECK(x->ev1.create());
   return 0;
@@ -272,7 +271,7 @@ pw_seed_index* pw_seeds_create(int device, const uint8_t* S, int64_t nS, const u
   x->nkT = self_comp ? x->nkS : (nT >= wordlen ? nT - wordlen + 1 : 0);
   x->ms.n = n_masks;
   for (int i = 0; i < kMaxMasks; i++) x->ms.set[i] = i < n_masks ? mask_sets[i] : 0;
-  if (upload(x, S, T) != 0) { delete x; return nullptr; }
+  if (to_device(x, S, T) != 0) { delete x; return nullptr; }
   return x;
 }
 
@@ -284,21 +283,20 @@ int pw_seeds_build(pw_seed_index* x, int64_t max_rows, void* stream) {
   x->nrows = -1; x->g.edges = -1; x->g.npts = -1;
   CHECK(hipEventRecord(x->ev0.e, st));
   const int64_t ns = x->nkS;
-  CHECK(x->scalar.ensure(16));
-  if (ns > 0) { CHECK(x->lo.ensure((size_t)ns * 4)); CHECK(x->cnt.ensure((size_t)ns * 8)); CHECK(x->off.ensure((size_t)ns * 8)); }
+  CHECK(x->scalar.ensure(2));
+  if (ns > 0) { CHECK(x->lo.ensure((size_t)ns)); CHECK(x->cnt.ensure((size_t)ns)); CHECK(x->off.ensure((size_t)ns)); }
   if ((x->ws.key32 ? build_join<uint32_t>(x, st, ns, true, 0) : build_join<uint64_t>(x, st, ns, true, 0)) != 0) return -1;
   unsigned long long total = 0;
   if (ns > 0) {
     CHECK(rocprim_run(x->tmp, [&](void* t, size_t& b) {
-      return rocprim::exclusive_scan(t, b, (const uint64_t*)x->cnt.p, (uint64_t*)x->off.p, (uint64_t)0, (size_t)ns, rocprim::plus<uint64_t>(), st);
+      return rocprim::exclusive_scan(t, b, x->cnt.cp(), x->off.p, (uint64_t)0, (size_t)ns, rocprim::plus<uint64_t>(), st);
     }));
-    hipLaunchKernelGGL(k_total, dim3(1), dim3(64), 0, st, (const uint64_t*)x->off.p, (const uint64_t*)x->cnt.p, ns,
-                       (unsigned long long*)x->scalar.p);
-    CHECK(hipMemcpyAsync(&total, x->scalar.p, 8, hipMemcpyDeviceToHost, st));
+    hipLaunchKernelGGL(k_total, dim3(1), dim3(64), 0, st, x->off.p, x->cnt.p, ns, x->scalar.p);
+    CHECK(hipMemcpyAsync(&total, x->scalar.p, sizeof total, hipMemcpyDeviceToHost, st));
     CHECK(hipStreamSynchronize(st));
   }
   if (check_row_limit(set_err, total, max_rows) != 0) return -1;    // (a sum of at most nS * nT: never saturated)
-  CHECK(x->rows.ensure((size_t)std::max<unsigned long long>(total, 1) * 8));
+  CHECK(x->rows.ensure((size_t)std::max<unsigned long long>(total, 1)));
   if (total > 0 && (x->ws.key32 ? build_join<uint32_t>(x, st, ns, false, total) : build_join<uint64_t>(x, st, ns, false, total)) != 0) return -1;
   if (elapsed(set_err, x->ev0, x->ev1, st, &x->ms_build) != 0) return -1;
   x->nrows = (int64_t)total;
@@ -307,7 +305,7 @@ int pw_seeds_build(pw_seed_index* x, int64_t max_rows, void* stream) {
 
 int64_t pw_seeds_num_rows(const pw_seed_index* x) { return x ? x->nrows : -1; }
 int pw_seeds_is_self(const pw_seed_index* x) { return x ? x->self : -1; }
-const int32_t* pw_seeds_rows_device(const pw_seed_index* x) { return (x && x->nrows >= 0) ? (const int32_t*)x->rows.p : nullptr; }
+const int32_t* pw_seeds_rows_device(const pw_seed_index* x) { return (x && x->nrows >= 0) ? x->rows.as<const int32_t>() : nullptr; }
 double pw_seeds_build_ms(const pw_seed_index* x) { return x ? (double)x->ms_build : -1.0; }
 int64_t pw_seeds_algorithmic_bytes(const pw_seed_index* x) {
   if (!x || x->nrows < 0) return -1;
@@ -318,7 +316,7 @@ int pw_seeds_rows(const pw_seed_index* x, int32_t* da, int64_t cap) {
   if (!x || x->nrows < 0) { set_err("pw_seeds_rows before a successful pw_seeds_build"); return -1; }
   if (cap < x->nrows) { set_err("pw_seeds_rows: capacity too small"); return -1; }
   CHECK(hipSetDevice(x->device));
-  if (x->nrows) CHECK(hipMemcpy(da, x->rows.p, (size_t)x->nrows * 8, hipMemcpyDeviceToHost));
+  if (x->nrows) CHECK(hipMemcpy(da, x->rows.p, x->rows.bytes((size_t)x->nrows), hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -328,13 +326,12 @@ int64_t pw_seeds_count(const pw_seed_index* x, int have_d, int32_t dmin, int32_t
   if (!have_d && !have_a) return x->nrows;
   if (x->nrows == 0) return 0;
   CHECK(hipSetDevice(x->device));
-  unsigned long long* out = (unsigned long long*)x->scalar.p + 1;
-  CHECK(hipMemsetAsync(out, 0, 8, nullptr));
+  unsigned long long* out = x->scalar.p + 1;
+  CHECK(hipMemsetAsync(out, 0, sizeof *out, nullptr));
   const int64_t blocks = std::min<int64_t>((x->nrows + 255) / 256, 256 * 16);
-  hipLaunchKernelGGL(k_count, dim3((unsigned)blocks), dim3(256), 0, nullptr, (const int2*)x->rows.p, x->nrows, have_d,
-                     dmin, dmax, have_a, amin, amax, out);
+  hipLaunchKernelGGL(k_count, dim3((unsigned)blocks), kBlock256, 0, nullptr, x->rows.p, x->nrows, have_d, dmin, dmax, have_a, amin, amax, out);
   unsigned long long c = 0;
-  CHECK(hipMemcpy(&c, out, 8, hipMemcpyDeviceToHost));
+  CHECK(hipMemcpy(&c, out, sizeof c, hipMemcpyDeviceToHost));
   return (int64_t)c;
 }
 
@@ -345,12 +342,12 @@ int64_t pw_seeds_kmers(const pw_seed_index* x, int which, int64_t* out, int64_t 
   if (cap < nk) { set_err("pw_seeds_kmers: capacity too small"); return -1; }
   if (nk <= 0) return 0;
   CHECK(hipSetDevice(x->device));
-  DeviceBuffer keys, pos;
-  CHECK(keys.ensure((size_t)nk * 8)); CHECK(pos.ensure((size_t)nk * 4));
-  hipLaunchKernelGGL((k_encode<uint64_t>), dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, nullptr,
-                     (const uint8_t*)(t ? x->dT.p : x->dS.p), n, x->ws.k, x->ws.L, x->ws.kinv, x->ms, (uint64_t*)keys.p, (uint32_t*)pos.p);
+  DeviceArray<uint64_t> keys; DeviceArray<uint32_t> pos;
+  CHECK(keys.ensure((size_t)nk)); CHECK(pos.ensure((size_t)nk));
+  hipLaunchKernelGGL((k_encode<uint64_t>), rows_grid((uint64_t)nk), kBlock256, 0, nullptr, t ? x->dT.p : x->dS.p, n, x->ws.k, x->ws.L,
+                     x->ws.kinv, x->ms, keys.p, pos.p);
   std::vector<uint64_t> h((size_t)nk);
-  CHECK(hipMemcpy(h.data(), keys.p, (size_t)nk * 8, hipMemcpyDeviceToHost));
+  CHECK(hipMemcpy(h.data(), keys.p, keys.bytes((size_t)nk), hipMemcpyDeviceToHost));
   for (int64_t i = 0; i < nk; i++) out[i] = h[(size_t)i] >= x->ws.kinv ? -1 : (int64_t)h[(size_t)i];
   return nk;
 }
@@ -365,16 +362,15 @@ int pw_seeds_band_neighbours(const pw_seed_index* xc, const double* radius, int6
   const int64_t n = x->nrows;
   if (n == 0) return 0;
   CHECK(hipSetDevice(x->device));
-  DeviceBuffer rad, xu, xs, cn;
-  CHECK(rad.ensure((size_t)n_radius * 8)); CHECK(xu.ensure((size_t)n * 8)); CHECK(xs.ensure((size_t)n * 8)); CHECK(cn.ensure((size_t)n * 4));
-  CHECK(hipMemcpy(rad.p, radius, (size_t)n_radius * 8, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(k_scale, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, (const int2*)x->rows.p, n,
-                     (const double*)rad.p, (int)x->nT, (double*)xu.p);
+  DeviceArray<double> rad, xu, xs; DeviceArray<int32_t> cn;
+  CHECK(rad.ensure((size_t)n_radius)); CHECK(xu.ensure((size_t)n)); CHECK(xs.ensure((size_t)n)); CHECK(cn.ensure((size_t)n));
+  if (upload(set_err, rad, radius, (size_t)n_radius) != 0) return -1;
+  hipLaunchKernelGGL(k_scale, rows_grid((uint64_t)n), kBlock256, 0, nullptr, x->rows.p, n, rad.p, (int)x->nT, xu.p);
   CHECK(rocprim_run(x->tmp, [&](void* t, size_t& b) {
-    return rocprim::radix_sort_keys(t, b, (const double*)xu.p, (double*)xs.p, (size_t)n, 0u, 64u, (hipStream_t) nullptr);
+    return rocprim::radix_sort_keys(t, b, xu.cp(), xs.p, (size_t)n, 0u, 64u, (hipStream_t) nullptr);
   }));
-  hipLaunchKernelGGL(k_neigh, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, (const double*)xu.p, (const double*)xs.p, n, (int32_t*)cn.p);
-  CHECK(hipMemcpy(counts, cn.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+  hipLaunchKernelGGL(k_neigh, rows_grid((uint64_t)n), kBlock256, 0, nullptr, xu.p, xs.p, n, cn.p);
+  CHECK(hipMemcpy(counts, cn.p, cn.bytes((size_t)n), hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -384,44 +380,42 @@ int64_t pw_seeds_graph_build(pw_seed_index* x, double d_coeff, double radius) {
   SeedGraph& g = x->g;
   g.edges = -1; g.npts = -1;
   CHECK(hipSetDevice(x->device));
-  const int2* pts = (const int2*)x->rows.p;
+  const int2* pts = x->rows.p;
   int64_t n = x->nrows;
   if (x->self && n > 0) {
     // the point list of a self comparison: non-trivial rows and their mirror images, in table order
-    DeviceBuffer flag, pos;                       // (freed at the end of this block)
-    CHECK(flag.ensure((size_t)n * 8)); CHECK(pos.ensure((size_t)n * 8));
-    const dim3 g((unsigned)((n + 255) / 256)), bl(256);
-    hipLaunchKernelGGL(k_self_flag, g, bl, 0, nullptr, (const int2*)x->rows.p, n, (uint64_t*)flag.p);
+    DeviceArray<uint64_t> flag, pos;              // (freed at the end of this block)
+    CHECK(flag.ensure((size_t)n)); CHECK(pos.ensure((size_t)n));
+    const dim3 g = rows_grid((uint64_t)n), bl = kBlock256;
+    hipLaunchKernelGGL(k_self_flag, g, bl, 0, nullptr, x->rows.p, n, flag.p);
     CHECK(rocprim_run(x->tmp, [&](void* t, size_t& b) {
-      return rocprim::exclusive_scan(t, b, (const uint64_t*)flag.p, (uint64_t*)pos.p, (uint64_t)0, (size_t)n, rocprim::plus<uint64_t>(), (hipStream_t) nullptr);
+      return rocprim::exclusive_scan(t, b, flag.cp(), pos.p, (uint64_t)0, (size_t)n, rocprim::plus<uint64_t>(), (hipStream_t) nullptr);
     }));
     uint64_t lp = 0, lf = 0;
-    CHECK(hipMemcpy(&lp, (uint64_t*)pos.p + (n - 1), 8, hipMemcpyDeviceToHost));
-    CHECK(hipMemcpy(&lf, (uint64_t*)flag.p + (n - 1), 8, hipMemcpyDeviceToHost));
+    CHECK(hipMemcpy(&lp, pos.p + (n - 1), sizeof lp, hipMemcpyDeviceToHost));
+    CHECK(hipMemcpy(&lf, flag.p + (n - 1), sizeof lf, hipMemcpyDeviceToHost));
     const int64_t np = (int64_t)(2 * (lp + lf));
-    CHECK(x->g_pts.ensure((size_t)std::max<int64_t>(np, 1) * 8));
-    hipLaunchKernelGGL(k_self_points, g, bl, 0, nullptr, (const int2*)x->rows.p, n, (const uint64_t*)pos.p, (int2*)x->g_pts.p);
+    CHECK(x->g_pts.ensure((size_t)std::max<int64_t>(np, 1)));
+    hipLaunchKernelGGL(k_self_points, g, bl, 0, nullptr, x->rows.p, n, pos.p, x->g_pts.p);
     CHECK(hipDeviceSynchronize());
-    pts = (const int2*)x->g_pts.p; n = np;
+    pts = x->g_pts.p; n = np;
   }
   g.npts = n;
   if (n == 0) { g.edges = 0; return 0; }
   const int64_t nd = x->nS + x->nT + 1;
   const double wd = floor(radius / d_coeff) + 2;
   const int win = wd > (double)nd ? (int)nd : (int)wd;
-  DeviceBuffer kin, vin;
-  CHECK(kin.ensure((size_t)n * 8)); CHECK(vin.ensure((size_t)n * 4)); CHECK(x->g_dstart.ensure((size_t)(nd + 1) * 4));
-  const dim3 grid((unsigned)((n + 255) / 256)), blk(256);
-  hipLaunchKernelGGL(k_graph_keys, grid, blk, 0, nullptr, pts, n, (int)x->nT, (uint64_t*)kin.p, (uint32_t*)vin.p);
+  DeviceArray<uint64_t> kin; DeviceArray<uint32_t> vin;      // kin: the sort keys, then graph_finish's widened counts
+  CHECK(kin.ensure((size_t)n)); CHECK(vin.ensure((size_t)n)); CHECK(x->g_dstart.ensure((size_t)nd + 1));
+  const dim3 grid = rows_grid((uint64_t)n), blk = kBlock256;
+  hipLaunchKernelGGL(k_graph_keys, grid, blk, 0, nullptr, pts, n, (int)x->nT, kin.p, vin.p);
   if (graph_sort(set_err, g, x->tmp, kin, vin, n, 32 + bits_for((uint64_t)nd)) != 0) return -1;
-  hipLaunchKernelGGL(k_graph_dstart, dim3((unsigned)((nd + 256) / 256)), blk, 0, nullptr, (const uint64_t*)g.keys.p, n, nd, (uint32_t*)x->g_dstart.p);
-  hipLaunchKernelGGL((k_graph_scan<false>), grid, blk, 0, nullptr, (const uint64_t*)g.keys.p, (const uint32_t*)g.order.p, n,
-                     (const uint32_t*)x->g_dstart.p, (int)nd, (int)x->nT, d_coeff, radius, win, (uint32_t*)g.cnt.p,
-                     (const uint64_t*)nullptr, (uint32_t*)nullptr);
-  const int64_t total = graph_finish(set_err, g, x->tmp, x->scalar, (uint64_t*)kin.p, n, [&] {
-    hipLaunchKernelGGL((k_graph_scan<true>), grid, blk, 0, nullptr, (const uint64_t*)g.keys.p, (const uint32_t*)g.order.p, n,
-                       (const uint32_t*)x->g_dstart.p, (int)nd, (int)x->nT, d_coeff, radius, win, (uint32_t*)nullptr,
-                       (const uint64_t*)g.off.p, (uint32_t*)g.adj.p);
+  hipLaunchKernelGGL(k_graph_dstart, rows_grid((uint64_t)nd + 1), blk, 0, nullptr, g.keys.p, n, nd, x->g_dstart.p);
+  hipLaunchKernelGGL((k_graph_scan<false>), grid, blk, 0, nullptr, g.keys.p, g.order.p, n, x->g_dstart.p, (int)nd, (int)x->nT, d_coeff, radius,
+                     win, g.cnt.p, (const uint64_t*)nullptr, (uint32_t*)nullptr);
+  const int64_t total = graph_finish(set_err, g, x->tmp, x->scalar, kin.p, n, [&] {
+    hipLaunchKernelGGL((k_graph_scan<true>), grid, blk, 0, nullptr, g.keys.p, g.order.p, n, x->g_dstart.p, (int)nd, (int)x->nT, d_coeff, radius,
+                       win, (uint32_t*)nullptr, g.off.p, g.adj.p);
     return 0;
   });
   if (total < 0) return -1;
@@ -437,7 +431,7 @@ int pw_seeds_graph_points(const pw_seed_index* x, int32_t* da, int64_t cap) {
   if (!x || x->g.edges < 0) { set_err("pw_seeds_graph_points before a successful pw_seeds_graph_build"); return -1; }
   if (cap < x->g.npts) { set_err("pw_seeds_graph_points: capacity too small"); return -1; }
   CHECK(hipSetDevice(x->device));
-  if (x->g.npts) CHECK(hipMemcpy(da, x->self ? x->g_pts.p : x->rows.p, (size_t)x->g.npts * 8, hipMemcpyDeviceToHost));
+  if (x->g.npts) CHECK(hipMemcpy(da, x->self ? x->g_pts.p : x->rows.p, x->rows.bytes((size_t)x->g.npts), hipMemcpyDeviceToHost));
   return 0;
 }
 

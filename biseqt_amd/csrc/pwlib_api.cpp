@@ -173,7 +173,7 @@ struct BkClass {
   int bk = 0;
   int nw = 1;                   // wavefronts per pair (> 1: multi-wavefront kernel for wide bands)
   std::vector<int32_t> order;   // pair indices, largest table first
-  DeviceBuffer d_order;         // int32_t[order.size()]
+  DeviceArray<int32_t> d_order; // [order.size()]
 };
 
 }  // namespace
@@ -199,14 +199,14 @@ struct pw_batch {
   std::vector<int32_t> strips;          // standard-mode pairs wider than a workgroup: the strip pipeline (K2c, pw_strip.h)
   std::vector<uint32_t> strip_ctl_init;                   // per strip pair: the 16 dwords its control block starts from
   PoolBuffer<uint64_t> d_fifo; size_t fifo_bytes = 0;   // FIFO rows of the largest strip pair (pairs run one after another)
-  DeviceBuffer d_sbest;                  // pw::StripBest[max strips]
-  DeviceBuffer d_ctl;                    // uint32_t[strip pairs][16]: control blocks (work queue head, abort flag, ..)
+  DeviceArray<pw::StripBest> d_sbest;    // [max strips]
+  DeviceArray<uint32_t> d_ctl;           // [strip pairs][16]: control blocks (work queue head, abort flag, ..)
   std::vector<int32_t> tiled;           // pairs that go through the time-blocked tiled kernel (K2b)
-  DeviceBuffer d_state[2];               // their per-diagonal state, double buffered (shared: pairs run one after another)
+  DeviceBuffer d_state[2];               // their per-diagonal state in the score type (int32_t or double), double buffered (shared: pairs run one after another)
   int32_t st_pitch = 0;
   int packed_seg = 0, packed_rule = 0, packed_nw = 1;     // packed_nw: wavefronts per pair (K2a with the 16-bit body)
   int packed_mat = 0;                                     // the packed kernel reads a substitution matrix (WaveFill16<.., MAT>)
-  DeviceBuffer d_waves;                  // pw::WaveDesc[waves.size()]
+  DeviceArray<pw::WaveDesc> d_waves;     // [waves.size()]
   int64_t cells = 0, alg_bytes = 0;
   // device (~pw_batch releases all of it)
   bool on_device = false;                // batch_alloc ran: a batch that only planned makes no HIP call when it goes
@@ -219,17 +219,17 @@ struct pw_batch {
   PoolBuffer<pw::Result> d_results;
   PoolBuffer<uint8_t> d_tx; uint64_t tx_bytes = 0;
   DeviceBuffer d_subst;                  // int32_t or double [L][L]
-  DeviceBuffer d_ends;                   // int32_t[n][2]: pw_batch_traceback_from
+  DeviceArray<int32_t> d_ends;           // [n][2]: pw_batch_traceback_from
   PoolBuffer<uint8_t> d_txpacked;        // pw_batch_pack_transcripts: the ops back to back
-  DeviceBuffer d_txoffsets;              // uint64_t[n + 1]
+  DeviceArray<uint64_t> d_txoffsets;     // [n + 1]
   PoolBuffer<pw_tx_summary> d_summaries; // pw_batch_summarize: allocated on its first call
   uint64_t trace_seq = 0, summary_seq = 0;   // tracebacks so far / the one the summaries were taken after
-  DeviceBuffer d_cigoffsets;             // pw_batch_cigars: uint64_t[n + 1], allocated on its first call
+  DeviceArray<uint64_t> d_cigoffsets;    // pw_batch_cigars: [n + 1], allocated on its first call
   PoolBuffer<uint32_t> d_cigruns;        // ... and the runs; grows to the largest total seen
   uint64_t cigar_room = 0, cigar_total = 0, cigar_seq = 0;   // runs d_cigruns holds / the last total / the traceback it describes
   int cigar_form = -1;
   hipStream_t cigar_stream = nullptr;    // the stream of the last pw_batch_cigars
-  DeviceBuffer d_col0;                   // pw_batch_pileup_add: int64_t[n] frame starts, allocated on its first call with a col0
+  DeviceArray<int64_t> d_col0;           // pw_batch_pileup_add: [n] frame starts, allocated on its first call with a col0
   DeviceEvent ev_fill0, ev_fill1, ev_tr0, ev_tr1;
   bool fill_timed = false, trace_timed = false;
   // scores as the caller gave them (batch_plan may scale b->subst / go / ge by a power of two)
@@ -458,7 +458,7 @@ int batch_plan(pw_batch* b) {
       d.layout = 1;
       mask_words += (uint64_t)nstrips * nkq * 64 * 4;
       b->strips.push_back(k);
-      b->fifo_bytes = std::max<size_t>(b->fifo_bytes, (size_t)nstrips * (size_t)pw::strip_fifo_pitch(d.Y) * 8);
+      b->fifo_bytes = std::max<size_t>(b->fifo_bytes, (size_t)nstrips * (size_t)pw::strip_fifo_pitch(d.Y) * sizeof(uint64_t));
       continue;
     }
     if (lay.kind == pw::PAIR_TILED && (b->flags & PW_FLAG_DUMP_SCORES)) return fail("the score plane is not available for tiled (very wide) tables");
@@ -516,19 +516,14 @@ int batch_alloc(pw_batch* b) {
     HIP_TRY(b->d_fifo.alloc(dev, b->fifo_bytes));
     // granules are recognised by their epoch tag: whatever the (possibly recycled) buffer holds must never look like one
     HIP_TRY(hipMemset(b->d_fifo.p, 0, b->fifo_bytes));
-    HIP_TRY(b->d_sbest.ensure(sizeof(pw::StripBest) * (size_t)maxs));
-    HIP_TRY(b->d_ctl.ensure(64 * b->strips.size()));
+    HIP_TRY(b->d_sbest.ensure((size_t)maxs));
+    HIP_TRY(b->d_ctl.ensure(b->strips.size() * 16));
   }
   if (!b->tiled.empty())
-    for (DeviceBuffer& st : b->d_state) HIP_TRY(st.ensure((size_t)5 * b->st_pitch * 8));
-  if (!b->waves.empty()) {
-    HIP_TRY(b->d_waves.ensure(sizeof(pw::WaveDesc) * b->waves.size()));
-    HIP_TRY(hipMemcpy(b->d_waves.p, b->waves.data(), sizeof(pw::WaveDesc) * b->waves.size(), hipMemcpyHostToDevice));
-  }
-  for (auto& c : b->classes) {
-    HIP_TRY(c.d_order.ensure(4 * c.order.size()));
-    HIP_TRY(hipMemcpy(c.d_order.p, c.order.data(), 4 * c.order.size(), hipMemcpyHostToDevice));
-  }
+    for (DeviceBuffer& st : b->d_state) HIP_TRY(st.ensure((size_t)5 * b->st_pitch * sizeof(double)));   // (room for either score type)
+  if (!b->waves.empty() && upload(fail, b->d_waves, b->waves.data(), b->waves.size()) != 0) return -1;
+  for (auto& c : b->classes)
+    if (upload(fail, c.d_order, c.order.data(), c.order.size()) != 0) return -1;
   {  // records of pairs no kernel will touch
     std::vector<pw::Result> init(std::max<int32_t>(b->n, 1));
     for (auto& r : init) { r.score = 0; r.opt_i = r.opt_j = -1; r.origin_idx = r.mutant_idx = 0; r.tx_len = 0; r.status = 0; }
@@ -562,9 +557,9 @@ int xcc_queues(int device, int32_t* xcc_queue) {
   std::lock_guard<std::mutex> lk(mu);
   if (device < 0 || device >= kMaxDevices) return 0;
   if (cached_n[device] == 0) {
-    DeviceBuffer d; uint32_t h[8] = {0};
-    if (d.ensure(sizeof h) != hipSuccess || hipMemset(d.p, 0, sizeof h) != hipSuccess ||
-        pw::launch_xcc_census((uint32_t*)d.p, nullptr) != hipSuccess || hipMemcpy(h, d.p, sizeof h, hipMemcpyDeviceToHost) != hipSuccess)
+    DeviceArray<uint32_t> d; uint32_t h[8] = {0};
+    if (d.ensure(8) != hipSuccess || hipMemset(d.p, 0, sizeof h) != hipSuccess ||
+        pw::launch_xcc_census(d.p, nullptr) != hipSuccess || hipMemcpy(h, d.p, sizeof h, hipMemcpyDeviceToHost) != hipSuccess)
       return 0;
     int n = 0;
     for (int i = 0; i < 8; i++) cached_map[device][i] = h[i] ? n++ : -1;
@@ -592,8 +587,8 @@ int launch_strip_fills(pw_batch* b, hipStream_t st) {
     pw::StripParams a;
     memset(&a, 0, sizeof a);
     a.arena = b->d_arena; a.o_off = d.o_off; a.m_off = d.m_off;
-    a.fifo = b->d_fifo.p; a.masks = b->d_masks.p + d.mask_off; a.sbest = (pw::StripBest*)b->d_sbest.p;
-    a.ctl = (uint32_t*)b->d_ctl.p + 16 * q++;
+    a.fifo = b->d_fifo.p; a.masks = b->d_masks.p + d.mask_off; a.sbest = b->d_sbest.p;
+    a.ctl = b->d_ctl.p + 16 * q++;
     a.result = b->d_results.p + k;
     a.X = d.X; a.Y = d.Y;
     a.nstrips = pw::strip_count(d.X); a.nkq = pw::strip_nkq(d.Y);
@@ -613,11 +608,11 @@ int launch_strip_fills(pw_batch* b, hipStream_t st) {
     // tuning aid: PWLIB_STRIP_TRACE=<file> dumps per-strip clock stamps (100 MHz; [8 + i]: shader-clock counts at the same points) of the first strip pair: dequeue, set-up
     // done, first granules seen, steps 64 / 96 reached, end; [7] = XCC id | workgroup << 8
     const char* trace = getenv("PWLIB_STRIP_TRACE");
-    DeviceBuffer stamps;
+    DeviceArray<uint64_t> stamps;                                  // 16 per strip
     if (trace && *trace && q == 1) {
-      HIP_TRY(stamps.ensure((size_t)a.nstrips * 128));
-      HIP_TRY(hipMemset(stamps.p, 0, (size_t)a.nstrips * 128));
-      a.stamps = (uint64_t*)stamps.p;
+      HIP_TRY(stamps.ensure((size_t)a.nstrips * 16));
+      HIP_TRY(hipMemset(stamps.p, 0, stamps.bytes((size_t)a.nstrips * 16)));
+      a.stamps = stamps.p;
     }
     const bool byte_rows = strip_byte_rows_ok(b);
     if (!byte_rows && !b->simple) return fail("internal: a substitution matrix on the strips needs their byte rows");
@@ -634,7 +629,7 @@ int launch_strip_fills(pw_batch* b, hipStream_t st) {
     if (stamps.p) {
       std::vector<uint64_t> h((size_t)a.nstrips * 16);
       HIP_TRY(hipStreamSynchronize(st));
-      HIP_TRY(hipMemcpy(h.data(), stamps.p, h.size() * 8, hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy(h.data(), stamps.p, stamps.bytes(h.size()), hipMemcpyDeviceToHost));
       if (FILE* f = fopen(trace, "wb")) { fwrite(h.data(), 8, h.size(), f); fclose(f); }
     }
   }
@@ -658,9 +653,9 @@ pw::FillParams<T> fill_params(const pw_batch* b) {
 template <typename T>
 int launch_all_fills(pw_batch* b, hipStream_t st) {
   pw::FillParams<T> a = fill_params<T>(b);
-  a.hdump = (T*)b->d_hdump.p; a.subst = (const T*)b->d_subst.p;
+  a.hdump = b->d_hdump.as<T>(); a.subst = b->d_subst.as<const T>();
   for (auto& c : b->classes) {
-    a.order = (const int32_t*)c.d_order.p;
+    a.order = c.d_order.p;
     if (c.nw > 1) HIP_TRY(pw::launch_fill_mw(a, b->variant, c.bk, c.nw, (int)c.order.size(), st));
     else HIP_TRY(pw::launch_fill(a, b->variant, c.bk, (int)c.order.size(), st));
   }
@@ -673,11 +668,11 @@ int launch_all_fills(pw_batch* b, hipStream_t st) {
     int cur = 0;
     for (int tb = 0; tb < d.nblocks; tb += pw::kTileBlocks) {
       a.tile_b0 = tb; a.tile_nb = std::min(pw::kTileBlocks, d.nblocks - tb);
-      a.st_in = (const T*)b->d_state[cur].p; a.st_out = (T*)b->d_state[cur ^ 1].p;
+      a.st_in = b->d_state[cur].as<const T>(); a.st_out = b->d_state[cur ^ 1].as<T>();
       HIP_TRY(pw::launch_tile(a, b->variant, (int)k, ntiles, st));
       cur ^= 1;
     }
-    a.st_in = (const T*)b->d_state[cur].p;
+    a.st_in = b->d_state[cur].as<const T>();
     HIP_TRY(pw::launch_tile_finish(a, (int)k, st));
   }
   return 0;
@@ -685,7 +680,7 @@ int launch_all_fills(pw_batch* b, hipStream_t st) {
 
 int launch_packed_fill(pw_batch* b, hipStream_t st) {
   pw::FillParams<int32_t> a = fill_params<int32_t>(b);
-  a.order = (const int32_t*)b->classes[0].d_order.p; a.waves = (const pw::WaveDesc*)b->d_waves.p;
+  a.order = b->classes[0].d_order.p; a.waves = b->d_waves.p;
   if (b->packed_mat) pw::packed_matrix_rows(b->subst.data(), b->L, b->packed_rule == 3, a.mat_rows, &a.mat_bias);
   if (b->packed_nw > 1) HIP_TRY(pw::launch_fill16_mw(a, b->classes[0].bk, b->packed_rule, b->packed_mat, b->packed_nw, (int)b->waves.size(), st));
   else HIP_TRY(pw::launch_fill16(a, b->classes[0].bk, b->packed_seg, b->packed_rule, b->packed_mat, (int)b->waves.size(), st));
@@ -933,7 +928,7 @@ int pw_batch_traceback(pw_batch* b, void* stream) {
 int pw_batch_traceback_from(pw_batch* b, const int32_t* ends_ij, void* stream) {
   HIP_TRY(hipSetDevice(b->device));
   hipStream_t st = (hipStream_t)stream;
-  HIP_TRY(b->d_ends.ensure(8 * std::max<int32_t>(b->n, 1)));
+  HIP_TRY(b->d_ends.ensure(2 * (size_t)std::max<int32_t>(b->n, 1)));
   // validate on the host: an end cell outside the table would send the walker out of the mask plane
   for (int32_t k = 0; k < b->n; k++) {
     if (!b->descs[k].solvable) continue;
@@ -946,10 +941,10 @@ int pw_batch_traceback_from(pw_batch* b, const int32_t* ends_ij, void* stream) {
     else ok = i >= 0 && i < pl.num_rows && j >= 0 && j < pw::plan_len(X, Y, pl.dmin + i);
     if (!ok) return fail("traceback end cell outside the table");
   }
-  HIP_TRY(hipMemcpyAsync(b->d_ends.p, ends_ij, 8 * (size_t)b->n, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(b->d_ends.p, ends_ij, b->d_ends.bytes(2 * (size_t)b->n), hipMemcpyHostToDevice, st));
   b->traced = true; b->traced_from = true;
   b->last_ends.assign(ends_ij, ends_ij + 2 * (size_t)b->n);
-  return do_trace(b, (const int32_t*)b->d_ends.p, st);
+  return do_trace(b, b->d_ends.p, st);
 }
 
 int pw_batch_sync(pw_batch* b, void* stream) {
@@ -995,9 +990,9 @@ int pw_batch_pack_transcripts(pw_batch* b, void* stream) {
   HIP_TRY(hipSetDevice(b->device));
   if (!b->d_txoffsets.p) {
     HIP_TRY(b->d_txpacked.alloc(b->device, std::max<uint64_t>(b->tx_bytes, 16)));
-    HIP_TRY(b->d_txoffsets.ensure(8 * ((size_t)b->n + 1)));
+    HIP_TRY(b->d_txoffsets.ensure((size_t)b->n + 1));
   }
-  HIP_TRY(pw::launch_tx_pack(b->d_pairs.p, b->d_results.p, b->d_tx.p, b->n, (uint64_t*)b->d_txoffsets.p, b->d_txpacked.p,
+  HIP_TRY(pw::launch_tx_pack(b->d_pairs.p, b->d_results.p, b->d_tx.p, b->n, b->d_txoffsets.p, b->d_txpacked.p,
                              (hipStream_t)stream));
   return mark_done(b, (hipStream_t)stream);
 }
@@ -1006,14 +1001,14 @@ void* pw_batch_packed_offsets_device(pw_batch* b) { return b->d_txoffsets.p; }
 int pw_batch_packed_total_async(pw_batch* b, uint64_t* host_out, void* stream) {
   if (!b->d_txoffsets.p) return fail("pw_batch_packed_total_async before pw_batch_pack_transcripts");
   HIP_TRY(hipSetDevice(b->device));
-  HIP_TRY(hipMemcpyAsync(host_out, (uint64_t*)b->d_txoffsets.p + b->n, 8, hipMemcpyDeviceToHost, (hipStream_t)stream));
+  HIP_TRY(hipMemcpyAsync(host_out, b->d_txoffsets.p + b->n, sizeof *host_out, hipMemcpyDeviceToHost, (hipStream_t)stream));
   return mark_done(b, (hipStream_t)stream);
 }
 int pw_batch_packed(pw_batch* b, uint8_t* out, uint64_t cap, uint64_t* offsets_out) {
   if (!b->d_txoffsets.p) return fail("pw_batch_packed before pw_batch_pack_transcripts");
   HIP_TRY(hipSetDevice(b->device));
   std::vector<uint64_t> off((size_t)b->n + 1);
-  HIP_TRY(hipMemcpy(off.data(), b->d_txoffsets.p, 8 * off.size(), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(off.data(), b->d_txoffsets.p, b->d_txoffsets.bytes(off.size()), hipMemcpyDeviceToHost));
   if (offsets_out) memcpy(offsets_out, off.data(), 8 * off.size());
   if (out) {
     if (off[b->n] > cap) return fail("packed transcripts: buffer too small");
@@ -1057,14 +1052,13 @@ int pw_tx_summarize_packed(int device, const uint8_t* ops, const uint64_t* offse
   const uint64_t total = offsets[n];
   if (total && !ops) return fail("pw_tx_summarize_packed: null ops with a non-zero total");
   HIP_TRY(hipSetDevice(device));
-  DeviceBuffer d_ops, d_off, d_out;
+  DeviceArray<uint8_t> d_ops; DeviceArray<uint64_t> d_off; DeviceArray<pw_tx_summary> d_out;
   HIP_TRY(d_ops.ensure((size_t)total));
-  HIP_TRY(d_off.ensure(8 * ((size_t)n + 1)));
-  HIP_TRY(d_out.ensure(sizeof(pw_tx_summary) * (size_t)n));
-  if (total) HIP_TRY(hipMemcpy(d_ops.p, ops, (size_t)total, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_off.p, offsets, 8 * ((size_t)n + 1), hipMemcpyHostToDevice));
-  HIP_TRY(pw::launch_tx_summary_packed((const uint8_t*)d_ops.p, (const uint64_t*)d_off.p, (int)n, d_out.p, nullptr));
-  HIP_TRY(hipMemcpy(out, d_out.p, sizeof(pw_tx_summary) * (size_t)n, hipMemcpyDeviceToHost));
+  HIP_TRY(d_off.ensure((size_t)n + 1));
+  HIP_TRY(d_out.ensure((size_t)n));
+  if (upload(fail, d_ops, ops, (size_t)total) != 0 || upload(fail, d_off, offsets, (size_t)n + 1) != 0) return -1;
+  HIP_TRY(pw::launch_tx_summary_packed(d_ops.p, d_off.p, (int)n, d_out.p, nullptr));
+  HIP_TRY(hipMemcpy(out, d_out.p, d_out.bytes((size_t)n), hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -1083,11 +1077,11 @@ int pw_batch_cigars(pw_batch* b, int form, void* stream) {
   if (b->d_cigoffsets.p && st != b->cigar_stream)
     for (auto& se : b->done_events) HIP_TRY(hipEventSynchronize(se.second.e));
   b->cigar_stream = st;
-  HIP_TRY(b->d_cigoffsets.ensure(8 * ((size_t)b->n + 1)));
-  HIP_TRY(pw::launch_cigar_count(b->d_pairs.p, b->d_results.p, b->d_tx.p, b->n, form, (uint64_t*)b->d_cigoffsets.p, st));
+  HIP_TRY(b->d_cigoffsets.ensure((size_t)b->n + 1));
+  HIP_TRY(pw::launch_cigar_count(b->d_pairs.p, b->d_results.p, b->d_tx.p, b->n, form, b->d_cigoffsets.p, st));
   // the one blocking read: the total sizes the run buffer
   uint64_t total = 0;
-  HIP_TRY(hipMemcpyAsync(&total, (uint64_t*)b->d_cigoffsets.p + b->n, 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(&total, b->d_cigoffsets.p + b->n, sizeof total, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   if (!b->d_cigruns.p || total > b->cigar_room) {
     // (a write of an earlier call may still run on another stream: the old buffer goes back to the pool only behind it)
@@ -1095,7 +1089,7 @@ int pw_batch_cigars(pw_batch* b, int form, void* stream) {
     HIP_TRY(b->d_cigruns.alloc(b->device, 4 * (size_t)std::max<uint64_t>(total, 4)));
     b->cigar_room = std::max<uint64_t>(total, 4);
   }
-  HIP_TRY(pw::launch_cigar_write(b->d_pairs.p, b->d_results.p, b->d_tx.p, b->n, form, (const uint64_t*)b->d_cigoffsets.p, b->d_cigruns.p, st));
+  HIP_TRY(pw::launch_cigar_write(b->d_pairs.p, b->d_results.p, b->d_tx.p, b->n, form, b->d_cigoffsets.p, b->d_cigruns.p, st));
   b->cigar_total = total; b->cigar_seq = b->trace_seq; b->cigar_form = form;
   return mark_done(b, st);
 }
@@ -1109,7 +1103,7 @@ int pw_batch_cigar(pw_batch* b, int form, uint32_t* runs_out, uint64_t cap, uint
   if ((!b->d_cigruns.p || b->cigar_seq != b->trace_seq || b->cigar_form != form) && pw_batch_cigars(b, form, nullptr) != 0) return -1;
   if (runs_out && b->cigar_total > cap) return fail("pw_batch_cigar: run buffer too small");
   HIP_TRY(hipSetDevice(b->device));
-  if (offsets_out) HIP_TRY(hipMemcpy(offsets_out, b->d_cigoffsets.p, 8 * ((size_t)b->n + 1), hipMemcpyDeviceToHost));
+  if (offsets_out) HIP_TRY(hipMemcpy(offsets_out, b->d_cigoffsets.p, b->d_cigoffsets.bytes((size_t)b->n + 1), hipMemcpyDeviceToHost));
   if (runs_out && b->cigar_total) HIP_TRY(hipMemcpy(runs_out, b->d_cigruns.p, 4 * (size_t)b->cigar_total, hipMemcpyDeviceToHost));
   return 0;
 }
@@ -1129,21 +1123,19 @@ int pw_tx_cigar_packed(int device, const uint8_t* ops, const uint64_t* offsets, 
     if (ops[k] != 'M' && ops[k] != 'S' && ops[k] != 'I' && ops[k] != 'D')
       return fail("pw_tx_cigar_packed: byte " + std::to_string(k) + " is none of M, S, I, D");
   HIP_TRY(hipSetDevice(device));
-  DeviceBuffer d_ops, d_off, d_roff, d_runs;
+  DeviceArray<uint8_t> d_ops; DeviceArray<uint64_t> d_off, d_roff; DeviceArray<uint32_t> d_runs;
   HIP_TRY(d_ops.ensure((size_t)total));
-  HIP_TRY(d_off.ensure(8 * ((size_t)n + 1)));
-  HIP_TRY(d_roff.ensure(8 * ((size_t)n + 1)));
-  if (total) HIP_TRY(hipMemcpy(d_ops.p, ops, (size_t)total, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_off.p, offsets, 8 * ((size_t)n + 1), hipMemcpyHostToDevice));
-  HIP_TRY(pw::launch_cigar_count_packed((const uint8_t*)d_ops.p, (const uint64_t*)d_off.p, (int)n, form, (uint64_t*)d_roff.p, nullptr));
+  HIP_TRY(d_off.ensure((size_t)n + 1));
+  HIP_TRY(d_roff.ensure((size_t)n + 1));
+  if (upload(fail, d_ops, ops, (size_t)total) != 0 || upload(fail, d_off, offsets, (size_t)n + 1) != 0) return -1;
+  HIP_TRY(pw::launch_cigar_count_packed(d_ops.p, d_off.p, (int)n, form, d_roff.p, nullptr));
   std::vector<uint64_t> roff((size_t)n + 1);
-  HIP_TRY(hipMemcpy(roff.data(), d_roff.p, 8 * roff.size(), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(roff.data(), d_roff.p, d_roff.bytes(roff.size()), hipMemcpyDeviceToHost));
   if (runs_out) {
     if (roff[n] > cap) return fail("pw_tx_cigar_packed: run buffer too small");
-    HIP_TRY(d_runs.ensure(4 * (size_t)roff[n]));
-    HIP_TRY(pw::launch_cigar_write_packed((const uint8_t*)d_ops.p, (const uint64_t*)d_off.p, (int)n, form, (const uint64_t*)d_roff.p,
-                                          (uint32_t*)d_runs.p, nullptr));
-    if (roff[n]) HIP_TRY(hipMemcpy(runs_out, d_runs.p, 4 * (size_t)roff[n], hipMemcpyDeviceToHost));
+    HIP_TRY(d_runs.ensure((size_t)roff[n]));
+    HIP_TRY(pw::launch_cigar_write_packed(d_ops.p, d_off.p, (int)n, form, d_roff.p, d_runs.p, nullptr));
+    if (roff[n]) HIP_TRY(hipMemcpy(runs_out, d_runs.p, d_runs.bytes((size_t)roff[n]), hipMemcpyDeviceToHost));
   }
   memcpy(run_offsets_out, roff.data(), 8 * roff.size());
   return 0;
@@ -1154,9 +1146,10 @@ struct pw_pileup {
   int device = 0;
   int64_t n_cols = 0;
   int L = 0;
-  DeviceBuffer d_counts;                 // uint32_t[n_cols][L + 2]
-  DeviceBuffer d_sites;                  // pw_pileup_site[n_cols]: allocated by the first pw_pileup_call
-  size_t count_bytes() const { return 4 * (size_t)n_cols * (size_t)(L + 2); }
+  DeviceArray<uint32_t> d_counts;        // [n_cols][L + 2]
+  DeviceArray<pw_pileup_site> d_sites;   // [n_cols]: allocated by the first pw_pileup_call
+  size_t row() const { return (size_t)(L + 2); }                         // counters per column
+  size_t count_bytes() const { return d_counts.bytes((size_t)n_cols * row()); }
 };
 
 pw_pileup* pw_pileup_create(int device, int64_t n_cols, int alphabet_len) {
@@ -1164,7 +1157,7 @@ pw_pileup* pw_pileup_create(int device, int64_t n_cols, int alphabet_len) {
   if (n_cols < 0 || n_cols > ((int64_t)1 << 36)) { fail("pw_pileup_create: n_cols out of range"); return nullptr; }
   std::unique_ptr<pw_pileup> p(new pw_pileup);
   p->device = device; p->n_cols = n_cols; p->L = alphabet_len;
-  if (hipSetDevice(device) != hipSuccess || p->d_counts.ensure(p->count_bytes()) != hipSuccess ||
+  if (hipSetDevice(device) != hipSuccess || p->d_counts.ensure((size_t)n_cols * p->row()) != hipSuccess ||
       hipMemset(p->d_counts.p, 0, std::max<size_t>(p->count_bytes(), 16)) != hipSuccess) {
     (void)hipGetLastError();
     fail("pw_pileup_create: allocation failed");
@@ -1194,12 +1187,11 @@ int pw_batch_pileup_add(pw_batch* b, pw_pileup* p, const int64_t* col0, int64_t 
   if (col0 && b->n) {
     // (the staging buffer is rewritten in place: an add of an earlier call on ANOTHER stream may still read it)
     if (b->d_col0.p) for (auto& se : b->done_events) if (se.first != st) HIP_TRY(hipEventSynchronize(se.second.e));
-    HIP_TRY(b->d_col0.ensure(8 * (size_t)b->n));
-    HIP_TRY(hipMemcpyAsync(b->d_col0.p, col0, 8 * (size_t)b->n, hipMemcpyHostToDevice, st));
-    d_col0 = (const int64_t*)b->d_col0.p;
+    if (upload(fail, b->d_col0, col0, (size_t)b->n, st) != 0) return -1;
+    d_col0 = b->d_col0.p;
   }
-  HIP_TRY(pw::launch_pileup_add(b->d_pairs.p, b->d_results.p, b->d_tx.p, b->d_arena, b->n, d_col0, arena_first, (uint32_t*)p->d_counts.p,
-                                p->n_cols, p->L, st));
+  HIP_TRY(pw::launch_pileup_add(b->d_pairs.p, b->d_results.p, b->d_tx.p, b->d_arena, b->n, d_col0, arena_first, p->d_counts.p, p->n_cols,
+                                p->L, st));
   return mark_done(b, st);
 }
 void* pw_pileup_counts_device(pw_pileup* p) { return p ? p->d_counts.p : nullptr; }
@@ -1209,8 +1201,8 @@ int pw_pileup_counts(pw_pileup* p, int64_t lo, int64_t hi, uint32_t* host_out) {
   if (hi == lo) return 0;
   if (!host_out) return fail("pw_pileup_counts: null output");
   HIP_TRY(hipSetDevice(p->device));
-  const size_t row = 4 * (size_t)(p->L + 2);
-  HIP_TRY(hipMemcpy(host_out, (const uint8_t*)p->d_counts.p + row * (size_t)lo, row * (size_t)(hi - lo), hipMemcpyDeviceToHost));
+  const size_t row = p->row();
+  HIP_TRY(hipMemcpy(host_out, p->d_counts.p + row * (size_t)lo, p->d_counts.bytes(row * (size_t)(hi - lo)), hipMemcpyDeviceToHost));
   return 0;
 }
 int pw_pileup_set_counts(pw_pileup* p, int64_t lo, int64_t hi, const uint32_t* host_in) {
@@ -1219,15 +1211,15 @@ int pw_pileup_set_counts(pw_pileup* p, int64_t lo, int64_t hi, const uint32_t* h
   if (hi == lo) return 0;
   if (!host_in) return fail("pw_pileup_set_counts: null input");
   HIP_TRY(hipSetDevice(p->device));
-  const size_t row = 4 * (size_t)(p->L + 2);
-  HIP_TRY(hipMemcpy((uint8_t*)p->d_counts.p + row * (size_t)lo, host_in, row * (size_t)(hi - lo), hipMemcpyHostToDevice));
+  const size_t row = p->row();
+  HIP_TRY(hipMemcpy(p->d_counts.p + row * (size_t)lo, host_in, p->d_counts.bytes(row * (size_t)(hi - lo)), hipMemcpyHostToDevice));
   return 0;
 }
 int pw_pileup_call(pw_pileup* p, const uint8_t* ref_letters_device, uint32_t min_depth, void* stream) {
   if (!p) return fail("pw_pileup_call: null pileup");
   HIP_TRY(hipSetDevice(p->device));
-  if (!p->d_sites.p) HIP_TRY(p->d_sites.ensure(sizeof(pw_pileup_site) * (size_t)p->n_cols));
-  HIP_TRY(pw::launch_pileup_call((const uint32_t*)p->d_counts.p, ref_letters_device, p->n_cols, p->L, min_depth, p->d_sites.p,
+  if (!p->d_sites.p) HIP_TRY(p->d_sites.ensure((size_t)p->n_cols));
+  HIP_TRY(pw::launch_pileup_call(p->d_counts.p, ref_letters_device, p->n_cols, p->L, min_depth, p->d_sites.p,
                                  (hipStream_t)stream));
   return 0;
 }
@@ -1239,7 +1231,7 @@ int pw_pileup_sites(pw_pileup* p, int64_t lo, int64_t hi, pw_pileup_site* host_o
   if (hi == lo) return 0;
   if (!host_out) return fail("pw_pileup_sites: null output");
   HIP_TRY(hipSetDevice(p->device));
-  HIP_TRY(hipMemcpy(host_out, (const pw_pileup_site*)p->d_sites.p + lo, sizeof(pw_pileup_site) * (size_t)(hi - lo), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(host_out, p->d_sites.p + lo, p->d_sites.bytes((size_t)(hi - lo)), hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -1250,11 +1242,11 @@ int pw_batch_scores(pw_batch* b, int32_t k, double* out, int64_t n) {
   if (n < want) return fail("score buffer too small");
   HIP_TRY(hipSetDevice(b->device));
   if (b->use_f64) {
-    HIP_TRY(hipMemcpy(out, (double*)b->d_hdump.p + d.h_off, 8 * (size_t)want, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out, b->d_hdump.as<double>() + d.h_off, 8 * (size_t)want, hipMemcpyDeviceToHost));
     for (int64_t i = 0; i < want; i++) out[i] *= b->score_mul;          // (dyadic scaling on f64 as well: a power of two)
   } else {
     std::vector<int32_t> tmp((size_t)want);
-    HIP_TRY(hipMemcpy(tmp.data(), (int32_t*)b->d_hdump.p + d.h_off, 4 * (size_t)want, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(tmp.data(), b->d_hdump.as<int32_t>() + d.h_off, 4 * (size_t)want, hipMemcpyDeviceToHost));
     for (int64_t i = 0; i < want; i++) out[i] = (double)tmp[(size_t)i] * b->score_mul;
   }
   return 0;
@@ -1281,11 +1273,11 @@ int pw_batch_table(pw_batch* b, int32_t k, double* out, int64_t n) {
   const int64_t want = (int64_t)(d.X + 1) * (d.Y + 1);
   if (n < want) return fail("table buffer too small");
   HIP_TRY(hipSetDevice(b->device));
-  DeviceBuffer dev;
-  HIP_TRY(dev.ensure(8 * (size_t)want));
-  const void* plane = b->use_f64 ? (const void*)((double*)b->d_hdump.p + d.h_off) : (const void*)((int32_t*)b->d_hdump.p + d.h_off);
-  HIP_TRY(pw::launch_table_rowmajor(plane, b->use_f64, d.X, d.Y, d.h_pitch, b->score_mul, (double*)dev.p, nullptr));
-  HIP_TRY(hipMemcpy(out, dev.p, 8 * (size_t)want, hipMemcpyDeviceToHost));
+  DeviceArray<double> dev;
+  HIP_TRY(dev.ensure((size_t)want));
+  const void* plane = b->use_f64 ? (const void*)(b->d_hdump.as<double>() + d.h_off) : (const void*)(b->d_hdump.as<int32_t>() + d.h_off);
+  HIP_TRY(pw::launch_table_rowmajor(plane, b->use_f64, d.X, d.Y, d.h_pitch, b->score_mul, dev.p, nullptr));
+  HIP_TRY(hipMemcpy(out, dev.p, dev.bytes((size_t)want), hipMemcpyDeviceToHost));
   return 0;
 }
 
