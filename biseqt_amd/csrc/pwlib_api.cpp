@@ -230,6 +230,7 @@ struct pw_batch {
   int cigar_form = -1;
   hipStream_t cigar_stream = nullptr;    // the stream of the last pw_batch_cigars
   DeviceArray<int64_t> d_col0;           // pw_batch_pileup_add: [n] frame starts, allocated on its first call with a col0
+  std::vector<int64_t> h_col0;           // ... and the host copy they are uploaded from
   DeviceEvent ev_fill0, ev_fill1, ev_tr0, ev_tr1;
   bool fill_timed = false, trace_timed = false;
   // scores as the caller gave them (batch_plan may scale b->subst / go / ge by a power of two)
@@ -941,9 +942,13 @@ int pw_batch_traceback_from(pw_batch* b, const int32_t* ends_ij, void* stream) {
     else ok = i >= 0 && i < pl.num_rows && j >= 0 && j < pw::plan_len(X, Y, pl.dmin + i);
     if (!ok) return fail("traceback end cell outside the table");
   }
-  HIP_TRY(hipMemcpyAsync(b->d_ends.p, ends_ij, b->d_ends.bytes(2 * (size_t)b->n), hipMemcpyHostToDevice, st));
-  b->traced = true; b->traced_from = true;
+  // The copy reads the batch's own pageable copy: the caller's array is consumed here, also where it is page-locked (a copy
+  // from such memory reads it when the stream gets there).  That the copy below is done with last_ends when it returns --
+  // the next call assigns to it again -- is the runtime's rule for pageable sources (hipMemcpyAsync returns once a pageable
+  // buffer is staged), at any size; the tests see it at 64 pairs only.
   b->last_ends.assign(ends_ij, ends_ij + 2 * (size_t)b->n);
+  HIP_TRY(hipMemcpyAsync(b->d_ends.p, b->last_ends.data(), b->d_ends.bytes(2 * (size_t)b->n), hipMemcpyHostToDevice, st));
+  b->traced = true; b->traced_from = true;
   return do_trace(b, b->d_ends.p, st);
 }
 
@@ -1187,7 +1192,8 @@ int pw_batch_pileup_add(pw_batch* b, pw_pileup* p, const int64_t* col0, int64_t 
   if (col0 && b->n) {
     // (the staging buffer is rewritten in place: an add of an earlier call on ANOTHER stream may still read it)
     if (b->d_col0.p) for (auto& se : b->done_events) if (se.first != st) HIP_TRY(hipEventSynchronize(se.second.e));
-    if (upload(fail, b->d_col0, col0, (size_t)b->n, st) != 0) return -1;
+    b->h_col0.assign(col0, col0 + (size_t)b->n);           // (the caller's array is consumed here: see pw_batch_traceback_from)
+    if (upload(fail, b->d_col0, b->h_col0.data(), (size_t)b->n, st) != 0) return -1;
     d_col0 = b->d_col0.p;
   }
   HIP_TRY(pw::launch_pileup_add(b->d_pairs.p, b->d_results.p, b->d_tx.p, b->d_arena, b->n, d_col0, arena_first, p->d_counts.p, p->n_cols,

@@ -128,7 +128,9 @@ int pw_batch_transcripts_async(pw_batch* b, uint8_t* host_out, void* stream);
 int pw_batch_solve(pw_batch* b, void* stream);
 /* K4 from each pair's optimal cell: asynchronous on `stream`, after pw_batch_solve on the same stream. */
 int pw_batch_traceback(pw_batch* b, void* stream);
-/* K4 from explicit end cells (table coordinates i,j per pair, host array of 2*n_pairs ints). */
+/* K4 from explicit end cells (table coordinates i,j per pair, host array of 2*n_pairs ints): asynchronous on `stream`.  The
+ * host array is consumed at return -- the batch keeps its own copy and uploads from that -- so the caller may overwrite or
+ * free it as soon as the call returns, whether it is pageable or page-locked (pw_host_alloc) memory. */
 int pw_batch_traceback_from(pw_batch* b, const int32_t* ends_ij, void* stream);
 int pw_batch_sync(pw_batch* b, void* stream);
 

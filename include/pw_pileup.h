@@ -46,9 +46,10 @@ void pw_pileup_destroy(pw_pileup*);
 /* All counts back to zero, asynchronous on `stream`. */
 int pw_pileup_clear(pw_pileup*, void* stream);
 /* After pw_batch_traceback or pw_batch_traceback_from on the same stream: every contributing pair of the batch added to
- * the pileup (the definition above), asynchronous on `stream`.  col0: a host array of n_pairs frame starts, consumed
- * before the call returns (staged in a device buffer of the batch, as the end cells of pw_batch_traceback_from are), or
- * NULL for origin_off - arena_first.  Adding is cumulative: two adds of one batch double its counts, several batches may
+ * the pileup (the definition above), asynchronous on `stream`.  col0: a host array of n_pairs frame starts, consumed at
+ * return (the batch keeps its own host copy and uploads from that, as for the end cells of pw_batch_traceback_from: the
+ * caller may overwrite or free the array as soon as the call returns, pageable or page-locked), or NULL for
+ * origin_off - arena_first.  Adding is cumulative: two adds of one batch double its counts, several batches may
  * add to one pileup.  An error before any traceback of the batch, and when batch and pileup live on different devices. */
 int pw_batch_pileup_add(pw_batch* b, pw_pileup* p, const int64_t* col0 /* host, n_pairs, or NULL */, int64_t arena_first,
                         void* stream);
