@@ -795,12 +795,14 @@ def transcript_of_cigar(s):
 
 
 def plan_only(shapes, alnmode=W.STD_MODE, alntype=W.GLOBAL, alphabet_len=4, subst_scores=None, match_score=1, mismatch_score=0,
-              go_score=0, ge_score=0, flags=0):
+              go_score=0, ge_score=0, flags=0, ramp_free=False):
     """What :class:`BatchAligner` would choose for problems of these shapes, without a GPU and without allocating anything
     (``pw_plan_only``): ``shapes`` is a list of ``(origin_len, mutant_len)`` or ``(origin_len, mutant_len, dmin, dmax)``.
     Returns a dict: ``kernel`` (as :attr:`BatchAligner.kernel_name`), ``score_dtype``, ``scale_shift`` (dyadic scaling:
     scores held times ``2**shift``), the number of pairs on one-wavefront kernels / workgroup kernels / the tiled kernel /
-    the strip pipeline, ``packed_rule`` (-1 unless a packed 16-bit kernel) and ``matrix`` (packed kernel in matrix form)."""
+    the strip pipeline, ``packed_rule`` (-1 unless a packed 16-bit kernel), ``matrix`` (packed kernel in matrix form) and, asked for
+    with ``ramp_free=True``, ``ramp_free`` (the packed kernel runs its start and end blocks on the steady body;
+    ``PWLIB_RAMP_BLOCKS=1`` turns that off)."""
     lib = W.load()
     L = alphabet_len
     if subst_scores is None:
@@ -821,5 +823,8 @@ def plan_only(shapes, alnmode=W.STD_MODE, alntype=W.GLOBAL, alphabet_len=4, subs
     info = (C.c_int32 * 8)()
     if lib.pw_plan_only(C.byref(sc), len(shapes), pairs, max(off, 16), flags, name, 128, info) != 0:
         raise RuntimeError('pw_plan_only failed: ' + W.last_error())
-    return dict(kernel=name.value.decode(), score_dtype='f64' if info[0] else 'i32', scale_shift=info[1], one_wavefront=info[2],
-                workgroup=info[3], tiled=info[4], strips=info[5], packed_rule=info[6], matrix=bool(info[7]))
+    out = dict(kernel=name.value.decode(), score_dtype='f64' if info[0] else 'i32', scale_shift=info[1], one_wavefront=info[2],
+                workgroup=info[3], tiled=info[4], strips=info[5], packed_rule=info[6], matrix=bool(info[7] & 1))
+    if ramp_free:
+        out['ramp_free'] = bool(info[7] & 2)
+    return out

@@ -233,6 +233,7 @@ struct PlanKnobs {
   bool mw_wide_lanes = false;       // PWLIB_MW_WIDE_LANES=1: many wide pairs on 32 diagonals per lane
   int simple_as_matrix = -1;        // PWLIB_SIMPLE_AS_MATRIX=0 / 1: match / mismatch in the packed matrix form never / always
   bool no_scaled16 = false;         // PWLIB_NO_SCALED16=1: no scores-times-4 form (rule 3)
+  bool ramp_blocks = false;         // PWLIB_RAMP_BLOCKS=1: blocks in which diagonals start or end keep their own bodies (ramp_free)
   bool packed_bk_forced = false;    // PWLIB_PACKED_BK="<bk>" or "<bk>s": the packed lane width (s: lane packing)
   int packed_bk = 0;
   bool packed_bk_seg = false;
@@ -329,6 +330,33 @@ static inline PackedAdmission admit_packed(int rule, const ScoreSummary& s, int 
   a.x4 = rule == 0 && best <= 2047 && !kn.no_scaled16;
   a.x4_matrix = packed_matrix_bytes_ok(s, L, true);
   return a;
+}
+
+// ramp_free: whether the packed body that runs one loop per kind of block (WaveFill16::SPLIT: the matrix form of rule 0 and
+// of its scores-times-4 twin, rule 3) may run the blocks in which diagonals start or end on the STEADY body, which neither
+// withholds the begin candidate from cells that have not started nor masks cells beyond a diagonal's end out of the running
+// best.  `rule` and `matrix` as the batch runs (PackedAdmission, packed_matrix_form); go, ge, smin as the kernels hold them
+// (integers; admit_packed already requires go <= 0, ge <= 0, packed_matrix_bytes_ok smin <= 0).  True iff
+//     ge < 0,   ge + go < 0,   smin < 0.
+// Start ramp.  The in-band slots start at H = 0 instead of the sentinel.  A virtual cell (one with a negative coordinate)
+// has only virtual predecessors.  Letters outside a sequence score smin <= 0 and every gap offer is H + ge (+ go) < H, so by
+// induction a virtual cell's candidates are <= 0 and, with the begin candidate, it stays EXACTLY 0 -- what such a cell
+// counts as in the running best today.  A real cell sees from a virtual predecessor a diagonal candidate 0 + smin <= 0,
+// which cannot lift it above the begin candidate it holds anyway (the packed plane stores no M bit), and a gap offer
+// ge + go < 0, which never equals its own H >= 0: no D or I bit is set that the sentinel would not have set.  Every in-band
+// diagonal predecessor is >= 0 from block 0 on, which is all the steady body's saturating subtract asks, and 0 lies inside
+// the [0, 8191] the body's 32-bit diagonal add requires of H (pw_wave.h, cellpair).
+// End ramp.  Cells beyond a diagonal's end stay in the running best.  The letters they read are outside a sequence and
+// score as such: the steady loop then replaces the feed letters outside the sequences in EVERY block that is fed one, because a letter
+// beyond a sequence's end is fed long before the band reads it, in blocks that are still steady (pw_wave.h, RAMPF).  So
+// each of their candidates is a predecessor's H plus smin < 0 or
+// plus at most ge < 0, or the begin candidate 0: by induction over the steps such a cell holds at most max(0, G - 1), G the
+// best in-table score.  If G > 0 no such cell reaches G: a slot whose diagonal holds an in-table G cell keeps that cell (the
+// key's stamp moves only on a strict rise of the score), a slot that reports a cell beyond its end reports less than G and
+// loses the end-cell reduction.  If G = 0 no score rises at all, no stamp is written and every diagonal reports its first
+// cell as before.  The tie nibbles of such cells go where they went before: mask slots no walk visits.
+static inline bool ramp_free(int rule, bool matrix, double go, double ge, double smin, const PlanKnobs& kn) {
+  return (rule == 0 || rule == 3) && matrix && !kn.ramp_blocks && ge < 0 && ge + go < 0 && smin < 0;
 }
 
 struct PackedLayout { int bk = 0, nl = 0, seg = 0, nw = 1; };   // bk = 0: none; seg: several pairs per wavefront

@@ -113,6 +113,9 @@ struct FillParams {
   // four bytes scale * (subst[o][m] - min(subst)), m = 0 .. 3 from the low byte up; mat_bias = scale * -min(subst)
   uint32_t mat_rows[4];
   int32_t mat_bias;
+  // Packed kernels that run one loop per kind of block: the planner's `ramp_free` (pw_plan.h) -- the blocks in which
+  // diagonals start or end run on the steady body (WaveFill16::run).  (Sits in what was tail padding: no offset moves.)
+  int32_t ramp_free;
 };
 
 struct TraceParams {

@@ -33,6 +33,9 @@
 #endif
 
 #include "pw_types.h"
+#if !defined(__HIPCC__)
+#include <stdlib.h>
+#endif
 
 namespace pw {
 
@@ -750,6 +753,18 @@ extern "C" __attribute__((used, visibility("default"))) inline unsigned pw_pk_ad
   if (reset) pk::add32_breaches() = 0;
   return n;
 }
+// Which body ran: blocks of one launch per kind of block (block16<EK>: 0 steady, 1 not started, 2 ended, 3 both), counted by
+// lane 0 of the emulated wavefront or workgroup.  The emulator's harness fills FillParams without the planner, so the
+// planner's ramp_free is handed to the lane program here: -1 as FillParams says, 0 / 1 for the launches that follow;
+// PWLIB_RAMP_BLOCKS=1 turns it off as it does in the planner.
+namespace pk {
+inline unsigned* ramp_block_counts() { static unsigned n[4] = {0, 0, 0, 0}; return n; }
+inline int& ramp_free_emu() { static int v = -1; return v; }
+}  // namespace pk
+extern "C" __attribute__((used, visibility("default"))) inline void pw_ramp_block_counts(unsigned* out, int reset) {
+  for (int i = 0; i < 4; i++) { out[i] = pk::ramp_block_counts()[i]; if (reset) pk::ramp_block_counts()[i] = 0; }
+}
+extern "C" __attribute__((used, visibility("default"))) inline void pw_emu_ramp_free(int v) { pk::ramp_free_emu() = v; }
 #endif
 
 // RULE selects the begin / end rules the kernel serves:
@@ -873,7 +888,25 @@ struct WaveFill16 {
   // lane.  (Elsewhere the BK / 4 addresses cost registers the body has no room for: the rules that begin on the table edge
   // spilled scalar registers, the match / mismatch body at 28 diagonals per lane lost its second wavefront per SIMD.)
   static constexpr bool SBASE = !SEG && SPLIT;
-  uint32_t mrowb;               // SBASE: the byte offset of this lane's dwords in the block to come
+  // ... and, where the best is tracked (rules 0 and 3), takes the blocks in which diagonals start or end into the steady loop
+  // when the planner says the scores allow it (pw_plan.h, ramp_free: the two proofs are there).  Then
+  //   * the slots up to and including the first diagonal above the band start at H = 0 instead of the sentinel (run()): the
+  //     cells before a diagonal's first stay exactly 0, so the steady body's saturating subtract (FLOOR0) and its 32-bit
+  //     diagonal add hold from block 0 on.  Slot ndiag starts at 0 with them: the edge bodies lift it to 0 on step 0
+  //     (tfirst_of), the steady body has no maximum with 0, and left at the sentinel it would take the band's offers
+  //     H + ge + go -- small negative values, which the 32-bit add carries out of;
+  //   * cells beyond a diagonal's end stay in the key (track_key<0> masks nothing): they hold less than the best;
+  //   * the steady loop replaces the feed letters outside the sequences in EVERY block that is fed one (feed_commit), not
+  //     only in the blocks in which diagonals start or end: a letter beyond a sequence's end is fed many blocks before the
+  //     band's cells beyond the table read it -- the origin feed runs a whole wavefront of lanes ahead -- i.e. in blocks
+  //     that are steady by the planner's bounds.  Left as loaded (a copy of the sequence's last letters) it would match,
+  //     and a cell beyond a diagonal's end could then outscore the table.  The test is two scalar compares per block; the
+  //     replacement itself, about 40 scalar instructions, runs only in the blocks that need it.
+  // The three other loops stay for batches whose scores do not allow it.
+  static constexpr bool RAMPF = SPLIT && TRK;
+  bool rf;                      // RAMPF and the planner's ramp_free
+  uint32_t flimx, flimy;        // RAMPF: max(length - 7, 0) of each sequence (blocks_step)
+  uint32_t mrowb;              // SBASE: the byte offset of this lane's dwords in the block to come
   uint8_t* mbase[BK / 4];       // SBASE: the plane's address plus the distance of lane group g
 
   PW_FN WaveFill16(const FillParams<int32_t>& a_, const WaveDesc& wd_) : a(a_), wd(wd_) {}
@@ -916,7 +949,8 @@ struct WaveFill16 {
       // half, so no half carries into its neighbour and the bits are the packed add's.  A half of H is one of
       //   * a started cell's score, or a cell's beyond its diagonal's end: 0 .. 8191 -- admit_packed (pw_plan.h) holds
       //     min(X, Y) * max(subst) to 8000, to 2047 times 4 in the scores-times-4 form, and letters outside a sequence score
-      //     the matrix minimum, which packed_matrix_bytes_ok requires to be <= 0;
+      //     the matrix minimum, which packed_matrix_bytes_ok requires to be <= 0; with ramp_free (RAMPF) also a cell before
+      //     its diagonal's first: exactly 0;
       //   * the first diagonal above the band (slot ndiag): begins at step 0 (tfirst_of), so it is 0 .. 8191 like a started
       //     cell from its first update on.  (Left at the sentinel it took the in-band offers H + ge + go, small negative
       //     values, and carried into the slot it shares a register with.)  Its offers go out 8192 lower (blocked), below every
@@ -1085,6 +1119,9 @@ struct WaveFill16 {
 
   template <int EK>
   PW_FN void block16(int b) {
+#if !defined(__HIPCC__)
+    if (P::lane() == 0) pk::ramp_block_counts()[EK]++;       // (the CPU emulator: which body ran)
+#endif
 #pragma unroll
     for (int p = 0; p < RH; p++) { accE[p] = 0; accO[p] = 0; acc2E[p] = 0; acc2O[p] = 0; }
     uint32_t kb0E[RH], kb0O[RH];
@@ -1182,6 +1219,10 @@ struct WaveFill16 {
   // MAT, blocks in which diagonals start or end (`edge`): the block's feed letters outside the sequences are replaced here,
   // once per block, by letters that encode "outside" (origin 0xff: row 0; mutant MOUT: selector 8 or 12) instead of a range
   // check per iteration.  Steady blocks keep the letters as loaded (only out-of-band slots read those beyond a sequence).
+  // (The steady loop of RAMPF passes a run-time `edge`, see blocks_step: a branch around the replacement, in front of the
+  // unrolled body -- wave-uniform with one pair per wavefront.  RT marks that call: the two paths join, and the high halves
+  // are made opaque behind the join.)
+  template <bool RT = false>
   PW_FN void feed_commit(int b, bool edge) {
     const int ro = (xfeed_o + 8 * b) & 3, rm = (yfeed_m + 8 * b) & 3;
     fo_lo = Base::funnel(fo_n1, fo_n0, ro); fo_hi = Base::funnel(fo_n2, fo_n1, ro);
@@ -1194,8 +1235,9 @@ struct WaveFill16 {
       fm_lo = (uint32_t)m; fm_hi = (uint32_t)(m >> 32);
       // (seen as the halves of one 64-bit value, "the last letter is 0" became a 64-bit unsigned compare, which exists as a
       //  vector instruction only)
-      if (!SEG) { fo_hi = pk::opaque_su(fo_hi); fm_hi = pk::opaque_su(fm_hi); }
+      if (!SEG && !RT) { fo_hi = pk::opaque_su(fo_hi); fm_hi = pk::opaque_su(fm_hi); }
     }
+    if (MAT && !SEG && RT) { fo_hi = pk::opaque_su(fo_hi); fm_hi = pk::opaque_su(fm_hi); }
   }
 
   PW_FN int tfirst_of(int j) const {      // first step of slot j's diagonal; never for a diagonal outside the band
@@ -1231,6 +1273,18 @@ struct WaveFill16 {
   PW_FN uint32_t letter_o(int i) const { return (uint32_t)i < (uint32_t)X ? (uint32_t)oseq[i] : SENT_O; }
   PW_FN uint32_t letter_m(int i) const { return (uint32_t)i < (uint32_t)Y ? (uint32_t)mseq[i] : SENT_M; }
   PW_FN int blocked(int j) const { return li * BK + j == ndiag ? NEG16 : 0; }   // first diagonal above the band
+  // RAMPF with ramp_free: what slot j holds before step 0 -- 0 in the band and on the first diagonal above it (see RAMPF)
+  PW_FN int start_of(int j) const { return (valid && li * BK + j <= ndiag) ? 0 : NEG16; }
+  // the planner's ramp_free (the CPU emulator: as its test set it, and under the planner's knob)
+  PW_FN bool ramp_free_on() const {
+#if !defined(__HIPCC__)
+    if (pk::ramp_free_emu() >= 0) {
+      const char* knob = getenv("PWLIB_RAMP_BLOCKS");
+      return pk::ramp_free_emu() != 0 && !(knob && atoi(knob) != 0);
+    }
+#endif
+    return a.ramp_free != 0;
+  }
 
   PW_FN void run() {
     const int lane = P::lane();
@@ -1251,6 +1305,7 @@ struct WaveFill16 {
     const int xbase = e + li * R, ybase = f - li * R;
     xfeed_o = e + nl * R - 1;                   // the letter a virtual lane `nl` would hand down
     yfeed_m = f;
+    rf = RAMPF && ramp_free_on();
     ONE = pk::opaque(0x00010001u); SH15 = pk::opaque(0x000f000fu);
     C2 = pk::opaque(0x00020002u); C4 = pk::opaque(0x00040004u); C16 = pk::opaque(0x00100010u);
     C8 = pk::opaque(0x00080008u); SEVEN = pk::opaque(0x00070007u);
@@ -1282,6 +1337,9 @@ struct WaveFill16 {
       }
       tlE[p] = pk::pack(tlast_of(e0), tlast_of(e1)); tlO[p] = pk::pack(tlast_of(o0), tlast_of(o1));
       HE[p] = UE[p] = LE[p] = HO[p] = UO[p] = LO[p] = NEGV;
+      if (RAMPF && rf) {        // (the offers stay at the sentinel: nothing was offered before step 0)
+        HE[p] = pk::pack(start_of(e0), start_of(e1)); HO[p] = pk::pack(start_of(o0), start_of(o1));
+      }
       up_prev = left_next = NEGV; phase_l = 0; phase_r = 0;
       // tracking rules: best 0 and no stamp yet (finish(): such a diagonal reports its first cell under rule 0)
       bestE[p] = bestO[p] = NEGV;
@@ -1316,10 +1374,13 @@ struct WaveFill16 {
       const int nb = nblocks_run();
       const int b0 = wd.steady_b0 < nb ? (wd.steady_b0 > 0 ? wd.steady_b0 : 0) : nb;
       const int b1 = sb1 < nb ? sb1 : nb;
+      // RAMPF with ramp_free: the steady loop takes every block, the other three run none
+      const int r0 = (RAMPF && rf) ? 0 : b0, r1 = (RAMPF && rf) ? nb : b1;
+      flimx = (uint32_t)(X > 7 ? X - 7 : 0); flimy = (uint32_t)(Y > 7 ? Y - 7 : 0);
       int b = 0;
-      if (sb1 > wd.steady_b0) for (; b < b0; b++) blocks_step<1>(b);   // some have not started; none has ended before the steady range
-      else for (; b < b0; b++) blocks_step<3>(b);                      // (no steady range: the planner's bounds cannot tell)
-      for (; b < b1; b++) blocks_step<0>(b);
+      if (sb1 > wd.steady_b0) for (; b < r0; b++) blocks_step<1>(b);   // some have not started; none has ended before the steady range
+      else for (; b < r0; b++) blocks_step<3>(b);                      // (no steady range: the planner's bounds cannot tell)
+      for (; b < r1; b++) blocks_step<0>(b);
       for (; b < nb; b++) blocks_step<2>(b);                           // every diagonal has started, some may have ended
     } else {
       for (int b = 0, nb = nblocks_run(); b < nb; b++) {
@@ -1340,7 +1401,11 @@ struct WaveFill16 {
   PW_FN int nblocks_run() const { return SBASE ? (wd.nblocks < pd.nblocks ? wd.nblocks : pd.nblocks) : wd.nblocks; }
   template <int EK>
   PW_FN void blocks_step(int b) {
-    feed_commit(b, EK != 0);
+    // (the steady loop, RAMPF with ramp_free: the letters are replaced in every block that is fed one from outside a
+    //  sequence -- the first of its eight origin or mutant letters has a negative index or lies past length - 8)
+    if constexpr (RAMPF && EK == 0)
+      feed_commit<true>(b, rf & (((uint32_t)(xfeed_o + 8 * b) >= flimx) | ((uint32_t)(yfeed_m + 8 * b) >= flimy)));
+    else feed_commit(b, EK != 0);
     if (b + 1 < nblocks_run()) feed_issue(b + 1);
     block16<EK>(b);
   }

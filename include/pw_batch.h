@@ -92,7 +92,8 @@ void pw_batch_destroy(pw_batch* b);
  * nothing allocated (works on a machine without a GPU; the tests pin the kernel choices with it).  `kernel` receives the
  * name pw_batch_kernel_name would report (NUL-terminated, at most kernel_cap bytes); `info`, if not NULL, 8 ints: score
  * type (0 int32 / 1 double), dyadic scale shift (scores are held times 2^shift), pairs on one-wavefront kernels, on
- * workgroup kernels, on the tiled kernel, on the strip pipeline, packed rule (-1: not a packed kernel), matrix form (0 / 1).
+ * workgroup kernels, on the tiled kernel, on the strip pipeline, packed rule (-1: not a packed kernel), and the packed
+ * kernel's form as bits: 1 the matrix form, 2 its start and end blocks run on the steady body (ramp_free).
  * 0, or -1 with pw_last_error set. */
 int pw_plan_only(const pw_scoring* scoring, int32_t n_pairs, const pw_pair* pairs, uint64_t arena_bytes, uint32_t flags,
                  char* kernel, int32_t kernel_cap, int32_t* info);
