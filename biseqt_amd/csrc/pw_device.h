@@ -48,7 +48,23 @@ PW_FN uint32_t dev_const_dword(const uint8_t* base, int idx) {
   return ((c_u32*)base)[idx];
 }
 
-struct DevP {
+// Dwords 1 and 2 behind a WAVE-UNIFORM byte offset into such a frame, as ONE scalar load (the first in the low half): the 64-bit type is 4-byte
+// aligned (frames start on 4-byte boundaries, nothing more), and read through the constant address space it is selected as
+// s_load_dwordx2 sdst, sbase, soffset offset:4 -- the frame's base, the offset in a scalar register and a constant, with no
+// 64-bit address arithmetic in front of it.
+typedef uint64_t FeedDwords __attribute__((aligned(4)));
+PW_FN uint64_t dev_const_dword2(const uint8_t* base, uint32_t byte_off) {
+  typedef const __attribute__((address_space(4))) uint8_t c_u8;
+  typedef const __attribute__((address_space(4))) FeedDwords c_fd;
+  return *(c_fd*)((c_u8*)base + byte_off + 4u);
+}
+
+// (what the packed kernels' edge-lane feeders read through: pw_wave.h, WaveFill16::feed_issue)
+struct DevFeed {
+  PW_FN static uint64_t const_dword2(const uint8_t* base, uint32_t byte_off) { return dev_const_dword2(base, byte_off); }
+};
+
+struct DevP : DevFeed {
   PW_FN static uint32_t const_dword(const uint8_t* base, int idx) { return dev_const_dword(base, idx); }
   template <typename T, bool A> PW_FN static T tab_read(const T* tab, uint32_t h, uint32_t off, bool in_lds) { return dev_tab_read<T, A>(tab, h, off, in_lds); }
   PW_FN static uint32_t shl1_in(uint32_t m, bool flag) { return dev_shl1_in(m, flag); }
@@ -119,7 +135,7 @@ template <int N, int MAXW> PW_FN void wg_shift_left(int32_t* v, const int32_t* o
 // long row of lanes.  Inside a wavefront the shifts are the same DPP moves; the value that crosses a wavefront
 // boundary goes through LDS (one slot per wavefront, written by its edge lane) between two workgroup barriers.
 // Every wavefront runs the same sequence of shifts, so the barriers are reached uniformly.
-struct DevPM {
+struct DevPM : DevFeed {
   PW_FN static uint32_t const_dword(const uint8_t* base, int idx) { return dev_const_dword(base, idx); }
   template <typename T, bool A> PW_FN static T tab_read(const T* tab, uint32_t h, uint32_t off, bool in_lds) { return dev_tab_read<T, A>(tab, h, off, in_lds); }
   PW_FN static uint32_t shl1_in(uint32_t m, bool flag) { return dev_shl1_in(m, flag); }
@@ -229,7 +245,7 @@ __global__ __launch_bounds__(512) void k_fill16_mw(const FillParams<int32_t> a) 
 // lane indices are global (tile * kTileCentral - kTileGhost + thread); the first kTileGhost and the last
 // kTileGhost lanes are ghost copies of the neighbouring tiles' lanes.
 constexpr int kTileLanes = PW_TILE_LANES, kTileGhost = PW_TILE_GHOST, kTileCentral = kTileLanes - 2 * kTileGhost;
-struct DevPT {
+struct DevPT : DevFeed {
   PW_FN static uint32_t const_dword(const uint8_t* base, int idx) { return dev_const_dword(base, idx); }
   template <typename T, bool A> PW_FN static T tab_read(const T* tab, uint32_t h, uint32_t off, bool in_lds) { return dev_tab_read<T, A>(tab, h, off, in_lds); }
   PW_FN static uint32_t shl1_in(uint32_t m, bool flag) { return dev_shl1_in(m, flag); }

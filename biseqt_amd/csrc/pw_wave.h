@@ -675,6 +675,13 @@ PW_FN uint32_t sign(uint32_t a, uint32_t sh15) { return __builtin_bit_cast(uint3
 PW_FN uint32_t opaque(uint32_t v) { asm volatile("" : "+v"(v)); return v; }
 PW_FN uint32_t opaque_su(uint32_t v) { asm volatile("" : "+s"(v)); return v; }   // a wave-uniform value, kept in a scalar register
 PW_FN uint8_t* opaque_s(uint8_t* v) { asm volatile("" : "+s"(v)); return v; }   // a wave-uniform address, kept in scalar registers
+// a copy of wave-uniform `src` into a scalar register of its own, in ONE statement with `pass`: what depends on `pass`
+// afterwards comes behind the copy
+PW_FN uint32_t copy_su(uint32_t src, uint32_t& pass) {
+  uint32_t d;
+  asm volatile("s_mov_b32 %0, %2" : "=&s"(d), "+s"(pass) : "s"(src));
+  return d;
+}
 // 16 bytes to base + off in GLOBAL memory (an address that went through opaque_s has lost its address space, and a flat store
 // would count against the scalar loads' counter as well)
 PW_FN void store_global(uint8_t* base, uint32_t off, const U4& v) {
@@ -725,6 +732,7 @@ PW_FN uint32_t sign(uint32_t a, uint32_t) { return mk(sl(a) < 0 ? 0xffffu : 0u, 
 PW_FN uint32_t opaque(uint32_t v) { return v; }
 PW_FN uint32_t opaque_su(uint32_t v) { return v; }
 PW_FN uint8_t* opaque_s(uint8_t* v) { return v; }
+PW_FN uint32_t copy_su(uint32_t src, uint32_t&) { return src; }
 PW_FN void store_global(uint8_t* base, uint32_t off, const U4& v) { *(U4*)(base + off) = v; }
 PW_FN uint32_t perm(uint32_t a, uint32_t b, uint32_t sel) {
   const uint64_t in = ((uint64_t)a << 32) | b;
@@ -765,6 +773,21 @@ extern "C" __attribute__((used, visibility("default"))) inline void pw_ramp_bloc
   for (int i = 0; i < 4; i++) { out[i] = pk::ramp_block_counts()[i]; if (reset) pk::ramp_block_counts()[i] = 0; }
 }
 extern "C" __attribute__((used, visibility("default"))) inline void pw_emu_ramp_free(int v) { pk::ramp_free_emu() = v; }
+// The packed kernels' edge-lane feeders, one pair per wavefront (WaveFill16::feed_issue): dwords the emulator's reader was
+// asked for outside [0, wlast] of the frame it was reading (counted by every lane; must stay 0), and the blocks whose
+// window took each path, counted by lane 0: [origin ahead, origin late, mutant ahead, mutant late].
+namespace pk {
+inline unsigned& feed_breaches() { static unsigned n = 0; return n; }
+inline unsigned* feed_path_counts() { static unsigned n[4] = {0, 0, 0, 0}; return n; }
+}  // namespace pk
+extern "C" __attribute__((used, visibility("default"))) inline unsigned pw_feed_breaches(int reset) {
+  const unsigned n = pk::feed_breaches();
+  if (reset) pk::feed_breaches() = 0;
+  return n;
+}
+extern "C" __attribute__((used, visibility("default"))) inline void pw_feed_path_counts(unsigned* out, int reset) {
+  for (int i = 0; i < 4; i++) { out[i] = pk::feed_path_counts()[i]; if (reset) pk::feed_path_counts()[i] = 0; }
+}
 #endif
 
 // RULE selects the begin / end rules the kernel serves:
@@ -844,7 +867,11 @@ struct WaveFill16 {
   const uint8_t* oseq;
   const uint8_t* mseq;
   int X, Y, ndiag, owlast, mwlast, xfeed_o, yfeed_m;
-  uint32_t fo_lo, fo_hi, fm_lo, fm_hi, fo_n0, fo_n1, fo_n2, fm_n0, fm_n1, fm_n2;
+  // the current block's 8 + 8 letters; the next block's raw dwords: the first, and the second and third as one 64-bit value
+  // (what the two-dword load delivers; feed_commit shifts it in place)
+  uint32_t fo_lo, fo_hi, fm_lo, fm_hi, fo_n0, fm_n0;
+  uint64_t fo_n12, fm_n12;
+  uint32_t fo_w, fm_w, fo_lim, fm_lim;  // !SEG: byte offset of the first dword of the block to come; the bound of the load ahead (feed_issue)
 
   // packed state: index p <-> even slots (2p, 2p + R) [E*] / odd slots (2p + 1, 2p + 1 + R) [O*]
   uint32_t HE[RH], UE[RH], LE[RH], HO[RH], UO[RH], LO[RH];
@@ -904,6 +931,10 @@ struct WaveFill16 {
   //     replacement itself, about 40 scalar instructions, runs only in the blocks that need it.
   // The three other loops stay for batches whose scores do not allow it.
   static constexpr bool RAMPF = SPLIT && TRK;
+  // One pair per wavefront, matrix form, blocks unrolled in full: the rows of a block's 8 origin feed letters are selected
+  // when the block starts (feed_commit), on bits read in place (row_bits) -- wave-uniform, scalar registers.
+  static constexpr bool FROWS = MAT && !SEG && UNR == 4 && BK <= 8;
+  uint32_t frow[FROWS ? 8 : 1];
   bool rf;                      // RAMPF and the planner's ramp_free
   uint32_t flimx, flimy;        // RAMPF: max(length - 7, 0) of each sequence (blocks_step)
   uint32_t mrowb;              // SBASE: the byte offset of this lane's dwords in the block to come
@@ -1058,7 +1089,7 @@ struct WaveFill16 {
       const int oi = xfeed_o + it;
       const uint32_t fb = Base::feed_byte(fo_lo, fo_hi, k);
       uint32_t feed = (!EDGE || (uint32_t)oi < (uint32_t)X) ? fb : SENT_O;
-      if (MAT) feed = row_of(fb);
+      if (MAT) feed = FROWS ? frow[FROWS ? k : 0] : row_of(fb);
       int32_t mv[2] = {(int32_t)(MAT ? ROW[0] : OW[0]), (int32_t)LE[0]};
       const int32_t mo[2] = {(int32_t)feed, (int32_t)left_next};
       xshlv<P, 2>(mv, mo, phase_l); phase_l ^= 1;
@@ -1187,20 +1218,82 @@ struct WaveFill16 {
     }
   }
 
+  // One pair per wavefront (or workgroup): the indices are wave-uniform -- scalar loads, which leave vmcnt to the mask stores.
+  // A block consumes 8 letters, so its 3-dword window (words w, w + 1, w + 2 of the frame, each clamped to 0 .. wlast) moves
+  // on by exactly 2 dwords per block: the first word of a block's window IS the last word of the block before, clamped or
+  // not.  The window's place is carried as a byte offset (fw = 4 w, + 8 per block), and
+  //   * where the other two words are unclamped -- 0 <= w and w + 2 <= wlast, i.e. fw < 4 max(wlast - 1, 0) as UNSIGNED
+  //     numbers (a negative offset is a huge one) -- they are loaded ONE BLOCK AHEAD by one two-dword load at an offset held
+  //     in a scalar register (feed_issue), against three loads with a clamp and a 64-bit address each.  The load reads words
+  //     w + 1 and w + 2 <= wlast: never a dword outside the frame's own (a caller-owned arena has nothing behind its last
+  //     frame but 16 bytes of slack).  A frame of fewer than 3 dwords never qualifies;
+  //   * elsewhere the block that needs the words fetches them itself, when it starts (feed_late, behind a branch in front of
+  //     the body): the three clamped loads -- or, where the window lies past the frame's end or before its start altogether
+  //     (w >= wlast or w + 2 <= 0), no load: all three words are the word carried over.  Loads are left for a pair's first
+  //     block and the one or two blocks in which a window straddles an end of its sequence.
+  // Each sequence decides for itself: a short one at its end does not send the long one down the slow path.
+  PW_FN static uint64_t dwords(uint32_t lo, uint32_t hi) { return ((uint64_t)hi << 32) | lo; }
+  PW_FN static void feed_count(int which) {
+#if !defined(__HIPCC__)
+    if (P::lane() == 0) pk::feed_path_counts()[which]++;       // (the CPU emulator: which path ran)
+#endif
+  }
+  // The two readers.  On the device: scalar loads (P::const_dword; P::const_dword2, the two-dword load).  On the CPU emulator:
+  // plain reads through the platform's const_dword that COUNT every dword asked for outside [0, wlast] of the frame
+  // (pk::feed_breaches) and deliver a poison value for it instead of touching memory.
+  PW_FN static uint32_t feed_dword(const uint8_t* base, int idx, int wlast) {
+#if !defined(__HIPCC__)
+    if (idx < 0 || idx > wlast) { pk::feed_breaches()++; return 0xa5a5a5a5u; }
+#endif
+    return P::const_dword(base, idx);
+  }
+  PW_FN static uint64_t feed_dword2(const uint8_t* base, uint32_t byte_off, int wlast) {
+#if !defined(__HIPCC__)
+    const int idx = (int)(byte_off + 4u) >> 2;
+    if ((byte_off & 3u) != 0) pk::feed_breaches()++;
+    return dwords(feed_dword(base, idx, wlast), feed_dword(base, idx + 1, wlast));
+#else
+    return P::const_dword2(base, byte_off);
+#endif
+  }
+  PW_FN void feed_load3(const uint8_t* seq, int wlast, uint32_t fw, uint32_t& n0, uint64_t& n12) {
+    const int w = (int)fw >> 2;
+    n0 = feed_dword(seq, pw_clampi(w, 0, wlast), wlast);
+    n12 = dwords(feed_dword(seq, pw_clampi(w + 1, 0, wlast), wlast), feed_dword(seq, pw_clampi(w + 2, 0, wlast), wlast));
+  }
+  PW_FN void feed_late(const uint8_t* seq, int wlast, uint32_t fw, uint32_t& n0, uint64_t& n12, int which) {
+    const int w = (int)fw >> 2;
+    feed_count(2 * which + 1);
+    if (w >= wlast || w + 2 <= 0) { n0 = (uint32_t)(n12 >> 32); n12 = dwords(n0, n0); }
+    else feed_load3(seq, wlast, fw, n0, n12);
+  }
+  PW_FN void feed_ahead(const uint8_t* seq, int wlast, uint32_t& fw, uint32_t flim, uint32_t& n0, uint64_t& n12, int which) {
+    fw += 8u;
+    if (fw < flim) {
+      feed_count(2 * which);
+      // (the copy of the word carried over comes BEFORE the load, which then lands in the registers it was copied from: the
+      //  load's offset passes through the statement that makes the copy (pk::copy_su).  Scheduled first, the load took registers of
+      //  its own and was waited for on the spot, to be copied into place.)
+      n0 = pk::copy_su((uint32_t)(n12 >> 32), fw);
+      n12 = feed_dword2(seq, fw, wlast);
+    }
+  }
+  // FIRST: a pair's first block, in front of the block loops -- nothing is carried yet
+  template <bool FIRST = false>
   PW_FN void feed_issue(int b) {
+    if (!SEG) {
+      if (FIRST) {
+        feed_load3(oseq, owlast, fo_w, fo_n0, fo_n12); feed_load3(mseq, mwlast, fm_w, fm_n0, fm_n12);
+      } else {
+        feed_ahead(oseq, owlast, fo_w, fo_lim, fo_n0, fo_n12, 0); feed_ahead(mseq, mwlast, fm_w, fm_lim, fm_n0, fm_n12, 1);
+      }
+      return;
+    }
     const uint32_t* o32 = (const uint32_t*)oseq;
     const uint32_t* m32 = (const uint32_t*)mseq;
     const int wo = (xfeed_o + 8 * b) >> 2, wm = (yfeed_m + 8 * b) >> 2;
-    if (!SEG) {
-      // one pair per wavefront (or workgroup): the indices are wave-uniform -- scalar loads, which leave vmcnt to the mask stores
-      fo_n0 = P::const_dword(oseq, pw_clampi(wo, 0, owlast)); fo_n1 = P::const_dword(oseq, pw_clampi(wo + 1, 0, owlast));
-      fo_n2 = P::const_dword(oseq, pw_clampi(wo + 2, 0, owlast));
-      fm_n0 = P::const_dword(mseq, pw_clampi(wm, 0, mwlast)); fm_n1 = P::const_dword(mseq, pw_clampi(wm + 1, 0, mwlast));
-      fm_n2 = P::const_dword(mseq, pw_clampi(wm + 2, 0, mwlast));
-      return;
-    }
-    fo_n0 = o32[pw_clampi(wo, 0, owlast)]; fo_n1 = o32[pw_clampi(wo + 1, 0, owlast)]; fo_n2 = o32[pw_clampi(wo + 2, 0, owlast)];
-    fm_n0 = m32[pw_clampi(wm, 0, mwlast)]; fm_n1 = m32[pw_clampi(wm + 1, 0, mwlast)]; fm_n2 = m32[pw_clampi(wm + 2, 0, mwlast)];
+    fo_n0 = o32[pw_clampi(wo, 0, owlast)]; fo_n12 = dwords(o32[pw_clampi(wo + 1, 0, owlast)], o32[pw_clampi(wo + 2, 0, owlast)]);
+    fm_n0 = m32[pw_clampi(wm, 0, mwlast)]; fm_n12 = dwords(m32[pw_clampi(wm + 1, 0, mwlast)], m32[pw_clampi(wm + 2, 0, mwlast)]);
   }
   // bytes k = 0 .. 7 of the result are 0xff where i0 + k lies in [0, n), 0 elsewhere
   // (one pair per wavefront: the arguments are wave-uniform, and a clamp written as one expression is selected as a vector
@@ -1225,19 +1318,42 @@ struct WaveFill16 {
   template <bool RT = false>
   PW_FN void feed_commit(int b, bool edge) {
     const int ro = (xfeed_o + 8 * b) & 3, rm = (yfeed_m + 8 * b) & 3;
-    fo_lo = Base::funnel(fo_n1, fo_n0, ro); fo_hi = Base::funnel(fo_n2, fo_n1, ro);
-    fm_lo = Base::funnel(fm_n1, fm_n0, rm); fm_hi = Base::funnel(fm_n2, fm_n1, rm);
+    if (!SEG) {      // (a window the block before could not load ahead: feed_issue; the first block's is loaded, and stays)
+      // (ONE branch in front of both: a test of its own per sequence opened the loop with a block of two instructions, which
+      //  the block placement copied into the loop's closing block)
+      const bool late_o = fo_w >= fo_lim, late_m = fm_w >= fm_lim;
+      if (late_o | late_m) {
+        if (late_o) feed_late(oseq, owlast, fo_w, fo_n0, fo_n12, 0);
+        if (late_m) feed_late(mseq, mwlast, fm_w, fm_n0, fm_n12, 1);
+      }
+    }
+    fo_lo = Base::funnel((uint32_t)fo_n12, fo_n0, ro); fo_hi = (uint32_t)(fo_n12 >> (8 * ro));
+    fm_lo = Base::funnel((uint32_t)fm_n12, fm_n0, rm); fm_hi = (uint32_t)(fm_n12 >> (8 * rm));
+    if (FROWS) {
+#pragma unroll
+      for (int k = 0; k < 8; k++) frow[k] = row_bits(fo_lo, fo_hi, k);
+    }
     if (MAT && edge) {
       const uint64_t io = inside_bytes(xfeed_o + 8 * b, X), im = inside_bytes(yfeed_m + 8 * b, Y);
-      const uint64_t o = ((((uint64_t)fo_hi) << 32) | fo_lo) | ~io;
       const uint64_t m = (((((uint64_t)fm_hi) << 32) | fm_lo) & im) | ((0x0101010101010101ull * MOUT) & ~im);
-      fo_lo = (uint32_t)o; fo_hi = (uint32_t)(o >> 32);
       fm_lo = (uint32_t)m; fm_hi = (uint32_t)(m >> 32);
+      if (FROWS) {
+        // the rows are there already: a letter outside the sequence gets the all-zero row here, once per block, and the
+        // selection per letter (row_bits) knows the four real rows only
+        // (the halves apart and opaque: on the 64-bit value a test of the top byte became a 64-bit unsigned compare, which
+        //  exists as a vector instruction only)
+        const uint32_t io_lo = pk::opaque_su((uint32_t)io), io_hi = pk::opaque_su((uint32_t)(io >> 32));
+#pragma unroll
+        for (int k = 0; k < 8; k++) frow[k] = (((k < 4 ? io_lo : io_hi) >> (8 * (k & 3))) & 1u) ? frow[k] : 0u;
+      } else {
+        const uint64_t o = ((((uint64_t)fo_hi) << 32) | fo_lo) | ~io;
+        fo_lo = (uint32_t)o; fo_hi = (uint32_t)(o >> 32);
+      }
       // (seen as the halves of one 64-bit value, "the last letter is 0" became a 64-bit unsigned compare, which exists as a
       //  vector instruction only)
-      if (!SEG && !RT) { fo_hi = pk::opaque_su(fo_hi); fm_hi = pk::opaque_su(fm_hi); }
+      if (!SEG && !RT) { if (!FROWS) fo_hi = pk::opaque_su(fo_hi); fm_hi = pk::opaque_su(fm_hi); }
     }
-    if (MAT && !SEG && RT) { fo_hi = pk::opaque_su(fo_hi); fm_hi = pk::opaque_su(fm_hi); }
+    if (MAT && !SEG && RT) { if (!FROWS) fo_hi = pk::opaque_su(fo_hi); fm_hi = pk::opaque_su(fm_hi); }
   }
 
   PW_FN int tfirst_of(int j) const {      // first step of slot j's diagonal; never for a diagonal outside the band
@@ -1266,6 +1382,16 @@ struct WaveFill16 {
     r = l == 2u ? MR2 : r;
     r = l == 1u ? MR1 : r;
     return l == 0u ? MR0 : r;
+  }
+  // ... of the k-th letter of a block's 8 origin letters, selected on the letter's two bits where they lie in the feed
+  // words (k is a constant in the unrolled block): two bit tests and three selects -- against four compares and four
+  // selects behind an extraction of the letter.  Knows letters 0 .. 3 only: feed_commit gives the letters outside the
+  // sequence their all-zero row.
+  PW_FN uint32_t row_bits(uint32_t lo, uint32_t hi, int k) const {
+    const uint32_t w = k < 4 ? lo : hi;
+    const bool b0 = (w & (1u << (8 * (k & 3)))) != 0, b1 = (w & (2u << (8 * (k & 3)))) != 0;
+    const uint32_t r01 = b0 ? MR1 : MR0, r23 = b0 ? MR3 : MR2;
+    return b1 ? r23 : r01;
   }
   PW_FN uint32_t row_at(int i) const { return (uint32_t)i < (uint32_t)X ? row_of((uint32_t)oseq[i]) : 0u; }
   // selector code of mutant letter i; plus4: the code reads v_perm_b32's first operand
@@ -1305,6 +1431,8 @@ struct WaveFill16 {
     const int xbase = e + li * R, ybase = f - li * R;
     xfeed_o = e + nl * R - 1;                   // the letter a virtual lane `nl` would hand down
     yfeed_m = f;
+    fo_w = (uint32_t)xfeed_o & ~3u; fm_w = (uint32_t)yfeed_m & ~3u;
+    fo_lim = 4u * (uint32_t)(owlast > 1 ? owlast - 1 : 0); fm_lim = 4u * (uint32_t)(mwlast > 1 ? mwlast - 1 : 0);
     rf = RAMPF && ramp_free_on();
     ONE = pk::opaque(0x00010001u); SH15 = pk::opaque(0x000f000fu);
     C2 = pk::opaque(0x00020002u); C4 = pk::opaque(0x00040004u); C16 = pk::opaque(0x00100010u);
@@ -1366,7 +1494,7 @@ struct WaveFill16 {
       for (int g = 0; g < BK / 4; g++)   // (opaque: left to itself the compiler adds the group's distance per lane, in 64 bits)
         mbase[g] = pk::opaque_s((uint8_t*)(a.masks + pd.mask_off) + (uint64_t)(4u * (uint32_t)g * mgroup));
     }
-    feed_issue(0);
+    feed_issue<true>(0);
     if constexpr (SPLIT) {
       // One loop per kind of block, in the order a pair runs through them: with a single body the loop-carried state stays in
       // the registers it was computed in.  (One loop that chose among the four bodies joined them in a shared tail, and the
