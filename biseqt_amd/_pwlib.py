@@ -173,16 +173,21 @@ QSEED_EXPORTS = ['pw_qseeds_create', 'pw_qseeds_build', 'pw_qseeds_build_strande
 # every symbol include/pw_overlap.h declares
 OVERLAP_EXPORTS = ['pw_overlap_bands', 'pw_overlap_all_pairs', 'pw_overlap_last_ms', 'pw_overlap_last_error',
                    'pw_overlap_bands_stranded', 'pw_overlap_all_pairs_stranded', 'pw_overlap_all_pairs_capped', 'pw_overlap_arena_upload',
-                   'pw_overlap_arena_read']
+                   'pw_overlap_arena_read', 'pw_overlap_all_pairs_sampled']
 PW_STRAND_PLUS, PW_STRAND_MINUS, PW_STRAND_BOTH = 1, 2, 3
 # every symbol include/pw_kmers.h declares
 KMERS_EXPORTS = ['pw_kmers_create', 'pw_kmers_build', 'pw_kmers_num_entries', 'pw_kmers_num_distinct', 'pw_kmers_distinct',
                  'pw_kmers_lookup', 'pw_kmers_hits', 'pw_kmers_spectrum', 'pw_kmers_occurrences', 'pw_kmers_destroy',
-                 'pw_kmers_last_ms', 'pw_kmers_last_error']
+                 'pw_kmers_last_ms', 'pw_kmers_last_error', 'pw_kmers_build_sampled', 'pw_kmers_num_positions', 'pw_kmers_rows',
+                 'pw_kmers_read_starts']
 
 
 class pw_overlap_cap_stats(C.Structure):
     _fields_ = [(f, C.c_uint64) for f in ('entries', 'masked_entries', 'distinct_masked', 'seeds_kept', 'seeds_dropped')]
+
+
+class pw_overlap_sample_stats(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ('positions', 'sampled')]
 
 
 class pw_read_pair(C.Structure):
@@ -442,6 +447,7 @@ def load():
                                                   C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64,
                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.pw_overlap_all_pairs_capped.argtypes = lib.pw_overlap_all_pairs_stranded.argtypes + [C.c_uint32, P(pw_overlap_cap_stats)]
+    lib.pw_overlap_all_pairs_sampled.argtypes = lib.pw_overlap_all_pairs_capped.argtypes + [C.c_int, P(pw_overlap_sample_stats)]
     lib.pw_overlap_arena_upload.argtypes = [C.c_int, C.c_void_p, C.c_uint64, C.c_uint64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_int]
     lib.pw_overlap_arena_upload.restype = C.c_void_p
@@ -452,6 +458,12 @@ def load():
     lib.pw_kmers_create.argtypes = [C.c_int, C.c_int, C.c_int]
     lib.pw_kmers_create.restype = C.c_void_p
     lib.pw_kmers_build.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]
+    lib.pw_kmers_build_sampled.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int,
+                                           C.c_void_p]
+    lib.pw_kmers_num_positions.argtypes = [C.c_void_p]
+    lib.pw_kmers_num_positions.restype = C.c_int64
+    lib.pw_kmers_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
+    lib.pw_kmers_read_starts.argtypes = [C.c_void_p, C.c_void_p]
     lib.pw_kmers_num_entries.argtypes = [C.c_void_p]
     lib.pw_kmers_num_entries.restype = C.c_int64
     lib.pw_kmers_num_distinct.argtypes = [C.c_void_p]

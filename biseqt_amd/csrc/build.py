@@ -122,11 +122,11 @@ def _jobs():
                   os.path.join(ROOT, 'include', 'pw_qseeds.h')]))
     obj = os.path.join(OBJ_DIR, 'pw_overlap.o')
     jobs.append((obj, [HIPCC] + COMMON + ['-Wno-unused-parameter', '-c', os.path.join(HERE, 'pw_overlap.hip'), '-o', obj],
-                 [os.path.join(HERE, 'pw_overlap.hip'), os.path.join(HERE, 'pw_complement.h'), os.path.join(HERE, 'pw_kmer_encode.h'),
+                 [os.path.join(HERE, 'pw_overlap.hip'), os.path.join(HERE, 'pw_complement.h'), os.path.join(HERE, 'pw_kmer_encode.h'), os.path.join(HERE, 'pw_minimizer.h'),
                   os.path.join(ROOT, 'include', 'pw_overlap.h')]))
     obj = os.path.join(OBJ_DIR, 'pw_kmers.o')
     jobs.append((obj, [HIPCC] + COMMON + ['-Wno-unused-parameter', '-c', os.path.join(HERE, 'pw_kmers.hip'), '-o', obj],
-                 [os.path.join(HERE, 'pw_kmers.hip'), os.path.join(HERE, 'pw_complement.h'), os.path.join(HERE, 'pw_kmer_encode.h'),
+                 [os.path.join(HERE, 'pw_kmers.hip'), os.path.join(HERE, 'pw_complement.h'), os.path.join(HERE, 'pw_kmer_encode.h'), os.path.join(HERE, 'pw_minimizer.h'),
                   os.path.join(ROOT, 'include', 'pw_kmers.h'), os.path.join(ROOT, 'include', 'pw_overlap.h')]))
     obj = os.path.join(OBJ_DIR, 'pwlib_api.o')
     jobs.append((obj, [HIPCC] + COMMON + ['-x', 'hip', '-c', os.path.join(HERE, 'pwlib_api.cpp'), '-o', obj],

@@ -12,6 +12,8 @@
 //   K14d k_kmers_spectrum grid-stride over the runs: histogram of min(count, max_mult) in LDS, flushed once per workgroup
 //   K14e k_kmers_lookup   one thread per query: a binary search over the D distinct keys
 //   K14f k_kmers_occ      one thread per row: a forward row writes its run's length to (read, pos)
+// A SAMPLED table (pw_kmers_build_sampled, window > 1) holds the window minimizers only: K15a-c of pw_minimizer.h stand in for
+// the encoders, everything from the sort on is the same, and K15d k_mini_occ stands in for K14f.
 // Everything is asynchronous on the stream of the build; the number of runs stays on the device until a call returns host
 // data.
 #include <hip/hip_runtime.h>
@@ -27,6 +29,7 @@
 #include "pw_complement.h"
 #include "pw_hip_host.h"
 #include "pw_kmer_encode.h"
+#include "pw_minimizer.h"
 
 namespace {
 
@@ -115,6 +118,20 @@ __global__ __launch_bounds__(256) void k_kmers_occ(const uint64_t* __restrict__ 
   occ[rstart[v >> 32] + (v & (kStrandBit - 1))] = run_count(ustart, u);
 }
 
+// K15d: K14f of a sampled table.  fhits: the hits of the sampled forward rows in (read, pos) order (they ascend): the place of
+// a forward row among them is where its run's length goes.
+__global__ __launch_bounds__(256) void k_mini_occ(const uint64_t* __restrict__ hits, int64_t n, const uint64_t* __restrict__ ustart,
+                                                  const unsigned long long* __restrict__ n_runs, const uint64_t* __restrict__ fhits,
+                                                  int64_t n_fwd, uint32_t* __restrict__ occ) {
+  const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (g >= n) return;
+  const uint64_t v = hits[g];
+  if (v & kStrandBit) return;
+  const int64_t D = (int64_t)*n_runs;
+  const int64_t u = upper_bound_dev<uint64_t>(ustart, D, (uint64_t)g) - 1;
+  occ[lower_bound_dev<uint64_t>(fhits, n_fwd, v)] = run_count(ustart, u);
+}
+
 }  // namespace
 
 struct pw_kmer_index {
@@ -122,6 +139,9 @@ struct pw_kmer_index {
   bool built = false;
   int64_t R = 0;
   uint64_t K = 0, N = 0;                               // forward rows, rows
+  uint64_t P = 0;                                      // forward positions: K, more where the table is sampled
+  bool sampled = false;                                // built with a window above 1
+  MiniSample mini; DeviceArray<uint64_t> fhits;        // (sampled) the selection; the forward hits in (read, pos) order
   int64_t D = -1;                                      // distinct keys; -1: still on the device (n_runs)
   hipStream_t stream = nullptr;
   DeviceArray<uint8_t> arena, comp; DeviceArray<uint64_t> roff, rstart; DeviceArray<int32_t> rlen;     // the reads
@@ -174,10 +194,58 @@ int lookup(pw_kmer_index* x, const uint64_t* keys, int64_t n, uint32_t* counts_o
   return 0;
 }
 
+// the staged rows (kin, vin) -> the sorted table and its runs; ends the build's timing
+int sort_and_runs(pw_kmer_index* x, int kbits) {
+  const hipStream_t st = x->stream;
+  const uint64_t N = x->N;
+  CHECK(sort_pairs(x->tmp, x->kin, x->keys, x->vin, x->hits, (size_t)N, kbits, st));
+  // the staging buffers are free again: run heads in kin, their ranks in vin
+  hipLaunchKernelGGL(k_kmers_heads, rows_grid(N), kBlock256, 0, st, x->keys.p, (int64_t)N, x->kin.p);
+  CHECK(scan_u64(x->tmp, x->kin, x->vin, (size_t)N, st));
+  hipLaunchKernelGGL(k_kmers_runs, rows_grid(N), kBlock256, 0, st, x->keys.p, x->kin.p, x->vin.p, (int64_t)N, x->ukeys.p, x->ustart.p,
+                     x->n_runs.p);
+  CHECK(hipEventRecord(x->bev1.e, st));
+  CHECK(hipGetLastError());
+  x->built = true;
+  return 0;
+}
+
+// The build of a sampled table, from the uploads on (x->K holds the unsampled forward positions on entry).  The order value
+// is canonical exactly when the table holds both strands.  K15a and its scan run first and the host waits for the row count:
+// the table's buffers are sized by it, not by the positions.
+int build_sampled(pw_kmer_index* x, const uint8_t* arena, uint64_t arena_bytes, const uint64_t* read_off, const int32_t* read_len,
+                  const std::vector<uint64_t>& rstart, const uint8_t* complement, int window) {
+  const hipStream_t st = x->stream;
+  const bool both = x->strands == PW_STRAND_BOTH;
+  const int64_t R = x->R;
+  const uint64_t P = x->P;
+  if (upload(set_err, x->arena, arena, (size_t)arena_bytes, st) != 0 || upload(set_err, x->roff, read_off, (size_t)R, st) != 0 ||
+      upload(set_err, x->rlen, read_len, (size_t)R, st) != 0 || upload(set_err, x->rstart, rstart.data(), (size_t)R + 1, st) != 0)
+    return -1;
+  if (both && upload_complement(set_err, complement, x->L, x->comp, st) != 0) return -1;
+  CHECK(x->n_runs.ensure(1));
+  CHECK(hipStreamSynchronize(st));                     // the host arrays are the caller's again
+  CHECK(hipEventRecord(x->bev0.e, st));
+  if (x->mini.count(set_err, x->tmp, x->arena.p, x->roff.p, x->rstart.p, R, P, x->k, x->L, window, both, x->comp.p, st) != 0) return -1;
+  const uint64_t K = x->mini.rows, N = both ? 2 * K : K;
+  x->K = K; x->N = N;
+  CHECK(x->kin.ensure((size_t)N)); CHECK(x->vin.ensure((size_t)N)); CHECK(x->keys.ensure((size_t)N)); CHECK(x->hits.ensure((size_t)N));
+  CHECK(x->ukeys.ensure((size_t)N)); CHECK(x->ustart.ensure((size_t)N + 1)); CHECK(x->fhits.ensure((size_t)K));
+  x->mini.emit(false, x->arena.p, x->roff.p, x->rstart.p, R, x->k, x->L, x->comp.p, x->kin.p, x->vin.p, st);
+  CHECK(hipMemcpyAsync(x->fhits.p, x->vin.p, x->fhits.bytes((size_t)K), hipMemcpyDeviceToDevice, st));
+  x->mini.read_starts(x->fhits.p, R, st);
+  if (both) {
+    x->mini.emit(true, x->arena.p, x->roff.p, x->rstart.p, R, x->k, x->L, x->comp.p, x->kin.p + K, x->vin.p + K, st);
+    hipLaunchKernelGGL(k_kmers_tag, rows_grid(K), kBlock256, 0, st, x->vin.p + K, (int64_t)K);
+  }
+  return sort_and_runs(x, x->kbits);
+}
+
 int build(pw_kmer_index* x, const uint8_t* arena, uint64_t arena_bytes, const uint64_t* read_off, const int32_t* read_len,
-          int64_t n_reads, int strands, const uint8_t* complement, hipStream_t st) {
+          int64_t n_reads, int strands, const uint8_t* complement, hipStream_t st, int window = 1) {
   if (!x) { set_err("bad arguments"); return -1; }
   if (strands != PW_STRAND_PLUS && strands != PW_STRAND_BOTH) { set_err("strands must be 1 (+) or 3 (both)"); return -1; }
+  if (window < 1 || window > kMiniMaxWindow) { set_err("window must be 1..128"); return -1; }
   if (strands == PW_STRAND_BOTH && check_complement(set_err, complement, x->L) != 0) return -1;
   int kbits = 0;
   if (check_args(set_err, x->L, x->k, n_reads < 0 || n_reads >= (1ll << 31) || (n_reads && (!read_off || !read_len)) || (arena_bytes && !arena),
@@ -199,9 +267,11 @@ int build(pw_kmer_index* x, const uint8_t* arena, uint64_t arena_bytes, const ui
   CHECK(hipSetDevice(x->device));
   x->built = false;
   if (x->stream != st && x->D < 0 && x->N) CHECK(hipStreamSynchronize(x->stream));    // (a build still running on another stream)
-  const uint64_t N = both ? 2 * K : K;
-  x->stream = st; x->strands = strands; x->R = n_reads; x->K = K; x->N = N; x->D = N ? -1 : 0;
+  uint64_t N = both ? 2 * K : K;
+  x->stream = st; x->strands = strands; x->R = n_reads; x->K = K; x->P = K; x->N = N; x->D = N ? -1 : 0;
+  x->sampled = window > 1 && N != 0;
   if (N == 0) { x->built = true; return 0; }
+  if (x->sampled) return build_sampled(x, arena, arena_bytes, read_off, read_len, rstart, complement, window);
   CHECK(x->kin.ensure((size_t)N)); CHECK(x->vin.ensure((size_t)N)); CHECK(x->keys.ensure((size_t)N)); CHECK(x->hits.ensure((size_t)N));
   CHECK(x->ukeys.ensure((size_t)N)); CHECK(x->ustart.ensure((size_t)N + 1)); CHECK(x->n_runs.ensure(1));
   if (upload(set_err, x->arena, arena, (size_t)arena_bytes, st) != 0 || upload(set_err, x->roff, read_off, (size_t)n_reads, st) != 0 ||
@@ -218,16 +288,7 @@ int build(pw_kmer_index* x, const uint8_t* arena, uint64_t arena_bytes, const ui
                        x->k, x->L, x->comp.p, x->kin.p + K, x->vin.p + K);
     hipLaunchKernelGGL(k_kmers_tag, rows_grid(K), kBlock256, 0, st, x->vin.p + K, (int64_t)K);
   }
-  CHECK(sort_pairs(x->tmp, x->kin, x->keys, x->vin, x->hits, (size_t)N, kbits, st));
-  // the staging buffers are free again: run heads in kin, their ranks in vin
-  hipLaunchKernelGGL(k_kmers_heads, rows_grid(N), kBlock256, 0, st, x->keys.p, (int64_t)N, x->kin.p);
-  CHECK(scan_u64(x->tmp, x->kin, x->vin, (size_t)N, st));
-  hipLaunchKernelGGL(k_kmers_runs, rows_grid(N), kBlock256, 0, st, x->keys.p, x->kin.p, x->vin.p, (int64_t)N, x->ukeys.p, x->ustart.p,
-                     x->n_runs.p);
-  CHECK(hipEventRecord(x->bev1.e, st));
-  CHECK(hipGetLastError());
-  x->built = true;
-  return 0;
+  return sort_and_runs(x, kbits);
 }
 
 }  // namespace
@@ -252,6 +313,32 @@ pw_kmer_index* pw_kmers_create(int device, int alphabet_len, int wordlen) {
 int pw_kmers_build(pw_kmer_index* x, const uint8_t* arena, uint64_t arena_bytes, const uint64_t* read_off, const int32_t* read_len,
                    int64_t n_reads, int strands, const uint8_t* complement, void* stream) {
   return build(x, arena, arena_bytes, read_off, read_len, n_reads, strands, complement, (hipStream_t)stream);
+}
+
+int pw_kmers_build_sampled(pw_kmer_index* x, const uint8_t* arena, uint64_t arena_bytes, const uint64_t* read_off, const int32_t* read_len,
+                           int64_t n_reads, int strands, const uint8_t* complement, int window, void* stream) {
+  return build(x, arena, arena_bytes, read_off, read_len, n_reads, strands, complement, (hipStream_t)stream, window);
+}
+
+int64_t pw_kmers_num_positions(const pw_kmer_index* x) { return x && x->built ? (int64_t)x->P : -1; }
+
+int pw_kmers_rows(pw_kmer_index* x, uint64_t* keys_out, uint64_t* hits_out, int64_t cap) {
+  if (ready(x, "pw_kmers_rows") != 0) return -1;
+  if (cap < (int64_t)x->N) { set_err("pw_kmers_rows: capacity too small"); return -1; }
+  if (x->N == 0) return 0;
+  if (!keys_out || !hits_out) { set_err("bad arguments"); return -1; }
+  CHECK(hipMemcpy(keys_out, x->keys.p, x->keys.bytes((size_t)x->N), hipMemcpyDeviceToHost));
+  CHECK(hipMemcpy(hits_out, x->hits.p, x->hits.bytes((size_t)x->N), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int pw_kmers_read_starts(pw_kmer_index* x, uint64_t* out) {
+  if (ready(x, "pw_kmers_read_starts") != 0) return -1;
+  if (!out) { set_err("bad arguments"); return -1; }
+  const size_t n = (size_t)x->R + 1;
+  if (x->N == 0) { std::fill(out, out + n, 0ull); return 0; }
+  CHECK(hipMemcpy(out, x->sampled ? x->mini.starts.p : x->rstart.p, n * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  return 0;
 }
 
 int64_t pw_kmers_num_entries(const pw_kmer_index* x) { return x && x->built ? (int64_t)x->N : -1; }
@@ -325,8 +412,12 @@ int pw_kmers_occurrences(pw_kmer_index* x, uint32_t* occ_out) {
   DeviceArray<uint32_t> docc;
   CHECK(docc.ensure((size_t)x->K));
   if (query_begin(x) != 0) return -1;
-  hipLaunchKernelGGL(k_kmers_occ, rows_grid(x->N), kBlock256, 0, x->stream, x->hits.p, (int64_t)x->N, x->ustart.p, x->n_runs.p, x->rstart.p,
-                     docc.p);
+  if (x->sampled)
+    hipLaunchKernelGGL(k_mini_occ, rows_grid(x->N), kBlock256, 0, x->stream, x->hits.p, (int64_t)x->N, x->ustart.p, x->n_runs.p, x->fhits.p,
+                       (int64_t)x->K, docc.p);
+  else
+    hipLaunchKernelGGL(k_kmers_occ, rows_grid(x->N), kBlock256, 0, x->stream, x->hits.p, (int64_t)x->N, x->ustart.p, x->n_runs.p, x->rstart.p,
+                       docc.p);
   if (query_end(x) != 0) return -1;
   CHECK(hipMemcpy(occ_out, docc.p, docc.bytes((size_t)x->K), hipMemcpyDeviceToHost));
   return 0;

@@ -27,6 +27,7 @@
 #include "pw_complement.h"
 #include "pw_hip_host.h"
 #include "pw_kmer_encode.h"
+#include "pw_minimizer.h"
 
 namespace {
 
@@ -652,6 +653,9 @@ struct AllPairs {
   const uint8_t* d_arena; const uint8_t* d_comp;
   int64_t R; int L, k, kbits, sel, shard_rank, shard_world; int64_t max_pairs; BandConst bc;
   uint32_t max_occ;                                    // 0: no cap, K9b / K9b' as they always were
+  int window;                                          // above 1: the index holds the window minimizers only (pw_minimizer.h)
+  MiniSample mini;                                     // (window > 1) the selection: K15a's bitmap and ranks, the reads' sampled starts
+  uint64_t positions = 0;                              // forward positions of the read set: K before sampling
   pw_overlap_cap_stats cap{};                          // (max_occ != 0) filled by self_join
   DeviceArray<unsigned long long> dstats;              // the three counters of the cap
   bool st = false;                                     // sel != 1
@@ -666,8 +670,12 @@ struct AllPairs {
   DeviceArray<pw_overlap_band> dout; DeviceArray<uint32_t> hist;                                                 // score_tiers: the records
 
   // Stage 1, once per strand: K9a (K9a' for the reverse strand) into kin / vin, then the stable sort by k-mer.
+  // Sampled: K15b writes the selected rows of the strand instead (the reverse strand from the same flags, after K15c).
   int build_index(bool reverse) {
-    if (reverse)
+    if (window > 1) {
+      mini.emit(reverse, d_arena, droff.p, drstart.p, R, k, L, d_comp, kin.p, vin.p, nullptr);
+      if (!reverse && st) mini.read_starts(vin.p, R, nullptr);     // K15c, while vin holds the forward hits in (read, pos) order
+    } else if (reverse)
       hipLaunchKernelGGL(k_enc_reads_rc, rows_grid(K), blk, 0, nullptr, d_arena, droff.p, drlen.p, drstart.p, R, (int64_t)K, k, L, d_comp,
                          kin.p, vin.p);
     else
@@ -805,14 +813,31 @@ struct AllPairs {
                  : "more than 2^32 k-mers in one index: split the read set");
       return -1;
     }
-    DeviceEvent ev0, ev1;
+    positions = K;
+    DeviceEvent ev0, ev1, evs0, evs1;
     CHECK(ev0.create()); CHECK(ev1.create());
+    auto upload_reads = [&]() -> int {
+      return upload(set_err, droff, read_off, (size_t)R) != 0 || upload(set_err, drlen, read_len, (size_t)R) != 0 ||
+                     upload(set_err, drstart, rstart.data(), (size_t)R + 1) != 0
+                 ? -1 : 0;
+    };
+    float ms_sample = 0.f;
+    if (window > 1) {
+      // The selection comes first: K15a, its scan, and the host waits for the number of rows, which becomes K -- the index and
+      // everything behind it are sized by it.  Timed by its own pair of events, so that still no allocation is timed.
+      CHECK(evs0.create()); CHECK(evs1.create());
+      if (mini.reserve(set_err, R, K) != 0 || upload_reads() != 0) return -1;
+      CHECK(hipEventRecord(evs0.e, nullptr));
+      if (mini.count(set_err, tmp, d_arena, droff.p, drstart.p, R, K, k, L, window, st, d_comp, nullptr) != 0) return -1;
+      CHECK(hipEventRecord(evs1.e, nullptr));
+      CHECK(hipEventSynchronize(evs1.e));
+      CHECK(hipEventElapsedTime(&ms_sample, evs0.e, evs1.e));
+      K = mini.rows;
+    }
     // what the forward strand needs is allocated before the first event: no allocation of it is timed
     CHECK(kin.ensure((size_t)K)); CHECK(vin.ensure((size_t)K)); CHECK(ks.ensure((size_t)K)); CHECK(vs.ensure((size_t)K));
     CHECK(fs.ensure((size_t)K)); CHECK(cnt.ensure((size_t)K)); CHECK(off.ensure((size_t)K));
-    if (upload(set_err, droff, read_off, (size_t)R) != 0 || upload(set_err, drlen, read_len, (size_t)R) != 0 ||
-        upload(set_err, drstart, rstart.data(), (size_t)R + 1) != 0)
-      return -1;
+    if (window <= 1 && upload_reads() != 0) return -1;
     CHECK(hipEventRecord(ev0.e, nullptr));
     if (build_index(false) != 0) return -1;
     if (st) {
@@ -829,6 +854,7 @@ struct AllPairs {
     if (st) CHECK(hipMemcpy(pair_strand, dps.p, (size_t)NP, hipMemcpyDeviceToHost));
     CHECK(hipGetLastError());
     CHECK(hipEventElapsedTime(ms, ev0.e, ev1.e));
+    *ms += ms_sample;
     *n_out = (int64_t)NP;
     return 0;
   }
@@ -853,8 +879,10 @@ int all_pairs(int device, const uint8_t* arena, uint64_t arena_bytes, const uint
               int64_t n_reads, int alphabet_len, int wordlen, double len_coeff, double radius_coeff, double word_p_null,
               bool stranded, const uint8_t* complement, int strands, int shard_rank, int shard_world, int64_t max_pairs,
               int32_t* pair_a, int32_t* pair_b, uint8_t* pair_strand, pw_overlap_band* out, int64_t* n_out, uint32_t max_occ = 0,
-              pw_overlap_cap_stats* stats = nullptr) {
+              pw_overlap_cap_stats* stats = nullptr, int window = 0, pw_overlap_sample_stats* sample = nullptr) {
   if (stats) memset(stats, 0, sizeof *stats);
+  if (sample) memset(sample, 0, sizeof *sample);
+  if (window < 0 || window > kMiniMaxWindow) { set_err("window must be 0..128"); return -1; }
   if (stranded) {
     if (strands < PW_STRAND_PLUS || strands > PW_STRAND_BOTH) { set_err("strands must be 1 (+), 2 (-) or 3 (both)"); return -1; }
     if (strands != PW_STRAND_PLUS && check_complement(complement, alphabet_len) != 0) return -1;
@@ -873,9 +901,10 @@ int all_pairs(int device, const uint8_t* arena, uint64_t arena_bytes, const uint
   if (strands != PW_STRAND_PLUS && upload_complement(complement, alphabet_len, d_comp) != 0) return -1;
   float ms = 0.f;
   AllPairs job{d_arena.p, d_comp.p, n_reads, alphabet_len, wordlen, kbits, strands, shard_rank, shard_world,
-               max_pairs, BandConst{len_coeff, radius_coeff, word_p_null}, max_occ};
+               max_pairs, BandConst{len_coeff, radius_coeff, word_p_null}, max_occ, window};
   const int rc = job.run(read_off, read_len, pair_a, pair_b, pair_strand, out, n_out, &ms);
   if (stats) *stats = job.cap;                         // (what the join counted, also where a refusal followed it)
+  if (sample) *sample = pw_overlap_sample_stats{job.positions, job.K};
   if (rc == 0 && stranded && strands == PW_STRAND_PLUS) memset(pair_strand, 0, (size_t)*n_out);
   g_ms = (double)ms;
   return rc;
@@ -962,6 +991,17 @@ int pw_overlap_all_pairs_capped(int device, const uint8_t* arena, uint64_t arena
                                 pw_overlap_band* out, int64_t* n_out, uint32_t max_occ, pw_overlap_cap_stats* stats) {
   return all_pairs(device, arena, arena_bytes, read_off, read_len, n_reads, alphabet_len, wordlen, len_coeff, radius_coeff, word_p_null,
                    true, complement, strands, shard_rank, shard_world, max_pairs, pair_a, pair_b, pair_strand, out, n_out, max_occ, stats);
+}
+
+int pw_overlap_all_pairs_sampled(int device, const uint8_t* arena, uint64_t arena_bytes, const uint64_t* read_off,
+                                 const int32_t* read_len, int64_t n_reads, int alphabet_len, int wordlen, double len_coeff,
+                                 double radius_coeff, double word_p_null, const uint8_t* complement, int strands, int shard_rank,
+                                 int shard_world, int64_t max_pairs, int32_t* pair_a, int32_t* pair_b, uint8_t* pair_strand,
+                                 pw_overlap_band* out, int64_t* n_out, uint32_t max_occ, pw_overlap_cap_stats* stats, int window,
+                                 pw_overlap_sample_stats* sample) {
+  return all_pairs(device, arena, arena_bytes, read_off, read_len, n_reads, alphabet_len, wordlen, len_coeff, radius_coeff, word_p_null,
+                   true, complement, strands, shard_rank, shard_world, max_pairs, pair_a, pair_b, pair_strand, out, n_out, max_occ, stats,
+                   window, sample);
 }
 
 void* pw_overlap_arena_upload(int device, const uint8_t* host_arena, uint64_t bytes, uint64_t total_bytes, int64_t n_frames,

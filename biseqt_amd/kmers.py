@@ -11,6 +11,10 @@ storage: ``index_kmers``, ``hits`` and ``kmers`` with the reference's arguments 
 lookup), :meth:`KmerIndex.spectrum` (count of counts) and :meth:`KmerIndex.occurrences` (the per-position repeat profile
 of a sequence).  :func:`kmer_spectrum` builds one from a read list in one call.  A database ``path``, masked indexing and
 ``KmerCache`` are storage or out of scope and are refused or absent.
+
+``window`` (:class:`KmerIndex`, :func:`kmer_spectrum`) samples the table by WINDOW MINIMIZERS (``include/pw_kmers.h`` states the
+rule): only the positions whose order value is the minimum of some window of ``window`` consecutive positions of their read are
+rows, every query answers from those rows, and :attr:`KmerIndex.density` tells which share of the positions they are.
 """
 import ctypes as C
 
@@ -28,6 +32,16 @@ def check_limits(alphabet, wordlen):
     assert len(alphabet) <= len(DIGITS), 'Maximum alphabet size of %d exceeded' % len(DIGITS)
     assert wordlen < (64 - 1) / 2., 'Maximum kmer length %d for %d-bit integers exceeded' % (wordlen, 64)
     assert len(alphabet) ** wordlen < 2 ** 62, 'alphabet size ** word length must stay below 2^62'
+
+
+def check_window(window, name='window'):
+    """A minimizer window of the Python calls: None or 0 (no sampling), or an integer in 1..128 (1 selects every position).
+    Returns the integer the C calls take (0 for None); anything else is a ValueError."""
+    if window is None:
+        return 0
+    if isinstance(window, bool) or not isinstance(window, (int, np.integer)) or not 0 <= int(window) <= 128:
+        raise ValueError('%s is None or an integer in 1..128, not %r' % (name, window))
+    return int(window)
 
 
 def kmer_as_int(contents, alphabet):
@@ -70,9 +84,16 @@ class KmerIndex(object):
     ``strands='both'`` (with ``complement``: a table, or the ``mappings`` of ``Alphabet.transform``) adds, for every
     position, the k-mer of the reverse complement of the sequence: ``count(x) = n_f(x) + n_f(rc(x))``, so a k-mer that is its
     own reverse complement counts twice, and :meth:`hits` returns ``(seqid, pos, strand)`` with ``pos`` of a strand-1 hit
-    in the frame of the reverse complement."""
+    in the frame of the reverse complement.
 
-    def __init__(self, name='', alphabet=None, wordlen=None, path=':memory:', mask=[], device=0, strands='+', complement=None):
+    ``window`` (None: every position, today's table): the table holds the window minimizers only (``pw_kmers_build_sampled``).
+    The order value of a k-mer is a fixed 64-bit mix of its key with ``strands='+'`` and of the smaller of its key and its
+    reverse complement's with ``strands='both'``; every position that attains the minimum of a window of ``window`` consecutive
+    positions is a row.  Counts, hits, the spectrum and the occurrence profile are those of the sampled rows; positions in
+    hits stay positions in the read.  :attr:`read_starts` and :meth:`occurrences` follow the sampled rows of every read."""
+
+    def __init__(self, name='', alphabet=None, wordlen=None, path=':memory:', mask=[], device=0, strands='+', complement=None,
+                 window=None):
         self.name = name
         assert all(isinstance(lets, set) for lets in mask)
         assert isinstance(wordlen, int)                   # kmers.py:263-271; the table itself takes alphabet ** wordlen == 2^62
@@ -86,6 +107,7 @@ class KmerIndex(object):
             raise ValueError('KmerIndex does not support masked indexing: mask must be empty')
         if strands not in ('+', 'both'):
             raise ValueError("strands is '+' or 'both', not %r" % (strands,))
+        self.window = check_window(window)
         self.mask, self.path, self.alphabet, self.wordlen, self.device, self.strands = mask, path, alphabet, wordlen, device, strands
         self._comp = None
         if strands == 'both':
@@ -144,13 +166,20 @@ class KmerIndex(object):
             arena = np.ascontiguousarray(np.concatenate(self._reads)) if self._reads else np.zeros(0, np.uint8)
             roff = np.ascontiguousarray(offs[:-1])
             W = self._W
-            rc = self._lib.pw_kmers_build(self._handle, arena.ctypes.data, arena.size, roff.ctypes.data, lens.ctypes.data, len(lens),
-                                          W.PW_STRAND_BOTH if self.strands == 'both' else W.PW_STRAND_PLUS,
-                                          None if self._comp is None else self._comp.ctypes.data, None)
-            if rc != 0:
-                raise RuntimeError('pw_kmers_build failed: ' + self._error())
-            self._rstart = np.zeros(len(lens) + 1, np.int64)
-            self._rstart[1:] = np.cumsum(np.maximum(lens.astype(np.int64) - self.wordlen + 1, 0))
+            args = (self._handle, arena.ctypes.data, arena.size, roff.ctypes.data, lens.ctypes.data, len(lens),
+                    W.PW_STRAND_BOTH if self.strands == 'both' else W.PW_STRAND_PLUS, None if self._comp is None else self._comp.ctypes.data)
+            if self.window > 1:
+                if self._lib.pw_kmers_build_sampled(*(args + (self.window, None))) != 0:
+                    raise RuntimeError('pw_kmers_build_sampled failed: ' + self._error())
+                starts = np.zeros(len(lens) + 1, np.uint64)
+                if self._lib.pw_kmers_read_starts(self._handle, starts.ctypes.data) != 0:
+                    raise RuntimeError('pw_kmers_read_starts failed: ' + self._error())
+                self._rstart = starts.astype(np.int64)
+            else:
+                if self._lib.pw_kmers_build(*(args + (None,))) != 0:
+                    raise RuntimeError('pw_kmers_build failed: ' + self._error())
+                self._rstart = np.zeros(len(lens) + 1, np.int64)
+                self._rstart[1:] = np.cumsum(np.maximum(lens.astype(np.int64) - self.wordlen + 1, 0))
             self._dirty = False
         return self._handle
 
@@ -158,6 +187,28 @@ class KmerIndex(object):
     def num_entries(self):
         """Rows of the table."""
         return int(self._lib.pw_kmers_num_entries(self._table()))
+
+    @property
+    def num_positions(self):
+        """Forward k-mer positions of the indexed sequences, sampled or not."""
+        return int(self._lib.pw_kmers_num_positions(self._table()))
+
+    @property
+    def density(self):
+        """Forward rows per forward position: 1.0 without a window, about ``2 / (window + 1)`` on random sequence; ``nan`` for an
+        index without positions."""
+        n = self.num_positions
+        return float(self.read_starts[-1]) / n if n else float('nan')
+
+    def rows(self):
+        """``(keys uint64, hits uint64)`` of the whole table in table order: by (key, strand, read, pos), a hit is
+        ``(read << 32) | (strand << 31) | pos``."""
+        h = self._table()
+        n = int(self._lib.pw_kmers_num_entries(h))
+        keys, hits = np.zeros(n, np.uint64), np.zeros(n, np.uint64)
+        if self._lib.pw_kmers_rows(h, keys.ctypes.data, hits.ctypes.data, n) != 0:
+            raise RuntimeError('pw_kmers_rows failed: ' + self._error())
+        return keys, hits
 
     @property
     def last_ms(self):
@@ -216,7 +267,7 @@ class KmerIndex(object):
 
     def all_occurrences(self):
         """``count(k-mer at (read, pos))`` for every forward position of every read, reads in index order (uint32); read ``r``
-        (seqid ``r + 1``) starts at ``read_starts[r]``."""
+        (seqid ``r + 1``) starts at ``read_starts[r]``.  With a window: for every SAMPLED forward row, in ``(read, pos)`` order."""
         h = self._table()
         occ = np.zeros(int(self._rstart[-1]), np.uint32)
         if self._lib.pw_kmers_occurrences(h, occ.ctypes.data) != 0:
@@ -225,6 +276,7 @@ class KmerIndex(object):
 
     @property
     def read_starts(self):
+        """The forward rows before every read (``len(reads) + 1`` entries); with a window, the sampled ones."""
         self._table()
         return self._rstart
 
@@ -236,9 +288,9 @@ class KmerIndex(object):
         return occ[self._rstart[seqid - 1]:self._rstart[seqid]]
 
 
-def kmer_spectrum(reads, wordlen, alphabet, strands='+', complement=None, device=0):
+def kmer_spectrum(reads, wordlen, alphabet, strands='+', complement=None, device=0, window=None):
     """A :class:`KmerIndex` over ``reads`` (Sequences or letter arrays; equal reads stay separate reads, seqid = position in
-    the list + 1), built in one device pass."""
-    idx = KmerIndex(alphabet=alphabet, wordlen=wordlen, device=device, strands=strands, complement=complement)
+    the list + 1), built in one device pass.  ``window``: the minimizer window of :class:`KmerIndex`."""
+    idx = KmerIndex(alphabet=alphabet, wordlen=wordlen, device=device, strands=strands, complement=complement, window=window)
     idx._add_arrays(reads)
     return idx

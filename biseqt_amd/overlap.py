@@ -15,6 +15,17 @@ Both strands: reads come from either strand of the molecule, so every entry poin
 in the frame of that ``T`` (position ``j'`` of ``T`` is letter ``len(b) - 1 - j'`` of ``reads[b]``, complemented) and
 equal what the forward code returns for ``(a, rc(b))`` with ``rc(b)`` materialised.  :func:`minus_to_forward` maps a
 result back to forward coordinates of ``reads[b]``.  A read is never paired with its own reverse complement.
+
+Minimizer sampling (``minimizer_window`` of the all-pairs calls): the index holds only the window minimizers of every read
+(``include/pw_kmers.h`` states the rule), so the sort, the join and the seed sort shrink by the density, about
+``2 / (window + 1)``.  A seed then exists only between two selected k-mers.  What this means for a caller:
+
+* ``p`` of a sampled band is the estimate from the SAMPLED seeds: it lies below the unsampled one (a true overlap keeps about
+  the density's share of its seeds, and ``p`` is the ``wordlen``-th root of the seed excess per letter);
+* a ``p_min`` threshold of :func:`overlap_alignments` therefore needs rescaling by the caller -- ``stats['density']`` is there
+  for that;
+* ``d_band`` (``d_best`` / ``r_best`` of the record), which the alignment stage consumes, is unaffected in kind: the best
+  diagonal of the surviving seeds and the radius of its overlap length.
 """
 import ctypes as C
 
@@ -24,6 +35,7 @@ from scipy.special import erfcinv
 from . import _pwlib as W
 from .batch import BatchAligner
 from .blot import H1_moments, WordBlotOverlap
+from .kmers import check_window
 from .sequence import Alphabet, Sequence, check_complement, complement_table, reverse_complement
 
 BAND_DTYPE = np.dtype([('n_seeds', '<i8'), ('w_best', '<f8'), ('d_best', '<i4'), ('n_best', '<i4'),
@@ -202,7 +214,7 @@ def overlap_bands(reads, pairs, wordlen, alphabet, g_max, sensitivity, device=0,
 
 
 def raw_all_pairs(reads, wordlen, alphabet_len, g_max, sensitivity, device=0, max_pairs=None, rank=0, world=1, strands='+',
-                  complement=None, with_strand=None, max_kmer_occ=None, stats=None):
+                  complement=None, with_strand=None, max_kmer_occ=None, stats=None, minimizer_window=None):
     """All pairs ``a < b`` of ``reads`` that share at least one seed, through ONE k-mer index over all reads:
     returns ``(pairs (n, 2) int32, records BAND_DTYPE, device ms)``.  With ``world > 1`` only the pairs whose smaller
     read index is ``rank`` modulo ``world`` (one process per GPU, no data-path collective).
@@ -215,8 +227,17 @@ def raw_all_pairs(reads, wordlen, alphabet_len, g_max, sensitivity, device=0, ma
     ``max_kmer_occ``: None or 0 (today's calls, unchanged), or the occurrence cap of ``pw_overlap_all_pairs_capped``: a k-mer
     that occurs more than ``max_kmer_occ`` times in the whole read set (both strands counted unless ``strands == '+'``) gives
     no seeds.  ``stats`` (a dict) then receives the fields of ``pw_overlap_cap_stats``: ``entries``, ``masked_entries``,
-    ``distinct_masked``, ``seeds_kept``, ``seeds_dropped``."""
+    ``distinct_masked``, ``seeds_kept``, ``seeds_dropped``.
+
+    ``minimizer_window``: None, 0 or 1 (today's calls, unchanged), or a window of 2..128: the call goes through
+    ``pw_overlap_all_pairs_sampled`` and only the window minimizers of every read are indexed -- under the plain order of a
+    k-mer's mixed key with ``strands='+'``, under the canonical order (the smaller of the k-mer and its reverse complement)
+    otherwise.  Every record is the documented record of the seeds between two selected k-mers; ``w_best`` (and the ``p``
+    made of it) is the estimate from those seeds and lies below the unsampled one, ``d_best`` / ``r_best`` are unaffected in
+    kind.  The cap then counts occurrences in the sampled index.  ``stats`` receives ``positions`` (forward k-mer positions),
+    ``sampled`` (those indexed) and ``density`` (their ratio).  Anything but None or an integer in 0..128 is a ValueError."""
     assert 0 < g_max < 1 and 0 < sensitivity < 1
+    window = check_window(minimizer_window, 'minimizer_window')
     if max_kmer_occ is not None and not 0 <= int(max_kmer_occ) < 2 ** 32:
         raise ValueError('max_kmer_occ is None or 0 (no cap) or a count below 2^32, not %r' % (max_kmer_occ,))
     if strands not in _STRAND_SEL:
@@ -237,6 +258,24 @@ def raw_all_pairs(reads, wordlen, alphabet_len, g_max, sensitivity, device=0, ma
     rlen = np.ascontiguousarray(np.diff(offs).astype(np.int32))
     arena_c = np.ascontiguousarray(arena)
     coeffs = _band_coeffs(g_max, sensitivity, alphabet_len, wordlen)
+    if window > 1:
+        ps = np.zeros(max(cap, 1), np.uint8)
+        cs, ss = W.pw_overlap_cap_stats(), W.pw_overlap_sample_stats()
+        rc = lib.pw_overlap_all_pairs_sampled(device, arena_c.ctypes.data, arena_c.size, roff.ctypes.data, rlen.ctypes.data, R,
+                                              alphabet_len, wordlen, *coeffs, None if comp is None else comp.ctypes.data,
+                                              _STRAND_SEL[strands], int(rank), int(world), cap, pa.ctypes.data, pb.ctypes.data,
+                                              ps.ctypes.data, out.ctypes.data, C.byref(n_out), int(max_kmer_occ or 0), C.byref(cs),
+                                              window, C.byref(ss))
+        if stats is not None:
+            if max_kmer_occ:
+                stats.update((f, int(getattr(cs, f))) for f, _ in cs._fields_)
+            stats.update(positions=int(ss.positions), sampled=int(ss.sampled),
+                         density=float(ss.sampled) / ss.positions if ss.positions else float('nan'))
+        if rc != 0:
+            raise RuntimeError('pw_overlap_all_pairs_sampled failed: ' + (lib.pw_overlap_last_error() or b'').decode())
+        n = n_out.value
+        pairs = np.stack([pa[:n], pb[:n]], axis=1)
+        return (pairs, ps[:n], out[:n], lib.pw_overlap_last_ms()) if with_strand else (pairs, out[:n], lib.pw_overlap_last_ms())
     if max_kmer_occ:
         ps = np.zeros(max(cap, 1), np.uint8)
         cs = W.pw_overlap_cap_stats()
@@ -271,7 +310,7 @@ def raw_all_pairs(reads, wordlen, alphabet_len, g_max, sensitivity, device=0, ma
 
 
 def overlap_all_pairs(reads, wordlen, alphabet, g_max, sensitivity, device=0, max_pairs=None, stats=None, strands='+',
-                      complement=None, max_kmer_occ=None):
+                      complement=None, max_kmer_occ=None, minimizer_window=None):
     """The reference's all-pairs loop (``experiments/blot_overlaps.py:262-272``) in one device pass: returns a dict
     ``{(a, b): highest_scoring_overlap_band()}`` for the pairs ``a < b`` that share a seed; for every other pair the
     reference's answer is None.  With ``strands='-'`` or ``'both'`` the keys are ``(a, b, '+' | '-')`` and a minus entry
@@ -281,15 +320,22 @@ def overlap_all_pairs(reads, wordlen, alphabet, g_max, sensitivity, device=0, ma
     ``max_kmer_occ`` (None or 0: no cap): k-mers that occur more often in the whole read set give no seeds
     (:func:`raw_all_pairs`), and ``stats`` also receives the cap's five counters.  With a cap no pair goes to the
     single-pair fallback -- that path knows no cap, and the reference defines no row order for a filtered seeds table:
-    where ``tie > 1`` the record's own rule decides (largest ``w``, then smallest ``d``) and ``fallback_pairs`` is 0."""
+    where ``tie > 1`` the record's own rule decides (largest ``w``, then smallest ``d``) and ``fallback_pairs`` is 0.
+
+    ``minimizer_window`` (None, 0 or 1: no sampling): only the window minimizers of every read are indexed
+    (:func:`raw_all_pairs`), and ``stats`` also receives ``positions``, ``sampled`` and ``density``.  ``p`` of every band is
+    then the estimate from the sampled seeds and lies below the unsampled one: rescale a ``p_min`` of
+    :func:`overlap_alignments` accordingly (``density`` is there for that); ``d_band`` is unaffected in kind.  As under the
+    cap, no pair goes to the single-pair fallback: that path knows no sampling."""
     assert isinstance(alphabet, Alphabet)
     cap_stats = {}
-    cap_kw = dict(max_kmer_occ=max_kmer_occ, stats=cap_stats)
+    sampled = check_window(minimizer_window, 'minimizer_window') > 1
+    cap_kw = dict(max_kmer_occ=max_kmer_occ, stats=cap_stats, minimizer_window=minimizer_window)
     if strands == '+':
         pairs, recs, ms = raw_all_pairs(reads, wordlen, len(alphabet), g_max, sensitivity, device, max_pairs, **cap_kw)
         plist = [(int(a), int(b)) for a, b in pairs.tolist()]
         res, n_fallback = _records_to_results(reads, plist, recs, wordlen, alphabet, g_max, sensitivity, device,
-                                              fallback=not max_kmer_occ)
+                                              fallback=not max_kmer_occ and not sampled)
         keys = plist
     else:
         comp = _complement(complement, len(alphabet), alphabet)
@@ -297,7 +343,7 @@ def overlap_all_pairs(reads, wordlen, alphabet, g_max, sensitivity, device=0, ma
                                                complement=comp, **cap_kw)
         plist = [(int(a), int(b)) for a, b in pairs.tolist()]
         res, n_fallback = _records_to_results(reads, plist, recs, wordlen, alphabet, g_max, sensitivity, device, flags, comp,
-                                              fallback=not max_kmer_occ)
+                                              fallback=not max_kmer_occ and not sampled)
         keys = [(a, b, '-' if f else '+') for (a, b), f in zip(plist, flags.tolist())]
     if stats is not None:
         stats.update(device_ms=ms, fallback_pairs=n_fallback, pairs=len(plist))
@@ -446,20 +492,23 @@ def raw_bands_sharded(reads, pairs, wordlen, alphabet_len, g_max, sensitivity, r
 
 
 def raw_all_pairs_sharded(reads, wordlen, alphabet_len, g_max, sensitivity, rank, world, device=None, max_pairs=None, strands='+',
-                          complement=None, max_kmer_occ=None, stats=None):
+                          complement=None, max_kmer_occ=None, stats=None, minimizer_window=None):
     """Config 4 across GPUs: every rank indexes all reads (cheap) and joins / scores the pairs whose smaller read
     index is ``rank`` modulo ``world``; pair lists and 64-byte records are gathered to rank 0 (ragged byte gather over
     ``torch.distributed``) and merged in ascending (a, b) order.  Returns ``(pairs, records)`` on rank 0, None elsewhere.
     With ``strands`` other than ``'+'``: ``(pairs, strand, records)`` in ascending (a, b, strand) order.
     ``max_kmer_occ`` / ``stats``: the occurrence cap of :func:`raw_all_pairs`, counted over the whole read set on every rank, so
-    the merged output equals the unsharded capped call's; ``stats`` receives THIS rank's counters."""
+    the merged output equals the unsharded capped call's; ``stats`` receives THIS rank's counters.
+    ``minimizer_window``: the sampling of :func:`raw_all_pairs`; every rank samples the whole read set, so the merged output
+    equals the unsharded sampled call's."""
     import torch
     from .distributed import gather_bytes
     if strands != '+':
         return _raw_all_pairs_sharded_stranded(reads, wordlen, alphabet_len, g_max, sensitivity, rank, world, device, max_pairs,
-                                               strands, complement, max_kmer_occ, stats)
+                                               strands, complement, max_kmer_occ, stats, minimizer_window)
     pairs, recs, _ = raw_all_pairs(reads, wordlen, alphabet_len, g_max, sensitivity, device=rank if device is None else device,
-                                   max_pairs=max_pairs, rank=rank, world=world, max_kmer_occ=max_kmer_occ, stats=stats)
+                                   max_pairs=max_pairs, rank=rank, world=world, max_kmer_occ=max_kmer_occ, stats=stats,
+                                   minimizer_window=minimizer_window)
     blob = np.concatenate([np.ascontiguousarray(pairs, np.int32).view(np.uint8).reshape(-1), recs.view(np.uint8).reshape(-1)])
     got = gather_bytes(torch.from_numpy(blob.copy()), rank, world)
     if rank != 0:
@@ -476,13 +525,13 @@ def raw_all_pairs_sharded(reads, wordlen, alphabet_len, g_max, sensitivity, rank
 
 
 def _raw_all_pairs_sharded_stranded(reads, wordlen, alphabet_len, g_max, sensitivity, rank, world, device, max_pairs, strands,
-                                    complement, max_kmer_occ=None, stats=None):
+                                    complement, max_kmer_occ=None, stats=None, minimizer_window=None):
     """:func:`raw_all_pairs_sharded` with the strand column: the third int32 of every gathered pair."""
     import torch
     from .distributed import gather_bytes
     pairs, flags, recs, _ = raw_all_pairs(reads, wordlen, alphabet_len, g_max, sensitivity, device=rank if device is None else device,
                                           max_pairs=max_pairs, rank=rank, world=world, strands=strands, complement=complement,
-                                          max_kmer_occ=max_kmer_occ, stats=stats)
+                                          max_kmer_occ=max_kmer_occ, stats=stats, minimizer_window=minimizer_window)
     triples = np.ascontiguousarray(np.concatenate([pairs, flags.astype(np.int32)[:, None]], axis=1), np.int32)
     blob = np.concatenate([triples.view(np.uint8).reshape(-1), recs.view(np.uint8).reshape(-1)])
     got = gather_bytes(torch.from_numpy(blob.copy()), rank, world)

@@ -120,6 +120,28 @@ int pw_overlap_all_pairs_capped(int device, const uint8_t* arena, uint64_t arena
                                 int32_t* pair_b, uint8_t* pair_strand, pw_overlap_band* out, int64_t* n_out,
                                 uint32_t max_occ, pw_overlap_cap_stats* stats);
 
+/* ---- minimizer sampling ----------------------------------------------------------------------------------------------
+ * pw_overlap_all_pairs_capped over an index that holds the WINDOW MINIMIZERS of every read only (pw_kmers.h states the rule:
+ * the order value is mix(x) with PW_STRAND_PLUS and the canonical mix(min(x, rc(x))) with PW_STRAND_MINUS or PW_STRAND_BOTH,
+ * every position that attains a window's minimum is selected).  Both indexes hold the same number of rows: under the
+ * canonical order the selected positions of rc(read) mirror the read's own.  A seed exists only between two selected rows;
+ * everything after the index is unchanged, so every field of every record is the documented record of the surviving seed
+ * set.  The estimate behind w_best therefore sees fewer seeds than the unsampled call's and lies below it; d_best and r_best
+ * are of the same kind as ever.  occ(x) of the cap counts the SAMPLED rows: count(x) of a pw_kmers_build_sampled with the same
+ * strands and window; `entries` of the cap's stats counts sampled rows.  Two reads that share an exact stretch of window +
+ * wordlen - 1 letters, on the strand joined, share a seed inside it.  Every rank samples the whole read set; the union of
+ * the ranks equals the unsharded call.  The 2^32 limit on k-mers is judged on the unsampled positions, the one on seeds on
+ * what survives.  window 0 or 1: pw_overlap_all_pairs_capped bit for bit; a window outside 0..128 is refused.
+ * sample (may be NULL): the forward positions of the read set and how many of them the index kept (equal without a window). */
+typedef struct { uint64_t positions, sampled; } pw_overlap_sample_stats;
+int pw_overlap_all_pairs_sampled(int device, const uint8_t* arena, uint64_t arena_bytes, const uint64_t* read_off,
+                                 const int32_t* read_len, int64_t n_reads, int alphabet_len, int wordlen,
+                                 double len_coeff, double radius_coeff, double word_p_null, const uint8_t* complement,
+                                 int strands, int shard_rank, int shard_world, int64_t max_pairs, int32_t* pair_a,
+                                 int32_t* pair_b, uint8_t* pair_strand, pw_overlap_band* out, int64_t* n_out,
+                                 uint32_t max_occ, pw_overlap_cap_stats* stats, int window,
+                                 pw_overlap_sample_stats* sample);
+
 /* Reads for the alignment stage: a device arena of total_bytes (+ the slack the kernels read) whose first `bytes` are the
  * host arena, uploaded once; behind them the device writes the reverse complement of n_frames reads: frame f =
  * rc(arena[src_off[f], src_off[f] + len[f])) at dst_off[f].  The dst frames ascend without overlap inside
