@@ -1,5 +1,5 @@
 """ctypes binding of biseqt_amd/pwlib/pwlib.so (the HIP library; C ABI in include/pwlib.h,
-include/pw_batch.h, include/pw_txsum.h, include/pw_cigar.h, include/pw_pileup.h and the seed headers include/pw_seeds.h, pw_mseeds.h, pw_qseeds.h, pw_overlap.h).
+include/pw_batch.h, include/pw_txsum.h, include/pw_cigar.h, include/pw_pileup.h, include/pw_polish.h and the seed headers include/pw_seeds.h, pw_mseeds.h, pw_qseeds.h, pw_overlap.h).
 
 The reference binds its C library with cffi in ABI mode (``biseqt/pw.py:45-69``); cffi is not
 available in this image, so the same structs are declared with ctypes -- field for field the layout of
@@ -112,6 +112,11 @@ class pw_pileup_site(C.Structure):
     _fields_ = [('depth', C.c_uint32), ('call', C.c_uint8), ('ref', C.c_uint8), ('flags', C.c_uint16)]
 
 
+# ---- read correction (include/pw_polish.h) ----
+class pw_polish_stats(C.Structure):
+    _fields_ = [(f, C.c_uint32) for f in ('kept', 'substituted', 'deleted', 'inserted')]
+
+
 PW_TXSUM_DONE = 1
 PW_ST_TRACED, PW_ST_EMPTY, PW_ST_PANICK, PW_ST_BADPATH = 1, 2, 4, 8
 PW_FLAG_DUMP_SCORES, PW_FLAG_FORCE_F64, PW_FLAG_FORCE_GENERIC, PW_FLAG_PROFILE = 1, 2, 4, 8
@@ -123,7 +128,7 @@ PW_FLAG_NO_STRIP = 256
 
 SIZEOF = dict(intpair=8, alnscores=24, alnframe=32, std_alnparams=4, banded_alnparams=12,
               alnprob=32, alnchoice=32, dpcell=16, dptable=32, alignment=24,
-              pw_scoring=40, pw_pair=32, pw_result=32, pw_tx_summary=48, pw_pileup_site=8)
+              pw_scoring=40, pw_pair=32, pw_result=32, pw_tx_summary=48, pw_pileup_site=8, pw_polish_stats=16)
 
 # every symbol include/pwlib.h and include/pw_batch.h declare
 EXPORTS = ['dptable_init', 'dptable_solve', 'dptable_traceback', 'dptable_free',
@@ -150,6 +155,13 @@ PW_CIGAR_MAX_LEN = 1 << 28
 PILEUP_EXPORTS = ['pw_pileup_create', 'pw_pileup_destroy', 'pw_pileup_clear', 'pw_batch_pileup_add', 'pw_pileup_counts_device',
                   'pw_pileup_counts', 'pw_pileup_set_counts', 'pw_pileup_call', 'pw_pileup_sites_device', 'pw_pileup_sites']
 PW_PILEUP_COVERED, PW_PILEUP_DIFFERS, PW_PILEUP_INSERT = 1, 2, 4
+# every symbol and constant include/pw_polish.h declares
+POLISH_EXPORTS = ['pw_pileup_create_ins', 'pw_pileup_ins_slots', 'pw_pileup_ins_counts_device', 'pw_pileup_ins_counts',
+                  'pw_batch_pileup_add_sides', 'pw_pileup_add_letters', 'pw_pileup_polish', 'pw_pileup_polished_total',
+                  'pw_pileup_polished_offsets', 'pw_pileup_polished_letters', 'pw_pileup_polished_stats',
+                  'pw_pileup_polished_letters_device', 'pw_pileup_polished_offsets_device']
+PW_POLISH_MAX_SLOTS = 8
+PW_SIDE_ORIGIN, PW_SIDE_MUTANT, PW_SIDE_BOTH = 1, 2, 3
 # every symbol include/pw_seeds.h declares
 SEED_EXPORTS = ['pw_seeds_create', 'pw_seeds_build', 'pw_seeds_num_rows', 'pw_seeds_is_self', 'pw_seeds_rows_device',
                 'pw_seeds_rows', 'pw_seeds_count', 'pw_seeds_kmers', 'pw_seeds_band_neighbours', 'pw_seeds_graph_build', 'pw_seeds_graph_num_points', 'pw_seeds_graph_points',
@@ -352,6 +364,26 @@ def load():
     lib.pw_pileup_sites_device.argtypes = [C.c_void_p]
     lib.pw_pileup_sites_device.restype = C.c_void_p
     lib.pw_pileup_sites.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]
+    # include/pw_polish.h
+    lib.pw_pileup_create_ins.argtypes = [C.c_int, C.c_int64, C.c_int, C.c_int]
+    lib.pw_pileup_create_ins.restype = C.c_void_p
+    lib.pw_pileup_ins_slots.argtypes = [C.c_void_p]
+    lib.pw_pileup_ins_counts_device.argtypes = [C.c_void_p]
+    lib.pw_pileup_ins_counts_device.restype = C.c_void_p
+    lib.pw_pileup_ins_counts.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]
+    lib.pw_batch_pileup_add_sides.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                              C.c_int64, C.c_void_p]
+    lib.pw_pileup_add_letters.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_uint32, C.c_void_p]
+    lib.pw_pileup_polish.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_uint32, C.c_void_p]
+    lib.pw_pileup_polished_total.argtypes = [C.c_void_p]
+    lib.pw_pileup_polished_total.restype = C.c_int64
+    lib.pw_pileup_polished_offsets.argtypes = [C.c_void_p, C.c_void_p]
+    lib.pw_pileup_polished_letters.argtypes = [C.c_void_p, C.c_void_p]
+    lib.pw_pileup_polished_stats.argtypes = [C.c_void_p, C.c_void_p]
+    lib.pw_pileup_polished_letters_device.argtypes = [C.c_void_p]
+    lib.pw_pileup_polished_letters_device.restype = C.c_void_p
+    lib.pw_pileup_polished_offsets_device.argtypes = [C.c_void_p]
+    lib.pw_pileup_polished_offsets_device.restype = C.c_void_p
     # include/pw_seeds.h
     lib.pw_seeds_create.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int,
                                     P(C.c_uint64), C.c_int, C.c_int]

@@ -28,6 +28,10 @@ _CIGAR_FORMS = {'extended': CIGAR_EXTENDED, 'classic': CIGAR_CLASSIC}
 # pw_pileup_site of include/pw_pileup.h: one called column of a pileup
 SITE_DTYPE = np.dtype([('depth', '<u4'), ('call', 'u1'), ('ref', 'u1'), ('flags', '<u2')])
 assert SITE_DTYPE.itemsize == 8
+# pw_polish_stats of include/pw_polish.h: what became of the columns of one polished read
+POLISH_STATS_DTYPE = np.dtype([(f, '<u4') for f in ('kept', 'substituted', 'deleted', 'inserted')])
+assert POLISH_STATS_DTYPE.itemsize == 16
+_SIDES = {'origin': W.PW_SIDE_ORIGIN, 'mutant': W.PW_SIDE_MUTANT, 'both': W.PW_SIDE_BOTH}
 _CIGAR_LETTERS = ({'M': '=', 'S': 'X', 'I': 'I', 'D': 'D'}, {'M': 'M', 'S': 'M', 'I': 'I', 'D': 'D'})
 
 
@@ -179,22 +183,31 @@ class Pileup(object):
     insertion events anchored to the column on their left) -- zeroed at creation and filled by
     :meth:`BatchAligner.pileup_add` from the transcripts where the traceback left them.  The header has the definition op by
     op.  A cell wraps past ``2**32 - 1``; keeping the depth below that is the caller's business.  A context manager that
-    frees itself, like :class:`DeviceArena`."""
+    frees itself, like :class:`DeviceArena`.
 
-    def __init__(self, n_cols, alphabet_len, device=0):
+    With ``ins_slots = J`` in 1 .. 8 the pileup also owns the insertion plane of include/pw_polish.h, ``uint32
+    ins[n_cols][J][alphabet_len]``: the first ``J`` letters of every insertion run, per column and slot, filled by
+    :meth:`BatchAligner.pileup_add` with ``sides=`` and read by :meth:`polish`."""
+
+    def __init__(self, n_cols, alphabet_len, device=0, ins_slots=0):
         self.handle = None
-        n_cols, alphabet_len = int(n_cols), int(alphabet_len)
+        n_cols, alphabet_len, ins_slots = int(n_cols), int(alphabet_len), int(ins_slots)
         if not 1 <= alphabet_len <= 32:
             raise ValueError('alphabet_len must be 1..32, not %d' % alphabet_len)
         if n_cols < 0:
             raise ValueError('n_cols must not be negative')
+        if not 0 <= ins_slots <= W.PW_POLISH_MAX_SLOTS:
+            raise ValueError('ins_slots must be 0 (no insertion plane) or 1..8, not %d' % ins_slots)
         self.lib = W.load()
-        self.n_cols, self.alphabet_len, self.device = n_cols, alphabet_len, device
+        self.n_cols, self.alphabet_len, self.device, self.ins_slots = n_cols, alphabet_len, device, ins_slots
         self.DEL, self.INS = alphabet_len, alphabet_len + 1
         self._ref = None                     # the device copy of a host reference given to call(): alive as long as the sites
-        self.handle = self.lib.pw_pileup_create(device, n_cols, alphabet_len)
+        if ins_slots:
+            self.handle = self.lib.pw_pileup_create_ins(device, n_cols, alphabet_len, ins_slots)
+        else:
+            self.handle = self.lib.pw_pileup_create(device, n_cols, alphabet_len)
         if not self.handle:
-            raise RuntimeError('pw_pileup_create failed: ' + W.last_error())
+            raise RuntimeError('%s failed: %s' % ('pw_pileup_create_ins' if ins_slots else 'pw_pileup_create', W.last_error()))
 
     def close(self):
         if getattr(self, 'handle', None):
@@ -287,6 +300,82 @@ class Pileup(object):
         if not ptr:
             raise RuntimeError('sites_device before call')
         return DeviceBuffer(ptr, 8 * self.n_cols, self)
+
+    # ---- read correction (include/pw_polish.h) ----
+    def ins_counts(self, lo=0, hi=None):
+        """``uint32[hi - lo, ins_slots, alphabet_len]`` of the insertion plane's columns ``[lo, hi)`` (synchronous D2H)."""
+        lo, hi = self._range(lo, hi)
+        if not self.ins_slots:
+            raise ValueError('the pileup has no insertion plane (ins_slots=0)')
+        out = np.zeros((hi - lo, self.ins_slots, self.alphabet_len), np.uint32)
+        self._ck(self.lib.pw_pileup_ins_counts(self.handle, lo, hi, out.ctypes.data), 'pw_pileup_ins_counts')
+        return out
+
+    def ins_counts_device(self):
+        if not self.ins_slots:
+            raise ValueError('the pileup has no insertion plane (ins_slots=0)')
+        return DeviceBuffer(self.lib.pw_pileup_ins_counts_device(self.handle), 4 * self.n_cols * self.ins_slots * self.alphabet_len, self)
+
+    def _letters(self, ref, lo, n):
+        """``(device pointer of the letter of column lo, a DeviceArena to close or None)`` for ``n`` letters given as a host
+        array or as ``(DeviceArena, offset)``."""
+        if isinstance(ref, tuple):
+            arena, off = ref
+            if not isinstance(arena, DeviceArena) or arena.device != self.device or not 0 <= int(off) <= arena.nbytes - n:
+                raise ValueError('letters are (DeviceArena on device %d, offset) with %d letters behind the offset' % (self.device, n))
+            return arena.ptr + int(off), None
+        letters = _as_u8(ref)
+        if len(letters) != n:
+            raise ValueError('%d letters for %d columns' % (len(letters), n))
+        held = DeviceArena(letters if len(letters) else np.zeros(1, np.uint8), device=self.device)
+        return held.ptr, held
+
+    def add_letters(self, ref, weight=1, lo=0, stream=None):
+        """The self vote (``pw_pileup_add_letters``): column ``lo + x`` gains ``weight`` in the channel of letter ``x`` of
+        ``ref`` -- a host array, or ``(DeviceArena, offset)`` with ``n_cols - lo`` letters behind the offset, as for
+        :meth:`call`.  A letter outside the alphabet adds nothing."""
+        weight, lo = int(weight), int(lo)
+        if not 0 <= weight < 1 << 32:
+            raise ValueError('weight must fit 32 bits')
+        if isinstance(ref, tuple):
+            lo, hi = self._range(lo, None)
+        else:
+            lo, hi = self._range(lo, lo + len(_as_u8(ref)))
+        ptr, held = self._letters(ref, lo, hi - lo)
+        try:
+            self._ck(self.lib.pw_pileup_add_letters(self.handle, ptr, lo, hi, weight, stream), 'pw_pileup_add_letters')
+        finally:
+            if held is not None:
+                held.close()                 # (pw_arena_free waits for the device: the kernel has read the letters by then)
+
+    def polish(self, ref, offs, lens, min_depth=1, stream=None):
+        """The polished reads (``pw_pileup_polish``; the rule is in include/pw_polish.h): read ``r`` has its letters and its
+        columns at ``offs[r] .. offs[r] + lens[r]``; ``ref`` holds one letter per column of the pileup, a host array or
+        ``(DeviceArena, offset)`` as for :meth:`call`.  Returns ``(letters uint8, offsets int64[n + 1], stats)``: read ``r``
+        is ``letters[offsets[r]:offsets[r + 1]]`` and ``stats[r]`` its :data:`POLISH_STATS_DTYPE` record."""
+        min_depth = int(min_depth)
+        if not 0 <= min_depth < 1 << 32:
+            raise ValueError('min_depth must fit 32 bits')
+        o = np.ascontiguousarray(offs, np.int64).reshape(-1)
+        ln = np.ascontiguousarray(lens, np.int32).reshape(-1)
+        if len(o) != len(ln):
+            raise ValueError('%d offsets for %d lengths' % (len(o), len(ln)))
+        if len(o) and ((ln < 0).any() or (o < 0).any() or (o + ln.astype(np.int64) > self.n_cols).any()):
+            bad = int(np.flatnonzero((ln < 0) | (o < 0) | (o + ln.astype(np.int64) > self.n_cols))[0])
+            raise ValueError('read %d lies outside the pileup of %d columns' % (bad, self.n_cols))
+        ptr, held = self._letters(ref, 0, self.n_cols)
+        try:
+            self._ck(self.lib.pw_pileup_polish(self.handle, ptr, o.ctypes.data, ln.ctypes.data, len(o), min_depth, stream), 'pw_pileup_polish')
+            total = int(self.lib.pw_pileup_polished_total(self.handle))
+            letters, offsets = np.zeros(total, np.uint8), np.zeros(len(o) + 1, np.int64)
+            stats = np.zeros(len(o), POLISH_STATS_DTYPE)
+            self._ck(self.lib.pw_pileup_polished_offsets(self.handle, offsets.ctypes.data), 'pw_pileup_polished_offsets')
+            self._ck(self.lib.pw_pileup_polished_letters(self.handle, letters.ctypes.data), 'pw_pileup_polished_letters')
+            self._ck(self.lib.pw_pileup_polished_stats(self.handle, stats.ctypes.data), 'pw_pileup_polished_stats')
+        finally:
+            if held is not None:
+                held.close()
+        return letters, offsets, stats
 
     def consensus(self, lo=0, hi=None):
         """The ``call`` bytes of the columns ``[lo, hi)``: a letter, ``alphabet_len`` for a deletion, 255 for no call."""
@@ -641,21 +730,50 @@ class BatchAligner(object):
         return DeviceBuffer(runs, 4 * int(self.lib.pw_batch_cigar_total(self.handle)), self), DeviceBuffer(off, 8 * (self.n + 1), self)
 
     # ---- pileups (include/pw_pileup.h): the transcripts scattered into per-column counts where they are ----
-    def pileup_add(self, pileup, col0=None, arena_first=0, stream=None):
+    def pileup_add(self, pileup, col0=None, arena_first=0, stream=None, sides='origin', mutant_col0=None, reverse=None, complement=None):
         """After a traceback on ``stream``: every pair with an alignment adds its ops to the columns of its origin in
         ``pileup`` (a :class:`Pileup` on the same device; ``pw_batch_pileup_add``, asynchronous on ``stream``).  The origin
         frame of pair ``k`` starts at column ``col0[k]`` -- an int64 per pair, negative to skip the pair -- or, without
         ``col0``, at its arena offset minus ``arena_first``; a pair whose frame does not lie inside the pileup adds nothing.
-        Adding is cumulative."""
+        Adding is cumulative.
+
+        ``sides``: ``'origin'`` (with the other defaults and a pileup without an insertion plane: the call above, exactly), ``'mutant'`` or ``'both'``
+        (``pw_batch_pileup_add_sides``, include/pw_polish.h): the mutant side adds the swapped pair to the columns of the
+        mutant, whose frame starts at ``mutant_col0[k]`` or at its arena offset minus ``arena_first``; where ``reverse[k]`` is
+        set the mutant frame is read backwards through ``complement`` (a table of ``alphabet_len`` letters), so that the
+        columns are the forward letters of a read whose reverse complement was aligned.  These calls also fill the
+        insertion plane of a pileup that has one."""
+        if sides not in _SIDES:
+            raise ValueError("sides is 'origin', 'mutant' or 'both', not %r" % (sides,))
+
+        def per_pair(a, dtype, what):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype).reshape(-1)
+            if len(a) != self.n:
+                raise ValueError('%s has %d entries for %d pairs' % (what, len(a), self.n))
+            return a
+        c, mc = per_pair(col0, np.int64, 'col0'), per_pair(mutant_col0, np.int64, 'mutant_col0')
+        rv = per_pair(None if reverse is None else np.asarray(reverse) != 0, np.uint8, 'reverse')
+        comp = None
+        if rv is not None and rv.any():
+            if sides == 'origin':
+                raise ValueError("reverse applies to the mutant side: sides is 'mutant' or 'both'")
+            if complement is None:
+                raise ValueError('reversed pairs need a complement table')
+            comp = np.ascontiguousarray(complement, np.uint8).reshape(-1)
         if not isinstance(pileup, Pileup) or not pileup.handle:
             raise ValueError('pileup must be an open Pileup')
-        c = None
-        if col0 is not None:
-            c = np.ascontiguousarray(col0, np.int64).reshape(-1)
-            if len(c) != self.n:
-                raise ValueError('col0 has %d entries for %d pairs' % (len(c), self.n))
-        self._ck(self.lib.pw_batch_pileup_add(self.handle, pileup.handle, None if c is None else c.ctypes.data, int(arena_first), stream),
-                 'pw_batch_pileup_add')
+        if sides == 'origin' and mc is None and rv is None and complement is None and not pileup.ins_slots:
+            self._ck(self.lib.pw_batch_pileup_add(self.handle, pileup.handle, None if c is None else c.ctypes.data, int(arena_first), stream),
+                     'pw_batch_pileup_add')
+            return
+
+        def ptr(a):
+            return None if a is None else a.ctypes.data
+        self._ck(self.lib.pw_batch_pileup_add_sides(self.handle, pileup.handle, _SIDES[sides], ptr(c), ptr(mc), ptr(rv), ptr(comp),
+                                                    0 if comp is None else len(comp), int(arena_first), stream),
+                 'pw_batch_pileup_add_sides')
 
     def scores_plane(self, k):
         """Score of every cell of pair k as ``plane[d - dmin, a]`` (needs PW_FLAG_DUMP_SCORES)."""

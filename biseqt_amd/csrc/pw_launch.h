@@ -49,6 +49,24 @@ hipError_t launch_pileup_add(const PairDesc* pairs, const Result* results, const
                              const int64_t* col0, int64_t arena_first, uint32_t* counts, int64_t n_cols, int L, hipStream_t st);
 hipError_t launch_pileup_call(const uint32_t* counts, const uint8_t* ref, int64_t n_cols, int L, uint32_t min_depth, void* sites,
                               hipStream_t st);
+// read correction (pw_polish.hip; the definitions in include/pw_polish.h).  add -- one wavefront per pair and side (sides: 1
+// origin, 2 mutant, 3 both) into counts and, when not null, ins[n_cols][J][L]; ocol0 / mcol0 / reversed: device arrays per pair
+// or null; comp: the complement table, 32 bytes by value.  letters -- the self vote over [lo, hi).  count -- per read the
+// emitted length into lens[n + 1] and the statistics record, then offsets[n + 1] = the exclusive sums of lens ([n] = total)
+// through rocprim_run in `tmp`; write -- the letters at out[offsets[read] ..]
+struct PolishComplement { uint32_t w[8]; };
+}  // namespace pw
+struct DeviceBuffer;
+namespace pw {
+hipError_t launch_polish_add(const PairDesc* pairs, const Result* results, const uint8_t* slots, const uint8_t* arena, int n, int sides,
+                             const int64_t* ocol0, const int64_t* mcol0, const uint8_t* reversed, const PolishComplement& comp,
+                             int64_t arena_first, uint32_t* counts, uint32_t* ins, int64_t n_cols, int L, int J, hipStream_t st);
+hipError_t launch_polish_letters(uint32_t* counts, const uint8_t* letters, int64_t lo, int64_t hi, int L, uint32_t weight, hipStream_t st);
+hipError_t launch_polish_count(const uint32_t* counts, const uint32_t* ins, const uint8_t* letters, const int64_t* roff, const int32_t* rlen,
+                               int64_t n, int L, int J, uint32_t min_depth, uint64_t* lens, uint64_t* offsets, void* stats, DeviceBuffer& tmp,
+                               hipStream_t st);
+hipError_t launch_polish_write(const uint32_t* counts, const uint32_t* ins, const uint8_t* letters, const int64_t* roff, const int32_t* rlen,
+                               int64_t n, int L, int J, uint32_t min_depth, const uint64_t* offsets, uint8_t* out, hipStream_t st);
 // strip pipeline (pw_strip.h / pw_strip.hip): one standard-mode pair wider than a workgroup
 struct StripParams;
 struct StripTraceParams;

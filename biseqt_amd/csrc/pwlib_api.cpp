@@ -23,10 +23,12 @@
 #include "../../include/pw_txsum.h"
 #include "../../include/pw_cigar.h"
 #include "../../include/pw_pileup.h"
+#include "../../include/pw_polish.h"
 #include "pw_launch.h"
 #include "pw_plan.h"
 #include "pw_model.h"
 #include "pw_hip_host.h"
+#include "pw_complement.h"
 #define PW_FN inline
 #include "pw_strip.h"
 #include <atomic>
@@ -232,6 +234,10 @@ struct pw_batch {
   hipStream_t cigar_stream = nullptr;    // the stream of the last pw_batch_cigars
   DeviceArray<int64_t> d_col0;           // pw_batch_pileup_add: [n] frame starts, allocated on its first call with a col0
   std::vector<int64_t> h_col0;           // ... and the host copy they are uploaded from
+  DeviceArray<int64_t> d_sides_col0;     // pw_batch_pileup_add_sides: [2][n] frame starts of the origin and the mutant side
+  DeviceArray<uint8_t> d_reversed;       // ... [n] reversal bytes
+  std::vector<int64_t> h_sides_col0;     // ... and the host copies they are uploaded from
+  std::vector<uint8_t> h_reversed;
   DeviceEvent ev_fill0, ev_fill1, ev_tr0, ev_tr1;
   bool fill_timed = false, trace_timed = false;
   // scores as the caller gave them (batch_plan may scale b->subst / go / ge by a power of two)
@@ -1158,6 +1164,20 @@ struct pw_pileup {
   DeviceArray<pw_pileup_site> d_sites;   // [n_cols]: allocated by the first pw_pileup_call
   size_t row() const { return (size_t)(L + 2); }                         // counters per column
   size_t count_bytes() const { return d_counts.bytes((size_t)n_cols * row()); }
+  // include/pw_polish.h: the insertion plane of pw_pileup_create_ins and the results of the last pw_pileup_polish
+  int J = 0;                             // ins_slots; 0: no plane
+  DeviceArray<uint32_t> d_ins;           // [n_cols][J][L]
+  size_t ins_row() const { return (size_t)J * (size_t)L; }
+  size_t ins_bytes() const { return d_ins.bytes((size_t)n_cols * ins_row()); }
+  bool polished = false;
+  int64_t polish_reads = 0, polish_total = 0;
+  DeviceArray<int64_t> d_roff;           // [n_reads]
+  DeviceArray<int32_t> d_rlen;           // [n_reads]
+  DeviceArray<uint64_t> d_plens, d_poffs;   // [n_reads + 1]: emitted lengths, their exclusive sums
+  DeviceArray<pw_polish_stats> d_pstats; // [n_reads]
+  DeviceArray<uint8_t> d_pletters;       // [polish_total]
+  DeviceBuffer polish_tmp;               // rocPRIM's scratch
+  std::vector<int64_t> h_roff; std::vector<int32_t> h_rlen;
 };
 
 pw_pileup* pw_pileup_create(int device, int64_t n_cols, int alphabet_len) {
@@ -1182,6 +1202,7 @@ int pw_pileup_clear(pw_pileup* p, void* stream) {
   if (!p) return fail("pw_pileup_clear: null pileup");
   HIP_TRY(hipSetDevice(p->device));
   if (p->count_bytes()) HIP_TRY(hipMemsetAsync(p->d_counts.p, 0, p->count_bytes(), (hipStream_t)stream));
+  if (p->J && p->ins_bytes()) HIP_TRY(hipMemsetAsync(p->d_ins.p, 0, p->ins_bytes(), (hipStream_t)stream));
   return 0;
 }
 int pw_batch_pileup_add(pw_batch* b, pw_pileup* p, const int64_t* col0, int64_t arena_first, void* stream) {
@@ -1242,6 +1263,158 @@ int pw_pileup_sites(pw_pileup* p, int64_t lo, int64_t hi, pw_pileup_site* host_o
   HIP_TRY(hipSetDevice(p->device));
   HIP_TRY(hipMemcpy(host_out, p->d_sites.p + lo, p->d_sites.bytes((size_t)(hi - lo)), hipMemcpyDeviceToHost));
   return 0;
+}
+
+// ---- read correction (include/pw_polish.h; kernels in pw_polish.hip) ----
+pw_pileup* pw_pileup_create_ins(int device, int64_t n_cols, int alphabet_len, int ins_slots) {
+  if (ins_slots < 1 || ins_slots > PW_POLISH_MAX_SLOTS) { fail("pw_pileup_create_ins: ins_slots must be 1..8"); return nullptr; }
+  std::unique_ptr<pw_pileup> p(pw_pileup_create(device, n_cols, alphabet_len));
+  if (!p) return nullptr;
+  p->J = ins_slots;
+  if (p->d_ins.ensure((size_t)n_cols * p->ins_row()) != hipSuccess || hipMemset(p->d_ins.p, 0, std::max<size_t>(p->ins_bytes(), 16)) != hipSuccess) {
+    (void)hipGetLastError();
+    (void)hipSetDevice(device);
+    fail("pw_pileup_create_ins: allocation failed");
+    return nullptr;
+  }
+  return p.release();
+}
+int pw_pileup_ins_slots(const pw_pileup* p) { return p ? p->J : 0; }
+void* pw_pileup_ins_counts_device(pw_pileup* p) { return p && p->J ? p->d_ins.p : nullptr; }
+int pw_pileup_ins_counts(pw_pileup* p, int64_t lo, int64_t hi, uint32_t* host_out) {
+  if (!p) return fail("pw_pileup_ins_counts: null pileup");
+  if (!p->J) return fail("pw_pileup_ins_counts: the pileup has no insertion plane (pw_pileup_create_ins)");
+  if (lo < 0 || hi < lo || hi > p->n_cols) return fail("pw_pileup_ins_counts: columns outside the pileup");
+  if (hi == lo) return 0;
+  if (!host_out) return fail("pw_pileup_ins_counts: null output");
+  HIP_TRY(hipSetDevice(p->device));
+  const size_t row = p->ins_row();
+  HIP_TRY(hipMemcpy(host_out, p->d_ins.p + row * (size_t)lo, p->d_ins.bytes(row * (size_t)(hi - lo)), hipMemcpyDeviceToHost));
+  return 0;
+}
+int pw_batch_pileup_add_sides(pw_batch* b, pw_pileup* p, int sides, const int64_t* origin_col0, const int64_t* mutant_col0,
+                              const uint8_t* reversed, const uint8_t* complement, int complement_len, int64_t arena_first, void* stream) {
+  if (sides < PW_SIDE_ORIGIN || sides > PW_SIDE_BOTH) return fail("pw_batch_pileup_add_sides: sides must be 1 (origin), 2 (mutant) or 3 (both)");
+  if (!b || !p) return fail("pw_batch_pileup_add_sides: null batch or pileup");
+  if (!b->traced) return fail("pw_batch_pileup_add_sides before a traceback of the batch");
+  if (b->device != p->device) return fail("pw_batch_pileup_add_sides: the batch and the pileup live on different devices");
+  if (p->L < 1 || p->L > 32) return fail("pw_batch_pileup_add_sides: alphabet_len must be 1..32");
+  const size_t n = (size_t)b->n;
+  bool any_rev = false;
+  if (reversed && (sides & PW_SIDE_MUTANT)) for (size_t k = 0; k < n && !any_rev; k++) any_rev = reversed[k] != 0;
+  pw::PolishComplement comp = {{0, 0, 0, 0, 0, 0, 0, 0}};
+  if (any_rev) {
+    if (!complement) return fail("pw_batch_pileup_add_sides: reversed pairs need a complement");
+    if (complement_len != p->L) return fail("pw_batch_pileup_add_sides: complement_len must be the pileup's alphabet_len");
+    if (check_complement(fail, complement, p->L) != 0) return -1;
+    memcpy(comp.w, complement, (size_t)p->L);
+  }
+  const hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(hipSetDevice(b->device));
+  const int64_t *d_o = nullptr, *d_m = nullptr;
+  const uint8_t* d_rev = nullptr;
+  if (n && (origin_col0 || mutant_col0 || any_rev)) {
+    // (the staging buffers are rewritten in place: an add of an earlier call on ANOTHER stream may still read them)
+    if (b->d_sides_col0.p || b->d_reversed.p) for (auto& se : b->done_events) if (se.first != st) HIP_TRY(hipEventSynchronize(se.second.e));
+    b->h_sides_col0.assign(2 * n, 0);                        // (the caller's arrays are consumed here: see pw_batch_traceback_from)
+    if (origin_col0) std::copy(origin_col0, origin_col0 + n, b->h_sides_col0.begin());
+    if (mutant_col0) std::copy(mutant_col0, mutant_col0 + n, b->h_sides_col0.begin() + n);
+    if (origin_col0 || mutant_col0) {
+      if (upload(fail, b->d_sides_col0, b->h_sides_col0.data(), 2 * n, st) != 0) return -1;
+      if (origin_col0) d_o = b->d_sides_col0.p;
+      if (mutant_col0) d_m = b->d_sides_col0.p + n;
+    }
+    if (any_rev) {
+      b->h_reversed.assign(reversed, reversed + n);
+      if (upload(fail, b->d_reversed, b->h_reversed.data(), n, st) != 0) return -1;
+      d_rev = b->d_reversed.p;
+    }
+  }
+  HIP_TRY(pw::launch_polish_add(b->d_pairs.p, b->d_results.p, b->d_tx.p, b->d_arena, b->n, sides, d_o, d_m, d_rev, comp, arena_first,
+                                p->d_counts.p, p->J ? p->d_ins.p : nullptr, p->n_cols, p->L, p->J, st));
+  return mark_done(b, st);
+}
+int pw_pileup_add_letters(pw_pileup* p, const uint8_t* letters_device, int64_t lo, int64_t hi, uint32_t weight, void* stream) {
+  if (!p) return fail("pw_pileup_add_letters: null pileup");
+  if (lo < 0 || hi < lo || hi > p->n_cols) return fail("pw_pileup_add_letters: columns outside the pileup");
+  if (hi == lo) return 0;
+  if (!letters_device) return fail("pw_pileup_add_letters: null letters");
+  HIP_TRY(hipSetDevice(p->device));
+  HIP_TRY(pw::launch_polish_letters(p->d_counts.p, letters_device, lo, hi, p->L, weight, (hipStream_t)stream));
+  return 0;
+}
+int pw_pileup_polish(pw_pileup* p, const uint8_t* letters_device, const int64_t* read_offs, const int32_t* read_lens, int64_t n_reads,
+                     uint32_t min_depth, void* stream) {
+  if (!p) return fail("pw_pileup_polish: null pileup");
+  if (n_reads < 0 || n_reads > INT32_MAX || (n_reads > 0 && (!read_offs || !read_lens))) return fail("pw_pileup_polish: bad read arrays");
+  bool letters_needed = false;
+  for (int64_t r = 0; r < n_reads; r++) {
+    if (read_lens[r] < 0 || read_offs[r] < 0 || read_offs[r] > p->n_cols || read_lens[r] > p->n_cols - read_offs[r])
+      return fail("pw_pileup_polish: read " + std::to_string(r) + " lies outside the pileup");
+    letters_needed = letters_needed || read_lens[r] > 0;
+  }
+  if (letters_needed && !letters_device) return fail("pw_pileup_polish: null letters");
+  const hipStream_t st = (hipStream_t)stream;
+  const size_t n = (size_t)n_reads;
+  HIP_TRY(hipSetDevice(p->device));
+  p->polished = false;
+  p->h_roff.assign(read_offs, read_offs + n);                // (the caller's arrays are consumed here)
+  p->h_rlen.assign(read_lens, read_lens + n);
+  if (upload(fail, p->d_roff, p->h_roff.data(), n, st) != 0 || upload(fail, p->d_rlen, p->h_rlen.data(), n, st) != 0) return -1;
+  HIP_TRY(p->d_plens.ensure(n + 1));
+  HIP_TRY(p->d_poffs.ensure(n + 1));
+  HIP_TRY(p->d_pstats.ensure(n));
+  const uint32_t* ins = p->J ? p->d_ins.p : nullptr;
+  HIP_TRY(pw::launch_polish_count(p->d_counts.p, ins, letters_device, p->d_roff.p, p->d_rlen.p, n_reads, p->L, p->J, min_depth, p->d_plens.p,
+                                  p->d_poffs.p, p->d_pstats.p, p->polish_tmp, st));
+  uint64_t total = 0;                                        // the output is allocated from the counted total
+  HIP_TRY(hipMemcpyAsync(&total, p->d_poffs.p + n, 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  HIP_TRY(p->d_pletters.ensure((size_t)total));
+  HIP_TRY(pw::launch_polish_write(p->d_counts.p, ins, letters_device, p->d_roff.p, p->d_rlen.p, n_reads, p->L, p->J, min_depth, p->d_poffs.p,
+                                  p->d_pletters.p, st));
+  HIP_TRY(hipStreamSynchronize(st));                         // (the call is synchronous: it has waited for the total already)
+  p->polish_reads = n_reads; p->polish_total = (int64_t)total; p->polished = true;
+  return 0;
+}
+int64_t pw_pileup_polished_total(pw_pileup* p) {
+  if (!p) return fail("pw_pileup_polished_total: null pileup");
+  if (!p->polished) return fail("pw_pileup_polished_total before pw_pileup_polish");
+  return p->polish_total;
+}
+int pw_pileup_polished_offsets(pw_pileup* p, int64_t* host_out) {
+  if (!p) return fail("pw_pileup_polished_offsets: null pileup");
+  if (!p->polished) return fail("pw_pileup_polished_offsets before pw_pileup_polish");
+  if (!host_out) return fail("pw_pileup_polished_offsets: null output");
+  HIP_TRY(hipSetDevice(p->device));
+  HIP_TRY(hipMemcpy(host_out, p->d_poffs.p, p->d_poffs.bytes((size_t)p->polish_reads + 1), hipMemcpyDeviceToHost));
+  return 0;
+}
+int pw_pileup_polished_letters(pw_pileup* p, uint8_t* host_out) {
+  if (!p) return fail("pw_pileup_polished_letters: null pileup");
+  if (!p->polished) return fail("pw_pileup_polished_letters before pw_pileup_polish");
+  if (p->polish_total == 0) return 0;
+  if (!host_out) return fail("pw_pileup_polished_letters: null output");
+  HIP_TRY(hipSetDevice(p->device));
+  HIP_TRY(hipMemcpy(host_out, p->d_pletters.p, (size_t)p->polish_total, hipMemcpyDeviceToHost));
+  return 0;
+}
+int pw_pileup_polished_stats(pw_pileup* p, pw_polish_stats* host_out) {
+  if (!p) return fail("pw_pileup_polished_stats: null pileup");
+  if (!p->polished) return fail("pw_pileup_polished_stats before pw_pileup_polish");
+  if (p->polish_reads == 0) return 0;
+  if (!host_out) return fail("pw_pileup_polished_stats: null output");
+  HIP_TRY(hipSetDevice(p->device));
+  HIP_TRY(hipMemcpy(host_out, p->d_pstats.p, p->d_pstats.bytes((size_t)p->polish_reads), hipMemcpyDeviceToHost));
+  return 0;
+}
+void* pw_pileup_polished_letters_device(pw_pileup* p) {
+  if (!p || !p->polished) { fail("pw_pileup_polished_letters_device before pw_pileup_polish"); return nullptr; }
+  return p->d_pletters.p;
+}
+void* pw_pileup_polished_offsets_device(pw_pileup* p) {
+  if (!p || !p->polished) { fail("pw_pileup_polished_offsets_device before pw_pileup_polish"); return nullptr; }
+  return p->d_poffs.p;
 }
 
 int pw_batch_scores(pw_batch* b, int32_t k, double* out, int64_t n) {

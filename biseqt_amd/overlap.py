@@ -411,7 +411,7 @@ def aligned_batches(arena, offs, lens, pidx, dr, alphabet_len, device=0, max_cel
 
 
 def overlap_alignments(reads, pairs, bands, alphabet, p_min=0., device=0, max_cells=2 * 10 ** 10, want_transcripts=True,
-                       strands=None, complement=None, want_summaries=False, pileup=None, **aligner_kw):
+                       strands=None, complement=None, want_summaries=False, pileup=None, pileup_sides='origin', **aligner_kw):
     """Banded overlap alignment (``B_OVERLAP``) of every pair whose band has ``p >= p_min``; the ``diag_range`` is the
     band clamped to the table as ``Aligner`` requires (``pw.py:224-226``).  All reads are uploaded ONCE and the pairs
     refer to them (``BatchAligner.from_arena``); the pairs are solved in batches of at most ``max_cells`` cells
@@ -429,8 +429,15 @@ def overlap_alignments(reads, pairs, bands, alphabet, p_min=0., device=0, max_ce
     ``a`` of a pair ``(a, b)`` is always in its forward frame, minus strand included, where the letters piled onto it are
     those of ``rc(reads[b])``.  With ``arena, offs, lens = pack_reads(reads)``, letter ``x`` of read ``r`` is column
     ``offs[r] + x``: the columns of read ``r`` are ``pileup.counts(offs[r], offs[r] + lens[r])``; the columns between two
-    reads (alignment padding) stay zero.  The caller owns the pileup."""
+    reads (alignment padding) stay zero.  The caller owns the pileup.
+
+    ``pileup_sides``: ``'origin'`` (the above) or ``'both'`` (include/pw_polish.h): every batch also adds pair ``(a, b)`` onto
+    read ``b``, at ``mutant_col0 = offs[b]``, and reversed for a minus pair -- the batch itself only knows the frame of
+    ``rc(reads[b])`` behind the arena -- so that the columns of read ``b`` are always its forward letters.  The inserted
+    letters go to the insertion plane of a pileup that has one (``Pileup(..., ins_slots=J)``)."""
     from .batch import Pileup, pack_reads, summary_dict
+    if pileup_sides not in ('origin', 'both'):
+        raise ValueError("pileup_sides is 'origin' or 'both', not %r" % (pileup_sides,))
     arena, offs, lens = pack_reads(reads)
     if pileup is not None:
         if not isinstance(pileup, Pileup) or not pileup.handle:
@@ -463,7 +470,11 @@ def overlap_alignments(reads, pairs, bands, alphabet, p_min=0., device=0, max_ce
         txs = b.transcripts(res) if want_transcripts else [None] * (stop - start)
         sums = b.summaries() if want_summaries else None
         if pileup is not None:
-            b.pileup_add(pileup)
+            if pileup_sides == 'both':
+                b.pileup_add(pileup, sides='both', mutant_col0=offs[pidx[start:stop, 1]],
+                             reverse=None if sub is None else sub[start:stop], complement=comp)
+            else:
+                b.pileup_add(pileup)
             b.sync()                                               # (the batch goes when the generator moves on)
         for k in range(stop - start):
             if res['opt_i'][k] < 0:
@@ -475,6 +486,57 @@ def overlap_alignments(reads, pairs, bands, alphabet, p_min=0., device=0, max_ce
             if sums is not None:
                 out[sel[start + k]]['summary'] = summary_dict(sums[k])
     return out
+
+
+def polish_reads(reads, pairs, bands, alphabet, p_min=0., strands=None, complement=None, min_depth=3, ins_slots=2, self_weight=1,
+                 device=0, stats=None, **aligner_kw):
+    """Read correction from overlaps that are known (include/pw_polish.h): the reads are packed, every read votes for its own
+    letters with ``self_weight``, :func:`overlap_alignments` piles every aligned pair onto BOTH of its reads
+    (``pileup_sides='both'``, no transcript leaves the device) into a pileup with ``ins_slots`` insertion slots, and the
+    pileup is polished with ``min_depth``.  ``pairs``, ``bands``, ``p_min``, ``strands``, ``complement`` and ``aligner_kw``
+    are :func:`overlap_alignments`'.  Returns the corrected reads as uint8 arrays, in read order.  ``stats`` (a dict)
+    receives ``records`` (one ``batch.POLISH_STATS_DTYPE`` record per read), ``aligned`` (pairs with an alignment) and the
+    times of the three device stages in ms, taken on the host around synchronised device work: ``vote_ms``, ``align_ms``
+    (alignment and two-sided adds), ``polish_ms``."""
+    import time
+    from .batch import DeviceArena, Pileup, pack_reads
+    assert isinstance(alphabet, Alphabet)
+    arena, offs, lens = pack_reads(reads)
+    letters = np.full(arena.nbytes, 255, np.uint8)             # the padding between two reads votes for nothing
+    for o, n in zip(offs.tolist(), lens.tolist()):
+        letters[o:o + n] = arena[o:o + n]
+    with Pileup(arena.nbytes, len(alphabet), device=device, ins_slots=ins_slots) as pile, DeviceArena(letters, device) as dev:
+        t0 = time.perf_counter()
+        pile.add_letters((dev, 0), weight=self_weight)
+        dev.read(0, 1)                                         # (a synchronous copy behind the vote)
+        t1 = time.perf_counter()
+        alns = overlap_alignments(reads, pairs, bands, alphabet, p_min=p_min, device=device, want_transcripts=False, strands=strands,
+                                  complement=complement, pileup=pile, pileup_sides='both', **aligner_kw)
+        t2 = time.perf_counter()
+        out, offsets, records = pile.polish((dev, 0), offs, lens, min_depth=min_depth)
+        t3 = time.perf_counter()
+    if stats is not None:
+        stats.update(records=records, aligned=sum(a is not None for a in alns), vote_ms=1e3 * (t1 - t0), align_ms=1e3 * (t2 - t1),
+                     polish_ms=1e3 * (t3 - t2))
+    return [out[offsets[r]:offsets[r + 1]].copy() for r in range(len(lens))]
+
+
+def correct_reads(reads, wordlen, alphabet, g_max, sensitivity, p_min=.8, strands='+', complement=None, minimizer_window=None,
+                  max_kmer_occ=None, max_pairs=None, min_depth=3, ins_slots=2, self_weight=1, device=0, stats=None, **aligner_kw):
+    """From reads to corrected reads in one call: :func:`overlap_all_pairs` (``strands``, ``complement``, ``minimizer_window``,
+    ``max_kmer_occ``, ``max_pairs`` are its arguments), then :func:`polish_reads` on the pairs it found whose band has
+    ``p >= p_min`` (under minimizer sampling ``p`` is the estimate from the sampled seeds: rescale ``p_min``).  ``stats``
+    receives what both stages report, the overlap stage's under ``overlaps``."""
+    ostats = {}
+    found = overlap_all_pairs(reads, wordlen, alphabet, g_max, sensitivity, device=device, max_pairs=max_pairs, stats=ostats,
+                              strands=strands, complement=complement, max_kmer_occ=max_kmer_occ, minimizer_window=minimizer_window)
+    keys = list(found)
+    pairs = [(k[0], k[1]) for k in keys]
+    pstrands = [k[2] for k in keys] if strands != '+' else None
+    if stats is not None:
+        stats['overlaps'] = ostats
+    return polish_reads(reads, pairs, [found[k] for k in keys], alphabet, p_min=p_min, strands=pstrands, complement=complement,
+                        min_depth=min_depth, ins_slots=ins_slots, self_weight=self_weight, device=device, stats=stats, **aligner_kw)
 
 
 def raw_bands_sharded(reads, pairs, wordlen, alphabet_len, g_max, sensitivity, rank, world, device=None, gather_device=None,
