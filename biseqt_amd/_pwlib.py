@@ -1,5 +1,5 @@
 """ctypes binding of biseqt_amd/pwlib/pwlib.so (the HIP library; C ABI in include/pwlib.h,
-include/pw_batch.h, include/pw_txsum.h, include/pw_cigar.h, include/pw_pileup.h, include/pw_polish.h and the seed headers include/pw_seeds.h, pw_mseeds.h, pw_qseeds.h, pw_overlap.h).
+include/pw_batch.h, include/pw_txsum.h, include/pw_cigar.h, include/pw_pileup.h, include/pw_polish.h, include/pw_graph.h and the seed headers include/pw_seeds.h, pw_mseeds.h, pw_qseeds.h, pw_overlap.h).
 
 The reference binds its C library with cffi in ABI mode (``biseqt/pw.py:45-69``); cffi is not
 available in this image, so the same structs are declared with ctypes -- field for field the layout of
@@ -117,6 +117,29 @@ class pw_polish_stats(C.Structure):
     _fields_ = [(f, C.c_uint32) for f in ('kept', 'substituted', 'deleted', 'inserted')]
 
 
+# ---- the overlap graph (include/pw_graph.h) ----
+class pw_graph_overlap(C.Structure):
+    _fields_ = [(f, C.c_int32) for f in ('a', 'b', 'strand', 'cls', 'a_beg', 'a_end', 'b_beg', 'b_end', 'n_match', 'n_ops')]
+
+
+class pw_graph_params(C.Structure):
+    _fields_ = [('max_hang', C.c_int32), ('min_overlap', C.c_int32), ('fuzz', C.c_int32), ('pad_', C.c_int32),
+                ('int_frac', C.c_double), ('min_identity', C.c_double)]
+
+
+class pw_graph_arc(C.Structure):
+    _fields_ = [(f, C.c_int32) for f in ('v', 'w', 'len', 'ol', 'src', 'flags')]
+
+
+class pw_unitig(C.Structure):
+    _fields_ = [('first_member', C.c_int64), ('length', C.c_int64), ('n_members', C.c_int32), ('head', C.c_int32),
+                ('circular', C.c_int32), ('pad_', C.c_int32)]
+
+
+class pw_unitig_member(C.Structure):
+    _fields_ = [('vertex', C.c_int32), ('advance', C.c_int32), ('offset', C.c_int64)]
+
+
 PW_TXSUM_DONE = 1
 PW_ST_TRACED, PW_ST_EMPTY, PW_ST_PANICK, PW_ST_BADPATH = 1, 2, 4, 8
 PW_FLAG_DUMP_SCORES, PW_FLAG_FORCE_F64, PW_FLAG_FORCE_GENERIC, PW_FLAG_PROFILE = 1, 2, 4, 8
@@ -128,7 +151,8 @@ PW_FLAG_NO_STRIP = 256
 
 SIZEOF = dict(intpair=8, alnscores=24, alnframe=32, std_alnparams=4, banded_alnparams=12,
               alnprob=32, alnchoice=32, dpcell=16, dptable=32, alignment=24,
-              pw_scoring=40, pw_pair=32, pw_result=32, pw_tx_summary=48, pw_pileup_site=8, pw_polish_stats=16)
+              pw_scoring=40, pw_pair=32, pw_result=32, pw_tx_summary=48, pw_pileup_site=8, pw_polish_stats=16,
+              pw_graph_overlap=40, pw_graph_params=32, pw_graph_arc=24, pw_unitig=32, pw_unitig_member=16)
 
 # every symbol include/pwlib.h and include/pw_batch.h declare
 EXPORTS = ['dptable_init', 'dptable_solve', 'dptable_traceback', 'dptable_free',
@@ -162,6 +186,15 @@ POLISH_EXPORTS = ['pw_pileup_create_ins', 'pw_pileup_ins_slots', 'pw_pileup_ins_
                   'pw_pileup_polished_letters_device', 'pw_pileup_polished_offsets_device']
 PW_POLISH_MAX_SLOTS = 8
 PW_SIDE_ORIGIN, PW_SIDE_MUTANT, PW_SIDE_BOTH = 1, 2, 3
+# every symbol and constant include/pw_graph.h declares
+GRAPH_EXPORTS = ['pw_graph_create', 'pw_graph_free', 'pw_graph_num_overlaps', 'pw_graph_device_bytes', 'pw_graph_add_overlaps', 'pw_batch_graph_add', 'pw_graph_build', 'pw_graph_num_arcs', 'pw_graph_num_unitigs',
+                 'pw_graph_num_members', 'pw_graph_reduce_ms', 'pw_graph_overlaps', 'pw_graph_contained', 'pw_graph_arcs', 'pw_graph_rows', 'pw_graph_unitigs',
+                 'pw_graph_members', 'pw_graph_overlaps_device', 'pw_graph_contained_device', 'pw_graph_arcs_device',
+                 'pw_graph_rows_device', 'pw_graph_unitigs_device', 'pw_graph_members_device', 'pw_graph_contigs',
+                 'pw_graph_contig_total', 'pw_graph_contig_offsets', 'pw_graph_contig_letters', 'pw_graph_contig_letters_device',
+                 'pw_graph_contig_offsets_device']
+PW_OVL_NONE, PW_OVL_WEAK, PW_OVL_INTERNAL, PW_OVL_A_CONTAINED, PW_OVL_B_CONTAINED, PW_OVL_A_TO_B, PW_OVL_B_TO_A = range(7)
+PW_ARC_REDUCED, PW_ARC_REMOVED, PW_ARC_CHAIN = 1, 2, 4
 # every symbol include/pw_seeds.h declares
 SEED_EXPORTS = ['pw_seeds_create', 'pw_seeds_build', 'pw_seeds_num_rows', 'pw_seeds_is_self', 'pw_seeds_rows_device',
                 'pw_seeds_rows', 'pw_seeds_count', 'pw_seeds_kmers', 'pw_seeds_band_neighbours', 'pw_seeds_graph_build', 'pw_seeds_graph_num_points', 'pw_seeds_graph_points',
@@ -384,6 +417,28 @@ def load():
     lib.pw_pileup_polished_letters_device.restype = C.c_void_p
     lib.pw_pileup_polished_offsets_device.argtypes = [C.c_void_p]
     lib.pw_pileup_polished_offsets_device.restype = C.c_void_p
+    # include/pw_graph.h
+    lib.pw_graph_create.argtypes = [C.c_int, C.c_int64, C.c_void_p]
+    lib.pw_graph_create.restype = C.c_void_p
+    lib.pw_graph_free.argtypes = [C.c_void_p]
+    lib.pw_graph_free.restype = None
+    for f in ('pw_graph_num_overlaps', 'pw_graph_device_bytes', 'pw_graph_num_arcs', 'pw_graph_num_unitigs',
+              'pw_graph_num_members', 'pw_graph_contig_total'):
+        getattr(lib, f).argtypes = [C.c_void_p]
+        getattr(lib, f).restype = C.c_int64
+    lib.pw_graph_reduce_ms.argtypes = [C.c_void_p]
+    lib.pw_graph_reduce_ms.restype = C.c_double
+    lib.pw_graph_add_overlaps.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+    lib.pw_batch_graph_add.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.pw_graph_build.argtypes = [C.c_void_p, P(pw_graph_params), C.c_void_p]
+    for f in ('pw_graph_overlaps', 'pw_graph_contained', 'pw_graph_arcs', 'pw_graph_rows', 'pw_graph_unitigs', 'pw_graph_members',
+              'pw_graph_contig_offsets', 'pw_graph_contig_letters'):
+        getattr(lib, f).argtypes = [C.c_void_p, C.c_void_p]
+    for f in ('pw_graph_overlaps_device', 'pw_graph_contained_device', 'pw_graph_arcs_device', 'pw_graph_rows_device',
+              'pw_graph_unitigs_device', 'pw_graph_members_device', 'pw_graph_contig_letters_device', 'pw_graph_contig_offsets_device'):
+        getattr(lib, f).argtypes = [C.c_void_p]
+        getattr(lib, f).restype = C.c_void_p
+    lib.pw_graph_contigs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     # include/pw_seeds.h
     lib.pw_seeds_create.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int,
                                     P(C.c_uint64), C.c_int, C.c_int]

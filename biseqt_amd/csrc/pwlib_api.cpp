@@ -6,6 +6,7 @@
 // reported as an error.
 #include <hip/hip_runtime.h>
 #include <math.h>
+#include <cmath>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -18,17 +19,20 @@
 #include <mutex>
 #include <thread>
 #include <vector>
+#include <unordered_set>
 
 #include "../../include/pw_batch.h"
 #include "../../include/pw_txsum.h"
 #include "../../include/pw_cigar.h"
 #include "../../include/pw_pileup.h"
 #include "../../include/pw_polish.h"
+#include "../../include/pw_graph.h"
 #include "pw_launch.h"
 #include "pw_plan.h"
 #include "pw_model.h"
 #include "pw_hip_host.h"
 #include "pw_complement.h"
+#include "pw_graph_launch.h"
 #define PW_FN inline
 #include "pw_strip.h"
 #include <atomic>
@@ -1415,6 +1419,207 @@ void* pw_pileup_polished_letters_device(pw_pileup* p) {
 void* pw_pileup_polished_offsets_device(pw_pileup* p) {
   if (!p || !p->polished) { fail("pw_pileup_polished_offsets_device before pw_pileup_polish"); return nullptr; }
   return p->d_poffs.p;
+}
+
+// ---- the overlap graph (include/pw_graph.h; kernels and stage sequences in pw_graph.hip) ----
+struct pw_graph {
+  pw::GraphState s;
+  std::vector<int32_t> lens;             // [n_reads]
+  std::unordered_set<uint64_t> keys;     // (a * n_reads + b) * 2 + strand of every record
+  std::string duplicate;                 // the first duplicate key, in words; pw_graph_build reports it
+  std::vector<int32_t> h_stage;          // pw_batch_graph_add: the host copy d_stage is uploaded from
+  std::vector<int64_t> h_roff;           // pw_graph_contigs: ... and d_roff
+};
+
+namespace {
+
+// what both add paths refuse of (a, b, strand), and the duplicate keys they remember for the build
+int graph_check_key(const char* who, pw_graph* g, int64_t k, int64_t a, int64_t b, int64_t strand) {
+  const int64_t R = g->s.n_reads;
+  if (a < 0 || a >= R || b < 0 || b >= R) return fail(std::string(who) + ": record " + std::to_string(k) + " names a read outside the graph");
+  if (a == b) return fail(std::string(who) + ": record " + std::to_string(k) + " pairs read " + std::to_string(a) + " with itself");
+  if (strand != 0 && strand != 1) return fail(std::string(who) + ": record " + std::to_string(k) + " has a strand other than 0 / 1");
+  return 0;
+}
+void graph_note_key(pw_graph* g, int64_t a, int64_t b, int64_t strand) {
+  if (!g->keys.insert((uint64_t)((a * g->s.n_reads + b) * 2 + strand)).second && g->duplicate.empty())
+    g->duplicate = "(" + std::to_string(a) + ", " + std::to_string(b) + ", " + std::to_string(strand) + ")";
+}
+
+}  // namespace
+
+pw_graph* pw_graph_create(int device, int64_t n_reads, const int32_t* read_lens) {
+  if (n_reads < 0 || n_reads > ((int64_t)1 << 28)) { fail("pw_graph_create: n_reads out of range"); return nullptr; }
+  if (n_reads > 0 && !read_lens) { fail("pw_graph_create: null read lengths"); return nullptr; }
+  for (int64_t r = 0; r < n_reads; r++)
+    if (read_lens[r] < 0) { fail("pw_graph_create: read " + std::to_string(r) + " has a negative length"); return nullptr; }
+  std::unique_ptr<pw_graph> g(new pw_graph);
+  g->s.device = device; g->s.n_reads = n_reads; g->s.V = 2 * n_reads;
+  g->lens.assign(read_lens, read_lens + n_reads);
+  if (hipSetDevice(device) != hipSuccess || upload(fail, g->s.d_lens, g->lens.data(), (size_t)n_reads) != 0) {
+    fail("pw_graph_create: allocation failed");
+    return nullptr;
+  }
+  return g.release();
+}
+void pw_graph_free(pw_graph* g) {
+  if (!g) return;
+  (void)hipSetDevice(g->s.device);
+  delete g;
+}
+int64_t pw_graph_num_overlaps(const pw_graph* g) { return g ? g->s.n_recs : 0; }
+int64_t pw_graph_device_bytes(const pw_graph* g) { return g ? pw::graph_device_bytes(g->s) : 0; }
+
+int pw_graph_add_overlaps(pw_graph* g, const pw_graph_overlap* recs, int64_t n) {
+  if (!g) return fail("pw_graph_add_overlaps: null graph");
+  if (n < 0 || g->s.n_recs + n > ((int64_t)1 << 30)) return fail("pw_graph_add_overlaps: record count out of range");
+  if (n == 0) return 0;
+  if (!recs) return fail("pw_graph_add_overlaps: null records");
+  for (int64_t k = 0; k < n; k++) {
+    const pw_graph_overlap& r = recs[k];
+    if (graph_check_key("pw_graph_add_overlaps", g, k, r.a, r.b, r.strand) != 0) return -1;
+    const int la = g->lens[(size_t)r.a], lb = g->lens[(size_t)r.b];
+    if (r.a_beg < 0 || r.a_beg > r.a_end || r.a_end > la || r.b_beg < 0 || r.b_beg > r.b_end || r.b_end > lb)
+      return fail("pw_graph_add_overlaps: record " + std::to_string(k) + " has an interval outside its read");
+    if (r.n_match < 0 || r.n_match > r.n_ops) return fail("pw_graph_add_overlaps: record " + std::to_string(k) + " has not 0 <= n_match <= n_ops");
+  }
+  HIP_TRY(hipSetDevice(g->s.device));
+  HIP_TRY(pw::graph_reserve(g->s, n, nullptr));
+  std::vector<pw_graph_overlap> tmp(recs, recs + n);
+  for (auto& r : tmp) r.cls = PW_OVL_NONE;
+  HIP_TRY(hipMemcpy(g->s.d_recs.p + g->s.n_recs, tmp.data(), sizeof(pw_graph_overlap) * (size_t)n, hipMemcpyHostToDevice));
+  for (int64_t k = 0; k < n; k++) graph_note_key(g, recs[k].a, recs[k].b, recs[k].strand);
+  g->s.n_recs += n;
+  return 0;
+}
+
+int pw_batch_graph_add(pw_batch* b, pw_graph* g, const int32_t* read_a, const int32_t* read_b, const uint8_t* strand, void* stream) {
+  if (!b || !g) return fail("pw_batch_graph_add: null batch or graph");
+  if (!b->traced) return fail("pw_batch_graph_add before a traceback of the batch");
+  if (b->device != g->s.device) return fail("pw_batch_graph_add: the batch and the graph live on different devices");
+  const int64_t n = b->n;
+  if (g->s.n_recs + n > ((int64_t)1 << 30)) return fail("pw_batch_graph_add: record count out of range");
+  if (n == 0) return 0;
+  if (!read_a || !read_b) return fail("pw_batch_graph_add: null read indices");
+  for (int64_t k = 0; k < n; k++) {
+    if (graph_check_key("pw_batch_graph_add", g, k, read_a[k], read_b[k], strand ? strand[k] : 0) != 0) return -1;
+    if (b->pairs[(size_t)k].origin_len != g->lens[(size_t)read_a[k]] || b->pairs[(size_t)k].mutant_len != g->lens[(size_t)read_b[k]])
+      return fail("pw_batch_graph_add: the frames of pair " + std::to_string(k) + " are not the whole reads " + std::to_string(read_a[k]) +
+                  " and " + std::to_string(read_b[k]));
+  }
+  const hipStream_t st = (hipStream_t)stream;
+  if ((!b->d_summaries.p || b->summary_seq != b->trace_seq) && pw_batch_summarize(b, stream) != 0) return -1;
+  HIP_TRY(hipSetDevice(b->device));
+  HIP_TRY(pw::graph_reserve(g->s, n, st));
+  HIP_TRY(hipStreamSynchronize(st));                         // (the staging array is rewritten in place: the last add has read it)
+  g->h_stage.resize(3 * (size_t)n);                          // (the caller's arrays are consumed here)
+  for (int64_t k = 0; k < n; k++) {
+    g->h_stage[(size_t)k] = read_a[k]; g->h_stage[(size_t)(n + k)] = read_b[k]; g->h_stage[(size_t)(2 * n + k)] = strand ? strand[k] : 0;
+  }
+  if (upload(fail, g->s.d_stage, g->h_stage.data(), 3 * (size_t)n, st) != 0) return -1;
+  HIP_TRY(pw::launch_graph_from_batch(g->s, b->d_results.p, b->d_summaries.p, (int)n, st));
+  for (int64_t k = 0; k < n; k++) graph_note_key(g, read_a[k], read_b[k], strand ? strand[k] : 0);
+  g->s.n_recs += n;
+  return mark_done(b, st);
+}
+
+int pw_graph_build(pw_graph* g, const pw_graph_params* p, void* stream) {
+  if (!g || !p) return fail("pw_graph_build: null graph or parameters");
+  if (!g->duplicate.empty()) return fail("pw_graph_build: duplicate overlap key " + g->duplicate);
+  if (!std::isfinite(p->int_frac) || !std::isfinite(p->min_identity)) return fail("pw_graph_build: int_frac and min_identity must be finite");
+  if (p->max_hang < 0 || p->min_overlap < 0 || p->fuzz < 0) return fail("pw_graph_build: max_hang, min_overlap and fuzz must not be negative");
+  HIP_TRY(hipSetDevice(g->s.device));
+  HIP_TRY(pw::graph_build(g->s, *p, (hipStream_t)stream));
+  return 0;
+}
+
+int64_t pw_graph_num_arcs(pw_graph* g) { return g && g->s.built ? g->s.n_arcs : fail("pw_graph_num_arcs before pw_graph_build"); }
+int64_t pw_graph_num_unitigs(pw_graph* g) { return g && g->s.built ? g->s.n_unitigs : fail("pw_graph_num_unitigs before pw_graph_build"); }
+double pw_graph_reduce_ms(pw_graph* g) { return g && g->s.built ? g->s.reduce_ms : -1.; }
+int64_t pw_graph_num_members(pw_graph* g) { return g && g->s.built ? g->s.n_members : fail("pw_graph_num_members before pw_graph_build"); }
+
+namespace {
+
+extern "C++" {
+template <class T, class U>
+int graph_copy_out(const char* who, pw_graph* g, bool ready, const DeviceArray<T>& arr, int64_t count, U* host_out) {
+  if (!g) return fail(std::string(who) + ": null graph");
+  if (!ready) return fail(std::string(who) + " before pw_graph_build");
+  if (count == 0) return 0;
+  if (!host_out) return fail(std::string(who) + ": null output");
+  static_assert(sizeof(T) == sizeof(U), "host and device records have one size");
+  HIP_TRY(hipSetDevice(g->s.device));
+  HIP_TRY(hipMemcpy(host_out, arr.p, arr.bytes((size_t)count), hipMemcpyDeviceToHost));
+  return 0;
+}
+template <class T>
+void* graph_device_ptr(const char* who, pw_graph* g, bool ready, const DeviceArray<T>& arr) {
+  if (!g || !ready) { fail(std::string(who) + " before pw_graph_build"); return nullptr; }
+  return arr.p;
+}
+}  // extern "C++"
+
+}  // namespace
+
+int pw_graph_overlaps(pw_graph* g, pw_graph_overlap* out) { if (!g) return fail("pw_graph_overlaps: null graph"); return graph_copy_out("pw_graph_overlaps", g, true, g->s.d_recs, g->s.n_recs, out); }
+int pw_graph_contained(pw_graph* g, uint8_t* out) { if (!g) return fail("pw_graph_contained: null graph"); return graph_copy_out("pw_graph_contained", g, g && g->s.built, g->s.d_contained, g->s.n_reads, out); }
+int pw_graph_arcs(pw_graph* g, pw_graph_arc* out) { if (!g) return fail("pw_graph_arcs: null graph"); return graph_copy_out("pw_graph_arcs", g, g && g->s.built, g->s.d_arcs, g->s.n_arcs, out); }
+int pw_graph_rows(pw_graph* g, int64_t* out) { if (!g) return fail("pw_graph_rows: null graph"); return graph_copy_out("pw_graph_rows", g, g && g->s.built, g->s.d_rows, g->s.V + 1, out); }
+int pw_graph_unitigs(pw_graph* g, pw_unitig* out) { if (!g) return fail("pw_graph_unitigs: null graph"); return graph_copy_out("pw_graph_unitigs", g, g && g->s.built, g->s.d_unitigs, g->s.n_unitigs, out); }
+int pw_graph_members(pw_graph* g, pw_unitig_member* out) { if (!g) return fail("pw_graph_members: null graph"); return graph_copy_out("pw_graph_members", g, g && g->s.built, g->s.d_members, g->s.n_members, out); }
+void* pw_graph_overlaps_device(pw_graph* g) { if (!g) { fail("pw_graph_overlaps_device: null graph"); return nullptr; } return graph_device_ptr("pw_graph_overlaps_device", g, true, g->s.d_recs); }
+void* pw_graph_contained_device(pw_graph* g) { if (!g) { fail("pw_graph_contained_device: null graph"); return nullptr; } return graph_device_ptr("pw_graph_contained_device", g, g && g->s.built, g->s.d_contained); }
+void* pw_graph_arcs_device(pw_graph* g) { if (!g) { fail("pw_graph_arcs_device: null graph"); return nullptr; } return graph_device_ptr("pw_graph_arcs_device", g, g && g->s.built, g->s.d_arcs); }
+void* pw_graph_rows_device(pw_graph* g) { if (!g) { fail("pw_graph_rows_device: null graph"); return nullptr; } return graph_device_ptr("pw_graph_rows_device", g, g && g->s.built, g->s.d_rows); }
+void* pw_graph_unitigs_device(pw_graph* g) { if (!g) { fail("pw_graph_unitigs_device: null graph"); return nullptr; } return graph_device_ptr("pw_graph_unitigs_device", g, g && g->s.built, g->s.d_unitigs); }
+void* pw_graph_members_device(pw_graph* g) { if (!g) { fail("pw_graph_members_device: null graph"); return nullptr; } return graph_device_ptr("pw_graph_members_device", g, g && g->s.built, g->s.d_members); }
+
+int pw_graph_contigs(pw_graph* g, const uint8_t* letters_device, const int64_t* read_offs, const uint8_t* complement, int complement_len,
+                     void* stream) {
+  if (!g) return fail("pw_graph_contigs: null graph");
+  if (!g->s.built) return fail("pw_graph_contigs before pw_graph_build");
+  if (complement && (complement_len < 1 || complement_len > 256)) return fail("pw_graph_contigs: complement_len must be 1..256");
+  const int64_t R = g->s.n_reads;
+  if (R > 0 && !read_offs) return fail("pw_graph_contigs: null read offsets");
+  for (int64_t r = 0; r < R; r++)
+    if (read_offs[r] < 0) return fail("pw_graph_contigs: read " + std::to_string(r) + " has a negative offset");
+  if (g->s.n_members > 0 && !letters_device) return fail("pw_graph_contigs: null letters");
+  const hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(hipSetDevice(g->s.device));
+  uint8_t table[256];
+  for (int c = 0; c < 256; c++) table[c] = complement && c < complement_len ? complement[c] : (uint8_t)c;
+  g->h_roff.assign(read_offs, read_offs + R);                // (the caller's array is consumed here)
+  if (upload(fail, g->s.d_roff, g->h_roff.data(), (size_t)R, st) != 0) return -1;
+  HIP_TRY(g->s.d_comp.ensure(256));
+  HIP_TRY(hipMemcpy(g->s.d_comp.p, table, 256, hipMemcpyHostToDevice));
+  HIP_TRY(pw::graph_contigs(g->s, letters_device, st));
+  return 0;
+}
+int64_t pw_graph_contig_total(pw_graph* g) {
+  return g && g->s.has_contigs ? g->s.contig_total : fail("pw_graph_contig_total before pw_graph_contigs");
+}
+int pw_graph_contig_offsets(pw_graph* g, int64_t* out) {
+  if (!g || !g->s.has_contigs) return fail("pw_graph_contig_offsets before pw_graph_contigs");
+  if (!out) return fail("pw_graph_contig_offsets: null output");
+  HIP_TRY(hipSetDevice(g->s.device));
+  HIP_TRY(hipMemcpy(out, g->s.d_coff.p, g->s.d_coff.bytes((size_t)g->s.n_unitigs + 1), hipMemcpyDeviceToHost));
+  return 0;
+}
+int pw_graph_contig_letters(pw_graph* g, uint8_t* out) {
+  if (!g || !g->s.has_contigs) return fail("pw_graph_contig_letters before pw_graph_contigs");
+  if (g->s.contig_total == 0) return 0;
+  if (!out) return fail("pw_graph_contig_letters: null output");
+  HIP_TRY(hipSetDevice(g->s.device));
+  HIP_TRY(hipMemcpy(out, g->s.d_cletters.p, (size_t)g->s.contig_total, hipMemcpyDeviceToHost));
+  return 0;
+}
+void* pw_graph_contig_letters_device(pw_graph* g) {
+  if (!g || !g->s.has_contigs) { fail("pw_graph_contig_letters_device before pw_graph_contigs"); return nullptr; }
+  return g->s.d_cletters.p;
+}
+void* pw_graph_contig_offsets_device(pw_graph* g) {
+  if (!g || !g->s.has_contigs) { fail("pw_graph_contig_offsets_device before pw_graph_contigs"); return nullptr; }
+  return g->s.d_coff.p;
 }
 
 int pw_batch_scores(pw_batch* b, int32_t k, double* out, int64_t n) {

@@ -1,0 +1,170 @@
+"""The overlap graph on the device (include/pw_graph.h holds the contract): overlap records, their containment / dovetail
+classes, arcs, transitive reduction, unitigs and contig letters.  Every computing call goes to the kernels of
+``pw_graph.hip``; there is no host fallback."""
+import ctypes as C
+
+import numpy as np
+
+from . import _pwlib as W
+from .batch import BatchAligner, DeviceArena, _as_u8, pack_reads
+
+OVERLAP_DTYPE = np.dtype([(f, '<i4') for f in ('a', 'b', 'strand', 'cls', 'a_beg', 'a_end', 'b_beg', 'b_end', 'n_match', 'n_ops')])
+ARC_DTYPE = np.dtype([(f, '<i4') for f in ('v', 'w', 'len', 'ol', 'src', 'flags')])
+UNITIG_DTYPE = np.dtype([('first_member', '<i8'), ('length', '<i8'), ('n_members', '<i4'), ('head', '<i4'), ('circular', '<i4'),
+                         ('pad_', '<i4')])
+MEMBER_DTYPE = np.dtype([('vertex', '<i4'), ('advance', '<i4'), ('offset', '<i8')])
+assert (OVERLAP_DTYPE.itemsize, ARC_DTYPE.itemsize, UNITIG_DTYPE.itemsize, MEMBER_DTYPE.itemsize) == (40, 24, 32, 16)
+NONE, WEAK, INTERNAL, A_CONTAINED, B_CONTAINED, A_TO_B, B_TO_A = range(7)
+CLASS_NAMES = ('NONE', 'WEAK', 'INTERNAL', 'A_CONTAINED', 'B_CONTAINED', 'A_TO_B', 'B_TO_A')
+ARC_REDUCED, ARC_REMOVED, ARC_CHAIN = W.PW_ARC_REDUCED, W.PW_ARC_REMOVED, W.PW_ARC_CHAIN
+
+
+def overlap_records(rows):
+    """An :data:`OVERLAP_DTYPE` array from rows ``(a, b, strand, a_beg, a_end, b_beg, b_end, n_match, n_ops)``; ``cls`` is 0."""
+    out = np.zeros(len(rows), OVERLAP_DTYPE)
+    for k, row in enumerate(rows):
+        (out['a'][k], out['b'][k], out['strand'][k], out['a_beg'][k], out['a_end'][k], out['b_beg'][k], out['b_end'][k],
+         out['n_match'][k], out['n_ops'][k]) = row
+    return out
+
+
+class OverlapGraph(object):
+    """The overlap graph of ``len(read_lens)`` reads, device-resident: records come from :meth:`add` (planted, host) or
+    :meth:`add_batch` (a traced-back :class:`BatchAligner`), :meth:`build` classifies them, reduces the graph and lays out the
+    unitigs, :meth:`contigs` writes the letters.  A context manager that frees itself, like :class:`biseqt_amd.batch.Pileup`."""
+
+    def __init__(self, read_lens, device=0):
+        self.handle = None
+        lens = np.ascontiguousarray(read_lens, np.int64).reshape(-1)
+        if len(lens) and (lens.min() < 0 or lens.max() >= 1 << 31):
+            raise ValueError('read lengths must lie in 0 .. 2**31 - 1')
+        self.read_lens = lens.astype(np.int32)
+        self.n_reads, self.device = len(lens), device
+        self.lib = W.load()
+        self.handle = self.lib.pw_graph_create(device, self.n_reads, self.read_lens.ctypes.data)
+        if not self.handle:
+            raise RuntimeError('pw_graph_create failed: ' + W.last_error())
+
+    def close(self):
+        if getattr(self, 'handle', None):
+            self.lib.pw_graph_free(self.handle)
+            self.handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _ck(self, rc, what):
+        if rc != 0:
+            raise RuntimeError('%s failed: %s' % (what, W.last_error()))
+
+    def _count(self, what):
+        n = int(getattr(self.lib, what)(self.handle))
+        if n < 0:
+            raise RuntimeError('%s failed: %s' % (what, W.last_error()))
+        return n
+
+    def __len__(self):
+        return int(self.lib.pw_graph_num_overlaps(self.handle))
+
+    @property
+    def device_bytes(self):
+        return int(self.lib.pw_graph_device_bytes(self.handle))
+
+    @property
+    def reduce_ms(self):
+        """Device time of the reduction kernel in the last build, ms; -1 before a build and for a graph without arcs."""
+        return float(self.lib.pw_graph_reduce_ms(self.handle))
+
+    def add(self, records):
+        """Append planted records: an :data:`OVERLAP_DTYPE` array (``cls`` is ignored; ``n_ops == 0`` is a pair without an
+        alignment), or rows for :func:`overlap_records`."""
+        recs = records if isinstance(records, np.ndarray) and records.dtype == OVERLAP_DTYPE else overlap_records(list(records))
+        recs = np.ascontiguousarray(recs)
+        self._ck(self.lib.pw_graph_add_overlaps(self.handle, recs.ctypes.data, len(recs)), 'pw_graph_add_overlaps')
+
+    def add_batch(self, batch, read_a, read_b, strands=None, stream=None):
+        """One record per pair of a traced-back ``batch`` (asynchronous on ``stream``): pair ``k`` aligns the whole of read
+        ``read_a[k]`` with the whole of read ``read_b[k]``, or with its reverse complement where ``strands[k]`` is set."""
+        if not isinstance(batch, BatchAligner) or not batch.handle:
+            raise ValueError('batch must be an open BatchAligner')
+        a = np.ascontiguousarray(read_a, np.int32).reshape(-1)
+        b = np.ascontiguousarray(read_b, np.int32).reshape(-1)
+        s = None if strands is None else np.ascontiguousarray(strands, np.uint8).reshape(-1)
+        if len(a) != batch.n or len(b) != batch.n or (s is not None and len(s) != batch.n):
+            raise ValueError('read_a, read_b and strands need one entry per pair of the batch (%d)' % batch.n)
+        self._ck(self.lib.pw_batch_graph_add(batch.handle, self.handle, a.ctypes.data, b.ctypes.data, None if s is None else s.ctypes.data,
+                                             stream), 'pw_batch_graph_add')
+
+    def build(self, max_hang=1000, int_frac=.8, min_overlap=0, min_identity=0., fuzz=10, stream=None):
+        """Classify, reduce and lay out what has been added (``pw_graph_build``; synchronous).  A second build replaces the first."""
+        for name, v in (('max_hang', max_hang), ('min_overlap', min_overlap), ('fuzz', fuzz)):
+            if not 0 <= int(v) < 1 << 31:
+                raise ValueError('%s must lie in 0 .. 2**31 - 1' % name)
+        if not (np.isfinite(int_frac) and np.isfinite(min_identity)):
+            raise ValueError('int_frac and min_identity must be finite')
+        p = W.pw_graph_params(int(max_hang), int(min_overlap), int(fuzz), 0, float(int_frac), float(min_identity))
+        self._ck(self.lib.pw_graph_build(self.handle, C.byref(p), stream), 'pw_graph_build')
+
+    def _fetch(self, what, n, dtype):
+        out = np.zeros(n, dtype)
+        self._ck(getattr(self.lib, what)(self.handle, out.ctypes.data), what)
+        return out
+
+    def overlaps(self):
+        """The records (:data:`OVERLAP_DTYPE`), ``cls`` as the last :meth:`build` left it."""
+        return self._fetch('pw_graph_overlaps', len(self), OVERLAP_DTYPE)
+
+    def contained(self):
+        """One byte per read: 1 where some record classifies the read as contained."""
+        return self._fetch('pw_graph_contained', self.n_reads, np.uint8)
+
+    def arcs(self):
+        """``(arcs, rows)``: the sorted arc table (:data:`ARC_DTYPE`) and its row index ``int64[2 * n_reads + 1]``."""
+        return self._fetch('pw_graph_arcs', self._count('pw_graph_num_arcs'), ARC_DTYPE), \
+            self._fetch('pw_graph_rows', 2 * self.n_reads + 1, np.int64)
+
+    def unitigs(self):
+        """``(unitigs, members)``: :data:`UNITIG_DTYPE` records and the :data:`MEMBER_DTYPE` records they index."""
+        return self._fetch('pw_graph_unitigs', self._count('pw_graph_num_unitigs'), UNITIG_DTYPE), \
+            self._fetch('pw_graph_members', self._count('pw_graph_num_members'), MEMBER_DTYPE)
+
+    def contigs(self, reads, complement=None, stream=None):
+        """The contig letters of the last build, a list of uint8 arrays in unitig order.  ``reads``: the reads themselves, or
+        ``(DeviceArena, offs)`` for letters that are on the device already (``offs[r]``: where read ``r`` starts).
+        ``complement``: the table that turns a letter into its complement; required as soon as a member is an odd vertex."""
+        n_unitigs = self._count('pw_graph_num_unitigs')     # (raises before the first build)
+        held = None
+        if isinstance(reads, tuple):
+            arena, offs = reads
+            offs = np.ascontiguousarray(offs, np.int64).reshape(-1)
+            if not isinstance(arena, DeviceArena) or arena.device != self.device or len(offs) != self.n_reads or \
+                    (len(offs) and (offs.min() < 0 or (offs + self.read_lens).max() > arena.nbytes)):
+                raise ValueError('reads are (DeviceArena on device %d, offs) with every read inside the arena' % self.device)
+        else:
+            if len(reads) != self.n_reads or any(len(_as_u8(r)) != n for r, n in zip(reads, self.read_lens.tolist())):
+                raise ValueError('reads must be the %d reads of the graph, with its lengths' % self.n_reads)
+            host, offs, _ = pack_reads(reads)
+            arena = held = DeviceArena(host, self.device)
+        comp = None if complement is None else np.ascontiguousarray(complement, np.uint8).reshape(-1)
+        if comp is not None and not 1 <= len(comp) <= 256:
+            raise ValueError('complement must hold 1 .. 256 letters')
+        try:
+            if comp is None and (self.unitigs()[1]['vertex'] & 1).any():
+                raise ValueError('a member is a reverse-complemented read: contigs needs the complement table')
+            self._ck(self.lib.pw_graph_contigs(self.handle, arena.ptr, offs.ctypes.data, None if comp is None else comp.ctypes.data,
+                                               0 if comp is None else len(comp), stream), 'pw_graph_contigs')
+            letters = self._fetch('pw_graph_contig_letters', self._count('pw_graph_contig_total'), np.uint8)
+            coff = self._fetch('pw_graph_contig_offsets', n_unitigs + 1, np.int64)
+        finally:
+            if held is not None:
+                held.close()
+        return [letters[coff[u]:coff[u + 1]].copy() for u in range(n_unitigs)]

@@ -411,7 +411,7 @@ def aligned_batches(arena, offs, lens, pidx, dr, alphabet_len, device=0, max_cel
 
 
 def overlap_alignments(reads, pairs, bands, alphabet, p_min=0., device=0, max_cells=2 * 10 ** 10, want_transcripts=True,
-                       strands=None, complement=None, want_summaries=False, pileup=None, pileup_sides='origin', **aligner_kw):
+                       strands=None, complement=None, want_summaries=False, pileup=None, pileup_sides='origin', graph=None, **aligner_kw):
     """Banded overlap alignment (``B_OVERLAP``) of every pair whose band has ``p >= p_min``; the ``diag_range`` is the
     band clamped to the table as ``Aligner`` requires (``pw.py:224-226``).  All reads are uploaded ONCE and the pairs
     refer to them (``BatchAligner.from_arena``); the pairs are solved in batches of at most ``max_cells`` cells
@@ -434,7 +434,11 @@ def overlap_alignments(reads, pairs, bands, alphabet, p_min=0., device=0, max_ce
     ``pileup_sides``: ``'origin'`` (the above) or ``'both'`` (include/pw_polish.h): every batch also adds pair ``(a, b)`` onto
     read ``b``, at ``mutant_col0 = offs[b]``, and reversed for a minus pair -- the batch itself only knows the frame of
     ``rc(reads[b])`` behind the arena -- so that the columns of read ``b`` are always its forward letters.  The inserted
-    letters go to the insertion plane of a pileup that has one (``Pileup(..., ins_slots=J)``)."""
+    letters go to the insertion plane of a pileup that has one (``Pileup(..., ins_slots=J)``).
+
+    ``graph``: None, or an open :class:`biseqt_amd.graph.OverlapGraph` over the lengths of ``reads``: every batch appends one
+    overlap record per pair it aligned (include/pw_graph.h) -- read ``a``, read ``b`` and the strand flag of the pair -- with or
+    without ``want_transcripts``; a pair without an alignment gives a ``NONE`` record.  The caller owns the graph."""
     from .batch import Pileup, pack_reads, summary_dict
     if pileup_sides not in ('origin', 'both'):
         raise ValueError("pileup_sides is 'origin' or 'both', not %r" % (pileup_sides,))
@@ -445,6 +449,12 @@ def overlap_alignments(reads, pairs, bands, alphabet, p_min=0., device=0, max_ce
         if pileup.n_cols != arena.nbytes or pileup.alphabet_len != len(alphabet) or pileup.device != device:
             raise ValueError('pileup must span the arena of pack_reads(reads): n_cols == %d, alphabet_len %d, on device %d'
                              % (arena.nbytes, len(alphabet), device))
+    if graph is not None:
+        from .graph import OverlapGraph
+        if not isinstance(graph, OverlapGraph) or not graph.handle:
+            raise ValueError('graph must be an open biseqt_amd.graph.OverlapGraph')
+        if graph.device != device or graph.n_reads != len(lens) or (graph.read_lens != lens).any():
+            raise ValueError('graph must hold the lengths of `reads`, on device %d' % device)
     sflags = _strand_flags(strands, len(pairs))
     comp = _complement(complement, len(alphabet), alphabet) if sflags is not None and sflags.any() else None
     sel, dr = [], []
@@ -476,6 +486,9 @@ def overlap_alignments(reads, pairs, bands, alphabet, p_min=0., device=0, max_ce
             else:
                 b.pileup_add(pileup)
             b.sync()                                               # (the batch goes when the generator moves on)
+        if graph is not None:
+            graph.add_batch(b, pidx[start:stop, 0], pidx[start:stop, 1], None if sub is None else sub[start:stop])
+            b.sync()
         for k in range(stop - start):
             if res['opt_i'][k] < 0:
                 continue
@@ -537,6 +550,48 @@ def correct_reads(reads, wordlen, alphabet, g_max, sensitivity, p_min=.8, strand
         stats['overlaps'] = ostats
     return polish_reads(reads, pairs, [found[k] for k in keys], alphabet, p_min=p_min, strands=pstrands, complement=complement,
                         min_depth=min_depth, ins_slots=ins_slots, self_weight=self_weight, device=device, stats=stats, **aligner_kw)
+
+
+def assemble_reads(reads, wordlen, alphabet, g_max, sensitivity, p_min=.8, strands='+', complement=None, minimizer_window=None,
+                   max_kmer_occ=None, stats=None, max_hang=1000, int_frac=.8, min_overlap=0, min_identity=0., fuzz=10, device=0,
+                   **aligner_kw):
+    """From reads to contigs in one call (include/pw_graph.h): :func:`overlap_all_pairs` (``strands``, ``complement``,
+    ``minimizer_window``, ``max_kmer_occ`` are its arguments), :func:`overlap_alignments` of the pairs it found whose band has
+    ``p >= p_min`` into an :class:`biseqt_amd.graph.OverlapGraph` (no transcript leaves the device), its ``build`` with
+    ``max_hang``, ``int_frac``, ``min_overlap``, ``min_identity``, ``fuzz``, and its ``contigs``.  Returns ``(contigs, unitigs,
+    members, contained)``: the contig letters as uint8 arrays, the ``graph.UNITIG_DTYPE`` and ``graph.MEMBER_DTYPE`` records and
+    one byte per read.  There is no consensus: correct the reads first (:func:`correct_reads`).  ``stats`` (a dict) receives the
+    overlap stage's report under ``overlaps``, ``records`` (the overlap records with their classes), ``aligned``, ``arcs``,
+    ``kept_arcs``, ``device_bytes`` and the times of the stages in ms, taken on the host around synchronised device work:
+    ``overlap_ms``, ``align_ms``, ``build_ms``, ``contigs_ms``."""
+    import time
+    from .graph import ARC_REMOVED, OverlapGraph
+    assert isinstance(alphabet, Alphabet)
+    ostats = {}
+    t0 = time.perf_counter()
+    found = overlap_all_pairs(reads, wordlen, alphabet, g_max, sensitivity, device=device, stats=ostats, strands=strands,
+                              complement=complement, max_kmer_occ=max_kmer_occ, minimizer_window=minimizer_window)
+    keys = list(found)
+    pairs = [(k[0], k[1]) for k in keys]
+    pstrands = [k[2] for k in keys] if strands != '+' else None
+    comp = _complement(complement, len(alphabet), alphabet) if strands != '+' else None
+    t1 = time.perf_counter()
+    with OverlapGraph([len(r) for r in reads], device=device) as G:
+        alns = overlap_alignments(reads, pairs, [found[k] for k in keys], alphabet, p_min=p_min, device=device, want_transcripts=False,
+                                  strands=pstrands, complement=complement, graph=G, **aligner_kw)
+        t2 = time.perf_counter()
+        G.build(max_hang=max_hang, int_frac=int_frac, min_overlap=min_overlap, min_identity=min_identity, fuzz=fuzz)
+        t3 = time.perf_counter()
+        contigs = G.contigs(reads, complement=comp)
+        t4 = time.perf_counter()
+        unitigs, members = G.unitigs()
+        contained = G.contained()
+        if stats is not None:
+            arcs, _ = G.arcs()
+            stats.update(overlaps=ostats, records=G.overlaps(), aligned=sum(a is not None for a in alns), arcs=len(arcs),
+                         kept_arcs=int((arcs['flags'] & ARC_REMOVED == 0).sum()), device_bytes=G.device_bytes,
+                         overlap_ms=1e3 * (t1 - t0), align_ms=1e3 * (t2 - t1), build_ms=1e3 * (t3 - t2), contigs_ms=1e3 * (t4 - t3))
+    return contigs, unitigs, members, contained
 
 
 def raw_bands_sharded(reads, pairs, wordlen, alphabet_len, g_max, sensitivity, rank, world, device=None, gather_device=None,
