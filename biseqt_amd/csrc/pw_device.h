@@ -231,6 +231,18 @@ void k_fill16(const FillParams<int32_t> a) {
   w.run();
 }
 
+// The grouped form (WaveFill16, GRP = 4: the running best stamped once per four blocks), a kernel and an object of its own
+// (pw_fill16g_tu.hip) beside k_fill16, which stays as it is.  Launched only for the batches the planner's stamp_group names
+// (pw_plan.h) -- ramp_free among the conditions: it holds the steady loop alone.
+template <int BK, bool SEG, int RULE, bool MAT = false>
+__global__ __launch_bounds__(64) PW_FILL_ATTR
+__attribute__((amdgpu_waves_per_eu(Fill16Occupancy<BK, SEG, RULE>::lo, Fill16Occupancy<BK, SEG, RULE>::hi)))
+void k_fill16g(const FillParams<int32_t> a) {
+  const WaveDesc wd = a.waves[blockIdx.x];
+  WaveFill16<DevP, BK, SEG, RULE, MAT, 4> w(a, wd);
+  w.run();
+}
+
 // The same 16-bit body on a workgroup of up to 8 wavefronts per pair (K2a's exchange through LDS): bands of 2049 .. 16 384
 // diagonals, e.g. standard-mode tables of 1 .. 8 kb, whose scores fit the packed kernel.  One WaveDesc per pair,
 // nl = 64 x wavefronts.

@@ -16,6 +16,9 @@ hipError_t launch_fill(const FillParams<double>& a, int variant, int bk, int nbl
 // rule: 0 .. 5 (pw_wave.h, WaveFill16); mat != 0: scores from FillParams::mat_rows (rules 0 .. 3 only)
 hipError_t launch_fill16(const FillParams<int32_t>& a, int bk, int seg, int rule, int mat, int nwaves, hipStream_t st);
 hipError_t launch_fill16_mw(const FillParams<int32_t>& a, int bk, int rule, int mat, int nw, int npairs, hipStream_t st);   // nw wavefronts per pair
+// the grouped kernel k_fill16g<8, false, 3, true> (pw_plan.h, stamp_group == 4): rule 3, matrix form, 8 diagonals per lane, one
+// pair per wavefront, FillParams::ramp_free set
+hipError_t launch_fill16g(const FillParams<int32_t>& a, int nwaves, hipStream_t st);
 // wide bands: one workgroup of nw wavefronts (2048 diagonals each, nw <= kMaxWavesPerPair) per pair
 hipError_t launch_fill_mw(const FillParams<int32_t>& a, int variant, int bk, int nw, int nblocks, hipStream_t st);
 hipError_t launch_fill_mw(const FillParams<double>& a, int variant, int bk, int nw, int nblocks, hipStream_t st);

@@ -234,6 +234,7 @@ struct PlanKnobs {
   int simple_as_matrix = -1;        // PWLIB_SIMPLE_AS_MATRIX=0 / 1: match / mismatch in the packed matrix form never / always
   bool no_scaled16 = false;         // PWLIB_NO_SCALED16=1: no scores-times-4 form (rule 3)
   bool ramp_blocks = false;         // PWLIB_RAMP_BLOCKS=1: blocks in which diagonals start or end keep their own bodies (ramp_free)
+  bool stamp_group1 = false;        // PWLIB_STAMP_GROUP=1: the running best stamped per block, never per four (stamp_group)
   bool packed_bk_forced = false;    // PWLIB_PACKED_BK="<bk>" or "<bk>s": the packed lane width (s: lane packing)
   int packed_bk = 0;
   bool packed_bk_seg = false;
@@ -357,6 +358,15 @@ static inline PackedAdmission admit_packed(int rule, const ScoreSummary& s, int 
 // cell as before.  The tie nibbles of such cells go where they went before: mask slots no walk visits.
 static inline bool ramp_free(int rule, bool matrix, double go, double ge, double smin, const PlanKnobs& kn) {
   return (rule == 0 || rule == 3) && matrix && !kn.ramp_blocks && ge < 0 && ge + go < 0 && smin < 0;
+}
+
+// stamp_group: the blocks per stamp of the running best (pw_wave.h, WaveFill16, GRP).  4 -- the grouped kernel k_fill16g --
+// exactly for packed rule 3, matrix form, 8 diagonals per lane, one pair per wavefront (no lane packing), one wavefront per
+// pair, with ramp_free (the kernel holds the steady loop alone); 1 otherwise, and under PWLIB_STAMP_GROUP=1.  No admission
+// bound of its own: the grouped key 8 (4 score) + (31 - cell) needs 4 score <= 8188, and rule 3 is admitted only with
+// min(X, Y) max(subst) <= 2047 (admit_packed, x4), which is that bound.
+static inline int stamp_group(int rule, bool matrix, int bk, bool seg, int nw, bool ramp_free_on, const PlanKnobs& kn) {
+  return (rule == 3 && matrix && bk == 8 && !seg && nw == 1 && ramp_free_on && !kn.stamp_group1) ? 4 : 1;
 }
 
 struct PackedLayout { int bk = 0, nl = 0, seg = 0, nw = 1; };   // bk = 0: none; seg: several pairs per wavefront

@@ -773,6 +773,20 @@ extern "C" __attribute__((used, visibility("default"))) inline void pw_ramp_bloc
   for (int i = 0; i < 4; i++) { out[i] = pk::ramp_block_counts()[i]; if (reset) pk::ramp_block_counts()[i] = 0; }
 }
 extern "C" __attribute__((used, visibility("default"))) inline void pw_emu_ramp_free(int v) { pk::ramp_free_emu() = v; }
+// The stamp group of the running best (WaveFill16, GRP) is a template constant on the device; the emulator's harness
+// instantiates the five-argument form only, so here it is a run-time value: 4 runs the grouped form wherever the kernel's
+// form allows it (WaveFill16::GOK, with ramp_free on), 1 or -1 the stamp per block.
+namespace pk {
+inline int& stamp_group_emu() { static int v = -1; return v; }
+inline unsigned& group_stamps() { static unsigned n = 0; return n; }
+}  // namespace pk
+extern "C" __attribute__((used, visibility("default"))) inline void pw_emu_stamp_group(int v) { pk::stamp_group_emu() = v; }
+// (the stamps written per group, counted by lane 0: one per four blocks and one for a last, shorter group)
+extern "C" __attribute__((used, visibility("default"))) inline unsigned pw_group_stamps(int reset) {
+  const unsigned n = pk::group_stamps();
+  if (reset) pk::group_stamps() = 0;
+  return n;
+}
 // The packed kernels' edge-lane feeders, one pair per wavefront (WaveFill16::feed_issue): dwords the emulator's reader was
 // asked for outside [0, wlast] of the frame it was reading (counted by every lane; must stay 0), and the blocks whose
 // window took each path, counted by lane 0: [origin ahead, origin late, mutant ahead, mutant late].
@@ -813,7 +827,9 @@ extern "C" __attribute__((used, visibility("default"))) inline void pw_feed_path
 // each -- and the mutant window carries byte SELECTORS (0x0c00 | letter, + 4 in ONE half of a register, see FIXSEL): one
 // v_perm_b32 looks up both cells of a pair.  Letters outside a sequence are the all-zero row / a selector that reads as
 // 0x00: the matrix minimum, which the planner requires to be <= 0 ("matches nothing").
-template <class P, int BK, bool SEG, int RULE = 0, bool MAT = false>
+// GRP: the blocks per STAMP GROUP of the running best (1 or 4; stamp_best).  4 is a kernel of its own (k_fill16g) for the
+// batches the planner's stamp_group (pw_plan.h) names; every other instantiation is the five-argument form.
+template <class P, int BK, bool SEG, int RULE = 0, bool MAT = false, int GRP = 1>
 struct WaveFill16 {
   // RULE 3 = rule 0 with every score held times 4 (admitted when the scores stay below 2048): a kept-or-not difference
   // of two running values is then 0 or at least 4, so min(x, 2) and min(x, 4) deliver the D and I tie bits already
@@ -931,6 +947,20 @@ struct WaveFill16 {
   //     replacement itself, about 40 scalar instructions, runs only in the blocks that need it.
   // The three other loops stay for batches whose scores do not allow it.
   static constexpr bool RAMPF = SPLIT && TRK;
+  // ... and, scores times 4, one pair per wavefront, 8 diagonals per lane, with ramp_free on, may stamp the running best once
+  // per GROUP of four blocks (stamp_best).  On the device the group is the template constant and the grouped kernel is
+  // launched for ramp_free batches only: it holds the steady loop alone.  The CPU emulator decides at run time
+  // (pk::stamp_group_emu).
+  static constexpr bool GOK = SC4 && SPLIT && TRK && !SEG && BK == 8;
+  static_assert(GRP == 1 || (GRP == 4 && GOK), "a stamp group of 4: rule 3, matrix form, one pair per wavefront, 8 per lane");
+#if defined(__HIPCC__)
+  PW_FN static constexpr bool grp4() { return GRP == 4; }
+#else
+  bool grp4_rt = false;
+  PW_FN bool grp4() const { return grp4_rt; }
+#endif
+  uint32_t kgE[RH], kgO[RH];    // grouped: the keys as they stood before the group
+  uint32_t POS[8];              // grouped: 31 - cell within the group, in both halves, of the block's 8 iterations (wave-uniform)
   // One pair per wavefront, matrix form, blocks unrolled in full: the rows of a block's 8 origin feed letters are selected
   // when the block starts (feed_commit), on bits read in place (row_bits) -- wave-uniform, scalar registers.
   static constexpr bool FROWS = MAT && !SEG && UNR == 4 && BK <= 8;
@@ -1047,6 +1077,28 @@ struct WaveFill16 {
     const uint32_t ch = pk::minu((kb ^ kb0) & ~SEVEN, ONE);      // 1 where the best strictly improved in this block
     bts = pk::maxu(bts, pk::mad(ch, blk8, kb & SEVEN));
   }
+  // Grouped (grp4): the key is 8 H + (31 - cell within the GROUP of four blocks), H = 4 score <= 8188 under the times-4
+  // admission (min(X, Y) max(subst) <= 2047), so 8 * 8188 + 31 = 65535 fills the 16 bits exactly; the score part is bits 5
+  // and up, `kg` the key before the group, and the stamp 32 (group + 1) + 31 - cell -- at most 32 * 1024 + 31 for 4096
+  // blocks -- is written once per group, behind a scalar branch (block16), and once more behind the loop for a last group of
+  // fewer than four blocks (run()).  An equal score later never wins, for the reasons above restated for groups: within a
+  // group a later cell has a smaller position code, so the unsigned maximum keeps the first; in a later group an equal score
+  // can only raise the low bits; the low bits are read only in a group whose score part rose (ch = 1); and the key that made
+  // it rise rewrote them with its own code, after which only smaller codes follow at that score in the group.  Stamps grow
+  // from group to group; the candidate where nothing rose is 0 .. 31, below every real stamp.
+  PW_FN void stamp_group(uint32_t g1) {
+#if !defined(__HIPCC__)
+    if (P::lane() == 0) pk::group_stamps()++;                 // (the CPU emulator: the grouped form ran)
+#endif
+    const uint32_t sv = pk::both((int32_t)(32u * g1));
+#pragma unroll
+    for (int p = 0; p < RH; p++) {
+      const uint32_t chE = pk::minu((kbE[p] ^ kgE[p]) & 0xffe0ffe0u, ONE), chO = pk::minu((kbO[p] ^ kgO[p]) & 0xffe0ffe0u, ONE);
+      btE[p] = pk::maxu(btE[p], pk::mad(chE, sv, kbE[p] & 0x001f001fu));
+      btO[p] = pk::maxu(btO[p], pk::mad(chO, sv, kbO[p] & 0x001f001fu));
+      kgE[p] = kbE[p]; kgO[p] = kbO[p];
+    }
+  }
 
   // HALF selects the accumulator set: iterations 0-3 of a block (cells 0-3 of every slot) or 4-7.
   // Rule 0: the slot's running best as a key (see kbE): cells of a diagonal that has not started hold the sentinel and
@@ -1054,7 +1106,7 @@ struct WaveFill16 {
   template <int EK>
   PW_FN void track_key(uint32_t& kb, uint32_t H, uint32_t tl, uint32_t tv, int k) {
     const uint32_t hk = (!ANYB || (EK & 1)) ? pk::max(H, 0u) : H;   // (rule 5: real scores go negative and count as 0)
-    uint32_t key = pk::mad(hk, SC4 ? C2 : C8, pk::both(7 - k));
+    uint32_t key = grp4() ? pk::mad(hk, C8, POS[k]) : pk::mad(hk, SC4 ? C2 : C8, pk::both(7 - k));
     if (EK & 2) key &= ~pk::sign(pk::sub(tl, tv), SH15);
     kb = pk::maxu(kb, key);
   }
@@ -1156,7 +1208,7 @@ struct WaveFill16 {
 #pragma unroll
     for (int p = 0; p < RH; p++) { accE[p] = 0; accO[p] = 0; acc2E[p] = 0; acc2O[p] = 0; }
     uint32_t kb0E[RH], kb0O[RH];
-    if (TRK) {
+    if (TRK && !grp4()) {
 #pragma unroll
       for (int p = 0; p < RH; p++) { kb0E[p] = kbE[p]; kb0O[p] = kbO[p]; }
     }
@@ -1166,7 +1218,7 @@ struct WaveFill16 {
     for (int k = 0; k < 4; k++) iteration16<EK, 0>(8 * b + k, k);
 #pragma clang loop unroll_count(UNR)
     for (int k = 4; k < 8; k++) iteration16<EK, 1>(8 * b + k, k);
-    if (TRK) {
+    if (TRK && !grp4()) {
       const uint32_t blk8 = pk::both(8 * b + 8);
 #pragma unroll
       for (int p = 0; p < RH; p++) {
@@ -1214,6 +1266,18 @@ struct WaveFill16 {
           pk::store_global(mbase[g], mrowb, v);
         }
         mrowb += 4u * mrow_step;
+      }
+    }
+    // Grouped: the position codes move on by a block (scalar registers); the last block of a group stamps, takes the keys as
+    // the next group's "before" and starts the codes again -- behind ONE scalar branch, after the mask stores, so that the
+    // unrolled body stays one basic block.
+    if (TRK && grp4()) {
+#pragma unroll
+      for (int k = 0; k < 8; k++) POS[k] -= 0x00080008u;
+      if ((b & 3) == 3) {
+        stamp_group((uint32_t)(b >> 2) + 1u);
+#pragma unroll
+        for (int k = 0; k < 8; k++) POS[k] += 0x00200020u;
       }
     }
   }
@@ -1433,8 +1497,15 @@ struct WaveFill16 {
     yfeed_m = f;
     fo_w = (uint32_t)xfeed_o & ~3u; fm_w = (uint32_t)yfeed_m & ~3u;
     fo_lim = 4u * (uint32_t)(owlast > 1 ? owlast - 1 : 0); fm_lim = 4u * (uint32_t)(mwlast > 1 ? mwlast - 1 : 0);
-    rf = RAMPF && ramp_free_on();
-    ONE = pk::opaque(0x00010001u); SH15 = pk::opaque(0x000f000fu);
+    rf = RAMPF && (GRP == 4 || ramp_free_on());      // (the grouped kernel is launched for ramp_free batches only)
+#if !defined(__HIPCC__)
+    grp4_rt = GRP == 4 || (GOK && rf && P::nwaves() == 1 && pk::stamp_group_emu() == 4);
+#endif
+    if (grp4()) {
+#pragma unroll
+      for (int k = 0; k < 8; k++) POS[k] = pk::opaque_su(pk::both(31 - k));
+    }
+    ONE =pk::opaque(0x00010001u); SH15 = pk::opaque(0x000f000fu);
     C2 = pk::opaque(0x00020002u); C4 = pk::opaque(0x00040004u); C16 = pk::opaque(0x00100010u);
     C8 = pk::opaque(0x00080008u); SEVEN = pk::opaque(0x00070007u);
     NEGV = pk::both(NEG16); LIMV = pk::both(-32767);
@@ -1471,7 +1542,7 @@ struct WaveFill16 {
       up_prev = left_next = NEGV; phase_l = 0; phase_r = 0;
       // tracking rules: best 0 and no stamp yet (finish(): such a diagonal reports its first cell under rule 0)
       bestE[p] = bestO[p] = NEGV;
-      kbE[p] = kbO[p] = 0u; btE[p] = btO[p] = 0u;
+      kbE[p] = kbO[p] = 0u; btE[p] = btO[p] = 0u; kgE[p] = kgO[p] = 0u;
       OW[p] = pk::pack((int32_t)letter_o(xbase + p - 1), (int32_t)letter_o(xbase + p + RH - 1));
       if (MAT) {
         // (FIXSEL: letter y was, or would have been, fed on iteration y - f)
@@ -1506,10 +1577,14 @@ struct WaveFill16 {
       const int r0 = (RAMPF && rf) ? 0 : b0, r1 = (RAMPF && rf) ? nb : b1;
       flimx = (uint32_t)(X > 7 ? X - 7 : 0); flimy = (uint32_t)(Y > 7 ? Y - 7 : 0);
       int b = 0;
-      if (sb1 > wd.steady_b0) for (; b < r0; b++) blocks_step<1>(b);   // some have not started; none has ended before the steady range
-      else for (; b < r0; b++) blocks_step<3>(b);                      // (no steady range: the planner's bounds cannot tell)
+      if (GRP != 4) {                                                  // (the grouped kernel: the steady loop alone)
+        if (sb1 > wd.steady_b0) for (; b < r0; b++) blocks_step<1>(b);   // some have not started; none has ended before the steady range
+        else for (; b < r0; b++) blocks_step<3>(b);                      // (no steady range: the planner's bounds cannot tell)
+      }
       for (; b < r1; b++) blocks_step<0>(b);
-      for (; b < nb; b++) blocks_step<2>(b);                           // every diagonal has started, some may have ended
+      if (GRP != 4) for (; b < nb; b++) blocks_step<2>(b);             // every diagonal has started, some may have ended
+      // grouped: a last group of fewer than four blocks has not been stamped yet
+      if (grp4() && (nb & 3) != 0 && nb > 0) stamp_group((uint32_t)(nb >> 2) + 1u);
     } else {
       for (int b = 0, nb = nblocks_run(); b < nb; b++) {
         const bool steady = b >= wd.steady_b0 && b < sb1;
@@ -1569,9 +1644,17 @@ struct WaveFill16 {
           // best stays 0 reports its first cell (score 0 on the table edge).  (Rule 5: a best of 0 never wins -- the end cell
           // must beat 0 -- so where it "was reached" does not matter.)
           const uint32_t key = h ? (bq >> 16) : (bq & 0xffffu), stamp = h ? (tq >> 16) : (tq & 0xffffu);
-          s = (int32_t)(key >> 3);
-          if (stamp < 8u) bt = ANYB ? (int)((uint32_t)tfirst & 0xffffu) : 0;
-          else bt = 16 * ((int)(stamp >> 3) - 1) + 2 * (7 - (int)(stamp & 7u)) + odd;
+          // Grouped: key = 32 score + (31 - cell within the group), stamp = 32 (group + 1) + 31 - cell, below 32 while the best
+          // stayed 0; a group is 64 steps.
+          if (!grp4()) {
+            s = (int32_t)(key >> 3);
+            if (stamp < 8u) bt = ANYB ? (int)((uint32_t)tfirst & 0xffffu) : 0;
+            else bt = 16 * ((int)(stamp >> 3) - 1) + 2 * (7 - (int)(stamp & 7u)) + odd;
+          } else {
+            s = (int32_t)(key >> 5);
+            if (stamp < 32u) bt = ANYB ? (int)((uint32_t)tfirst & 0xffffu) : 0;
+            else bt = 64 * ((int)(stamp >> 5) - 1) + 2 * (31 - (int)(stamp & 31u)) + odd;
+          }
         } else {
           s = (h ? pk::hi_s(bq) : pk::lo_s(bq)) / SCL;                 // (exact: every running value is a multiple of SCL)
           bt = 0;
