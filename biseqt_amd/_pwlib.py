@@ -1,5 +1,5 @@
 """ctypes binding of biseqt_amd/pwlib/pwlib.so (the HIP library; C ABI in include/pwlib.h,
-include/pw_batch.h, include/pw_txsum.h, include/pw_cigar.h, include/pw_pileup.h, include/pw_polish.h, include/pw_graph.h and the seed headers include/pw_seeds.h, pw_mseeds.h, pw_qseeds.h, pw_overlap.h).
+include/pw_batch.h, include/pw_txsum.h, include/pw_cigar.h, include/pw_pileup.h, include/pw_polish.h, include/pw_graph.h, include/pw_consensus.h and the seed headers include/pw_seeds.h, pw_mseeds.h, pw_qseeds.h, pw_overlap.h).
 
 The reference binds its C library with cffi in ABI mode (``biseqt/pw.py:45-69``); cffi is not
 available in this image, so the same structs are declared with ctypes -- field for field the layout of
@@ -140,6 +140,15 @@ class pw_unitig_member(C.Structure):
     _fields_ = [('vertex', C.c_int32), ('advance', C.c_int32), ('offset', C.c_int64)]
 
 
+# ---- the consensus layout (include/pw_consensus.h) ----
+class pw_cons_place(C.Structure):
+    _fields_ = [('unitig', C.c_int32), ('rev', C.c_int32), ('pos', C.c_int64), ('root', C.c_int32), ('depth', C.c_int32)]
+
+
+class pw_cons_task(C.Structure):
+    _fields_ = [('col0', C.c_int64), ('mut_off', C.c_int64)] + [(f, C.c_int32) for f in ('read', 'win_len', 'dmin', 'dmax', 'rev', 'pad_')]
+
+
 PW_TXSUM_DONE = 1
 PW_ST_TRACED, PW_ST_EMPTY, PW_ST_PANICK, PW_ST_BADPATH = 1, 2, 4, 8
 PW_FLAG_DUMP_SCORES, PW_FLAG_FORCE_F64, PW_FLAG_FORCE_GENERIC, PW_FLAG_PROFILE = 1, 2, 4, 8
@@ -152,7 +161,7 @@ PW_FLAG_NO_STRIP = 256
 SIZEOF = dict(intpair=8, alnscores=24, alnframe=32, std_alnparams=4, banded_alnparams=12,
               alnprob=32, alnchoice=32, dpcell=16, dptable=32, alignment=24,
               pw_scoring=40, pw_pair=32, pw_result=32, pw_tx_summary=48, pw_pileup_site=8, pw_polish_stats=16,
-              pw_graph_overlap=40, pw_graph_params=32, pw_graph_arc=24, pw_unitig=32, pw_unitig_member=16)
+              pw_graph_overlap=40, pw_graph_params=32, pw_graph_arc=24, pw_unitig=32, pw_unitig_member=16, pw_cons_place=24, pw_cons_task=40)
 
 # every symbol include/pwlib.h and include/pw_batch.h declare
 EXPORTS = ['dptable_init', 'dptable_solve', 'dptable_traceback', 'dptable_free',
@@ -193,6 +202,10 @@ GRAPH_EXPORTS = ['pw_graph_create', 'pw_graph_free', 'pw_graph_num_overlaps', 'p
                  'pw_graph_rows_device', 'pw_graph_unitigs_device', 'pw_graph_members_device', 'pw_graph_contigs',
                  'pw_graph_contig_total', 'pw_graph_contig_offsets', 'pw_graph_contig_letters', 'pw_graph_contig_letters_device',
                  'pw_graph_contig_offsets_device']
+# every symbol include/pw_consensus.h declares
+CONSENSUS_EXPORTS = ['pw_graph_place', 'pw_graph_placements', 'pw_graph_placements_device', 'pw_graph_consensus_layout',
+                     'pw_graph_cons_num_tasks', 'pw_graph_cons_num_cols', 'pw_graph_cons_arena_bytes', 'pw_graph_cons_cstart',
+                     'pw_graph_cons_tasks', 'pw_graph_cons_cstart_device', 'pw_graph_cons_tasks_device', 'pw_graph_cons_arena_device']
 PW_OVL_NONE, PW_OVL_WEAK, PW_OVL_INTERNAL, PW_OVL_A_CONTAINED, PW_OVL_B_CONTAINED, PW_OVL_A_TO_B, PW_OVL_B_TO_A = range(7)
 PW_ARC_REDUCED, PW_ARC_REMOVED, PW_ARC_CHAIN = 1, 2, 4
 # every symbol include/pw_seeds.h declares
@@ -439,6 +452,17 @@ def load():
         getattr(lib, f).argtypes = [C.c_void_p]
         getattr(lib, f).restype = C.c_void_p
     lib.pw_graph_contigs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    # include/pw_consensus.h
+    lib.pw_graph_place.argtypes = [C.c_void_p, C.c_void_p]
+    lib.pw_graph_consensus_layout.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int32, C.c_double, C.c_void_p]
+    for f in ('pw_graph_cons_num_tasks', 'pw_graph_cons_num_cols', 'pw_graph_cons_arena_bytes'):
+        getattr(lib, f).argtypes = [C.c_void_p]
+        getattr(lib, f).restype = C.c_int64
+    for f in ('pw_graph_placements', 'pw_graph_cons_cstart', 'pw_graph_cons_tasks'):
+        getattr(lib, f).argtypes = [C.c_void_p, C.c_void_p]
+    for f in ('pw_graph_placements_device', 'pw_graph_cons_cstart_device', 'pw_graph_cons_tasks_device', 'pw_graph_cons_arena_device'):
+        getattr(lib, f).argtypes = [C.c_void_p]
+        getattr(lib, f).restype = C.c_void_p
     # include/pw_seeds.h
     lib.pw_seeds_create.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int,
                                     P(C.c_uint64), C.c_int, C.c_int]

@@ -150,6 +150,20 @@ class DeviceArena(object):
             raise RuntimeError('pw_overlap_arena_upload failed: ' + (self.lib.pw_overlap_last_error() or b'').decode())
         return self
 
+    @classmethod
+    def adopt(cls, ptr, nbytes, device=0, owner=None):
+        """A non-owning view of ``nbytes`` bytes of device memory at ``ptr`` that somebody else owns (``owner``, kept alive as
+        long as the view): frames of it serve batches, pileups and :meth:`read` as those of an uploaded arena do, and
+        :meth:`close` never frees the pointer.  The memory must carry the 16 bytes of slack behind ``nbytes`` that
+        ``pw_arena_upload`` gives."""
+        if not ptr or int(nbytes) < 0:
+            raise ValueError('adopt needs a device pointer and a size')
+        self = cls.__new__(cls)
+        self.lib = W.load()
+        self.device, self.nbytes, self.ptr = device, int(nbytes), int(ptr)
+        self._adopted, self._owner = True, owner
+        return self
+
     def read(self, offset=0, nbytes=None):
         """A piece of the device arena back on the host (uint8 array)."""
         nbytes = self.nbytes - offset if nbytes is None else nbytes
@@ -160,6 +174,9 @@ class DeviceArena(object):
         return out[:nbytes]
 
     def close(self):
+        if getattr(self, '_adopted', False):                # (an adopted pointer belongs to its owner)
+            self.ptr = self._owner = None
+            return
         if self.ptr:
             self.lib.pw_arena_free(self.device, self.ptr)
             self.ptr = None

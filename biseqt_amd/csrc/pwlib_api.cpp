@@ -27,12 +27,14 @@
 #include "../../include/pw_pileup.h"
 #include "../../include/pw_polish.h"
 #include "../../include/pw_graph.h"
+#include "../../include/pw_consensus.h"
 #include "pw_launch.h"
 #include "pw_plan.h"
 #include "pw_model.h"
 #include "pw_hip_host.h"
 #include "pw_complement.h"
 #include "pw_graph_launch.h"
+#include "pw_consensus_launch.h"
 #define PW_FN inline
 #include "pw_strip.h"
 #include <atomic>
@@ -1428,6 +1430,7 @@ void* pw_pileup_polished_offsets_device(pw_pileup* p) {
 // ---- the overlap graph (include/pw_graph.h; kernels and stage sequences in pw_graph.hip) ----
 struct pw_graph {
   pw::GraphState s;
+  pw::ConsState c;                       // the consensus stage (include/pw_consensus.h; pw_consensus.hip)
   std::vector<int32_t> lens;             // [n_reads]
   std::unordered_set<uint64_t> keys;     // (a * n_reads + b) * 2 + strand of every record
   std::string duplicate;                 // the first duplicate key, in words; pw_graph_build reports it
@@ -1472,7 +1475,7 @@ void pw_graph_free(pw_graph* g) {
   delete g;
 }
 int64_t pw_graph_num_overlaps(const pw_graph* g) { return g ? g->s.n_recs : 0; }
-int64_t pw_graph_device_bytes(const pw_graph* g) { return g ? pw::graph_device_bytes(g->s) : 0; }
+int64_t pw_graph_device_bytes(const pw_graph* g) { return g ? pw::graph_device_bytes(g->s) + pw::cons_device_bytes(g->c) : 0; }
 
 int pw_graph_add_overlaps(pw_graph* g, const pw_graph_overlap* recs, int64_t n) {
   if (!g) return fail("pw_graph_add_overlaps: null graph");
@@ -1533,6 +1536,7 @@ int pw_graph_build(pw_graph* g, const pw_graph_params* p, void* stream) {
   if (!std::isfinite(p->int_frac) || !std::isfinite(p->min_identity)) return fail("pw_graph_build: int_frac and min_identity must be finite");
   if (p->max_hang < 0 || p->min_overlap < 0 || p->fuzz < 0) return fail("pw_graph_build: max_hang, min_overlap and fuzz must not be negative");
   HIP_TRY(hipSetDevice(g->s.device));
+  g->c.placed = false; g->c.has_layout = false;              // (a build drops every consensus result)
   HIP_TRY(pw::graph_build(g->s, *p, (hipStream_t)stream));
   return 0;
 }
@@ -1596,6 +1600,7 @@ int pw_graph_contigs(pw_graph* g, const uint8_t* letters_device, const int64_t* 
   if (upload(fail, g->s.d_roff, g->h_roff.data(), (size_t)R, st) != 0) return -1;
   HIP_TRY(g->s.d_comp.ensure(256));
   HIP_TRY(hipMemcpy(g->s.d_comp.p, table, 256, hipMemcpyHostToDevice));
+  g->c.has_layout = false;                                   // (the consensus arena holds the letters of an earlier call)
   HIP_TRY(pw::graph_contigs(g->s, letters_device, st));
   return 0;
 }
@@ -1624,6 +1629,94 @@ void* pw_graph_contig_letters_device(pw_graph* g) {
 void* pw_graph_contig_offsets_device(pw_graph* g) {
   if (!g || !g->s.has_contigs) { fail("pw_graph_contig_offsets_device before pw_graph_contigs"); return nullptr; }
   return g->s.d_coff.p;
+}
+
+// ---- the consensus stage (include/pw_consensus.h; kernels and stage sequences in pw_consensus.hip) ----
+int pw_graph_place(pw_graph* g, void* stream) {
+  if (!g) return fail("pw_graph_place: null graph");
+  if (!g->s.built) return fail("pw_graph_place before pw_graph_build");
+  HIP_TRY(hipSetDevice(g->s.device));
+  HIP_TRY(pw::cons_place(g->s, g->c, (hipStream_t)stream));
+  return 0;
+}
+int pw_graph_placements(pw_graph* g, pw_cons_place* out) {
+  if (!g || !g->s.built || !g->c.placed) return fail("pw_graph_placements before pw_graph_place");
+  if (g->s.n_reads == 0) return 0;
+  if (!out) return fail("pw_graph_placements: null output");
+  HIP_TRY(hipSetDevice(g->s.device));
+  HIP_TRY(hipMemcpy(out, g->c.d_place.p, g->c.d_place.bytes((size_t)g->s.n_reads), hipMemcpyDeviceToHost));
+  return 0;
+}
+void* pw_graph_placements_device(pw_graph* g) {
+  if (!g || !g->s.built || !g->c.placed) { fail("pw_graph_placements_device before pw_graph_place"); return nullptr; }
+  return g->c.d_place.p;
+}
+
+int pw_graph_consensus_layout(pw_graph* g, const uint8_t* letters_device, const int64_t* read_offs, const uint8_t* complement,
+                              int complement_len, int32_t slack, double drift, void* stream) {
+  if (!g) return fail("pw_graph_consensus_layout: null graph");
+  if (!g->s.built) return fail("pw_graph_consensus_layout before pw_graph_build");
+  if (slack < 0) return fail("pw_graph_consensus_layout: slack must not be negative");
+  if (!std::isfinite(drift) || drift < 0 || drift > 1048576.) return fail("pw_graph_consensus_layout: drift must be finite and lie in 0 .. 2^20");
+  if (complement && (complement_len < 1 || complement_len > 256)) return fail("pw_graph_consensus_layout: complement_len must be 1..256");
+  const int64_t R = g->s.n_reads;
+  if (R > 0 && !read_offs) return fail("pw_graph_consensus_layout: null read offsets");
+  for (int64_t r = 0; r < R; r++)
+    if (read_offs[r] < 0) return fail("pw_graph_consensus_layout: read " + std::to_string(r) + " has a negative offset");
+  const hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(hipSetDevice(g->s.device));
+  if (!g->c.placed) HIP_TRY(pw::cons_place(g->s, g->c, st));
+  if (!g->s.has_contigs && pw_graph_contigs(g, letters_device, read_offs, complement, complement_len, stream) != 0) return -1;
+  g->c.has_layout = false;
+  bool any = false;                                          // a read of at least one letter: the frames are read from the letters
+  for (int64_t r = 0; r < R && !any; r++) any = g->lens[r] > 0;
+  if (any && !letters_device) return fail("pw_graph_consensus_layout: null letters");
+  uint8_t table[256];
+  for (int c = 0; c < 256; c++) table[c] = complement && c < complement_len ? complement[c] : (uint8_t)c;
+  g->h_roff.assign(read_offs, read_offs + R);                // (the caller's array is consumed here)
+  if (upload(fail, g->c.d_roff, g->h_roff.data(), (size_t)R, st) != 0) return -1;
+  HIP_TRY(g->c.d_comp.ensure(256));
+  HIP_TRY(hipMemcpy(g->c.d_comp.p, table, 256, hipMemcpyHostToDevice));
+  bool too_long = false;
+  HIP_TRY(pw::cons_layout(g->s, g->c, letters_device, slack, drift, &too_long, st));
+  if (too_long) return fail("pw_graph_consensus_layout: a contig has 2^31 letters or more");
+  return 0;
+}
+int64_t pw_graph_cons_num_tasks(pw_graph* g) {
+  return g && g->s.built && g->c.has_layout ? g->c.n_tasks : fail("pw_graph_cons_num_tasks before pw_graph_consensus_layout");
+}
+int64_t pw_graph_cons_num_cols(pw_graph* g) {
+  return g && g->s.built && g->c.has_layout ? g->c.n_cols : fail("pw_graph_cons_num_cols before pw_graph_consensus_layout");
+}
+int64_t pw_graph_cons_arena_bytes(pw_graph* g) {
+  return g && g->s.built && g->c.has_layout ? g->c.arena_bytes : fail("pw_graph_cons_arena_bytes before pw_graph_consensus_layout");
+}
+int pw_graph_cons_cstart(pw_graph* g, int64_t* out) {
+  if (!g || !g->s.built || !g->c.has_layout) return fail("pw_graph_cons_cstart before pw_graph_consensus_layout");
+  if (!out) return fail("pw_graph_cons_cstart: null output");
+  HIP_TRY(hipSetDevice(g->s.device));
+  HIP_TRY(hipMemcpy(out, g->c.d_cstart.p, g->c.d_cstart.bytes((size_t)g->s.n_unitigs + 1), hipMemcpyDeviceToHost));
+  return 0;
+}
+int pw_graph_cons_tasks(pw_graph* g, pw_cons_task* out) {
+  if (!g || !g->s.built || !g->c.has_layout) return fail("pw_graph_cons_tasks before pw_graph_consensus_layout");
+  if (g->c.n_tasks == 0) return 0;
+  if (!out) return fail("pw_graph_cons_tasks: null output");
+  HIP_TRY(hipSetDevice(g->s.device));
+  HIP_TRY(hipMemcpy(out, g->c.d_tasks.p, g->c.d_tasks.bytes((size_t)g->c.n_tasks), hipMemcpyDeviceToHost));
+  return 0;
+}
+void* pw_graph_cons_cstart_device(pw_graph* g) {
+  if (!g || !g->s.built || !g->c.has_layout) { fail("pw_graph_cons_cstart_device before pw_graph_consensus_layout"); return nullptr; }
+  return g->c.d_cstart.p;
+}
+void* pw_graph_cons_tasks_device(pw_graph* g) {
+  if (!g || !g->s.built || !g->c.has_layout) { fail("pw_graph_cons_tasks_device before pw_graph_consensus_layout"); return nullptr; }
+  return g->c.d_tasks.p;
+}
+void* pw_graph_cons_arena_device(pw_graph* g) {
+  if (!g || !g->s.built || !g->c.has_layout) { fail("pw_graph_cons_arena_device before pw_graph_consensus_layout"); return nullptr; }
+  return g->c.d_arena.p;
 }
 
 int pw_batch_scores(pw_batch* b, int32_t k, double* out, int64_t n) {

@@ -1,6 +1,7 @@
 """The overlap graph on the device (include/pw_graph.h holds the contract): overlap records, their containment / dovetail
-classes, arcs, transitive reduction, unitigs and contig letters.  Every computing call goes to the kernels of
-``pw_graph.hip``; there is no host fallback."""
+classes, arcs, transitive reduction, unitigs and contig letters -- and the consensus stage on top of it
+(include/pw_consensus.h): where every read lies on its contig, the read-against-contig alignment tasks and the polished
+contigs.  Every computing call goes to the kernels of ``pw_graph.hip`` and ``pw_consensus.hip``; there is no host fallback."""
 import ctypes as C
 
 import numpy as np
@@ -14,6 +15,9 @@ UNITIG_DTYPE = np.dtype([('first_member', '<i8'), ('length', '<i8'), ('n_members
                          ('pad_', '<i4')])
 MEMBER_DTYPE = np.dtype([('vertex', '<i4'), ('advance', '<i4'), ('offset', '<i8')])
 assert (OVERLAP_DTYPE.itemsize, ARC_DTYPE.itemsize, UNITIG_DTYPE.itemsize, MEMBER_DTYPE.itemsize) == (40, 24, 32, 16)
+PLACE_DTYPE = np.dtype([('unitig', '<i4'), ('rev', '<i4'), ('pos', '<i8'), ('root', '<i4'), ('depth', '<i4')])
+TASK_DTYPE = np.dtype([('col0', '<i8'), ('mut_off', '<i8')] + [(f, '<i4') for f in ('read', 'win_len', 'dmin', 'dmax', 'rev', 'pad_')])
+assert (PLACE_DTYPE.itemsize, TASK_DTYPE.itemsize) == (24, 40)
 NONE, WEAK, INTERNAL, A_CONTAINED, B_CONTAINED, A_TO_B, B_TO_A = range(7)
 CLASS_NAMES = ('NONE', 'WEAK', 'INTERNAL', 'A_CONTAINED', 'B_CONTAINED', 'A_TO_B', 'B_TO_A')
 ARC_REDUCED, ARC_REMOVED, ARC_CHAIN = W.PW_ARC_REDUCED, W.PW_ARC_REMOVED, W.PW_ARC_CHAIN
@@ -142,18 +146,7 @@ class OverlapGraph(object):
         ``(DeviceArena, offs)`` for letters that are on the device already (``offs[r]``: where read ``r`` starts).
         ``complement``: the table that turns a letter into its complement; required as soon as a member is an odd vertex."""
         n_unitigs = self._count('pw_graph_num_unitigs')     # (raises before the first build)
-        held = None
-        if isinstance(reads, tuple):
-            arena, offs = reads
-            offs = np.ascontiguousarray(offs, np.int64).reshape(-1)
-            if not isinstance(arena, DeviceArena) or arena.device != self.device or len(offs) != self.n_reads or \
-                    (len(offs) and (offs.min() < 0 or (offs + self.read_lens).max() > arena.nbytes)):
-                raise ValueError('reads are (DeviceArena on device %d, offs) with every read inside the arena' % self.device)
-        else:
-            if len(reads) != self.n_reads or any(len(_as_u8(r)) != n for r, n in zip(reads, self.read_lens.tolist())):
-                raise ValueError('reads must be the %d reads of the graph, with its lengths' % self.n_reads)
-            host, offs, _ = pack_reads(reads)
-            arena = held = DeviceArena(host, self.device)
+        arena, offs, held = self._device_reads(reads)
         comp = None if complement is None else np.ascontiguousarray(complement, np.uint8).reshape(-1)
         if comp is not None and not 1 <= len(comp) <= 256:
             raise ValueError('complement must hold 1 .. 256 letters')
@@ -168,3 +161,131 @@ class OverlapGraph(object):
             if held is not None:
                 held.close()
         return [letters[coff[u]:coff[u + 1]].copy() for u in range(n_unitigs)]
+
+    # ---- the consensus stage (include/pw_consensus.h) ----
+    def placements(self, stream=None):
+        """One :data:`PLACE_DTYPE` record per read: where the read lies on the contigs of the last build (``pw_graph_place``;
+        synchronous).  ``unitig == -1``: the read is unplaced."""
+        self._count('pw_graph_num_unitigs')                 # (raises before the first build)
+        if not self.lib.pw_graph_placements_device(self.handle):       # (not placed since the build)
+            self._ck(self.lib.pw_graph_place(self.handle, stream), 'pw_graph_place')
+        return self._fetch('pw_graph_placements', self.n_reads, PLACE_DTYPE)
+
+    def _device_reads(self, reads):
+        """``(arena, offs, held)``: the reads on the device, from the reads themselves (``held`` is then the arena to close) or
+        from ``(DeviceArena, offs)``."""
+        if isinstance(reads, tuple):
+            arena, offs = reads
+            offs = np.ascontiguousarray(offs, np.int64).reshape(-1)
+            if not isinstance(arena, DeviceArena) or arena.device != self.device or len(offs) != self.n_reads or \
+                    (len(offs) and (offs.min() < 0 or (offs + self.read_lens).max() > arena.nbytes)):
+                raise ValueError('reads are (DeviceArena on device %d, offs) with every read inside the arena' % self.device)
+            return arena, offs, None
+        if len(reads) != self.n_reads or any(len(_as_u8(r)) != n for r, n in zip(reads, self.read_lens.tolist())):
+            raise ValueError('reads must be the %d reads of the graph, with its lengths' % self.n_reads)
+        host, offs, _ = pack_reads(reads)
+        arena = DeviceArena(host, self.device)
+        return arena, offs, arena
+
+    def consensus_layout(self, reads, complement=None, slack=50, drift=.1, stream=None):
+        """``(cstart, tasks, arena)`` of ``pw_graph_consensus_layout`` (synchronous): the padded contig starts
+        ``int64[n_unitigs + 1]``, the :data:`TASK_DTYPE` records and the consensus arena as a :class:`DeviceArena` that owns
+        nothing -- it is the graph's, and good until the next layout, build or :meth:`close`.  ``reads`` and ``complement``
+        as for :meth:`contigs`."""
+        n_unitigs = self._count('pw_graph_num_unitigs')     # (raises before the first build)
+        if not 0 <= int(slack) < 1 << 31:
+            raise ValueError('slack must lie in 0 .. 2**31 - 1')
+        if not (np.isfinite(drift) and 0 <= drift <= 1 << 20):
+            raise ValueError('drift must be finite and lie in 0 .. 2**20')
+        comp = None if complement is None else np.ascontiguousarray(complement, np.uint8).reshape(-1)
+        if comp is not None and not 1 <= len(comp) <= 256:
+            raise ValueError('complement must hold 1 .. 256 letters')
+        if comp is None and (self.unitigs()[1]['vertex'] & 1).any():
+            raise ValueError('a member is a reverse-complemented read: the consensus needs the complement table')
+        src, offs, held = self._device_reads(reads)
+        try:
+            self._ck(self.lib.pw_graph_consensus_layout(self.handle, src.ptr, offs.ctypes.data, None if comp is None else comp.ctypes.data,
+                                                        0 if comp is None else len(comp), int(slack), float(drift), stream),
+                     'pw_graph_consensus_layout')
+        finally:
+            if held is not None:
+                held.close()
+        cstart = self._fetch('pw_graph_cons_cstart', n_unitigs + 1, np.int64)
+        tasks = self._fetch('pw_graph_cons_tasks', self._count('pw_graph_cons_num_tasks'), TASK_DTYPE)
+        if comp is None and len(tasks) and tasks['rev'].any():
+            raise ValueError('a read lies reverse-complemented on its contig: the consensus needs the complement table')
+        arena = DeviceArena.adopt(self.lib.pw_graph_cons_arena_device(self.handle), self._count('pw_graph_cons_arena_bytes'), self.device,
+                                  owner=self)
+        return cstart, tasks, arena
+
+    def consensus(self, reads, alphabet_len, complement=None, slack=50, drift=.1, min_depth=3, ins_slots=2, self_weight=1,
+                  max_cells=2 * 10 ** 10, stats=None, **aligner_kw):
+        """The polished contigs of the last build (include/pw_consensus.h): every read is placed on its contig, aligned
+        (banded ``B_OVERLAP``, scores 1 / -3 / -5 / -2 unless ``aligner_kw`` says otherwise) against a window of the draft
+        around its place -- ``slack + drift * len`` letters wider on either side, the band as wide around the nominal diagonal
+        -- in batches of at most ``max_cells`` cells, the next batch planned while one runs; the alignments are piled onto the
+        draft's columns, which vote for themselves with ``self_weight``, into a pileup with ``ins_slots`` insertion slots,
+        and the pileup is polished with ``min_depth`` (the rule of include/pw_polish.h).  Only the tasks and the contig
+        starts come to the host on the way: no draft letter and no transcript.  ``reads`` and ``complement`` as for
+        :meth:`contigs`.  Returns ``(contigs, records)``: uint8 arrays in unitig order and one ``batch.POLISH_STATS_DTYPE``
+        record per contig.  ``stats`` (a dict) receives ``placed``, ``unplaced``, ``tasks``, ``aligned`` and the times of the
+        stages in ms, taken on the host around synchronised device work: ``layout_ms``, ``align_ms``, ``polish_ms``."""
+        import time
+        from .batch import POLISH_STATS_DTYPE, Pileup
+        t0 = time.perf_counter()
+        cstart, tasks, arena = self.consensus_layout(reads, complement=complement, slack=slack, drift=drift)
+        n_cols, T = int(cstart[-1]), len(tasks)
+        lengths = self.unitigs()[0]['length'].astype(np.int64)
+        t1 = time.perf_counter()
+        aligned = 0
+        if n_cols == 0:
+            out, offsets, records = np.zeros(0, np.uint8), np.zeros(len(lengths) + 1, np.int64), np.zeros(len(lengths), POLISH_STATS_DTYPE)
+            t2 = t3 = t1
+        else:
+            # frames: the windows, then the mutants
+            offs = np.concatenate([tasks['col0'], tasks['mut_off']]).astype(np.int64)
+            lens = np.concatenate([tasks['win_len'], self.read_lens[tasks['read']]]).astype(np.int64)
+            pidx = np.stack([np.arange(T), T + np.arange(T)], 1).astype(np.int64)
+            dr = np.stack([tasks['dmin'], tasks['dmax']], 1).astype(np.int64)
+            cells = (dr[:, 1] - dr[:, 0] + 1) * np.minimum(lens[:T], lens[T:])
+            csum, bounds, start = np.cumsum(cells), [], 0
+            while start < T:
+                base = csum[start - 1] if start else 0
+                stop = max(start + 1, int(np.searchsorted(csum, base + max_cells, 'right')))
+                bounds.append((start, stop)); start = stop
+            kw = dict(match_score=1, mismatch_score=-3, go_score=-5, ge_score=-2)
+            kw.update(aligner_kw)
+            nothing = np.zeros(0, np.uint8)
+
+            def create(lo, hi):
+                return BatchAligner.from_arena(nothing, offs, lens, pidx[lo:hi], dr[lo:hi], device_arena=arena, alnmode=W.BANDED_MODE,
+                                               alntype=W.B_OVERLAP, alphabet_len=alphabet_len, device=self.device,
+                                               arena_bytes=arena.nbytes, **kw)
+
+            with Pileup(n_cols, alphabet_len, device=self.device, ins_slots=ins_slots) as pile:
+                pile.add_letters((arena, 0), weight=self_weight)
+                cur = nxt = None
+                try:
+                    nxt = create(*bounds[0]) if bounds else None
+                    for q, (lo, hi) in enumerate(bounds):
+                        cur, nxt = nxt, None
+                        cur.solve(); cur.traceback()               # asynchronous: the device is busy from here ...
+                        if q + 1 < len(bounds):
+                            nxt = create(*bounds[q + 1])           # ... while the next batch is planned
+                        cur.pileup_add(pile, col0=tasks['col0'][lo:hi], sides='origin')
+                        cur.sync()
+                        aligned += int((cur.results()['opt_i'] >= 0).sum())
+                        cur.close(); cur = None
+                finally:
+                    for b in (cur, nxt):
+                        if b is not None:
+                            b.close()
+                arena.read(0, 1)                                   # (a synchronous copy behind the last add)
+                t2 = time.perf_counter()
+                out, offsets, records = pile.polish((arena, 0), cstart[:-1], lengths, min_depth=min_depth)
+                t3 = time.perf_counter()
+        if stats is not None:
+            place = self._fetch('pw_graph_placements', self.n_reads, PLACE_DTYPE)
+            stats.update(placed=int((place['unitig'] >= 0).sum()), unplaced=int((place['unitig'] < 0).sum()), tasks=T, aligned=aligned,
+                         layout_ms=1e3 * (t1 - t0), align_ms=1e3 * (t2 - t1), polish_ms=1e3 * (t3 - t2))
+        return [out[offsets[u]:offsets[u + 1]].copy() for u in range(len(lengths))], records

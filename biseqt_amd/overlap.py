@@ -554,16 +554,24 @@ def correct_reads(reads, wordlen, alphabet, g_max, sensitivity, p_min=.8, strand
 
 def assemble_reads(reads, wordlen, alphabet, g_max, sensitivity, p_min=.8, strands='+', complement=None, minimizer_window=None,
                    max_kmer_occ=None, stats=None, max_hang=1000, int_frac=.8, min_overlap=0, min_identity=0., fuzz=10, device=0,
-                   **aligner_kw):
+                   consensus=False, slack=50, drift=.1, min_depth=3, ins_slots=2, self_weight=1, **aligner_kw):
     """From reads to contigs in one call (include/pw_graph.h): :func:`overlap_all_pairs` (``strands``, ``complement``,
     ``minimizer_window``, ``max_kmer_occ`` are its arguments), :func:`overlap_alignments` of the pairs it found whose band has
     ``p >= p_min`` into an :class:`biseqt_amd.graph.OverlapGraph` (no transcript leaves the device), its ``build`` with
     ``max_hang``, ``int_frac``, ``min_overlap``, ``min_identity``, ``fuzz``, and its ``contigs``.  Returns ``(contigs, unitigs,
     members, contained)``: the contig letters as uint8 arrays, the ``graph.UNITIG_DTYPE`` and ``graph.MEMBER_DTYPE`` records and
-    one byte per read.  There is no consensus: correct the reads first (:func:`correct_reads`).  ``stats`` (a dict) receives the
+    one byte per read.  Without ``consensus`` the contig letters are those of single reads, one after another: correct the
+    reads first (:func:`correct_reads`), or ask for the consensus.  ``stats`` (a dict) receives the
     overlap stage's report under ``overlaps``, ``records`` (the overlap records with their classes), ``aligned``, ``arcs``,
     ``kept_arcs``, ``device_bytes`` and the times of the stages in ms, taken on the host around synchronised device work:
-    ``overlap_ms``, ``align_ms``, ``build_ms``, ``contigs_ms``."""
+    ``overlap_ms``, ``align_ms``, ``build_ms``, ``contigs_ms``.
+
+    ``consensus=True`` (include/pw_consensus.h): the first element holds the POLISHED contigs instead --
+    :meth:`biseqt_amd.graph.OverlapGraph.consensus` with ``slack``, ``drift``, ``min_depth``, ``ins_slots``, ``self_weight`` and the
+    same ``aligner_kw``: every read, the contained ones included, is placed on its contig, realigned against the draft and
+    piled onto it.  ``stats`` then gains ``draft`` (the unpolished letters, what the call returns without ``consensus``),
+    ``placements`` (``graph.PLACE_DTYPE``), ``consensus_records`` (one ``batch.POLISH_STATS_DTYPE`` record per contig),
+    ``consensus_stats`` (``placed``, ``unplaced``, ``tasks``, ``aligned``) and ``layout_ms``, ``consensus_align_ms``, ``polish_ms``."""
     import time
     from .graph import ARC_REMOVED, OverlapGraph
     assert isinstance(alphabet, Alphabet)
@@ -586,6 +594,15 @@ def assemble_reads(reads, wordlen, alphabet, g_max, sensitivity, p_min=.8, stran
         t4 = time.perf_counter()
         unitigs, members = G.unitigs()
         contained = G.contained()
+        if consensus:
+            cstats = {}
+            draft = contigs
+            contigs, crecords = G.consensus(reads, len(alphabet), complement=comp, slack=slack, drift=drift, min_depth=min_depth,
+                                            ins_slots=ins_slots, self_weight=self_weight, stats=cstats, **aligner_kw)
+            if stats is not None:
+                stats.update(draft=draft, placements=G.placements(), consensus_records=crecords,
+                             consensus_stats={k: cstats[k] for k in ('placed', 'unplaced', 'tasks', 'aligned')},
+                             layout_ms=cstats['layout_ms'], consensus_align_ms=cstats['align_ms'], polish_ms=cstats['polish_ms'])
         if stats is not None:
             arcs, _ = G.arcs()
             stats.update(overlaps=ostats, records=G.overlaps(), aligned=sum(a is not None for a in alns), arcs=len(arcs),
