@@ -930,7 +930,7 @@ def transcript_of_cigar(s):
 
 
 def plan_only(shapes, alnmode=W.STD_MODE, alntype=W.GLOBAL, alphabet_len=4, subst_scores=None, match_score=1, mismatch_score=0,
-              go_score=0, ge_score=0, flags=0, ramp_free=False, stamp_group=False):
+              go_score=0, ge_score=0, flags=0, ramp_free=False, stamp_group=False, lds_feed=False):
     """What :class:`BatchAligner` would choose for problems of these shapes, without a GPU and without allocating anything
     (``pw_plan_only``): ``shapes`` is a list of ``(origin_len, mutant_len)`` or ``(origin_len, mutant_len, dmin, dmax)``.
     Returns a dict: ``kernel`` (as :attr:`BatchAligner.kernel_name`), ``score_dtype``, ``scale_shift`` (dyadic scaling:
@@ -938,7 +938,9 @@ def plan_only(shapes, alnmode=W.STD_MODE, alntype=W.GLOBAL, alphabet_len=4, subs
     the strip pipeline, ``packed_rule`` (-1 unless a packed 16-bit kernel), ``matrix`` (packed kernel in matrix form) and, asked for
     with ``ramp_free=True``, ``ramp_free`` (the packed kernel runs its start and end blocks on the steady body;
     ``PWLIB_RAMP_BLOCKS=1`` turns that off) and, asked for with ``stamp_group=True``, ``stamp_group`` (4: the packed kernel
-    stamps its running best once per four blocks, the grouped kernel; 1 otherwise and under ``PWLIB_STAMP_GROUP=1``)."""
+    stamps its running best once per four blocks, the grouped kernel; 1 otherwise and under ``PWLIB_STAMP_GROUP=1``) and,
+    asked for with ``lds_feed=True``, ``lds_feed`` (the grouped kernel reads its letters from LDS; ``PWLIB_LDS_FEED=0`` turns
+    that off)."""
     lib = W.load()
     L = alphabet_len
     if subst_scores is None:
@@ -965,4 +967,6 @@ def plan_only(shapes, alnmode=W.STD_MODE, alntype=W.GLOBAL, alphabet_len=4, subs
         out['ramp_free'] = bool(info[7] & 2)
     if stamp_group:
         out['stamp_group'] = 4 if info[7] & 4 else 1
+    if lds_feed:
+        out['lds_feed'] = bool(info[7] & 8)
     return out

@@ -60,8 +60,14 @@ PW_FN uint64_t dev_const_dword2(const uint8_t* base, uint32_t byte_off) {
 }
 
 // (what the packed kernels' edge-lane feeders read through: pw_wave.h, WaveFill16::feed_issue)
+// ... and the letter rings of WaveFill16's LDSF read and write through (LDS by 32-bit address: ds_read_b32 / ds_write_b32 /
+// ds_write_b16, whose constant part of the address becomes the instruction's immediate offset)
 struct DevFeed {
   PW_FN static uint64_t const_dword2(const uint8_t* base, uint32_t byte_off) { return dev_const_dword2(base, byte_off); }
+  PW_FN static uint32_t lds_read32(uint32_t addr) { return *(__attribute__((address_space(3))) const uint32_t*)(uintptr_t)addr; }
+  PW_FN static void lds_write32(uint32_t addr, uint32_t v) { *(__attribute__((address_space(3))) uint32_t*)(uintptr_t)addr = v; }
+  PW_FN static void lds_write16(uint32_t addr, uint32_t v) { *(__attribute__((address_space(3))) uint16_t*)(uintptr_t)addr = (uint16_t)v; }
+  PW_FN static void lds_sync() { __syncthreads(); }
 };
 
 struct DevP : DevFeed {
@@ -240,6 +246,22 @@ __attribute__((amdgpu_waves_per_eu(Fill16Occupancy<BK, SEG, RULE>::lo, Fill16Occ
 void k_fill16g(const FillParams<int32_t> a) {
   const WaveDesc wd = a.waves[blockIdx.x];
   WaveFill16<DevP, BK, SEG, RULE, MAT, 4> w(a, wd);
+  w.run();
+}
+
+// The grouped form with its letters read from LDS (WaveFill16, GRP = 4, LDSF): a kernel and an object of its own
+// (pw_fill16l_tu.hip) beside the two above, which stay as they are.  Launched only for the batches the planner's lds_feed names
+// (pw_plan.h).  The workgroup is one wavefront; its two rings take 2 * 528 words = 4224 bytes of LDS, which leaves room for more
+// workgroups per CU than the registers do.
+template <int BK, bool SEG, int RULE, bool MAT = false>
+__global__ __launch_bounds__(64) PW_FILL_ATTR
+__attribute__((amdgpu_waves_per_eu(Fill16Occupancy<BK, SEG, RULE>::lo, Fill16Occupancy<BK, SEG, RULE>::hi)))
+void k_fill16l(const FillParams<int32_t> a) {
+  using W = WaveFill16<DevP, BK, SEG, RULE, MAT, 4, true>;
+  __shared__ uint32_t ring[2 * W::kRingWords];
+  const WaveDesc wd = a.waves[blockIdx.x];
+  W w(a, wd);
+  w.ring_h = dev_lds_handle(ring);
   w.run();
 }
 

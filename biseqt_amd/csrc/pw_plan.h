@@ -235,6 +235,7 @@ struct PlanKnobs {
   bool no_scaled16 = false;         // PWLIB_NO_SCALED16=1: no scores-times-4 form (rule 3)
   bool ramp_blocks = false;         // PWLIB_RAMP_BLOCKS=1: blocks in which diagonals start or end keep their own bodies (ramp_free)
   bool stamp_group1 = false;        // PWLIB_STAMP_GROUP=1: the running best stamped per block, never per four (stamp_group)
+  bool no_lds_feed = false;         // PWLIB_LDS_FEED=0: the grouped kernel keeps its edge-lane feeders (lds_feed)
   bool packed_bk_forced = false;    // PWLIB_PACKED_BK="<bk>" or "<bk>s": the packed lane width (s: lane packing)
   int packed_bk = 0;
   bool packed_bk_seg = false;
@@ -368,6 +369,13 @@ static inline bool ramp_free(int rule, bool matrix, double go, double ge, double
 static inline int stamp_group(int rule, bool matrix, int bk, bool seg, int nw, bool ramp_free_on, const PlanKnobs& kn) {
   return (rule == 3 && matrix && bk == 8 && !seg && nw == 1 && ramp_free_on && !kn.stamp_group1) ? 4 : 1;
 }
+
+// lds_feed: whether the grouped kernel reads the matrix rows and selector dwords of its letters from two rings in LDS
+// (pw_wave.h, WaveFill16, LDSF: the kernel k_fill16l) instead of passing them through the lanes from scalar feeders.  Exactly
+// where stamp_group says 4 -- the same form, ramp_free among its conditions: the rings hold every letter outside a sequence
+// already replaced -- and not under PWLIB_LDS_FEED=0, which keeps k_fill16g.  No admission bound of its own: the rings hold
+// what the feeders deliver, letter for letter.
+static inline bool lds_feed(int stamp_group_, const PlanKnobs& kn) { return stamp_group_ == 4 && !kn.no_lds_feed; }
 
 struct PackedLayout { int bk = 0, nl = 0, seg = 0, nw = 1; };   // bk = 0: none; seg: several pairs per wavefront
 

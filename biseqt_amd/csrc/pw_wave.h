@@ -787,6 +787,21 @@ extern "C" __attribute__((used, visibility("default"))) inline unsigned pw_group
   if (reset) pk::group_stamps() = 0;
   return n;
 }
+// The letter rings (WaveFill16, LDSF) are a template constant on the device too; here 1 runs them wherever the kernel's form
+// allows it (WaveFill16::LOK, with ramp_free on), 0 or -1 the edge-lane feeders.  The emulated wavefront's LDS is the two
+// rings below; a byte the restage step asks for outside its frame is counted with the feeders' breaches (pw_feed_breaches).
+namespace pk {
+inline int& lds_feed_emu() { static int v = -1; return v; }
+inline unsigned& ring_restages() { static unsigned n = 0; return n; }
+inline uint32_t* emu_ring() { static uint32_t r[2 * 528]; return r; }
+}  // namespace pk
+extern "C" __attribute__((used, visibility("default"))) inline void pw_emu_lds_feed(int v) { pk::lds_feed_emu() = v; }
+// (the chunks of 64 letters staged, counted by lane 0: six in front of the loop and one per eight blocks run in full)
+extern "C" __attribute__((used, visibility("default"))) inline unsigned pw_ring_restages(int reset) {
+  const unsigned n = pk::ring_restages();
+  if (reset) pk::ring_restages() = 0;
+  return n;
+}
 // The packed kernels' edge-lane feeders, one pair per wavefront (WaveFill16::feed_issue): dwords the emulator's reader was
 // asked for outside [0, wlast] of the frame it was reading (counted by every lane; must stay 0), and the blocks whose
 // window took each path, counted by lane 0: [origin ahead, origin late, mutant ahead, mutant late].
@@ -829,7 +844,9 @@ extern "C" __attribute__((used, visibility("default"))) inline void pw_feed_path
 // 0x00: the matrix minimum, which the planner requires to be <= 0 ("matches nothing").
 // GRP: the blocks per STAMP GROUP of the running best (1 or 4; stamp_best).  4 is a kernel of its own (k_fill16g) for the
 // batches the planner's stamp_group (pw_plan.h) names; every other instantiation is the five-argument form.
-template <class P, int BK, bool SEG, int RULE = 0, bool MAT = false, int GRP = 1>
+// LDSF: the matrix rows and selector dwords of the letters are READ from two rings in LDS instead of travelling through the
+// lanes (ring_read, restage); a kernel of its own (k_fill16l) for the batches the planner's lds_feed names.
+template <class P, int BK, bool SEG, int RULE = 0, bool MAT = false, int GRP = 1, bool LDSF = false>
 struct WaveFill16 {
   // RULE 3 = rule 0 with every score held times 4 (admitted when the scores stay below 2048): a kept-or-not difference
   // of two running values is then 0 or at least 4, so min(x, 2) and min(x, 4) deliver the D and I tie bits already
@@ -961,6 +978,109 @@ struct WaveFill16 {
 #endif
   uint32_t kgE[RH], kgO[RH];    // grouped: the keys as they stood before the group
   uint32_t POS[8];              // grouped: 31 - cell within the group, in both halves, of the block's 8 iterations (wave-uniform)
+  // LDSF, letters from LDS.  What an iteration hands a lane -- the 4-byte matrix row of ONE origin letter (the new ROW[R - 1])
+  // and the selector dword of ONE mutant letter (the new MW[0]: the letter's code in the low half, the code of the letter two
+  // back in the high half; FIXSEL: a letter keeps one code, chosen by its index, sel4_fed) -- is a function of the sequences
+  // alone.  The feeders rebuild both in scalar code block by block and the lanes pass them on, one DPP move and one copy of the
+  // feed value each per iteration, plus the alignbit that splices the selector.  Here the wavefront keeps them EXPANDED in two
+  // rings in LDS and every lane reads the two values it needs: one LDS read with an immediate offset each, no vector ALU work;
+  // the lane exchanges shrink to the two offers.
+  //   * ring offset u counts letters: origin letter e + u, mutant letter f - 256 + u (e, f: run()).  On iteration `it` lane l
+  //     reads origin offset 4 l + 3 + it and mutant offset 256 - 4 l + it: a span of 256 offsets between lane 0 and lane 63.
+  //   * a ring holds 512 offsets; offset u lives in slot s = u mod 512, word (s mod 4) * kRingRow + s / 4: four rows of 128
+  //     words, so that the 64 lanes of a read, 4 slots apart, fall on 64 consecutive words (no bank conflict), each row with
+  //     its first 4 words repeated behind it, so that a block's reads are immediates on ONE address per ring that moves on by
+  //     two words per block and wraps with one AND (8 iterations reach at most 2 words past the row's end).
+  //   * restaging, once per 8 blocks = 64 iterations = 64 letters per sequence (restage): behind the scalar branch of the
+  //     stamp group, after the mask stores.  Lane l takes letter u0 + l of each sequence -- one byte load per sequence at a
+  //     CLAMPED index (never a byte outside the frame), issued one section ahead and held in nx_o / nx_m --, expands it, with
+  //     the letters outside a sequence replaced by the all-zero row / MOUT as feed_commit replaces them for ramp_free, and
+  //     writes the row, the low half of its own selector dword and the high half of the dword two letters on.
+  //   * at the start of section s (blocks 8 s ..) both rings hold offsets [64 s, 64 s + 384): the section reads origin offsets
+  //     64 s + 3 .. 64 s + 318 and mutant offsets 64 s + 4 .. 64 s + 319.  The restage behind it writes [64 s + 384, 64 s + 448)
+  //     (the selector's high halves up to 64 s + 449), slots that held offsets below 64 s - 62: read by nobody any more.
+  // Runs where RAMPF does with ramp_free on (the steady loop alone; every letter outside a sequence replaced), one pair per
+  // wavefront, 8 diagonals per lane.  On the device it is the template constant (k_fill16l); the CPU emulator decides at run time
+  // (pk::lds_feed_emu) and may run it with either stamp group.
+  static constexpr bool LOK = SPLIT && TRK && !SEG && BK == 8;
+  static_assert(!LDSF || (LOK && GRP == 4), "letters from LDS: the grouped kernel's form");
+  static constexpr int kRingRow = 132, kRingWords = 4 * kRingRow;      // words per row (128 + 4 repeated) and per ring
+#if defined(__HIPCC__)
+#define PW_IF_LDSF if constexpr (LDSF)
+#else
+  bool ldsf_rt = false;
+#define PW_IF_LDSF if (ldsf_rt)
+#endif
+  // (the rings' per-lane state -- ring_h, ro, rm, nx_o, nx_m, fe, ff -- is declared at the end of the struct)
+  // word c of the block's reads (the slot's distance from the lane's base, a constant in the unrolled block)
+  PW_FN uint32_t ring_read(int which, uint32_t base, int c) const {
+    const uint32_t w = (uint32_t)(which * kRingWords + (c & 3) * kRingRow + (c >> 2));
+#if defined(__HIPCC__)
+    return P::lds_read32(ring_h + base + 4u * w);
+#else
+    return pk::emu_ring()[w + (base >> 2)];
+#endif
+  }
+  // half: -1 the whole word, 0 / 1 its low / high 16 bits
+  PW_FN void ring_store(uint32_t w, uint32_t v, int half) {
+#if defined(__HIPCC__)
+    if (half < 0) P::lds_write32(ring_h + 4u * w, v);
+    else P::lds_write16(ring_h + 4u * w + 2u * (uint32_t)half, v);
+#else
+    uint32_t& d = pk::emu_ring()[w];
+    d = half < 0 ? v : (half == 0 ? ((d & 0xffff0000u) | (v & 0xffffu)) : ((d & 0xffffu) | (v << 16)));
+#endif
+  }
+  PW_FN void ring_put(int which, uint32_t u, uint32_t v, int half) {
+    const uint32_t s = u & 511u;
+    const uint32_t w = (uint32_t)(which * kRingWords) + (s & 3u) * (uint32_t)kRingRow + (s >> 2);
+    ring_store(w, v, half);
+    if ((s >> 2) < 4u) ring_store(w + 128u, v, half);          // the row's first words again behind its end
+  }
+  PW_FN static void ring_sync() {
+#if defined(__HIPCC__)
+    P::lds_sync();
+#else
+    (void)P::shr1z(0);            // (the emulator's lanes meet at every exchange)
+#endif
+  }
+  // letter idx of a frame of n letters, idx clamped into the frame (the CPU emulator counts a byte asked for outside it)
+  PW_FN static uint32_t ring_letter(const uint8_t* seq, int idx, int n) {
+    const int c = pw_clampi(idx, 0, n > 0 ? n - 1 : 0);
+#if !defined(__HIPCC__)
+    if (c < 0 || c >= (n > 0 ? n : 1)) { pk::feed_breaches()++; return 0xa5u; }
+#endif
+    return (uint32_t)seq[c];
+  }
+  PW_FN void stage_issue(int u0) {
+    const int u = u0 + P::lane();
+    nx_o = ring_letter(oseq, fe + u, X); nx_m = ring_letter(mseq, ff - 256 + u, Y);
+  }
+  PW_FN void stage_commit(int u0) {
+#if !defined(__HIPCC__)
+    if (P::lane() == 0) pk::ring_restages()++;                 // (the CPU emulator: chunks staged)
+#endif
+    const int u = u0 + P::lane();
+    const uint32_t row = (uint32_t)(fe + u) < (uint32_t)X ? row_of(nx_o) : 0u;
+    const uint32_t code = MSEL | (((uint32_t)(ff - 256 + u) < (uint32_t)Y ? nx_m : MOUT) + 4u * sel4_fed(u));   // (256 = 0 mod 4)
+    ring_put(0, (uint32_t)u, row, -1);
+    ring_put(1, (uint32_t)u, code, 0);
+    ring_put(1, (uint32_t)u + 2u, code, 1);
+  }
+  // in front of the block loops: offsets [0, 384) of both rings, the loads of the first restage, the lanes' addresses
+  PW_FN void ring_begin() {
+#pragma unroll 1
+    for (int c = 0; c < 6; c++) { stage_issue(64 * c); stage_commit(64 * c); }
+    ring_sync();
+    stage_issue(384);
+    ro = 4u * (uint32_t)li; rm = 4u * (uint32_t)(64 - li);
+  }
+  // behind the last block of section s
+  PW_FN void restage(int s) {
+    stage_commit(64 * s + 384);
+    ring_sync();
+    stage_issue(64 * s + 448);
+  }
   // One pair per wavefront, matrix form, blocks unrolled in full: the rows of a block's 8 origin feed letters are selected
   // when the block starts (feed_commit), on bits read in place (row_bits) -- wave-uniform, scalar registers.
   static constexpr bool FROWS = MAT && !SEG && UNR == 4 && BK <= 8;
@@ -1135,7 +1255,14 @@ struct WaveFill16 {
     // slots whose values nobody reads, so the range check is needed in EDGE blocks only.
     // The letter and the left offer of the odd step travel the same way: ONE exchange (platforms whose shifts cross
     // wavefronts through LDS pay one barrier for the pair).
-    {
+    PW_IF_LDSF {
+      // letters from LDS: only the left offer crosses lanes; the row of the letter that enters the window is read
+      left_next = (uint32_t)P::shl1((int32_t)LE[0], (int32_t)left_next);
+      const uint32_t nxt = ring_read(0, ro, 3 + k);
+#pragma unroll
+      for (int i = 0; i + 1 < (MAT ? R : 1); i++) ROW[i] = ROW[i + 1];
+      ROW[MAT ? R - 1 : 0] = nxt;
+    } else {
       // (MAT: feed_commit has already turned the letters outside the sequence into 0xff, whose row is 0 -- no range check
       //  here: on a wave-uniform feed it compiled to a branch per iteration, which serialises the packed ops)
       const int oi = xfeed_o + it;
@@ -1175,7 +1302,14 @@ struct WaveFill16 {
       }
     }
     // mutant window moves on: first register <- (previous lane's last.hi | the pair's feeder, own last.lo)
-    {
+    PW_IF_LDSF {
+      // letters from LDS: only the up offer crosses lanes; the first register's new value is read whole
+      up_prev = (uint32_t)P::shr1((int32_t)UO[RH - 1], (int32_t)up_prev);
+      const uint32_t first = ring_read(1, rm, k);
+#pragma unroll
+      for (int p = RH - 1; p > 0; p--) MW[p] = MW[p - 1];
+      MW[0] = first;
+    } else {
       const int mi = yfeed_m + it;
       const uint32_t fbm = Base::feed_byte(fm_lo, fm_hi, k);
       // (MAT: the letter arrives in a high half and is moved to the low half of the first register below: high-half code,
@@ -1278,8 +1412,13 @@ struct WaveFill16 {
         stamp_group((uint32_t)(b >> 2) + 1u);
 #pragma unroll
         for (int k = 0; k < 8; k++) POS[k] += 0x00200020u;
+        PW_IF_LDSF { if ((b & 7) == 7) restage(b >> 3); }      // (the same branch serves both)
       }
+    } else PW_IF_LDSF {
+      if ((b & 7) == 7) restage(b >> 3);
     }
+    // letters from LDS: both ring addresses move on by a block -- 8 slots, two words of a row
+    PW_IF_LDSF { ro = (ro + 8u) & 511u; rm = (rm + 8u) & 511u; }
   }
 
   // One pair per wavefront (or workgroup): the indices are wave-uniform -- scalar loads, which leave vmcnt to the mask stores.
@@ -1565,7 +1704,11 @@ struct WaveFill16 {
       for (int g = 0; g < BK / 4; g++)   // (opaque: left to itself the compiler adds the group's distance per lane, in 64 bits)
         mbase[g] = pk::opaque_s((uint8_t*)(a.masks + pd.mask_off) + (uint64_t)(4u * (uint32_t)g * mgroup));
     }
-    feed_issue<true>(0);
+#if !defined(__HIPCC__)
+    ldsf_rt = LOK && rf && P::nwaves() == 1 && pk::lds_feed_emu() == 1;
+#endif
+    PW_IF_LDSF { fe = e; ff = f; ring_begin(); }
+    else feed_issue<true>(0);
     if constexpr (SPLIT) {
       // One loop per kind of block, in the order a pair runs through them: with a single body the loop-carried state stays in
       // the registers it was computed in.  (One loop that chose among the four bodies joined them in a shared tail, and the
@@ -1606,10 +1749,14 @@ struct WaveFill16 {
   PW_FN void blocks_step(int b) {
     // (the steady loop, RAMPF with ramp_free: the letters are replaced in every block that is fed one from outside a
     //  sequence -- the first of its eight origin or mutant letters has a negative index or lies past length - 8)
-    if constexpr (RAMPF && EK == 0)
-      feed_commit<true>(b, rf & (((uint32_t)(xfeed_o + 8 * b) >= flimx) | ((uint32_t)(yfeed_m + 8 * b) >= flimy)));
-    else feed_commit(b, EK != 0);
-    if (b + 1 < nblocks_run()) feed_issue(b + 1);
+    PW_IF_LDSF {
+      // (letters from LDS: no feeders -- the rings are restaged at the end of every eighth block, block16)
+    } else {
+      if constexpr (RAMPF && EK == 0)
+        feed_commit<true>(b, rf & (((uint32_t)(xfeed_o + 8 * b) >= flimx) | ((uint32_t)(yfeed_m + 8 * b) >= flimy)));
+      else feed_commit(b, EK != 0);
+      if (b + 1 < nblocks_run()) feed_issue(b + 1);
+    }
     block16<EK>(b);
   }
 
@@ -1714,7 +1861,13 @@ struct WaveFill16 {
       }
     }
   }
+  // LDSF (declared last: the members above keep the places they had)
+  uint32_t ring_h = 0;          // the device's LDS address of the origin ring; the mutant ring lies kRingWords words behind it
+  uint32_t ro, rm;              // byte offset of this lane's word within a row, as of the current block: origin, mutant ring
+  uint32_t nx_o, nx_m;          // this lane's two letters of the chunk the next restage writes
+  int fe, ff;                   // e, f of run()
 };
+#undef PW_IF_LDSF
 
 // =================================================================================================
 // K4: traceback of one pair by one lane, over the tie-mask plane.
