@@ -930,7 +930,7 @@ def transcript_of_cigar(s):
 
 
 def plan_only(shapes, alnmode=W.STD_MODE, alntype=W.GLOBAL, alphabet_len=4, subst_scores=None, match_score=1, mismatch_score=0,
-              go_score=0, ge_score=0, flags=0, ramp_free=False, stamp_group=False, lds_feed=False):
+              go_score=0, ge_score=0, flags=0, ramp_free=False, stamp_group=False, lds_feed=False, pair_keys=False):
     """What :class:`BatchAligner` would choose for problems of these shapes, without a GPU and without allocating anything
     (``pw_plan_only``): ``shapes`` is a list of ``(origin_len, mutant_len)`` or ``(origin_len, mutant_len, dmin, dmax)``.
     Returns a dict: ``kernel`` (as :attr:`BatchAligner.kernel_name`), ``score_dtype``, ``scale_shift`` (dyadic scaling:
@@ -940,7 +940,8 @@ def plan_only(shapes, alnmode=W.STD_MODE, alntype=W.GLOBAL, alphabet_len=4, subs
     ``PWLIB_RAMP_BLOCKS=1`` turns that off) and, asked for with ``stamp_group=True``, ``stamp_group`` (4: the packed kernel
     stamps its running best once per four blocks, the grouped kernel; 1 otherwise and under ``PWLIB_STAMP_GROUP=1``) and,
     asked for with ``lds_feed=True``, ``lds_feed`` (the grouped kernel reads its letters from LDS; ``PWLIB_LDS_FEED=0`` turns
-    that off)."""
+    that off) and, asked for with ``pair_keys=True``, ``pair_keys`` (that kernel keeps one running-best key per two cells;
+    ``PWLIB_PAIR_KEYS=0`` turns that off)."""
     lib = W.load()
     L = alphabet_len
     if subst_scores is None:
@@ -969,4 +970,6 @@ def plan_only(shapes, alnmode=W.STD_MODE, alntype=W.GLOBAL, alphabet_len=4, subs
         out['stamp_group'] = 4 if info[7] & 4 else 1
     if lds_feed:
         out['lds_feed'] = bool(info[7] & 8)
+    if pair_keys:
+        out['pair_keys'] = bool(info[7] & 16)
     return out

@@ -265,6 +265,20 @@ void k_fill16l(const FillParams<int32_t> a) {
   w.run();
 }
 
+// ... and with one running-best key per two cells, resolved in the end-cell search (WaveFill16, GRP = 4, LDSF, PAIRK): a kernel
+// and an object of its own again (pw_fill16p_tu.hip).  Launched only for the batches the planner's pair_keys names (pw_plan.h).
+template <int BK, bool SEG, int RULE, bool MAT = false>
+__global__ __launch_bounds__(64) PW_FILL_ATTR
+__attribute__((amdgpu_waves_per_eu(Fill16Occupancy<BK, SEG, RULE>::lo, Fill16Occupancy<BK, SEG, RULE>::hi)))
+void k_fill16p(const FillParams<int32_t> a) {
+  using W = WaveFill16<DevP, BK, SEG, RULE, MAT, 4, true, true>;
+  __shared__ uint32_t ring[2 * W::kRingWords];
+  const WaveDesc wd = a.waves[blockIdx.x];
+  W w(a, wd);
+  w.ring_h = dev_lds_handle(ring);
+  w.run();
+}
+
 // The same 16-bit body on a workgroup of up to 8 wavefronts per pair (K2a's exchange through LDS): bands of 2049 .. 16 384
 // diagonals, e.g. standard-mode tables of 1 .. 8 kb, whose scores fit the packed kernel.  One WaveDesc per pair,
 // nl = 64 x wavefronts.

@@ -21,6 +21,8 @@ hipError_t launch_fill16_mw(const FillParams<int32_t>& a, int bk, int rule, int 
 hipError_t launch_fill16g(const FillParams<int32_t>& a, int nwaves, hipStream_t st);
 // ... and the same form with its letters read from LDS, k_fill16l<8, false, 3, true> (pw_plan.h, lds_feed)
 hipError_t launch_fill16l(const FillParams<int32_t>& a, int nwaves, hipStream_t st);
+// ... and with one running-best key per two cells, k_fill16p<8, false, 3, true> (pw_plan.h, pair_keys)
+hipError_t launch_fill16p(const FillParams<int32_t>& a, int nwaves, hipStream_t st);
 // wide bands: one workgroup of nw wavefronts (2048 diagonals each, nw <= kMaxWavesPerPair) per pair
 hipError_t launch_fill_mw(const FillParams<int32_t>& a, int variant, int bk, int nw, int nblocks, hipStream_t st);
 hipError_t launch_fill_mw(const FillParams<double>& a, int variant, int bk, int nw, int nblocks, hipStream_t st);

@@ -236,6 +236,7 @@ struct PlanKnobs {
   bool ramp_blocks = false;         // PWLIB_RAMP_BLOCKS=1: blocks in which diagonals start or end keep their own bodies (ramp_free)
   bool stamp_group1 = false;        // PWLIB_STAMP_GROUP=1: the running best stamped per block, never per four (stamp_group)
   bool no_lds_feed = false;         // PWLIB_LDS_FEED=0: the grouped kernel keeps its edge-lane feeders (lds_feed)
+  bool no_pair_keys = false;        // PWLIB_PAIR_KEYS=0: one running-best key per cell, the kernel k_fill16l (pair_keys)
   bool packed_bk_forced = false;    // PWLIB_PACKED_BK="<bk>" or "<bk>s": the packed lane width (s: lane packing)
   int packed_bk = 0;
   bool packed_bk_seg = false;
@@ -376,6 +377,19 @@ static inline int stamp_group(int rule, bool matrix, int bk, bool seg, int nw, b
 // already replaced -- and not under PWLIB_LDS_FEED=0, which keeps k_fill16g.  No admission bound of its own: the rings hold
 // what the feeders deliver, letter for letter.
 static inline bool lds_feed(int stamp_group_, const PlanKnobs& kn) { return stamp_group_ == 4 && !kn.no_lds_feed; }
+
+// pair_keys: whether the kernel that reads its letters from LDS keeps ONE running-best key per two consecutive cells of a slot
+// and finds out in the end-cell search which of the two held the best (pw_wave.h, WaveFill16, PAIRK: the kernel k_fill16p).
+// Exactly where lds_feed says so, and only with ge < 0, go <= 0 and no substitution score equal to 0 (`subst` as the kernels
+// hold it, L x L): then the best cell of the table kept the diagonal move alone on a positive substitution score, which is
+// what tells the second cell of a pair from the first (the argument is at WaveFill16::pairk).  Not under PWLIB_PAIR_KEYS=0,
+// which keeps k_fill16l.
+static inline bool pair_keys(bool lds_feed_, const double* subst, int L, double go, double ge, const PlanKnobs& kn) {
+  if (!lds_feed_ || kn.no_pair_keys || !(ge < 0) || !(go <= 0)) return false;
+  for (int i = 0; i < L * L; i++)
+    if (subst[i] == 0) return false;
+  return true;
+}
 
 struct PackedLayout { int bk = 0, nl = 0, seg = 0, nw = 1; };   // bk = 0: none; seg: several pairs per wavefront
 

@@ -802,6 +802,17 @@ extern "C" __attribute__((used, visibility("default"))) inline unsigned pw_ring_
   if (reset) pk::ring_restages() = 0;
   return n;
 }
+// One running-best key per TWO cells (WaveFill16, PAIRK) is a template constant on the device as well; here 1 runs it wherever
+// the grouped form runs (WaveFill16::grp4), 0 or -1 one key per cell.  finish() counts what it resolved: [slots resolved to the
+// pair's first cell c, to its second cell c', the reported end cell resolved to c, to c'] -- slots that were stamped only.
+namespace pk {
+inline int& pair_keys_emu() { static int v = -1; return v; }
+inline unsigned* pair_key_counts() { static unsigned n[4] = {0, 0, 0, 0}; return n; }
+}  // namespace pk
+extern "C" __attribute__((used, visibility("default"))) inline void pw_emu_pair_keys(int v) { pk::pair_keys_emu() = v; }
+extern "C" __attribute__((used, visibility("default"))) inline void pw_pair_key_counts(unsigned* out, int reset) {
+  for (int i = 0; i < 4; i++) { out[i] = pk::pair_key_counts()[i]; if (reset) pk::pair_key_counts()[i] = 0; }
+}
 // The packed kernels' edge-lane feeders, one pair per wavefront (WaveFill16::feed_issue): dwords the emulator's reader was
 // asked for outside [0, wlast] of the frame it was reading (counted by every lane; must stay 0), and the blocks whose
 // window took each path, counted by lane 0: [origin ahead, origin late, mutant ahead, mutant late].
@@ -846,7 +857,9 @@ extern "C" __attribute__((used, visibility("default"))) inline void pw_feed_path
 // batches the planner's stamp_group (pw_plan.h) names; every other instantiation is the five-argument form.
 // LDSF: the matrix rows and selector dwords of the letters are READ from two rings in LDS instead of travelling through the
 // lanes (ring_read, restage); a kernel of its own (k_fill16l) for the batches the planner's lds_feed names.
-template <class P, int BK, bool SEG, int RULE = 0, bool MAT = false, int GRP = 1, bool LDSF = false>
+// PAIRK: the running best takes ONE key per two consecutive cells of a slot, and finish() finds out which of the two held it
+// (track_pair, second_of_pair); a kernel of its own (k_fill16p) for the batches the planner's pair_keys names.
+template <class P, int BK, bool SEG, int RULE = 0, bool MAT = false, int GRP = 1, bool LDSF = false, bool PAIRK = false>
 struct WaveFill16 {
   // RULE 3 = rule 0 with every score held times 4 (admitted when the scores stay below 2048): a kept-or-not difference
   // of two running values is then 0 or at least 4, so min(x, 2) and min(x, 4) deliver the D and I tie bits already
@@ -978,6 +991,26 @@ struct WaveFill16 {
 #endif
   uint32_t kgE[RH], kgO[RH];    // grouped: the keys as they stood before the group
   uint32_t POS[8];              // grouped: 31 - cell within the group, in both halves, of the block's 8 iterations (wave-uniform)
+  // PAIRK, one key per two cells (grouped form only).  The cells of iterations k and k + 1 (k even) of a slot are consecutive
+  // cells c, c' of one diagonal; they share the key 8 max(H(c), H(c')) + (15 - pair within the group), taken on iteration
+  // k + 1, where H(c) is still there as the cell pair's input: one signed maximum, one multiply-add and one unsigned maximum
+  // per register and TWO iterations, against two multiply-adds and two unsigned maxima.  POS[0 .. 3] hold the codes of the
+  // block's four pairs; the code takes four of the key's five low bits, so stamp_group reads key and stamp as before.
+  // Which of the two cells held the maximum is lost, and recovered in finish() for the key that matters.  Let S > 0 be the best
+  // score of the table, with ge < 0, go <= 0 and no substitution score 0 (the planner's pair_keys, pw_plan.h):
+  //   * if H(c') = S, c' kept the diagonal move alone, on a substitution score s > 0: a kept D or I needs a predecessor of
+  //     H >= S - ge > S, a kept B needs S = 0; so H(c) = S - s < S;
+  //   * if c' kept the diagonal move alone on s > 0, then H(c') = H(c) + s > H(c) (no B kept: the floor at 0 did not act).
+  // So where a pair's maximum is S, c' holds it iff the tie nibble of c' has none of B, D, I and the letters at c' score above
+  // 0; otherwise c does, never both.  A slot whose own best is below S may resolve wrongly: it loses the end-cell search on its
+  // score.  Cells before a diagonal's first and beyond its last hold less than S (pw_plan.h, ramp_free), so a pair that
+  // straddles either end resolves to its in-table cell: letters outside a sequence score the matrix minimum, which is <= 0.
+  static_assert(!PAIRK || (GRP == 4 && LDSF), "one key per two cells: the form of the kernel that reads its letters from LDS");
+#if defined(__HIPCC__)
+  PW_FN static constexpr bool pairk() { return PAIRK; }
+#else
+  PW_FN bool pairk() const { return pairk_rt; }
+#endif
   // LDSF, letters from LDS.  What an iteration hands a lane -- the 4-byte matrix row of ONE origin letter (the new ROW[R - 1])
   // and the selector dword of ONE mutant letter (the new MW[0]: the letter's code in the low half, the code of the letter two
   // back in the high half; FIXSEL: a letter keeps one code, chosen by its index, sel4_fed) -- is a function of the sequences
@@ -1230,6 +1263,10 @@ struct WaveFill16 {
     if (EK & 2) key &= ~pk::sign(pk::sub(tl, tv), SH15);
     kb = pk::maxu(kb, key);
   }
+  // PAIRK, iteration k odd: `H0` is the slot's cell of iteration k - 1, `H` the one of iteration k (steady body only)
+  PW_FN void track_pair(uint32_t& kb, uint32_t H0, uint32_t H, int k) {
+    kb = pk::maxu(kb, pk::mad(pk::max(H0, H), C8, POS[(k >> 1) & 3]));
+  }
 
   template <int EK, int HALF>
   PW_FN void iteration16(int it, int k) {
@@ -1244,10 +1281,14 @@ struct WaveFill16 {
 #pragma unroll
       for (int p = 0; p < RH; p++)
       {
+        const uint32_t h0 = HE[p];
         cellpair<EK>(HE[p], UE[p], LE[p], bestE[p], btE[p], gebE[p], tfE[p], tlE[p], HALF == 0 ? accE[p] : acc2E[p],
                      p == 0 ? up0 : UO[p == 0 ? 0 : p - 1], LO[p], MAT ? ROW[MAT ? p : 0] : OW[p], MW[p], tv0, clE[p],
                      MAT ? ROW[MAT ? p + RH : 0] : 0u, FIXSEL && sel4_lo(k, p));
-        if (TRK) track_key<EK>(kbE[p], HE[p], tlE[p], tv0, k);
+        if (TRK) {
+          if (pairk()) { if (k & 1) track_pair(kbE[p], h0, HE[p], k); }
+          else track_key<EK>(kbE[p], HE[p], tlE[p], tv0, k);
+        }
       }
     }
     // origin window moves on: last register <- (own first.hi, next lane's first.lo | the pair's feeder).
@@ -1295,10 +1336,14 @@ struct WaveFill16 {
 #pragma unroll
       for (int p = 0; p < RH; p++)
       {
+        const uint32_t h0 = HO[p];
         cellpair<EK>(HO[p], UO[p], LO[p], bestO[p], btO[p], gebO[p], tfO[p], tlO[p], HALF == 0 ? accO[p] : acc2O[p],
                      UE[p], p == RH - 1 ? leftl : LE[p == RH - 1 ? p : p + 1], MAT ? ROW[MAT ? p : 0] : OW[p], MW[p], tv1, clO[p],
                      MAT ? ROW[MAT ? p + RH : 0] : 0u, FIXSEL && sel4_lo(k, p));
-        if (TRK) track_key<EK>(kbO[p], HO[p], tlO[p], tv1, k);
+        if (TRK) {
+          if (pairk()) { if (k & 1) track_pair(kbO[p], h0, HO[p], k); }
+          else track_key<EK>(kbO[p], HO[p], tlO[p], tv1, k);
+        }
       }
     }
     // mutant window moves on: first register <- (previous lane's last.hi | the pair's feeder, own last.lo)
@@ -1406,12 +1451,23 @@ struct WaveFill16 {
     // the next group's "before" and starts the codes again -- behind ONE scalar branch, after the mask stores, so that the
     // unrolled body stays one basic block.
     if (TRK && grp4()) {
+      // (PAIRK: four codes, 15 - pair within the group -- four pairs per block, sixteen per group)
+      if (pairk()) {
 #pragma unroll
-      for (int k = 0; k < 8; k++) POS[k] -= 0x00080008u;
+        for (int k = 0; k < 4; k++) POS[k] -= 0x00040004u;
+      } else {
+#pragma unroll
+        for (int k = 0; k < 8; k++) POS[k] -= 0x00080008u;
+      }
       if ((b & 3) == 3) {
         stamp_group((uint32_t)(b >> 2) + 1u);
+        if (pairk()) {
 #pragma unroll
-        for (int k = 0; k < 8; k++) POS[k] += 0x00200020u;
+          for (int k = 0; k < 4; k++) POS[k] += 0x00100010u;
+        } else {
+#pragma unroll
+          for (int k = 0; k < 8; k++) POS[k] += 0x00200020u;
+        }
         PW_IF_LDSF { if ((b & 7) == 7) restage(b >> 3); }      // (the same branch serves both)
       }
     } else PW_IF_LDSF {
@@ -1640,9 +1696,17 @@ struct WaveFill16 {
 #if !defined(__HIPCC__)
     grp4_rt = GRP == 4 || (GOK && rf && P::nwaves() == 1 && pk::stamp_group_emu() == 4);
 #endif
+#if !defined(__HIPCC__)
+    pairk_rt = grp4_rt && pk::pair_keys_emu() == 1;
+#endif
     if (grp4()) {
+      if (pairk()) {
 #pragma unroll
-      for (int k = 0; k < 8; k++) POS[k] = pk::opaque_su(pk::both(31 - k));
+        for (int k = 0; k < 4; k++) POS[k] = pk::opaque_su(pk::both(15 - k));
+      } else {
+#pragma unroll
+        for (int k = 0; k < 8; k++) POS[k] = pk::opaque_su(pk::both(31 - k));
+      }
     }
     ONE =pk::opaque(0x00010001u); SH15 = pk::opaque(0x000f000fu);
     C2 = pk::opaque(0x00020002u); C4 = pk::opaque(0x00040004u); C16 = pk::opaque(0x00100010u);
@@ -1760,11 +1824,29 @@ struct WaveFill16 {
     block16<EK>(b);
   }
 
+  // PAIRK: whether slot j's key, taken for the cells of iterations itp - 1 and itp of diagonal d, belongs to the second of the
+  // two, c' = cell aap of the diagonal: c' lies in the table off its edges, kept the diagonal move alone -- its tie nibble,
+  // read back from the dword of the mask plane this very lane stored -- and its letters score above 0 (see pairk()).  Reads
+  // nothing outside the pair's plane and frames, whatever the stamp says.
+  PW_FN bool second_of_pair(int j, int d, int itp, int aap) const {
+    const int xp = aap + (d > 0 ? d : 0), yp = aap - (d < 0 ? d : 0);
+    const int bp = itp >> 3;
+    if (!(valid && li * BK + j < ndiag && li < pd.nl && bp >= 0 && bp < pd.nblocks && xp >= 1 && yp >= 1 && xp <= X && yp <= Y)) return false;
+    const uint32_t w = (a.masks + pd.mask_off)[mask_word_index(BK, pd.nl, bp, li, j)];
+    const uint32_t nib = (w >> (4 * (7 - (itp & 7)))) & 7u;
+    const uint32_t row = row_of((uint32_t)oseq[xp - 1]);
+    const int32_t sc = (int32_t)((row >> (8u * ((uint32_t)mseq[yp - 1] & 3u))) & 0xffu) - a.mat_bias;
+    return nib == 0u && sc > 0;
+  }
+
   // End-cell search for the two rules this kernel serves (END_STD_LOCAL, END_BANDED_LOCAL): the first best
   // cell of every in-band diagonal, reduced on (score desc, scan rank asc) -- once per pair of the wave.
   PW_FN void finish() {
     const int endrule = a.endrule;
     int32_t cs = -32768; uint64_t ck = ~(uint64_t)0; int cx = -1, cy = -1; bool have = false;
+#if !defined(__HIPCC__)
+    int csec = -1;
+#endif
     // Runs once per pair: keep it out of the register budget of the fill loop.  The packed bests are parked
     // in a small private array and scanned by a rolled loop.
     uint32_t parked[4 * RH];
@@ -1785,6 +1867,9 @@ struct WaveFill16 {
         const int dd = li * BK + j, d = pd.dmin + dd;
         const int tfirst = (d < 0 ? -d : d) - pd.s0;
         int32_t s; int bt;
+#if !defined(__HIPCC__)
+        int s_second = -1;           // (the CPU emulator: how this slot's key was resolved, pk::pair_key_counts)
+#endif
         if (TRK) {
           // key = 8 score + (7 - cell) with the score unscaled (SC4: 2 (4 score) + ..); stamp = 8 (block + 1) + 7 - cell of the
           // cell that first reached it, below 8 while the best stayed 0.  Rule 0: scores never go below 0, and a diagonal whose
@@ -1800,7 +1885,18 @@ struct WaveFill16 {
           } else {
             s = (int32_t)(key >> 5);
             if (stamp < 32u) bt = ANYB ? (int)((uint32_t)tfirst & 0xffffu) : 0;
-            else bt = 64 * ((int)(stamp >> 5) - 1) + 2 * (31 - (int)(stamp & 31u)) + odd;
+            else if (!pairk()) bt = 64 * ((int)(stamp >> 5) - 1) + 2 * (31 - (int)(stamp & 31u)) + odd;
+            else {
+              // one key per two cells: the code is 15 - pair within the group; c' is the pair's second cell
+              const int itp = 32 * ((int)(stamp >> 5) - 1) + 2 * (15 - (int)(stamp & 31u)) + 1;
+              bt = 2 * itp + odd;
+              const bool second = second_of_pair(j, d, itp, (bt - tfirst) >> 1);
+              if (!second) bt -= 2;
+#if !defined(__HIPCC__)
+              if (valid && dd < ndiag) pk::pair_key_counts()[second ? 1 : 0]++;
+              s_second = second;
+#endif
+            }
           }
         } else {
           s = (h ? pk::hi_s(bq) : pk::lo_s(bq)) / SCL;                 // (exact: every running value is a multiple of SCL)
@@ -1822,6 +1918,9 @@ struct WaveFill16 {
         else k = ((uint64_t)(uint32_t)dd << 32) | (uint64_t)(uint32_t)aa;
         const bool better = ok && valid && dd < ndiag && (!have || s > cs || (s == cs && k < ck));
         if (better) { cs = s; ck = k; cx = x; cy = y; have = true; }
+#if !defined(__HIPCC__)
+        if (better) csec = s_second;
+#endif
       }
     }
     const int lane = P::lane();
@@ -1829,14 +1928,24 @@ struct WaveFill16 {
     for (int sidx = 0; sidx < wd.count; sidx++) {
       int hv = (have && seg == sidx) ? 1 : 0;
       int32_t rs = cs; uint64_t rk = ck; int rx = cx, ry = cy;
+#if !defined(__HIPCC__)
+      int rsec = csec;
+#endif
 #pragma unroll
       for (int off = 32; off >= 1; off >>= 1) {
         const int32_t os = P::shfl_xor(rs, off);
         const uint64_t ok_ = xshfl_xor<P>(rk, off);
         const int ox = P::shfl_xor(rx, off), oy = P::shfl_xor(ry, off), oh = P::shfl_xor(hv, off);
         const bool take = oh && (!hv || os > rs || (os == rs && ok_ < rk));
+#if !defined(__HIPCC__)
+        const int osec = P::shfl_xor(rsec, off);
+        if (take) rsec = osec;
+#endif
         if (take) { rs = os; rk = ok_; rx = ox; ry = oy; hv = 1; }
       }
+#if !defined(__HIPCC__)
+      if (P::nwaves() == 1 && seg == sidx && li == 0 && hv && rsec >= 0) pk::pair_key_counts()[2 + rsec]++;
+#endif
       // several wavefronts per pair (K2a with this body; one pair, SEG = false): the per-wave winners the same way
       if (P::nwaves() > 1) {
         int32_t bs = rs; uint64_t bk_ = rk; int bx = rx, by = ry, bh = 0;
@@ -1866,6 +1975,9 @@ struct WaveFill16 {
   uint32_t ro, rm;              // byte offset of this lane's word within a row, as of the current block: origin, mutant ring
   uint32_t nx_o, nx_m;          // this lane's two letters of the chunk the next restage writes
   int fe, ff;                   // e, f of run()
+#if !defined(__HIPCC__)
+  bool pairk_rt = false;        // (the CPU emulator: PAIRK at run time, pk::pair_keys_emu)
+#endif
 };
 #undef PW_IF_LDSF
 
