@@ -930,7 +930,8 @@ def transcript_of_cigar(s):
 
 
 def plan_only(shapes, alnmode=W.STD_MODE, alntype=W.GLOBAL, alphabet_len=4, subst_scores=None, match_score=1, mismatch_score=0,
-              go_score=0, ge_score=0, flags=0, ramp_free=False, stamp_group=False, lds_feed=False, pair_keys=False):
+              go_score=0, ge_score=0, flags=0, ramp_free=False, stamp_group=False, lds_feed=False, pair_keys=False,
+              lds_exchange=False):
     """What :class:`BatchAligner` would choose for problems of these shapes, without a GPU and without allocating anything
     (``pw_plan_only``): ``shapes`` is a list of ``(origin_len, mutant_len)`` or ``(origin_len, mutant_len, dmin, dmax)``.
     Returns a dict: ``kernel`` (as :attr:`BatchAligner.kernel_name`), ``score_dtype``, ``scale_shift`` (dyadic scaling:
@@ -941,7 +942,8 @@ def plan_only(shapes, alnmode=W.STD_MODE, alntype=W.GLOBAL, alphabet_len=4, subs
     stamps its running best once per four blocks, the grouped kernel; 1 otherwise and under ``PWLIB_STAMP_GROUP=1``) and,
     asked for with ``lds_feed=True``, ``lds_feed`` (the grouped kernel reads its letters from LDS; ``PWLIB_LDS_FEED=0`` turns
     that off) and, asked for with ``pair_keys=True``, ``pair_keys`` (that kernel keeps one running-best key per two cells;
-    ``PWLIB_PAIR_KEYS=0`` turns that off)."""
+    ``PWLIB_PAIR_KEYS=0`` turns that off) and, asked for with ``lds_exchange=True``, ``lds_exchange`` (that kernel hands its
+    lane-crossing offers on through LDS; ``PWLIB_LDS_EXCHANGE=0`` turns that off)."""
     lib = W.load()
     L = alphabet_len
     if subst_scores is None:
@@ -972,4 +974,6 @@ def plan_only(shapes, alnmode=W.STD_MODE, alntype=W.GLOBAL, alphabet_len=4, subs
         out['lds_feed'] = bool(info[7] & 8)
     if pair_keys:
         out['pair_keys'] = bool(info[7] & 16)
+    if lds_exchange:
+        out['lds_exchange'] = bool(info[7] & 32)
     return out

@@ -64,7 +64,7 @@ F64_FLAGS = {'f64': ['-fno-honor-nans'] + os.environ.get('PW_F64_EXTRA_CXXFLAGS'
 # BK = 8 body too (159 -> 172): they keep the default.
 FILL_EXTRA = {('f64', 8): ['-mllvm', '-amdgpu-sched-strategy=max-ilp']}
 # objects whose kernels get a fingerprint in biseqt_amd/pwlib/kernel_hashes.json (config 2's and config 3's fill kernels)
-HASHED_OBJECTS = ('pw_fill16_bk8_r3_mat.o', 'pw_fill16g_bk8_r3_mat.o', 'pw_fill16l_bk8_r3_mat.o', 'pw_fill16p_bk8_r3_mat.o', 'pw_fill16_bk8_r3.o', 'pw_fill16_bk8_r0.o', 'pw_fill_i32_bk8.o', 'pw_fill_f64_bk8.o', 'pw_strip.o')
+HASHED_OBJECTS = ('pw_fill16_bk8_r3_mat.o', 'pw_fill16g_bk8_r3_mat.o', 'pw_fill16l_bk8_r3_mat.o', 'pw_fill16p_bk8_r3_mat.o', 'pw_fill16x_bk8_r3_mat.o', 'pw_fill16_bk8_r3.o', 'pw_fill16_bk8_r0.o', 'pw_fill_i32_bk8.o', 'pw_fill_f64_bk8.o', 'pw_strip.o')
 HEADERS = ['pw_types.h', 'pw_wave.h', 'pw_strip.h', 'pw_plan.h', 'pw_model.h', 'pw_launch.h', 'pw_device.h', 'pw_hip_host.h']
 
 
@@ -111,6 +111,13 @@ def _jobs():
     jobs.append((obj, [HIPCC] + COMMON + ['-mllvm', '-amdgpu-sched-strategy=max-ilp', '-DPW_FILL16_WAVES=%d' % occ,
                                           '-DPW_FILL16_WAVES_SEG=%d' % occ_seg, '-c', os.path.join(HERE, 'pw_fill16p_tu.hip'), '-o', obj],
                  [os.path.join(HERE, 'pw_fill16p_tu.hip')]))
+    # ... and with the offers that cross lanes handed on through LDS (pw_fill16x_tu.hip): an object of its own again, same flags
+    # (PW_FILL16X_DIRS: A/B builds with one direction alone, 1 the up offer, 2 the left offer)
+    obj = os.path.join(OBJ_DIR, 'pw_fill16x_bk8_r3_mat.o')
+    dirs = ['-DPW_FILL16X_DIRS=' + os.environ['PW_FILL16X_DIRS']] if os.environ.get('PW_FILL16X_DIRS') else []
+    jobs.append((obj, [HIPCC] + COMMON + ['-mllvm', '-amdgpu-sched-strategy=max-ilp', '-DPW_FILL16_WAVES=%d' % occ,
+                                          '-DPW_FILL16_WAVES_SEG=%d' % occ_seg] + dirs + ['-c', os.path.join(HERE, 'pw_fill16x_tu.hip'), '-o', obj],
+                 [os.path.join(HERE, 'pw_fill16x_tu.hip')]))
     obj = os.path.join(OBJ_DIR, 'pw_trace.o')
     jobs.append((obj, [HIPCC] + COMMON + ['-c', os.path.join(HERE, 'pw_trace.hip'), '-o', obj],
                  [os.path.join(HERE, 'pw_trace.hip')]))

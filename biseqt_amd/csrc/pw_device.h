@@ -68,6 +68,17 @@ struct DevFeed {
   PW_FN static void lds_write32(uint32_t addr, uint32_t v) { *(__attribute__((address_space(3))) uint32_t*)(uintptr_t)addr = v; }
   PW_FN static void lds_write16(uint32_t addr, uint32_t v) { *(__attribute__((address_space(3))) uint16_t*)(uintptr_t)addr = (uint16_t)v; }
   PW_FN static void lds_sync() { __syncthreads(); }
+  // ... and the offers that cross lanes through LDS go through (WaveFill16, XLDS): the two halves of `v` to the two 16-bit
+  // places at addr and addr + 2 (ds_write_b16, ds_write_b16_d16_hi), a dword whose halves two lanes wrote (ds_read_b32).  The
+  // types may alias each other: the read stays behind the writes of the same lane, with the compiler's own wait count.
+  typedef uint16_t __attribute__((may_alias)) xch16_t;
+  typedef uint32_t __attribute__((may_alias)) xch32_t;
+  PW_FN static void lds_put_halves(uint32_t addr, uint32_t v) {
+    *(__attribute__((address_space(3))) xch16_t*)(uintptr_t)addr = (uint16_t)v;
+    *(__attribute__((address_space(3))) xch16_t*)(uintptr_t)(addr + 2u) = (uint16_t)(v >> 16);
+  }
+  PW_FN static void lds_put32(uint32_t addr, uint32_t v) { *(__attribute__((address_space(3))) xch32_t*)(uintptr_t)addr = v; }
+  PW_FN static uint32_t lds_take32(uint32_t addr) { return *(__attribute__((address_space(3))) const xch32_t*)(uintptr_t)addr; }
 };
 
 struct DevP : DevFeed {
@@ -273,6 +284,24 @@ __attribute__((amdgpu_waves_per_eu(Fill16Occupancy<BK, SEG, RULE>::lo, Fill16Occ
 void k_fill16p(const FillParams<int32_t> a) {
   using W = WaveFill16<DevP, BK, SEG, RULE, MAT, 4, true, true>;
   __shared__ uint32_t ring[2 * W::kRingWords];
+  const WaveDesc wd = a.waves[blockIdx.x];
+  W w(a, wd);
+  w.ring_h = dev_lds_handle(ring);
+  w.run();
+}
+
+// ... and with the two offers that cross lanes handed on through LDS, no DPP move and no v_alignbit (WaveFill16, GRP = 4, LDSF,
+// PAIRK, XLDS; pw_wave.h, offer_up / offer_left): a kernel and an object of its own again (pw_fill16x_tu.hip).  The two arrays
+// of 64 + 1 dwords lie behind the rings.  Launched only for the batches the planner's lds_exchange names (pw_plan.h).
+#ifndef PW_FILL16X_DIRS
+#define PW_FILL16X_DIRS 3      // (A/B builds: 1 the up offer alone, 2 the left offer alone)
+#endif
+template <int BK, bool SEG, int RULE, bool MAT = false>
+__global__ __launch_bounds__(64) PW_FILL_ATTR
+__attribute__((amdgpu_waves_per_eu(Fill16Occupancy<BK, SEG, RULE>::lo, Fill16Occupancy<BK, SEG, RULE>::hi)))
+void k_fill16x(const FillParams<int32_t> a) {
+  using W = WaveFill16<DevP, BK, SEG, RULE, MAT, 4, true, true, PW_FILL16X_DIRS>;
+  __shared__ uint32_t ring[2 * W::kRingWords + 2 * kOfferWords];
   const WaveDesc wd = a.waves[blockIdx.x];
   W w(a, wd);
   w.ring_h = dev_lds_handle(ring);

@@ -23,6 +23,8 @@ hipError_t launch_fill16g(const FillParams<int32_t>& a, int nwaves, hipStream_t 
 hipError_t launch_fill16l(const FillParams<int32_t>& a, int nwaves, hipStream_t st);
 // ... and with one running-best key per two cells, k_fill16p<8, false, 3, true> (pw_plan.h, pair_keys)
 hipError_t launch_fill16p(const FillParams<int32_t>& a, int nwaves, hipStream_t st);
+// ... and with the offers that cross lanes handed on through LDS, k_fill16x<8, false, 3, true> (pw_plan.h, lds_exchange)
+hipError_t launch_fill16x(const FillParams<int32_t>& a, int nwaves, hipStream_t st);
 // wide bands: one workgroup of nw wavefronts (2048 diagonals each, nw <= kMaxWavesPerPair) per pair
 hipError_t launch_fill_mw(const FillParams<int32_t>& a, int variant, int bk, int nw, int nblocks, hipStream_t st);
 hipError_t launch_fill_mw(const FillParams<double>& a, int variant, int bk, int nw, int nblocks, hipStream_t st);

@@ -237,7 +237,8 @@ struct PlanKnobs {
   bool stamp_group1 = false;        // PWLIB_STAMP_GROUP=1: the running best stamped per block, never per four (stamp_group)
   bool no_lds_feed = false;         // PWLIB_LDS_FEED=0: the grouped kernel keeps its edge-lane feeders (lds_feed)
   bool no_pair_keys = false;        // PWLIB_PAIR_KEYS=0: one running-best key per cell, the kernel k_fill16l (pair_keys)
-  bool packed_bk_forced = false;    // PWLIB_PACKED_BK="<bk>" or "<bk>s": the packed lane width (s: lane packing)
+  bool no_lds_exchange = false;     // PWLIB_LDS_EXCHANGE=0: the offers cross lanes by DPP moves, the kernel k_fill16p (lds_exchange)
+  bool packed_bk_forced = false;   // PWLIB_PACKED_BK="<bk>" or "<bk>s": the packed lane width (s: lane packing)
   int packed_bk = 0;
   bool packed_bk_seg = false;
 };
@@ -390,6 +391,11 @@ static inline bool pair_keys(bool lds_feed_, const double* subst, int L, double 
     if (subst[i] == 0) return false;
   return true;
 }
+
+// lds_exchange: whether that kernel hands the two offers that cross lanes on through LDS instead of a DPP move and a
+// v_alignbit each (pw_wave.h, WaveFill16, XLDS: the kernel k_fill16x).  Exactly where pair_keys says so: the values are the
+// same ones, bit for bit, so there is no bound of its own.  Not under PWLIB_LDS_EXCHANGE=0, which keeps k_fill16p.
+static inline bool lds_exchange(bool pair_keys_, const PlanKnobs& kn) { return pair_keys_ && !kn.no_lds_exchange; }
 
 struct PackedLayout { int bk = 0, nl = 0, seg = 0, nw = 1; };   // bk = 0: none; seg: several pairs per wavefront
 

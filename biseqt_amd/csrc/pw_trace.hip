@@ -228,6 +228,12 @@ hipError_t launch_fill16p(const FillParams<int32_t>& a, int nwaves, hipStream_t 
   return launch_fill16p_bk8_r3_m1(a, nwaves, st);
 }
 
+hipError_t launch_fill16x_bk8_r3_m1(const FillParams<int32_t>&, int, hipStream_t);      // pw_fill16x_tu.hip
+hipError_t launch_fill16x(const FillParams<int32_t>& a, int nwaves, hipStream_t st) {
+  if (!a.ramp_free) return hipErrorInvalidValue;      // (the kernel holds the steady loop alone)
+  return launch_fill16x_bk8_r3_m1(a, nwaves, st);
+}
+
 hipError_t launch_fill16_mw(const FillParams<int32_t>& a, int bk, int rule, int mat, int nw, int npairs, hipStream_t st) {
 #define PW_CASE16(BK, R, MT) case ((BK) * 8 + (R)) * 2 + (MT): return launch_fill16mw_bk##BK##_r##R##_m##MT(a, nw, npairs, st);
   switch ((bk * 8 + rule) * 2 + (mat ? 1 : 0)) {

@@ -830,6 +830,48 @@ extern "C" __attribute__((used, visibility("default"))) inline void pw_feed_path
 }
 #endif
 
+// The two offers of the packed kernels that cross lanes, one pair per wavefront.  Each is handed on where it is produced
+// (TAKE = false: `own` goes to the neighbour, nothing is returned) and taken where it is consumed (TAKE = true): the register
+// the cell pair reads, one half the lane's own value, the other half the neighbour's.
+//   up offer:    (lane below's own.hi, own.lo)  -- handed on after the odd step, taken in front of the next even step
+//   left offer:  (own.hi, next lane's own.lo)   -- handed on after the even step, taken in front of the odd step
+// LDS = false: a DPP move into `carried`, whose edge lane (0 / 63) keeps what it held, and one v_alignbit.
+// LDS = true (WaveFill16, XLDS; device only): no vector ALU work.  Two arrays of 64 + 1 dwords behind the letter rings,
+// this lane's dword of the first at `xa`; the lane STORES its two halves where their readers want them -- ds_write_b16 and
+// ds_write_b16_d16_hi, two halfwords side by side that straddle two dwords -- and takes its register as ONE aligned dword:
+//   up:    own.lo -> high half of U[lane], own.hi -> low half of U[lane + 1];  taken: U[lane]      (U[0].lo: the seed)
+//   left:  own.lo -> high half of L[lane], own.hi -> low half of L[lane + 1];  taken: L[lane + 1]  (L[64].hi: the seed)
+// Every lane writes and reads its own words with its neighbour, 64 consecutive words: no bank conflict.  The workgroup is one
+// wavefront and a wavefront's LDS operations complete in order, so a lane's read finds what the other lanes' stores of the same
+// instruction left; the compiler sees plain stores and a load that may alias them and places the one wait the load needs.
+// (The 16-bit LDS LOADS that write one half of a register and keep the other are not what this target gives: with SRAM ECC on
+// they clear the other half, and the compiler never selects them for gfx950.  Stores have no such half to keep.)
+static constexpr uint32_t kOfferWords = 65, kOfferLeft = 4u * kOfferWords;      // dwords per array; byte distance of L from U
+template <class P, bool LDS, bool TAKE>
+PW_FN uint32_t offer_up(uint32_t xa, uint32_t& carried, uint32_t own) {
+  if constexpr (LDS) {
+    if (TAKE) return P::lds_take32(xa);
+    P::lds_put_halves(xa + 2u, own);
+    return 0u;
+  } else {
+    if (TAKE) return pk::align16(own, carried);                 // (carried.hi, own.lo)
+    carried = (uint32_t)P::shr1((int32_t)own, (int32_t)carried);
+    return 0u;
+  }
+}
+template <class P, bool LDS, bool TAKE>
+PW_FN uint32_t offer_left(uint32_t xa, uint32_t& carried, uint32_t own) {
+  if constexpr (LDS) {
+    if (TAKE) return P::lds_take32(xa + kOfferLeft + 4u);
+    P::lds_put_halves(xa + kOfferLeft + 2u, own);
+    return 0u;
+  } else {
+    if (TAKE) return pk::align16(carried, own);                 // (own.hi, carried.lo)
+    carried = (uint32_t)P::shl1((int32_t)own, (int32_t)carried);
+    return 0u;
+  }
+}
+
 // RULE selects the begin / end rules the kernel serves:
 //   0  LOCAL / B_LOCAL            begin anywhere (B = 0 in every started cell), end = first best cell (tracked)
 //   1  B_OVERLAP                  begin on the table edge (B = 0 only in the FIRST cell of a diagonal), end = the best
@@ -859,7 +901,10 @@ extern "C" __attribute__((used, visibility("default"))) inline void pw_feed_path
 // lanes (ring_read, restage); a kernel of its own (k_fill16l) for the batches the planner's lds_feed names.
 // PAIRK: the running best takes ONE key per two consecutive cells of a slot, and finish() finds out which of the two held it
 // (track_pair, second_of_pair); a kernel of its own (k_fill16p) for the batches the planner's pair_keys names.
-template <class P, int BK, bool SEG, int RULE = 0, bool MAT = false, int GRP = 1, bool LDSF = false, bool PAIRK = false>
+// XLDS: the offers that cross lanes go through LDS instead of a DPP move and a v_alignbit each (offer_up, offer_left): bit 0 the
+// up offer, bit 1 the left offer; a kernel of its own (k_fill16x) for the batches the planner's lds_exchange names.
+template <class P, int BK, bool SEG, int RULE = 0, bool MAT = false, int GRP = 1, bool LDSF = false, bool PAIRK = false,
+          int XLDS = 0>
 struct WaveFill16 {
   // RULE 3 = rule 0 with every score held times 4 (admitted when the scores stay below 2048): a kept-or-not difference
   // of two running values is then 0 or at least 4, so min(x, 2) and min(x, 4) deliver the D and I tie bits already
@@ -1108,6 +1153,19 @@ struct WaveFill16 {
     stage_issue(384);
     ro = 4u * (uint32_t)li; rm = 4u * (uint32_t)(64 - li);
   }
+  // XLDS, in front of the block loops: the lane's address, and both arrays as the DPP moves' registers stand before the first
+  // exchange -- U[0].lo is lane 0's up_prev, which no move ever writes, L[64].hi lane 63's left_next likewise (whole dwords
+  // from every lane: the other halves are stored over before anyone reads them); then the up offer of iteration 0, which the
+  // loop hands on at the end of the iteration before: every lane's UO[RH - 1] as it starts, whose high half is up_prev's.
+  static constexpr bool XUP = (XLDS & 1) != 0, XLEFT = (XLDS & 2) != 0;
+  static_assert(XLDS == 0 || (LDSF && XLDS <= 3), "offers through LDS: the form of the kernel that reads its letters from LDS");
+  PW_FN void offers_begin() {
+    if constexpr (XLDS != 0) {
+      xch_a = ring_h + 4u * (uint32_t)(2 * kRingWords) + 4u * (uint32_t)P::lane();
+      if (XUP) { P::lds_put32(xch_a, up_prev >> 16); offer_up<P, true, false>(xch_a, up_prev, UO[RH - 1]); }
+      if (XLEFT) P::lds_put32(xch_a + kOfferLeft + 4u, left_next << 16);
+    }
+  }
   // behind the last block of section s
   PW_FN void restage(int s) {
     stage_commit(64 * s + 384);
@@ -1277,7 +1335,7 @@ struct WaveFill16 {
       // (the lane below's last odd slot: moved at the end of the previous iteration, together with the mutant window)
       uint32_t prev = up_prev;
       if (SEG) prev = segfirst ? NEGV : prev;
-      const uint32_t up0 = pk::align16(UO[RH - 1], prev);         // (prev.hi, own.lo)
+      const uint32_t up0 = offer_up<P, XUP, true>(xch_a, prev, UO[RH - 1]);         // (prev.hi, own.lo)
 #pragma unroll
       for (int p = 0; p < RH; p++)
       {
@@ -1298,7 +1356,7 @@ struct WaveFill16 {
     // wavefronts through LDS pay one barrier for the pair).
     PW_IF_LDSF {
       // letters from LDS: only the left offer crosses lanes; the row of the letter that enters the window is read
-      left_next = (uint32_t)P::shl1((int32_t)LE[0], (int32_t)left_next);
+      offer_left<P, XLEFT, false>(xch_a, left_next, LE[0]);
       const uint32_t nxt = ring_read(0, ro, 3 + k);
 #pragma unroll
       for (int i = 0; i + 1 < (MAT ? R : 1); i++) ROW[i] = ROW[i + 1];
@@ -1332,7 +1390,7 @@ struct WaveFill16 {
     {
       uint32_t nxt = left_next;
       if (SEG) nxt = seglast ? NEGV : nxt;
-      const uint32_t leftl = pk::align16(nxt, LE[0]);              // (own.hi, next.lo)
+      const uint32_t leftl = offer_left<P, XLEFT, true>(xch_a, nxt, LE[0]);              // (own.hi, next.lo)
 #pragma unroll
       for (int p = 0; p < RH; p++)
       {
@@ -1349,7 +1407,7 @@ struct WaveFill16 {
     // mutant window moves on: first register <- (previous lane's last.hi | the pair's feeder, own last.lo)
     PW_IF_LDSF {
       // letters from LDS: only the up offer crosses lanes; the first register's new value is read whole
-      up_prev = (uint32_t)P::shr1((int32_t)UO[RH - 1], (int32_t)up_prev);
+      offer_up<P, XUP, false>(xch_a, up_prev, UO[RH - 1]);
       const uint32_t first = ring_read(1, rm, k);
 #pragma unroll
       for (int p = RH - 1; p > 0; p--) MW[p] = MW[p - 1];
@@ -1773,6 +1831,7 @@ struct WaveFill16 {
 #endif
     PW_IF_LDSF { fe = e; ff = f; ring_begin(); }
     else feed_issue<true>(0);
+    if constexpr (XLDS != 0) offers_begin();
     if constexpr (SPLIT) {
       // One loop per kind of block, in the order a pair runs through them: with a single body the loop-carried state stays in
       // the registers it was computed in.  (One loop that chose among the four bodies joined them in a shared tail, and the
@@ -1975,6 +2034,7 @@ struct WaveFill16 {
   uint32_t ro, rm;              // byte offset of this lane's word within a row, as of the current block: origin, mutant ring
   uint32_t nx_o, nx_m;          // this lane's two letters of the chunk the next restage writes
   int fe, ff;                   // e, f of run()
+  uint32_t xch_a = 0;           // XLDS: the device's LDS address of this lane's dword of the up offers' array (offers_begin)
 #if !defined(__HIPCC__)
   bool pairk_rt = false;        // (the CPU emulator: PAIRK at run time, pk::pair_keys_emu)
 #endif

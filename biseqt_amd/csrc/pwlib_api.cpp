@@ -218,6 +218,7 @@ struct pw_batch {
   int stamp_group = 1;                                    // ... and stamps the running best once per this many blocks (pw_plan.h, stamp_group)
   int lds_feed = 0;                                       // ... and reads its letters from LDS (pw_plan.h, lds_feed)
   int pair_keys = 0;                                      // ... and keeps one running-best key per two cells (pw_plan.h, pair_keys)
+  int lds_exchange = 0;                                   // ... and hands its lane-crossing offers on through LDS (pw_plan.h, lds_exchange)
   DeviceArray<pw::WaveDesc> d_waves;     // [waves.size()]
   int64_t cells = 0, alg_bytes = 0;
   // device (~pw_batch releases all of it)
@@ -296,6 +297,7 @@ pw::PlanKnobs plan_knobs() {
   k.stamp_group1 = env_int("PWLIB_STAMP_GROUP", 0) == 1;
   k.no_lds_feed = env_int("PWLIB_LDS_FEED", 1) == 0;
   k.no_pair_keys = env_int("PWLIB_PAIR_KEYS", 1) == 0;
+  k.no_lds_exchange = env_int("PWLIB_LDS_EXCHANGE", 1) == 0;
   const char* bk = getenv("PWLIB_PACKED_BK");
   if (bk && *bk) { k.packed_bk_forced = true; k.packed_bk = atoi(bk); k.packed_bk_seg = strchr(bk, 's') != nullptr; }
   return k;
@@ -458,6 +460,7 @@ int batch_plan(pw_batch* b) {
     b->stamp_group = pw::stamp_group(b->packed_rule, b->packed_mat != 0, p16.bk, p16.seg != 0, p16.nw, b->ramp_free != 0, kn);
     b->lds_feed = pw::lds_feed(b->stamp_group, kn) ? 1 : 0;
     b->pair_keys = pw::pair_keys(b->lds_feed != 0, b->subst.data(), L, b->go, b->ge, kn) ? 1 : 0;
+    b->lds_exchange = pw::lds_exchange(b->pair_keys != 0, kn) ? 1 : 0;
   }
   // ---- pass 2: kernel geometry per pair (pw_plan.h, pair_layout), mask planes, launch classes ----
   pw::PairRules pr;
@@ -708,6 +711,7 @@ int launch_packed_fill(pw_batch* b, hipStream_t st) {
   if (b->packed_mat) pw::packed_matrix_rows(b->subst.data(), b->L, b->packed_rule == 3, a.mat_rows, &a.mat_bias);
   a.ramp_free = b->ramp_free;
   if (b->packed_nw > 1) HIP_TRY(pw::launch_fill16_mw(a, b->classes[0].bk, b->packed_rule, b->packed_mat, b->packed_nw, (int)b->waves.size(), st));
+  else if (b->lds_exchange) HIP_TRY(pw::launch_fill16x(a, (int)b->waves.size(), st));
   else if (b->pair_keys) HIP_TRY(pw::launch_fill16p(a, (int)b->waves.size(), st));
   else if (b->lds_feed) HIP_TRY(pw::launch_fill16l(a, (int)b->waves.size(), st));
   else if (b->stamp_group == 4) HIP_TRY(pw::launch_fill16g(a, (int)b->waves.size(), st));
@@ -761,7 +765,7 @@ int pw_plan_only(const pw_scoring* sc, int32_t n_pairs, const pw_pair* pairs, ui
     for (const auto& c : b.classes) (c.nw > 1 || (b.variant == pw::VAR_FAST16 && b.packed_nw > 1) ? wg : one) += (int64_t)c.order.size();
     info[0] = b.use_f64 ? 1 : 0; info[1] = b.scale_shift; info[2] = (int32_t)one; info[3] = (int32_t)wg;
     info[4] = (int32_t)b.tiled.size(); info[5] = (int32_t)b.strips.size();
-    info[6] = b.variant == pw::VAR_FAST16 ? b.packed_rule : -1; info[7] = (b.packed_mat ? 1 : 0) | (b.ramp_free ? 2 : 0) | (b.stamp_group == 4 ? 4 : 0) | (b.lds_feed ? 8 : 0) | (b.pair_keys ? 16 : 0);
+    info[6] = b.variant == pw::VAR_FAST16 ? b.packed_rule : -1; info[7] = (b.packed_mat ? 1 : 0) | (b.ramp_free ? 2 : 0) | (b.stamp_group == 4 ? 4 : 0) | (b.lds_feed ? 8 : 0) | (b.pair_keys ? 16 : 0) | (b.lds_exchange ? 32 : 0);
   }
   return 0;
 }

@@ -96,7 +96,8 @@ void pw_batch_destroy(pw_batch* b);
  * kernel's form as bits: 1 the matrix form, 2 its start and end blocks run on the steady body (ramp_free), 4 the running
  * best is stamped once per four blocks (stamp group 4: the grouped kernel; off under PWLIB_STAMP_GROUP=1), 8 the grouped
  * kernel reads its letters from LDS (off under PWLIB_LDS_FEED=0), 16 that kernel keeps one running-best key per two cells
- * (off under PWLIB_PAIR_KEYS=0).
+ * (off under PWLIB_PAIR_KEYS=0), 32 that kernel hands its lane-crossing offers on through LDS (off under
+ * PWLIB_LDS_EXCHANGE=0).
  * 0, or -1 with pw_last_error set. */
 int pw_plan_only(const pw_scoring* scoring, int32_t n_pairs, const pw_pair* pairs, uint64_t arena_bytes, uint32_t flags,
                  char* kernel, int32_t kernel_cap, int32_t* info);
