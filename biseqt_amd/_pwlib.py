@@ -127,6 +127,10 @@ class pw_graph_params(C.Structure):
                 ('int_frac', C.c_double), ('min_identity', C.c_double)]
 
 
+class pw_graph_clean_params(C.Structure):
+    _fields_ = [(f, C.c_int32) for f in ('max_tip_reads', 'max_bubble_reads', 'rounds', 'pad_')]
+
+
 class pw_graph_arc(C.Structure):
     _fields_ = [(f, C.c_int32) for f in ('v', 'w', 'len', 'ol', 'src', 'flags')]
 
@@ -161,7 +165,7 @@ PW_FLAG_NO_STRIP = 256
 SIZEOF = dict(intpair=8, alnscores=24, alnframe=32, std_alnparams=4, banded_alnparams=12,
               alnprob=32, alnchoice=32, dpcell=16, dptable=32, alignment=24,
               pw_scoring=40, pw_pair=32, pw_result=32, pw_tx_summary=48, pw_pileup_site=8, pw_polish_stats=16,
-              pw_graph_overlap=40, pw_graph_params=32, pw_graph_arc=24, pw_unitig=32, pw_unitig_member=16, pw_cons_place=24, pw_cons_task=40)
+              pw_graph_overlap=40, pw_graph_params=32, pw_graph_clean_params=16, pw_graph_arc=24, pw_unitig=32, pw_unitig_member=16, pw_cons_place=24, pw_cons_task=40)
 
 # every symbol include/pwlib.h and include/pw_batch.h declare
 EXPORTS = ['dptable_init', 'dptable_solve', 'dptable_traceback', 'dptable_free',
@@ -196,7 +200,7 @@ POLISH_EXPORTS = ['pw_pileup_create_ins', 'pw_pileup_ins_slots', 'pw_pileup_ins_
 PW_POLISH_MAX_SLOTS = 8
 PW_SIDE_ORIGIN, PW_SIDE_MUTANT, PW_SIDE_BOTH = 1, 2, 3
 # every symbol and constant include/pw_graph.h declares
-GRAPH_EXPORTS = ['pw_graph_create', 'pw_graph_free', 'pw_graph_num_overlaps', 'pw_graph_device_bytes', 'pw_graph_add_overlaps', 'pw_batch_graph_add', 'pw_graph_build', 'pw_graph_num_arcs', 'pw_graph_num_unitigs',
+GRAPH_EXPORTS = ['pw_graph_create', 'pw_graph_free', 'pw_graph_num_overlaps', 'pw_graph_device_bytes', 'pw_graph_add_overlaps', 'pw_batch_graph_add', 'pw_graph_build', 'pw_graph_build_clean', 'pw_graph_dropped', 'pw_graph_dropped_device', 'pw_graph_num_arcs', 'pw_graph_num_unitigs',
                  'pw_graph_num_members', 'pw_graph_reduce_ms', 'pw_graph_overlaps', 'pw_graph_contained', 'pw_graph_arcs', 'pw_graph_rows', 'pw_graph_unitigs',
                  'pw_graph_members', 'pw_graph_overlaps_device', 'pw_graph_contained_device', 'pw_graph_arcs_device',
                  'pw_graph_rows_device', 'pw_graph_unitigs_device', 'pw_graph_members_device', 'pw_graph_contigs',
@@ -207,7 +211,7 @@ CONSENSUS_EXPORTS = ['pw_graph_place', 'pw_graph_placements', 'pw_graph_placemen
                      'pw_graph_cons_num_tasks', 'pw_graph_cons_num_cols', 'pw_graph_cons_arena_bytes', 'pw_graph_cons_cstart',
                      'pw_graph_cons_tasks', 'pw_graph_cons_cstart_device', 'pw_graph_cons_tasks_device', 'pw_graph_cons_arena_device']
 PW_OVL_NONE, PW_OVL_WEAK, PW_OVL_INTERNAL, PW_OVL_A_CONTAINED, PW_OVL_B_CONTAINED, PW_OVL_A_TO_B, PW_OVL_B_TO_A = range(7)
-PW_ARC_REDUCED, PW_ARC_REMOVED, PW_ARC_CHAIN = 1, 2, 4
+PW_ARC_REDUCED, PW_ARC_REMOVED, PW_ARC_CHAIN, PW_ARC_DROPPED = 1, 2, 4, 8
 # every symbol include/pw_seeds.h declares
 SEED_EXPORTS = ['pw_seeds_create', 'pw_seeds_build', 'pw_seeds_num_rows', 'pw_seeds_is_self', 'pw_seeds_rows_device',
                 'pw_seeds_rows', 'pw_seeds_count', 'pw_seeds_kmers', 'pw_seeds_band_neighbours', 'pw_seeds_graph_build', 'pw_seeds_graph_num_points', 'pw_seeds_graph_points',
@@ -444,10 +448,11 @@ def load():
     lib.pw_graph_add_overlaps.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
     lib.pw_batch_graph_add.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.pw_graph_build.argtypes = [C.c_void_p, P(pw_graph_params), C.c_void_p]
-    for f in ('pw_graph_overlaps', 'pw_graph_contained', 'pw_graph_arcs', 'pw_graph_rows', 'pw_graph_unitigs', 'pw_graph_members',
+    lib.pw_graph_build_clean.argtypes = [C.c_void_p, P(pw_graph_params), P(pw_graph_clean_params), C.c_void_p]
+    for f in ('pw_graph_overlaps', 'pw_graph_contained', 'pw_graph_dropped', 'pw_graph_arcs', 'pw_graph_rows', 'pw_graph_unitigs', 'pw_graph_members',
               'pw_graph_contig_offsets', 'pw_graph_contig_letters'):
         getattr(lib, f).argtypes = [C.c_void_p, C.c_void_p]
-    for f in ('pw_graph_overlaps_device', 'pw_graph_contained_device', 'pw_graph_arcs_device', 'pw_graph_rows_device',
+    for f in ('pw_graph_overlaps_device', 'pw_graph_contained_device', 'pw_graph_dropped_device', 'pw_graph_arcs_device', 'pw_graph_rows_device',
               'pw_graph_unitigs_device', 'pw_graph_members_device', 'pw_graph_contig_letters_device', 'pw_graph_contig_offsets_device'):
         getattr(lib, f).argtypes = [C.c_void_p]
         getattr(lib, f).restype = C.c_void_p

@@ -138,6 +138,10 @@ def _jobs():
     jobs.append((obj, [HIPCC] + COMMON + ['-Wno-unused-parameter', '-c', os.path.join(HERE, 'pw_graph.hip'), '-o', obj],
                  [os.path.join(HERE, 'pw_graph.hip'), os.path.join(HERE, 'pw_graph_launch.h'), os.path.join(ROOT, 'include', 'pw_graph.h'),
                   os.path.join(ROOT, 'include', 'pw_txsum.h'), os.path.join(ROOT, 'include', 'pw_batch.h')]))
+    obj = os.path.join(OBJ_DIR, 'pw_clean.o')
+    jobs.append((obj, [HIPCC] + COMMON + ['-Wno-unused-parameter', '-c', os.path.join(HERE, 'pw_clean.hip'), '-o', obj],
+                 [os.path.join(HERE, 'pw_clean.hip'), os.path.join(HERE, 'pw_graph_launch.h'), os.path.join(ROOT, 'include', 'pw_graph.h'),
+                  os.path.join(ROOT, 'include', 'pw_batch.h')]))
     obj = os.path.join(OBJ_DIR, 'pw_consensus.o')
     jobs.append((obj, [HIPCC] + COMMON + ['-Wno-unused-parameter', '-c', os.path.join(HERE, 'pw_consensus.hip'), '-o', obj],
                  [os.path.join(HERE, 'pw_consensus.hip'), os.path.join(HERE, 'pw_consensus_launch.h'), os.path.join(HERE, 'pw_graph_launch.h'),

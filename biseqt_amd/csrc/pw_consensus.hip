@@ -53,16 +53,27 @@ __device__ __forceinline__ bool co_window(const pw_cons_place& p, int l, long lo
 
 }  // namespace
 
-// best[c] of the read a containment record contains: the largest n_match << 32 | ~index (best is zeroed before)
+// best[c] of the read a containment record contains, and of a dropped read that a dovetail record joins to a live one: the
+// largest n_match << 32 | ~index (best is zeroed before).  A dropped read is never contained, so the two kinds of offer never
+// meet in one entry.
 __global__ __launch_bounds__(256) void k_cons_parent(const pw_graph_overlap* __restrict__ recs, long long n, long long n_reads,
+                                                     const uint8_t* __restrict__ contained, const uint8_t* __restrict__ dropped,
                                                      unsigned long long* __restrict__ best) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   const pw_graph_overlap& r = recs[i];
   const int cls = r.cls;
-  if (cls != PW_OVL_A_CONTAINED && cls != PW_OVL_B_CONTAINED) return;
-  const int c = cls == PW_OVL_A_CONTAINED ? r.a : r.b;
-  if ((unsigned long long)c >= (unsigned long long)n_reads) return;  // (never: read indices are validated when a record is added)
+  if (cls < PW_OVL_A_CONTAINED) return;
+  if ((unsigned long long)r.a >= (unsigned long long)n_reads || (unsigned long long)r.b >= (unsigned long long)n_reads) return;      // (never: read indices are validated when a record is added)
+  int c;
+  if (cls == PW_OVL_A_CONTAINED) c = r.a;
+  else if (cls == PW_OVL_B_CONTAINED) c = r.b;
+  else {                                                    // a dovetail: the dropped side hangs on the live side
+    const bool live_a = !(contained[r.a] | dropped[r.a]), live_b = !(contained[r.b] | dropped[r.b]);
+    if (dropped[r.a] && live_b) c = r.a;
+    else if (dropped[r.b] && live_a) c = r.b;
+    else return;
+  }
   atomicMax(&best[c], ((unsigned long long)(uint32_t)r.n_match << 32) | (uint32_t)~(uint32_t)i);
 }
 
@@ -77,7 +88,7 @@ __global__ __launch_bounds__(256) void k_cons_chain_init(const pw_graph_overlap*
   const uint32_t i = ~(uint32_t)key;
   if (key != 0 && (long long)i < n_recs) {
     const pw_graph_overlap rec = recs[i];
-    const bool a_child = rec.cls == PW_OVL_A_CONTAINED;
+    const bool a_child = rec.a == r;                        // (A_CONTAINED, or the dropped read of a dovetail; a != b)
     const int parent = a_child ? rec.b : rec.a;
     if ((uint32_t)parent < (uint32_t)n_reads) {             // (always)
       const long long delta = a_child ? (long long)rec.b_beg - rec.a_beg : (long long)rec.a_beg - rec.b_beg;
@@ -239,7 +250,7 @@ hipError_t cons_place(const GraphState& g, ConsState& c, hipStream_t st) {
     CO_TRY(hipMemsetAsync(c.d_first.p, 0x7f, c.d_first.bytes(nR), st));
     if (n) {
       hipLaunchKernelGGL(k_cons_parent, rows_grid((uint64_t)n), kBlock256, 0, st, g.d_recs.cp(), (long long)n, (long long)R,
-                         c.d_best.as<unsigned long long>());
+                         g.d_contained.cp(), g.d_dropped.cp(), c.d_best.as<unsigned long long>());
       CO_TRY(hipGetLastError());
     }
     hipLaunchKernelGGL(k_cons_chain_init, rgrid, kBlock256, 0, st, g.d_recs.cp(), (long long)n, c.d_best.as<const unsigned long long>(),

@@ -13,6 +13,8 @@
 // the link entering that vertex and the doubling runs once more.  The last member of every chain (k_graph_tails) hands
 // the member count, the length and the smallest vertex to its head; heads and members are placed by two exclusive scans.
 // No kernel waits for another workgroup: every dependency is a launch boundary on the stream.  No LDS, no scratch.
+// The decomposition (graph_chains: out, chain links, doubling, cut, tails) runs once for the unitigs and, before that, once
+// per cleaning round (K19, pw_clean.hip), then without marking the links; tails and heads skip contained and dropped reads.
 // The arc sort (stable: the contract's order relies on it), the sort by target, the scans and the row index (a lower
 // bound of v << 32 in the sorted keys) are rocPRIM's, through rocprim_run.
 #include <hip/hip_runtime.h>
@@ -194,8 +196,9 @@ __global__ __launch_bounds__(256) void k_graph_out(const pw_graph_arc* __restric
 }
 
 // Chain links: succ / adv of every vertex; pred (filled with -1 before) of the link's target -- one writer: out(w ^ 1) == 1.
+// mark == 0 (the decomposition of a cleaning round): the links get no PW_ARC_CHAIN.
 __global__ __launch_bounds__(256) void k_graph_chain(pw_graph_arc* __restrict__ arcs, const uint32_t* __restrict__ out,
-                                                     const int32_t* __restrict__ one, int V, int32_t* __restrict__ succ,
+                                                     const int32_t* __restrict__ one, int V, int mark, int32_t* __restrict__ succ,
                                                      int32_t* __restrict__ pred, int32_t* __restrict__ adv) {
   const int v = (int)(blockIdx.x * 256 + threadIdx.x);
   if (v >= V) return;
@@ -206,7 +209,7 @@ __global__ __launch_bounds__(256) void k_graph_chain(pw_graph_arc* __restrict__ 
     if ((uint32_t)w < (uint32_t)V && out[w ^ 1] == 1 && w != v && w != (v ^ 1)) {
       s = w; a = arcs[i].len;
       pred[w] = v;
-      arcs[i].flags |= PW_ARC_CHAIN;                      // (the arc's only writer in this launch)
+      if (mark) arcs[i].flags |= PW_ARC_CHAIN;            // (the arc's only writer in this launch)
     }
   }
   succ[v] = s; adv[v] = a;
@@ -246,10 +249,11 @@ __global__ __launch_bounds__(256) void k_graph_cut(const GraphChain* __restrict_
 // The last member of every chain writes, at its head: the members, the length, the smallest vertex.
 __global__ __launch_bounds__(256) void k_graph_tails(const GraphChain* __restrict__ st, const int32_t* __restrict__ succ,
                                                      const int32_t* __restrict__ adv, const uint8_t* __restrict__ cut,
-                                                     const uint8_t* __restrict__ contained, const int32_t* __restrict__ lens, int V,
-                                                     int32_t* __restrict__ hcnt, int32_t* __restrict__ hmin, unsigned long long* __restrict__ hlen) {
+                                                     const uint8_t* __restrict__ contained, const uint8_t* __restrict__ dropped,
+                                                     const int32_t* __restrict__ lens, int V, int32_t* __restrict__ hcnt,
+                                                     int32_t* __restrict__ hmin, unsigned long long* __restrict__ hlen) {
   const int v = (int)(blockIdx.x * 256 + threadIdx.x);
-  if (v >= V || contained[v >> 1]) return;
+  if (v >= V || (contained[v >> 1] | dropped[v >> 1])) return;      // (live vertices only)
   const int s = succ[v];
   if (s >= 0 && !cut[s]) return;
   const GraphChain c = st[v];
@@ -261,12 +265,13 @@ __global__ __launch_bounds__(256) void k_graph_tails(const GraphChain* __restric
 
 // flag[v] = 1 for the head of a kept unitig, mcnt[v] = its members (the inputs of the two scans)
 __global__ __launch_bounds__(256) void k_graph_heads(const GraphChain* __restrict__ st, const uint8_t* __restrict__ contained,
-                                                     const int32_t* __restrict__ hcnt, const int32_t* __restrict__ hmin, int V,
+                                                     const uint8_t* __restrict__ dropped, const int32_t* __restrict__ hcnt,
+                                                     const int32_t* __restrict__ hmin, int V,
                                                      unsigned long long* __restrict__ flag, unsigned long long* __restrict__ mcnt) {
   const int v = (int)(blockIdx.x * 256 + threadIdx.x);
   if (v >= V) return;
   const GraphChain c = st[v];
-  const bool keep = !contained[v >> 1] && c.nxt < 0 && c.d == 0 && !(hmin[v] & 1);
+  const bool keep = !(contained[v >> 1] | dropped[v >> 1]) && c.nxt < 0 && c.d == 0 && !(hmin[v] & 1);
   flag[v] = keep; mcnt[v] = keep ? (unsigned long long)hcnt[v] : 0ull;
 }
 
@@ -355,16 +360,46 @@ hipError_t chain_ranks(GraphState& g, int rounds, int* cur, hipStream_t st) {
 
 }  // namespace
 
-hipError_t graph_build(GraphState& g, const pw_graph_params& p, hipStream_t st) {
+namespace {
+
+// The UNITIGS decomposition over the live vertices, up to what every chain's tail hands its head: out / one, the chain
+// links (with PW_ARC_CHAIN when mark is set), ranks by doubling, the cycles cut at their smallest vertex, the ranks redone,
+// hcnt / hmin / hlen.  The final doubling state is in d_chain[*cur].
+hipError_t graph_chains(GraphState& g, int mark, int* cur, hipStream_t st) {
+  const int V = (int)g.V;
+  const size_t nV = (size_t)V;
+  const dim3 vgrid = rows_grid((uint64_t)V);
+  hipLaunchKernelGGL(k_graph_out, vgrid, kBlock256, 0, st, g.d_arcs.cp(), (const long long*)g.d_rows.cp(), V, g.d_out.p, g.d_one.p);
+  GR_TRY(hipGetLastError());
+  GR_TRY(hipMemsetAsync(g.d_pred.p, 0xff, g.d_pred.bytes(nV), st));
+  GR_TRY(hipMemsetAsync(g.d_cut.p, 0, nV, st));
+  hipLaunchKernelGGL(k_graph_chain, vgrid, kBlock256, 0, st, g.d_arcs.p, g.d_out.cp(), g.d_one.cp(), V, mark, g.d_succ.p, g.d_pred.p, g.d_adv.p);
+  GR_TRY(hipGetLastError());
+  int rounds = 1;                                         // ceil(log2(V)) + 1: fixed from the number of vertices alone
+  while (((int64_t)1 << (rounds - 1)) < V) rounds++;
+  GR_TRY(chain_ranks(g, rounds, cur, st));
+  hipLaunchKernelGGL(k_graph_cut, vgrid, kBlock256, 0, st, g.d_chain[*cur].cp(), V, g.d_cut.p);
+  GR_TRY(hipGetLastError());
+  GR_TRY(chain_ranks(g, rounds, cur, st));
+  hipLaunchKernelGGL(k_graph_tails, vgrid, kBlock256, 0, st, g.d_chain[*cur].cp(), g.d_succ.cp(), g.d_adv.cp(), g.d_cut.cp(), g.d_contained.cp(),
+                     g.d_dropped.cp(), g.d_lens.cp(), V, g.d_hcnt.p, g.d_hmin.p, g.d_hlen.as<unsigned long long>());
+  return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t graph_build(GraphState& g, const pw_graph_params& p, const pw_graph_clean_params& clean, hipStream_t st) {
   const int64_t n = g.n_recs, V = g.V;
   const size_t nV = (size_t)V;
   g.built = false; g.has_contigs = false;
   // ---- classification, contained flags, the arc count ----
   const size_t scan_n = (size_t)(n > V ? n : V) + 1;
   GR_TRY(g.d_contained.ensure((size_t)g.n_reads));
+  GR_TRY(g.d_dropped.ensure((size_t)g.n_reads));
   GR_TRY(g.d_cnt.ensure(scan_n));
   GR_TRY(g.d_off.ensure(scan_n));
   if (g.n_reads) GR_TRY(hipMemsetAsync(g.d_contained.p, 0, (size_t)g.n_reads, st));
+  if (g.n_reads) GR_TRY(hipMemsetAsync(g.d_dropped.p, 0, (size_t)g.n_reads, st));
   GR_TRY(hipMemsetAsync(g.d_cnt.p + n, 0, 8, st));
   if (n) {
     hipLaunchKernelGGL(k_graph_classify, rows_grid((uint64_t)n), kBlock256, 0, st, g.d_recs.p, (long long)n, g.d_lens.cp(), p, g.d_contained.p);
@@ -424,26 +459,18 @@ hipError_t graph_build(GraphState& g, const pw_graph_params& p, hipStream_t st) 
       hipLaunchKernelGGL(k_graph_twins, rows_grid((uint64_t)A), kBlock256, 0, st, g.d_arcs.p, g.d_idx_s.cp(), g.d_pos.cp(), (long long)A);
       GR_TRY(hipGetLastError());
     }
-    hipLaunchKernelGGL(k_graph_out, vgrid, kBlock256, 0, st, g.d_arcs.cp(), (const long long*)g.d_rows.cp(), (int)V, g.d_out.p, g.d_one.p);
-    GR_TRY(hipGetLastError());
-    GR_TRY(hipMemsetAsync(g.d_pred.p, 0xff, g.d_pred.bytes(nV), st));
-    GR_TRY(hipMemsetAsync(g.d_cut.p, 0, nV, st));
-    hipLaunchKernelGGL(k_graph_chain, vgrid, kBlock256, 0, st, g.d_arcs.p, g.d_out.cp(), g.d_one.cp(), (int)V, g.d_succ.p, g.d_pred.p, g.d_adv.p);
-    GR_TRY(hipGetLastError());
-    // ---- unitigs: ranks by doubling, the cycles cut at their smallest vertex, the ranks redone ----
-    int rounds = 1;                                       // ceil(log2(V)) + 1: fixed from the number of vertices alone
-    while (((int64_t)1 << (rounds - 1)) < V) rounds++;
+    // ---- cleaning: a fixed number of rounds, each on a decomposition of its own that marks no chain link ----
     int cur = 0;
-    GR_TRY(chain_ranks(g, rounds, &cur, st));
-    hipLaunchKernelGGL(k_graph_cut, vgrid, kBlock256, 0, st, g.d_chain[cur].cp(), (int)V, g.d_cut.p);
-    GR_TRY(hipGetLastError());
-    GR_TRY(chain_ranks(g, rounds, &cur, st));
-    hipLaunchKernelGGL(k_graph_tails, vgrid, kBlock256, 0, st, g.d_chain[cur].cp(), g.d_succ.cp(), g.d_adv.cp(), g.d_cut.cp(), g.d_contained.cp(),
-                       g.d_lens.cp(), (int)V, g.d_hcnt.p, g.d_hmin.p, g.d_hlen.as<unsigned long long>());
-    GR_TRY(hipGetLastError());
+    const int clean_rounds = (clean.max_tip_reads > 0 || clean.max_bubble_reads > 0) && A ? clean.rounds : 0;
+    for (int r = 0; r < clean_rounds; r++) {
+      GR_TRY(graph_chains(g, 0, &cur, st));
+      GR_TRY(clean_round(g, cur, A, clean, st));
+    }
+    // ---- unitigs: ranks by doubling, the cycles cut at their smallest vertex, the ranks redone ----
+    GR_TRY(graph_chains(g, 1, &cur, st));
     GR_TRY(hipMemsetAsync(g.d_cnt.p + V, 0, 8, st));
     GR_TRY(hipMemsetAsync(g.d_mcnt.p + V, 0, 8, st));
-    hipLaunchKernelGGL(k_graph_heads, vgrid, kBlock256, 0, st, g.d_chain[cur].cp(), g.d_contained.cp(), g.d_hcnt.cp(), g.d_hmin.cp(), (int)V,
+    hipLaunchKernelGGL(k_graph_heads, vgrid, kBlock256, 0, st, g.d_chain[cur].cp(), g.d_contained.cp(), g.d_dropped.cp(), g.d_hcnt.cp(), g.d_hmin.cp(), (int)V,
                        g.d_cnt.as<unsigned long long>(), g.d_mcnt.as<unsigned long long>());
     GR_TRY(hipGetLastError());
     GR_TRY(exclusive_sums(g, g.d_cnt.cp(), g.d_off.p, nV + 1, st));
@@ -503,7 +530,7 @@ int64_t graph_device_bytes(const GraphState& g) {
   add(g.d_lens); add(g.d_recs); add(g.d_stage); add(g.d_contained); add(g.d_cnt); add(g.d_off); add(g.d_mcnt); add(g.d_moff);
   add(g.d_gen); add(g.d_arcs); add(g.d_keys); add(g.d_keys_s); add(g.d_idx); add(g.d_idx_s); add(g.d_pos); add(g.d_tarc);
   add(g.d_rows); add(g.d_out); add(g.d_one); add(g.d_succ); add(g.d_pred); add(g.d_adv); add(g.d_cut); add(g.d_chain[0]); add(g.d_chain[1]);
-  add(g.d_hcnt); add(g.d_hmin); add(g.d_hlen); add(g.d_unitigs); add(g.d_members); add(g.d_mem_uid); add(g.d_roff); add(g.d_comp);
+  add(g.d_hcnt); add(g.d_hmin); add(g.d_hlen); add(g.d_dropped); add(g.d_cflag); add(g.d_cdrop); add(g.d_ctail); add(g.d_cs); add(g.d_cz); add(g.d_unitigs); add(g.d_members); add(g.d_mem_uid); add(g.d_roff); add(g.d_comp);
   add(g.d_coff); add(g.d_cletters);
   return (int64_t)b;
 }

@@ -49,6 +49,11 @@ struct GraphState {
   DeviceArray<GraphChain> d_chain[2];    // [V]: ping-pong
   DeviceArray<int32_t> d_hcnt, d_hmin;   // [V]: per head, written by its tail: members, smallest vertex
   DeviceArray<uint64_t> d_hlen;          // [V]: ... and the unitig's length
+  // ---- cleaning (K19, pw_clean.hip); d_dropped is all zero after a build without it, the rest is allocated by the first round ----
+  DeviceArray<uint8_t> d_dropped;        // [n_reads]: 0, 1 (tip), 2 (bubble)
+  DeviceArray<uint8_t> d_cflag;          // [V]: per head: 1 tip candidate, 2 bubble candidate
+  DeviceArray<uint8_t> d_cdrop;          // [V]: per head: the component is dropped as a tip (1) or as a bubble (2)
+  DeviceArray<int32_t> d_ctail, d_cs, d_cz;              // [V]: per head: the tail; of a bubble candidate the source s and the sink z
   DeviceArray<pw_unitig> d_unitigs;      // [n_unitigs]
   DeviceArray<pw_unitig_member> d_members;               // [n_members]
   DeviceArray<int32_t> d_mem_uid;        // [n_members]: the member's unitig
@@ -66,7 +71,11 @@ struct GraphState {
 hipError_t graph_reserve(GraphState& g, int64_t extra, hipStream_t st);
 // records [n_recs, n_recs + n) from a batch (d_stage holds a, b, strand); summaries: pw_tx_summary[n] on the device
 hipError_t launch_graph_from_batch(GraphState& g, const Result* results, const void* summaries, int n, hipStream_t st);
-hipError_t graph_build(GraphState& g, const pw_graph_params& p, hipStream_t st);
+// c.rounds cleaning rounds between the twins and the unitigs; none when c.rounds == 0 or both maxima are 0
+hipError_t graph_build(GraphState& g, const pw_graph_params& p, const pw_graph_clean_params& c, hipStream_t st);
+// pw_clean.hip (K19): one cleaning round on the decomposition that graph_build left in d_out, d_one, d_succ, d_cut, d_hcnt,
+// d_hmin and d_chain[cur]: candidates, tips, bubbles, d_dropped, and REMOVED | DROPPED on the n_arcs arcs.  Asynchronous on `st`.
+hipError_t clean_round(GraphState& g, int cur, int64_t n_arcs, const pw_graph_clean_params& c, hipStream_t st);
 hipError_t graph_contigs(GraphState& g, const uint8_t* letters, hipStream_t st);
 int64_t graph_device_bytes(const GraphState& g);
 

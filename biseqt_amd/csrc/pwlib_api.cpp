@@ -1542,14 +1542,20 @@ int pw_batch_graph_add(pw_batch* b, pw_graph* g, const int32_t* read_a, const in
   return mark_done(b, st);
 }
 
-int pw_graph_build(pw_graph* g, const pw_graph_params* p, void* stream) {
+int pw_graph_build(pw_graph* g, const pw_graph_params* p, void* stream) { return pw_graph_build_clean(g, p, nullptr, stream); }
+
+int pw_graph_build_clean(pw_graph* g, const pw_graph_params* p, const pw_graph_clean_params* c, void* stream) {
+  static_assert(sizeof(pw_graph_clean_params) == 16, "cleaning parameter record must be 16 bytes");
   if (!g || !p) return fail("pw_graph_build: null graph or parameters");
+  if (c && (c->max_tip_reads < 0 || c->max_bubble_reads < 0)) return fail("pw_graph_build_clean: max_tip_reads and max_bubble_reads must not be negative");
+  if (c && (c->rounds < 0 || c->rounds > 8)) return fail("pw_graph_build_clean: rounds must lie in 0 .. 8");
+  const pw_graph_clean_params clean = c ? *c : pw_graph_clean_params{0, 0, 0, 0};
   if (!g->duplicate.empty()) return fail("pw_graph_build: duplicate overlap key " + g->duplicate);
   if (!std::isfinite(p->int_frac) || !std::isfinite(p->min_identity)) return fail("pw_graph_build: int_frac and min_identity must be finite");
   if (p->max_hang < 0 || p->min_overlap < 0 || p->fuzz < 0) return fail("pw_graph_build: max_hang, min_overlap and fuzz must not be negative");
   HIP_TRY(hipSetDevice(g->s.device));
   g->c.placed = false; g->c.has_layout = false;              // (a build drops every consensus result)
-  HIP_TRY(pw::graph_build(g->s, *p, (hipStream_t)stream));
+  HIP_TRY(pw::graph_build(g->s, *p, clean, (hipStream_t)stream));
   return 0;
 }
 
@@ -1583,6 +1589,8 @@ void* graph_device_ptr(const char* who, pw_graph* g, bool ready, const DeviceArr
 
 int pw_graph_overlaps(pw_graph* g, pw_graph_overlap* out) { if (!g) return fail("pw_graph_overlaps: null graph"); return graph_copy_out("pw_graph_overlaps", g, true, g->s.d_recs, g->s.n_recs, out); }
 int pw_graph_contained(pw_graph* g, uint8_t* out) { if (!g) return fail("pw_graph_contained: null graph"); return graph_copy_out("pw_graph_contained", g, g && g->s.built, g->s.d_contained, g->s.n_reads, out); }
+int pw_graph_dropped(pw_graph* g, uint8_t* out) { if (!g) return fail("pw_graph_dropped: null graph"); return graph_copy_out("pw_graph_dropped", g, g && g->s.built, g->s.d_dropped, g->s.n_reads, out); }
+void* pw_graph_dropped_device(pw_graph* g) { if (!g) { fail("pw_graph_dropped_device: null graph"); return nullptr; } return graph_device_ptr("pw_graph_dropped_device", g, g && g->s.built, g->s.d_dropped); }
 int pw_graph_arcs(pw_graph* g, pw_graph_arc* out) { if (!g) return fail("pw_graph_arcs: null graph"); return graph_copy_out("pw_graph_arcs", g, g && g->s.built, g->s.d_arcs, g->s.n_arcs, out); }
 int pw_graph_rows(pw_graph* g, int64_t* out) { if (!g) return fail("pw_graph_rows: null graph"); return graph_copy_out("pw_graph_rows", g, g && g->s.built, g->s.d_rows, g->s.V + 1, out); }
 int pw_graph_unitigs(pw_graph* g, pw_unitig* out) { if (!g) return fail("pw_graph_unitigs: null graph"); return graph_copy_out("pw_graph_unitigs", g, g && g->s.built, g->s.d_unitigs, g->s.n_unitigs, out); }

@@ -20,7 +20,7 @@ TASK_DTYPE = np.dtype([('col0', '<i8'), ('mut_off', '<i8')] + [(f, '<i4') for f 
 assert (PLACE_DTYPE.itemsize, TASK_DTYPE.itemsize) == (24, 40)
 NONE, WEAK, INTERNAL, A_CONTAINED, B_CONTAINED, A_TO_B, B_TO_A = range(7)
 CLASS_NAMES = ('NONE', 'WEAK', 'INTERNAL', 'A_CONTAINED', 'B_CONTAINED', 'A_TO_B', 'B_TO_A')
-ARC_REDUCED, ARC_REMOVED, ARC_CHAIN = W.PW_ARC_REDUCED, W.PW_ARC_REMOVED, W.PW_ARC_CHAIN
+ARC_REDUCED, ARC_REMOVED, ARC_CHAIN, ARC_DROPPED = W.PW_ARC_REDUCED, W.PW_ARC_REMOVED, W.PW_ARC_CHAIN, W.PW_ARC_DROPPED
 
 
 def overlap_records(rows):
@@ -108,15 +108,28 @@ class OverlapGraph(object):
         self._ck(self.lib.pw_batch_graph_add(batch.handle, self.handle, a.ctypes.data, b.ctypes.data, None if s is None else s.ctypes.data,
                                              stream), 'pw_batch_graph_add')
 
-    def build(self, max_hang=1000, int_frac=.8, min_overlap=0, min_identity=0., fuzz=10, stream=None):
-        """Classify, reduce and lay out what has been added (``pw_graph_build``; synchronous).  A second build replaces the first."""
+    def build(self, max_hang=1000, int_frac=.8, min_overlap=0, min_identity=0., fuzz=10, stream=None, max_tip_reads=0,
+              max_bubble_reads=0, clean_rounds=1):
+        """Classify, reduce and lay out what has been added (``pw_graph_build``; synchronous).  A second build replaces the first.
+        ``max_tip_reads`` / ``max_bubble_reads`` above 0 switch on the CLEANING of include/pw_graph.h (``pw_graph_build_clean``):
+        ``clean_rounds`` rounds (0 .. 8) that drop tips of at most so many reads and the weaker of parallel paths of at most so
+        many reads, between the reduction and the unitigs; :meth:`dropped` tells which reads went."""
         for name, v in (('max_hang', max_hang), ('min_overlap', min_overlap), ('fuzz', fuzz)):
             if not 0 <= int(v) < 1 << 31:
                 raise ValueError('%s must lie in 0 .. 2**31 - 1' % name)
         if not (np.isfinite(int_frac) and np.isfinite(min_identity)):
             raise ValueError('int_frac and min_identity must be finite')
         p = W.pw_graph_params(int(max_hang), int(min_overlap), int(fuzz), 0, float(int_frac), float(min_identity))
-        self._ck(self.lib.pw_graph_build(self.handle, C.byref(p), stream), 'pw_graph_build')
+        for name, v in (('max_tip_reads', max_tip_reads), ('max_bubble_reads', max_bubble_reads)):
+            if not 0 <= int(v) < 1 << 31:
+                raise ValueError('%s must lie in 0 .. 2**31 - 1' % name)
+        if not 0 <= int(clean_rounds) <= 8:
+            raise ValueError('clean_rounds must lie in 0 .. 8')
+        if not (int(max_tip_reads) or int(max_bubble_reads)):
+            self._ck(self.lib.pw_graph_build(self.handle, C.byref(p), stream), 'pw_graph_build')
+            return
+        c = W.pw_graph_clean_params(int(max_tip_reads), int(max_bubble_reads), int(clean_rounds), 0)
+        self._ck(self.lib.pw_graph_build_clean(self.handle, C.byref(p), C.byref(c), stream), 'pw_graph_build_clean')
 
     def _fetch(self, what, n, dtype):
         out = np.zeros(n, dtype)
@@ -130,6 +143,10 @@ class OverlapGraph(object):
     def contained(self):
         """One byte per read: 1 where some record classifies the read as contained."""
         return self._fetch('pw_graph_contained', self.n_reads, np.uint8)
+
+    def dropped(self):
+        """One byte per read: 1 where the cleaning of the last :meth:`build` dropped the read as a tip, 2 as a bubble."""
+        return self._fetch('pw_graph_dropped', self.n_reads, np.uint8)
 
     def arcs(self):
         """``(arcs, rows)``: the sorted arc table (:data:`ARC_DTYPE`) and its row index ``int64[2 * n_reads + 1]``."""

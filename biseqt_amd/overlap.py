@@ -554,7 +554,8 @@ def correct_reads(reads, wordlen, alphabet, g_max, sensitivity, p_min=.8, strand
 
 def assemble_reads(reads, wordlen, alphabet, g_max, sensitivity, p_min=.8, strands='+', complement=None, minimizer_window=None,
                    max_kmer_occ=None, stats=None, max_hang=1000, int_frac=.8, min_overlap=0, min_identity=0., fuzz=10, device=0,
-                   consensus=False, slack=50, drift=.1, min_depth=3, ins_slots=2, self_weight=1, **aligner_kw):
+                   consensus=False, slack=50, drift=.1, min_depth=3, ins_slots=2, self_weight=1, max_tip_reads=0, max_bubble_reads=0,
+                   clean_rounds=1, **aligner_kw):
     """From reads to contigs in one call (include/pw_graph.h): :func:`overlap_all_pairs` (``strands``, ``complement``,
     ``minimizer_window``, ``max_kmer_occ`` are its arguments), :func:`overlap_alignments` of the pairs it found whose band has
     ``p >= p_min`` into an :class:`biseqt_amd.graph.OverlapGraph` (no transcript leaves the device), its ``build`` with
@@ -565,6 +566,10 @@ def assemble_reads(reads, wordlen, alphabet, g_max, sensitivity, p_min=.8, stran
     overlap stage's report under ``overlaps``, ``records`` (the overlap records with their classes), ``aligned``, ``arcs``,
     ``kept_arcs``, ``device_bytes`` and the times of the stages in ms, taken on the host around synchronised device work:
     ``overlap_ms``, ``align_ms``, ``build_ms``, ``contigs_ms``.
+
+    ``max_tip_reads``, ``max_bubble_reads``, ``clean_rounds`` go to ``build`` (the CLEANING of include/pw_graph.h: tips and the
+    weaker of parallel paths are dropped before the unitigs are laid out; off by default).  ``stats`` gains ``dropped``: a dict
+    of ``reads`` (one byte per read: 1 tip, 2 bubble), ``tips`` and ``bubbles`` (their counts).
 
     ``consensus=True`` (include/pw_consensus.h): the first element holds the POLISHED contigs instead --
     :meth:`biseqt_amd.graph.OverlapGraph.consensus` with ``slack``, ``drift``, ``min_depth``, ``ins_slots``, ``self_weight`` and the
@@ -588,7 +593,8 @@ def assemble_reads(reads, wordlen, alphabet, g_max, sensitivity, p_min=.8, stran
         alns = overlap_alignments(reads, pairs, [found[k] for k in keys], alphabet, p_min=p_min, device=device, want_transcripts=False,
                                   strands=pstrands, complement=complement, graph=G, **aligner_kw)
         t2 = time.perf_counter()
-        G.build(max_hang=max_hang, int_frac=int_frac, min_overlap=min_overlap, min_identity=min_identity, fuzz=fuzz)
+        G.build(max_hang=max_hang, int_frac=int_frac, min_overlap=min_overlap, min_identity=min_identity, fuzz=fuzz,
+                max_tip_reads=max_tip_reads, max_bubble_reads=max_bubble_reads, clean_rounds=clean_rounds)
         t3 = time.perf_counter()
         contigs = G.contigs(reads, complement=comp)
         t4 = time.perf_counter()
@@ -605,6 +611,8 @@ def assemble_reads(reads, wordlen, alphabet, g_max, sensitivity, p_min=.8, stran
                              layout_ms=cstats['layout_ms'], consensus_align_ms=cstats['align_ms'], polish_ms=cstats['polish_ms'])
         if stats is not None:
             arcs, _ = G.arcs()
+            gone = G.dropped()
+            stats['dropped'] = dict(reads=gone, tips=int((gone == 1).sum()), bubbles=int((gone == 2).sum()))
             stats.update(overlaps=ostats, records=G.overlaps(), aligned=sum(a is not None for a in alns), arcs=len(arcs),
                          kept_arcs=int((arcs['flags'] & ARC_REMOVED == 0).sum()), device_bytes=G.device_bytes,
                          overlap_ms=1e3 * (t1 - t0), align_ms=1e3 * (t2 - t1), build_ms=1e3 * (t3 - t2), contigs_ms=1e3 * (t4 - t3))

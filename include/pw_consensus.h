@@ -28,6 +28,14 @@
  *     B_CONTAINED (child b, parent a)   0     a_beg - b_beg    a      0   delta
  *     B_CONTAINED                       1     a_beg - b_beg    a      1   delta
  *
+ *   Dropped reads (include/pw_graph.h, CLEANING).  The parent record of a dropped read d is chosen among the records with cls
+ *   in {A_TO_B, B_TO_A} that have d on one side and a LIVE read -- neither contained nor dropped -- on the other: the largest
+ *   n_match wins, a tie goes to the lowest record index (the same 64-bit atomic max; a dropped read is never contained, so
+ *   no entry sees both kinds of offer).  d is the child, and (parent, rel, off) follow the table above unchanged, by the rows
+ *   "child a" / "child b" and the strand: the table's geometry does not depend on the class, only off may now be negative
+ *   or pass the parent's end.  A dropped read without such a record is unplaced.  A contained read whose parent is dropped
+ *   resolves through the doubling below like any other chain.  With nothing dropped the placements are what they were.
+ *
  *   Composition.  A child placement (p, rel_c, off_c) of a read of lc letters on a read p of lp letters, composed with the
  *   placement (F, rel_p, off_p) of p -- F a grand-parent read or, at the root, a contig -- is
  *     rel_p == 0:  (F, rel_c,     off_p + off_c)

@@ -58,6 +58,38 @@
  * last member of a circular one the len of its link back to the head -- and its offset, the sum of the advances before
  * it.  The unitig's length is the sum of all advances.
  *
+ * CLEANING (pw_graph_build_clean: tip removal and bubble popping, between the reduction and the unitigs).  Parameters, all
+ * int32: max_tip_reads >= 0, max_bubble_reads >= 0, rounds in 0 .. 8.  With rounds == 0, or both maxima 0, nothing is dropped
+ * and the build is exactly pw_graph_build's.  Everything is evaluated on the arcs that are not REMOVED, after reduction and
+ * twins.  A read is LIVE iff it is neither contained nor dropped; a vertex is live iff its read is.  out(v) is as in UNITIGS,
+ * and in(v) = out(v ^ 1): REMOVED is twin-symmetric and reads are dropped whole, so the kept arcs entering v are the twins
+ * of the kept arcs leaving v ^ 1.  Where UNITIGS says "the reads that are not contained", read "the live reads".
+ *   A ROUND.  (1) The chain links and components over the live vertices, exactly as UNITIGS defines them.  (2) For a linear
+ *   (not circular) component C: h is its head, t its tail (its last member), n its member count, mr(C) its smallest vertex
+ *   >> 1.  (3) TIPS and BUBBLES below are decided for every component, of both orientations, on this one decomposition.
+ *   (4) Every read that has a vertex in a dropped component is dropped: dropped[r] = 1 for a tip, 2 for a bubble.  (5) Every
+ *   arc that is not yet REMOVED and has an end on a dropped read gets REMOVED | DROPPED.
+ *   The rounds are a fixed count, not a loop on a flag: a round that drops nothing changes nothing.  After the last round
+ *   the UNITIGS pass runs once over the live vertices and gives the unitigs, the members and the CHAIN flags; the chain
+ *   links of the rounds leave no CHAIN flag behind.  A dropped read is in no unitig.
+ *   TIPS (max_tip_reads > 0).  C is a tip candidate iff it is linear, n <= max_tip_reads, in(h) == 0 and out(t) >= 1.  A kept
+ *   arc u -> w with u != t COMPETES with C at w iff C has a kept arc t -> w; u is then the tail of its component D (w has
+ *   two kept arcs entering it, so u -> w is no chain link).  D is STRONGER than C iff D is no tip candidate, or n_D > n_C,
+ *   or n_D == n_C and mr(D) < mr(C).  C is dropped iff some competing arc at some w comes from a stronger D.
+ *     - A dead-end spur (in(h) >= 1, out(t) == 0) is caught through its reverse-complement component, which is a dead start.
+ *     - Of the two short branches of a Y the better one survives: the longer, at equal length the one with the smaller mr.
+ *     - A short path that is the only way into a fork is kept: nothing competes with it.
+ *     - An isolated component is never a tip: out(t) == 0.
+ *   BUBBLES (max_bubble_reads > 0).  C is a bubble candidate iff it is linear, n <= max_bubble_reads, in(h) == 1,
+ *   out(t) == 1, and, with s the tail of the one kept arc entering h and z the head of the one kept arc leaving t, neither
+ *   s >> 1 nor z >> 1 is the read of h or of t.  C is dropped iff another bubble candidate D with (s_D, z_D) == (s_C, z_C)
+ *   has n_D > n_C, or n_D == n_C and mr(D) < mr(C).  Of k parallel paths exactly one survives; equal n and equal mr (a
+ *   component against its own twin, in a hairpin z == s ^ 1) drops neither.
+ *   Both rules compare only n and mr, which a component shares with its twin C ^ 1 (the reverse complements of its members
+ *   in reverse order), so the decisions for C and C ^ 1 never contradict each other: C is a bubble candidate, and dropped as
+ *   one, iff C ^ 1 is; C and C ^ 1 are never both tip candidates; and no read is dropped as a tip through one of its
+ *   vertices and as a bubble through the other.  dropped[r] is therefore one well-defined value.
+ *
  * CONTIG LETTERS.  Members in order; each contributes the first `advance` letters of its oriented read.  The letters of
  * 2r + 1 are those of rc(reads[r]) under the call's complement table; a letter >= complement_len stays what it is.  There
  * is no consensus here.
@@ -78,6 +110,7 @@ enum { PW_OVL_NONE = 0, PW_OVL_WEAK = 1, PW_OVL_INTERNAL = 2, PW_OVL_A_CONTAINED
 #define PW_ARC_REDUCED 1
 #define PW_ARC_REMOVED 2
 #define PW_ARC_CHAIN 4
+#define PW_ARC_DROPPED 0x8              /* 8: removed by CLEANING (always beside PW_ARC_REMOVED) */
 
 /* Plain records, identical on host and device. */
 typedef struct {
@@ -90,6 +123,7 @@ typedef struct {
   int32_t max_hang, min_overlap, fuzz, pad_;
   double int_frac, min_identity;
 } pw_graph_params;                      /* 32 bytes */
+typedef struct { int32_t max_tip_reads, max_bubble_reads, rounds, pad_; } pw_graph_clean_params;      /* 16 bytes; CLEANING */
 typedef struct { int32_t v, w, len, ol, src, flags; } pw_graph_arc;              /* 24 bytes; flags: PW_ARC_* */
 typedef struct {
   int64_t first_member;                 /* its members are [first_member, first_member + n_members) */
@@ -126,6 +160,9 @@ int pw_batch_graph_add(pw_batch*, pw_graph*, const int32_t* read_a, const int32_
  * first and drops the contig letters.  An error for a duplicate key, for int_frac or min_identity that is not finite, and
  * for a negative max_hang, min_overlap or fuzz. */
 int pw_graph_build(pw_graph*, const pw_graph_params*, void* stream);
+/* pw_graph_build with the CLEANING rounds between the reduction and the unitigs.  A NULL third argument is pw_graph_build
+ * (which is this call).  An error, besides what pw_graph_build refuses, for a negative maximum and for rounds outside 0 .. 8. */
+int pw_graph_build_clean(pw_graph*, const pw_graph_params*, const pw_graph_clean_params*, void* stream);
 
 /* Results of the last build.  The counts are -1 and every accessor an error (NULL for the _device forms) before the
  * first build -- except the overlaps, which may be read at any time (cls is then that of the last build, 0 for records
@@ -138,12 +175,14 @@ int64_t pw_graph_num_members(pw_graph*);
 double pw_graph_reduce_ms(pw_graph*);
 int pw_graph_overlaps(pw_graph*, pw_graph_overlap* host_out);       /* num_overlaps records */
 int pw_graph_contained(pw_graph*, uint8_t* host_out);               /* n_reads bytes, 0 / 1 */
+int pw_graph_dropped(pw_graph*, uint8_t* host_out);                 /* n_reads bytes: 0, 1 (tip) or 2 (bubble); all 0 without cleaning */
 int pw_graph_arcs(pw_graph*, pw_graph_arc* host_out);               /* num_arcs records, sorted */
 int pw_graph_rows(pw_graph*, int64_t* host_out);                    /* 2 * n_reads + 1 */
 int pw_graph_unitigs(pw_graph*, pw_unitig* host_out);               /* num_unitigs records */
 int pw_graph_members(pw_graph*, pw_unitig_member* host_out);        /* num_members records */
 void* pw_graph_overlaps_device(pw_graph*);
 void* pw_graph_contained_device(pw_graph*);
+void* pw_graph_dropped_device(pw_graph*);
 void* pw_graph_arcs_device(pw_graph*);
 void* pw_graph_rows_device(pw_graph*);
 void* pw_graph_unitigs_device(pw_graph*);
