@@ -210,6 +210,9 @@ GRAPH_EXPORTS = ['pw_graph_create', 'pw_graph_free', 'pw_graph_num_overlaps', 'p
 CONSENSUS_EXPORTS = ['pw_graph_place', 'pw_graph_placements', 'pw_graph_placements_device', 'pw_graph_consensus_layout',
                      'pw_graph_cons_num_tasks', 'pw_graph_cons_num_cols', 'pw_graph_cons_arena_bytes', 'pw_graph_cons_cstart',
                      'pw_graph_cons_tasks', 'pw_graph_cons_cstart_device', 'pw_graph_cons_tasks_device', 'pw_graph_cons_arena_device']
+# include/pw_rounds.h
+ROUNDS_EXPORTS = ['pw_pileup_polish_columns', 'pw_pileup_colmap_device', 'pw_pileup_colmap', 'pw_graph_consensus_relayout',
+                  'pw_graph_cons_round', 'pw_graph_cons_positions', 'pw_graph_cons_lengths']
 PW_OVL_NONE, PW_OVL_WEAK, PW_OVL_INTERNAL, PW_OVL_A_CONTAINED, PW_OVL_B_CONTAINED, PW_OVL_A_TO_B, PW_OVL_B_TO_A = range(7)
 PW_ARC_REDUCED, PW_ARC_REMOVED, PW_ARC_CHAIN, PW_ARC_DROPPED = 1, 2, 4, 8
 # every symbol include/pw_seeds.h declares
@@ -468,6 +471,16 @@ def load():
     for f in ('pw_graph_placements_device', 'pw_graph_cons_cstart_device', 'pw_graph_cons_tasks_device', 'pw_graph_cons_arena_device'):
         getattr(lib, f).argtypes = [C.c_void_p]
         getattr(lib, f).restype = C.c_void_p
+    # include/pw_rounds.h
+    lib.pw_pileup_polish_columns.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_uint32, C.c_void_p]
+    lib.pw_pileup_colmap_device.argtypes = [C.c_void_p]
+    lib.pw_pileup_colmap_device.restype = C.c_void_p
+    lib.pw_pileup_colmap.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]
+    lib.pw_graph_consensus_relayout.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                                C.c_int32, C.c_double, C.c_void_p]
+    lib.pw_graph_cons_round.argtypes = [C.c_void_p]
+    for f in ('pw_graph_cons_positions', 'pw_graph_cons_lengths'):
+        getattr(lib, f).argtypes = [C.c_void_p, C.c_void_p]
     # include/pw_seeds.h
     lib.pw_seeds_create.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int,
                                     P(C.c_uint64), C.c_int, C.c_int]

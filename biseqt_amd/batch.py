@@ -365,11 +365,19 @@ class Pileup(object):
             if held is not None:
                 held.close()                 # (pw_arena_free waits for the device: the kernel has read the letters by then)
 
-    def polish(self, ref, offs, lens, min_depth=1, stream=None):
+    def polish(self, ref, offs, lens, min_depth=1, stream=None, columns=False):
         """The polished reads (``pw_pileup_polish``; the rule is in include/pw_polish.h): read ``r`` has its letters and its
         columns at ``offs[r] .. offs[r] + lens[r]``; ``ref`` holds one letter per column of the pileup, a host array or
         ``(DeviceArena, offset)`` as for :meth:`call`.  Returns ``(letters uint8, offsets int64[n + 1], stats)``: read ``r``
-        is ``letters[offsets[r]:offsets[r + 1]]`` and ``stats[r]`` its :data:`POLISH_STATS_DTYPE` record."""
+        is ``letters[offsets[r]:offsets[r + 1]]`` and ``stats[r]`` its :data:`POLISH_STATS_DTYPE` record.  ``columns=True``
+        polishes one column per lane (``pw_pileup_polish_columns``, include/pw_rounds.h): the same triple, for reads that come
+        in column order and do not overlap, and :meth:`colmap` then returns the map from columns to polished letters."""
+        offsets, stats, letters = self._polish(ref, offs, lens, min_depth, stream, columns, True)
+        return letters, offsets, stats
+
+    def _polish(self, ref, offs, lens, min_depth, stream, columns, fetch):
+        """:meth:`polish`; ``(offsets, stats)`` without ``fetch``: the letters stay on the device (:meth:`polished_letters`)."""
+        entry = 'pw_pileup_polish_columns' if columns else 'pw_pileup_polish'
         min_depth = int(min_depth)
         if not 0 <= min_depth < 1 << 32:
             raise ValueError('min_depth must fit 32 bits')
@@ -382,17 +390,36 @@ class Pileup(object):
             raise ValueError('read %d lies outside the pileup of %d columns' % (bad, self.n_cols))
         ptr, held = self._letters(ref, 0, self.n_cols)
         try:
-            self._ck(self.lib.pw_pileup_polish(self.handle, ptr, o.ctypes.data, ln.ctypes.data, len(o), min_depth, stream), 'pw_pileup_polish')
-            total = int(self.lib.pw_pileup_polished_total(self.handle))
-            letters, offsets = np.zeros(total, np.uint8), np.zeros(len(o) + 1, np.int64)
-            stats = np.zeros(len(o), POLISH_STATS_DTYPE)
+            self._ck(getattr(self.lib, entry)(self.handle, ptr, o.ctypes.data, ln.ctypes.data, len(o), min_depth, stream), entry)
+            offsets, stats = np.zeros(len(o) + 1, np.int64), np.zeros(len(o), POLISH_STATS_DTYPE)
             self._ck(self.lib.pw_pileup_polished_offsets(self.handle, offsets.ctypes.data), 'pw_pileup_polished_offsets')
-            self._ck(self.lib.pw_pileup_polished_letters(self.handle, letters.ctypes.data), 'pw_pileup_polished_letters')
+            if fetch:
+                letters = self.polished_letters()
             self._ck(self.lib.pw_pileup_polished_stats(self.handle, stats.ctypes.data), 'pw_pileup_polished_stats')
         finally:
             if held is not None:
                 held.close()
-        return letters, offsets, stats
+        return (offsets, stats, letters) if fetch else (offsets, stats)
+
+    def polished_letters(self):
+        """The letters of the last :meth:`polish`, all reads one after another (uint8)."""
+        total = int(self.lib.pw_pileup_polished_total(self.handle))
+        if total < 0:
+            raise RuntimeError('pw_pileup_polished_total failed: ' + W.last_error())
+        letters = np.zeros(total, np.uint8)
+        self._ck(self.lib.pw_pileup_polished_letters(self.handle, letters.ctypes.data), 'pw_pileup_polished_letters')
+        return letters
+
+    def colmap(self, lo=0, hi=None):
+        """Entries ``[lo, hi)`` of the coordinate map of the last :meth:`polish` with ``columns=True`` (``uint64``, ``n_cols + 1``
+        entries in all): ``colmap[c]`` is where the letters of column ``c`` begin among the polished letters."""
+        lo = int(lo)
+        hi = self.n_cols + 1 if hi is None else int(hi)
+        if not 0 <= lo <= hi <= self.n_cols + 1:
+            raise ValueError('entries [%d, %d) outside 0 .. %d' % (lo, hi, self.n_cols + 1))
+        out = np.zeros(hi - lo, np.uint64)
+        self._ck(self.lib.pw_pileup_colmap(self.handle, lo, hi, out.ctypes.data), 'pw_pileup_colmap')
+        return out
 
     def consensus(self, lo=0, hi=None):
         """The ``call`` bytes of the columns ``[lo, hi)``: a letter, ``alphabet_len`` for a deletion, 255 for no call."""

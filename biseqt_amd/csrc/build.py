@@ -4,7 +4,7 @@
 
 One object per (score type, diagonals-per-lane) fill translation unit plus the traceback unit and the
 host API, compiled in parallel, linked into one shared object that exports the four drop-in functions
-of include/pwlib.h, the batch API of include/pw_batch.h, the alignment summaries of include/pw_txsum.h, the CIGARs of include/pw_cigar.h, the pileups of include/pw_pileup.h, the read correction of include/pw_polish.h, the overlap graph of include/pw_graph.h, the consensus layout of include/pw_consensus.h, the seed APIs of include/pw_seeds.h, pw_mseeds.h, pw_qseeds.h and
+of include/pwlib.h, the batch API of include/pw_batch.h, the alignment summaries of include/pw_txsum.h, the CIGARs of include/pw_cigar.h, the pileups of include/pw_pileup.h, the read correction of include/pw_polish.h, the overlap graph of include/pw_graph.h, the consensus layout of include/pw_consensus.h, the consensus rounds of include/pw_rounds.h, the seed APIs of include/pw_seeds.h, pw_mseeds.h, pw_qseeds.h and
 pw_overlap.h, and the k-mer table of include/pw_kmers.h.  The header is copied next to the library
 (biseqt_amd/pwlib/pwlib.h) the way the reference keeps biseqt/pwlib/pwlib.{h,so} side by side.
 """
@@ -132,7 +132,7 @@ def _jobs():
                  [os.path.join(HERE, 'pw_pileup.hip'), os.path.join(ROOT, 'include', 'pw_pileup.h'), os.path.join(ROOT, 'include', 'pw_batch.h')]))
     obj = os.path.join(OBJ_DIR, 'pw_polish.o')
     jobs.append((obj, [HIPCC] + COMMON + ['-Wno-unused-parameter', '-c', os.path.join(HERE, 'pw_polish.hip'), '-o', obj],
-                 [os.path.join(HERE, 'pw_polish.hip'), os.path.join(ROOT, 'include', 'pw_polish.h'), os.path.join(ROOT, 'include', 'pw_pileup.h'),
+                 [os.path.join(HERE, 'pw_polish.hip'), os.path.join(HERE, 'pw_polish_column.h'), os.path.join(ROOT, 'include', 'pw_polish.h'), os.path.join(ROOT, 'include', 'pw_pileup.h'),
                   os.path.join(ROOT, 'include', 'pw_batch.h')]))
     obj = os.path.join(OBJ_DIR, 'pw_graph.o')
     jobs.append((obj, [HIPCC] + COMMON + ['-Wno-unused-parameter', '-c', os.path.join(HERE, 'pw_graph.hip'), '-o', obj],
@@ -144,9 +144,15 @@ def _jobs():
                   os.path.join(ROOT, 'include', 'pw_batch.h')]))
     obj = os.path.join(OBJ_DIR, 'pw_consensus.o')
     jobs.append((obj, [HIPCC] + COMMON + ['-Wno-unused-parameter', '-c', os.path.join(HERE, 'pw_consensus.hip'), '-o', obj],
-                 [os.path.join(HERE, 'pw_consensus.hip'), os.path.join(HERE, 'pw_consensus_launch.h'), os.path.join(HERE, 'pw_graph_launch.h'),
+                 [os.path.join(HERE, 'pw_consensus.hip'), os.path.join(HERE, 'pw_consensus_launch.h'), os.path.join(HERE, 'pw_cons_window.h'), os.path.join(HERE, 'pw_graph_launch.h'),
                   os.path.join(ROOT, 'include', 'pw_consensus.h'), os.path.join(ROOT, 'include', 'pw_graph.h'),
                   os.path.join(ROOT, 'include', 'pw_batch.h')]))
+    obj = os.path.join(OBJ_DIR, 'pw_rounds.o')
+    jobs.append((obj, [HIPCC] + COMMON + ['-Wno-unused-parameter', '-c', os.path.join(HERE, 'pw_rounds.hip'), '-o', obj],
+                 [os.path.join(HERE, 'pw_rounds.hip'), os.path.join(HERE, 'pw_rounds_launch.h'), os.path.join(HERE, 'pw_consensus_launch.h'),
+                  os.path.join(HERE, 'pw_graph_launch.h'), os.path.join(HERE, 'pw_polish_column.h'), os.path.join(HERE, 'pw_cons_window.h'),
+                  os.path.join(ROOT, 'include', 'pw_rounds.h'), os.path.join(ROOT, 'include', 'pw_consensus.h'),
+                  os.path.join(ROOT, 'include', 'pw_polish.h'), os.path.join(ROOT, 'include', 'pw_graph.h')]))
     obj = os.path.join(OBJ_DIR, 'pw_strip.o')
     # (PW_STRIP_CXXFLAGS: A/B builds of the strip kernel alone, e.g. -DPW_STRIP_LEAD=16)
     jobs.append((obj, [HIPCC] + COMMON + os.environ.get('PW_STRIP_CXXFLAGS', '').split() + ['-c', os.path.join(HERE, 'pw_strip.hip'), '-o', obj],
@@ -176,7 +182,8 @@ def _jobs():
                   os.path.join(ROOT, 'include', 'pw_cigar.h'), os.path.join(ROOT, 'include', 'pw_pileup.h'),
                   os.path.join(ROOT, 'include', 'pw_polish.h'), os.path.join(ROOT, 'include', 'pw_graph.h'),
                   os.path.join(HERE, 'pw_graph_launch.h'), os.path.join(HERE, 'pw_complement.h'),
-                  os.path.join(ROOT, 'include', 'pw_consensus.h'), os.path.join(HERE, 'pw_consensus_launch.h')]))
+                  os.path.join(ROOT, 'include', 'pw_consensus.h'), os.path.join(HERE, 'pw_consensus_launch.h'),
+                  os.path.join(ROOT, 'include', 'pw_rounds.h'), os.path.join(HERE, 'pw_rounds_launch.h')]))
     return jobs
 
 

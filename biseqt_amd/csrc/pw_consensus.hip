@@ -21,6 +21,7 @@
 
 #include "../../include/pw_consensus.h"
 #include "pw_consensus_launch.h"
+#include "pw_cons_window.h"
 
 static_assert(sizeof(pw_cons_place) == 24, "placement record must be 24 bytes");
 static_assert(sizeof(pw_cons_task) == 40, "task record must be 40 bytes");
@@ -37,18 +38,6 @@ namespace {
 __device__ __forceinline__ void co_compose(int rel_p, long long off_p, int lp, int lc, int& rel_c, long long& off_c) {
   if (rel_p == 0) { off_c = off_p + off_c; }
   else { off_c = off_p + (long long)lp - off_c - (long long)lc; rel_c ^= 1; }
-}
-
-// The window of a placed read of l letters on a contig of `length` letters; false: the read has no task.
-__device__ __forceinline__ bool co_window(const pw_cons_place& p, int l, long long length, int slack, double drift, long long& lo,
-                                          long long& hi, long long& radius) {
-  if (p.unitig < 0 || l <= 0) return false;
-  const long long pos = p.pos, end = pos + l;
-  if (!((pos > 0 ? pos : 0) < (end < length ? end : length))) return false;
-  radius = (long long)slack + (long long)((double)l * drift);
-  lo = pos - radius; lo = (lo > 0 ? lo : 0) & ~3ll;
-  hi = end + radius; hi = hi < length ? hi : length;
-  return true;
 }
 
 }  // namespace
@@ -277,6 +266,20 @@ hipError_t cons_place(const GraphState& g, ConsState& c, hipStream_t st) {
   return hipSuccess;
 }
 
+hipError_t cons_arena_contigs(ConsState& c, const uint8_t* cletters, const uint64_t* coff, int64_t n_unitigs, int64_t n_cols, hipStream_t st) {
+  if (n_cols <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_cons_arena_contigs, rows_grid((uint64_t)n_cols / 4), kBlock256, 0, st, cletters, (const unsigned long long*)coff,
+                     c.d_cstart.as<const unsigned long long>(), (long long)n_unitigs, (long long)n_cols, c.d_arena.p);
+  return hipGetLastError();
+}
+
+hipError_t cons_arena_mutants(const GraphState& g, ConsState& c, const uint8_t* letters, int64_t n_tasks, int64_t arena_bytes, hipStream_t st) {
+  if (n_tasks <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_cons_arena_mutants, dim3((unsigned)n_tasks), dim3(64), 0, st, c.d_tasks.cp(), letters, (const long long*)c.d_roff.cp(),
+                     g.d_lens.cp(), c.d_comp.cp(), (long long)arena_bytes, c.d_arena.p);
+  return hipGetLastError();
+}
+
 hipError_t cons_layout(const GraphState& g, ConsState& c, const uint8_t* letters, int32_t slack, double drift, bool* too_long,
                        hipStream_t st) {
   const int64_t R = g.n_reads, U = g.n_unitigs;
@@ -322,16 +325,8 @@ hipError_t cons_layout(const GraphState& g, ConsState& c, const uint8_t* letters
                        (int)R, (int)slack, drift, c.d_tasks.p);
     CO_TRY(hipGetLastError());
   }
-  if (n_cols) {
-    hipLaunchKernelGGL(k_cons_arena_contigs, rows_grid(n_cols / 4), kBlock256, 0, st, g.d_cletters.cp(), g.d_coff.as<const unsigned long long>(),
-                       c.d_cstart.as<const unsigned long long>(), (long long)U, (long long)n_cols, c.d_arena.p);
-    CO_TRY(hipGetLastError());
-  }
-  if (n_tasks) {
-    hipLaunchKernelGGL(k_cons_arena_mutants, dim3((unsigned)n_tasks), dim3(64), 0, st, c.d_tasks.cp(), letters, (const long long*)c.d_roff.cp(),
-                       g.d_lens.cp(), c.d_comp.cp(), (long long)arena_bytes, c.d_arena.p);
-    CO_TRY(hipGetLastError());
-  }
+  CO_TRY(cons_arena_contigs(c, g.d_cletters.cp(), g.d_coff.cp(), U, (int64_t)n_cols, st));
+  CO_TRY(cons_arena_mutants(g, c, letters, (int64_t)n_tasks, (int64_t)arena_bytes, st));
   CO_TRY(hipStreamSynchronize(st));
   c.n_tasks = (int64_t)n_tasks; c.n_cols = (int64_t)n_cols; c.arena_bytes = (int64_t)arena_bytes; c.has_layout = true;
   return hipSuccess;

@@ -48,6 +48,11 @@ hipError_t cons_place(const GraphState& g, ConsState& c, hipStream_t st);
 // more, and nothing was laid out.
 hipError_t cons_layout(const GraphState& g, ConsState& c, const uint8_t* letters, int32_t slack, double drift, bool* too_long,
                        hipStream_t st);
+// The two arena writers of cons_layout on their own (pw_rounds.hip lays the later rounds out with them): contig u of
+// coff[u + 1] - coff[u] letters from cletters[coff[u] ..] at c.d_cstart[u] with 255 behind it, and the mutant frames of
+// c.d_tasks from c.d_roff and c.d_comp.  c.d_arena is allocated and zeroed by the caller.
+hipError_t cons_arena_contigs(ConsState& c, const uint8_t* cletters, const uint64_t* coff, int64_t n_unitigs, int64_t n_cols, hipStream_t st);
+hipError_t cons_arena_mutants(const GraphState& g, ConsState& c, const uint8_t* letters, int64_t n_tasks, int64_t arena_bytes, hipStream_t st);
 int64_t cons_device_bytes(const ConsState& c);
 
 }  // namespace pw

@@ -27,6 +27,7 @@
 #include "../../include/pw_polish.h"
 #include "pw_hip_host.h"
 #include "pw_launch.h"
+#include "pw_polish_column.h"
 
 static_assert(sizeof(pw_polish_stats) == 16, "statistics record must be 16 bytes");
 
@@ -185,41 +186,6 @@ __global__ __launch_bounds__(256) void k_polish_letters(uint32_t* __restrict__ c
   const int y = (int)letters[c - lo];
   if (y < L) atomicAdd(counts + c * (L + 2) + y, weight);
 }
-
-namespace {
-
-// What one column emits (include/pw_polish.h, POLISHING): emit(letter) for each of its 0 .. 1 + J letters, in order;
-// returns the statistics of the column as kept | substituted << 8 | deleted << 16 | inserted << 24.
-template <typename Emit>
-__device__ __forceinline__ uint32_t po_column(const uint32_t* __restrict__ row, const uint32_t* __restrict__ irow, int s, int L, int J,
-                                              uint32_t min_depth, Emit&& emit) {
-  unsigned long long depth = 0;
-  uint32_t best = 0, call = 0;
-  for (int ch = 0; ch <= L; ch++) {                     // letters, then DEL; a tie stays with the lower channel
-    const uint32_t c = row[ch];
-    depth += c;
-    if (c > best) { best = c; call = (uint32_t)ch; }
-  }
-  if (depth < (unsigned long long)min_depth) { emit((uint8_t)s); return 1u; }
-  uint32_t st;
-  if (call == (uint32_t)L) st = 1u << 16;
-  else { emit((uint8_t)call); st = call == (uint32_t)s ? 1u : 1u << 8; }
-  for (int j = 0; j < J; j++) {
-    unsigned long long nj = 0;
-    uint32_t bj = 0, cj = 0;
-    for (int y = 0; y < L; y++) {
-      const uint32_t c = irow[j * L + y];
-      nj += c;
-      if (c > bj) { bj = c; cj = (uint32_t)y; }
-    }
-    if (!(2ull * nj > depth)) break;
-    emit((uint8_t)cj);
-    st += 1u << 24;
-  }
-  return st;
-}
-
-}  // namespace
 
 // One wavefront per read: lens[read] = the letters it emits, stats[read] its record.  (lens is uint64: the scan's input.)
 __global__ __launch_bounds__(64) void k_polish_count(const uint32_t* __restrict__ counts, const uint32_t* __restrict__ ins,

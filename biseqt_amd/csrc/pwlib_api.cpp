@@ -28,6 +28,7 @@
 #include "../../include/pw_polish.h"
 #include "../../include/pw_graph.h"
 #include "../../include/pw_consensus.h"
+#include "../../include/pw_rounds.h"
 #include "pw_launch.h"
 #include "pw_plan.h"
 #include "pw_model.h"
@@ -35,6 +36,7 @@
 #include "pw_complement.h"
 #include "pw_graph_launch.h"
 #include "pw_consensus_launch.h"
+#include "pw_rounds_launch.h"
 #define PW_FN inline
 #include "pw_strip.h"
 #include <atomic>
@@ -1200,6 +1202,8 @@ struct pw_pileup {
   DeviceArray<uint8_t> d_pletters;       // [polish_total]
   DeviceBuffer polish_tmp;               // rocPRIM's scratch
   std::vector<int64_t> h_roff; std::vector<int32_t> h_rlen;
+  pw::ColumnPolish col;                  // include/pw_rounds.h: the per-column arrays of pw_pileup_polish_columns
+  std::vector<pw::RoundBlock> h_blocks;
 };
 
 pw_pileup* pw_pileup_create(int device, int64_t n_cols, int alphabet_len) {
@@ -1379,7 +1383,7 @@ int pw_pileup_polish(pw_pileup* p, const uint8_t* letters_device, const int64_t*
   const hipStream_t st = (hipStream_t)stream;
   const size_t n = (size_t)n_reads;
   HIP_TRY(hipSetDevice(p->device));
-  p->polished = false;
+  p->polished = false; p->col.valid = false;
   p->h_roff.assign(read_offs, read_offs + n);                // (the caller's arrays are consumed here)
   p->h_rlen.assign(read_lens, read_lens + n);
   if (upload(fail, p->d_roff, p->h_roff.data(), n, st) != 0 || upload(fail, p->d_rlen, p->h_rlen.data(), n, st) != 0) return -1;
@@ -1439,10 +1443,72 @@ void* pw_pileup_polished_offsets_device(pw_pileup* p) {
   return p->d_poffs.p;
 }
 
+// ---- the column polish (include/pw_rounds.h; kernels and stage sequences in pw_rounds.hip) ----
+int pw_pileup_polish_columns(pw_pileup* p, const uint8_t* letters_device, const int64_t* read_offs, const int32_t* read_lens, int64_t n_reads,
+                             uint32_t min_depth, void* stream) {
+  if (!p) return fail("pw_pileup_polish_columns: null pileup");
+  if (n_reads < 0 || n_reads > INT32_MAX || (n_reads > 0 && (!read_offs || !read_lens))) return fail("pw_pileup_polish_columns: bad read arrays");
+  bool letters_needed = false;
+  int64_t n_blocks = 0;
+  for (int64_t r = 0; r < n_reads; r++) {
+    if (read_lens[r] < 0 || read_offs[r] < 0 || read_offs[r] > p->n_cols || read_lens[r] > p->n_cols - read_offs[r])
+      return fail("pw_pileup_polish_columns: read " + std::to_string(r) + " lies outside the pileup");
+    if (r > 0 && read_offs[r] < read_offs[r - 1])
+      return fail("pw_pileup_polish_columns: read " + std::to_string(r) + " is not in column order");
+    if (r > 0 && read_offs[r - 1] + read_lens[r - 1] > read_offs[r])
+      return fail("pw_pileup_polish_columns: read " + std::to_string(r) + " overlaps read " + std::to_string(r - 1));
+    letters_needed = letters_needed || read_lens[r] > 0;
+    n_blocks += ((int64_t)read_lens[r] + pw::kRoundChunk - 1) / pw::kRoundChunk;
+  }
+  if (letters_needed && !letters_device) return fail("pw_pileup_polish_columns: null letters");
+  if (n_blocks > INT32_MAX) return fail("pw_pileup_polish_columns: more than 2^31 chunks of columns");
+  const hipStream_t st = (hipStream_t)stream;
+  const size_t n = (size_t)n_reads;
+  HIP_TRY(hipSetDevice(p->device));
+  p->polished = false; p->col.valid = false;
+  p->h_roff.assign(read_offs, read_offs + n);                // (the caller's arrays are consumed here)
+  p->h_rlen.assign(read_lens, read_lens + n);
+  p->h_blocks.clear();
+  p->h_blocks.reserve((size_t)n_blocks);
+  for (int64_t r = 0; r < n_reads; r++)                      // one workgroup per 256 columns of a read: no kernel searches for its read
+    for (int32_t k = 0; (int64_t)k * pw::kRoundChunk < read_lens[r]; k++) p->h_blocks.push_back({(int32_t)r, k});
+  if (upload(fail, p->d_roff, p->h_roff.data(), n, st) != 0 || upload(fail, p->d_rlen, p->h_rlen.data(), n, st) != 0 ||
+      upload(fail, p->col.d_blocks, p->h_blocks.data(), (size_t)n_blocks, st) != 0)
+    return -1;
+  HIP_TRY(p->d_poffs.ensure(n + 1));
+  HIP_TRY(p->d_pstats.ensure(n));
+  const uint32_t* ins = p->J ? p->d_ins.p : nullptr;
+  HIP_TRY(pw::round_polish_count(p->col, p->d_counts.p, ins, letters_device, p->d_roff.p, p->d_rlen.p, n_blocks, n_reads, p->n_cols, p->L, p->J,
+                                 min_depth, p->d_poffs.p, p->d_pstats.p, p->polish_tmp, st));
+  uint64_t total = 0;                                        // the output is allocated from the counted total
+  HIP_TRY(hipMemcpyAsync(&total, p->col.d_colmap.p + p->n_cols, 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  HIP_TRY(p->d_pletters.ensure((size_t)total));
+  HIP_TRY(pw::round_polish_write(p->col, p->d_roff.p, p->d_rlen.p, n_blocks, total, p->d_pletters.p, st));
+  HIP_TRY(hipStreamSynchronize(st));                         // (the call is synchronous: it has waited for the total already)
+  p->polish_reads = n_reads; p->polish_total = (int64_t)total; p->polished = true; p->col.valid = true;
+  return 0;
+}
+void* pw_pileup_colmap_device(pw_pileup* p) {
+  if (!p || !p->polished || !p->col.valid) { fail("pw_pileup_colmap_device before pw_pileup_polish_columns"); return nullptr; }
+  return p->col.d_colmap.p;
+}
+int pw_pileup_colmap(pw_pileup* p, int64_t lo, int64_t hi, uint64_t* host_out) {
+  if (!p) return fail("pw_pileup_colmap: null pileup");
+  if (!p->polished || !p->col.valid) return fail("pw_pileup_colmap before pw_pileup_polish_columns");
+  if (lo < 0 || hi < lo || hi > p->n_cols + 1) return fail("pw_pileup_colmap: entries outside 0 .. n_cols + 1");
+  if (hi == lo) return 0;
+  if (!host_out) return fail("pw_pileup_colmap: null output");
+  HIP_TRY(hipSetDevice(p->device));
+  HIP_TRY(hipMemcpy(host_out, p->col.d_colmap.p + lo, p->col.d_colmap.bytes((size_t)(hi - lo)), hipMemcpyDeviceToHost));
+  return 0;
+}
+
 // ---- the overlap graph (include/pw_graph.h; kernels and stage sequences in pw_graph.hip) ----
 struct pw_graph {
   pw::GraphState s;
   pw::ConsState c;                       // the consensus stage (include/pw_consensus.h; pw_consensus.hip)
+  pw::RoundState r;                      // its later rounds (include/pw_rounds.h; pw_rounds.hip)
   std::vector<int32_t> lens;             // [n_reads]
   std::unordered_set<uint64_t> keys;     // (a * n_reads + b) * 2 + strand of every record
   std::string duplicate;                 // the first duplicate key, in words; pw_graph_build reports it
@@ -1487,7 +1553,7 @@ void pw_graph_free(pw_graph* g) {
   delete g;
 }
 int64_t pw_graph_num_overlaps(const pw_graph* g) { return g ? g->s.n_recs : 0; }
-int64_t pw_graph_device_bytes(const pw_graph* g) { return g ? pw::graph_device_bytes(g->s) + pw::cons_device_bytes(g->c) : 0; }
+int64_t pw_graph_device_bytes(const pw_graph* g) { return g ? pw::graph_device_bytes(g->s) + pw::cons_device_bytes(g->c) + pw::round_device_bytes(g->r) : 0; }
 
 int pw_graph_add_overlaps(pw_graph* g, const pw_graph_overlap* recs, int64_t n) {
   if (!g) return fail("pw_graph_add_overlaps: null graph");
@@ -1700,6 +1766,7 @@ int pw_graph_consensus_layout(pw_graph* g, const uint8_t* letters_device, const 
   bool too_long = false;
   HIP_TRY(pw::cons_layout(g->s, g->c, letters_device, slack, drift, &too_long, st));
   if (too_long) return fail("pw_graph_consensus_layout: a contig has 2^31 letters or more");
+  g->r.round = 1; g->r.have = false;                         // (include/pw_rounds.h: a layout is round 1)
   return 0;
 }
 int64_t pw_graph_cons_num_tasks(pw_graph* g) {
@@ -1737,6 +1804,61 @@ void* pw_graph_cons_tasks_device(pw_graph* g) {
 void* pw_graph_cons_arena_device(pw_graph* g) {
   if (!g || !g->s.built || !g->c.has_layout) { fail("pw_graph_cons_arena_device before pw_graph_consensus_layout"); return nullptr; }
   return g->c.d_arena.p;
+}
+
+// ---- the later rounds of the consensus (include/pw_rounds.h; kernels and stage sequences in pw_rounds.hip) ----
+int pw_graph_consensus_relayout(pw_graph* g, const uint8_t* polished_device, const uint64_t* polished_offsets_device,
+                                const uint64_t* colmap_device, const uint8_t* letters_device, const int64_t* read_offs,
+                                const uint8_t* complement, int complement_len, int32_t slack, double drift, void* stream) {
+  if (!g) return fail("pw_graph_consensus_relayout: null graph");
+  if (!g->s.built || !g->c.has_layout) return fail("pw_graph_consensus_relayout before pw_graph_consensus_layout");
+  if (slack < 0) return fail("pw_graph_consensus_relayout: slack must not be negative");
+  if (!std::isfinite(drift) || drift < 0 || drift > 1048576.) return fail("pw_graph_consensus_relayout: drift must be finite and lie in 0 .. 2^20");
+  if (complement && (complement_len < 1 || complement_len > 256)) return fail("pw_graph_consensus_relayout: complement_len must be 1..256");
+  if (!polished_offsets_device || !colmap_device) return fail("pw_graph_consensus_relayout: null offsets or colmap");
+  if (g->c.n_cols > 0 && !polished_device) return fail("pw_graph_consensus_relayout: null polished letters");
+  const int64_t R = g->s.n_reads;
+  if (R > 0 && !read_offs) return fail("pw_graph_consensus_relayout: null read offsets");
+  for (int64_t r = 0; r < R; r++)
+    if (read_offs[r] < 0) return fail("pw_graph_consensus_relayout: read " + std::to_string(r) + " has a negative offset");
+  bool any = false;                                          // a read of at least one letter: the frames are read from the letters
+  for (int64_t r = 0; r < R && !any; r++) any = g->lens[r] > 0;
+  if (any && !letters_device) return fail("pw_graph_consensus_relayout: null letters");
+  const hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(hipSetDevice(g->s.device));
+  uint8_t table[256];
+  for (int c = 0; c < 256; c++) table[c] = complement && c < complement_len ? complement[c] : (uint8_t)c;
+  g->h_roff.assign(read_offs, read_offs + R);                // (the caller's array is consumed here)
+  if (upload(fail, g->c.d_roff, g->h_roff.data(), (size_t)R, st) != 0) return -1;
+  HIP_TRY(g->c.d_comp.ensure(256));
+  HIP_TRY(hipMemcpy(g->c.d_comp.p, table, 256, hipMemcpyHostToDevice));
+  int refused = 0;
+  HIP_TRY(pw::round_relayout(g->s, g->c, g->r, polished_device, polished_offsets_device, colmap_device, letters_device, slack, drift, &refused,
+                             st));
+  if (refused == 1) return fail("pw_graph_consensus_relayout: a contig has 2^31 letters or more");
+  if (refused) return fail("pw_graph_consensus_relayout: the polished offsets disagree with colmap about a contig's length");
+  return 0;
+}
+int pw_graph_cons_round(pw_graph* g) {
+  return g && g->s.built && g->c.has_layout ? g->r.round : fail("pw_graph_cons_round before pw_graph_consensus_layout");
+}
+int pw_graph_cons_positions(pw_graph* g, int64_t* out) {
+  if (!g || !g->s.built || !g->c.has_layout) return fail("pw_graph_cons_positions before pw_graph_consensus_layout");
+  if (g->s.n_reads == 0) return 0;
+  if (!out) return fail("pw_graph_cons_positions: null output");
+  HIP_TRY(hipSetDevice(g->s.device));
+  if (!g->r.have) HIP_TRY(pw::round_init(g->s, g->c, g->r, nullptr));
+  HIP_TRY(hipMemcpy(out, g->r.d_pos.p, g->r.d_pos.bytes((size_t)g->s.n_reads), hipMemcpyDeviceToHost));
+  return 0;
+}
+int pw_graph_cons_lengths(pw_graph* g, int64_t* out) {
+  if (!g || !g->s.built || !g->c.has_layout) return fail("pw_graph_cons_lengths before pw_graph_consensus_layout");
+  if (g->s.n_unitigs == 0) return 0;
+  if (!out) return fail("pw_graph_cons_lengths: null output");
+  HIP_TRY(hipSetDevice(g->s.device));
+  if (!g->r.have) HIP_TRY(pw::round_init(g->s, g->c, g->r, nullptr));
+  HIP_TRY(hipMemcpy(out, g->r.d_len[g->r.cur].p, g->r.d_len[0].bytes((size_t)g->s.n_unitigs), hipMemcpyDeviceToHost));
+  return 0;
 }
 
 int pw_batch_scores(pw_batch* b, int32_t k, double* out, int64_t n) {

@@ -1,7 +1,8 @@
 """The overlap graph on the device (include/pw_graph.h holds the contract): overlap records, their containment / dovetail
 classes, arcs, transitive reduction, unitigs and contig letters -- and the consensus stage on top of it
 (include/pw_consensus.h): where every read lies on its contig, the read-against-contig alignment tasks and the polished
-contigs.  Every computing call goes to the kernels of ``pw_graph.hip`` and ``pw_consensus.hip``; there is no host fallback."""
+contigs.  Every computing call goes to the kernels of ``pw_graph.hip``, ``pw_consensus.hip`` and ``pw_rounds.hip`` (the later rounds of
+the consensus, include/pw_rounds.h); there is no host fallback."""
 import ctypes as C
 
 import numpy as np
@@ -227,6 +228,9 @@ class OverlapGraph(object):
         finally:
             if held is not None:
                 held.close()
+        return self._layout_results(n_unitigs, comp)
+
+    def _layout_results(self, n_unitigs, comp):
         cstart = self._fetch('pw_graph_cons_cstart', n_unitigs + 1, np.int64)
         tasks = self._fetch('pw_graph_cons_tasks', self._count('pw_graph_cons_num_tasks'), TASK_DTYPE)
         if comp is None and len(tasks) and tasks['rev'].any():
@@ -235,8 +239,104 @@ class OverlapGraph(object):
                                   owner=self)
         return cstart, tasks, arena
 
+    # ---- the later rounds of the consensus (include/pw_rounds.h) ----
+    def consensus_relayout(self, polished, offsets, colmap, reads, complement=None, slack=50, drift=.1, stream=None):
+        """``(cstart, tasks, arena)`` of the NEXT round (``pw_graph_consensus_relayout``; synchronous), like
+        :meth:`consensus_layout`: ``polished`` are the polished contig letters one after another, ``offsets`` their
+        ``n_unitigs + 1`` offsets and ``colmap`` the ``n_cols + 1`` entries of :meth:`biseqt_amd.batch.Pileup.colmap` over the
+        current layout -- each a host array, or a device pointer (an ``int``, as the pileup's ``*_device`` accessors give
+        it).  The placements are remapped through ``colmap`` and the tasks and the arena are laid out from the polished
+        letters; :meth:`positions` and :meth:`lengths` then return the new round's values."""
+        n_unitigs = self._count('pw_graph_num_unitigs')     # (raises before the first build)
+        if not 0 <= int(slack) < 1 << 31:
+            raise ValueError('slack must lie in 0 .. 2**31 - 1')
+        if not (np.isfinite(drift) and 0 <= drift <= 1 << 20):
+            raise ValueError('drift must be finite and lie in 0 .. 2**20')
+        comp = None if complement is None else np.ascontiguousarray(complement, np.uint8).reshape(-1)
+        if comp is not None and not 1 <= len(comp) <= 256:
+            raise ValueError('complement must hold 1 .. 256 letters')
+        held = []
+
+        def dev(x, dtype):
+            if isinstance(x, (int, np.integer)):
+                return int(x)
+            host = np.ascontiguousarray(x, dtype).reshape(-1)
+            held.append(DeviceArena(host.view(np.uint8) if len(host) else np.zeros(8, np.uint8), self.device))
+            return held[-1].ptr
+        try:
+            ptrs = dev(polished, np.uint8), dev(offsets, np.uint64), dev(colmap, np.uint64)
+            src, offs, own = self._device_reads(reads)
+            if own is not None:
+                held.append(own)
+            self._ck(self.lib.pw_graph_consensus_relayout(self.handle, ptrs[0], ptrs[1], ptrs[2], src.ptr, offs.ctypes.data,
+                                                          None if comp is None else comp.ctypes.data, 0 if comp is None else len(comp),
+                                                          int(slack), float(drift), stream), 'pw_graph_consensus_relayout')
+        finally:
+            for h in held:
+                h.close()
+        return self._layout_results(n_unitigs, comp)
+
+    def round(self):
+        """The round of the current layout: 1 after :meth:`consensus_layout`, one more per :meth:`consensus_relayout`."""
+        n = int(self.lib.pw_graph_cons_round(self.handle))
+        if n < 0:
+            raise RuntimeError('pw_graph_cons_round failed: ' + W.last_error())
+        return n
+
+    def positions(self):
+        """``int64[n_reads]``: where every read begins on its contig in the current round (0 for an unplaced read)."""
+        return self._fetch('pw_graph_cons_positions', self.n_reads, np.int64)
+
+    def lengths(self):
+        """``int64[n_unitigs]``: the contig lengths of the current round."""
+        return self._fetch('pw_graph_cons_lengths', self._count('pw_graph_num_unitigs'), np.int64)
+
+    def _pile_tasks(self, pile, tasks, arena, alphabet_len, self_weight, max_cells, aligner_kw):
+        """The self vote of the arena's columns and the alignments of ``tasks`` piled onto ``pile``, in batches of at most
+        ``max_cells`` cells, the next batch planned while one runs.  Returns the number of tasks that aligned."""
+        T, aligned = len(tasks), 0
+        # frames: the windows, then the mutants
+        offs = np.concatenate([tasks['col0'], tasks['mut_off']]).astype(np.int64)
+        lens = np.concatenate([tasks['win_len'], self.read_lens[tasks['read']]]).astype(np.int64)
+        pidx = np.stack([np.arange(T), T + np.arange(T)], 1).astype(np.int64)
+        dr = np.stack([tasks['dmin'], tasks['dmax']], 1).astype(np.int64)
+        cells = (dr[:, 1] - dr[:, 0] + 1) * np.minimum(lens[:T], lens[T:])
+        csum, bounds, start = np.cumsum(cells), [], 0
+        while start < T:
+            base = csum[start - 1] if start else 0
+            stop = max(start + 1, int(np.searchsorted(csum, base + max_cells, 'right')))
+            bounds.append((start, stop)); start = stop
+        kw = dict(match_score=1, mismatch_score=-3, go_score=-5, ge_score=-2)
+        kw.update(aligner_kw)
+        nothing = np.zeros(0, np.uint8)
+
+        def create(lo, hi):
+            return BatchAligner.from_arena(nothing, offs, lens, pidx[lo:hi], dr[lo:hi], device_arena=arena, alnmode=W.BANDED_MODE,
+                                           alntype=W.B_OVERLAP, alphabet_len=alphabet_len, device=self.device,
+                                           arena_bytes=arena.nbytes, **kw)
+
+        pile.add_letters((arena, 0), weight=self_weight)
+        cur = nxt = None
+        try:
+            nxt = create(*bounds[0]) if bounds else None
+            for q, (lo, hi) in enumerate(bounds):
+                cur, nxt = nxt, None
+                cur.solve(); cur.traceback()               # asynchronous: the device is busy from here ...
+                if q + 1 < len(bounds):
+                    nxt = create(*bounds[q + 1])           # ... while the next batch is planned
+                cur.pileup_add(pile, col0=tasks['col0'][lo:hi], sides='origin')
+                cur.sync()
+                aligned += int((cur.results()['opt_i'] >= 0).sum())
+                cur.close(); cur = None
+        finally:
+            for b in (cur, nxt):
+                if b is not None:
+                    b.close()
+        arena.read(0, 1)                                   # (a synchronous copy behind the last add)
+        return aligned
+
     def consensus(self, reads, alphabet_len, complement=None, slack=50, drift=.1, min_depth=3, ins_slots=2, self_weight=1,
-                  max_cells=2 * 10 ** 10, stats=None, **aligner_kw):
+                  max_cells=2 * 10 ** 10, stats=None, rounds=1, **aligner_kw):
         """The polished contigs of the last build (include/pw_consensus.h): every read is placed on its contig, aligned
         (banded ``B_OVERLAP``, scores 1 / -3 / -5 / -2 unless ``aligner_kw`` says otherwise) against a window of the draft
         around its place -- ``slack + drift * len`` letters wider on either side, the band as wide around the nominal diagonal
@@ -246,63 +346,59 @@ class OverlapGraph(object):
         starts come to the host on the way: no draft letter and no transcript.  ``reads`` and ``complement`` as for
         :meth:`contigs`.  Returns ``(contigs, records)``: uint8 arrays in unitig order and one ``batch.POLISH_STATS_DTYPE``
         record per contig.  ``stats`` (a dict) receives ``placed``, ``unplaced``, ``tasks``, ``aligned`` and the times of the
-        stages in ms, taken on the host around synchronised device work: ``layout_ms``, ``align_ms``, ``polish_ms``."""
+        stages in ms, taken on the host around synchronised device work: ``layout_ms``, ``align_ms``, ``polish_ms``.
+
+        ``rounds`` >= 2 (include/pw_rounds.h) iterates: the pileup is polished by columns, the placements are remapped
+        through the coordinate map of that polish and the next round's tasks and arena are laid out from the polished letters
+        where they are (:meth:`consensus_relayout`, from the pileup's device arrays), at most ``rounds`` times; a round whose
+        records show no substitution, deletion or insertion on any contig has emitted its own input, and the loop stops
+        there.  Between the rounds only offsets, records, tasks and contig starts come to the host.  The result is the last
+        round's.  ``stats['rounds']`` lists, per round that ran, ``tasks``, ``aligned``, ``records``, ``layout_ms``,
+        ``align_ms``, ``polish_ms``; ``tasks`` and ``aligned`` of ``stats`` itself are the last round's, the times are sums."""
         import time
         from .batch import POLISH_STATS_DTYPE, Pileup
+        rounds = int(rounds)
+        if rounds < 1:
+            raise ValueError('rounds must be at least 1')
         t0 = time.perf_counter()
         cstart, tasks, arena = self.consensus_layout(reads, complement=complement, slack=slack, drift=drift)
-        n_cols, T = int(cstart[-1]), len(tasks)
         lengths = self.unitigs()[0]['length'].astype(np.int64)
         t1 = time.perf_counter()
-        aligned = 0
-        if n_cols == 0:
-            out, offsets, records = np.zeros(0, np.uint8), np.zeros(len(lengths) + 1, np.int64), np.zeros(len(lengths), POLISH_STATS_DTYPE)
-            t2 = t3 = t1
-        else:
-            # frames: the windows, then the mutants
-            offs = np.concatenate([tasks['col0'], tasks['mut_off']]).astype(np.int64)
-            lens = np.concatenate([tasks['win_len'], self.read_lens[tasks['read']]]).astype(np.int64)
-            pidx = np.stack([np.arange(T), T + np.arange(T)], 1).astype(np.int64)
-            dr = np.stack([tasks['dmin'], tasks['dmax']], 1).astype(np.int64)
-            cells = (dr[:, 1] - dr[:, 0] + 1) * np.minimum(lens[:T], lens[T:])
-            csum, bounds, start = np.cumsum(cells), [], 0
-            while start < T:
-                base = csum[start - 1] if start else 0
-                stop = max(start + 1, int(np.searchsorted(csum, base + max_cells, 'right')))
-                bounds.append((start, stop)); start = stop
-            kw = dict(match_score=1, mismatch_score=-3, go_score=-5, ge_score=-2)
-            kw.update(aligner_kw)
-            nothing = np.zeros(0, np.uint8)
-
-            def create(lo, hi):
-                return BatchAligner.from_arena(nothing, offs, lens, pidx[lo:hi], dr[lo:hi], device_arena=arena, alnmode=W.BANDED_MODE,
-                                               alntype=W.B_OVERLAP, alphabet_len=alphabet_len, device=self.device,
-                                               arena_bytes=arena.nbytes, **kw)
-
-            with Pileup(n_cols, alphabet_len, device=self.device, ins_slots=ins_slots) as pile:
-                pile.add_letters((arena, 0), weight=self_weight)
-                cur = nxt = None
-                try:
-                    nxt = create(*bounds[0]) if bounds else None
-                    for q, (lo, hi) in enumerate(bounds):
-                        cur, nxt = nxt, None
-                        cur.solve(); cur.traceback()               # asynchronous: the device is busy from here ...
-                        if q + 1 < len(bounds):
-                            nxt = create(*bounds[q + 1])           # ... while the next batch is planned
-                        cur.pileup_add(pile, col0=tasks['col0'][lo:hi], sides='origin')
-                        cur.sync()
-                        aligned += int((cur.results()['opt_i'] >= 0).sum())
-                        cur.close(); cur = None
-                finally:
-                    for b in (cur, nxt):
-                        if b is not None:
-                            b.close()
-                arena.read(0, 1)                                   # (a synchronous copy behind the last add)
-                t2 = time.perf_counter()
-                out, offsets, records = pile.polish((arena, 0), cstart[:-1], lengths, min_depth=min_depth)
-                t3 = time.perf_counter()
+        per_round = []
+        for k in range(1, rounds + 1):
+            n_cols, T = int(cstart[-1]), len(tasks)
+            aligned, nxt = 0, None
+            if n_cols == 0:
+                out, offsets, records = np.zeros(0, np.uint8), np.zeros(len(lengths) + 1, np.int64), np.zeros(len(lengths), POLISH_STATS_DTYPE)
+                t2 = t3 = t4 = t1
+                last = True
+            else:
+                with Pileup(n_cols, alphabet_len, device=self.device, ins_slots=ins_slots) as pile:
+                    aligned = self._pile_tasks(pile, tasks, arena, alphabet_len, self_weight, max_cells, aligner_kw)
+                    t2 = time.perf_counter()
+                    if rounds == 1:
+                        out, offsets, records = pile.polish((arena, 0), cstart[:-1], lengths, min_depth=min_depth)
+                    else:
+                        offsets, records = pile._polish((arena, 0), cstart[:-1], lengths, min_depth, None, True, False)
+                    t3 = t4 = time.perf_counter()
+                    last = k == rounds or not (records['substituted'].any() or records['deleted'].any() or records['inserted'].any())
+                    if last and rounds > 1:
+                        out = pile.polished_letters()
+                    elif not last:                             # (before the pileup closes: its arrays are the relayout's input)
+                        nxt = self.consensus_relayout(int(self.lib.pw_pileup_polished_letters_device(pile.handle)),
+                                                      int(self.lib.pw_pileup_polished_offsets_device(pile.handle)),
+                                                      int(self.lib.pw_pileup_colmap_device(pile.handle)), reads, complement=complement,
+                                                      slack=slack, drift=drift)
+                        t4 = time.perf_counter()
+            per_round.append(dict(tasks=T, aligned=aligned, records=records, layout_ms=1e3 * (t1 - t0), align_ms=1e3 * (t2 - t1),
+                                  polish_ms=1e3 * (t3 - t2)))
+            if last:
+                break
+            (cstart, tasks, arena), lengths = nxt, np.diff(offsets).astype(np.int64)
+            t0, t1 = t3, t4
         if stats is not None:
             place = self._fetch('pw_graph_placements', self.n_reads, PLACE_DTYPE)
-            stats.update(placed=int((place['unitig'] >= 0).sum()), unplaced=int((place['unitig'] < 0).sum()), tasks=T, aligned=aligned,
-                         layout_ms=1e3 * (t1 - t0), align_ms=1e3 * (t2 - t1), polish_ms=1e3 * (t3 - t2))
+            stats.update(placed=int((place['unitig'] >= 0).sum()), unplaced=int((place['unitig'] < 0).sum()), tasks=per_round[-1]['tasks'],
+                         aligned=per_round[-1]['aligned'], rounds=per_round,
+                         **{key: sum(r[key] for r in per_round) for key in ('layout_ms', 'align_ms', 'polish_ms')})
         return [out[offsets[u]:offsets[u + 1]].copy() for u in range(len(lengths))], records

@@ -555,7 +555,7 @@ def correct_reads(reads, wordlen, alphabet, g_max, sensitivity, p_min=.8, strand
 def assemble_reads(reads, wordlen, alphabet, g_max, sensitivity, p_min=.8, strands='+', complement=None, minimizer_window=None,
                    max_kmer_occ=None, stats=None, max_hang=1000, int_frac=.8, min_overlap=0, min_identity=0., fuzz=10, device=0,
                    consensus=False, slack=50, drift=.1, min_depth=3, ins_slots=2, self_weight=1, max_tip_reads=0, max_bubble_reads=0,
-                   clean_rounds=1, **aligner_kw):
+                   clean_rounds=1, consensus_rounds=1, **aligner_kw):
     """From reads to contigs in one call (include/pw_graph.h): :func:`overlap_all_pairs` (``strands``, ``complement``,
     ``minimizer_window``, ``max_kmer_occ`` are its arguments), :func:`overlap_alignments` of the pairs it found whose band has
     ``p >= p_min`` into an :class:`biseqt_amd.graph.OverlapGraph` (no transcript leaves the device), its ``build`` with
@@ -576,7 +576,9 @@ def assemble_reads(reads, wordlen, alphabet, g_max, sensitivity, p_min=.8, stran
     same ``aligner_kw``: every read, the contained ones included, is placed on its contig, realigned against the draft and
     piled onto it.  ``stats`` then gains ``draft`` (the unpolished letters, what the call returns without ``consensus``),
     ``placements`` (``graph.PLACE_DTYPE``), ``consensus_records`` (one ``batch.POLISH_STATS_DTYPE`` record per contig),
-    ``consensus_stats`` (``placed``, ``unplaced``, ``tasks``, ``aligned``) and ``layout_ms``, ``consensus_align_ms``, ``polish_ms``."""
+    ``consensus_stats`` (``placed``, ``unplaced``, ``tasks``, ``aligned``) and ``layout_ms``, ``consensus_align_ms``, ``polish_ms``.
+    ``consensus_rounds`` is the consensus's ``rounds`` (include/pw_rounds.h: the polished contigs are laid out, realigned and
+    polished again, until a round changes nothing); ``stats['consensus_rounds']`` holds its per-round list."""
     import time
     from .graph import ARC_REMOVED, OverlapGraph
     assert isinstance(alphabet, Alphabet)
@@ -604,11 +606,12 @@ def assemble_reads(reads, wordlen, alphabet, g_max, sensitivity, p_min=.8, stran
             cstats = {}
             draft = contigs
             contigs, crecords = G.consensus(reads, len(alphabet), complement=comp, slack=slack, drift=drift, min_depth=min_depth,
-                                            ins_slots=ins_slots, self_weight=self_weight, stats=cstats, **aligner_kw)
+                                            ins_slots=ins_slots, self_weight=self_weight, stats=cstats, rounds=consensus_rounds, **aligner_kw)
             if stats is not None:
                 stats.update(draft=draft, placements=G.placements(), consensus_records=crecords,
                              consensus_stats={k: cstats[k] for k in ('placed', 'unplaced', 'tasks', 'aligned')},
-                             layout_ms=cstats['layout_ms'], consensus_align_ms=cstats['align_ms'], polish_ms=cstats['polish_ms'])
+                             layout_ms=cstats['layout_ms'], consensus_align_ms=cstats['align_ms'], polish_ms=cstats['polish_ms'],
+                             consensus_rounds=cstats['rounds'])
         if stats is not None:
             arcs, _ = G.arcs()
             gone = G.dropped()
